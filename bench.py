@@ -5,13 +5,22 @@ Default workload = BASELINE.json configs[1]: Flux-Dev 1024x1024.  A "step" = one
 FluxTransformer2DModel forward (19 double + 38 single MM-DiT blocks, S_img 4096 + S_txt 512, 24x128
 heads, bf16, B=1, no CFG) + one FlowMatch-Euler scheduler.step on synthetic latents / prompt embeddings
 and random-init weights of the FLUX.1-dev architecture (no network for checkpoints).  Inputs are resident
-in HBM before the timed region.  After the timed steps one whole clip (28 steps + 2-D VAE decode to
-1024x1024, bf16) is timed as `sec_per_clip`.  The K timed steps are ONE clip: its per-clip set-up (the modulation table of its K
+in HBM before the timed region.  The K timed steps are ONE clip: its per-clip set-up (the modulation table of its K
 steps, after the hand-over from the warm-up clip) runs inside the timed region; the warm-up clip is scheduled equally long and has
 itself been handed over once, so that set-up pays no first-use cost.  APEX_BENCH_STEP_TIMES=1 prints the set-up's and every timed
 step's GPU time to stderr (diagnostics: two events per step inside the timed region).
 
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the result line.  Everything
+else the benchmark measures or checks runs only with --full, after the timed region: the host-enqueue burst, the per-kernel
+roofline and clock passes, one whole clip (28 steps + 2-D VAE decode to 1024x1024, bf16) timed as `sec_per_clip`, the CPU
+baseline, the Wan-2.2 half of the default line and, for N > 1, the shared-weight exchange.
+
+--dump-outputs DIR writes what the timed path returned from its last timed step (rank 0: the latents after the scheduler step)
+to DIR/latents.npy as float32 — at most 19 MB (Wan 720p).  Weights and inputs are seeded, so the same arguments give the same
+inputs in every run and two builds can be compared output for output.
+
   python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -34,7 +43,7 @@ same token ids and the outputs are compared bit for bit ("verified" in the JSON)
 Started WITHOUT torchrun, `bench.py --gpus N` (N > 1) re-executes itself under torch.distributed.run with N ranks and
 refuses to run when fewer than N GPUs are visible: an N-GPU number only ever comes from N processes.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries two extra objects among others:
   roofline     achieved TFLOP/s of the dominant kernel (gemm_bf16_kernel) = algorithmic 2MNK flops of its
                launches / their summed HIP-event durations, measured live over extra profiled steps
   cpu_baseline the CPU oracle (fp32 PyTorch restatement of the reference path) timed on this box's host
@@ -75,12 +84,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", choices=["flux", "flux512", "qwen", "wan", "hunyuan", "queue"], default="flux")
     ap.add_argument("--layers", type=str, default="", help="debug: 'D,S' block counts (invalid as a result)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beyond the headline figure (host-enqueue burst, roofline, "
+                         "clip, CPU baseline, the Wan half, the N > 1 weight exchange); the --no-* options below select among those")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's output (rank 0) to DIR/latents.npy as float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-clip", action="store_true", help="skip the whole-clip (28 steps + decode) timing")
     ap.add_argument("--no-mod-table", action="store_true",
                     help="A/B: per-step AdaLN GEMVs instead of the per-clip modulation table (flux, qwen)")
-    ap.add_argument("--clip", action="store_true", help="wan: also time a whole 30-step clip + decode")
+    ap.add_argument("--clip", action="store_true",
+                    help="also time a whole clip + decode (wan: 30 steps; flux, flux512: on with --full)")
     ap.add_argument("--fp8", action="store_true",
                     help="wan: block Linear weights RESIDENT as float8_e4m3fn + per-tensor scale_weight (the layout the Wan-2.2 manifest's "
                          "default files ship, R/manifest/video/wan-2.2-a14b-text-to-video-1.0.0.v1.yml:108-116), dequantised per call")
@@ -718,6 +733,14 @@ def run_queue(args, dev, rank, world):
             "broadcast": bcast}), flush=True)
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as path/<name>.npy in float32 (exact for the bf16 / f32 latents)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def _flush_c_stdio():
     try:
         import ctypes
@@ -794,6 +817,8 @@ def shared_weights(workload, dev, rank):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.workload == "queue":
+        raise SystemExit("bench.py --dump-outputs: the queue workload has no timed step whose output could be written")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
     rank = int(os.environ.get("RANK", "0"))
@@ -879,21 +904,32 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     finite = bool(torch.isfinite(latents.float()).all().item())
-    # The Python + ctypes launch path, priced: OUTSIDE the timed region, from an idle queue, a burst of steps
-    # short enough never to meet HIP's queue-depth back-pressure (~2000 launches in flight: the timed loop's own enqueue time
-    # is mostly that wait once the host is a few steps ahead) is enqueued with no sync inside; its wall time is host work only.
-    nburst = max(1, min(3, args.steps))
-    reset(total)
-    begin(0, nburst)
-    lat_b = latents
-    torch.cuda.synchronize()
-    tb = time.perf_counter()
-    for i in range(nburst):
-        lat_b = step(i, lat_b)
-    host_burst = (time.perf_counter() - tb) / nburst
-    torch.cuda.synchronize()
-    burst_total = (time.perf_counter() - tb) / nburst
-    del lat_b
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"latents": latents})
+    host = {}
+    if args.full:
+        # The Python + ctypes launch path, priced: OUTSIDE the timed region, from an idle queue, a burst of steps
+        # short enough never to meet HIP's queue-depth back-pressure (~2000 launches in flight: the timed loop's own enqueue time
+        # is mostly that wait once the host is a few steps ahead) is enqueued with no sync inside; its wall time is host work only.
+        nburst = max(1, min(3, args.steps))
+        reset(total)
+        begin(0, nburst)
+        lat_b = latents
+        torch.cuda.synchronize()
+        tb = time.perf_counter()
+        for i in range(nburst):
+            lat_b = step(i, lat_b)
+        host_burst = (time.perf_counter() - tb) / nburst
+        torch.cuda.synchronize()
+        burst_total = (time.perf_counter() - tb) / nburst
+        del lat_b
+        host = {"host_enqueue_ms_per_step": 1e3 * host_burst,
+                "gpu_to_host_enqueue_ratio": (elapsed / args.steps) / host_burst if host_burst > 0 else None,
+                "host_enqueue": {"burst_steps": nburst, "burst_ms_per_step_incl_gpu": 1e3 * burst_total,
+                                 "timed_loop_enqueue_ms_per_step": 1e3 * enqueued / args.steps,
+                                 "note": "host_enqueue_ms_per_step = wall time to enqueue one step's launches from an idle queue "
+                                         "(no sync, burst outside the timed region); timed_loop_enqueue includes the HIP queue's "
+                                         "back-pressure once the host runs ~2000 launches ahead"}}
 
     def core_line(extra_bcast=None):
         """The driver's line from what is known right after the timed region (the watchdog below prints exactly this)."""
@@ -911,21 +947,14 @@ def main():
                 "world": world, "rccl_ranks": world if distributed else 1,
                 "model_tflops_per_gpu": (tf_ / (ms * 1e-3)) if full_ else None,
                 "mfma_utilisation_step": (tf_ / (ms * 1e-3) / PEAK_BF16_TFLOPS) if full_ else None,
-                "finite": finite, "broadcast": b or None, **({"debug_shared_gpu": True} if share_gpu else {}),
-                "host_enqueue_ms_per_step": 1e3 * host_burst,
-                "gpu_to_host_enqueue_ratio": (elapsed / args.steps) / host_burst if host_burst > 0 else None,
-                "host_enqueue": {"burst_steps": nburst, "burst_ms_per_step_incl_gpu": 1e3 * burst_total,
-                                 "timed_loop_enqueue_ms_per_step": 1e3 * enqueued / args.steps,
-                                 "note": "host_enqueue_ms_per_step = wall time to enqueue one step's launches from an idle queue "
-                                         "(no sync, burst outside the timed region); timed_loop_enqueue includes the HIP queue's "
-                                         "back-pressure once the host runs ~2000 launches ahead"}}
+                "finite": finite, "broadcast": b or None, **({"debug_shared_gpu": True} if share_gpu else {}), **host}
 
     # The ONE exchange step of the queue — shared text-encoder / VAE weights from rank 0, scatter + all-gather per 1 GiB
     # bucket, every rank then encodes the same ids with ITS copy and the results are compared bit for bit — runs AFTER the
     # timed region and under a watchdog: N > 1 executes for the first time on the driver's node, and a stuck collective must
     # cost the weights report, not the measured line.  On expiry rank 0 prints the line with the failure recorded and every
     # rank leaves; an exception on a rank is gathered (MIN over an ok flag) so that no rank reports success alone.
-    if distributed and not args.no_shared_weights:
+    if args.full and distributed and not args.no_shared_weights:
         import threading
         mods, what, probe = shared_weights(args.workload, dev, rank)
         if mods is not None:
@@ -960,7 +989,7 @@ def main():
 
     roofline = None
     kernels = {}
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         nprof = min(3, args.steps)
         reset(total)
         begin(0, nprof)
@@ -1023,7 +1052,7 @@ def main():
                                  "un-instrumented steps", "peak_at_clock": adj, "frac_of_clock_adjusted_peak": ach / adj})
 
     clip = None
-    if rank == 0 and clip_fn is not None and not args.no_clip and not args.layers:
+    if rank == 0 and clip_fn is not None and (args.full or args.clip) and not args.no_clip and not args.layers:
         clip = clip_fn()
 
     if rank == 0:
@@ -1033,10 +1062,10 @@ def main():
         out = core_line()
         out.update({"sec_per_clip": clip["sec_per_clip"] if clip else None, "clip": clip, "roofline": roofline,
                     "kernels": kernels})
-        if not args.no_cpu_baseline and args.gpus == 1 and args.workload in ("flux", "flux512", "qwen", "wan"):
+        if args.full and not args.no_cpu_baseline and args.gpus == 1 and args.workload in ("flux", "flux512", "qwen", "wan"):
             out["cpu_baseline"] = {"flux": cpu_baseline, "flux512": lambda: cpu_baseline(1024, 32), "qwen": cpu_baseline_qwen,
                                    "wan": cpu_baseline_wan}[args.workload]()
-        if args.workload == "flux" and args.gpus == 1 and full and not args.no_wan:
+        if args.full and args.workload == "flux" and args.gpus == 1 and full and not args.no_wan:
             del step, latents, clip_fn
             torch.cuda.empty_cache()
             out["wan"] = wan_half(dev, cpu=not args.no_cpu_baseline)

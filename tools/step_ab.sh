@@ -5,7 +5,7 @@ W=${1:-flux}; N=${2:-2}; A=${3:--}; B=${4:--}
 for r in $(seq 1 $N); do
   for L in "$A" "$B"; do
     if [ "$L" = "-" ]; then unset APEX_MI355_LIB; else export APEX_MI355_LIB=$L; fi
-    python bench.py --workload $W --no-cpu-baseline --no-clip --no-wan 2>/dev/null | tail -1 | python -c "
+    python bench.py --workload $W --full --no-cpu-baseline --no-clip --no-wan 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d.get('kernels',{})

@@ -4,7 +4,7 @@ W=${1:-flux}; N=${2:-2}; shift 2
 for r in $(seq 1 $N); do
   for T in "$@"; do
     if [ "$T" = "-" ]; then A=""; else A="--tune $T"; fi
-    python bench.py --workload $W $A --no-cpu-baseline --no-clip --no-wan 2>/dev/null | tail -1 | python -c "
+    python bench.py --workload $W $A --full --no-cpu-baseline --no-clip --no-wan 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 k=d.get('kernels',{})
