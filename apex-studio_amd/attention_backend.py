@@ -1,4 +1,4 @@
-"""The "hip_mfma" attention backend — B-op plug-in point.
+"""The "hip_mfma" and "hip_mfma_sdpa" attention backends — B-op plug-in point.
 
 Honours the calling convention of every backend in the reference's attention_register
 (apps/api/src/attention/functions.py:84, e.g. `sdpa` :338-377):
@@ -15,6 +15,12 @@ A KEY-PADDING mask (bool keep-mask or additive 0 / -inf mask that does not vary 
 kept keys only, by running the same kernel over each sample's kept keys (a prefix is a view, anything else one gather).
 It costs one host sync (the kept-key count sizes the launch).  Masks that vary along the query dimension, dropout and causal
 attention are not on any call site of the path: they raise, they do not fall back.
+
+"hip_mfma_sdpa" (KEY_SDPA) is the whole `sdpa` contract for manifests that need it (ops.attention_masked, one flash kernel):
+any attn_mask broadcastable to [B, Hq, Sq, Sk] (bool keep-mask, or additive float32 / q's dtype), is_causal (top-left
+aligned, AND-ed with the mask), grouped-query heads with enable_gqa, bf16 / f16, D = 64 or 128.  A query row with no allowed
+key returns zeros (as torch's CPU sdpa).  No host sync for any input.  Dropout, other dtypes or head sizes and CPU tensors
+raise ApexMIError; nothing falls back to torch.
 """
 from __future__ import annotations
 
@@ -24,6 +30,7 @@ from . import ops
 from .lib import ApexMIError
 
 KEY = "hip_mfma"
+KEY_SDPA = "hip_mfma_sdpa"
 
 
 def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False,
@@ -52,6 +59,13 @@ def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = 
             kb, vb = kb.index_select(2, idx), vb.index_select(2, idx)
         out[b:b + 1].copy_(ops.attention(q[b:b + 1], kb, vb, softmax_scale))
     return out
+
+
+def hip_mfma_sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None,
+                  enable_gqa: bool = False, **kwargs):
+    if dropout_p > 0:
+        raise ApexMIError("hip_mfma_sdpa: dropout is not supported (inference only)")
+    return ops.attention_masked(q, k, v, attn_mask, is_causal=is_causal, softmax_scale=softmax_scale, enable_gqa=enable_gqa)
 
 
 def _key_keep_mask(attn_mask: torch.Tensor, B: int, Sk: int) -> torch.Tensor:
@@ -84,8 +98,11 @@ def available() -> bool:
 
 
 def register(attention_register, set_default: bool = False, overwrite: bool = True):
-    """Register under KEY in the given FunctionRegister (the reference's, or register.attention_register)."""
-    attention_register(KEY, overwrite=overwrite, available=available())(hip_mfma)
+    """Register under KEY and KEY_SDPA in the given FunctionRegister (the reference's, or register.attention_register);
+    set_default makes KEY the default."""
+    ok = available()
+    attention_register(KEY, overwrite=overwrite, available=ok)(hip_mfma)
+    attention_register(KEY_SDPA, overwrite=overwrite, available=ok)(hip_mfma_sdpa)
     if set_default:
         attention_register.set_default(KEY)
     return attention_register

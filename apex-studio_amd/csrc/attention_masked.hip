@@ -1,0 +1,530 @@
+// Masked and causal attention forward: the whole contract of the reference's default "sdpa" backend
+// (R/src/attention/functions.py:338-377, i.e. F.scaled_dot_product_attention without dropout):
+//   out = softmax(q k^T * scale + mask) v,   mask broadcast to [B, Hq, Sq, Sk] (bool keep-mask or additive f32 / bf16 / f16),
+//   optionally AND-ed with the top-left causal mask (key j <= query i), grouped-query heads (query head h reads kv head
+//   h / (Hq / Hkv)), bf16 or f16, D = 64 or 128.  A query row without any allowed key yields zeros.
+//
+// One-pass flash kernel built like the plain attn_fwd_d128_kernel (attention.hip): 4 waves x 32 query rows per workgroup, 64-key
+// tiles, swapped products on v_mfma_f32_32x32x16_{bf16,f16} so lane l owns query row (l & 31), K and V^T tiles staged by 16-byte
+// global_load_lds into a double-buffered XOR-swizzled LDS image, workgroups of one (batch, head) kept on one XCD.  Differences:
+//   * q and k are read in place through their strides (no packing); V^T [B, Hkv, D, Skp] is staged in the workspace.
+//   * the online softmax keeps a RUNNING maximum (an additive mask can move a score by any amount), starting from a finite
+//     sentinel; excluded scores are -inf, so a row whose keys are all excluded so far never produces a NaN, and a row whose
+//     sum stays 0 stores zeros.  Consequence of the sentinel: an allowed score below -1e30 (base-2 units) counts as excluded.
+//   * per (query block, key tile) the kernel walks a list built at entry from the BLOCK MAP (attn_mask_map_kernel): SKIP tiles
+//     are never loaded nor multiplied, DENSE tiles (all allowed, additive value 0) run exactly the unmasked arithmetic, only
+//     PARTIAL tiles read the mask (4 runs of 8 keys per lane, issued ahead of the QK^T MFMAs).
+//   * causal: the key-tile range of a workgroup is computed from its query block (tiles above the diagonal are never in the
+//     list), only the tiles that cross the diagonal compare per element, and the query blocks of the whole launch run heaviest
+//     first so the short ones fill the last round.
+#include "common.h"
+
+#include <cstdint>
+
+namespace {
+
+constexpr int MKV = 64;            // keys per tile
+constexpr int MNW = 4;             // waves per workgroup
+constexpr int MQB = MNW * 32;      // query rows per workgroup (= rows of one block-map entry)
+constexpr int MAP_SKIP = 0, MAP_DENSE = 1, MAP_PARTIAL = 2;
+constexpr int MAX_TILES = 1 << 14;  // tile index + 2-bit code in the 16-bit LDS list entries
+constexpr float SENTINEL_MAX = -1.0e30f;
+constexpr float DEFER_MAX = 6.0f;     // as attention.hip: rescale only when a row maximum grows by more than 2^6
+constexpr float LOG2E_F = 1.4426950408889634f;
+
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+
+struct ElemBf16 {
+    using v8 = bf16x8;
+    static APEXMI_DEVICE f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+    static APEXMI_DEVICE void cvt(v8& r, int j, float x) { r[j] = (__bf16)x; }
+    static APEXMI_DEVICE uint32_t pack2(float a, float b) { return pack_bf16(a, b); }
+};
+struct ElemF16 {
+    using v8 = f16x8;
+    static APEXMI_DEVICE f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    static APEXMI_DEVICE void cvt(v8& r, int j, float x) { r[j] = (_Float16)x; }
+    static APEXMI_DEVICE uint32_t pack2(float a, float b) {
+        f16x2 r;
+        r[0] = (_Float16)a;
+        r[1] = (_Float16)b;
+        return __builtin_bit_cast(uint32_t, r);
+    }
+};
+
+// mask element -> additive value in natural units (bool: 0 keep / -inf drop)
+template <int MK>
+APEXMI_DEVICE float mask_value(const void* m, int64_t off);
+template <>
+APEXMI_DEVICE float mask_value<APEXMI_MASK_BOOL>(const void* m, int64_t off) {
+    return ((const uint8_t*)m)[off] ? 0.0f : -__builtin_inff();
+}
+template <>
+APEXMI_DEVICE float mask_value<APEXMI_F32>(const void* m, int64_t off) { return ((const float*)m)[off]; }
+template <>
+APEXMI_DEVICE float mask_value<APEXMI_BF16>(const void* m, int64_t off) { return bf16_to_f32(((const uint16_t*)m)[off]); }
+template <>
+APEXMI_DEVICE float mask_value<APEXMI_F16>(const void* m, int64_t off) {
+    return (float)__builtin_bit_cast(_Float16, ((const uint16_t*)m)[off]);
+}
+
+struct MaskedArgs {
+    const uint16_t* q;
+    const uint16_t* k;
+    const uint16_t* vt;
+    uint16_t* o;
+    const void* mask;       // nullptr: no mask (every tile DENSE)
+    const uint8_t* map;     // block map [Bm, Hm, nqb, nkt] (nullptr with mask == nullptr)
+    int64_t q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, o_sb, o_ss, o_sh;
+    int64_t m_sb, m_sh, m_sq, m_sk;   // element strides of the mask broadcast to [B, Hq, Sq, Sk] (0 on broadcast dims)
+    int Hq, group, Sq, Sk, Skp, nqb, nkt, total, mkind, causal, neg;
+    float c;                // |scale| * log2(e)
+};
+
+// Block map pre-pass: one workgroup per (key tile, query block, own mask (batch, head)).  SKIP: no allowed element; DENSE:
+// every element allowed with additive value 0; PARTIAL otherwise.  VEC (host: key stride 1, 16-byte aligned rows): whole tiles
+// are read 16 bytes per lane; otherwise (and on the key tail) one element per lane, 64 lanes along the keys, 4 rows per step.
+template <int MK, typename ET, bool VEC>
+__global__ __launch_bounds__(256) void attn_mask_map_kernel(const void* __restrict__ mask, int64_t m_sb, int64_t m_sh,
+                                                            int64_t m_sq, int64_t m_sk, int Hm, int Sq, int Sk, int nqb,
+                                                            int nkt, uint8_t* __restrict__ map) {
+    const int t = blockIdx.x, qb = blockIdx.y, z = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)(z / Hm) * m_sb + (int64_t)(z % Hm) * m_sh;
+    int any = 0, dense = 1;
+    if (VEC && (t + 1) * MKV <= Sk) {
+        constexpr int NE = 16 / sizeof(ET), LPR = MKV / NE, RPS = 256 / LPR;   // elements per lane, lanes per row, rows per step
+        const int key = t * MKV + (tid % LPR) * NE;
+        for (int r = qb * MQB + tid / LPR; r < min(Sq, (qb + 1) * MQB); r += RPS) {
+            const u32x4 raw = *(const u32x4*)((const ET*)mask + base + (int64_t)r * m_sq + key);
+            const ET* e = (const ET*)&raw;
+#pragma unroll
+            for (int j = 0; j < NE; ++j) {
+                const float v = mask_value<MK>(e, j);
+                const int ok = v != -__builtin_inff();
+                any |= ok;
+                dense &= ok && v == 0.0f;
+            }
+        }
+    } else {
+        const int key = t * MKV + (tid & 63);
+        if (key < Sk) {
+            const int64_t kof = base + (int64_t)key * m_sk;
+            for (int r = qb * MQB + (tid >> 6); r < min(Sq, (qb + 1) * MQB); r += 4) {
+                const float v = mask_value<MK>(mask, kof + (int64_t)r * m_sq);
+                const int ok = v != -__builtin_inff();
+                any |= ok;
+                dense &= ok && v == 0.0f;
+            }
+        }
+    }
+    any = __syncthreads_or(any);
+    dense = __syncthreads_and(dense);
+    if (tid == 0) map[((int64_t)z * nqb + qb) * nkt + t] = (uint8_t)(!any ? MAP_SKIP : dense ? MAP_DENSE : MAP_PARTIAL);
+}
+
+// V [B, Hkv, Sk, 64] (strided rows) -> V^T [B, Hkv, 64, Skp], keys >= Sk zero (the D = 128 case uses apexmi_v_transpose)
+__global__ __launch_bounds__(256) void v_transpose64_kernel(const uint16_t* __restrict__ v, int64_t sb, int64_t sh, int64_t ss,
+                                                            int Hkv, int Sk, int Skp, uint16_t* __restrict__ vt) {
+    constexpr int LDW = 66;   // odd dword pitch: the column reads below spread over the banks
+    __shared__ uint16_t tile[64 * LDW];
+    const int tid = threadIdx.x;
+    const int s0 = blockIdx.x * 64, h = blockIdx.y, b = blockIdx.z;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int idx = i * 256 + tid;
+        const int r = idx >> 3, c = idx & 7;
+        u32x4 val = u32x4{0u, 0u, 0u, 0u};
+        if (s0 + r < Sk) val = *(const u32x4*)(v + (int64_t)b * sb + (int64_t)h * sh + (int64_t)(s0 + r) * ss + c * 8);
+        uint32_t* dst = (uint32_t*)(tile + r * LDW + c * 8);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dst[j] = val[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int idx = i * 256 + tid;
+        const int d = idx >> 3, sc = idx & 7;
+        u32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            o[j] = (uint32_t)tile[(sc * 8 + 2 * j) * LDW + d] | ((uint32_t)tile[(sc * 8 + 2 * j + 1) * LDW + d] << 16);
+        *(u32x4*)(vt + (((int64_t)b * Hkv + h) * 64 + d) * Skp + s0 + sc * 8) = o;
+    }
+}
+
+// row i of a 32-row K sub-tile holds key mperm32(i): bits 2 and 3 swapped (as attention.hip's perm32)
+APEXMI_DEVICE int mperm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
+
+template <typename E, int D>
+__global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using v8 = typename E::v8;
+    constexpr int K_TILE = MKV * D * 2, V_TILE = D * MKV * 2, STAGE = K_TILE + V_TILE;
+    constexpr int CH = D / 8;                   // 16-byte chunks per K row
+    constexpr int NP = D / 8;                   // 1 KiB LDS-DMA pieces per image (K and V^T alike)
+    constexpr int LD = (NP + MNW - 1) / MNW;    // pieces per wave per image
+    constexpr int NKS = D / 16, NDT = D / 32;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+
+    // causal: query blocks in decreasing order of work over the whole launch (block id = position in dispatch order); workgroup
+    // b runs on XCD b % 8, so with B Hq a multiple of 8 every (batch, head) still stays on one XCD
+    const int s = a.causal ? (int)blockIdx.x : xcd_remap(blockIdx.x, a.total);
+    const int nhb = a.total / a.nqb;
+    const int hb = a.causal ? s % nhb : s / a.nqb;
+    const int qb = a.causal ? a.nqb - 1 - s / nhb : s % a.nqb;
+    const int b = hb / a.Hq, h = hb % a.Hq;
+    const int hk = h / a.group;
+
+    const uint16_t* Qp = a.q + (int64_t)b * a.q_sb + (int64_t)h * a.q_sh;
+    const uint16_t* Kp = a.k + (int64_t)b * a.k_sb + (int64_t)hk * a.k_sh;
+    const uint16_t* Vp = a.vt + ((int64_t)b * (a.Hq / a.group) + hk) * D * a.Skp;
+
+    const int q0 = qb * MQB;
+    const int qrow = q0 + wave * 32 + l31;
+    const int qrow_c = min(qrow, a.Sq - 1);
+
+    // ---- tile list: the key tiles this workgroup visits, with their block-map code (wave 0 builds it, LDS) ----
+    int* list_n = (int*)(smem + 2 * STAGE);
+    uint16_t* list = (uint16_t*)(smem + 2 * STAGE + 16);
+    const int nt = (a.Sk + MKV - 1) / MKV;
+    const int t_end = a.causal ? min(nt, min(q0 + MQB - 1, a.Sq - 1) / MKV + 1) : nt;
+    if (wave == 0) {
+        const uint8_t* mrow = nullptr;
+        if (a.map) {
+            const int mb = a.m_sb ? b : 0, mh = a.m_sh ? h : 0, Hm = a.m_sh ? a.Hq : 1;
+            mrow = a.map + ((int64_t)(mb * Hm + mh) * a.nqb + qb) * a.nkt;
+        }
+        int n = 0;
+        for (int t0 = 0; t0 < t_end; t0 += 64) {
+            const int t = t0 + lane;
+            const int code = t < t_end ? (mrow ? (int)mrow[t] : MAP_DENSE) : MAP_SKIP;
+            const uint64_t bal = __ballot(code != MAP_SKIP);
+            const int pos = n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+            if (code != MAP_SKIP) list[pos] = (uint16_t)(t | (code << 14));
+            n += __builtin_popcountll(bal);
+        }
+        if (lane == 0) *list_n = n;
+    }
+
+    // Q fragments (B operand of S^T): lane supplies Q[qrow][16 ks + 8 hi .. +7]; a negative scale flips their signs (exact)
+    v8 qf[NKS];
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+        u32x4 raw = *(const u32x4*)(Qp + (int64_t)qrow_c * a.q_ss + ks * 16 + hi * 8);
+        if (a.neg) raw ^= u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
+        qf[ks] = __builtin_bit_cast(v8, raw);
+    }
+
+    // staging sources.  K image: [64 rows][CH chunks], chunk ^= row & (CH - 1), row i <- key mperm32(i).
+    // V^T image: [D rows][8 chunks], chunk ^= (row >> 1) & 7.
+    int k_key[LD], k_c[LD];
+    const uint16_t* v_src[LD];
+#pragma unroll
+    for (int i = 0; i < LD; ++i) {
+        const int p = (i * MNW + wave) * 64 + lane;
+        {
+            const int row = (p / CH) & 63, pc = p % CH;
+            k_c[i] = (pc ^ (row & (CH - 1))) * 8;
+            k_key[i] = (row & 32) + mperm32(row & 31);
+        }
+        {
+            const int row = (p >> 3) & (D - 1), pc = p & 7;
+            v_src[i] = Vp + (int64_t)row * a.Skp + (pc ^ ((row >> 1) & 7)) * 8;
+        }
+    }
+    auto stage = [&](int buf, int t) {
+        char* base = smem + buf * STAGE + wave * 1024;
+        const int kv0 = t * MKV;
+#pragma unroll
+        for (int i = 0; i < LD; ++i)
+            if (i * MNW + wave < NP) {   // wave-uniform
+                const int key = min(kv0 + k_key[i], a.Sk - 1);
+                glds16(Kp + (int64_t)key * a.k_ss + k_c[i], base + i * (MNW * 1024));
+            }
+#pragma unroll
+        for (int i = 0; i < LD; ++i)
+            if (i * MNW + wave < NP) glds16(v_src[i] + kv0, base + K_TILE + i * (MNW * 1024));
+    };
+
+    int k_off[2], k_sw[2];
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+        const int row = kt * 32 + l31;
+        k_off[kt] = row * (D * 2);
+        k_sw[kt] = row & (CH - 1);
+    }
+    int v_off[NDT], v_sw[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+        const int row = dt * 32 + l31;
+        v_off[dt] = row * 128;
+        v_sw[dt] = (row >> 1) & 7;
+    }
+    const int64_t m_row = (int64_t)b * a.m_sb + (int64_t)h * a.m_sh + (int64_t)qrow_c * a.m_sq;
+
+    f32x16 oacc[NDT];
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
+    float m_run = SENTINEL_MAX;  // running maximum, base-2 domain, an integer (see attention.hip above DEFER)
+    float l_run = 0.0f;
+
+    __syncthreads();
+    const int n = *list_n;
+    if (n > 0) stage(0, list[0] & (MAX_TILES - 1));
+    for (int it = 0; it < n; ++it) {
+        const int ent = list[it];
+        const int t = ent & (MAX_TILES - 1), code = ent >> 14;
+        const int kv0 = t * MKV;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's LDS-DMA has landed (see attention.hip)
+        __syncthreads();
+
+        // mask values of a PARTIAL tile, issued before the next tile's staging so waiting for them does not wait for it
+        float mv[2][16];
+        if (code == MAP_PARTIAL) {
+#define MASK_LOADS(MK)                                                                                          \
+    _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) _Pragma("unroll") for (int r = 0; r < 16; ++r) {           \
+        const int g = r >> 2;                                                                                   \
+        const int key = min(kv0 + kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3), a.Sk - 1);         \
+        mv[kt][r] = mask_value<MK>(a.mask, m_row + (int64_t)key * a.m_sk) * LOG2E_F;                            \
+    }
+            switch (a.mkind) {
+                case APEXMI_MASK_BOOL: MASK_LOADS(APEXMI_MASK_BOOL); break;
+                case APEXMI_F32: MASK_LOADS(APEXMI_F32); break;
+                case APEXMI_BF16: MASK_LOADS(APEXMI_BF16); break;
+                default: MASK_LOADS(APEXMI_F16); break;
+            }
+#undef MASK_LOADS
+        }
+        if (it + 1 < n) stage((it + 1) & 1, list[it + 1] & (MAX_TILES - 1));
+        const char* Ks = smem + (it & 1) * STAGE;
+        const char* Vs = Ks + K_TILE;
+
+        // ---- S^T = K Q^T : sacc[kt][r] = score(q = l31, key kv0 + kt 32 + 16 (g >> 1) + 8 hi + 4 (g & 1) + (r & 3), g = r >> 2) ----
+        f32x16 sacc[2];
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sacc[kt][r] = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+            const int c = ks * 2 + hi;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                const v8 kf = *(const v8*)(Ks + k_off[kt] + ((c ^ k_sw[kt]) << 4));
+                sacc[kt] = E::mfma(kf, qf[ks], sacc[kt]);
+            }
+        }
+
+        // per-element path (workgroup-uniform): PARTIAL tiles, tiles crossing the causal diagonal, the key tail
+        const bool elem = code == MAP_PARTIAL || (a.causal && kv0 + MKV - 1 > q0) || kv0 + MKV > a.Sk;
+        float mx;
+        if (elem) {
+            const bool part = code == MAP_PARTIAL;
+            const int lim = a.causal ? min(a.Sk - 1, qrow) : a.Sk - 1;
+            mx = -__builtin_inff();
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int g = r >> 2;
+                    const int key = kv0 + kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3);
+                    const float x = fmaf(sacc[kt][r], a.c, part ? mv[kt][r] : 0.0f);
+                    sacc[kt][r] = key <= lim ? x : -__builtin_inff();
+                    mx = fmaxf(mx, sacc[kt][r]);
+                }
+        } else {
+            mx = sacc[0][0];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kt][r]);
+            mx *= a.c;
+        }
+        mx = max_xor32(mx);
+        if (__any(mx > m_run + DEFER_MAX)) {   // wave-uniform; -inf (nothing allowed yet) never raises the sentinel
+            const float m_new = ceilf(fmaxf(m_run, mx));
+            const float alpha = fast_exp2(m_run - m_new);
+            m_run = m_new;
+            l_run *= alpha;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
+        }
+        float psum = 0.0f;
+        if (elem) {
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = fast_exp2(sacc[kt][r] - m_run);
+                    sacc[kt][r] = p;
+                    psum += p;
+                }
+        } else {
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = fast_exp2(fmaf(sacc[kt][r], a.c, -m_run));
+                    sacc[kt][r] = p;
+                    psum += p;
+                }
+        }
+        l_run += psum;
+
+        // ---- P -> B-fragments: k-step kk takes regs 8 (kk & 1) .. +7 of sacc[kk >> 1] (keys 16 kk + 8 hi .. +7) ----
+        v8 pf[4];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) E::cvt(pf[kk], j, sacc[kk >> 1][8 * (kk & 1) + j]);
+
+        // ---- O^T += V^T P^T ----
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int c = kk * 2 + hi;
+#pragma unroll
+            for (int dt = 0; dt < NDT; ++dt) {
+                const v8 vf = *(const v8*)(Vs + v_off[dt] + ((c ^ v_sw[dt]) << 4));
+                oacc[dt] = E::mfma(vf, pf[kk], oacc[dt]);
+            }
+        }
+    }
+
+    // ---- epilogue: O[q][d] = O^T / l (0 for a row without an allowed key); lane holds d = 32 dt + 8 g + 4 hi + (0..3) ----
+    const float l_tot = sum_xor32(l_run);
+    const float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
+    if (qrow < a.Sq) {
+        uint16_t* op = a.o + (int64_t)b * a.o_sb + (int64_t)qrow * a.o_ss + (int64_t)h * a.o_sh;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                u32x2 o;
+                o[0] = E::pack2(oacc[dt][4 * g + 0] * inv, oacc[dt][4 * g + 1] * inv);
+                o[1] = E::pack2(oacc[dt][4 * g + 2] * inv, oacc[dt][4 * g + 3] * inv);
+                *(u32x2*)(op + dt * 32 + g * 8 + hi * 4) = o;
+            }
+    }
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+size_t vt_bytes(int B, int Hkv, int Sk, int D) {
+    const size_t skp = (size_t)((Sk + MKV - 1) / MKV) * MKV;
+    return align256((size_t)B * Hkv * D * skp * 2);
+}
+
+template <typename E, int D>
+int launch_masked(const MaskedArgs& a, hipStream_t stream) {
+    constexpr int STAGE = 2 * MKV * D * 2;
+    static uint64_t attr_done = 0;
+    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D>,
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                              2 * STAGE + 16 + 2 * MAX_TILES));
+    const int lds = 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15);
+    hipLaunchKernelGGL((attn_masked_kernel<E, D>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
+    return apexmi_check_launch("attn_fwd_masked");
+}
+
+template <int MK, typename ET>
+void launch_map(const MaskedArgs& a, int Bm, int Hm, uint8_t* map, hipStream_t stream) {
+    constexpr int64_t NE = 16 / sizeof(ET);
+    const bool vec = a.m_sk == 1 && ((uintptr_t)a.mask % 16) == 0 && a.m_sb % NE == 0 && a.m_sh % NE == 0 && a.m_sq % NE == 0;
+    auto kern = vec ? attn_mask_map_kernel<MK, ET, true> : attn_mask_map_kernel<MK, ET, false>;
+    hipLaunchKernelGGL(kern, dim3(a.nkt, a.nqb, Bm * Hm), dim3(256), 0, stream, a.mask, a.m_sb, a.m_sh, a.m_sq, a.m_sk, Hm, a.Sq, a.Sk, a.nqb, a.nkt, map);
+}
+
+}  // namespace
+
+extern "C" size_t apexmi_attn_masked_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D) {
+    if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || (D != 64 && D != 128)) return 0;
+    const size_t nqb = (size_t)((Sq + MQB - 1) / MQB), nkt = (size_t)((Sk + MKV - 1) / MKV);
+    return vt_bytes(B, Hkv, Sk, D) + align256((size_t)B * Hq * nqb * nkt);
+}
+
+extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq,
+                                      int Sk, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                                      const int64_t v_strides[3], const int64_t o_strides[3], const void* mask,
+                                      int mask_dtype, const int64_t mask_strides[4], int is_causal, float softmax_scale,
+                                      int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides,
+                   "attn_fwd_masked: null operand");
+    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "attn_fwd_masked: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)",
+                   B, Hq, Hkv, Sq, Sk);
+    APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_masked: head dim %d unsupported (64 or 128)", D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_masked: dtype %d unsupported (bf16 or f16)", dtype);
+    APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_masked: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
+    APEXMI_REQUIRE(!mask || (mask_strides && (mask_dtype == APEXMI_MASK_BOOL || mask_dtype == APEXMI_F32 ||
+                                              mask_dtype == APEXMI_BF16 || mask_dtype == APEXMI_F16)),
+                   "attn_fwd_masked: mask dtype code %d unsupported (bool, f32, bf16, f16)", mask_dtype);
+    APEXMI_REQUIRE(!mask || mask_strides[3] == 0 || mask_strides[3] == 1,
+                   "attn_fwd_masked: mask key stride %lld must be 0 or 1", (long long)(mask ? mask_strides[3] : 0));
+    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_masked: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_masked: too many query blocks");
+    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
+    for (int i = 0; i < 3; ++i)
+        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
+    APEXMI_REQUIRE(aligned, "attn_fwd_masked: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
+    const size_t need = apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D);
+    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "attn_fwd_masked: workspace too small (%zu < %zu)", workspace_bytes,
+                   need);
+
+    MaskedArgs a{};
+    a.q = (const uint16_t*)q;
+    a.k = (const uint16_t*)k;
+    a.o = (uint16_t*)out;
+    a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
+    a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
+    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + MKV - 1) / MKV) * MKV;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * Hq * a.nqb;
+    a.causal = is_causal ? 1 : 0;
+    a.neg = softmax_scale < 0.0f;
+    a.c = fabsf(softmax_scale) * LOG2E_F;
+
+    // V^T [B, Hkv, D, Skp]
+    uint16_t* vt = (uint16_t*)workspace;
+    a.vt = vt;
+    if (D == 128) {
+        for (int b = 0; b < B; ++b)
+            if (int rc = apexmi_v_transpose((const uint16_t*)v + b * v_strides[0], v_strides[1], v_strides[2], Sk, Hkv, D,
+                                            vt + (size_t)b * Hkv * D * a.Skp, a.Skp, 0, stream_))
+                return rc;
+    } else {
+        hipLaunchKernelGGL(v_transpose64_kernel, dim3(a.Skp / 64, Hkv, B), dim3(256), 0, stream, (const uint16_t*)v,
+                           v_strides[0], v_strides[1], v_strides[2], Hkv, Sk, a.Skp, vt);
+        if (int rc = apexmi_check_launch("attn_fwd_masked (V^T)")) return rc;
+    }
+
+    // block map of the mask over its own (batch, head) dims
+    if (mask) {
+        uint8_t* map = (uint8_t*)workspace + vt_bytes(B, Hkv, Sk, D);
+        a.mask = mask, a.mkind = mask_dtype, a.map = map;
+        a.m_sb = B > 1 ? mask_strides[0] : 0, a.m_sh = Hq > 1 ? mask_strides[1] : 0;
+        a.m_sq = Sq > 1 ? mask_strides[2] : 0, a.m_sk = Sk > 1 ? mask_strides[3] : 0;
+        const int Bm = a.m_sb ? B : 1, Hm = a.m_sh ? Hq : 1;
+        APEXMI_REQUIRE((int64_t)Bm * Hm <= 65535 && a.nqb <= 65535, "attn_fwd_masked: block map grid too large");
+        switch (mask_dtype) {
+            case APEXMI_MASK_BOOL: launch_map<APEXMI_MASK_BOOL, uint8_t>(a, Bm, Hm, map, stream); break;
+            case APEXMI_F32: launch_map<APEXMI_F32, float>(a, Bm, Hm, map, stream); break;
+            case APEXMI_BF16: launch_map<APEXMI_BF16, uint16_t>(a, Bm, Hm, map, stream); break;
+            default: launch_map<APEXMI_F16, uint16_t>(a, Bm, Hm, map, stream); break;
+        }
+        if (int rc = apexmi_check_launch("attn_fwd_masked (block map)")) return rc;
+    }
+
+    ApexmiProfScope prof(1, stream, 4.0 * B * Hq * (double)Sq * Sk * D, 0.0);
+    if (dtype == APEXMI_BF16) return D == 128 ? launch_masked<ElemBf16, 128>(a, stream) : launch_masked<ElemBf16, 64>(a, stream);
+    return D == 128 ? launch_masked<ElemF16, 128>(a, stream) : launch_masked<ElemF16, 64>(a, stream);
+}

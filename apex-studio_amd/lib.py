@@ -35,6 +35,9 @@ SIGNATURES = {
     "apexmi_attn_framecausal_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "apexmi_attn_fwd_framecausal": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                               c_i64p, c_i64p, c_i64p, c_i64p, C.c_float, vp, C.c_size_t, vp]),
+    "apexmi_attn_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "apexmi_attn_fwd_masked": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 4 + [vp, C.c_int, c_i64p, C.c_int,
+                                                                                        C.c_float, C.c_int, vp, C.c_size_t, vp]),
     "apexmi_gemm_bf16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
                                    C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
     "apexmi_gemm_bf16_grouped": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p,
@@ -142,6 +145,7 @@ NCLASS = 6
 PROF_CLASSES = ("gemm", "attention", "gemv", "ln_modulate", "qkv_prepare", "other")
 
 BF16, F16, F32 = 0, 1, 2
+MASK_BOOL = 3     # attention mask operand only (apexmi_attn_fwd_masked)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_F32, EPI_BIAS_GELU_ERF, EPI_BIAS_SILU, EPI_BIAS_QUICK_GELU = 0, 1, 2, 3, 4, 5, 6
 EPI_F32_IO = 0x100   # C and R are float: the f32-storage verification mode
 GEMV_PRE_SILU, GEMV_POST_SILU, GEMV_POST_GELU, GEMV_ACCUM = 1, 2, 4, 8
@@ -185,6 +189,10 @@ def check(rc: int, what: str = "") -> None:
 
 def i64x3(vals):
     return (C.c_int64 * 3)(*[int(v) for v in vals])
+
+
+def i64x4(vals):
+    return (C.c_int64 * 4)(*[int(v) for v in vals])
 
 
 def tune_set(key: str, value: int) -> None:

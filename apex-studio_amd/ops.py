@@ -672,6 +672,90 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return out.permute(0, 2, 1, 3)
 
 
+_MASK_CODES = {torch.bool: _l.MASK_BOOL, torch.float32: _l.F32, torch.bfloat16: _l.BF16, torch.float16: _l.F16}
+
+
+def _mask_operand(attn_mask: Optional[torch.Tensor], B: int, Hq: int, Sq: int, Sk: int, q_dtype=None):
+    """attn_mask -> (tensor, dtype code, element strides (b, h, q, k) of its broadcast to [B, Hq, Sq, Sk]), or (None, -1,
+    (0, 0, 0, 0)).  torch's rule: right-aligned broadcasting (expand), bool (True = attend) or additive f32 / q's dtype.
+    Broadcast dims get stride 0, so the mask is read in place and never materialised at [B, Hq, Sq, Sk].  A key dimension whose
+    stride is neither 0 nor 1 costs one contiguous copy of the mask's own elements."""
+    if attn_mask is None:
+        return None, -1, (0, 0, 0, 0)
+    m = attn_mask
+    if m.dtype not in _MASK_CODES:
+        raise _l.ApexMIError(f"attention_masked: attn_mask dtype {m.dtype} unsupported (bool, float32 or q's dtype)")
+    if m.dtype in (torch.bfloat16, torch.float16) and q_dtype is not None and m.dtype != q_dtype:
+        raise _l.ApexMIError(f"attention_masked: additive attn_mask of dtype {m.dtype} does not match q's dtype {q_dtype}")
+    if m.dim() > 4:
+        raise _l.ApexMIError(f"attention_masked: attn_mask of shape {tuple(m.shape)} has more than 4 dims")
+    shape = (B, Hq, Sq, Sk)
+    try:
+        e = m.expand(shape)
+    except RuntimeError as err:
+        raise _l.ApexMIError(f"attention_masked: attn_mask of shape {tuple(m.shape)} does not broadcast to {shape}") from err
+    if e.stride(3) not in (0, 1) and Sk > 1:
+        e = m.contiguous().expand(shape)
+    strides = tuple(0 if n == 1 else st for n, st in zip(shape, e.stride()))
+    return e, _MASK_CODES[m.dtype], strides
+
+
+def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
+                     is_causal: bool = False, softmax_scale: Optional[float] = None,
+                     enable_gqa: bool = False) -> torch.Tensor:
+    """F.scaled_dot_product_attention without dropout (the reference's "sdpa", R/src/attention/functions.py:338-377):
+    q [B,Hq,Sq,D], k / v [B,Hkv,Sk,D] bf16 or f16 (permuted views welcome), D = 64 or 128; attn_mask bool or additive,
+    broadcastable to [B,Hq,Sq,Sk]; is_causal top-left aligned, AND-ed with the mask; grouped-query heads with enable_gqa (or
+    Hkv == 1).  A row without any allowed key is zero.  Returns a [B,Hq,Sq,D] view of a [B,Sq,Hq,D] buffer.  Shapes alone
+    size every launch: no host synchronisation."""
+    _req(q, None, "attention_masked.q")
+    _req(k, None, "attention_masked.k")
+    _req(v, None, "attention_masked.v")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"attention_masked: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise _l.ApexMIError("attention_masked: q, k, v must be 4-D [B, H, S, D]")
+    B, Hq, Sq, D = q.shape
+    Bk, Hkv, Sk, Dk = k.shape
+    if D not in (64, 128):
+        raise _l.ApexMIError(f"attention_masked: head dim {D} unsupported (64 or 128)")
+    if Bk != B or Dk != D or tuple(v.shape) != tuple(k.shape):
+        raise _l.ApexMIError(f"attention_masked: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
+        raise _l.ApexMIError(f"attention_masked: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
+                             "whole ratio")
+    if min(B, Hq, Sq, Sk) == 0:
+        raise _l.ApexMIError("attention_masked: empty problem")
+    m, mcode, mst = _mask_operand(attn_mask, B, Hq, Sq, Sk, q.dtype)
+    if m is not None and m.device != q.device:
+        raise _l.ApexMIError(f"attention_masked: attn_mask is on {m.device}, q on {q.device}")
+
+    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
+        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
+        return t if ok else t.contiguous()
+
+    q, k, v = rows16(q), rows16(k), rows16(v)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
+    lib = _l.load()
+    need = lib.apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D)
+    key = ("masked", q.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        _ws_cache[key] = ws
+    rc = lib.apexmi_attn_fwd_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
+                                    _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
+                                    _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
+                                    _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
+                                    _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                    _ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale),
+                                    _DT[q.dtype], ws.data_ptr(), need, _stream())
+    _l.check(rc, "attn_fwd_masked")
+    return out.permute(0, 2, 1, 3)
+
+
 def attention_framecausal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tokens_per_frame: int,
                           softmax_scale: Optional[float] = None) -> torch.Tensor:
     """Frame-causal attention of the HunyuanVideo-1.5 VAE mid block: q, k, v [B,H,S,D] bf16 (D a multiple of 128 up to

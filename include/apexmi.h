@@ -29,6 +29,7 @@ typedef void* apexmi_stream_t; /* a hipStream_t; NULL = the null stream */
 #define APEXMI_BF16 0
 #define APEXMI_F16 1
 #define APEXMI_F32 2
+#define APEXMI_MASK_BOOL 3  /* attention mask operand only: one byte per element, non-zero = attend */
 
 /* GEMM epilogues */
 #define APEXMI_EPI_BIAS 0          /* C = A W^T + b                                   */
@@ -122,6 +123,22 @@ int apexmi_attn_fwd_framecausal(const void* q, const void* k, const void* v, voi
                                 int block, const int64_t q_strides[3], const int64_t k_strides[3],
                                 const int64_t v_strides[3], const int64_t o_strides[3], float softmax_scale,
                                 void* workspace, size_t workspace_bytes, apexmi_stream_t stream);
+
+/* The whole "sdpa" contract (R/src/attention/functions.py:338-377: F.scaled_dot_product_attention without dropout):
+ *     out = softmax(q k^T * softmax_scale + mask) v
+ * q [B,Hq,Sq,D], k / v [B,Hkv,Sk,D] with element strides (b, h, s) that are multiples of 8, D contiguous; bf16 or f16
+ * (`dtype`), D = 64 or 128; Hq a multiple of Hkv (query head h reads key/value head h / (Hq / Hkv)).  out is written as
+ * [B,Sq,Hq,D] with o_strides (b, s, h).  mask (NULL = none) is read in place through element strides (b, h, q, k) of its
+ * broadcast to [B,Hq,Sq,Sk] (0 on broadcast dims, the key stride 0 or 1); mask_dtype APEXMI_MASK_BOOL (non-zero = attend),
+ * APEXMI_F32, APEXMI_BF16 or APEXMI_F16 (additive, -inf = excluded).  is_causal: key j <= query i (top-left aligned, also
+ * for Sq != Sk), AND-ed with the mask.  A query row without any allowed key is written as zeros.  Launch sizes depend on
+ * the shapes only (no host sync).  workspace >= apexmi_attn_masked_workspace_bytes(...): V^T and the mask's block map. */
+size_t apexmi_attn_masked_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D);
+int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq, int Sk,
+                           int D, const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                           const int64_t o_strides[3], const void* mask, int mask_dtype, const int64_t mask_strides[4],
+                           int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
+                           apexmi_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Linear layers.  Replace torch.nn.Linear on the denoise path
