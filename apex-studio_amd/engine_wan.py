@@ -1,4 +1,5 @@
-"""Wan 2.2 A14B text-to-video engine surface on the HIP transformer + HIP VAE.
+"""Wan text-to-video (2.2 A14B) and image-to-video (2.2 A14B; 2.1 14B I2V / FLF2V with CLIP image conditioning) engine surfaces
+on the HIP transformer + HIP VAE (+ the HIP CLIP vision tower for Wan-2.1).
 
 Mirrors reference engine/wan/t2v.py:12-247 (`run`) and engine/wan/shared/__init__.py:478-608
 (`moe_denoise`), :464-476 (`_select_dual_noise_guidance_scale`), :309-462 (expert selection by
@@ -71,18 +72,21 @@ class WanT2VEngine(EngineLoraMixin):
                     use_cfg_guidance: bool = True, transformer_dtype=None, render_on_step: bool = False,
                     render_on_step_callback=None, render_on_step_interval: int = 3,
                     denoise_progress_callback=None, easy_cache_thresh: float = 0.0, easy_cache_ret_steps: int = 10,
-                    latent_condition: Optional[torch.Tensor] = None):
+                    latent_condition: Optional[torch.Tensor] = None, image_embeds: Optional[torch.Tensor] = None):
         """`easy_cache_thresh` > 0: EasyCache step skipping (R/src/engine/wan/shared/__init__.py:372-381, :435-444, :502-504).  The
         reference enables it on the high-noise expert WITH a reset of its (module-global) state and on the low-noise expert WITHOUT
         one, so the call count, the rate K, the accumulated error and the caches run on across the expert switch: no second
         warm-up of `ret_steps` pairs, and the last pair of the clip (`cnt >= 2n - 2`) is always computed.  Both experts are
         resident here: the first expert of the loop gets a fresh state, every later one continues it
-        (`share_easy_cache_state`), and the cache is switched off when the loop ends."""
+        (`share_easy_cache_state`), and the cache is switched off when the loop ends.  `image_embeds` (Wan-2.1 I2V / FLF2V: CLIP
+        image tokens [B, 257 n, image_dim]) goes to every transformer call, conditional and unconditional, as
+        `encoder_hidden_states_image`; without it the calls are exactly those of the text- / latent-conditioned path."""
         _emit(denoise_progress_callback, 0.0, "Starting denoise")
         try:
             return self._moe_loop(latents, timesteps, prompt_embeds, negative_prompt_embeds, guidance_scale, boundary_timestep,
                                   use_cfg_guidance, transformer_dtype, render_on_step, render_on_step_callback, render_on_step_interval,
-                                  denoise_progress_callback, easy_cache_thresh, easy_cache_ret_steps, latent_condition)
+                                  denoise_progress_callback, easy_cache_thresh, easy_cache_ret_steps, latent_condition,
+                                  image_embeds)
         finally:
             if easy_cache_thresh > 0.0:
                 for tr in {id(self.high_noise_transformer): self.high_noise_transformer,
@@ -92,8 +96,9 @@ class WanT2VEngine(EngineLoraMixin):
 
     def _moe_loop(self, latents, timesteps, prompt_embeds, negative_prompt_embeds, guidance_scale, boundary_timestep, use_cfg_guidance,
                   transformer_dtype, render_on_step, render_on_step_callback, render_on_step_interval, denoise_progress_callback,
-                  easy_cache_thresh, easy_cache_ret_steps, latent_condition=None):
+                  easy_cache_thresh, easy_cache_ret_steps, latent_condition=None, image_embeds=None):
         n = len(timesteps)
+        img_kw = {} if image_embeds is None else {"encoder_hidden_states_image": image_embeds}
         current = None
         for i, t in enumerate(timesteps):
             timestep = t.expand(latents.shape[0])
@@ -110,10 +115,10 @@ class WanT2VEngine(EngineLoraMixin):
             x = latents.to(dt_x) if latent_condition is None else torch.cat([latents, latent_condition.to(latents.dtype)], dim=1).to(dt_x)
             scale = self._select_dual_noise_guidance_scale(t, boundary_timestep, guidance_scale)
             noise_pred = transformer(hidden_states=x, timestep=timestep, encoder_hidden_states=prompt_embeds,
-                                     return_dict=False)[0]
+                                     return_dict=False, **img_kw)[0]
             if use_cfg_guidance and negative_prompt_embeds is not None:
                 uncond = transformer(hidden_states=x, timestep=timestep,
-                                     encoder_hidden_states=negative_prompt_embeds, return_dict=False)[0]
+                                     encoder_hidden_states=negative_prompt_embeds, return_dict=False, **img_kw)[0]
                 noise_pred = uncond + scale * (noise_pred - uncond)
             latents = self.scheduler.step(noise_pred.to(torch.float32), t, latents, return_dict=False)[0]
             if (render_on_step and render_on_step_callback and self.vae is not None
@@ -198,18 +203,68 @@ class WanT2VEngine(EngineLoraMixin):
 
 
 class WanI2VEngine(WanT2VEngine):
-    """Wan-2.2 A14B image-to-video (R/src/engine/wan/i2v.py:13-314, the `boundary_ratio` branch: two experts with
-    `in_channels` = 36, no CLIP image embeddings — `moe_denoise` drops `encoder_hidden_states_image`, shared/__init__.py:494-495).
-    The first frame conditions the clip through the latent path only:
+    """Wan image-to-video (R/src/engine/wan/i2v.py:13-314).  Two model families:
+
+    * Wan-2.2 A14B (the `boundary_ratio` branch: two experts with `in_channels` = 36, no `image_dim`): the first frame conditions
+      the clip through the latent path only (the reference's `moe_denoise` drops `encoder_hidden_states_image`,
+      shared/__init__.py:494-495).
+    * Wan-2.1 14B I2V / FLF2V (one transformer, `boundary_ratio=None`; its config has `image_dim`): the latent path as below AND
+      CLIP image embeddings (diffusers WanImageToVideoPipeline.encode_image: `image_encoder(...).hidden_states[-2]` of the
+      preprocessed ORIGINAL image, or of [image, last_image] for FLF2V), computed once per run (or passed as `image_embeds=`),
+      repeated over the batch and given to every transformer call as `encoder_hidden_states_image`.  `image_encoder`: a
+      `clip_vision.CLIPVisionModel` (or anything with its call surface); missing when the model needs one -> ValueError.
+
+    The latent path:
 
         video_condition = [image | zeros x (num_frames - 1)]                           (i2v.py:186-198)
         latent_condition = normalize_latents(vae.encode(video_condition).mode())       (BaseEngine.vae_encode, base_engine.py:2062-2165)
         mask = 1 on the first frame's four sub-frames, 0 after -> [B, 4, T_lat, h, w]  (i2v.py:220-249)
         every step:  hidden_states = cat([latents, mask, latent_condition], dim=1)     (36 channels)
 
+    FLF2V (`last_image`): video_condition = [image | zeros x (num_frames - 2) | last_image] and the mask is 1 on the first AND the
+    last pixel frame; `last_image` is resized to the first image's size.
+
     `image`: a PIL image / HWC uint8 array (resized to the aspect-preserving size of area height x width on the reference's
     rule, `_aspect_ratio_resize`, base_engine.py:501-514, then x / 127.5 - 1) or pixels [B|1, 3, H, W] in [-1, 1] (used as they
     are: H, W multiples of 16).  The TI2V-5B form (`expand_timesteps`: per-token timesteps) is a different model and raises."""
+
+    def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
+                 scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
+                 vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None):
+        super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
+                         vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder)
+        self.image_encoder = image_encoder
+
+    @property
+    def uses_image_embeds(self) -> bool:
+        """True for a transformer whose config has `image_dim` (Wan-2.1 I2V / FLF2V): the CLIP branch."""
+        return getattr(self.high_noise_transformer.config, "image_dim", None) is not None
+
+    def encode_image(self, images, batch: int = 1) -> torch.Tensor:
+        """CLIP image tokens of one image, or of [image, last_image] (FLF2V): `hidden_states[-2]` of the image encoder on the
+        CLIPImageProcessor-preprocessed images -> [batch, 257 n, image_dim], repeated over the batch."""
+        from .clip_vision import clip_preprocess
+        if self.image_encoder is None:
+            raise ValueError("wan i2v: this transformer conditions on CLIP image embeddings (its config has image_dim): pass "
+                             "image_encoder= to the engine, or image_embeds= to run()")
+        images = list(images) if isinstance(images, (list, tuple)) else [images]
+        pil = [self._to_pil(im) for im in images]
+        px = clip_preprocess(pil).to(self.image_encoder.device)
+        h = self.image_encoder(pixel_values=px, output_hidden_states=True).hidden_states[-2]
+        return h.reshape(1, -1, h.shape[-1]).repeat(batch, 1, 1)
+
+    @staticmethod
+    def _to_pil(image):
+        """PIL image / HWC uint8 array / pixels [1|3, H, W] or [1, 3, H, W] in [-1, 1] -> RGB PIL image."""
+        import numpy as np
+        from PIL import Image
+        if isinstance(image, Image.Image):
+            return image.convert("RGB")
+        if isinstance(image, torch.Tensor):
+            x = image[0] if image.dim() == 4 else image
+            x = ((x.detach().float().cpu().clamp(-1, 1) + 1.0) * 127.5).round().to(torch.uint8)
+            return Image.fromarray(x.permute(1, 2, 0).numpy())
+        return Image.fromarray(np.asarray(image)).convert("RGB")
 
     @staticmethod
     def aspect_ratio_size(h0: int, w0: int, max_area: int, mod_value: int = 16):
@@ -220,18 +275,21 @@ class WanI2VEngine(WanT2VEngine):
         return (int(round(np.sqrt(max_area * aspect))) // mod_value * mod_value,
                 int(round(np.sqrt(max_area / aspect))) // mod_value * mod_value)
 
-    def preprocess_image(self, image, height: int, width: int):
-        """-> (pixels [B, 3, H, W] float32 in [-1, 1] on the device, H, W)."""
+    def preprocess_image(self, image, height: int, width: int, size=None):
+        """-> (pixels [B, 3, H, W] float32 in [-1, 1] on the device, H, W).  `size` (H, W): resize to exactly that (FLF2V's
+        last image takes the first image's size)."""
         if isinstance(image, torch.Tensor):
             x = image if image.dim() == 4 else image[None]
             if x.shape[1] != 3 or x.shape[-2] % 16 or x.shape[-1] % 16:
                 raise ValueError(f"wan i2v: pixel tensors must be [B, 3, H, W] with H, W multiples of 16, got {tuple(image.shape)}")
+            if size is not None and tuple(x.shape[-2:]) != tuple(size):
+                raise ValueError(f"wan i2v: the last-frame pixels {tuple(x.shape[-2:])} must match the first image's {tuple(size)}")
             return x.to(self.device, torch.float32), int(x.shape[-2]), int(x.shape[-1])
         import numpy as np
         from PIL import Image
         img = image if isinstance(image, Image.Image) else Image.fromarray(np.asarray(image))
         img = img.convert("RGB")
-        h, w = self.aspect_ratio_size(img.height, img.width, height * width, 16)
+        h, w = size if size is not None else self.aspect_ratio_size(img.height, img.width, height * width, 16)
         img = img.resize((w, h), Image.Resampling.LANCZOS)
         x = torch.from_numpy(np.asarray(img).astype(np.float32) / 255.0).permute(2, 0, 1)[None]      # VideoProcessor.preprocess:
         return (2.0 * x - 1.0).to(self.device), h, w                                                  # [0, 1] -> [-1, 1]
@@ -242,23 +300,30 @@ class WanI2VEngine(WanT2VEngine):
         lat = self.vae.encode(video.to(self.device, compute_dtype(self.vae)), return_dict=False)[0].mode()
         return self.vae.normalize_latents(lat.to(dtype))
 
-    def first_frame_mask(self, batch: int, num_frames: int, latent_height: int, latent_width: int) -> torch.Tensor:
-        """i2v.py:220-249: ones on pixel frame 0, zeros after; frame 0 repeated to the temporal factor so every latent frame owns
-        `vae_scale_factor_temporal` mask channels -> [B, 4, T_lat, h, w]."""
+    def first_frame_mask(self, batch: int, num_frames: int, latent_height: int, latent_width: int,
+                         last_frame: bool = False) -> torch.Tensor:
+        """i2v.py:220-249: ones on pixel frame 0 (and on the last pixel frame with `last_frame`, FLF2V), zeros between; frame 0
+        repeated to the temporal factor so every latent frame owns `vae_scale_factor_temporal` mask channels -> [B, 4, T_lat, h, w]."""
         f = self.vae_scale_factor_temporal
         m = torch.ones(batch, 1, num_frames, latent_height, latent_width, device=self.device)
-        m[:, :, 1:] = 0
+        m[:, :, 1:num_frames - 1 if last_frame else num_frames] = 0
         m = torch.cat([torch.repeat_interleave(m[:, :, 0:1], dim=2, repeats=f), m[:, :, 1:]], dim=2)
         return m.view(batch, -1, f, latent_height, latent_width).transpose(1, 2)
 
-    def prepare_latent_condition(self, pixels: torch.Tensor, num_frames: int, batch: int) -> torch.Tensor:
+    def prepare_latent_condition(self, pixels: torch.Tensor, num_frames: int, batch: int,
+                                 last_pixels: Optional[torch.Tensor] = None) -> torch.Tensor:
         B0, _, H, W = pixels.shape
         first = pixels[:, :, None]
-        video = torch.cat([first, first.new_zeros(B0, 3, num_frames - 1, H, W)], dim=2)
+        if last_pixels is None:
+            video = torch.cat([first, first.new_zeros(B0, 3, num_frames - 1, H, W)], dim=2)
+        else:       # FLF2V: [image | zeros x (F - 2) | last_image]
+            last = last_pixels.expand(B0, -1, -1, -1)[:, :, None].to(first.dtype)
+            video = torch.cat([first, first.new_zeros(B0, 3, num_frames - 2, H, W), last], dim=2)
         cond = self.vae_encode(video, dtype=torch.float32)
         if cond.shape[0] != batch:
             cond = cond.repeat(batch // cond.shape[0], 1, 1, 1, 1)
-        mask = self.first_frame_mask(batch, num_frames, cond.shape[-2], cond.shape[-1]).to(cond.dtype)
+        mask = self.first_frame_mask(batch, num_frames, cond.shape[-2], cond.shape[-1],
+                                     last_frame=last_pixels is not None).to(cond.dtype)
         return torch.cat([mask, cond], dim=1)
 
     @torch.no_grad()
@@ -270,12 +335,16 @@ class WanI2VEngine(WanT2VEngine):
             progress_callback=None, render_on_step: bool = False, render_on_step_callback=None, render_on_step_interval: int = 3,
             output_type: Optional[str] = None, prompt=None, negative_prompt=None, prompt_ids=None, negative_prompt_ids=None,
             num_videos: int = 1, text_encoder_kwargs=None, easy_cache_thresh: float = 0.0, easy_cache_ret_steps: int = 10,
-            expand_timesteps: bool = False, ip_image=None, **_ignored):
+            expand_timesteps: bool = False, ip_image=None, last_image=None, image_embeds: Optional[torch.Tensor] = None,
+            **_ignored):
         if image is None:
             raise ValueError("wan i2v: `image` is required")
         if expand_timesteps or ip_image is not None:
             raise NotImplementedError("wan i2v: the TI2V-5B (`expand_timesteps`) and IP-image forms are other models; this engine "
-                                      "serves the Wan-2.2 A14B two-expert image-to-video path")
+                                      "serves the Wan-2.2 A14B and Wan-2.1 I2V / FLF2V image-to-video paths")
+        if self.uses_image_embeds and image_embeds is None and self.image_encoder is None:
+            raise ValueError("wan i2v: this transformer conditions on CLIP image embeddings (its config has image_dim): pass "
+                             "image_encoder= to the engine, or image_embeds= to run()")
         if self.vae is None:
             raise RuntimeError("WanI2VEngine needs the VAE (the condition video is encoded with it)")
         if self.high_noise_transformer.config.in_channels != 36:
@@ -294,7 +363,17 @@ class WanI2VEngine(WanT2VEngine):
         gs = list(guidance_scale) if isinstance(guidance_scale, (list, tuple)) else guidance_scale
         cfg = negative_prompt_embeds is not None and (all(g > 1.0 for g in gs) if isinstance(gs, list) else gs > 1.0)
         B = prompt_embeds.shape[0]
+        if self.uses_image_embeds:
+            if image_embeds is None:       # once per run, from the original image(s)
+                _emit(progress_callback, 0.1, "Encoding image")
+                image_embeds = self.encode_image(image if last_image is None else [image, last_image], B)
+            elif image_embeds.shape[0] != B:
+                image_embeds = image_embeds.repeat(B // image_embeds.shape[0], 1, 1)
+            image_embeds = image_embeds.to(dev, compute_dtype(self.high_noise_transformer))
+        else:
+            image_embeds = None            # the A14B experts take no image tokens
         pixels, height, width = self.preprocess_image(image, height, width)
+        last_pixels = None if last_image is None else self.preprocess_image(last_image, height, width, size=(height, width))[0]
         z_dim = 16
         num_latent_frames = (duration - 1) // self.vae_scale_factor_temporal + 1
         shape = (B, z_dim, num_latent_frames, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
@@ -307,7 +386,7 @@ class WanI2VEngine(WanT2VEngine):
         else:
             latents = latents.to(device=dev, dtype=torch.float32)
         _emit(progress_callback, 0.3, "Initialized latent noise")
-        latent_condition = self.prepare_latent_condition(pixels, duration, B)
+        latent_condition = self.prepare_latent_condition(pixels, duration, B, last_pixels)
         if tuple(latent_condition.shape[2:]) != tuple(latents.shape[2:]):
             raise ValueError(f"wan i2v: condition latents {tuple(latent_condition.shape)} do not match the video latents {tuple(latents.shape)}")
         timesteps = self.scheduler.set_timesteps(num_inference_steps, device=dev)
@@ -325,7 +404,7 @@ class WanI2VEngine(WanT2VEngine):
                                    render_on_step=render_on_step, render_on_step_callback=render_on_step_callback,
                                    render_on_step_interval=render_on_step_interval, denoise_progress_callback=mapped,
                                    easy_cache_thresh=easy_cache_thresh, easy_cache_ret_steps=easy_cache_ret_steps,
-                                   latent_condition=latent_condition)
+                                   latent_condition=latent_condition, image_embeds=image_embeds)
         _emit(progress_callback, 0.92, "Denoising complete")
         if return_latents:
             _emit(progress_callback, 1.0, "Returning latents")

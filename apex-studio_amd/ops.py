@@ -630,7 +630,38 @@ def attention_prepared(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: 
     return out
 
 
-_DT = {torch.bfloat16: _l.BF16, torch.float16: _l.F16, torch.float32: _l.F32}
+def attention_prepared_dual(q: torch.Tensor, k_t: torch.Tensor, vt_t: torch.Tensor, Sk_t: int,
+                            k_i: Optional[torch.Tensor], vt_i: Optional[torch.Tensor], Sk_i: int, out: torch.Tensor,
+                            scale: Optional[float] = None) -> torch.Tensor:
+    """Two-context cross-attention in one launch: out = bf16(bf16(attn(q, text)) + bf16(attn(q, image))), each key set with its
+    own softmax.  Operands as attention_prepared: q [B,H,Sq,128], k_* [B,H,>=Sk_*,128], vt_* [B,H,128,Skp_*] zero padded;
+    out [B,Sq,H,128] (strided ok).  Sk_i = 0 (k_i / vt_i may be None) is the text attention alone."""
+    _req_act(q, "attention_dual.q")
+    if q.dtype != torch.bfloat16:
+        raise _l.ApexMIError("attention_prepared_dual: bf16 operands only (the f32-storage verification mode has no dual "
+                             "cross-attention)")
+    B, H, Sq, D = q.shape
+    assert D == 128 and q.is_contiguous() and out.shape == (B, Sq, H, D) and out.stride(3) == 1
+    _req(out, torch.bfloat16, "attention_dual.out")
+    ops_ = [(k_t, vt_t, Sk_t)] + ([(k_i, vt_i, Sk_i)] if Sk_i else [])
+    for k_, vt_, sk in ops_:
+        _req(k_, torch.bfloat16, "attention_dual.k")
+        _req(vt_, torch.bfloat16, "attention_dual.vt")
+        assert k_.is_contiguous() and vt_.is_contiguous() and k_.shape[:2] == (B, H) and k_.shape[3] == D
+        assert vt_.shape[:3] == (B, H, D) and vt_.shape[3] >= (sk + 63) // 64 * 64
+        # the kernel addresses head (b, h) at (b H + h) Sk rows: k must hold exactly Sk rows per head
+        assert k_.shape[2] == sk, f"attention_prepared_dual: k has {k_.shape[2]} rows per head, Sk = {sk}"
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    rc = _l.load().apexmi_attn_fwd_prepared_dual(
+        q.data_ptr(), k_t.data_ptr(), vt_t.data_ptr(), int(Sk_t), vt_t.shape[3],
+        _ptr(k_i) if Sk_i else None, _ptr(vt_i) if Sk_i else None, int(Sk_i), vt_i.shape[3] if Sk_i else 0,
+        out.data_ptr(), B, H, Sq, _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), float(scale), _stream())
+    _l.check(rc, "attn_fwd_prepared_dual")
+    return out
+
+
+_DT ={torch.bfloat16: _l.BF16, torch.float16: _l.F16, torch.float32: _l.F32}
 _ws_cache: dict = {}
 
 

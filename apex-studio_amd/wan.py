@@ -11,8 +11,15 @@ Per block (reference model.py:1101-1333 + attention.py:305-413), as libapex_mi35
   -> qkv_prepare (RoPE + attention layout + V^T) -> attention -> out-proj gemm (gate * y + residual)
   -> affine LayerNorm -> q gemm + RMSNorm | text k,v gemm + RMSNorm -> prepare x2 -> cross attention
   -> out-proj gemm (+ residual) -> ln_modulate -> FFN-up gemm (+GELU) -> FFN-down gemm (gate + residual)
-Image-conditioning branches (`added_kv_proj_dim`, IP adapter) are outside the text-to-video scope and
-raise NotImplementedError.
+
+Image conditioning (Wan-2.1 I2V / FLF2V: `image_dim`, `added_kv_proj_dim`, optional `pos_embed_seq_len`; diffusers
+WanImageEmbedding / WanAttnProcessor with add_k_proj, which the reference's base model mirrors: model.py:207, 391-394):
+`forward(..., encoder_hidden_states_image [B, 257 n, image_dim])` runs the image embedder once per call
+(+pos_embed -> affine LayerNorm -> Linear + erf GELU -> Linear -> affine LayerNorm), and each block's cross-attention adds
+  fused image k|v gemm -> RMSNorm (norm_added_k) on k -> prepare -> ONE two-context attention launch
+  (apexmi_attn_fwd_prepared_dual: text and image keys in separate softmaxes, bf16 branch results added in bf16)
+in place of the single text attention.  Without image input (or without `added_kv_proj_dim`) the text-only path runs the
+same launches as before.  The IP adapter and `use_enhance` raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -50,13 +57,36 @@ class _AffineNorm(nn.Module):
 
 
 class _WanBlock(nn.Module):
-    def __init__(self, dim: int, ffn_dim: int, heads: int, cross_attn_norm: bool, **kw):
+    def __init__(self, dim: int, ffn_dim: int, heads: int, cross_attn_norm: bool, added_kv_proj_dim: Optional[int] = None,
+                 **kw):
         super().__init__()
         self.attn1 = _WanAttn(dim, heads, **kw)
         self.attn2 = _WanAttn(dim, heads, **kw)
+        if added_kv_proj_dim is not None:   # image branch of the cross-attention (diffusers WanAttention, added_kv_proj_dim)
+            self.attn2.add_k_proj = _Linear(added_kv_proj_dim, dim, **kw)
+            self.attn2.add_v_proj = _Linear(added_kv_proj_dim, dim, **kw)
+            self.attn2.norm_added_k = _Norm(dim, **kw)
         self.norm2 = _AffineNorm(dim, **kw) if cross_attn_norm else nn.Identity()
         self.ffn = _FF(dim, ffn_dim, **kw)
         self.scale_shift_table = nn.Parameter(torch.empty(1, 6, dim, **kw), requires_grad=False)
+
+
+class _ImageEmbedder(nn.Module):
+    """diffusers WanImageEmbedding: FP32LayerNorm (affine, eps 1e-5) -> FeedForward(mult=1, exact GELU) -> FP32LayerNorm; an
+    optional learned position embedding over the FLF2V pair's 2 x 257 tokens."""
+
+    def __init__(self, image_dim: int, dim: int, pos_embed_seq_len: Optional[int], **kw):
+        super().__init__()
+        self.norm1 = _AffineNorm(image_dim, **kw)
+        self.ff = nn.Module()
+        proj = nn.Module()
+        proj.proj = _Linear(image_dim, image_dim, **kw)
+        self.ff.net = nn.ModuleList([proj, nn.Identity(), _Linear(image_dim, dim, **kw)])
+        self.norm2 = _AffineNorm(dim, **kw)
+        if pos_embed_seq_len is not None:
+            self.pos_embed = nn.Parameter(torch.zeros(1, pos_embed_seq_len, image_dim, **kw), requires_grad=False)
+        else:
+            self.pos_embed = None
 
 
 class _TimeEmb(nn.Module):
@@ -66,11 +96,14 @@ class _TimeEmb(nn.Module):
 
 
 class _Cond(nn.Module):
-    def __init__(self, dim: int, freq_dim: int, proj_dim: int, text_dim: int, **kw):
+    def __init__(self, dim: int, freq_dim: int, proj_dim: int, text_dim: int, image_dim: Optional[int] = None,
+                 pos_embed_seq_len: Optional[int] = None, **kw):
         super().__init__()
         self.time_embedder = _TimeEmb(freq_dim, dim, **kw)
         self.time_proj = _Linear(dim, proj_dim, **kw)
         self.text_embedder = _TimeEmb(text_dim, dim, **kw)
+        if image_dim is not None:
+            self.image_embedder = _ImageEmbedder(image_dim, dim, pos_embed_seq_len, **kw)
 
 
 class _Conv3dParams(nn.Module):
@@ -95,9 +128,18 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         super().__init__()
         if attention_head_dim != 128:
             raise _l.ApexMIError("wan.mi355: attention_head_dim must be 128 (MFMA attention tile)")
-        if image_dim is not None or added_kv_proj_dim is not None or ip_adapter or use_enhance:
-            raise NotImplementedError("wan.mi355: image conditioning / IP adapter / enhance are outside the "
-                                      "text-to-video hot-path scope")
+        if ip_adapter or use_enhance:
+            raise NotImplementedError("wan.mi355: IP adapter / enhance are outside the hot-path scope")
+        if image_dim is not None and added_kv_proj_dim is None:
+            raise NotImplementedError("wan.mi355: image_dim without added_kv_proj_dim (image tokens that no cross-attention "
+                                      "reads) is not a Wan image-to-video configuration")
+        if added_kv_proj_dim is not None and image_dim is None:
+            raise ValueError("wan.mi355: added_kv_proj_dim needs image_dim (the image embedder feeds add_k_proj / add_v_proj)")
+        if image_dim is not None and image_dim % 64:
+            raise ValueError(f"wan.mi355: image_dim={image_dim} must be a multiple of 64 (the image embedder's GEMM K)")
+        if added_kv_proj_dim is not None and added_kv_proj_dim != num_attention_heads * attention_head_dim:
+            raise ValueError(f"wan.mi355: added_kv_proj_dim={added_kv_proj_dim} must equal the model width "
+                             f"{num_attention_heads * attention_head_dim} (the image embedder's output)")
         if qk_norm != "rms_norm_across_heads":
             raise NotImplementedError(f"wan.mi355: qk_norm={qk_norm!r}")
         self.config = _Config(patch_size=tuple(patch_size), num_attention_heads=num_attention_heads,
@@ -105,12 +147,12 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
                               out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim,
                               num_layers=num_layers, cross_attn_norm=cross_attn_norm, qk_norm=qk_norm, eps=eps,
                               image_dim=image_dim, added_kv_proj_dim=added_kv_proj_dim,
-                              rope_max_seq_len=rope_max_seq_len)
+                              rope_max_seq_len=rope_max_seq_len, pos_embed_seq_len=pos_embed_seq_len)
         kw = dict(device=device, dtype=dtype)
         self.inner_dim = dim = num_attention_heads * attention_head_dim
         self.patch_embedding = _Conv3dParams(in_channels, dim, tuple(patch_size), **kw)
-        self.condition_embedder = _Cond(dim, freq_dim, dim * 6, text_dim, **kw)
-        self.blocks = nn.ModuleList([_WanBlock(dim, ffn_dim, num_attention_heads, cross_attn_norm, **kw)
+        self.condition_embedder = _Cond(dim, freq_dim, dim * 6, text_dim, image_dim, pos_embed_seq_len, **kw)
+        self.blocks = nn.ModuleList([_WanBlock(dim, ffn_dim, num_attention_heads, cross_attn_norm, added_kv_proj_dim, **kw)
                                      for _ in range(num_layers)])
         self.proj_out = _Linear(dim, out_channels * math.prod(patch_size), **kw)
         self.scale_shift_table = nn.Parameter(torch.empty(1, 2, dim, **kw), requires_grad=False)
@@ -197,7 +239,7 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         g = torch.Generator(device=self.device)
         g.manual_seed(seed)
         for name, p in self.named_parameters():
-            if name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight")):
+            if name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight", "norm1.weight", "norm_added_k.weight")):
                 p.data.fill_(1.0)
             elif name.endswith("scale_shift_table"):
                 p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) / p.shape[-1] ** 0.5).to(p.dtype))
@@ -235,6 +277,11 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             blk._bkv2 = torch.empty(2 * dim, device=dev, dtype=dt)
             _repoint([a2.to_k.weight, a2.to_v.weight], blk._wkv2)
             _repoint([a2.to_k.bias, a2.to_v.bias], blk._bkv2)
+            if hasattr(a2, "add_k_proj"):      # image k|v, packed like _wkv2
+                blk._wkvi = torch.empty(2 * dim, a2.add_k_proj.in_features, device=dev, dtype=dt)
+                blk._bkvi = torch.empty(2 * dim, device=dev, dtype=dt)
+                _repoint([a2.add_k_proj.weight, a2.add_v_proj.weight], blk._wkvi)
+                _repoint([a2.add_k_proj.bias, a2.add_v_proj.bias], blk._bkvi)
         self._ones = torch.ones(dim, device=dev, dtype=torch.float32)
         self._packed = True
         self._weights_changed()
@@ -244,8 +291,8 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
     def _fp8_resident_key(key: str) -> bool:
         """Which fp8-scaled checkpoint tensors `weights.load_checkpoint_into(keep_fp8=True)` keeps as float8 + scale: the
         Linear weights of the blocks (attention projections and FFN: 99 % of an expert's bytes).  The embedders feed GEMVs and the
-        modulation tables are f32 copies: those stay dequantised."""
-        return key.startswith("blocks.") and key.endswith(".weight") and ".norm" not in key
+        modulation tables are f32 copies: those stay dequantised.  The image branch's add_k_proj / add_v_proj stay bf16."""
+        return key.startswith("blocks.") and key.endswith(".weight") and ".norm" not in key and ".add_" not in key
 
     @torch.no_grad()
     def _fp8_adopt(self):
@@ -337,8 +384,8 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         kp = (w.shape[1] + 63) // 64 * 64
         self._pe_w = w if kp == w.shape[1] else torch.cat([w, w.new_zeros(dim, kp - w.shape[1])], dim=1).contiguous()
 
-    def _workspace(self, S: int, s_txt: int):
-        key = (S, s_txt)
+    def _workspace(self, S: int, s_txt: int, s_img: int = 0):
+        key = (S, s_txt, s_img)
         ws = self._ws.get(key)
         if ws is not None:
             return ws
@@ -362,6 +409,12 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             VT2=torch.zeros(1, H, 128, tkp, **bf),
             MOD=torch.empty(max(len(self.blocks), 1), 6 * dim, **f32), MOD2=torch.empty(1, 2 * dim, **f32),
             TEMB=torch.empty(1, dim, **f32), TPROJ=torch.empty(1, 6 * dim, **f32))
+        if s_img:           # image branch of the cross-attention: embedded image tokens, their k|v, prepared k and V^T
+            ikp = (s_img + 63) // 64 * 64
+            ws.IMG = torch.empty(s_img, dim, **bf)
+            ws.KVI = torch.empty(s_img, 2 * dim, **bf)
+            ws.KI = torch.empty(1, H, s_img, 128, **bf)
+            ws.VTI = torch.zeros(1, H, 128, ikp, **bf)
         self._ws = {key: ws}
         return ws
 
@@ -379,8 +432,18 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             self._rope = {grid: t}
         return t
 
+    def _embed_image(self, img: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """condition_embedder.image_embedder on one sample's image tokens [s_img, image_dim] (storage dtype) -> out [s_img, dim]."""
+        ie = self.condition_embedder.image_embedder
+        if ie.pos_embed is not None:
+            img = ops.add(img.contiguous(), ie.pos_embed[0].to(img.dtype).contiguous())
+        h = ops.ln_modulate(img, gamma=ie.norm1.weight, beta=ie.norm1.bias, eps=1e-5)
+        h = ops.gemm(h, ie.ff.net[0].proj.weight, ie.ff.net[0].proj.bias, epilogue="gelu_erf")
+        h = ops.gemm(h, ie.ff.net[2].weight, ie.ff.net[2].bias)
+        return ops.ln_modulate(h, gamma=ie.norm2.weight, beta=ie.norm2.bias, eps=1e-5, out=out)
+
     @torch.no_grad()
-    def _forward_one(self, hidden_states, timestep, text):
+    def _forward_one(self, hidden_states, timestep, text, image=None):
         cfg = self.config
         dim, H = self.inner_dim, cfg.num_attention_heads
         C, T, Hh, Ww = hidden_states.shape
@@ -388,7 +451,8 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         grid = (T // pt, Hh // ph, Ww // pw)
         S = grid[0] * grid[1] * grid[2]
         s_txt = text.shape[0]
-        ws = self._workspace(S, s_txt)
+        s_img = 0 if image is None else image.shape[0]
+        ws = self._workspace(S, s_txt, s_img)
         X, XN, QKV, ATT, FFH = ws.X, ws.XN, ws.QKV, ws.ATT, ws.FFH
         eps = cfg.eps
 
@@ -408,6 +472,8 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         ops.gemm(text, ce.text_embedder.linear_1.weight, ce.text_embedder.linear_1.bias, out=ws.CTXH,
                  epilogue="gelu")
         ops.gemm(ws.CTXH, ce.text_embedder.linear_2.weight, ce.text_embedder.linear_2.bias, out=ws.CTX)
+        if s_img:
+            self._embed_image(image, ws.IMG)
         if len(self.blocks):
             ops.add_bcast(self._sst, ws.TPROJ[0], out=ws.MOD)    # scale_shift_table + temb.float()
         ops.add_bcast(self._sst_out.reshape(1, -1), torch.cat([ws.TEMB[0], ws.TEMB[0]]), out=ws.MOD2)
@@ -451,7 +517,13 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             if not fuse:
                 ops.qkv_prepare(q_in, None, None, H, ws.Q[0], None, None)
             ops.qkv_prepare(ws.KV2[:, :dim], None, ws.KV2[:, dim:], H, ws.K2[0], None, ws.VT2[0])
-            ops.attention_prepared(ws.Q, ws.K2, ws.VT2, att_v, s_txt)
+            if s_img:      # image keys: add_k|v gemm, RMSNorm over all heads on k, prepare, then one two-context launch
+                ops.gemm(ws.IMG, blk._wkvi, blk._bkvi, out=ws.KVI)
+                ops.ln_modulate(ws.KVI[:, :dim], gamma=a2.norm_added_k.weight, out=ws.KVI[:, :dim], eps=eps, rms=True)
+                ops.qkv_prepare(ws.KVI[:, :dim], None, ws.KVI[:, dim:], H, ws.KI[0], None, ws.VTI[0])
+                ops.attention_prepared_dual(ws.Q, ws.K2, ws.VT2, s_txt, ws.KI, ws.VTI, s_img, att_v)
+            else:
+                ops.attention_prepared(ws.Q, ws.K2, ws.VT2, att_v, s_txt)
             ops.gemm(ATT, a2.to_out[0].weight, a2.to_out[0].bias, out=X, epilogue="gate_res", gate=self._ones,
                      residual=X, lora_buf=ws.ATTf)
             # 3. feed-forward
@@ -466,21 +538,40 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         out = out.reshape(grid[0], grid[1], grid[2], pt, ph, pw, -1).permute(6, 0, 3, 1, 4, 2, 5)
         return out.reshape(-1, T, Hh, Ww)
 
+    def _image_tokens(self, image: torch.Tensor, batch: int) -> torch.Tensor:
+        """encoder_hidden_states_image [B, 257 n, image_dim] -> [B, s_img, image_dim] in the storage dtype.  With pos_embed (FLF2V)
+        the tokens are viewed as rows of pos_embed_seq_len first (diffusers WanImageEmbedding: the pair's 2 x 257 tokens as 514)."""
+        if self.storage_dtype != torch.bfloat16:
+            raise NotImplementedError("wan.mi355: the f32-storage verification mode has no image-conditioned cross-attention; "
+                                      "run the image branch with bfloat16 storage")
+        cfg = self.config
+        if image.dim() != 3 or image.shape[-1] != cfg.image_dim:
+            raise ValueError(f"wan.mi355: encoder_hidden_states_image must be [B, tokens, {cfg.image_dim}], got {tuple(image.shape)}")
+        if cfg.pos_embed_seq_len is not None:
+            image = image.reshape(-1, cfg.pos_embed_seq_len, cfg.image_dim)
+        if image.shape[0] != batch:
+            raise ValueError(f"wan.mi355: {image.shape[0]} image-token rows for a batch of {batch}")
+        return image.to(self.device, self.storage_dtype)
+
     @ops.on_model_device
     @torch.no_grad()
     def forward(self, hidden_states: torch.Tensor, timestep: torch.Tensor = None,
                 encoder_hidden_states: torch.Tensor = None, encoder_hidden_states_image=None,
                 ip_image_hidden_states=None, return_dict: bool = True, attention_kwargs=None,
                 enhance_kwargs=None, rope_on_cpu=None):
-        if encoder_hidden_states_image is not None or ip_image_hidden_states is not None:
-            raise NotImplementedError("wan.mi355: image conditioning is outside the text-to-video scope")
+        if ip_image_hidden_states is not None:
+            raise NotImplementedError("wan.mi355: the IP adapter is outside the hot-path scope")
         if timestep.ndim != 1:
             raise NotImplementedError("wan.mi355: per-token timesteps are not supported")
         self.pack()
         enc = encoder_hidden_states.to(self.storage_dtype)
+        img = None
+        if encoder_hidden_states_image is not None and self.config.added_kv_proj_dim is not None:
+            img = self._image_tokens(encoder_hidden_states_image, hidden_states.shape[0])
 
         def run():
-            return torch.stack([self._forward_one(hidden_states[b], timestep[b:b + 1], enc[b].contiguous())
+            return torch.stack([self._forward_one(hidden_states[b], timestep[b:b + 1], enc[b].contiguous(),
+                                                  None if img is None else img[b].contiguous())
                                 for b in range(hidden_states.shape[0])], dim=0)
         ec = getattr(self, "_easy_cache", None)
         if ec is not None:       # EasyCache: this call may be served from the cache; float32 out, as the reference returns

@@ -140,6 +140,17 @@ int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* ou
                            int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
                            apexmi_stream_t stream);
 
+/* Two-context cross-attention on prepared operands (bf16, D = 128): the image branch of Wan-2.1 I2V / FLF2V cross-attention,
+ * replacing the reference's two attention calls and their sum (R/src/transformer/wan/base/model.py:207, 391-394; diffusers
+ * WanAttnProcessor with add_k_proj).  The query attends the text keys and the image keys in two separate softmaxes:
+ *   out = bf16( bf16(softmax(q k_t^T scale) v_t) + bf16(softmax(q k_i^T scale) v_i) )
+ * in ONE launch (the query block is read once, one store).  Operands as apexmi_attn_fwd_prepared: q [B,H,Sq,128], k_* [B,H,Sk_*,128],
+ * vt_* [B,H,128,Skp_*] zero padded (Skp_* >= Sk_* rounded up to 64); out [B,Sq,H,128] with element strides o_strides (b, s, h).
+ * Sk_t >= 1; Sk_i >= 0 (0: the text attention alone, k_i / vt_i may be NULL). */
+int apexmi_attn_fwd_prepared_dual(const void* q, const void* k_t, const void* vt_t, int Sk_t, int Skp_t, const void* k_i,
+                                  const void* vt_i, int Sk_i, int Skp_i, void* out, int B, int H, int Sq,
+                                  const int64_t o_strides[3], float softmax_scale, apexmi_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Linear layers.  Replace torch.nn.Linear on the denoise path
  * (to_q/to_k/to_v/to_out, ff.net.0.proj/net.2, proj_mlp/proj_out:
