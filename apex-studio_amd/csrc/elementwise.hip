@@ -25,9 +25,9 @@ APEXMI_DEVICE float block_sum_256(float x, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
-template <typename T, int NIT>
+template <typename T, int NIT, typename TO = T>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(
-    const T* __restrict__ x, int64_t ldx, T* __restrict__ out, int64_t ldo, int M, int C,
+    const T* __restrict__ x, int64_t ldx, TO* __restrict__ out, int64_t ldo, int M, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2) {
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(
         }
     }
     const float rstd = rsqrtf(block_sum_256(sq, red) / (float)C + eps);
-    T* op = out + (int64_t)row * ldo;
+    TO* op = out + (int64_t)row * ldo;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
         const int c = it * 256 + threadIdx.x;
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(
                     y[j + 4] += s1[j];
                 }
             }
-            store8<T>(op + c * 8, y);
+            store8<TO>(op + c * 8, y);
         }
     }
 }
@@ -114,9 +114,11 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(
 // Wave-per-row variant for C = 64 * 8 * NCH (3072, 3584, 5120): a lane owns NCH 16-byte chunks, the two
 // statistics are wave reductions (no LDS, no barrier), four rows per workgroup.  Same arithmetic order per lane
 // as the block kernel's per-thread part; the cross-lane sums differ in shape, both are f32.
-template <typename T, int NCH, int NR>
+// TO = the type of `out`: T, or bf16 for a float x (the f32 residual stream, apexmi_ln_modulate2_f32in): a lane reads its
+// 8 columns as two 16-byte loads and stores them as ONE 16-byte bf16 group, rounded once; the row never leaves registers.
+template <typename T, int NCH, int NR, typename TO = T>
 __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
-    const T* __restrict__ x, int64_t ldx, T* __restrict__ out, int64_t ldo, int M, int C,
+    const T* __restrict__ x, int64_t ldx, TO* __restrict__ out, int64_t ldo, int M, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2) {
@@ -155,7 +157,7 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
                 sq += d * d;
             }
         const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-        T* op = out + (int64_t)row * ldo;
+        TO* op = out + (int64_t)row * ldo;
 #pragma unroll
         for (int it = 0; it < NCH; ++it) {
             const int c = it * 64 + lane;
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
                     y[j + 4] += s1[j];
                 }
             }
-            store8<T>(op + c * 8, y);
+            store8<TO>(op + c * 8, y);
         }
     }
 }
@@ -999,7 +1001,7 @@ extern "C" int apexmi_ln_modulate(const void* x, int64_t ldx, void* out, int64_t
 int g_ln_wave = 1;  // apexmi_tune_set("ln.wave", 0/1): wave-per-row kernel for C in {3072, 3584, 5120}
 void apexmi_set_ln_wave(int v) { g_ln_wave = v; }
 
-template <typename T>
+template <typename T, typename TO = T>
 static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
                              const float* scale, const float* shift, const void* gamma,
                              const void* beta, float eps, int rms, int split,
@@ -1012,14 +1014,14 @@ static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo,
     APEXMI_REQUIRE(M > 0 && C > 0, "ln_modulate: empty problem");
     APEXMI_REQUIRE(C % 8 == 0 && C <= LN_MAX_C, "ln_modulate: C=%d must be a multiple of 8 and <= %d", C,
                    LN_MAX_C);
-    APEXMI_REQUIRE(ldx % (16 / (int)sizeof(T)) == 0 && ldo % (16 / (int)sizeof(T)) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0,
+    APEXMI_REQUIRE(ldx % (16 / (int)sizeof(T)) == 0 && ldo % (16 / (int)sizeof(TO)) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)out % 16) == 0,
                    "ln_modulate: rows must be 16-byte aligned");
     APEXMI_REQUIRE((!scale || ((uintptr_t)scale % 16) == 0) && (!shift || ((uintptr_t)shift % 16) == 0),
                    "ln_modulate: scale/shift must be 16-byte aligned");
-    ApexmiProfScope prof(3, stream, 0.0, 2.0 * sizeof(T) * (double)M * C);
+    ApexmiProfScope prof(3, stream, 0.0, (double)(sizeof(T) + sizeof(TO)) * (double)M * C);
 #define LNW_LAUNCH_R(N, R)                                                                                          \
-    hipLaunchKernelGGL((ln_modulate_wave_kernel<T, N, R>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, (const T*)x, ldx, \
-                       (T*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms, \
+    hipLaunchKernelGGL((ln_modulate_wave_kernel<T, N, R, TO>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, (const T*)x, ldx, \
+                       (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms, \
                        split, scale2, shift2)
 #define LNW_LAUNCH(N)                         \
     do {                                      \
@@ -1042,8 +1044,8 @@ static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo,
 #undef LNW_LAUNCH
     const int nit = (C / 8 + 255) / 256;
 #define LN_LAUNCH(N)                                                                                  \
-    hipLaunchKernelGGL((ln_modulate_kernel<T, N>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx,   \
-                       (T*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                   \
+    hipLaunchKernelGGL((ln_modulate_kernel<T, N, TO>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx, \
+                       (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                   \
                        (const bf16_t*)beta, eps, rms, split, scale2, shift2)
     if (nit <= 1) LN_LAUNCH(1);
     else if (nit <= 2) LN_LAUNCH(2);
@@ -1066,6 +1068,21 @@ extern "C" int apexmi_ln_modulate2_f32(const void* x, int64_t ldx, void* out, in
                                        const void* beta, float eps, int rms, int split,
                                        const float* scale2, const float* shift2, apexmi_stream_t stream_) {
     return ln_modulate2_impl<float>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2, stream_);
+}
+
+// f32 residual stream: x is float (ldx in floats), out is bf16 (ldo in bf16 elements) -- the norm that makes the bf16 GEMM
+// operand from a float X.  Statistics and the modulation in f32, ONE rounding, at the store.
+extern "C" int apexmi_ln_modulate2_f32in(const float* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
+                                         const float* scale, const float* shift, const void* gamma,
+                                         const void* beta, float eps, int rms, int split,
+                                         const float* scale2, const float* shift2, apexmi_stream_t stream_) {
+    return ln_modulate2_impl<float, bf16_t>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2, stream_);
+}
+
+extern "C" int apexmi_ln_modulate_f32in(const float* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
+                                        const float* scale, const float* shift, const void* gamma,
+                                        const void* beta, float eps, int rms, apexmi_stream_t stream_) {
+    return apexmi_ln_modulate2_f32in(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, 0, nullptr, nullptr, stream_);
 }
 
 template <typename T>

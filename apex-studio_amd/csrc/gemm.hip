@@ -333,27 +333,44 @@ APEXMI_DEVICE void store_slab16(const f32x4_t (&x)[MT], const f32x4_t (&y)[MT], 
     if (EPI == APEXMI_EPI_BIAS_F32 || EPI == EPI_GATE_RES_F32) {  // float C / R: 4 consecutive columns per tile, no exchange
         float* Cf = (float*)P.C;
         const float* Rf = (const float*)P.R;
+        // residual rows of up to four m-tiles are loaded BEFORE the first of their stores, on clamped addresses (C may alias R, so
+        // the compiler cannot hoist them itself: one memory round trip per four m-tiles instead of one per 16-byte group) -- this
+        // epilogue is on the step's path with a float residual stream, not only in the verification mode
+        constexpr int CH = MT < 4 ? MT : 4;
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
+        for (int m0 = 0; m0 < MT; m0 += CH) {
+            f32x4 rr[CH][2];
+            if (EPI == EPI_GATE_RES_F32) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int n = nbase + 16 * t + 4 * g;
-                const f32x4_t& a = t ? y[mt] : x[mt];
-                if (m[mt] >= 0 && n < N) {
-                    float o[4];
+                for (int c = 0; c < CH; ++c)
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        o[j] = a[j] + bs[t][j];
-                        o[j] = act_c<ACT>(o[j]);
-                    }
-                    if (EPI == EPI_GATE_RES_F32) {
-                        const f32x4 r = *(const f32x4*)(Rf + (int64_t)m[mt] * P.ldr + n);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) o[j] = r[j] + gt[t][j] * o[j];
-                    }
-                    *(f32x4*)(Cf + (int64_t)m[mt] * P.ldc + n) = f32x4{o[0], o[1], o[2], o[3]};
-                }
+                    for (int t = 0; t < 2; ++t)
+                        if (m0 + c < MT)
+                            rr[c][t] = *(const f32x4*)(Rf + (int64_t)max(m[m0 + c < MT ? m0 + c : 0], 0) * P.ldr + min(nbase + 16 * t + 4 * g, N - 4));
             }
+#pragma unroll
+            for (int c = 0; c < CH; ++c)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    if (m0 + c >= MT) continue;
+                    const int mt = m0 + c < MT ? m0 + c : 0;
+                    const int n = nbase + 16 * t + 4 * g;
+                    const f32x4_t& a = t ? y[mt] : x[mt];
+                    if (m[mt] >= 0 && n < N) {
+                        float o[4];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            o[j] = a[j] + bs[t][j];
+                            o[j] = act_c<ACT>(o[j]);
+                        }
+                        if (EPI == EPI_GATE_RES_F32) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) o[j] = rr[c][t][j] + gt[t][j] * o[j];
+                        }
+                        *(f32x4*)(Cf + (int64_t)m[mt] * P.ldc + n) = f32x4{o[0], o[1], o[2], o[3]};
+                    }
+                }
+        }
         return;
     }
     const int nst = nbase + 16 * (g & 1) + 8 * (g >> 1);  // first of the 8 columns this lane stores
@@ -2203,7 +2220,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
         }
     }
     // ---- epilogue: per 32-column slab and a few m-tiles at a time (the accumulators leave 64 registers for everything else) ----
-    constexpr int MTC = EPI == APEXMI_EPI_BIAS_GATE_RES ? 3 : 6;      // m-tiles per call (gate / residual also holds the residual rows)
+    // m-tiles per call (gate / residual also holds the residual rows: 4 registers per m-tile as bf16, 8 as float -- with 2 the float
+    // class keeps its K-loop free of scratch; its epilogue reloads four spilled address pairs)
+    constexpr int MTC = EPI == APEXMI_EPI_BIAS_GATE_RES ? 3 : EPI == EPI_GATE_RES_F32 ? 2 : 6;
 #pragma unroll
     for (int h = 0; h < 12 / MTC; ++h) {
         int mrow[MTC];
@@ -2413,7 +2432,7 @@ inline bool x288_pays(const GemmGroup& G, const int* Ms) {
     return c288 < 0.95 * c256;
 }
 
-// bf16-epilogue launches only (the float-I/O classes of the verification mode stay on 256 x 256; their sums are the same anyway)
+// bf16-epilogue launches only (the float-I/O classes stay on 256 x 256 here; their sums are the same anyway)
 inline bool use_x288(const GemmGroup& G, const int* Ms) {
     if (g_x288 == 0 || G.batch != 1 || G.K % BK != 0 || !(g_force_cfg == 0 || g_force_cfg == 7) || g_large_cfg != 7) return false;
     int64_t mtot = 0;
@@ -2457,6 +2476,12 @@ int launch_epi(GemmGroup& G, const int* Ms, hipStream_t stream) {
         if (use_x288(G, Ms)) return launch_x288<EPI>(G, Ms, stream);
         if (use_x384(G, Ms)) return launch_x384<EPI>(G, Ms, stream);
     }
+    // float C / R (APEXMI_EPI_F32_IO; unbatched: the batched attention scores stay where they were): the tiling the bf16 launch
+    // of the same problem takes -- the f32 residual stream must not pay for its epilogue with a slower K-loop.  (The
+    // experimental 288 x 192 tiling, `gemm.x288`, has no float epilogue: such a launch runs 256 x 256, bit-identical by design.)
+    if constexpr (EPI == APEXMI_EPI_BIAS_F32 || EPI == EPI_GATE_RES_F32) {
+        if (G.batch == 1 && !use_x288(G, Ms) && use_x384(G, Ms)) return launch_x384<EPI>(G, Ms, stream);
+    }
     if (cfg == 0) {
         int64_t mtot = 0;
         int nmax = 0;
@@ -2472,7 +2497,7 @@ int launch_epi(GemmGroup& G, const int* Ms, hipStream_t stream) {
         // K 15360 295 -> 213 us, 48 tiles K 12288 237 -> 160 us, 96 tiles 238 -> 192 us; 144 tiles 236 vs 342 us: stays).
         // Gate / residual launches only (attention-out, FF-down, proj_out — the part-filled ones of the MM-DiT blocks): the
         // bias-class projections keep the tiling whose sums the fused q/k/v epilogue reproduces bit for bit.
-        if (EPI == APEXMI_EPI_BIAS_GATE_RES && cfg == 7 && G.batch == 1 && g_small_max > 0) {
+        if ((EPI == APEXMI_EPI_BIAS_GATE_RES || EPI == EPI_GATE_RES_F32) && cfg == 7 && G.batch == 1 && g_small_max > 0) {
             int64_t t256 = 0;
             bool any_qkv = false;
             for (int i = 0; i < G.count; ++i) {

@@ -67,9 +67,13 @@ class FluxT2IEngine(EngineLoraMixin):
 
     def __init__(self, transformer, scheduler: Optional[FlowMatchEulerDiscreteScheduler] = None,
                  decode_fn: Optional[Callable[[torch.Tensor], object]] = None, vae_scale_factor: int = 8,
-                 text_encoder=None, text_encoder_2=None):
+                 text_encoder=None, text_encoder_2=None, residual_dtype: Optional[torch.dtype] = None):
         from .prompt import TextEncoder
         self.transformer = transformer
+        # float32: the transformer keeps its residual stream in float (`set_residual_dtype`); None = bf16
+        self.residual_dtype = residual_dtype
+        if residual_dtype is not None:
+            transformer.set_residual_dtype(residual_dtype)
         self.scheduler = scheduler or FlowMatchEulerDiscreteScheduler.flux_dev()
         self.decode_fn = decode_fn
         self.vae_scale_factor = vae_scale_factor

@@ -31,12 +31,18 @@ def _emit(cb, p, msg):
 class WanT2VEngine(EngineLoraMixin):
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
-                 vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None):
+                 vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
+                 residual_dtype: Optional[torch.dtype] = None):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
         self.high_noise_transformer = high_noise_transformer
         self.low_noise_transformer = low_noise_transformer or high_noise_transformer
+        # float32: both experts keep their residual stream in float (`set_residual_dtype`); None = bf16
+        self.residual_dtype = residual_dtype
+        if residual_dtype is not None:
+            for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
+                tr.set_residual_dtype(residual_dtype)
         self.vae = vae
         self.scheduler = scheduler or UniPCMultistepScheduler(shift=3.0)
         self.boundary_ratio = boundary_ratio
@@ -230,9 +236,10 @@ class WanI2VEngine(WanT2VEngine):
 
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
-                 vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None):
+                 vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
+                 residual_dtype: Optional[torch.dtype] = None):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
-                         vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder)
+                         vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype)
         self.image_encoder = image_encoder
 
     @property

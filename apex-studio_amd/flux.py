@@ -248,6 +248,7 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
         self.batch_streams = 2           # images of a batch run side by side on HIP streams (see forward); 1 = sequential
         self._bstreams: List[Any] = []
         self.storage_dtype = torch.bfloat16
+        self.residual_dtype = torch.bfloat16      # set_residual_dtype(float32): X alone in float, everything else bf16
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (see _forward_one; APEX_FLUX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FLUX_FUSE_QKV", "1") != "0"
 
@@ -268,7 +269,23 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
         north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
         if dtype not in (torch.bfloat16, torch.float32):
             raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
+        if dtype == torch.float32 and self.residual_dtype == torch.float32:
+            raise ValueError("a float residual stream is for bfloat16 storage: set_residual_dtype(torch.bfloat16) first")
         self.storage_dtype = dtype
+        self._ws = {}
+        return self
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        """torch.bfloat16 (default) or torch.float32: the F32 RESIDUAL STREAM.  The residual stream X, and only
+        X, is kept in float32: the embedders write it through the GEMM's float epilogue, every gated residual update reads and
+        writes it in float, every norm reads float rows and writes the bf16 GEMM operand (apexmi_ln_modulate2_f32in).  All GEMM
+        and attention operands, and every other buffer, stay bf16 -- the rounding of X after each of its updates is what leaves
+        the bf16 chain.  Not to be combined with `set_storage_dtype(float32)`, which is all-float already."""
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"the residual stream must be bfloat16 or float32, got {dtype}")
+        if dtype == torch.float32 and self.storage_dtype == torch.float32:
+            raise ValueError("storage_dtype=float32 already keeps every buffer in float: a float residual stream is for bfloat16 storage")
+        self.residual_dtype = dtype
         self._ws = {}
         return self
 
@@ -381,8 +398,9 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
         bf = dict(device=dev, dtype=self.storage_dtype)     # activation buffers
         f32 = dict(device=dev, dtype=torch.float32)
         mlp = 4 * dim
+        xdt = torch.float32 if self.residual_dtype == torch.float32 else self.storage_dtype      # the residual stream
         ws = SimpleNamespace(
-            X=torch.empty(S, dim, **bf), XN=torch.empty(S, dim, **bf), QKV=torch.empty(S, 3 * dim, **bf),
+            X=torch.empty(S, dim, device=dev, dtype=xdt), XN=torch.empty(S, dim, **bf), QKV=torch.empty(S, 3 * dim, **bf),
             Q=torch.empty(1, H, S, 128, **bf), K=torch.empty(1, H, S, 128, **bf),
             VT=torch.zeros(1, H, 128, skp, **bf), CAT=torch.empty(S, dim + mlp, **bf),
             FFH=torch.empty(S, mlp, **bf), MOD=torch.empty(1, self._mod_total, **f32),

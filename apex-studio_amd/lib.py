@@ -139,6 +139,8 @@ SIGNATURES = {
 for _name in ("apexmi_ln_modulate2", "apexmi_qkv_prepare", "apexmi_rmsnorm_cl", "apexmi_groupnorm_cl",
               "apexmi_time_interleave_cl", "apexmi_crossfade", "apexmi_frames_to_u8"):
     SIGNATURES[_name + "_f32"] = SIGNATURES[_name]
+SIGNATURES["apexmi_ln_modulate_f32in"] = SIGNATURES["apexmi_ln_modulate"]        # float x -> bf16 out (f32 residual stream)
+SIGNATURES["apexmi_ln_modulate2_f32in"] = SIGNATURES["apexmi_ln_modulate2"]
 SIGNATURES["apexmi_attn_fwd_prepared_f32"] = SIGNATURES["apexmi_attn_fwd_prepared"]
 SIGNATURES["apexmi_split_bf16x3"] = (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int, vp, C.c_int64, vp])
 SIGNATURES["apexmi_conv3d_cl_f32"] = (C.c_int, [vp, vp, vp, vp, vp, vp] + [C.c_int] * 20 + [C.c_float, vp])
@@ -149,7 +151,7 @@ PROF_CLASSES = ("gemm", "attention", "gemv", "ln_modulate", "qkv_prepare", "othe
 BF16, F16, F32 = 0, 1, 2
 MASK_BOOL = 3     # attention mask operand only (apexmi_attn_fwd_masked)
 EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_GATE_RES, EPI_BIAS_F32, EPI_BIAS_GELU_ERF, EPI_BIAS_SILU, EPI_BIAS_QUICK_GELU = 0, 1, 2, 3, 4, 5, 6
-EPI_F32_IO = 0x100   # C and R are float: the f32-storage verification mode
+EPI_F32_IO = 0x100   # C and R are float: the f32 residual stream (plain bf16 A) and the f32-storage verification mode (split A)
 GEMV_PRE_SILU, GEMV_POST_SILU, GEMV_POST_GELU, GEMV_ACCUM = 1, 2, 4, 8
 ROPE_INTERLEAVED, ROPE_COMPLEX, ROPE_NONE = 0, 1, 2
 

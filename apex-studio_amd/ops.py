@@ -255,8 +255,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
          gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
          lora_buf: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  2-D operands, last dim contiguous; a / out / residual bf16, or float32
-    in the f32-storage verification mode (w and bias stay bf16).  `lora_buf`: see _gemm_fp8_lora (ignored unless `w` is a
-    resident-fp8 weight with run-time LoRA factors)."""
+    in the f32-storage verification mode (w and bias stay bf16).  A bf16 `a` with a float32 `out` (and `residual`) is the
+    f32 RESIDUAL STREAM: the same launch with the float epilogue, no split of `a`.  `lora_buf`: see _gemm_fp8_lora (ignored
+    unless `w` is a resident-fp8 weight with run-time LoRA factors)."""
     _req_act(a, "gemm.a")
     f8 = _fp8_of(w)
     if f8 is not None and f8.lora_A is not None:
@@ -271,20 +272,24 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     if out is None:
         out = torch.empty((M, N), dtype=act, device=a.device)
     else:
-        _req(out, act, "gemm.out")
         assert out.shape == (M, N) and out.stride(1) == 1
+    f32_out = act == torch.bfloat16 and out.dtype == torch.float32      # f32 residual stream: bf16 operand, float C / R
+    if not f32_out:
+        _req(out, act, "gemm.out")
     if bias is not None:
         _req(bias, torch.bfloat16, "gemm.bias")
         assert bias.is_contiguous() and bias.numel() == N
     ldr = 0
     if epilogue == "gate_res":
         _req(gate, torch.float32, "gemm.gate")
-        _req(residual, act, "gemm.residual")
+        _req(residual, out.dtype, "gemm.residual")
         assert gate.is_contiguous() and gate.numel() == N
         assert residual.shape == (M, N) and residual.stride(1) == 1
         ldr = residual.stride(0)
     epi = _EPI[epilogue]
-    if act == torch.float32:     # exact bf16 split of the activations against [w | w | w]: same kernel, float epilogue
+    if f32_out:
+        epi |= _l.EPI_F32_IO
+    elif act == torch.float32:     # exact bf16 split of the activations against [w | w | w]: same kernel, float epilogue
         a, w, K, epi = split3(a), _w3(w), 3 * K, epi | _l.EPI_F32_IO
     rc = _l.load().apexmi_gemm_bf16(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _ptr(bias),
                                     out.data_ptr(), out.stride(0), M, N, K, epi,
@@ -318,11 +323,14 @@ def gemm_grouped(a_list, w_list, bias_list, out_list, epilogue="bias", gate_list
                 ws.append(w if f is None else f.dequant(out=buf[off:off + f.shape[0] * f.shape[1]].view(f.shape[0], f.shape[1])))
                 off += n
             w_list = ws
+    # bf16 operands with float outputs (and residuals): the f32 residual stream (see gemm)
+    f32_out = act == torch.bfloat16 and out_list[0].dtype == torch.float32
+    odt = torch.float32 if f32_out else act
     for a, w, o in zip(a_list, w_list, out_list):
         _req_act(a, "gemm_grouped.a")
         _req(a, act, "gemm_grouped.a")
         _req(w, torch.bfloat16, "gemm_grouped.w")
-        _req(o, act, "gemm_grouped.out")
+        _req(o, odt, "gemm_grouped.out")
         assert a.dim() == 2 and a.stride(1) == 1 and w.stride(1) == 1 and o.stride(1) == 1
         assert w.shape[1] == K and a.shape[1] == K and o.shape == (a.shape[0], w.shape[0])
     VP = C.c_void_p * n
@@ -335,9 +343,9 @@ def gemm_grouped(a_list, w_list, bias_list, out_list, epilogue="bias", gate_list
     for e, g, r, o, w in zip(epis, gate_list, residual_list, out_list, w_list):
         if e == "gate_res":
             _req(g, torch.float32, "gemm_grouped.gate")
-            _req(r, act, "gemm_grouped.residual")
+            _req(r, odt, "gemm_grouped.residual")
             assert g.is_contiguous() and g.numel() == w.shape[0] and r.shape == o.shape and r.stride(1) == 1
-    flag = 0
+    flag = _l.EPI_F32_IO if f32_out else 0
     if act == torch.float32:     # f32-storage verification mode (see gemm)
         done: dict = {}
         sp = []
@@ -492,15 +500,18 @@ def ln_modulate(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
                 eps: float = 1e-6, rms: bool = False, split: int = 0,
                 scale2: Optional[torch.Tensor] = None, shift2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = LayerNorm(x) [*gamma + beta] * (1 + scale) + shift, or RMSNorm(x) * gamma.
-    Rows [0, split) use (scale2, shift2) instead (text rows of a joint buffer)."""
+    Rows [0, split) use (scale2, shift2) instead (text rows of a joint buffer).  `out` has x's dtype, or is bf16 for a
+    float32 x (the f32 residual stream feeding a bf16 GEMM operand: apexmi_ln_modulate2_f32in)."""
     _req_act(x, "ln_modulate.x")
     assert x.dim() == 2 and x.stride(1) == 1
     M, Cc = x.shape
     if out is None:
         out = torch.empty((M, Cc), dtype=x.dtype, device=x.device)
     else:
-        _req(out, x.dtype, "ln_modulate.out")
         assert out.shape == (M, Cc) and out.stride(1) == 1
+    f32in = x.dtype == torch.float32 and out.dtype == torch.bfloat16
+    if not f32in:
+        _req(out, x.dtype, "ln_modulate.out")
     for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
         if t is not None:
             _req(t, torch.float32, "ln_modulate." + nm)
@@ -509,9 +520,10 @@ def ln_modulate(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
         if t is not None:
             _req(t, torch.bfloat16, "ln_modulate." + nm)
             assert t.is_contiguous() and t.numel() == Cc
-    rc = _fn("apexmi_ln_modulate2", x)(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, Cc,
-                                        _ptr(scale), _ptr(shift), _ptr(gamma), _ptr(beta), float(eps),
-                                        1 if rms else 0, int(split), _ptr(scale2), _ptr(shift2), _stream())
+    fn = _l.load().apexmi_ln_modulate2_f32in if f32in else _fn("apexmi_ln_modulate2", x)
+    rc = fn(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, Cc,
+            _ptr(scale), _ptr(shift), _ptr(gamma), _ptr(beta), float(eps),
+            1 if rms else 0, int(split), _ptr(scale2), _ptr(shift2), _stream())
     _l.check(rc, "ln_modulate")
     return out
 
@@ -942,8 +954,12 @@ def mul(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) ->
 
 
 def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out = a + b for contiguous tensors of equal shape (bf16; float in the f32-storage mode; numel a multiple of 8)."""
+    """out = a + b for contiguous tensors of equal shape (bf16; float in the f32-storage mode; numel a multiple of 8).
+    A float32 a with a bf16 b (a float residual stream taking a bf16 term) is a + 1.0 * b in f32: the euler_step kernel."""
     _req_act(a, "add.a")
+    if a.dtype == torch.float32 and b.dtype == torch.bfloat16:
+        assert a.shape == b.shape
+        return euler_step(a, b, 1.0, out=out)
     _req(b, a.dtype, "add.b")
     assert a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
     if out is None:

@@ -159,6 +159,7 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         self._packed = False
         self._ws: Dict[Any, Any] = {}
         self.storage_dtype = torch.bfloat16
+        self.residual_dtype = torch.bfloat16      # set_residual_dtype(float32): X alone in float, everything else bf16
         self.fuse_qkv = os.environ.get("APEX_FUSE_QKV", "1") != "0"     # see _forward_one
         self._rope: Dict[Any, torch.Tensor] = {}
 
@@ -179,7 +180,23 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
         if dtype not in (torch.bfloat16, torch.float32):
             raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
+        if dtype == torch.float32 and self.residual_dtype == torch.float32:
+            raise ValueError("a float residual stream is for bfloat16 storage: set_residual_dtype(torch.bfloat16) first")
         self.storage_dtype = dtype
+        self._ws = {}
+        return self
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        """torch.bfloat16 (default) or torch.float32: the F32 RESIDUAL STREAM.  The residual stream X, and only
+        X, is kept in float32: the embedders write it through the GEMM's float epilogue, every gated residual update reads and
+        writes it in float, every norm reads float rows and writes the bf16 GEMM operand (apexmi_ln_modulate2_f32in).  All GEMM
+        and attention operands, and every other buffer, stay bf16 -- the rounding of X after each of its updates is what leaves
+        the bf16 chain.  Not to be combined with `set_storage_dtype(float32)`, which is all-float already."""
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"the residual stream must be bfloat16 or float32, got {dtype}")
+        if dtype == torch.float32 and self.storage_dtype == torch.float32:
+            raise ValueError("storage_dtype=float32 already keeps every buffer in float: a float residual stream is for bfloat16 storage")
+        self.residual_dtype = dtype
         self._ws = {}
         return self
 
@@ -400,8 +417,9 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         pad = int(getattr(self, "_lora_pad", 0))
         XNf, ATTf = torch.empty(S, dim + pad, **bf), torch.empty(S, dim + pad, **bf)
         FFHf, CTXf = torch.empty(S, ffn + pad, **bf), torch.empty(s_txt, dim + pad, **bf)
+        xdt = torch.float32 if self.residual_dtype == torch.float32 else self.storage_dtype      # the residual stream
         ws = SimpleNamespace(
-            X=torch.empty(S, dim, **bf), XN=XNf[:, :dim], QKV=torch.empty(S, 3 * dim, **bf),
+            X=torch.empty(S, dim, device=dev, dtype=xdt), XN=XNf[:, :dim], QKV=torch.empty(S, 3 * dim, **bf),
             Q=torch.empty(1, H, S, 128, **bf), K=torch.empty(1, H, S, 128, **bf),
             VT=torch.zeros(1, H, 128, skp, **bf), ATT=ATTf[:, :dim], FFH=FFHf[:, :ffn],
             CTX=CTXf[:, :dim], CTXH=torch.empty(s_txt, dim, **bf), XNf=XNf, ATTf=ATTf, FFHf=FFHf, CTXf=CTXf,
@@ -504,6 +522,9 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             # 2. cross attention over the text tokens (no RoPE, ungated residual)
             if isinstance(blk.norm2, _AffineNorm):
                 ops.ln_modulate(X, gamma=blk.norm2.weight, beta=blk.norm2.bias, out=XN, eps=eps)
+                src = XN
+            elif X.dtype != XN.dtype:      # float residual stream without norm2: the query projection reads X rounded to bf16
+                XN.copy_(ops.to_bf16(X))
                 src = XN
             else:
                 src = X

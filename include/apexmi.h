@@ -40,10 +40,18 @@ typedef void* apexmi_stream_t; /* a hipStream_t; NULL = the null stream */
 #define APEXMI_EPI_BIAS_SILU 5     /* C = silu(A W^T + b): the "linear-silu" FeedForward of its token refiner        */
 #define APEXMI_EPI_BIAS_F32 3      /* C = A W^T + b stored as float (C is float*, ldc in floats): attention scores */
 
-/* OR-ed into any epilogue above: C and R are float (ldc / ldr in floats).  The f32-STORAGE VERIFICATION MODE (DESIGN.md
- * §1.2): the same kernels and epilogue formulas with no bf16 rounding at the store; the activation operand A is then the
- * exact three-way bf16 split written by apexmi_split_bf16x3 (K-concatenated, W repeated three times along K), so the
- * MFMA products are exact and the whole layer is f32-accurate.  Not a production path: 3x the MFMA work. */
+/* OR-ed into any epilogue above: C and R are float (ldc / ldr in floats, 16-byte aligned), R may alias C; the same kernels and
+ * epilogue formulas with no bf16 rounding at the store.  A and W are bf16 as always, and the flag says nothing about where A came
+ * from.  Two uses:
+ *  - the F32 RESIDUAL STREAM (`set_residual_dtype(float32)` of the Flux / Wan models): A is a plain bf16
+ *    activation and K is the layer's K.  APEXMI_EPI_BIAS | APEXMI_EPI_F32_IO is C = float(A W^T + b) (the embedders writing a
+ *    float X); APEXMI_EPI_BIAS_GATE_RES | APEXMI_EPI_F32_IO is C = R + gate[n] * (A W^T + b) with float C / R (every residual
+ *    update of X).  Same accumulator as the bf16 launch of the same (M, N, K): rounding the float result to bf16 gives the bf16
+ *    launch's result up to the rounding of R itself.  These launches go out on the tiling the bf16 launch of the same problem
+ *    selects (256 x 256, 384 x 256, or 128 x 128 below `gemm.small_max` tiles), single and grouped;
+ *  - the f32-STORAGE VERIFICATION MODE: A is the exact three-way bf16 split written by apexmi_split_bf16x3
+ *    (K-concatenated, W repeated three times along K), so the MFMA products are exact and the whole layer is f32-accurate.
+ *    Not a production path: 3x the MFMA work. */
 #define APEXMI_EPI_F32_IO 0x100
 
 /* GEMV flags */
@@ -305,6 +313,18 @@ int apexmi_ln_modulate2(const void* x, int64_t ldx, void* out, int64_t ldo, int 
                         const float* scale, const float* shift, const void* gamma, const void* beta,
                         float eps, int rms, int split, const float* scale2, const float* shift2,
                         apexmi_stream_t stream);
+
+/* The same two entries reading a FLOAT x (ldx in floats, rows 16-byte aligned) and writing bf16 out: the norm between a float
+ * residual stream X and the bf16 GEMM operand.  Statistics and modulation in f32, ONE rounding, at the store.
+ * One wave per row where C is 3072, 3584 or 5120 (the row stays in registers: two 16-byte loads and one 16-byte store per
+ * 8 columns and lane); a workgroup per row otherwise.  Everything else as apexmi_ln_modulate / apexmi_ln_modulate2. */
+int apexmi_ln_modulate_f32in(const float* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
+                             const float* scale, const float* shift, const void* gamma,
+                             const void* beta, float eps, int rms, apexmi_stream_t stream);
+int apexmi_ln_modulate2_f32in(const float* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
+                              const float* scale, const float* shift, const void* gamma, const void* beta,
+                              float eps, int rms, int split, const float* scale2, const float* shift2,
+                              apexmi_stream_t stream);
 
 /* Wan's q / k preparation in ONE pass (reference transformer/wan/base/attention.py:305-413; InplaceRMSNorm,
  * transformer/efficiency/mod.py:24-35; apply_wan_rope_inplace, transformer/efficiency/ops.py:112-160): RMSNorm over ALL H * 128
