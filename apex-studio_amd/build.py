@@ -15,7 +15,8 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_NAME = "libapex_mi355.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
-SOURCES = ["runtime.hip", "gemm.hip", "attention.hip", "attention_masked.hip", "attention_dual.hip", "elementwise.hip", "conv.hip"]
+SOURCES = ["runtime.hip", "gemm.hip", "attention.hip", "attention_masked.hip", "attention_dual.hip", "elementwise.hip", "dequant_gguf.hip",
+           "conv.hip"]
 ARCH = "gfx950"
 
 

@@ -114,24 +114,15 @@ def _w3(w: torch.Tensor) -> torch.Tensor:
     return hit[1]
 
 
-# ---- fp8-scaled weights RESIDENT in HBM (reference FPScaledLinear, R/src/quantize/scaled_layer.py:390-552) --------------
-class Fp8Weight:
-    """A Linear weight kept as the checkpoint stores it — float8 (e4m3fn / e5m2) [N, K] + `scale_weight` (one value, or one per
-    row) — and dequantised PER CALL into a per-stream bf16 scratch right before the GEMM that reads it, as the reference's
-    `FPScaledLinear.forward` does (`_scale_and_cast_weight`, scaled_layer.py:496-549: `weight.to(bf16) * scale.to(bf16)`, then a
-    bf16 matmul).  Same dequantisation kernel as the load-time path (`apexmi_dequant_fp8_scaled`, every code point pinned by
-    tests/golden/fp_scaled.pt), so a forward is bit-identical to dequantise-at-load; the model holds half the weight bytes."""
+# ---- quantised weights RESIDENT in HBM: fp8-scaled and GGUF blocks (rows 16 / 18) -------------------------------------
+class ResidentWeight:
+    """What a Linear weight that stays quantised in HBM has in common, whatever its format: the [N, K] `shape`, which model Linears
+    its rows belong to (`parts`), `dequant(out=)` into a bf16 operand right before the GEMM that reads it, `nbytes()`, and the
+    RUN-TIME LoRA factors (`set_lora`).  Subclasses: Fp8Weight (float8 + scale), GgufWeight (ggml blocks)."""
 
-    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
-        if q.dtype not in (torch.float8_e4m3fn, torch.float8_e5m2) or q.dim() != 2:
-            raise TypeError(f"Fp8Weight: expected a 2-D float8 tensor, got {q.dtype} {tuple(q.shape)}")
-        self.q = q.contiguous()
-        s = scale.to(q.device).to(torch.bfloat16).reshape(-1).contiguous()
-        if s.numel() not in (1, q.shape[0]):
-            raise ValueError(f"Fp8Weight: scale has {s.numel()} values for {q.shape[0]} rows")
-        self.scale = s
-        self.shape = q.shape
-        self.device = q.device
+    def _init_record(self, shape, device) -> None:
+        self.shape = torch.Size(shape)
+        self.device = device
         # which model Linears the rows belong to: [(module path, first row, rows)] (set by the model that adopts the record)
         self.parts: List[Tuple[str, int, int]] = []
         # RUN-TIME LoRA on a weight whose bf16 form does not exist (set_lora): lora_A [Rp, K] = the active adapters' down factors
@@ -140,24 +131,22 @@ class Fp8Weight:
         self.lora_A: Optional[torch.Tensor] = None
         self.lora_B: Optional[torch.Tensor] = None
 
-    @classmethod
-    def cat(cls, parts: Sequence["Fp8Weight"]) -> "Fp8Weight":
-        """Rows of several weights stacked (a fused q | k | v projection): per-tensor scales become per-row vectors."""
-        if len({p.q.dtype for p in parts}) != 1 or len({p.shape[1] for p in parts}) != 1:
-            raise ValueError("Fp8Weight.cat: parts must share the fp8 format and the input width")
-        q = torch.cat([p.q.view(torch.uint8) for p in parts], dim=0).view(parts[0].q.dtype)
-        s = torch.cat([p.scale if p.scale.numel() == p.shape[0] else p.scale.expand(p.shape[0]) for p in parts])
-        out = cls(q, s)
+    def _cat_parts(self, parts: Sequence["ResidentWeight"]) -> None:
         r0 = 0
         for p in parts:
-            out.parts += [(m, r0 + a, n) for m, a, n in p.parts]
+            self.parts += [(m, r0 + a, n) for m, a, n in p.parts]
             r0 += p.shape[0]
-        return out
+
+    def nbytes(self) -> int:
+        raise NotImplementedError
+
+    def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        raise NotImplementedError
 
     @torch.no_grad()
     def set_lora(self, adapters: Sequence[Tuple[str, torch.Tensor, torch.Tensor, float]]) -> int:
         """`adapters`: (module path, A [r, K], B [rows of that part, r], scale) of every ACTIVE adapter touching this record.
-        The reference keeps fp8-scaled base weights and runs `base(x) + scale * B(A(x))` per Linear at run time (PEFT layers
+        The reference keeps quantised base weights and runs `base(x) + scale * B(A(x))` per Linear at run time (PEFT layers
         around FPScaledLinear, R/src/lora/manager.py:454-606); gemm() below does the same as ONE extra skinny GEMM and a K
         extended by the padded rank (see _gemm_fp8_lora).  Returns the padded rank (0 = no adapter left)."""
         if not adapters:
@@ -172,7 +161,7 @@ class Fp8Weight:
         c = 0
         for m, a, b, sc in adapters:
             if m not in row_of:
-                raise KeyError(f"Fp8Weight.set_lora: '{m}' is not a part of this record ({[p[0] for p in self.parts]})")
+                raise KeyError(f"{type(self).__name__}.set_lora: '{m}' is not a part of this record ({[p[0] for p in self.parts]})")
             r0, n = row_of[m]
             r = int(a.shape[0])
             if tuple(a.shape) != (r, K) or tuple(b.shape) != (n, r):
@@ -183,6 +172,35 @@ class Fp8Weight:
         self.lora_A, self.lora_B = A.to(torch.bfloat16), B.to(torch.bfloat16)
         return Rp
 
+
+class Fp8Weight(ResidentWeight):
+    """A Linear weight kept as the checkpoint stores it — float8 (e4m3fn / e5m2) [N, K] + `scale_weight` (one value, or one per
+    row) — and dequantised PER CALL into a per-stream bf16 scratch right before the GEMM that reads it, as the reference's
+    `FPScaledLinear.forward` does (`_scale_and_cast_weight`, scaled_layer.py:496-549: `weight.to(bf16) * scale.to(bf16)`, then a
+    bf16 matmul).  Same dequantisation kernel as the load-time path (`apexmi_dequant_fp8_scaled`, every code point pinned by
+    tests/golden/fp_scaled.pt), so a forward is bit-identical to dequantise-at-load; the model holds half the weight bytes."""
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dtype not in (torch.float8_e4m3fn, torch.float8_e5m2) or q.dim() != 2:
+            raise TypeError(f"Fp8Weight: expected a 2-D float8 tensor, got {q.dtype} {tuple(q.shape)}")
+        self.q = q.contiguous()
+        s = scale.to(q.device).to(torch.bfloat16).reshape(-1).contiguous()
+        if s.numel() not in (1, q.shape[0]):
+            raise ValueError(f"Fp8Weight: scale has {s.numel()} values for {q.shape[0]} rows")
+        self.scale = s
+        self._init_record(q.shape, q.device)
+
+    @classmethod
+    def cat(cls, parts: Sequence["Fp8Weight"]) -> "Fp8Weight":
+        """Rows of several weights stacked (a fused q | k | v projection): per-tensor scales become per-row vectors."""
+        if len({p.q.dtype for p in parts}) != 1 or len({p.shape[1] for p in parts}) != 1:
+            raise ValueError("Fp8Weight.cat: parts must share the fp8 format and the input width")
+        q = torch.cat([p.q.view(torch.uint8) for p in parts], dim=0).view(parts[0].q.dtype)
+        s = torch.cat([p.scale if p.scale.numel() == p.shape[0] else p.scale.expand(p.shape[0]) for p in parts])
+        out = cls(q, s)
+        out._cat_parts(parts)
+        return out
+
     def nbytes(self) -> int:
         return self.q.numel() + 2 * self.scale.numel()
 
@@ -190,11 +208,53 @@ class Fp8Weight:
         return dequant_fp8_scaled(self.q, self.scale, out=out)
 
 
+class GgufWeight(ResidentWeight):
+    """A Linear weight kept as a GGUF file stores it: ggml blocks, as a list of ROW SEGMENTS (ggml type, rows, uint8 bytes on the
+    device) — a fused projection may mix types (Q4_K_M files store some tensors as Q6_K) — dequantised PER CALL, one
+    `apexmi_dequant_gguf` launch per segment, as the reference's `GGMLLinear.forward` does (R/src/quantize/ggml_layer.py:220).
+    Same kernel as the load-time path, so a forward is bit-identical to dequantise-at-load."""
+
+    def __init__(self, segments: Sequence[Tuple[int, int, torch.Tensor]], K: int):
+        segs = []
+        for t, n, b in segments:
+            if b.dtype != torch.uint8 or not b.is_cuda:
+                raise TypeError(f"GgufWeight: block bytes must be a uint8 device tensor, got {b.dtype} on {b.device}")
+            if segs and segs[-1][0] == t:                       # neighbours of one type: one launch
+                segs[-1] = (t, segs[-1][1] + n, torch.cat([segs[-1][2].reshape(-1), b.reshape(-1)]))
+            else:
+                segs.append((int(t), int(n), b.reshape(-1).contiguous()))
+        self.segments = segs
+        self._init_record((sum(n for _, n, _ in segs), int(K)), segs[0][2].device)
+
+    @classmethod
+    def cat(cls, parts: Sequence["GgufWeight"]) -> "GgufWeight":
+        """Rows of several weights stacked (a fused q | k | v projection)."""
+        if len({p.shape[1] for p in parts}) != 1:
+            raise ValueError("GgufWeight.cat: parts must share the input width")
+        out = cls([seg for p in parts for seg in p.segments], parts[0].shape[1])
+        out._cat_parts(parts)
+        return out
+
+    def nbytes(self) -> int:
+        return sum(b.numel() for _, _, b in self.segments)
+
+    def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        N, K = self.shape
+        if out is None:
+            out = torch.empty((N, K), dtype=torch.bfloat16, device=self.device)
+        r0 = 0
+        for t, n, b in self.segments:
+            dequant_gguf(b, t, (n, K), out=out[r0:r0 + n])
+            r0 += n
+        return out
+
+
 _fp8_scratch: dict = {}
 
 
 def _fp8_of(w):
-    return w if isinstance(w, Fp8Weight) else getattr(w, "_fp8", None)
+    """The resident record behind `w` (an Fp8Weight / GgufWeight, or a parameter carrying one in `_fp8`), or None."""
+    return w if isinstance(w, ResidentWeight) else getattr(w, "_fp8", None)
 
 
 def _scratch(dev, n: int) -> torch.Tensor:
@@ -206,7 +266,7 @@ def _scratch(dev, n: int) -> torch.Tensor:
     return buf
 
 
-def _gemm_fp8_lora(a, f8: "Fp8Weight", bias, out, epilogue, gate, residual, lora_buf):
+def _gemm_fp8_lora(a, f8: "ResidentWeight", bias, out, epilogue, gate, residual, lora_buf):
     """epi(a W^T + (a A^T) B'^T + bias) for a resident-fp8 weight W with run-time LoRA factors, as TWO launches:
          t = a A^T                      [M, Rp] bf16 — the reference's `lora_A(x)` output, rounded as it is there — written into
                                         the columns right behind `a` in its padded buffer (`lora_buf`: same rows, >= K + Rp wide);
@@ -235,7 +295,7 @@ def _bf16_weight(w, float_acts: bool = False):
     """`w` as the bf16 [N, K] operand of a GEMM launched next on the current stream: the tensor itself, or — for an Fp8Weight / a
     parameter carrying one (`param._fp8`, weights.load_checkpoint_into(keep_fp8=True)) — its dequantisation into the stream's
     scratch.  Stream order makes the reuse safe: the next dequantisation is queued behind the GEMM that read the last one."""
-    f8 = w if isinstance(w, Fp8Weight) else getattr(w, "_fp8", None)
+    f8 = _fp8_of(w)
     if f8 is None:
         return w
     if f8.lora_A is not None:
@@ -1082,6 +1142,30 @@ def dequant_fp8_scaled(w: torch.Tensor, scale: torch.Tensor, out: Optional[torch
         assert out.shape == (rows, cols) and out.stride(1) == 1
     _l.check(_l.load().apexmi_dequant_fp8_scaled(w2.data_ptr(), fmt, s.data_ptr(), s.numel(), rows, cols,
                                                  out.data_ptr(), out.stride(0), _stream()), "dequant_fp8_scaled")
+    return out
+
+
+def dequant_gguf(blocks: torch.Tensor, ggml_type: int, shape: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[rows, K] (bf16) = the GGUF block bytes `blocks` (uint8, device) of a weight of `shape` = (rows, ..., K) dequantised by
+    ggml's definition in f32 (gguf_file.dequantize is the bit-exact restatement).  `out` may be a row-range view of a packed weight
+    matrix or of a wider scratch (row stride >= K)."""
+    if blocks.dtype != torch.uint8:
+        raise TypeError(f"dequant_gguf: block bytes must be uint8, got {blocks.dtype}")
+    _req(blocks, torch.uint8, "dequant_gguf.blocks")
+    rows = int(shape[0])
+    K = int(math.prod(int(d) for d in shape[1:])) if len(shape) > 1 else 1
+    b = blocks.reshape(-1).contiguous()
+    from .gguf_file import TYPES
+    if ggml_type in TYPES and rows * K // TYPES[ggml_type][1] * TYPES[ggml_type][2] != b.numel() and K % TYPES[ggml_type][1] == 0:
+        raise _l.ApexMIError(f"dequant_gguf: {b.numel()} bytes do not hold a {tuple(shape)} tensor of ggml type {ggml_type}")
+    if out is None:
+        out = torch.empty((rows, K), dtype=torch.bfloat16, device=blocks.device)
+    else:
+        _req(out, torch.bfloat16, "dequant_gguf.out")
+        if out.dim() != 2 or tuple(out.shape) != (rows, K) or out.stride(1) != 1:
+            raise _l.ApexMIError(f"dequant_gguf.out: expected a [{rows}, {K}] view with contiguous rows, got {tuple(out.shape)}")
+    ldo = out.stride(0) if rows > 1 else max(out.stride(0), K)
+    _l.check(_l.load().apexmi_dequant_gguf(b.data_ptr(), int(ggml_type), rows, K, out.data_ptr(), ldo, _stream()), "dequant_gguf")
     return out
 
 

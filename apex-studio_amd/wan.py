@@ -276,7 +276,8 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         if self._packed:
             return
         if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("wan.mi355: the block weights are resident fp8 (keep_fp8 load) and their bf16 storage is gone; "
+            raise _l.ApexMIError("wan.mi355: the block weights are resident quantised records (keep_fp8 / keep_quantized load) and their "
+                                 "bf16 storage is gone; "
                                  "moving / re-packing such a model is not supported — construct and load again")
         dev, dt = self.device, self.dtype
         if dev.type != "cuda" or dt != torch.bfloat16:
@@ -303,18 +304,19 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         self._packed = True
         self._weights_changed()
 
-    # ---- fp8-scaled expert weights resident in HBM -------------------------------------------------------------
+    # ---- quantised expert weights resident in HBM: fp8-scaled and GGUF blocks.  The `_fp8*` names date from the
+    # first of the two formats; a parameter's `_fp8` slot holds any ops.ResidentWeight --------------------------------------------
     @staticmethod
     def _fp8_resident_key(key: str) -> bool:
-        """Which fp8-scaled checkpoint tensors `weights.load_checkpoint_into(keep_fp8=True)` keeps as float8 + scale: the
+        """Which quantised checkpoint tensors `weights.load_checkpoint_into(keep_fp8=True / keep_quantized=True)` keeps as stored: the
         Linear weights of the blocks (attention projections and FFN: 99 % of an expert's bytes).  The embedders feed GEMVs and the
         modulation tables are f32 copies: those stay dequantised.  The image branch's add_k_proj / add_v_proj stay bf16."""
         return key.startswith("blocks.") and key.endswith(".weight") and ".norm" not in key and ".add_" not in key
 
     @torch.no_grad()
     def _fp8_adopt(self):
-        """After a keep_fp8 load: fused projections become fused `ops.Fp8Weight`s (per-row scales), every adopted parameter's bf16
-        storage is released.  The blocks' GEMMs then dequantise per call (`ops._bf16_weight`)."""
+        """After a keep_fp8 / keep_quantized load: fused projections become fused `ops.Fp8Weight`s (per-row scales) or
+        `ops.GgufWeight`s (row segments), every adopted parameter's bf16 storage is released.  The blocks' GEMMs then dequantise per call (`ops._bf16_weight`)."""
         self.pack()
         dev, dt = self.device, self.dtype
 
@@ -330,8 +332,10 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             if all(f is None for f in f8):
                 return None
             if any(f is None for f in f8):
-                raise _l.ApexMIError("wan.mi355 keep_fp8: a fused projection mixes fp8-scaled and plain weights")
-            return ops.Fp8Weight.cat(f8)
+                raise _l.ApexMIError("wan.mi355 keep_fp8 / keep_quantized: a fused projection mixes quantised and plain weights")
+            if len({type(f) for f in f8}) != 1:
+                raise _l.ApexMIError("wan.mi355: a fused projection mixes fp8-scaled and GGUF-quantised weights")
+            return type(f8[0]).cat(f8)
         n = 0
         self._fp8_records = {}                 # module path -> the record holding its rows
         for blk in self.blocks:
@@ -381,8 +385,9 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
 
     def state_dict(self, *a, **k):
         if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("wan.mi355: this model was loaded with keep_fp8=True — its block weights live as float8 + scale "
-                                 "records (inference only); it has no bf16 state dict to save.  Load without keep_fp8 to serialise.")
+            raise _l.ApexMIError("wan.mi355: this model was loaded with keep_fp8=True / keep_quantized=True — its block weights live as "
+                                 "quantised records (inference only); it has no bf16 state dict to save.  Load without keep_fp8 / "
+                                 "keep_quantized to serialise.")
         return super().state_dict(*a, **k)
 
     @torch.no_grad()

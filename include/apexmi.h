@@ -561,6 +561,17 @@ int apexmi_cast_bf16_to_f32(const void* x, float* out, int64_t n, apexmi_stream_
 int apexmi_dequant_fp8_scaled(const void* w, int format, const void* scale, int64_t scale_count, int64_t rows,
                               int64_t cols, void* out, int64_t ldo, apexmi_stream_t stream);
 
+/* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
+ * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
+ * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
+ * elements) = ggml's dequantize_row_* formula in IEEE float32, every multiply / add / subtract rounded separately (no FMA),
+ * rounded once to bf16 — a pure function of the bytes.  ggml_type: F32 0, F16 1, Q4_0 2, Q4_1 3, Q5_0 6, Q5_1 7, Q8_0 8,
+ * Q4_K 12, Q5_K 13, Q6_K 14, BF16 30; any other id is an error.  K must be a multiple of the block length (32; 256 for the
+ * K-quants; 1 for the float types); the quantised types need a 16-byte aligned `out` and ldo % 8 == 0.  The output is always bf16:
+ * weights are bf16 in the f32-storage verification mode too, so there is no float variant.  No workspace. */
+int apexmi_dequant_gguf(const void* blocks, int ggml_type, int64_t rows, int64_t K, void* out, int64_t ldo,
+                        apexmi_stream_t stream);
+
 /* Scheduler step on device (the loop stays in Python; this is the per-step axpy of
  * FlowMatchEulerDiscreteScheduler.step: prev = sample + dt * model_output in f32,
  * cast back).  sample/out: bf16 or f32 per sample_dtype; v bf16. */
