@@ -23,8 +23,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .flux import _Config
-from .text_encoders import _Base, _CLIPLayer, _Emb, _N, _cfg_dict
+from .module_base import HipEncoder, _CLIPLayer, _Config, _Emb, _N, _cfg_dict
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -61,7 +60,7 @@ def clip_preprocess(images, size: int = 224, crop_size: int = 224, mean: Sequenc
     return torch.stack(out)
 
 
-class CLIPVisionModel(_Base):
+class CLIPVisionModel(HipEncoder):
     """transformers.CLIPVisionModel: patch embedding, class token, pre-LN encoder (non-causal), CLS pooling + post-LN."""
 
     def __init__(self, config=None, device=None, dtype=torch.bfloat16, **kwargs):

@@ -54,11 +54,22 @@ def compute_dtype(module) -> torch.dtype:
 
 
 def _emit(cb, p, msg):
+    """Progress callback `(progress: float, message: str)`; a failing callback never interrupts a run."""
     if cb is not None:
         try:
             cb(p, msg)
         except Exception:
             pass
+
+
+def initial_noise(shape, device, dtype, seed: Optional[int] = None, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """The sampler's starting latents: N(0, 1) drawn in float32 ON THE GENERATOR'S DEVICE (a caller's CPU generator draws the CPU
+    sequence), then moved to `device` / `dtype`.  Without a generator one is made on `device` and, with `seed`, seeded."""
+    if generator is None:
+        generator = torch.Generator(device=device)
+        if seed is not None:
+            generator.manual_seed(seed)
+    return torch.randn(shape, generator=generator, device=generator.device, dtype=torch.float32).to(device=device, dtype=dtype)
 
 
 class FluxT2IEngine(EngineLoraMixin):
@@ -188,13 +199,7 @@ class FluxT2IEngine(EngineLoraMixin):
         h = 2 * (int(height) // (self.vae_scale_factor * 2))
         w = 2 * (int(width) // (self.vae_scale_factor * 2))
         if latents is None:
-            if generator is None:
-                generator = torch.Generator(device=dev)
-                if seed is not None:
-                    generator.manual_seed(seed)
-            raw = torch.randn((B, self.num_channels_latents, h, w), generator=generator,
-                              device=generator.device, dtype=torch.float32).to(device=dev, dtype=dt)
-            latents = pack_latents(raw)
+            latents = pack_latents(initial_noise((B, self.num_channels_latents, h, w), dev, dt, seed, generator))
         else:
             latents = latents.to(device=dev, dtype=dt)
         latent_ids = latent_image_ids(h // 2, w // 2, device=dev, dtype=dt)

@@ -18,11 +18,12 @@ from typing import Optional
 
 import torch
 
+from .engine_flux import initial_noise
 from .lora import EngineLoraMixin
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
 
-def _emit(cb, p, msg):
+def _emit(cb, p, msg):      # not engine_flux's: a three-argument callback is retried, and a callback's own exception propagates
     if cb is not None:
         try:
             cb(p, msg)
@@ -202,11 +203,7 @@ class HunyuanVideo15T2VEngine(EngineLoraMixin):
         shape = (B, self.num_channels_latents, (num_frames - 1) // self.vae_scale_factor_temporal + 1,
                  height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
         if latents is None:
-            if generator is None:
-                generator = torch.Generator(device=dev)
-                if seed is not None:
-                    generator.manual_seed(seed)
-            latents = torch.randn(shape, generator=generator, device=generator.device, dtype=torch.float32).to(dev, dt)
+            latents = initial_noise(shape, dev, dt, seed, generator)
         else:
             latents = latents.to(dev, dt)
         if image_embeds is None:      # t2v.py:181-187: zero vision states when there is no reference image

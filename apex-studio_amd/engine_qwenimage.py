@@ -11,16 +11,8 @@ import torch
 
 from .lora import EngineLoraMixin
 
-from .engine_flux import calculate_shift, compute_dtype
+from .engine_flux import _emit, calculate_shift, compute_dtype, initial_noise
 from .schedulers import FlowMatchEulerDiscreteScheduler
-
-
-def _emit(cb, p, msg):
-    if cb is not None:
-        try:
-            cb(p, msg)
-        except Exception:
-            pass
 
 
 class QwenImageEditPlusEngine(EngineLoraMixin):
@@ -210,10 +202,7 @@ class QwenImageEditPlusEngine(EngineLoraMixin):
         h2, w2 = height // 16, width // 16
         B = prompt_embeds.shape[0]
         if latents is None:
-            g = torch.Generator(device=dev)
-            if seed is not None:
-                g.manual_seed(seed)
-            latents = torch.randn((B, h2 * w2, 64), generator=g, device=dev, dtype=torch.float32).to(dt)
+            latents = initial_noise((B, h2 * w2, 64), dev, dt, seed)
         else:
             latents = latents.to(dev, dt)
         img_shapes = [[(1, h2, w2)] + [(1, ih // 16, iw // 16) for ih, iw in image_shapes]] * B

@@ -16,16 +16,8 @@ import torch
 
 from .lora import EngineLoraMixin
 
-from .engine_flux import compute_dtype
+from .engine_flux import _emit, compute_dtype, initial_noise
 from .schedulers import UniPCMultistepScheduler
-
-
-def _emit(cb, p, msg):
-    if cb is not None:
-        try:
-            cb(p, msg)
-        except Exception:
-            pass
 
 
 class WanT2VEngine(EngineLoraMixin):
@@ -168,11 +160,7 @@ class WanT2VEngine(EngineLoraMixin):
         shape = (B, self.num_channels_latents, num_latent_frames, height // self.vae_scale_factor_spatial,
                  width // self.vae_scale_factor_spatial)
         if latents is None:
-            if generator is None:
-                generator = torch.Generator(device=dev)
-                if seed is not None:
-                    generator.manual_seed(seed)
-            latents = torch.randn(shape, generator=generator, device=generator.device, dtype=torch.float32).to(dev)
+            latents = initial_noise(shape, dev, torch.float32, seed, generator)
         else:
             latents = latents.to(device=dev, dtype=torch.float32)
         _emit(progress_callback, 0.2, "Prepared latents")
@@ -385,11 +373,7 @@ class WanI2VEngine(WanT2VEngine):
         num_latent_frames = (duration - 1) // self.vae_scale_factor_temporal + 1
         shape = (B, z_dim, num_latent_frames, height // self.vae_scale_factor_spatial, width // self.vae_scale_factor_spatial)
         if latents is None:
-            if generator is None:
-                generator = torch.Generator(device=dev)
-                if seed is not None:
-                    generator.manual_seed(seed)
-            latents = torch.randn(shape, generator=generator, device=generator.device, dtype=torch.float32).to(dev)
+            latents = initial_noise(shape, dev, torch.float32, seed, generator)
         else:
             latents = latents.to(device=dev, dtype=torch.float32)
         _emit(progress_callback, 0.3, "Initialized latent noise")

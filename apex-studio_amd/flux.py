@@ -23,7 +23,6 @@ keep working and memory is not doubled.
 """
 from __future__ import annotations
 
-import contextlib
 import os
 from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Tuple
@@ -32,52 +31,12 @@ import torch
 import torch.nn as nn
 
 
-from .lora import LoraAdapterMixin  # noqa: E402
 from . import lib as _l
 from .schedule import ModulationSchedule, ScheduleRegistry
 from . import ops
-
-
-class _Config(SimpleNamespace):
-    def get(self, key, default=None):
-        return getattr(self, key, default)
-
-    def __getitem__(self, key):
-        return getattr(self, key)
-
-    def __contains__(self, key):
-        return hasattr(self, key)
-
-
-class _Linear(nn.Module):
-    """Parameter holder with nn.Linear's names/shapes (weight [out,in], bias [out])."""
-
-    def __init__(self, in_features: int, out_features: int, device=None, dtype=None):
-        super().__init__()
-        self.in_features, self.out_features = in_features, out_features
-        self.weight = nn.Parameter(torch.empty(out_features, in_features, device=device, dtype=dtype),
-                                   requires_grad=False)
-        self.bias = nn.Parameter(torch.empty(out_features, device=device, dtype=dtype), requires_grad=False)
-
-
-class _Norm(nn.Module):
-    def __init__(self, dim: int, device=None, dtype=None):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(dim, device=device, dtype=dtype), requires_grad=False)
-
-
-class _AdaNorm(nn.Module):
-    def __init__(self, dim: int, mult: int, cond_dim: Optional[int] = None, **kw):
-        super().__init__()
-        self.linear = _Linear(cond_dim or dim, mult * dim, **kw)
-
-
-class _FF(nn.Module):
-    def __init__(self, dim: int, inner: int, **kw):
-        super().__init__()
-        proj = nn.Module()
-        proj.proj = _Linear(dim, inner, **kw)
-        self.net = nn.ModuleList([proj, nn.Identity(), _Linear(inner, dim, **kw)])
+# the parameter holders live in module_base; they stay importable from here (the name older code and checkpoints' tools use)
+from .module_base import (F32ResidualMixin, HipTransformer, _AdaNorm, _Config, _FF, _Linear, _Norm, _TimestepEmbedding,  # noqa: F401
+                          _fuse_linears, _repoint)
 
 
 class _Attn(nn.Module):
@@ -178,13 +137,6 @@ class _SingleBlock(nn.Module):
         self.attn = _Attn(dim, heads, head_dim, joint=False, pre_only=True, **kw)
 
 
-class _TimestepEmbedding(nn.Module):
-    def __init__(self, in_dim: int, dim: int, **kw):
-        super().__init__()
-        self.linear_1 = _Linear(in_dim, dim, **kw)
-        self.linear_2 = _Linear(dim, dim, **kw)
-
-
 class _TimeTextEmbed(nn.Module):
     def __init__(self, dim: int, pooled_dim: int, guidance: bool, **kw):
         super().__init__()
@@ -194,20 +146,10 @@ class _TimeTextEmbed(nn.Module):
         self.text_embedder = _TimestepEmbedding(pooled_dim, dim, **kw)
 
 
-def _repoint(params, packed_rows):
-    """Copy each parameter into its slice of `packed_rows` and make the parameter a view of it."""
-    r = 0
-    for p in params:
-        n = p.shape[0]
-        dst = packed_rows[r:r + n]
-        dst.copy_(p.data)
-        p.data = dst
-        r += n
-    assert r == packed_rows.shape[0]
-
-
-class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
+class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
     _converter_base = "flux.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
+    _tag = "flux.mi355"
+    _drops = {"moved": ("_packed", "_ws"), "loaded": ("_packed",), "storage": ("_ws",)}
     _supports_gradient_checkpointing = False
     _no_split_modules = ["_DoubleBlock", "_SingleBlock"]
 
@@ -247,89 +189,16 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
         self._scheds = ScheduleRegistry()  # modulation schedules of the clips in flight (begin_schedule), one handle per clip
         self.batch_streams = 2           # images of a batch run side by side on HIP streams (see forward); 1 = sequential
         self._bstreams: List[Any] = []
-        self.storage_dtype = torch.bfloat16
-        self.residual_dtype = torch.bfloat16      # set_residual_dtype(float32): X alone in float, everything else bf16
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (see _forward_one; APEX_FLUX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FLUX_FUSE_QKV", "1") != "0"
 
-    # ---- reference-compatible plumbing -------------------------------------------------------
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
+    # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, cache_context, ...) ----
+    def _anchor(self):
+        return self.x_embedder.weight
 
-    _from_config = from_config
-
-    # ---- activation storage ------------------------------------------------------------------------------------------
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
-        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
-        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        if dtype == torch.float32 and self.residual_dtype == torch.float32:
-            raise ValueError("a float residual stream is for bfloat16 storage: set_residual_dtype(torch.bfloat16) first")
-        self.storage_dtype = dtype
-        self._ws = {}
-        return self
-
-    def set_residual_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (default) or torch.float32: the F32 RESIDUAL STREAM.  The residual stream X, and only
-        X, is kept in float32: the embedders write it through the GEMM's float epilogue, every gated residual update reads and
-        writes it in float, every norm reads float rows and writes the bf16 GEMM operand (apexmi_ln_modulate2_f32in).  All GEMM
-        and attention operands, and every other buffer, stay bf16 -- the rounding of X after each of its updates is what leaves
-        the bf16 chain.  Not to be combined with `set_storage_dtype(float32)`, which is all-float already."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"the residual stream must be bfloat16 or float32, got {dtype}")
-        if dtype == torch.float32 and self.storage_dtype == torch.float32:
-            raise ValueError("storage_dtype=float32 already keeps every buffer in float: a float residual stream is for bfloat16 storage")
-        self.residual_dtype = dtype
-        self._ws = {}
-        return self
-
-    @property
-    def dtype(self):
-        return self.x_embedder.weight.dtype
-
-    @property
-    def device(self):
-        return self.x_embedder.weight.device
-
-    @contextlib.contextmanager
-    def cache_context(self, name: str):
-        yield
-
-    def _apply(self, fn, *a, **k):
-        self._packed = False
-        self._ws = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = False
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
-        """N(0, std^2) weights, unit norm weights, small biases (SURVEY.md §8d synthetic inputs)."""
-        g = torch.Generator(device=self.device)
-        g.manual_seed(seed)
-        for name, p in self.named_parameters():
-            if name.endswith("norm_q.weight") or name.endswith("norm_k.weight") or \
-                    name.endswith("norm_added_q.weight") or name.endswith("norm_added_k.weight"):
-                p.data.fill_(1.0)
-            elif name.endswith(".bias"):
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * 0.01).to(p.dtype))
-            else:
-                # chunked to keep the f32 temporary small for the 12B-parameter model
-                flat = p.data.view(-1)
-                step = 1 << 26
-                for i in range(0, flat.numel(), step):
-                    n = min(step, flat.numel() - i)
-                    flat[i:i + n] = (torch.randn(n, generator=g, device=p.device) * std).to(p.dtype)
-        self._packed = False
-        return self
+        return self._fill_synthetic(seed, std, ones=lambda name, p: name.endswith(
+            ("norm_q.weight", "norm_k.weight", "norm_added_q.weight", "norm_added_k.weight")))
 
     # ---- weight packing ----------------------------------------------------------------------
     @torch.no_grad()
@@ -337,47 +206,29 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
         if self._packed:
             return
         self._scheds.clear()
-        dev, dt = self.device, self.dtype
-        if dev.type != "cuda" or dt != torch.bfloat16:
-            raise _l.ApexMIError(f"flux.mi355 needs bf16 weights on a ROCm device (got {dt} on {dev}); "
-                                 "there is no CPU fallback")
-        dim = self.inner_dim
-        mods_w, mods_b = [], []
+        self._pack_target()
+        mods = []
         self._mod_off = {}
         off = 0
 
         def reg(key, lin):
             nonlocal off
-            mods_w.append(lin.weight)
-            mods_b.append(lin.bias)
+            mods.append(lin)
             self._mod_off[key] = off
             off += lin.weight.shape[0]
 
         for i, blk in enumerate(self.transformer_blocks):
             a = blk.attn
-            blk._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.to_q.weight, a.to_k.weight, a.to_v.weight], blk._wqkv)
-            _repoint([a.to_q.bias, a.to_k.bias, a.to_v.bias], blk._bqkv)
-            blk._wqkv_c = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv_c = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.add_q_proj.weight, a.add_k_proj.weight, a.add_v_proj.weight], blk._wqkv_c)
-            _repoint([a.add_q_proj.bias, a.add_k_proj.bias, a.add_v_proj.bias], blk._bqkv_c)
+            blk._wqkv, blk._bqkv = _fuse_linears([a.to_q, a.to_k, a.to_v])
+            blk._wqkv_c, blk._bqkv_c = _fuse_linears([a.add_q_proj, a.add_k_proj, a.add_v_proj])
             reg(("d", i, "img"), blk.norm1.linear)
             reg(("d", i, "txt"), blk.norm1_context.linear)
         for i, blk in enumerate(self.single_transformer_blocks):
             a = blk.attn
-            blk._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.to_q.weight, a.to_k.weight, a.to_v.weight], blk._wqkv)
-            _repoint([a.to_q.bias, a.to_k.bias, a.to_v.bias], blk._bqkv)
+            blk._wqkv, blk._bqkv = _fuse_linears([a.to_q, a.to_k, a.to_v])
             reg(("s", i), blk.norm.linear)
         reg(("out",), self.norm_out.linear)
-        self._mod_w = torch.empty(off, dim, device=dev, dtype=dt)
-        self._mod_b = torch.empty(off, device=dev, dtype=dt)
-        _repoint(mods_w, self._mod_w)
-        _repoint(mods_b, self._mod_b)
-        self._mod_total = off
+        self._stack_modulation(mods)
         # rows of the first block that runs (its modulation is needed before the side stream is joined)
         offs = sorted(self._mod_off.values())
         self._mod_first = offs[1] if len(offs) > 1 else off
@@ -529,25 +380,7 @@ class FluxTransformer2DModel(LoraAdapterMixin, nn.Module):
             g = (guidance.to(cdt) * 1000).float().reshape(1)
             self._embed_t(tte.guidance_embedder, ops.timestep_embedding(g, 256), ws.TEMB, accum=True)
         self._embed_t(tte.text_embedder, pooled.float().reshape(1, -1), ws.TEMB, accum=True)
-        # Every AdaLN projection of every block is one weight-streaming GEMV (6.4 GB for FLUX-dev).
-        # Only the first block's slice is needed right away: the rest streams on a side HIP stream
-        # underneath the first block's MFMA-bound GEMMs and is joined before the second block.
-        n_first = self._mod_first
-        ops.gemv(self._mod_w[:n_first], ws.TEMB, self._mod_b[:n_first], out=ws.MOD[:, :n_first], pre_silu=True)
-        mod_ready = None
-        if n_first < self._mod_total:
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(ev)
-                ops.gemv(self._mod_w[n_first:], ws.TEMB, self._mod_b[n_first:], out=ws.MOD[:, n_first:],
-                         pre_silu=True)
-                mod_ready = torch.cuda.Event()
-                mod_ready.record(self._side)
-        return mod_ready
+        return self._modulation_gemv(ws.MOD, ws.TEMB)     # the first block's rows now, the rest on the side stream
 
     @torch.no_grad()
     def _forward_one(self, hidden_states, encoder_hidden_states, pooled, timestep, img_ids, txt_ids,

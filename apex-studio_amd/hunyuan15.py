@@ -21,7 +21,6 @@ temb with one more GEMV pair.
 """
 from __future__ import annotations
 
-import contextlib
 import os
 from types import SimpleNamespace
 from typing import Any, Dict, Optional, Tuple
@@ -31,9 +30,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .flux import _AdaNorm, _Config, _FF, _Linear, _TimestepEmbedding, _repoint
-from .lora import LoraAdapterMixin
-from .qwenimage import _QwenAttn
+from .module_base import HipTransformer, _AdaNorm, _Config, _FF, _JointAttn, _Linear, _TimestepEmbedding, _fuse_linears
 
 
 class _LN(nn.Module):
@@ -99,7 +96,7 @@ class _Block(nn.Module):
         super().__init__()
         self.norm1 = _AdaNorm(dim, 6, **kw)
         self.norm1_context = _AdaNorm(dim, 6, **kw)
-        self.attn = _QwenAttn(dim, heads, head_dim, **kw)
+        self.attn = _JointAttn(dim, heads, head_dim, **kw)
         self.ff = _FF(dim, inner, **kw)
         self.ff_context = _FF(dim, inner, **kw)
 
@@ -118,8 +115,10 @@ class _Embedding(nn.Module):
         self.weight = nn.Parameter(torch.empty(n, dim, device=device, dtype=dtype), requires_grad=False)
 
 
-class HunyuanVideo15Transformer3DModel(LoraAdapterMixin, nn.Module):
+class HunyuanVideo15Transformer3DModel(HipTransformer):
     _converter_base = "hunyuanvideo15.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
+    _tag = "hunyuanvideo15.mi355"
+    _drops = {"moved": ("_packed", "_ws", "_rope"), "loaded": ("_packed",), "storage": ("_ws",)}
     _no_split_modules = ["_Block", "_RefinerBlock"]
 
     def __init__(self, in_channels: int = 65, out_channels: int = 32, num_attention_heads: int = 16,
@@ -159,95 +158,34 @@ class HunyuanVideo15Transformer3DModel(LoraAdapterMixin, nn.Module):
         self._ws: Dict[Any, Any] = {}
         self._rope: Dict[Any, torch.Tensor] = {}
         self._side = None
-        self.storage_dtype = torch.bfloat16
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (APEX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FUSE_QKV", "1") != "0"
 
-    # ---- the duck-typed surface LoaderMixin / the engines use ----
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
+    # ---- the duck-typed surface LoaderMixin / the engines use: module_base ----
+    def _anchor(self):
+        return self.proj_out.weight
 
-    _from_config = from_config
-
-    @property
-    def dtype(self):
-        return self.proj_out.weight.dtype
-
-    @property
-    def device(self):
-        return self.proj_out.weight.device
-
-    @contextlib.contextmanager
-    def cache_context(self, name: str):
-        yield
-
-    def set_chunking_profile(self, profile_name: str) -> None:
-        """Chunking exists in the reference to fit 24 GB cards (model.py:904-924); nothing to do with 288 GB."""
-
-    def _apply(self, fn, *a, **k):
-        self._packed = False
-        self._ws, self._rope = {}, {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = False
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
-        g = torch.Generator(device=self.device)
-        g.manual_seed(seed)
-        for name, p in self.named_parameters():
-            if name.endswith(".bias"):
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * 0.01).to(p.dtype))
-            elif p.dim() == 1:
-                p.data.fill_(1.0)
-            else:
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * std).to(p.dtype))
-        self._packed = False
-        return self
+        # every 1-D parameter that is not a bias is a norm weight; no parameter reaches the fill's 2^26-element chunk, so the draws are
+        # those of one randn per parameter
+        return self._fill_synthetic(seed, std, ones=lambda name, p: p.dim() == 1 and not name.endswith(".bias"))
 
     @torch.no_grad()
     def pack(self):
         if self._packed:
             return
-        dev, dt = self.device, self.dtype
-        if dev.type != "cuda" or dt != torch.bfloat16:
-            raise _l.ApexMIError(f"hunyuanvideo15.mi355 needs bf16 weights on a ROCm device (got {dt} on {dev}); "
-                                 "there is no CPU fallback")
-        dim = self.inner_dim
-        mods_w, mods_b = [], []
+        self._pack_target()
+        mods = []
         for blk in self.transformer_blocks:
             a = blk.attn
-            blk._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.to_q.weight, a.to_k.weight, a.to_v.weight], blk._wqkv)
-            _repoint([a.to_q.bias, a.to_k.bias, a.to_v.bias], blk._bqkv)
-            blk._wqkv_c = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv_c = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.add_q_proj.weight, a.add_k_proj.weight, a.add_v_proj.weight], blk._wqkv_c)
-            _repoint([a.add_q_proj.bias, a.add_k_proj.bias, a.add_v_proj.bias], blk._bqkv_c)
-            mods_w += [blk.norm1.linear.weight, blk.norm1_context.linear.weight]
-            mods_b += [blk.norm1.linear.bias, blk.norm1_context.linear.bias]
-        mods_w.append(self.norm_out.linear.weight)
-        mods_b.append(self.norm_out.linear.bias)
-        total = sum(w.shape[0] for w in mods_w)
-        self._mod_w = torch.empty(total, dim, device=dev, dtype=dt)
-        self._mod_b = torch.empty(total, device=dev, dtype=dt)
-        _repoint(mods_w, self._mod_w)
-        _repoint(mods_b, self._mod_b)
-        self._mod_total = total
-        self._mod_first = min(12 * dim, total)
+            blk._wqkv, blk._bqkv = _fuse_linears([a.to_q, a.to_k, a.to_v])
+            blk._wqkv_c, blk._bqkv_c = _fuse_linears([a.add_q_proj, a.add_k_proj, a.add_v_proj])
+            mods += [blk.norm1.linear, blk.norm1_context.linear]
+        self._stack_modulation(mods + [self.norm_out.linear])
+        self._mod_first = min(12 * self.inner_dim, self._mod_total)
         for rb in self.context_embedder.token_refiner.refiner_blocks:
             a = rb.attn
-            rb._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            rb._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.to_q.weight, a.to_k.weight, a.to_v.weight], rb._wqkv)
-            _repoint([a.to_q.bias, a.to_k.bias, a.to_v.bias], rb._bqkv)
+            rb._wqkv, rb._bqkv = _fuse_linears([a.to_q, a.to_k, a.to_v])
         self._packed = True
         self._weights_changed()
 
@@ -282,15 +220,6 @@ class HunyuanVideo15Transformer3DModel(LoraAdapterMixin, nn.Module):
             TEMB=torch.empty(1, dim, **f32))
         self._ws = {key: ws}
         return ws
-
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same kernel
-        sequence with every activation buffer float and the library's `_f32` entry points.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        self._ws = {}
-        return self
 
     def _rope_table(self, grid: Tuple[int, int, int], s_txt: int):
         key = (grid, s_txt)
@@ -402,20 +331,7 @@ class HunyuanVideo15Transformer3DModel(LoraAdapterMixin, nn.Module):
             tr = timestep_r.to(self.storage_dtype).float().reshape(1)   # `timestep_r.expand(B).to(latents.dtype)`, i2v.py:281-286
             hr = ops.gemv(ter.linear_1.weight, ops.timestep_embedding(tr, 256, scale=1.0), ter.linear_1.bias, post="silu")
             ops.gemv(ter.linear_2.weight, hr, ter.linear_2.bias, out=ws.TEMB, accum=True)
-        n_first = self._mod_first
-        ops.gemv(self._mod_w[:n_first], ws.TEMB, self._mod_b[:n_first], out=ws.MOD[:, :n_first], pre_silu=True)
-        mod_ready = None
-        if n_first < self._mod_total:   # the other blocks' modulation streams on a side stream under block 0
-            main = torch.cuda.current_stream()
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=self.device)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(ev)
-                ops.gemv(self._mod_w[n_first:], ws.TEMB, self._mod_b[n_first:], out=ws.MOD[:, n_first:], pre_silu=True)
-                mod_ready = torch.cuda.Event()
-                mod_ready.record(self._side)
+        mod_ready = self._modulation_gemv(ws.MOD, ws.TEMB)   # the other blocks' rows stream on a side stream under block 0
         rope = self._rope_table(grid, s_txt)
 
         q_in, k_in, v_in = QKV[:, :dim], QKV[:, dim:2 * dim], QKV[:, 2 * dim:]

@@ -1,0 +1,369 @@
+"""What every HIP model wrapper shares: the small parameter holders, the reference-compatible plumbing (`from_config`,
+`dtype` / `device`, `set_storage_dtype`), ONE rule for which event drops which derived cache, the encoders' fused-weight
+cache, and — for the four DiT transformers — the packing helpers, the split modulation GEMV and the synthetic-weight fill.
+
+Nothing here adds a parameter, a buffer or a submodule: state-dict keys are those of the classes that derive from these.
+"""
+from __future__ import annotations
+
+import contextlib
+from types import SimpleNamespace
+from typing import Optional
+
+import torch
+import torch.nn as nn
+
+from . import lib as _l
+from . import ops
+from .lora import LoraAdapterMixin
+
+
+class _Config(SimpleNamespace):
+    def get(self, key, default=None):
+        return getattr(self, key, default)
+
+    def __getitem__(self, key):
+        return getattr(self, key)
+
+    def __contains__(self, key):
+        return hasattr(self, key)
+
+
+class _Linear(nn.Module):
+    """Parameter holder with nn.Linear's names/shapes (weight [out,in], bias [out])."""
+
+    def __init__(self, in_features: int, out_features: int, device=None, dtype=None):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.weight = nn.Parameter(torch.empty(out_features, in_features, device=device, dtype=dtype),
+                                   requires_grad=False)
+        self.bias = nn.Parameter(torch.empty(out_features, device=device, dtype=dtype), requires_grad=False)
+
+
+class _Norm(nn.Module):
+    def __init__(self, dim: int, device=None, dtype=None):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim, device=device, dtype=dtype), requires_grad=False)
+
+
+class _AdaNorm(nn.Module):
+    def __init__(self, dim: int, mult: int, cond_dim: Optional[int] = None, **kw):
+        super().__init__()
+        self.linear = _Linear(cond_dim or dim, mult * dim, **kw)
+
+
+class _FF(nn.Module):
+    def __init__(self, dim: int, inner: int, **kw):
+        super().__init__()
+        proj = nn.Module()
+        proj.proj = _Linear(dim, inner, **kw)
+        self.net = nn.ModuleList([proj, nn.Identity(), _Linear(inner, dim, **kw)])
+
+
+class _TimestepEmbedding(nn.Module):
+    def __init__(self, in_dim: int, dim: int, **kw):
+        super().__init__()
+        self.linear_1 = _Linear(in_dim, dim, **kw)
+        self.linear_2 = _Linear(dim, dim, **kw)
+
+
+class _JointAttn(nn.Module):
+    """Attention parameters of an MM-DiT double-stream block (QwenImage, HunyuanVideo-1.5): q/k/v + out projections and per-head
+    RMSNorm weights for the image stream and for the text stream (`add_*`, `norm_added_*`, `to_add_out`)."""
+
+    def __init__(self, dim: int, heads: int, head_dim: int, **kw):
+        super().__init__()
+        inner = heads * head_dim
+        self.heads = heads
+        self.to_q, self.to_k, self.to_v = _Linear(dim, inner, **kw), _Linear(dim, inner, **kw), _Linear(dim, inner, **kw)
+        self.add_q_proj, self.add_k_proj, self.add_v_proj = (_Linear(dim, inner, **kw), _Linear(dim, inner, **kw),
+                                                             _Linear(dim, inner, **kw))
+        self.norm_q, self.norm_k = _Norm(head_dim, **kw), _Norm(head_dim, **kw)
+        self.norm_added_q, self.norm_added_k = _Norm(head_dim, **kw), _Norm(head_dim, **kw)
+        self.to_out = nn.ModuleList([_Linear(inner, dim, **kw), nn.Identity()])
+        self.to_add_out = _Linear(inner, dim, **kw)
+
+
+class _Conv(nn.Module):
+    """Parameter holder of a 2-D / 3-D convolution of the VAEs (weight [out, in, *ksize], bias [out])."""
+
+    def __init__(self, cin, cout, ksize, **kw):
+        super().__init__()
+        self.ksize = tuple(ksize)
+        self.weight = nn.Parameter(torch.empty(cout, cin, *ksize, **kw), requires_grad=False)
+        self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
+
+
+def _repoint(params, packed_rows):
+    """Copy each parameter into its slice of `packed_rows` and make the parameter a view of it."""
+    r = 0
+    for p in params:
+        n = p.shape[0]
+        dst = packed_rows[r:r + n]
+        dst.copy_(p.data)
+        p.data = dst
+        r += n
+    assert r == packed_rows.shape[0]
+
+
+def _fuse_linears(linears):
+    """One packed weight [sum of out, in] and bias [sum of out] for `linears` (fused QKV / KV projections, the stacked AdaLN
+    table): the original nn.Parameters are re-pointed at views of the packed storage, so state_dict() / load_state_dict keep
+    working and memory is not doubled."""
+    w0 = linears[0].weight
+    rows = sum(lin.weight.shape[0] for lin in linears)
+    w = torch.empty(rows, w0.shape[1], device=w0.device, dtype=w0.dtype)
+    b = torch.empty(rows, device=w0.device, dtype=w0.dtype)
+    _repoint([lin.weight for lin in linears], w)
+    _repoint([lin.bias for lin in linears], b)
+    return w, b
+
+
+class HipModule(nn.Module):
+    """Base of every HIP model wrapper (transformers, VAEs, text / vision encoders, TAEHV).
+
+    A class names the parameter that stands for the module's `dtype` / `device` (`_anchor`) and states ONCE, in `_drops`,
+    which derived caches each event drops:
+      "moved"   `_apply`: `.to()`, `.cuda()`, `.bfloat16()` — storage of every parameter may be new
+      "loaded"  `load_state_dict`
+      "written" `_weights_changed`: parameters were written in place (`weights.load_checkpoint_into`, render_queue broadcast)
+      "storage" `set_storage_dtype` (and `set_residual_dtype`): the activation buffers change type
+    """
+
+    storage_dtype = torch.bfloat16
+    _drops: dict = {}
+
+    @classmethod
+    def from_config(cls, config, **kwargs):
+        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
+        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
+        cfg.update(kwargs)
+        return cls(**cfg)
+
+    @classmethod
+    def _from_config(cls, config, **kwargs):      # the name LoaderMixin._load_model calls
+        return cls.from_config(config, **kwargs)
+
+    def _anchor(self) -> torch.Tensor:
+        return next(self.parameters())
+
+    @property
+    def dtype(self):
+        return self._anchor().dtype
+
+    @property
+    def device(self):
+        return self._anchor().device
+
+    def _invalidate(self, event: str):
+        for name in self._drops.get(event, ()):
+            setattr(self, name, type(getattr(self, name))())      # {} for a cache dict, False for the `_packed` flag
+
+    def _apply(self, fn, *a, **k):
+        self._invalidate("moved")
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, *a, **k):
+        self._invalidate("loaded")
+        return super().load_state_dict(*a, **k)
+
+    def _weights_changed(self):
+        self._invalidate("written")
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
+        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
+        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
+        self.storage_dtype = dtype
+        self._invalidate("storage")
+        return self
+
+
+# ---- the text / vision encoders --------------------------------------------------------------------------------------
+
+def _cfg_dict(config, kwargs) -> dict:
+    if config is None:
+        cfg = {}
+    elif isinstance(config, dict):
+        cfg = dict(config)
+    elif hasattr(config, "to_dict"):
+        cfg = dict(config.to_dict())
+    else:
+        cfg = dict(vars(config))
+    cfg.update(kwargs)
+    return cfg
+
+
+class _W(nn.Module):
+    def __init__(self, cout, cin, bias, **kw):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(cout, cin, **kw), requires_grad=False)
+        if bias:
+            self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
+        else:
+            self.bias = None
+
+
+class _N(nn.Module):
+    def __init__(self, dim, bias, **kw):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(dim, **kw), requires_grad=False)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(dim, **kw), requires_grad=False)
+
+
+class _Emb(nn.Module):
+    def __init__(self, n, dim, **kw):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(n, dim, **kw), requires_grad=False)
+
+
+class HipEncoder(HipModule):
+    """Common surface of the encoders: fused-weight cache invalidation, the no-CPU-fallback check.  `set_storage_dtype(float32)` is
+    their verification mode: every activation between the kernels in f32 (GEMMs through the exact bf16 split, attention through
+    the f32 row kernel) so the bf16-weight encoder can be compared with the fp32 reference at ~1e-6 per element instead of the
+    bf16 rounding floor.  Not a production path.  `dtype` / `device` are those of the first parameter."""
+    _drops = {"moved": ("_fused",), "loaded": ("_fused",), "written": ("_fused",)}      # the fused / padded weight copies
+
+    @classmethod
+    def from_config(cls, config=None, **kwargs):      # transformers' convention: the config object is the first argument
+        return cls(config, **kwargs)
+
+    def _check(self, input_ids):
+        if self.device.type != "cuda" or self.dtype != torch.bfloat16:
+            raise _l.ApexMIError(f"{type(self).__name__} (mi355) needs bf16 weights on a ROCm device (no CPU fallback)")
+        if input_ids.dim() != 2:
+            raise ValueError("input_ids must be [batch, sequence]")
+
+    def _qkv(self, key, mods):
+        """Fused [3 inner, d] projection weight (and bias) of one attention layer, built once."""
+        f = self._fused.get(key)
+        if f is None:
+            w = torch.cat([m.weight.data for m in mods], dim=0).contiguous()
+            b = torch.cat([m.bias.data for m in mods], dim=0).contiguous() if mods[0].bias is not None else None
+            f = (w, b)
+            self._fused[key] = f
+        return f
+
+    def _ones(self, n):
+        o = self._fused.get(("ones", n))
+        if o is None:
+            o = (torch.ones(n, dtype=torch.float32, device=self.device),)
+            self._fused[("ones", n)] = o
+        return o[0]
+
+
+class _CLIPLayer(nn.Module):
+    def __init__(self, d, inter, **kw):
+        super().__init__()
+        self.self_attn = nn.Module()
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            setattr(self.self_attn, n, _W(d, d, True, **kw))
+        self.layer_norm1, self.layer_norm2 = _N(d, True, **kw), _N(d, True, **kw)
+        self.mlp = nn.Module()
+        self.mlp.fc1, self.mlp.fc2 = _W(inter, d, True, **kw), _W(d, inter, True, **kw)
+
+
+# ---- the DiT transformers -----------------------------------------------------------------------------------------------
+
+class HipTransformer(LoraAdapterMixin, HipModule):
+    """The layer the four DiT transformers add: the reference's no-op knobs, the `pack()` guard and helpers, the split
+    modulation GEMV, the synthetic-weight fill.  A class sets `_tag`, the prefix of its error messages."""
+
+    _tag = "mi355"
+
+    @contextlib.contextmanager
+    def cache_context(self, name: str):
+        yield
+
+    def set_chunking_profile(self, *a, **k):  # memory knobs of the reference (they exist to fit 8-24 GB cards): no-ops on 288 GB
+        return None
+
+    def set_chunk_feed_forward(self, *a, **k):
+        return None
+
+    def _pack_target(self):
+        """(device, dtype) of the weights `pack()` is about to fuse; raises unless they are bf16 on a ROCm device."""
+        dev, dt = self.device, self.dtype
+        if dev.type != "cuda" or dt != torch.bfloat16:
+            raise _l.ApexMIError(f"{self._tag} needs bf16 weights on a ROCm device (got {dt} on {dev}); "
+                                 "there is no CPU fallback")
+        return dev, dt
+
+    def _stack_modulation(self, linears):
+        """All AdaLN modulation projections as ONE matrix (`_mod_w` [total, dim], `_mod_b`, `_mod_total`), in the order given."""
+        self._mod_w, self._mod_b = _fuse_linears(linears)
+        self._mod_total = self._mod_w.shape[0]
+
+    def _modulation_gemv(self, MOD, TEMB):
+        """This step's modulation vectors: silu(TEMB) through the stacked projections into MOD.  Every AdaLN projection of every
+        block is one weight-streaming GEMV (6.4 GB for FLUX-dev).  Only the first block's slice (`_mod_first` rows) is needed right
+        away and runs on the calling stream: the rest streams on a side HIP stream underneath the first block's MFMA-bound GEMMs.
+        Returns the event to join before the second block, or None."""
+        n_first = self._mod_first
+        ops.gemv(self._mod_w[:n_first], TEMB, self._mod_b[:n_first], out=MOD[:, :n_first], pre_silu=True)
+        mod_ready = None
+        if n_first < self._mod_total:
+            main = torch.cuda.current_stream()
+            if self._side is None:
+                self._side = torch.cuda.Stream(device=self.device)
+            ev = torch.cuda.Event()
+            ev.record(main)
+            with torch.cuda.stream(self._side):
+                self._side.wait_event(ev)
+                ops.gemv(self._mod_w[n_first:], TEMB, self._mod_b[n_first:], out=MOD[:, n_first:],
+                         pre_silu=True)
+                mod_ready = torch.cuda.Event()
+                mod_ready.record(self._side)
+        return mod_ready
+
+    @torch.no_grad()
+    def _fill_synthetic(self, seed: int, std: float, ones, row_scaled=None):
+        """N(0, std^2) weights, small biases (N(0, 0.01^2)), ones where `ones(name, p)` says so (norm weights), N(0, 1 / last dim)
+        where `row_scaled(name, p)` does (SURVEY.md §8d synthetic inputs).  One generator on the model's device, parameters in
+        `named_parameters()` order: goldens and the benchmark's weights depend on the order and sizes of these draws."""
+        g = torch.Generator(device=self.device)
+        g.manual_seed(seed)
+        for name, p in self.named_parameters():
+            if ones(name, p):
+                p.data.fill_(1.0)
+            elif row_scaled is not None and row_scaled(name, p):
+                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) / p.shape[-1] ** 0.5).to(p.dtype))
+            elif name.endswith(".bias"):
+                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * 0.01).to(p.dtype))
+            else:
+                # chunked to keep the f32 temporary small for the 12B-parameter model
+                flat = p.data.view(-1)
+                step = 1 << 26
+                for i in range(0, flat.numel(), step):
+                    n = min(step, flat.numel() - i)
+                    flat[i:i + n] = (torch.randn(n, generator=g, device=p.device) * std).to(p.dtype)
+        self._invalidate("loaded")
+        return self
+
+
+class F32ResidualMixin:
+    """The F32 RESIDUAL STREAM mode of the Flux and Wan transformers, in front of HipTransformer in the bases."""
+
+    residual_dtype = torch.bfloat16      # set_residual_dtype(float32): X alone in float, everything else bf16
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and self.residual_dtype == torch.float32:
+            raise ValueError("a float residual stream is for bfloat16 storage: set_residual_dtype(torch.bfloat16) first")
+        return super().set_storage_dtype(dtype)
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        """torch.bfloat16 (default) or torch.float32: the F32 RESIDUAL STREAM.  The residual stream X, and only
+        X, is kept in float32: the embedders write it through the GEMM's float epilogue, every gated residual update reads and
+        writes it in float, every norm reads float rows and writes the bf16 GEMM operand (apexmi_ln_modulate2_f32in).  All GEMM
+        and attention operands, and every other buffer, stay bf16 -- the rounding of X after each of its updates is what leaves
+        the bf16 chain.  Not to be combined with `set_storage_dtype(float32)`, which is all-float already."""
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError(f"the residual stream must be bfloat16 or float32, got {dtype}")
+        if dtype == torch.float32 and self.storage_dtype == torch.float32:
+            raise ValueError("storage_dtype=float32 already keeps every buffer in float: a float residual stream is for bfloat16 storage")
+        self.residual_dtype = dtype
+        self._invalidate("storage")
+        return self

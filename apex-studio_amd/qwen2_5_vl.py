@@ -26,8 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .flux import _Config
-from .text_encoders import _Base, _Emb, _N, _W, _cfg_dict
+from .module_base import HipEncoder, _Config, _Emb, _N, _W, _cfg_dict
 
 
 def _pad_to(n: int, m: int) -> int:
@@ -150,7 +149,7 @@ _VISION_DEFAULTS = dict(depth=32, hidden_size=1280, intermediate_size=3420, num_
                         spatial_merge_size=2, temporal_patch_size=2, window_size=112, fullatt_block_indexes=(7, 15, 23, 31))
 
 
-class Qwen2_5_VLForConditionalGeneration(_Base):
+class Qwen2_5_VLForConditionalGeneration(HipEncoder):
     def __init__(self, config=None, device=None, dtype=torch.bfloat16, **kwargs):
         super().__init__()
         cfg = _cfg_dict(config, kwargs)

@@ -19,7 +19,6 @@ NotImplementedError.
 """
 from __future__ import annotations
 
-import contextlib
 import os
 from types import SimpleNamespace
 from typing import Any, Dict, List, Optional, Tuple
@@ -28,25 +27,12 @@ import torch
 import torch.nn as nn
 
 
-from .lora import LoraAdapterMixin  # noqa: E402
 from . import lib as _l
 from . import ops
 from .schedule import ModulationSchedule, ScheduleRegistry
-from .flux import _Config, _Linear, _Norm, _FF, _AdaNorm, _TimestepEmbedding, _repoint
+from .module_base import HipTransformer, _AdaNorm, _Config, _FF, _JointAttn, _Linear, _Norm, _TimestepEmbedding, _fuse_linears
 
-
-class _QwenAttn(nn.Module):
-    def __init__(self, dim: int, heads: int, head_dim: int, **kw):
-        super().__init__()
-        inner = heads * head_dim
-        self.heads = heads
-        self.to_q, self.to_k, self.to_v = _Linear(dim, inner, **kw), _Linear(dim, inner, **kw), _Linear(dim, inner, **kw)
-        self.add_q_proj, self.add_k_proj, self.add_v_proj = (_Linear(dim, inner, **kw), _Linear(dim, inner, **kw),
-                                                             _Linear(dim, inner, **kw))
-        self.norm_q, self.norm_k = _Norm(head_dim, **kw), _Norm(head_dim, **kw)
-        self.norm_added_q, self.norm_added_k = _Norm(head_dim, **kw), _Norm(head_dim, **kw)
-        self.to_out = nn.ModuleList([_Linear(inner, dim, **kw), nn.Identity()])
-        self.to_add_out = _Linear(inner, dim, **kw)
+_QwenAttn = _JointAttn      # the block's attention parameters (shared with hunyuan15.py, hence in module_base)
 
 
 def _mod_seq(dim: int, **kw):
@@ -71,8 +57,10 @@ class _TimeTextEmbed(nn.Module):
             self.addition_t_embedding = nn.Embedding(2, dim, **kw)
 
 
-class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
+class QwenImageTransformer2DModel(HipTransformer):
     _converter_base = "qwenimage.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
+    _tag = "qwenimage.mi355"
+    _drops = {"moved": ("_packed", "_ws", "_rope"), "loaded": ("_packed",), "storage": ("_ws",)}
     _no_split_modules = ["_QwenBlock"]
 
     def __init__(self, patch_size: int = 2, in_channels: int = 64, out_channels: Optional[int] = 16,
@@ -104,7 +92,6 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
         self.proj_out = _Linear(dim, patch_size * patch_size * self.out_channels, **kw)
         self._packed = False
         self._ws: Dict[Any, Any] = {}
-        self.storage_dtype = torch.bfloat16
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (APEX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FUSE_QKV", "1") != "0"
         self._rope: Dict[Any, torch.Tensor] = {}
@@ -113,98 +100,26 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
         self.batch_streams = 2           # images of a batch on side-by-side HIP streams (forward); 1 = sequential
         self._bstreams: List[Any] = []
 
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
+    def _anchor(self):
+        return self.img_in.weight
 
-    _from_config = from_config
-
-    # ---- activation storage ------------------------------------------------------------------------------------------
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
-        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
-        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        self._ws = {}
-        return self
-
-    @property
-    def dtype(self):
-        return self.img_in.weight.dtype
-
-    @property
-    def device(self):
-        return self.img_in.weight.device
-
-    @contextlib.contextmanager
-    def cache_context(self, name: str):
-        yield
-
-    def _apply(self, fn, *a, **k):
-        self._packed = False
-        self._ws = {}
-        self._rope = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = False
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
-        g = torch.Generator(device=self.device)
-        g.manual_seed(seed)
-        for name, p in self.named_parameters():
-            if "norm_" in name or name == "txt_norm.weight":
-                p.data.fill_(1.0)
-            elif name.endswith(".bias"):
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * 0.01).to(p.dtype))
-            else:
-                flat = p.data.view(-1)
-                step = 1 << 26
-                for i in range(0, flat.numel(), step):
-                    n = min(step, flat.numel() - i)
-                    flat[i:i + n] = (torch.randn(n, generator=g, device=p.device) * std).to(p.dtype)
-        self._packed = False
-        return self
+        return self._fill_synthetic(seed, std, ones=lambda name, p: "norm_" in name or name == "txt_norm.weight")
 
     @torch.no_grad()
     def pack(self):
         if self._packed:
             return
         self._scheds.clear()
-        dev, dt = self.device, self.dtype
-        if dev.type != "cuda" or dt != torch.bfloat16:
-            raise _l.ApexMIError(f"qwenimage.mi355 needs bf16 weights on a ROCm device (got {dt} on {dev}); "
-                                 "there is no CPU fallback")
-        dim = self.inner_dim
-        mods_w, mods_b = [], []
+        self._pack_target()
+        mods = []
         for blk in self.transformer_blocks:
             a = blk.attn
-            blk._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.to_q.weight, a.to_k.weight, a.to_v.weight], blk._wqkv)
-            _repoint([a.to_q.bias, a.to_k.bias, a.to_v.bias], blk._bqkv)
-            blk._wqkv_c = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv_c = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a.add_q_proj.weight, a.add_k_proj.weight, a.add_v_proj.weight], blk._wqkv_c)
-            _repoint([a.add_q_proj.bias, a.add_k_proj.bias, a.add_v_proj.bias], blk._bqkv_c)
-            mods_w += [blk.img_mod[1].weight, blk.txt_mod[1].weight]
-            mods_b += [blk.img_mod[1].bias, blk.txt_mod[1].bias]
-        mods_w.append(self.norm_out.linear.weight)
-        mods_b.append(self.norm_out.linear.bias)
-        total = sum(w.shape[0] for w in mods_w)
-        self._mod_w = torch.empty(total, dim, device=dev, dtype=dt)
-        self._mod_b = torch.empty(total, device=dev, dtype=dt)
-        _repoint(mods_w, self._mod_w)
-        _repoint(mods_b, self._mod_b)
-        self._mod_total = total
-        self._mod_first = min(12 * dim, total)   # img_mod + txt_mod of block 0
+            blk._wqkv, blk._bqkv = _fuse_linears([a.to_q, a.to_k, a.to_v])
+            blk._wqkv_c, blk._bqkv_c = _fuse_linears([a.add_q_proj, a.add_k_proj, a.add_v_proj])
+            mods += [blk.img_mod[1], blk.txt_mod[1]]
+        self._stack_modulation(mods + [self.norm_out.linear])
+        self._mod_first = min(12 * self.inner_dim, self._mod_total)   # img_mod + txt_mod of block 0
         self._packed = True
 
     def _workspace(self, s_txt: int, s_img: int):
@@ -323,21 +238,7 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
                 if addition_t_cond is None:
                     raise ValueError("When additional_t_cond is True, addition_t_cond must be provided.")
                 ws.TEMB.add_(self.time_text_embed.addition_t_embedding.weight[addition_t_cond.reshape(1).long()].float())
-
-            n_first = self._mod_first
-            ops.gemv(self._mod_w[:n_first], ws.TEMB, self._mod_b[:n_first], out=ws.MOD[:, :n_first], pre_silu=True)
-            if n_first < self._mod_total:   # the other blocks' modulation streams on a side stream under block 0
-                main = torch.cuda.current_stream()
-                if self._side is None:
-                    self._side = torch.cuda.Stream(device=self.device)
-                ev = torch.cuda.Event()
-                ev.record(main)
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(ev)
-                    ops.gemv(self._mod_w[n_first:], ws.TEMB, self._mod_b[n_first:], out=ws.MOD[:, n_first:],
-                             pre_silu=True)
-                    mod_ready = torch.cuda.Event()
-                    mod_ready.record(self._side)
+            mod_ready = self._modulation_gemv(ws.MOD, ws.TEMB)   # the other blocks' rows stream on a side stream under block 0
         rope = self._rope_table(shapes, s_txt)
 
         q_in, k_in, v_in = QKV[:, :dim], QKV[:, dim:2 * dim], QKV[:, 2 * dim:]
@@ -351,19 +252,9 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
         Qp, Kp, VTp = (ws.Qb, ws.Kb, ws.VTb) if (mixed and fuse) else (ws.Q, ws.K, ws.VT)
         # zero_cond_t: the first image (the target) is conditioned on t, the images after it on t = 0 (`modulate_index`, :914-921)
         n0 = int(shapes[0][0]) * int(shapes[0][1]) * int(shapes[0][2]) if zc else s_img
-        for i, blk in enumerate(self.transformer_blocks):
-            if i == 1 and mod_ready is not None:
-                torch.cuda.current_stream().wait_event(mod_ready)
-                mod_ready = None
+
+        def qkv_step(blk):
             a = blk.attn
-            base = i * 12 * dim
-            mi = lambda j: MOD[0, base + j * dim: base + (j + 1) * dim]              # noqa: E731
-            mt = lambda j: MOD[0, base + (6 + j) * dim: base + (7 + j) * dim]        # noqa: E731
-            # chunk order: shift1, scale1, gate1 | shift2, scale2, gate2
-            if zc:
-                self._block_zero_cond(blk, ws, MOD, base, s_txt, n0, rope, fuse, Qp, Kp, VTp, q_in, k_in, v_in, att_v, H)
-                continue
-            ops.ln_modulate(X, mi(1), mi(0), out=XN, split=s_txt, scale2=mt(1), shift2=mt(0))
             if fuse:
                 # q/k norm + RoPE + [H, S, D] layout and V^T leave the QKV GEMM's epilogue (bit-identical to the two passes)
                 ops.gemm_grouped_qkv([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [None, None], "bias",
@@ -375,6 +266,21 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VTp[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, wq2=a.norm_added_q.weight, wk2=a.norm_added_k.weight,
                                 split=s_txt, eps=1e-6, rope=rope, rope_mode=_l.ROPE_INTERLEAVED)
+
+        for i, blk in enumerate(self.transformer_blocks):
+            if i == 1 and mod_ready is not None:
+                torch.cuda.current_stream().wait_event(mod_ready)
+                mod_ready = None
+            a = blk.attn
+            base = i * 12 * dim
+            mi = lambda j: MOD[0, base + j * dim: base + (j + 1) * dim]              # noqa: E731
+            mt = lambda j: MOD[0, base + (6 + j) * dim: base + (7 + j) * dim]        # noqa: E731
+            # chunk order: shift1, scale1, gate1 | shift2, scale2, gate2
+            if zc:
+                self._block_zero_cond(blk, ws, MOD, base, s_txt, n0, qkv_step, Qp, Kp, VTp, att_v)
+                continue
+            ops.ln_modulate(X, mi(1), mi(0), out=XN, split=s_txt, scale2=mt(1), shift2=mt(0))
+            qkv_step(blk)
             ops.attention_prepared(Qp, Kp, VTp, att_v, S)
             ops.gemm_grouped([ATT[s_txt:], ATT[:s_txt]], [a.to_out[0].weight, a.to_add_out.weight],
                              [a.to_out[0].bias, a.to_add_out.bias], [Xi, Xt], epilogue="gate_res",
@@ -392,17 +298,17 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
         ops.ln_modulate(Xi, MOD[0, o:o + dim], MOD[0, o + dim:o + 2 * dim], out=XNi)
         return ops.gemm(XNi, self.proj_out.weight, self.proj_out.bias)
 
-    def _block_zero_cond(self, blk, ws, MOD, base, s_txt, n0, rope, fuse, Qp, Kp, VTp, q_in, k_in, v_in, att_v, H):
+    def _block_zero_cond(self, blk, ws, MOD, base, s_txt, n0, qkv_step, Qp, Kp, VTp, att_v):
         """One block with `zero_cond_t`: the same launches, with the image stream's modulation and gates taken per ROW RANGE —
         target tokens [s_txt, s_txt + n0) from conditioning row 0 (t), condition-image tokens behind them from row 1 (t = 0); the
         text stream from row 0 (`_modulate(index)`, model.py:640-677; `txt_mod(temb.chunk(2)[0])`, :692-693).  The LN + modulate
         pass runs once per range, the gate / residual GEMMs carry the two image ranges as two problems of the grouped launch."""
         dim = self.inner_dim
         a = blk.attn
-        X, XN, QKV, ATT, FFH = ws.X, ws.XN, ws.QKV, ws.ATT, ws.FFH
+        X, XN, ATT, FFH = ws.X, ws.XN, ws.ATT, ws.FFH
         S = X.shape[0]
         c0 = s_txt + n0                                   # first condition-image row
-        Xt, Xi, XNt, XNi = X[:s_txt], X[s_txt:], XN[:s_txt], XN[s_txt:]
+        XNt, XNi = XN[:s_txt], XN[s_txt:]
         m0 = lambda j: MOD[0, base + j * dim: base + (j + 1) * dim]                # noqa: E731  image stream, row t
         m1 = lambda j: MOD[1, base + j * dim: base + (j + 1) * dim]                # noqa: E731  image stream, row t = 0
         mt = lambda j: MOD[0, base + (6 + j) * dim: base + (7 + j) * dim]          # noqa: E731  text stream, row t
@@ -421,15 +327,7 @@ class QwenImageTransformer2DModel(LoraAdapterMixin, nn.Module):
                              gate_list=gates(j), residual_list=[X[lo:hi] for lo, hi in rng])
 
         ln(1, 0)
-        if fuse:
-            ops.gemm_grouped_qkv([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [None, None], "bias",
-                                 [1, 1], [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
-                                 [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VTp[0])
-        else:
-            ops.gemm_grouped([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [QKV[s_txt:], QKV[:s_txt]])
-            ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VTp[0], wq=a.norm_q.weight, wk=a.norm_k.weight,
-                            wq2=a.norm_added_q.weight, wk2=a.norm_added_k.weight, split=s_txt, eps=1e-6, rope=rope,
-                            rope_mode=_l.ROPE_INTERLEAVED)
+        qkv_step(blk)           # `_forward_one`'s: the QKV step does not depend on the modulation rows
         ops.attention_prepared(Qp, Kp, VTp, att_v, S)
         gated(ATT, a.to_out[0].weight, a.to_out[0].bias, a.to_add_out.weight, a.to_add_out.bias, 2)
         ln(4, 3)

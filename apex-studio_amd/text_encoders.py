@@ -17,118 +17,11 @@ from __future__ import annotations
 
 import math
 from types import SimpleNamespace
-from typing import Dict
-
 import torch
 import torch.nn as nn
 
-from . import lib as _l
 from . import ops
-from .flux import _Config
-
-
-def _cfg_dict(config, kwargs) -> dict:
-    if config is None:
-        cfg = {}
-    elif isinstance(config, dict):
-        cfg = dict(config)
-    elif hasattr(config, "to_dict"):
-        cfg = dict(config.to_dict())
-    else:
-        cfg = dict(vars(config))
-    cfg.update(kwargs)
-    return cfg
-
-
-class _W(nn.Module):
-    def __init__(self, cout, cin, bias, **kw):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(cout, cin, **kw), requires_grad=False)
-        if bias:
-            self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
-        else:
-            self.bias = None
-
-
-class _N(nn.Module):
-    def __init__(self, dim, bias, **kw):
-        super().__init__()
-        self.weight = nn.Parameter(torch.ones(dim, **kw), requires_grad=False)
-        if bias:
-            self.bias = nn.Parameter(torch.zeros(dim, **kw), requires_grad=False)
-
-
-class _Emb(nn.Module):
-    def __init__(self, n, dim, **kw):
-        super().__init__()
-        self.weight = nn.Parameter(torch.empty(n, dim, **kw), requires_grad=False)
-
-
-class _Base(nn.Module):
-    """Common surface: from_config, dtype/device, fused-weight cache invalidation, the no-CPU-fallback check."""
-
-    @classmethod
-    def from_config(cls, config=None, **kwargs):
-        return cls(config, **kwargs)
-
-    _from_config = from_config
-
-    storage_dtype = torch.bfloat16
-
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """Verification mode (flux.py `set_storage_dtype`): float32 keeps every activation between the kernels in f32 (GEMMs through
-        the exact bf16 split, attention through the f32 row kernel) so the bf16-weight encoder can be compared with the fp32
-        reference at ~1e-6 per element instead of the bf16 rounding floor.  Weights stay bf16.  Not a production path."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError("storage dtype is bfloat16 (production) or float32 (verification)")
-        self.storage_dtype = dtype
-        return self
-
-    def _first(self):
-        return next(self.parameters())
-
-    @property
-    def dtype(self):
-        return self._first().dtype
-
-    @property
-    def device(self):
-        return self._first().device
-
-    def _apply(self, fn, *a, **k):
-        self._fused: Dict[int, tuple] = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._fused = {}
-        return super().load_state_dict(*a, **k)
-
-    def _weights_changed(self):
-        """Parameters were written in place (`weights.load_checkpoint_into`): drop the fused / padded copies."""
-        self._fused = {}
-
-    def _check(self, input_ids):
-        if self.device.type != "cuda" or self.dtype != torch.bfloat16:
-            raise _l.ApexMIError(f"{type(self).__name__} (mi355) needs bf16 weights on a ROCm device (no CPU fallback)")
-        if input_ids.dim() != 2:
-            raise ValueError("input_ids must be [batch, sequence]")
-
-    def _qkv(self, key, mods):
-        """Fused [3 inner, d] projection weight (and bias) of one attention layer, built once."""
-        f = self._fused.get(key)
-        if f is None:
-            w = torch.cat([m.weight.data for m in mods], dim=0).contiguous()
-            b = torch.cat([m.bias.data for m in mods], dim=0).contiguous() if mods[0].bias is not None else None
-            f = (w, b)
-            self._fused[key] = f
-        return f
-
-    def _ones(self, n):
-        o = self._fused.get(("ones", n))
-        if o is None:
-            o = (torch.ones(n, dtype=torch.float32, device=self.device),)
-            self._fused[("ones", n)] = o
-        return o[0]
+from .module_base import HipEncoder, _CLIPLayer, _Config, _Emb, _N, _W, _cfg_dict
 
 
 # ---- T5 / UMT5 ------------------------------------------------------------------------------------------------
@@ -167,7 +60,7 @@ class _T5Block(nn.Module):
         self.layer = nn.ModuleList([sa, ff])
 
 
-class T5EncoderModel(_Base):
+class T5EncoderModel(HipEncoder):
     """transformers.T5EncoderModel (T5 v1.1 "gated-gelu" feed-forward: Flux's text_encoder_2)."""
 
     per_layer_bias = False
@@ -254,18 +147,7 @@ class UMT5EncoderModel(T5EncoderModel):
 
 # ---- CLIP text ------------------------------------------------------------------------------------------------
 
-class _CLIPLayer(nn.Module):
-    def __init__(self, d, inter, **kw):
-        super().__init__()
-        self.self_attn = nn.Module()
-        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-            setattr(self.self_attn, n, _W(d, d, True, **kw))
-        self.layer_norm1, self.layer_norm2 = _N(d, True, **kw), _N(d, True, **kw)
-        self.mlp = nn.Module()
-        self.mlp.fc1, self.mlp.fc2 = _W(inter, d, True, **kw), _W(d, inter, True, **kw)
-
-
-class CLIPTextModel(_Base):
+class CLIPTextModel(HipEncoder):
     """transformers.CLIPTextModel (Flux's pooled-prompt encoder): causal pre-LN encoder, EOS pooling."""
 
     def __init__(self, config=None, device=None, dtype=torch.bfloat16, **kwargs):

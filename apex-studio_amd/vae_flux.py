@@ -19,8 +19,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .flux import _Config, _Linear
-from .vae_wan import _Conv
+from .module_base import HipModule, _Config, _Conv, _Linear
 
 
 class _GN(nn.Module):
@@ -86,7 +85,9 @@ class _Decoder2D(nn.Module):
         self.conv_out = _Conv(rev[-1], out_channels, (3, 3), **kw)
 
 
-class AutoencoderKL(nn.Module):
+class AutoencoderKL(HipModule):
+    _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
+
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 16,
                  block_out_channels=(128, 256, 512, 512), layers_per_block: int = 2, norm_num_groups: int = 32,
                  scaling_factor: float = 0.3611, shift_factor: float = 0.1159, sample_size: int = 1024,
@@ -102,46 +103,9 @@ class AutoencoderKL(nn.Module):
         kw = dict(device=device, dtype=dtype)
         self.decoder = _Decoder2D(latent_channels, out_channels, block_out_channels, layers_per_block, **kw)
         self._packed: Dict[int, tuple] = {}
-        self.storage_dtype = torch.bfloat16
 
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
-
-    _from_config = from_config
-
-    # ---- activation storage ------------------------------------------------------------------------------------------
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
-        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
-        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        return self
-
-    @property
-    def dtype(self):
-        return self.decoder.conv_in.weight.dtype
-
-    @property
-    def device(self):
-        return self.decoder.conv_in.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
-
-    def _weights_changed(self):
-        """Parameters were written in place (`weights.load_checkpoint_into`): drop the packed conv-weight cache."""
-        self._packed = {}
+    def _anchor(self):
+        return self.decoder.conv_in.weight
 
     def enable_tiling(self, *a, **k):   # 1024^2 latents equal tile_latent_min_size: untiled (model.py:229-236)
         return None

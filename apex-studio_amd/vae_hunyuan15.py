@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .flux import _Config
+from .module_base import HipModule, _Config
 
 
 class _CConv(nn.Module):
@@ -180,7 +180,13 @@ def _rearrange_cl(x: torch.Tensor, r1: int, r2: int, r3: int) -> torch.Tensor:
     return x.view(T, H, W, r1, r2, r3, c).permute(0, 3, 1, 4, 2, 5, 6).reshape(T * r1, H * r2, W * r3, c)
 
 
-class AutoencoderKLHunyuanVideo15(nn.Module):
+class AutoencoderKLHunyuanVideo15(HipModule):
+    """`set_storage_dtype(float32)` here is the verification mode of the decoder AND the encoder: the convolutions on the exact
+    three-way bf16 split, and the frame-causal mid-block attention as one f32 attention call per frame over the keys of the frames
+    up to it — the same softmax, without the bf16 probabilities of the materialised production path.  The encoder's moments come
+    back float."""
+    _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
+
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 32,
                  block_out_channels: Tuple[int, ...] = (128, 256, 512, 1024, 1024), layers_per_block: int = 2,
                  spatial_compression_ratio: int = 16, temporal_compression_ratio: int = 4,
@@ -209,7 +215,6 @@ class AutoencoderKLHunyuanVideo15(nn.Module):
         self.tile_latent_min_height = self.tile_latent_min_width = 128 // spatial_compression_ratio
         self.tile_overlap_factor = 0.25
         self._packed: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
-        self.storage_dtype = torch.bfloat16
         # up blocks (after conv_in + mid) whose launches cover all equally shaped tiles at once; measured on the 480p x 121-frame
         # decode (tools/hunyuan_vae_streams_ab.py): 0 / 1 / 2 = 2382 / 2366 / 2351 ms at 7 / 10 / 26 GiB peak — 1 by default; stages
         # whose single-tile launch already takes the conv-shaped tiles must stay outside (another summation order)
@@ -225,33 +230,12 @@ class AutoencoderKLHunyuanVideo15(nn.Module):
             self._ensure_light_vae_loaded()
 
     @classmethod
-    def from_config(cls, config, **kwargs):
+    def from_config(cls, config, **kwargs):      # `.config` carries shift_factor=None for the engines; it is no constructor argument
         cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_") and k != "shift_factor"}
-        cfg.update(kwargs)
-        return cls(**cfg)
+        return super().from_config({k: v for k, v in cfg.items() if k != "shift_factor"}, **kwargs)
 
-    _from_config = from_config
-
-    @property
-    def dtype(self):
-        return self.decoder.conv_in.conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.decoder.conv_in.conv.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
-
-    def _weights_changed(self):
-        """Parameters were written in place (`weights.load_checkpoint_into`): drop the packed conv-weight cache."""
-        self._packed = {}
+    def _anchor(self):
+        return self.decoder.conv_in.conv.weight
 
     def _ensure_light_vae_loaded(self) -> None:
         """model.py:821-846."""
@@ -269,17 +253,6 @@ class AutoencoderKLHunyuanVideo15(nn.Module):
     def set_light_vae(self, light_vae) -> None:
         """Attach an already built `AutoencoderKLHunyuanVideo15Light` (weights streamed by the host's own loader)."""
         self.light_vae = light_vae
-
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE of the decoder AND the encoder
-        (DESIGN.md §1.2): every activation float, the library's `_f32` entry points (the convolutions on the exact three-way bf16
-        split), and the frame-causal mid-block attention as one f32 attention call per frame over the keys of the frames up to
-        it — the same softmax, without the bf16 probabilities of the materialised production path.  Weights stay bf16; the
-        encoder's moments come back float."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        return self
 
     def enable_tiling(self, tile_sample_min_height=None, tile_sample_min_width=None, tile_latent_min_height=None,
                       tile_latent_min_width=None, tile_overlap_factor=None, use_light_vae: Optional[bool] = None):

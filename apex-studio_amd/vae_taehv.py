@@ -30,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .module_base import HipModule
 
 
 class _Conv(nn.Module):
@@ -66,7 +67,9 @@ class _TGrow(nn.Module):
         self.conv = _Conv(n, n * stride, 1, bias=False, **kw)
 
 
-class TAEHV(nn.Module):
+class TAEHV(HipModule):
+    _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
+
     N_F = (256, 128, 64, 64)
 
     def __init__(self, checkpoint_path: Optional[str] = None, decoder_time_upscale: Sequence[bool] = (True, True),
@@ -103,31 +106,8 @@ class TAEHV(nn.Module):
         if checkpoint_path is not None:
             self.load_state_dict(self.patch_tgrow_layers(_read_checkpoint(checkpoint_path)))
 
-    # ---- state ------------------------------------------------------------------------------------------------------
-    storage_dtype = torch.bfloat16
-
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-storage verification mode — activations float,
-        the `_f32` entry points (convolutions on the exact bf16 split).  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        return self
-
-    @property
-    def dtype(self):
-        return self.decoder[1].weight.dtype
-
-    @property
-    def device(self):
-        return self.decoder[1].weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
-    def _weights_changed(self):
-        self._packed = {}
+    def _anchor(self):
+        return self.decoder[1].weight
 
     def patch_tgrow_layers(self, sd):
         """tae/model.py:283-297: a checkpoint trained with more temporal upscaling keeps the LAST-timestep output channels."""
@@ -140,7 +120,6 @@ class TAEHV(nn.Module):
         return sd
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
-        self._packed = {}
         sd = state_dict if self.with_encoder else {k: v for k, v in state_dict.items() if not k.startswith("encoder.")}
         return super().load_state_dict(sd, strict=strict, assign=assign)
 

@@ -31,20 +31,12 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .flux import _Config
+from .module_base import HipModule, _Config, _Conv
 
 WAN_LATENTS_MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508, 0.4134, -0.0715,
                     0.5517, -0.3632, -0.1922, -0.9497, 0.2503, -0.2921]
 WAN_LATENTS_STD = [2.8184, 1.4541, 2.3275, 2.6558, 1.2196, 1.7708, 2.6052, 2.0743, 3.2687, 2.1526, 2.8652,
                    1.5579, 1.6382, 1.1253, 2.8251, 1.9160]
-
-
-class _Conv(nn.Module):
-    def __init__(self, cin, cout, ksize, **kw):
-        super().__init__()
-        self.ksize = tuple(ksize)
-        self.weight = nn.Parameter(torch.empty(cout, cin, *ksize, **kw), requires_grad=False)
-        self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
 
 
 class _Gamma(nn.Module):
@@ -162,7 +154,9 @@ class DiagonalGaussianDistribution:
         return self.mean + self.std * noise
 
 
-class AutoencoderKLWan(nn.Module):
+class AutoencoderKLWan(HipModule):
+    _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
+
     def __init__(self, base_dim: int = 96, decoder_base_dim: Optional[int] = None, z_dim: int = 16,
                  dim_mult: List[int] = (1, 2, 4, 4), num_res_blocks: int = 2, attn_scales=(),
                  temperal_downsample=(False, True, True), dropout: float = 0.0,
@@ -199,46 +193,9 @@ class AutoencoderKLWan(nn.Module):
         self.tile_streams = 2            # video tiles decoded / encoded side by side on HIP streams (see _run_tiles_on_streams)
         self._streams: list = []
         self.batch_single_frame_tiles = True
-        self.storage_dtype = torch.bfloat16
 
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
-
-    _from_config = from_config
-
-    # ---- activation storage ------------------------------------------------------------------------------------------
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
-        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
-        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        self.storage_dtype = dtype
-        return self
-
-    @property
-    def dtype(self):
-        return self.post_quant_conv.weight.dtype
-
-    @property
-    def device(self):
-        return self.post_quant_conv.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._packed = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = {}
-        return super().load_state_dict(*a, **k)
-
-    def _weights_changed(self):
-        """Parameters were written in place (`weights.load_checkpoint_into`): drop the packed conv-weight cache."""
-        self._packed = {}
+    def _anchor(self):
+        return self.post_quant_conv.weight
 
     def enable_tiling(self, tile_sample_min_height=None, tile_sample_min_width=None,
                       tile_sample_stride_height=None, tile_sample_stride_width=None):

@@ -23,10 +23,8 @@ same launches as before.  The IP adapter and `use_enhance` raise NotImplementedE
 """
 from __future__ import annotations
 
-import os
-
-import contextlib
 import math
+import os
 from types import SimpleNamespace
 from typing import Any, Dict, Optional, Tuple
 
@@ -34,10 +32,9 @@ import torch
 import torch.nn as nn
 
 
-from .lora import LoraAdapterMixin  # noqa: E402
 from . import lib as _l
 from . import ops
-from .flux import _Config, _Linear, _Norm, _FF, _repoint
+from .module_base import F32ResidualMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
 
 
 class _WanAttn(nn.Module):
@@ -113,8 +110,10 @@ class _Conv3dParams(nn.Module):
         self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
 
 
-class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
+class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
+    _tag = "wan.mi355"
+    _drops = {"moved": ("_packed", "_ws", "_rope"), "loaded": ("_packed",), "storage": ("_ws",)}
     _no_split_modules = ["_WanBlock"]
 
     def __init__(self, patch_size: Tuple[int, int, int] = (1, 2, 2), num_attention_heads: int = 40,
@@ -158,65 +157,12 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         self.scale_shift_table = nn.Parameter(torch.empty(1, 2, dim, **kw), requires_grad=False)
         self._packed = False
         self._ws: Dict[Any, Any] = {}
-        self.storage_dtype = torch.bfloat16
-        self.residual_dtype = torch.bfloat16      # set_residual_dtype(float32): X alone in float, everything else bf16
         self.fuse_qkv = os.environ.get("APEX_FUSE_QKV", "1") != "0"     # see _forward_one
         self._rope: Dict[Any, torch.Tensor] = {}
 
-    # ---- reference-compatible plumbing -------------------------------------------------------
-    @classmethod
-    def from_config(cls, config, **kwargs):
-        cfg = dict(config) if isinstance(config, dict) else dict(vars(config))
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
-        cfg.update(kwargs)
-        return cls(**cfg)
-
-    _from_config = from_config
-
-    # ---- activation storage ------------------------------------------------------------------------------------------
-    def set_storage_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (production) or torch.float32: the f32-STORAGE VERIFICATION MODE — the same
-        kernel sequence with every activation buffer float and the library's `_f32` entry points, which is what
-        north_star's "within 1e-3 of the CPU fp32 reference" is tested with.  Weights stay bf16."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"activation storage must be bfloat16 or float32, got {dtype}")
-        if dtype == torch.float32 and self.residual_dtype == torch.float32:
-            raise ValueError("a float residual stream is for bfloat16 storage: set_residual_dtype(torch.bfloat16) first")
-        self.storage_dtype = dtype
-        self._ws = {}
-        return self
-
-    def set_residual_dtype(self, dtype: torch.dtype):
-        """torch.bfloat16 (default) or torch.float32: the F32 RESIDUAL STREAM.  The residual stream X, and only
-        X, is kept in float32: the embedders write it through the GEMM's float epilogue, every gated residual update reads and
-        writes it in float, every norm reads float rows and writes the bf16 GEMM operand (apexmi_ln_modulate2_f32in).  All GEMM
-        and attention operands, and every other buffer, stay bf16 -- the rounding of X after each of its updates is what leaves
-        the bf16 chain.  Not to be combined with `set_storage_dtype(float32)`, which is all-float already."""
-        if dtype not in (torch.bfloat16, torch.float32):
-            raise ValueError(f"the residual stream must be bfloat16 or float32, got {dtype}")
-        if dtype == torch.float32 and self.storage_dtype == torch.float32:
-            raise ValueError("storage_dtype=float32 already keeps every buffer in float: a float residual stream is for bfloat16 storage")
-        self.residual_dtype = dtype
-        self._ws = {}
-        return self
-
-    @property
-    def dtype(self):
-        return self.proj_out.weight.dtype
-
-    @property
-    def device(self):
-        return self.proj_out.weight.device
-
-    @contextlib.contextmanager
-    def cache_context(self, name: str):
-        yield
-
-    def set_chunking_profile(self, *a, **k):  # memory knobs of the reference: no-ops on 288 GB
-        return None
-
-    def set_chunk_feed_forward(self, *a, **k):
-        return None
+    # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, the no-op knobs, ...) ----
+    def _anchor(self):
+        return self.proj_out.weight
 
     def enable_easy_cache(self, num_steps: int, thresh: float, ret_steps: int = 10, should_reset_global_cache: bool = True):
         """The reference's EasyCache switch (R/src/transformer/wan/base/model.py:1645-1672): from now on `forward` serves
@@ -241,35 +187,11 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
         self._easy_cache = None
         return self
 
-    def _apply(self, fn, *a, **k):
-        self._packed = False
-        self._ws = {}
-        self._rope = {}
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, *a, **k):
-        self._packed = False
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
-        g = torch.Generator(device=self.device)
-        g.manual_seed(seed)
-        for name, p in self.named_parameters():
-            if name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight", "norm1.weight", "norm_added_k.weight")):
-                p.data.fill_(1.0)
-            elif name.endswith("scale_shift_table"):
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) / p.shape[-1] ** 0.5).to(p.dtype))
-            elif name.endswith(".bias"):
-                p.data.copy_((torch.randn(p.shape, generator=g, device=p.device) * 0.01).to(p.dtype))
-            else:
-                flat = p.data.view(-1)
-                step = 1 << 26
-                for i in range(0, flat.numel(), step):
-                    n = min(step, flat.numel() - i)
-                    flat[i:i + n] = (torch.randn(n, generator=g, device=p.device) * std).to(p.dtype)
-        self._packed = False
-        return self
+        return self._fill_synthetic(
+            seed, std, ones=lambda name, p: name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight", "norm1.weight",
+                                                            "norm_added_k.weight")),
+            row_scaled=lambda name, p: name.endswith("scale_shift_table"))
 
     @torch.no_grad()
     def pack(self):
@@ -279,28 +201,14 @@ class WanTransformer3DModel(LoraAdapterMixin, nn.Module):
             raise _l.ApexMIError("wan.mi355: the block weights are resident quantised records (keep_fp8 / keep_quantized load) and their "
                                  "bf16 storage is gone; "
                                  "moving / re-packing such a model is not supported — construct and load again")
-        dev, dt = self.device, self.dtype
-        if dev.type != "cuda" or dt != torch.bfloat16:
-            raise _l.ApexMIError(f"wan.mi355 needs bf16 weights on a ROCm device (got {dt} on {dev}); "
-                                 "there is no CPU fallback")
-        dim = self.inner_dim
-        L = len(self.blocks)
+        dev, _ = self._pack_target()
         for blk in self.blocks:
             a1, a2 = blk.attn1, blk.attn2
-            blk._wqkv = torch.empty(3 * dim, dim, device=dev, dtype=dt)
-            blk._bqkv = torch.empty(3 * dim, device=dev, dtype=dt)
-            _repoint([a1.to_q.weight, a1.to_k.weight, a1.to_v.weight], blk._wqkv)
-            _repoint([a1.to_q.bias, a1.to_k.bias, a1.to_v.bias], blk._bqkv)
-            blk._wkv2 = torch.empty(2 * dim, dim, device=dev, dtype=dt)
-            blk._bkv2 = torch.empty(2 * dim, device=dev, dtype=dt)
-            _repoint([a2.to_k.weight, a2.to_v.weight], blk._wkv2)
-            _repoint([a2.to_k.bias, a2.to_v.bias], blk._bkv2)
+            blk._wqkv, blk._bqkv = _fuse_linears([a1.to_q, a1.to_k, a1.to_v])
+            blk._wkv2, blk._bkv2 = _fuse_linears([a2.to_k, a2.to_v])
             if hasattr(a2, "add_k_proj"):      # image k|v, packed like _wkv2
-                blk._wkvi = torch.empty(2 * dim, a2.add_k_proj.in_features, device=dev, dtype=dt)
-                blk._bkvi = torch.empty(2 * dim, device=dev, dtype=dt)
-                _repoint([a2.add_k_proj.weight, a2.add_v_proj.weight], blk._wkvi)
-                _repoint([a2.add_k_proj.bias, a2.add_v_proj.bias], blk._bkvi)
-        self._ones = torch.ones(dim, device=dev, dtype=torch.float32)
+                blk._wkvi, blk._bkvi = _fuse_linears([a2.add_k_proj, a2.add_v_proj])
+        self._ones = torch.ones(self.inner_dim, device=dev, dtype=torch.float32)
         self._packed = True
         self._weights_changed()
 
