@@ -1,4 +1,4 @@
-"""The "hip_mfma" and "hip_mfma_sdpa" attention backends — B-op plug-in point.
+"""The "hip_mfma", "hip_mfma_sdpa" and "hip_mfma_window" attention backends — B-op plug-in point.
 
 Honours the calling convention of every backend in the reference's attention_register
 (apps/api/src/attention/functions.py:84, e.g. `sdpa` :338-377):
@@ -21,6 +21,11 @@ any attn_mask broadcastable to [B, Hq, Sq, Sk] (bool keep-mask, or additive floa
 aligned, AND-ed with the mask), grouped-query heads with enable_gqa, bf16 / f16, D = 64 or 128.  A query row with no allowed
 key returns zeros (as torch's CPU sdpa).  No host sync for any input.  Dropout, other dtypes or head sizes and CPU tensors
 raise ApexMIError; nothing falls back to torch.
+
+"hip_mfma_window" (KEY_WINDOW) is coordinate-window sparse attention (ops.attention_window): the reference
+calling convention plus `window_plan=` (an ops.WindowPlan from ops.window_plan) in **kwargs.  An opt-in approximation of the
+caller's choosing: keys outside the window are not attended.  attn_mask, is_causal, dropout and a missing plan raise; nothing
+falls back to dense attention.
 """
 from __future__ import annotations
 
@@ -31,6 +36,7 @@ from .lib import ApexMIError
 
 KEY = "hip_mfma"
 KEY_SDPA = "hip_mfma_sdpa"
+KEY_WINDOW = "hip_mfma_window"
 
 
 def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False,
@@ -68,6 +74,19 @@ def hip_mfma_sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bo
     return ops.attention_masked(q, k, v, attn_mask, is_causal=is_causal, softmax_scale=softmax_scale, enable_gqa=enable_gqa)
 
 
+def hip_mfma_window(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None,
+                    enable_gqa: bool = False, window_plan=None, **kwargs):
+    if dropout_p:
+        raise ApexMIError("hip_mfma_window: dropout is not supported (inference only)")
+    if is_causal:
+        raise ApexMIError("hip_mfma_window: causal attention is not supported (use hip_mfma_sdpa)")
+    if attn_mask is not None:
+        raise ApexMIError("hip_mfma_window: attn_mask is not supported next to a window (use hip_mfma_sdpa with a mask)")
+    if window_plan is None:
+        raise ApexMIError("hip_mfma_window: window_plan= (ops.window_plan(...)) is required; there is no dense fallback")
+    return ops.attention_window(q, k, v, window_plan, softmax_scale=softmax_scale, enable_gqa=enable_gqa)
+
+
 def _key_keep_mask(attn_mask: torch.Tensor, B: int, Sk: int) -> torch.Tensor:
     """attn_mask (bool keep-mask, or additive: finite-and-not-hugely-negative = keep) -> bool [B, Sk]; raises unless the mask
     is constant along the head and query dimensions."""
@@ -98,11 +117,12 @@ def available() -> bool:
 
 
 def register(attention_register, set_default: bool = False, overwrite: bool = True):
-    """Register under KEY and KEY_SDPA in the given FunctionRegister (the reference's, or register.attention_register);
+    """Register under KEY, KEY_SDPA and KEY_WINDOW in the given FunctionRegister (the reference's, or register.attention_register);
     set_default makes KEY the default."""
     ok = available()
     attention_register(KEY, overwrite=overwrite, available=ok)(hip_mfma)
     attention_register(KEY_SDPA, overwrite=overwrite, available=ok)(hip_mfma_sdpa)
+    attention_register(KEY_WINDOW, overwrite=overwrite, available=ok)(hip_mfma_window)
     if set_default:
         attention_register.set_default(KEY)
     return attention_register

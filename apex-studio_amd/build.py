@@ -39,7 +39,7 @@ if os.environ.get("APEXMI_DEBUG", "0") not in ("", "0"):
 # the build or spills — the second is silent, so every build parses `-Rpass-analysis=kernel-resource-usage` and refuses a binary
 # whose listed kernels use scratch or spill (source file -> substrings of the mangled kernel names).
 NO_SPILL = {"attention.hip": ["attn_fwd_d128_w64_kernel", "attn_fwd_d128_w64r_kernel"],
-            "attention_masked.hip": ["attn_masked_kernel"], "attention_dual.hip": ["attn_dual_kernel"]}
+            "attention_masked.hip": ["attn_masked_kernel", "attn_window_map_kernel"], "attention_dual.hip": ["attn_dual_kernel"]}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 
 

@@ -17,6 +17,15 @@
 //   * causal: the key-tile range of a workgroup is computed from its query block (tiles above the diagonal are never in the
 //     list), only the tiles that cross the diagonal compare per element, and the query blocks of the whole launch run heaviest
 //     first so the short ones fill the last round.
+//
+// COORDINATE WINDOW (attn_masked_kernel<.., WIN = true>, apexmi_attn_fwd_window / apexmi_attn_fwd_prepared_window): the mask is
+// a rule instead of an array.  Every token carries three int16 coordinates (one 8-byte record {c0, c1, c2, 0}); key j is allowed
+// for query i iff |cq[i][a] - ck[j][a]| <= r[a] on the three axes, one window for all batches and heads.  The block map of that
+// rule is built ONCE per plan by attn_window_map_kernel from the two coordinate arrays (no Sq x Sk array exists anywhere); the
+// kernel walks it exactly as it walks a mask's map, and a PARTIAL tile evaluates the rule in registers: the lane holds its query
+// row's coordinates from entry, the tile's 64 key records arrive in LDS with the tile (one 8-byte load per key, wave 0, issued
+// with the tile's staging and written before the barrier that publishes the tile).  Excluded scores become -inf through the
+// same fmaf as a bool mask's, so the result equals apexmi_attn_fwd_masked on the equivalent dense bool mask bit for bit.
 #include "common.h"
 
 #include <cstdint>
@@ -80,7 +89,69 @@ struct MaskedArgs {
     int64_t m_sb, m_sh, m_sq, m_sk;   // element strides of the mask broadcast to [B, Hq, Sq, Sk] (0 on broadcast dims)
     int Hq, group, Sq, Sk, Skp, nqb, nkt, total, mkind, causal, neg;
     float c;                // |scale| * log2(e)
+    // coordinate window (WIN kernels only): packed records {c0, c1, c2, 0} as 4 x int16 per token, radii clamped to 65535
+    const u32x2* wq;
+    const u32x2* wk;
+    int wr0, wr1, wr2;
 };
+
+// coordinate a (0..2) of a packed record, sign-extended
+APEXMI_DEVICE int wcoord0(u32x2 c) { return (int)(c[0] << 16) >> 16; }
+APEXMI_DEVICE int wcoord1(u32x2 c) { return (int)c[0] >> 16; }
+APEXMI_DEVICE int wcoord2(u32x2 c) { return (int)(c[1] << 16) >> 16; }
+
+// Block map of a coordinate window, built once per plan: one WAVE per (128-row query block, 64-key tile), 4 tiles per workgroup.
+// Lane l holds key l of the tile and query rows l and l + 64 of the block (indices clamped into the arrays: a clamped index
+// repeats a row / key of the same block / tile, which changes neither a bounding box nor a classification).  The two bounding
+// boxes settle most tiles: SKIP when on some axis the boxes are more than r apart, DENSE when on every axis the farthest pair
+// of box corners is within r.  The undecided tiles take the exact pass: 128 steps, one query row against the 64 keys each.
+// The codes equal what attn_mask_map_kernel gives for the dense bool mask of the same rule, ragged tails included.
+__global__ __launch_bounds__(256) void attn_window_map_kernel(const u32x2* __restrict__ wq, const u32x2* __restrict__ wk, int r0,
+                                                              int r1, int r2, int Sq, int Sk, int nkt,
+                                                              uint8_t* __restrict__ map) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6), qb = blockIdx.y;
+    if (t >= nkt) return;   // wave-uniform; no barrier below
+    const int q_lo = qb * MQB, q_n = min(Sq - q_lo, MQB);      // q_n >= 1
+    const int k_lo = t * MKV, k_n = min(Sk - k_lo, MKV);        // k_n >= 1
+    const u32x2 kc = wk[k_lo + min(lane, k_n - 1)];
+    const u32x2 qa = wq[q_lo + min(lane, q_n - 1)], qc = wq[q_lo + min(lane + 64, q_n - 1)];
+    const int k0 = wcoord0(kc), k1 = wcoord1(kc), k2 = wcoord2(kc);
+    int lo[6], hi[6];   // 0..2: keys, 3..5: queries
+    lo[0] = hi[0] = k0, lo[1] = hi[1] = k1, lo[2] = hi[2] = k2;
+    lo[3] = min(wcoord0(qa), wcoord0(qc)), hi[3] = max(wcoord0(qa), wcoord0(qc));
+    lo[4] = min(wcoord1(qa), wcoord1(qc)), hi[4] = max(wcoord1(qa), wcoord1(qc));
+    lo[5] = min(wcoord2(qa), wcoord2(qc)), hi[5] = max(wcoord2(qa), wcoord2(qc));
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            lo[i] = min(lo[i], __shfl_xor(lo[i], m));
+            hi[i] = max(hi[i], __shfl_xor(hi[i], m));
+        }
+    const int r[3] = {r0, r1, r2};
+    bool apart = false, within = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        apart = apart || lo[a] - hi[3 + a] > r[a] || lo[3 + a] - hi[a] > r[a];
+        within = within && hi[a] - lo[3 + a] <= r[a] && hi[3 + a] - lo[a] <= r[a];
+    }
+    int code = apart ? MAP_SKIP : within ? MAP_DENSE : -1;
+    if (code < 0) {   // wave-uniform
+        const uint64_t valid = k_n == 64 ? ~0ull : (1ull << k_n) - 1;
+        bool any = false, dense = true;
+        for (int i = 0; i < q_n; ++i) {
+            const u32x2 q = wq[q_lo + i];   // one address for the wave
+            const bool ok = (uint32_t)(wcoord0(q) - k0 + r0) <= 2u * (uint32_t)r0 && (uint32_t)(wcoord1(q) - k1 + r1) <= 2u * (uint32_t)r1 &&
+                            (uint32_t)(wcoord2(q) - k2 + r2) <= 2u * (uint32_t)r2;
+            const uint64_t bal = __ballot(ok) & valid;
+            any = any || bal != 0;
+            dense = dense && bal == valid;
+        }
+        code = !any ? MAP_SKIP : dense ? MAP_DENSE : MAP_PARTIAL;
+    }
+    if (lane == 0) map[(int64_t)qb * nkt + t] = (uint8_t)code;
+}
 
 // Block map pre-pass: one workgroup per (key tile, query block, own mask (batch, head)).  SKIP: no allowed element; DENSE:
 // every element allowed with additive value 0; PARTIAL otherwise.  VEC (host: key stride 1, 16-byte aligned rows): whole tiles
@@ -157,7 +228,7 @@ __global__ __launch_bounds__(256) void v_transpose64_kernel(const uint16_t* __re
 // row i of a 32-row K sub-tile holds key mperm32(i): bits 2 and 3 swapped (as attention.hip's perm32)
 APEXMI_DEVICE int mperm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
-template <typename E, int D>
+template <typename E, int D, bool WIN>
 __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using v8 = typename E::v8;
@@ -268,6 +339,17 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
     }
     const int64_t m_row = (int64_t)b * a.m_sb + (int64_t)h * a.m_sh + (int64_t)qrow_c * a.m_sq;
 
+    // coordinate window: |cq - ck| <= r  <=>  (unsigned)(cq + r - ck) <= 2 r; the lane keeps cq + r of its query row.  The key
+    // records of a PARTIAL tile live behind the tile list, one 512-byte image per LDS stage.
+    int wqa0 = 0, wqa1 = 0, wqa2 = 0;
+    u32x2 wk_next = u32x2{0u, 0u};
+    u32x2* wk_lds = (u32x2*)(smem + 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15));
+    if (WIN) {
+        const u32x2 cq = a.wq[qrow_c];
+        wqa0 = wcoord0(cq) + a.wr0, wqa1 = wcoord1(cq) + a.wr1, wqa2 = wcoord2(cq) + a.wr2;
+    }
+    const uint32_t w2r0 = 2u * (uint32_t)a.wr0, w2r1 = 2u * (uint32_t)a.wr1, w2r2 = 2u * (uint32_t)a.wr2;
+
     f32x16 oacc[NDT];
 #pragma unroll
     for (int dt = 0; dt < NDT; ++dt)
@@ -278,17 +360,23 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
 
     __syncthreads();
     const int n = *list_n;
-    if (n > 0) stage(0, list[0] & (MAX_TILES - 1));
+    if (n > 0) {
+        stage(0, list[0] & (MAX_TILES - 1));
+        if (WIN && wave == 0 && (list[0] >> 14) == MAP_PARTIAL) wk_next = a.wk[min((list[0] & (MAX_TILES - 1)) * MKV + lane, a.Sk - 1)];
+    }
     for (int it = 0; it < n; ++it) {
         const int ent = list[it];
         const int t = ent & (MAX_TILES - 1), code = ent >> 14;
         const int kv0 = t * MKV;
+        // window: this tile's key records (loaded with its staging) into the image of its stage; the image was last read two
+        // tiles ago, before the barrier every wave has passed since
+        if (WIN && wave == 0 && code == MAP_PARTIAL) wk_lds[(it & 1) * MKV + lane] = wk_next;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's LDS-DMA has landed (see attention.hip)
         __syncthreads();
 
         // mask values of a PARTIAL tile, issued before the next tile's staging so waiting for them does not wait for it
         float mv[2][16];
-        if (code == MAP_PARTIAL) {
+        if (!WIN && code == MAP_PARTIAL) {
 #define MASK_LOADS(MK)                                                                                          \
     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) _Pragma("unroll") for (int r = 0; r < 16; ++r) {           \
         const int g = r >> 2;                                                                                   \
@@ -303,7 +391,11 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
             }
 #undef MASK_LOADS
         }
-        if (it + 1 < n) stage((it + 1) & 1, list[it + 1] & (MAX_TILES - 1));
+        if (it + 1 < n) {
+            stage((it + 1) & 1, list[it + 1] & (MAX_TILES - 1));
+            if (WIN && wave == 0 && (list[it + 1] >> 14) == MAP_PARTIAL)
+                wk_next = a.wk[min((list[it + 1] & (MAX_TILES - 1)) * MKV + lane, a.Sk - 1)];
+        }
         const char* Ks = smem + (it & 1) * STAGE;
         const char* Vs = Ks + K_TILE;
 
@@ -330,6 +422,19 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
             const bool part = code == MAP_PARTIAL;
             const int lim = a.causal ? min(a.Sk - 1, qrow) : a.Sk - 1;
             mx = -__builtin_inff();
+            if (WIN && part) {   // the rule, evaluated on the tile's key records: 0 (keep) or -inf, as a bool mask's values
+                const u32x2* kc = wk_lds + (it & 1) * MKV;
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int g = r >> 2;
+                        const u32x2 c = kc[kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3)];
+                        const bool ok = (uint32_t)(wqa0 - wcoord0(c)) <= w2r0 && (uint32_t)(wqa1 - wcoord1(c)) <= w2r1 &&
+                                        (uint32_t)(wqa2 - wcoord2(c)) <= w2r2;
+                        mv[kt][r] = ok ? 0.0f : -__builtin_inff();
+                    }
+            }
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
@@ -424,16 +529,44 @@ size_t vt_bytes(int B, int Hkv, int Sk, int D) {
     return align256((size_t)B * Hkv * D * skp * 2);
 }
 
-template <typename E, int D>
+template <typename E, int D, bool WIN = false>
 int launch_masked(const MaskedArgs& a, hipStream_t stream) {
     constexpr int STAGE = 2 * MKV * D * 2;
+    constexpr int WK = WIN ? 2 * MKV * 8 : 0;   // the two key-record images of a window launch
     static uint64_t attr_done = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D>,
+    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D, WIN>,
                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                              2 * STAGE + 16 + 2 * MAX_TILES));
-    const int lds = 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15);
-    hipLaunchKernelGGL((attn_masked_kernel<E, D>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
-    return apexmi_check_launch("attn_fwd_masked");
+                                                              2 * STAGE + 16 + 2 * MAX_TILES + WK));
+    const int lds = 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15) + WK;
+    hipLaunchKernelGGL((attn_masked_kernel<E, D, WIN>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
+    return apexmi_check_launch(WIN ? "attn_fwd_window" : "attn_fwd_masked");
+}
+
+// V [B, Hkv, Sk, D] (strided rows) -> V^T [B, Hkv, D, Skp] zero padded
+int transpose_v(const void* v, const int64_t v_strides[3], int B, int Hkv, int Sk, int Skp, int D, uint16_t* vt,
+                apexmi_stream_t stream_) {
+    if (D == 128) {
+        for (int b = 0; b < B; ++b)
+            if (int rc = apexmi_v_transpose((const uint16_t*)v + b * v_strides[0], v_strides[1], v_strides[2], Sk, Hkv, D,
+                                            vt + (size_t)b * Hkv * D * Skp, Skp, 0, stream_))
+                return rc;
+        return 0;
+    }
+    hipLaunchKernelGGL(v_transpose64_kernel, dim3(Skp / 64, Hkv, B), dim3(256), 0, (hipStream_t)stream_, (const uint16_t*)v,
+                       v_strides[0], v_strides[1], v_strides[2], Hkv, Sk, Skp, vt);
+    return apexmi_check_launch("attn_fwd_masked (V^T)");
+}
+
+// the window operands of a launch: coordinates, radii (clamped: two int16 differ by at most 65535) and the plan's block map
+int window_args(MaskedArgs& a, const void* q_coords, const void* k_coords, int r0, int r1, int r2, const void* map,
+                const char* who) {
+    APEXMI_REQUIRE(q_coords && k_coords && map, "%s: null window operand (coordinates / block map)", who);
+    APEXMI_REQUIRE(((uintptr_t)q_coords % 8) == 0 && ((uintptr_t)k_coords % 8) == 0, "%s: coordinate records must be 8-byte aligned", who);
+    APEXMI_REQUIRE(r0 >= 0 && r1 >= 0 && r2 >= 0, "%s: negative radius (%d, %d, %d)", who, r0, r1, r2);
+    a.wq = (const u32x2*)q_coords, a.wk = (const u32x2*)k_coords;
+    a.wr0 = r0 < 65535 ? r0 : 65535, a.wr1 = r1 < 65535 ? r1 : 65535, a.wr2 = r2 < 65535 ? r2 : 65535;
+    a.map = (const uint8_t*)map;   // [nqb, nkt]: one window for every batch and head (mask strides stay 0)
+    return 0;
 }
 
 template <int MK, typename ET>
@@ -496,16 +629,7 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
     // V^T [B, Hkv, D, Skp]
     uint16_t* vt = (uint16_t*)workspace;
     a.vt = vt;
-    if (D == 128) {
-        for (int b = 0; b < B; ++b)
-            if (int rc = apexmi_v_transpose((const uint16_t*)v + b * v_strides[0], v_strides[1], v_strides[2], Sk, Hkv, D,
-                                            vt + (size_t)b * Hkv * D * a.Skp, a.Skp, 0, stream_))
-                return rc;
-    } else {
-        hipLaunchKernelGGL(v_transpose64_kernel, dim3(a.Skp / 64, Hkv, B), dim3(256), 0, stream, (const uint16_t*)v,
-                           v_strides[0], v_strides[1], v_strides[2], Hkv, Sk, a.Skp, vt);
-        if (int rc = apexmi_check_launch("attn_fwd_masked (V^T)")) return rc;
-    }
+    if (int rc = transpose_v(v, v_strides, B, Hkv, Sk, a.Skp, D, vt, stream_)) return rc;
 
     // block map of the mask over its own (batch, head) dims
     if (mask) {
@@ -527,4 +651,102 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
     ApexmiProfScope prof(1, stream, 4.0 * B * Hq * (double)Sq * Sk * D, 0.0);
     if (dtype == APEXMI_BF16) return D == 128 ? launch_masked<ElemBf16, 128>(a, stream) : launch_masked<ElemBf16, 64>(a, stream);
     return D == 128 ? launch_masked<ElemF16, 128>(a, stream) : launch_masked<ElemF16, 64>(a, stream);
+}
+
+// ---- coordinate window ------------------------------------------------------------------------------------------------------
+
+extern "C" size_t apexmi_attn_window_map_bytes(int Sq, int Sk) {
+    if (Sq <= 0 || Sk <= 0) return 0;
+    return (size_t)((Sq + MQB - 1) / MQB) * (size_t)((Sk + MKV - 1) / MKV);
+}
+
+extern "C" int apexmi_attn_window_map(const void* q_coords, const void* k_coords, int Sq, int Sk, int r0, int r1, int r2,
+                                      void* map, size_t map_bytes, apexmi_stream_t stream_) {
+    APEXMI_REQUIRE(Sq > 0 && Sk > 0, "attn_window_map: empty problem (Sq=%d Sk=%d)", Sq, Sk);
+    const int nqb = (Sq + MQB - 1) / MQB, nkt = (Sk + MKV - 1) / MKV;
+    APEXMI_REQUIRE(nkt <= MAX_TILES, "attn_window_map: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE(nqb <= 65535, "attn_window_map: Sq=%d above %d query rows", Sq, 65535 * MQB);
+    APEXMI_REQUIRE(map && map_bytes >= apexmi_attn_window_map_bytes(Sq, Sk), "attn_window_map: map buffer too small (%zu < %zu)",
+                   map_bytes, apexmi_attn_window_map_bytes(Sq, Sk));
+    MaskedArgs a{};
+    if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, "attn_window_map")) return rc;
+    hipLaunchKernelGGL(attn_window_map_kernel, dim3((nkt + 3) / 4, nqb), dim3(256), 0, (hipStream_t)stream_, a.wq, a.wk, a.wr0,
+                       a.wr1, a.wr2, Sq, Sk, nkt, (uint8_t*)map);
+    return apexmi_check_launch("attn_window_map");
+}
+
+extern "C" int apexmi_attn_fwd_window(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq,
+                                      int Sk, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                                      const int64_t v_strides[3], const int64_t o_strides[3], const void* q_coords,
+                                      const void* k_coords, int r0, int r1, int r2, const void* map, float softmax_scale,
+                                      int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attn_fwd_window: null operand");
+    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "attn_fwd_window: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)",
+                   B, Hq, Hkv, Sq, Sk);
+    APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_window: head dim %d unsupported (64 or 128)", D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_window: dtype %d unsupported (bf16 or f16)", dtype);
+    APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_window: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
+    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_window: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_window: too many query blocks");
+    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
+    for (int i = 0; i < 3; ++i)
+        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
+    APEXMI_REQUIRE(aligned, "attn_fwd_window: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
+    const size_t need = vt_bytes(B, Hkv, Sk, D);
+    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "attn_fwd_window: workspace too small (%zu < %zu)", workspace_bytes, need);
+
+    MaskedArgs a{};
+    if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, "attn_fwd_window")) return rc;
+    a.q = (const uint16_t*)q;
+    a.k = (const uint16_t*)k;
+    a.o = (uint16_t*)out;
+    a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
+    a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
+    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + MKV - 1) / MKV) * MKV;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * Hq * a.nqb;
+    a.neg = softmax_scale < 0.0f;
+    a.c = fabsf(softmax_scale) * LOG2E_F;
+    uint16_t* vt = (uint16_t*)workspace;
+    a.vt = vt;
+    if (int rc = transpose_v(v, v_strides, B, Hkv, Sk, a.Skp, D, vt, stream_)) return rc;
+
+    ApexmiProfScope prof(1, stream, 4.0 * B * Hq * (double)Sq * Sk * D, 0.0);
+    if (dtype == APEXMI_BF16)
+        return D == 128 ? launch_masked<ElemBf16, 128, true>(a, stream) : launch_masked<ElemBf16, 64, true>(a, stream);
+    return D == 128 ? launch_masked<ElemF16, 128, true>(a, stream) : launch_masked<ElemF16, 64, true>(a, stream);
+}
+
+extern "C" int apexmi_attn_fwd_prepared_window(const void* q, const void* k, const void* vt, void* out, int B, int H, int Sq,
+                                               int Sk, int Skp, const int64_t o_strides[3], const void* q_coords,
+                                               const void* k_coords, int r0, int r1, int r2, const void* map,
+                                               float softmax_scale, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    constexpr int D = 128;
+    APEXMI_REQUIRE(q && k && vt && out && o_strides, "attn_fwd_prepared_window: null operand");
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attn_fwd_prepared_window: empty problem");
+    APEXMI_REQUIRE(Skp % MKV == 0 && Skp >= Sk, "attn_fwd_prepared_window: Skp=%d must be Sk=%d rounded up to 64", Skp, Sk);
+    APEXMI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0,
+                   "attn_fwd_prepared_window: operands must be 16-byte aligned");
+    APEXMI_REQUIRE(o_strides[0] % 4 == 0 && o_strides[1] % 4 == 0 && o_strides[2] % 4 == 0,
+                   "attn_fwd_prepared_window: output strides must be multiples of 4 elements");
+    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_prepared_window: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((int64_t)B * H * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_prepared_window: too many query blocks");
+
+    MaskedArgs a{};
+    if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, "attn_fwd_prepared_window")) return rc;
+    a.q = (const uint16_t*)q;
+    a.k = (const uint16_t*)k;
+    a.vt = (const uint16_t*)vt;
+    a.o = (uint16_t*)out;
+    a.q_sb = (int64_t)H * Sq * D, a.q_sh = (int64_t)Sq * D, a.q_ss = D;
+    a.k_sb = (int64_t)H * Sk * D, a.k_sh = (int64_t)Sk * D, a.k_ss = D;
+    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    a.Hq = H, a.group = 1, a.Sq = Sq, a.Sk = Sk, a.Skp = Skp;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * H * a.nqb;
+    a.neg = softmax_scale < 0.0f;
+    a.c = fabsf(softmax_scale) * LOG2E_F;
+    ApexmiProfScope prof(1, stream, 4.0 * B * H * (double)Sq * Sk * D, 0.0);
+    return launch_masked<ElemBf16, 128, true>(a, stream);
 }

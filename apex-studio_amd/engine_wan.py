@@ -24,7 +24,7 @@ class WanT2VEngine(EngineLoraMixin):
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
-                 residual_dtype: Optional[torch.dtype] = None):
+                 residual_dtype: Optional[torch.dtype] = None, attention_window=None):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -35,6 +35,12 @@ class WanT2VEngine(EngineLoraMixin):
         if residual_dtype is not None:
             for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
                 tr.set_residual_dtype(residual_dtype)
+        # (frames, rows, cols) in token units: both experts' self-attention stays inside that window (`set_attention_window`,
+        # an opt-in approximation); None = dense
+        self.attention_window = None if attention_window is None else tuple(attention_window)
+        if attention_window is not None:
+            for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
+                tr.set_attention_window(self.attention_window)
         self.vae = vae
         self.scheduler = scheduler or UniPCMultistepScheduler(shift=3.0)
         self.boundary_ratio = boundary_ratio
@@ -225,9 +231,10 @@ class WanI2VEngine(WanT2VEngine):
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
-                 residual_dtype: Optional[torch.dtype] = None):
+                 residual_dtype: Optional[torch.dtype] = None, attention_window=None):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
-                         vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype)
+                         vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
+                         attention_window=attention_window)
         self.image_encoder = image_encoder
 
     @property

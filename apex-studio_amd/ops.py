@@ -702,6 +702,32 @@ def attention_prepared(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: 
     return out
 
 
+def attention_prepared_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, Sk: int,
+                              plan: "WindowPlan", scale: Optional[float] = None) -> torch.Tensor:
+    """attention_prepared restricted to the coordinate window of `plan` (window_plan): q [B,H,Sq,128], k [B,H,Sk,128],
+    vt [B,H,128,Skp] packed bf16; out [B,Sq,H,128] (strided ok).  Bit-identical to attention_masked on the window's dense bool
+    mask; the f32-storage verification mode has no window kernel."""
+    _req(q, None, "attention_window.q")
+    if q.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"attention_prepared_window: bf16 operands only, got {q.dtype} (the f32-storage verification mode "
+                             "has no window attention)")
+    for t_ in (k, vt, out):
+        _req(t_, torch.bfloat16, "attention_window operand")
+    B, H, Sq, D = q.shape
+    assert D == 128 and q.is_contiguous() and k.is_contiguous() and vt.is_contiguous()
+    assert k.shape == (B, H, Sk, D) and vt.shape[:3] == (B, H, D) and vt.shape[3] >= (Sk + 63) // 64 * 64
+    assert out.shape == (B, Sq, H, D) and out.stride(3) == 1
+    plan.check(Sq, Sk, q.device, "attention_prepared_window")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    rc = _l.load().apexmi_attn_fwd_prepared_window(
+        q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), B, H, Sq, Sk, vt.shape[3],
+        _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), plan.q_coords.data_ptr(), plan.k_coords.data_ptr(),
+        *plan.radius, plan.block_map.data_ptr(), float(scale), _stream())
+    _l.check(rc, "attn_fwd_prepared_window")
+    return out
+
+
 def attention_prepared_dual(q: torch.Tensor, k_t: torch.Tensor, vt_t: torch.Tensor, Sk_t: int,
                             k_i: Optional[torch.Tensor], vt_i: Optional[torch.Tensor], Sk_i: int, out: torch.Tensor,
                             scale: Optional[float] = None) -> torch.Tensor:
@@ -856,6 +882,153 @@ def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mas
                                     _ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale),
                                     _DT[q.dtype], ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_masked")
+    return out.permute(0, 2, 1, 3)
+
+
+class WindowPlan:
+    """A coordinate window, ready to launch (window_plan): the packed coordinates `q_coords` [Sq, 4] / `k_coords` [Sk, 4] int16
+    ({c0, c1, c2, 0} per token; one tensor for self-attention), the clamped `radius` and the `block_map` uint8 [ceil(Sq / 128),
+    ceil(Sk / 64)] (0 SKIP, 1 DENSE, 2 PARTIAL) the kernel walks.  Built once; every launch only reads it."""
+
+    def __init__(self, q_coords: torch.Tensor, k_coords: torch.Tensor, radius: Tuple[int, int, int], block_map: torch.Tensor):
+        self.q_coords, self.k_coords, self.radius, self.block_map = q_coords, k_coords, radius, block_map
+        self.Sq, self.Sk = int(q_coords.shape[0]), int(k_coords.shape[0])
+
+    @property
+    def device(self):
+        return self.block_map.device
+
+    def check(self, Sq: int, Sk: int, device, who: str) -> None:
+        if (Sq, Sk) != (self.Sq, self.Sk):
+            raise _l.ApexMIError(f"{who}: the window plan is for (Sq, Sk) = ({self.Sq}, {self.Sk}), the operands have ({Sq}, {Sk})")
+        if device != self.device:
+            raise _l.ApexMIError(f"{who}: the window plan is on {self.device}, the operands on {device}")
+
+    def tile_counts(self) -> Tuple[int, int, int]:
+        """(SKIP, DENSE, PARTIAL) tiles of the block map (synchronises: diagnostics, not part of a step)."""
+        c = torch.bincount(self.block_map.flatten().long(), minlength=3).tolist()
+        return int(c[0]), int(c[1]), int(c[2])
+
+
+_I16 = (-32768, 32767)
+_INT_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64)
+
+
+def _check_window_coords(c, name: str) -> None:
+    if not isinstance(c, torch.Tensor) or c.dtype not in _INT_DTYPES:
+        raise _l.ApexMIError(f"window_plan: {name} must be an integer tensor, got {getattr(c, 'dtype', type(c))}")
+    if c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0:
+        raise _l.ApexMIError(f"window_plan: {name} must be [S, 3] with S >= 1, got shape {tuple(c.shape)}")
+    lo, hi = int(c.min()), int(c.max())      # plan build time only
+    if lo < _I16[0] or hi > _I16[1]:
+        raise _l.ApexMIError(f"window_plan: {name} values span [{lo}, {hi}], outside int16 (the kernel's 8-byte token record)")
+
+
+def _pack_window_coords(c: torch.Tensor, name: str, device) -> torch.Tensor:
+    """integer [S, 3] (CPU tensors are moved once) -> int16 [S, 4] records {c0, c1, c2, 0} on `device`"""
+    packed = torch.zeros((c.shape[0], 4), dtype=torch.int16, device=device)
+    packed[:, :3] = c.to(device=device, dtype=torch.int16)
+    return packed
+
+
+def window_plan(q_coords: torch.Tensor, k_coords: Optional[torch.Tensor] = None, radius: Sequence[int] = (0, 0, 0),
+                device=None) -> WindowPlan:
+    """Plan of a coordinate window for attention_window / attention_prepared_window: key j is allowed for query i iff
+    |q_coords[i][a] - k_coords[j][a]| <= radius[a] on the three axes (one window for all batches and heads).  q_coords [Sq, 3],
+    k_coords [Sk, 3] integer tensors on the device (CPU tensors are moved once, to `device` or the other operand's device);
+    k_coords=None is self-attention.  The block map is written here, once, by a HIP pre-pass over the two coordinate arrays;
+    nothing of size Sq x Sk is ever allocated."""
+    try:
+        r = tuple(int(x) for x in radius)
+    except TypeError as err:
+        raise _l.ApexMIError(f"window_plan: radius must be three integers, got {radius!r}") from err
+    if len(r) != 3 or any(x < 0 for x in r):
+        raise _l.ApexMIError(f"window_plan: radius must be three non-negative integers, got {radius!r}")
+    for c, name in ((q_coords, "q_coords"), (k_coords, "k_coords")):
+        if c is not None or name == "q_coords":
+            _check_window_coords(c, name)
+    tensors = [t for t in (q_coords, k_coords) if isinstance(t, torch.Tensor)]
+    tensors = [t for t in (q_coords, k_coords) if isinstance(t, torch.Tensor)]
+    devs = {t.device for t in tensors if t.is_cuda}
+    if len(devs) > 1:
+        raise _l.ApexMIError(f"window_plan: q_coords and k_coords are on different devices ({sorted(map(str, devs))})")
+    if devs:
+        dev = devs.pop()
+        if device is not None and torch.device(device) != dev:
+            raise _l.ApexMIError(f"window_plan: coordinates are on {dev}, device={device} was asked for")
+    elif device is not None:
+        dev = torch.device(device)
+    else:
+        if not torch.cuda.is_available():
+            raise _l.ApexMIError("window_plan: no ROCm device to build the plan on (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise _l.ApexMIError(f"window_plan: expected a ROCm device, got {dev} (no CPU fallback)")
+    qc = _pack_window_coords(q_coords, "q_coords", dev)
+    kc = qc if k_coords is None else _pack_window_coords(k_coords, "k_coords", dev)
+    r = tuple(min(x, 65535) for x in r)     # two int16 coordinates differ by at most 65535
+    Sq, Sk = qc.shape[0], kc.shape[0]
+    lib = _l.load()
+    nbytes = lib.apexmi_attn_window_map_bytes(Sq, Sk)
+    bmap = torch.empty(((Sq + 127) // 128, (Sk + 63) // 64), dtype=torch.uint8, device=dev)
+    assert bmap.numel() == nbytes
+    with torch.cuda.device(dev):
+        rc = lib.apexmi_attn_window_map(qc.data_ptr(), kc.data_ptr(), Sq, Sk, *r, bmap.data_ptr(), nbytes, _stream())
+    _l.check(rc, "attn_window_map")
+    return WindowPlan(qc, kc, r, bmap)
+
+
+def attention_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, plan: WindowPlan, softmax_scale: Optional[float] = None,
+                     enable_gqa: bool = False) -> torch.Tensor:
+    """softmax(q k^T scale over the keys inside the coordinate window of `plan`) v: attention_masked with the bool mask given as
+    the rule of window_plan, bit-identical to it on the equivalent dense mask, without that mask.  q [B,Hq,Sq,D], k / v
+    [B,Hkv,Sk,D] bf16 or f16 (permuted views welcome), D = 64 or 128; a row without any allowed key is zero.  Returns a
+    [B,Hq,Sq,D] view of a [B,Sq,Hq,D] buffer.  No host synchronisation."""
+    _req(q, None, "attention_window.q")
+    _req(k, None, "attention_window.k")
+    _req(v, None, "attention_window.v")
+    if not isinstance(plan, WindowPlan):
+        raise _l.ApexMIError(f"attention_window: plan must be an ops.WindowPlan (ops.window_plan), got {type(plan).__name__}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"attention_window: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise _l.ApexMIError("attention_window: q, k, v must be 4-D [B, H, S, D]")
+    B, Hq, Sq, D = q.shape
+    Bk, Hkv, Sk, Dk = k.shape
+    if D not in (64, 128):
+        raise _l.ApexMIError(f"attention_window: head dim {D} unsupported (64 or 128)")
+    if Bk != B or Dk != D or tuple(v.shape) != tuple(k.shape):
+        raise _l.ApexMIError(f"attention_window: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
+        raise _l.ApexMIError(f"attention_window: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
+                             "whole ratio")
+    if min(B, Hq, Sq, Sk) == 0:
+        raise _l.ApexMIError("attention_window: empty problem")
+    plan.check(Sq, Sk, q.device, "attention_window")
+
+    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
+        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
+        return t if ok else t.contiguous()
+
+    q, k, v = rows16(q), rows16(k), rows16(v)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
+    lib = _l.load()
+    need = lib.apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D)
+    key = ("masked", q.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        _ws_cache[key] = ws
+    rc = lib.apexmi_attn_fwd_window(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
+                                    _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
+                                    _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
+                                    _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
+                                    _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                    plan.q_coords.data_ptr(), plan.k_coords.data_ptr(), *plan.radius,
+                                    plan.block_map.data_ptr(), float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
+    _l.check(rc, "attn_fwd_window")
     return out.permute(0, 2, 1, 3)
 
 

@@ -113,7 +113,7 @@ class _Conv3dParams(nn.Module):
 class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "wan.mi355"
-    _drops = {"moved": ("_packed", "_ws", "_rope"), "loaded": ("_packed",), "storage": ("_ws",)}
+    _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
     _no_split_modules = ["_WanBlock"]
 
     def __init__(self, patch_size: Tuple[int, int, int] = (1, 2, 2), num_attention_heads: int = 40,
@@ -159,6 +159,8 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         self._ws: Dict[Any, Any] = {}
         self.fuse_qkv = os.environ.get("APEX_FUSE_QKV", "1") != "0"     # see _forward_one
         self._rope: Dict[Any, torch.Tensor] = {}
+        self._attention_window: Optional[Tuple[int, int, int]] = None     # set_attention_window
+        self._window_plans: Dict[Any, Any] = {}
 
     # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, the no-op knobs, ...) ----
     def _anchor(self):
@@ -186,6 +188,36 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     def disable_easy_cache(self):
         self._easy_cache = None
         return self
+
+    def set_attention_window(self, radius: Optional[Tuple[int, int, int]]):
+        """Opt-in approximation: self-attention attends only the keys within `radius` = (frames, rows, cols) of
+        the query on the post-patch token grid (|df| <= frames, |dh| <= rows, |dw| <= cols); None restores dense attention.
+        Cross-attention and everything else is untouched.  Not a quality claim: the caller picks the window."""
+        if radius is not None:
+            try:
+                radius = tuple(int(r) for r in radius)
+            except TypeError as err:
+                raise ValueError(f"wan.mi355: attention window radius must be (frames, rows, cols), got {radius!r}") from err
+            if len(radius) != 3 or any(r < 0 for r in radius):
+                raise ValueError(f"wan.mi355: attention window radius must be three non-negative integers, got {radius!r}")
+        self._attention_window = radius
+        self._window_plans = {}
+        return self
+
+    def _grid_ids(self, grid) -> torch.Tensor:
+        """(frame, row, column) of every token in sequence order: what RoPE rotates by and what the attention window measures"""
+        f, h, w = grid
+        dev = self.device
+        return torch.stack(torch.meshgrid(torch.arange(f, device=dev), torch.arange(h, device=dev),
+                                          torch.arange(w, device=dev), indexing="ij"), dim=-1).reshape(-1, 3)
+
+    def _window_plan(self, grid):
+        key = (grid, self._attention_window)
+        plan = self._window_plans.get(key)
+        if plan is None:
+            plan = ops.window_plan(self._grid_ids(grid), radius=self._attention_window)
+            self._window_plans = {key: plan}
+        return plan
 
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
         return self._fill_synthetic(
@@ -352,11 +384,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     def _rope_table(self, grid):
         t = self._rope.get(grid)
         if t is None:
-            f, h, w = grid
-            dev = self.device
-            ids = torch.stack(torch.meshgrid(torch.arange(f, device=dev), torch.arange(h, device=dev),
-                                             torch.arange(w, device=dev), indexing="ij"), dim=-1)
-            ids = ids.reshape(-1, 3).float().contiguous()
+            ids = self._grid_ids(grid).float().contiguous()
             hd = self.config.attention_head_dim
             hw_dim = 2 * (hd // 6)
             t = ops.rope_table_axes(ids, (hd - 2 * hw_dim, hw_dim, hw_dim), 10000.0)
@@ -409,6 +437,12 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
             ops.add_bcast(self._sst, ws.TPROJ[0], out=ws.MOD)    # scale_shift_table + temb.float()
         ops.add_bcast(self._sst_out.reshape(1, -1), torch.cat([ws.TEMB[0], ws.TEMB[0]]), out=ws.MOD2)
         rope = self._rope_table(grid)
+        wplan = None
+        if self._attention_window is not None:
+            if self.storage_dtype != torch.bfloat16:
+                raise NotImplementedError("wan.mi355: the f32-storage verification mode has no window attention; clear the "
+                                          "window (set_attention_window(None)) or run with bfloat16 storage")
+            wplan = self._window_plan(grid)
 
         q_in, k_in, v_in = QKV[:, :dim], QKV[:, dim:2 * dim], QKV[:, 2 * dim:]
         att_v = ATT.unflatten(-1, (H, 128)).unsqueeze(0)
@@ -429,7 +463,10 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
                 ops.ln_modulate(k_in, gamma=a1.norm_k.weight, out=k_in, eps=eps, rms=True)
                 ops.qkv_prepare(q_in, k_in, v_in, H, ws.Q[0], ws.K[0], ws.VT[0], rope=rope,
                                 rope_mode=_l.ROPE_INTERLEAVED)
-            ops.attention_prepared(ws.Q, ws.K, ws.VT, att_v, S)
+            if wplan is None:
+                ops.attention_prepared(ws.Q, ws.K, ws.VT, att_v, S)
+            else:
+                ops.attention_prepared_window(ws.Q, ws.K, ws.VT, att_v, S, wplan)
             ops.gemm(ATT, a1.to_out[0].weight, a1.to_out[0].bias, out=X, epilogue="gate_res", gate=m(2),
                      residual=X, lora_buf=ws.ATTf)
             # 2. cross attention over the text tokens (no RoPE, ungated residual)

@@ -148,6 +148,32 @@ int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* ou
                            int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
                            apexmi_stream_t stream);
 
+/* Coordinate-window sparse attention: apexmi_attn_fwd_masked with the mask given as a RULE instead of an array.  Every query and
+ * key token carries three integer coordinates, stored as one 8-byte record of 4 x int16 {c0, c1, c2, 0} (q_coords [Sq], k_coords
+ * [Sk], device memory; the same pointer twice for self-attention).  Key j is allowed for query i iff
+ *     |q_coords[i][a] - k_coords[j][a]| <= r_a   for a = 0, 1, 2     (r_a >= 0; one window for all batches and heads)
+ * and out = softmax(q k^T * softmax_scale over the allowed keys) v; a query row without any allowed key is written as zeros.
+ * The result is bit-identical to apexmi_attn_fwd_masked on the dense bool mask of the same rule, but no Sq x Sk array exists:
+ *   apexmi_attn_window_map  writes the block map ONCE per (coordinates, radii): one byte per (128-row query block, 64-key tile),
+ *       0 = no allowed pair (the tile is never loaded nor multiplied), 1 = all pairs allowed (the unmasked arithmetic),
+ *       2 = mixed (the kernel evaluates the rule per element); `map` holds apexmi_attn_window_map_bytes(Sq, Sk) bytes.
+ *   apexmi_attn_fwd_window  takes q / k / v, strides, dtype and D as apexmi_attn_fwd_masked does, plus the coordinates, the SAME
+ *       radii and the map; workspace >= apexmi_attn_masked_workspace_bytes(...) (V^T).
+ *   apexmi_attn_fwd_prepared_window  takes the prepared operands of apexmi_attn_fwd_prepared (bf16, D = 128: q [B,H,Sq,128],
+ *       k [B,H,Sk,128], vt [B,H,128,Skp] zero padded, out [B,Sq,H,128] with o_strides (b, s, h)): no second V transpose.
+ * Launch sizes depend on the shapes only; no call synchronises with the host. */
+size_t apexmi_attn_window_map_bytes(int Sq, int Sk);
+int apexmi_attn_window_map(const void* q_coords, const void* k_coords, int Sq, int Sk, int r0, int r1, int r2, void* map,
+                           size_t map_bytes, apexmi_stream_t stream);
+int apexmi_attn_fwd_window(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq, int Sk,
+                           int D, const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                           const int64_t o_strides[3], const void* q_coords, const void* k_coords, int r0, int r1, int r2,
+                           const void* map, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
+                           apexmi_stream_t stream);
+int apexmi_attn_fwd_prepared_window(const void* q, const void* k, const void* vt, void* out, int B, int H, int Sq, int Sk,
+                                    int Skp, const int64_t o_strides[3], const void* q_coords, const void* k_coords, int r0,
+                                    int r1, int r2, const void* map, float softmax_scale, apexmi_stream_t stream);
+
 /* Two-context cross-attention on prepared operands (bf16, D = 128): the image branch of Wan-2.1 I2V / FLF2V cross-attention,
  * replacing the reference's two attention calls and their sum (R/src/transformer/wan/base/model.py:207, 391-394; diffusers
  * WanAttnProcessor with add_k_proj).  The query attends the text keys and the image keys in two separate softmaxes:
