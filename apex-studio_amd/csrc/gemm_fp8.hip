@@ -1,0 +1,312 @@
+// Opt-in FP8 GEMM for resident fp8-scaled weights: a per-row e4m3 quantiser for the activations and a GEMM on
+// the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 x e4m3 at twice the bf16 rate per clock) with UNIT block scales; the
+// per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.
+#include "common.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+
+constexpr float FP8_MAX = 448.0f;        // largest finite e4m3fn value
+
+// ---- apexmi_quant_rows_fp8 ----------------------------------------------------------------------------------------------------
+// One wave per ROW PAIR (rows 2p, 2p + 1): the loads of both rows are in flight together.  Pass 1 reads the pair for its two
+// absmax values (wave reduction), pass 2 reads it again — 2 x K x 2 bytes, served by the cache the first pass filled, so HBM is
+// streamed once — and stores 16 codes (16 bytes) per lane and step.  K % 128 == 0: a step covers 64 lanes x 16 = 1024 elements,
+// the last one may be partial in whole 16-element groups.
+//   scale = absmax == 0 ? 1 : absmax / 448         (IEEE f32 division)
+//   code  = e4m3fn_rne(min(max(x / scale, -448), 448))   (IEEE f32 division, round to nearest even, subnormals kept)
+APEXMI_DEVICE float absmax16(const u32x4 a, const u32x4 b) {
+    float m = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(a[i])), fabsf(bf16_hi(a[i]))));
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(b[i])), fabsf(bf16_hi(b[i]))));
+    }
+    return m;
+}
+
+APEXMI_DEVICE float quant1(float x, float scale) {
+    const float y = __fdiv_rn(x, scale);
+    return fminf(fmaxf(y, -FP8_MAX), FP8_MAX);
+}
+
+// 4 bf16 (2 dwords) -> 4 e4m3fn codes in one dword (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950, round to nearest even)
+APEXMI_DEVICE uint32_t quant4(uint32_t lo, uint32_t hi, float scale) {
+    int r = 0;
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(bf16_lo(lo), scale), quant1(bf16_hi(lo), scale), r, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(bf16_lo(hi), scale), quant1(bf16_hi(hi), scale), r, true);
+    return (uint32_t)r;
+}
+
+__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __restrict__ a, int64_t lda, int M, int K,
+                                                             uint8_t* __restrict__ q, int64_t ldq, float* __restrict__ scales) {
+    const int lane = threadIdx.x & 63;
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int r0 = 2 * pair;
+    if (r0 >= M) return;                                   // wave-uniform
+    const int r1 = min(r0 + 1, M - 1);                     // odd M: the last pair reads its row twice and stores it once
+    const bf16_t* p0 = a + (int64_t)r0 * lda;
+    const bf16_t* p1 = a + (int64_t)r1 * lda;
+    float m0 = 0.f, m1 = 0.f;
+    for (int k = lane * 16; k < K; k += 1024) {
+        const u32x4 x0 = *(const u32x4*)(p0 + k), x1 = *(const u32x4*)(p0 + k + 8);
+        const u32x4 y0 = *(const u32x4*)(p1 + k), y1 = *(const u32x4*)(p1 + k + 8);
+        m0 = fmaxf(m0, absmax16(x0, x1));
+        m1 = fmaxf(m1, absmax16(y0, y1));
+    }
+    m0 = wave_max(m0);
+    m1 = wave_max(m1);
+    const float s0 = m0 == 0.f ? 1.0f : __fdiv_rn(m0, FP8_MAX);
+    const float s1 = m1 == 0.f ? 1.0f : __fdiv_rn(m1, FP8_MAX);
+    if (lane == 0) {
+        scales[r0] = s0;
+        if (r1 != r0) scales[r1] = s1;
+    }
+    uint8_t* q0 = q + (int64_t)r0 * ldq;
+    uint8_t* q1 = q + (int64_t)r1 * ldq;
+    for (int k = lane * 16; k < K; k += 1024) {
+        const u32x4 x0 = *(const u32x4*)(p0 + k), x1 = *(const u32x4*)(p0 + k + 8);
+        const u32x4 y0 = *(const u32x4*)(p1 + k), y1 = *(const u32x4*)(p1 + k + 8);
+        *(u32x4*)(q0 + k) = u32x4{quant4(x0[0], x0[1], s0), quant4(x0[2], x0[3], s0), quant4(x1[0], x1[1], s0), quant4(x1[2], x1[3], s0)};
+        if (r1 != r0)
+            *(u32x4*)(q1 + k) = u32x4{quant4(y0[0], y0[1], s1), quant4(y0[2], y0[3], s1), quant4(y1[0], y1[1], s1), quant4(y1[2], y1[3], s1)};
+    }
+}
+
+// ---- apexmi_gemm_fp8 ----------------------------------------------------------------------------------------------------------
+// 128 x 128 output tile, K-tile of 128 codes, 256 threads = 2 x 2 waves of 64 x 64 (2 x 2 MFMA tiles of 32 x 32, 64 accumulator
+// registers).  Both operands are K-contiguous bytes and staged by global_load_lds (16 bytes per lane) into ONE __shared__ array:
+//   lds[buf][operand][row 0..127][128 bytes], 16 KB per operand and buffer, 64 KB in all (two workgroups per CU).
+// A wave instruction writes 8 whole rows (64 lanes x 16 bytes = lane-linear); the XOR swizzle is on the SOURCE address:
+//   16-byte piece c of row r holds the row's bytes 16 (c ^ ((r >> 1) & 7)) ..,
+// so the 16 lanes of one ds_read_b128 phase (16 consecutive rows, one k position) cover all 64 banks once.
+// One barrier per K-tile: tile t + 1 is requested into the other buffer before tile t is read; the barrier's vmcnt(0) retires it.
+//
+// Operand lane map of v_mfma_scale_f32_32x32x64_f8f6f4 with 8-bit formats, as verified by the exact integer tests
+// (tests/test_gpu_gemm_fp8.py): lane l holds, in its 8 registers, the 32 codes k = 32 (l >> 5) + 0..31 of row (A) / column (B)
+// l & 31, byte j of the 32 = k offset j.  The result layout is the 32 x 32 one of every gfx950 MFMA: column l & 31, rows
+// (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  As in the bf16 kernels the WEIGHT tile is the A operand, so a lane holds 4 consecutive
+// output columns of one output row per register group and stores them as 8 bytes.
+constexpr int FBM = 128, FBN = 128, FBK = 128;
+constexpr int FOPB = FBM * FBK;              // bytes of one operand tile
+constexpr int UNIT_E8M0 = 0x7f7f7f7f;        // 2^0 in every byte: the block scales are not used
+
+struct Fp8Gemm {
+    const uint8_t* A;     // activation codes [M, K]
+    const uint8_t* W;     // weight codes [N, K]
+    const float* sa;      // [M]
+    const bf16_t* sw;     // [N] or [1]
+    const bf16_t* bias;   // [N] or null
+    bf16_t* C;
+    const float* gate;
+    const bf16_t* R;
+    int64_t lda, ldw, ldc, ldr;
+    int M, N, K, sw_rows;  // sw_rows: 1 = one scale per weight row, 0 = a single value
+    int tiles_m, tiles_n;
+    unsigned long long* clk;
+};
+
+APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
+    const int sw = (row >> 1) & 7;
+    const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece ^ sw) << 4));
+    const u32x4 hi = *(const u32x4*)(tile + row * FBK + (((piece + 1) ^ sw) << 4));
+    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+
+template <int EPI>     // APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
+__global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
+    __shared__ __attribute__((aligned(16))) uint8_t lds[4 * FOPB];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+
+    // XCD-grouped tile order: each XCD takes a contiguous run of tiles; inside a run, bands of 8 tile rows share the weight tiles
+    const int total = G.tiles_m * G.tiles_n;
+    const int t = xcd_remap(blockIdx.x, total);
+    const int band = 8 * G.tiles_n, first_m = (t / band) * 8;
+    const int gsz = min(G.tiles_m - first_m, 8);
+    const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
+
+    // staging: wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 rows per instruction
+    const char* a_src[4];
+    const char* w_src[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = 32 * wid + 8 * i + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        a_src[i] = (const char*)(G.A + (int64_t)min(m0 + r, G.M - 1) * G.lda + c * 16);
+        w_src[i] = (const char*)(G.W + (int64_t)min(n0 + r, G.N - 1) * G.ldw + c * 16);
+    }
+    auto stage = [&](int kt, int buf) {
+        uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;     // wave-uniform; the hardware adds lane * 16
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            glds16(a_src[i] + (int64_t)kt * FBK, da + 8 * i * FBK);
+            glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
+        }
+    };
+
+    unsigned long long clk_c0 = 0, clk_r0 = 0;
+    if (G.clk != nullptr) {          // kernel-uniform
+        clk_c0 = __builtin_readcyclecounter();
+        clk_r0 = __builtin_amdgcn_s_memrealtime();
+    }
+
+    f32x16 acc[2][2];                 // [weight tile (output columns)][activation tile (output rows)]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int nk = G.K / FBK;
+    const int fr = lane & 31, fh = lane >> 5;
+    stage(0, 0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
+        const uint8_t* ta = lds + buf * 2 * FOPB;
+        const uint8_t* tw = ta + FOPB;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int piece = 4 * kk + 2 * fh;
+            i32x8 fa[2], fw[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                fa[i] = lds_frag(ta, 64 * wr + 32 * i + fr, piece);
+                fw[i] = lds_frag(tw, 64 * wc + 32 * i + fr, piece);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, UNIT_E8M0, 0,
+                                                                               UNIT_E8M0);
+        }
+        __syncthreads();
+    }
+
+    if (G.clk != nullptr) {
+        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
+        if (tid == 0) {
+            atomicAdd(G.clk, c1 - clk_c0);
+            atomicAdd(G.clk + 1, r1 - clk_r0);
+        }
+    }
+
+    // ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float sw[4][4], bs[4][4];
+        f32x4 gt[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
+            u32x2 s;
+            if (G.sw_rows) {          // uniform condition
+                s = *(const u32x2*)(G.sw + n);
+            } else {
+                const uint32_t one = G.sw[0];
+                s = u32x2{one * 0x10001u, one * 0x10001u};
+            }
+            u32x2 b = {0u, 0u};
+            if (G.bias != nullptr) b = *(const u32x2*)(G.bias + n);
+            sw[g][0] = bf16_lo(s[0]), sw[g][1] = bf16_hi(s[0]), sw[g][2] = bf16_lo(s[1]), sw[g][3] = bf16_hi(s[1]);
+            bs[g][0] = bf16_lo(b[0]), bs[g][1] = bf16_hi(b[0]), bs[g][2] = bf16_lo(b[1]), bs[g][3] = bf16_hi(b[1]);
+            if (EPI == APEXMI_EPI_BIAS_GATE_RES) gt[g] = *(const f32x4*)(G.gate + n);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m = m0 + 64 * wr + 32 * j + fr;
+            const int mc = min(m, G.M - 1);
+            const float sa = G.sa[mc];
+            u32x2 rr[4];
+            if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
+                    rr[g] = *(const u32x2*)(G.R + (int64_t)mc * G.ldr + n);
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                    if (EPI == APEXMI_EPI_BIAS_GELU) o[e] = gelu_tanh_f(o[e]);
+                }
+                if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
+                    o[0] = bf16_lo(rr[g][0]) + gt[g][0] * o[0];
+                    o[1] = bf16_hi(rr[g][0]) + gt[g][1] * o[1];
+                    o[2] = bf16_lo(rr[g][1]) + gt[g][2] * o[2];
+                    o[3] = bf16_hi(rr[g][1]) + gt[g][3] * o[3];
+                }
+                if (m < G.M && n < G.N)
+                    *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, float* scales,
+                                     apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(a && codes && scales, "quant_rows_fp8: null operand");
+    APEXMI_REQUIRE(M >= 1, "quant_rows_fp8: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "quant_rows_fp8: K=%d must be a multiple of 128", K);
+    APEXMI_REQUIRE(lda >= K && ldq >= K && lda % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 16) == 0,
+                   "quant_rows_fp8: rows must be 16-byte aligned and at least K wide (lda %lld, ldq %lld)", (long long)lda,
+                   (long long)ldq);
+    ApexmiProfScope prof(5, stream, 0.0, 3.0 * (double)M * K);
+    const int pairs = (M + 1) / 2;
+    hipLaunchKernelGGL(quant_rows_fp8_kernel, dim3((unsigned)((pairs + 3) / 4)), dim3(256), 0, stream, (const bf16_t*)a, lda, M, K,
+                       (uint8_t*)codes, ldq, scales);
+    return apexmi_check_launch("quant_rows_fp8");
+}
+
+extern "C" int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format,
+                               const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K,
+                               int epilogue, const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(qa && sa && qw && sw && C, "gemm_fp8: null operand");
+    APEXMI_REQUIRE(w_format == 0, "gemm_fp8: weight format %d is not e4m3fn (0): e5m2 weights take the bf16 path "
+                                  "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16)", w_format);
+    APEXMI_REQUIRE(M >= 1, "gemm_fp8: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "gemm_fp8: N=%d must be a multiple of 16", N);
+    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8: K=%d must be a multiple of 128", K);
+    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
+                   "gemm_fp8: f32 output (epilogue %d, the f32 residual stream) is not supported: the output is bf16", epilogue);
+    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
+                   "gemm_fp8: epilogue %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", epilogue);
+    APEXMI_REQUIRE(sw_count == 1 || sw_count == N, "gemm_fp8: the weight scale has %lld values for N=%d rows", (long long)sw_count, N);
+    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K && ldw >= K && ldc >= N,
+                   "gemm_fp8: leading dimensions must keep rows 16-byte aligned (lda %lld, ldw %lld, ldc %lld)", (long long)lda,
+                   (long long)ldw, (long long)ldc);
+    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22),
+                   "gemm_fp8: leading dimensions above 2^22 elements are not supported (lda %lld, ldw %lld)", (long long)lda,
+                   (long long)ldw);
+    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)sa % 4) == 0 &&
+                       ((uintptr_t)sw % (sw_count == 1 ? 2 : 8)) == 0 && ((uintptr_t)bias % 8) == 0,
+                   "gemm_fp8: operands must be 16-byte aligned (scales and bias 8-byte)");
+    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
+        APEXMI_REQUIRE(gate && R, "gemm_fp8: gate/residual epilogue needs gate and R");
+        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "gemm_fp8: gate/R alignment");
+    }
+    const int64_t tiles = (int64_t)((M + FBM - 1) / FBM) * ((N + FBN - 1) / FBN);
+    APEXMI_REQUIRE(tiles < (1ll << 31), "gemm_fp8: too many output tiles");
+    Fp8Gemm G{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
+              lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, (M + FBM - 1) / FBM, (N + FBN - 1) / FBN, apexmi_clk_ptr()};
+    ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (double)M * K + (double)N * K + 2.0 * (double)M * N);
+    switch (epilogue) {
+        case APEXMI_EPI_BIAS: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+        default: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+    }
+    return apexmi_check_launch("gemm_fp8");
+}

@@ -178,7 +178,12 @@ class Fp8Weight(ResidentWeight):
     row) — and dequantised PER CALL into a per-stream bf16 scratch right before the GEMM that reads it, as the reference's
     `FPScaledLinear.forward` does (`_scale_and_cast_weight`, scaled_layer.py:496-549: `weight.to(bf16) * scale.to(bf16)`, then a
     bf16 matmul).  Same dequantisation kernel as the load-time path (`apexmi_dequant_fp8_scaled`, every code point pinned by
-    tests/golden/fp_scaled.pt), so a forward is bit-identical to dequantise-at-load; the model holds half the weight bytes."""
+    tests/golden/fp_scaled.pt), so a forward is bit-identical to dequantise-at-load; the model holds half the weight bytes.
+
+    `compute`: "bf16" (the default: the path above) or "fp8" — the OPT-IN approximation of DESIGN.md §3.6: `gemm` quantises the
+    activations per row to e4m3 and multiplies the resident codes directly (`gemm_fp8`), where `fp8_compute_route` allows it."""
+
+    compute = "bf16"
 
     def __init__(self, q: torch.Tensor, scale: torch.Tensor):
         if q.dtype not in (torch.float8_e4m3fn, torch.float8_e5m2) or q.dim() != 2:
@@ -306,6 +311,110 @@ def _bf16_weight(w, float_acts: bool = False):
     return f8.dequant(out=_scratch(f8.device, n)[:n].view(f8.shape[0], f8.shape[1]))
 
 
+# ---- opt-in FP8 compute on resident e4m3 weights ---------------------------------------------------------------------
+_FP8_EPI = ("bias", "gelu", "gate_res")
+
+
+def fp8_compute_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
+    """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as quantise + `gemm_fp8`.  Pure: reads dtypes, shapes and strides
+    only (CPU tensors are fine).  True only when ALL of these hold:
+      * `w` is (or carries) an `Fp8Weight` in float8_e4m3fn with `compute == "fp8"`;
+      * `a` is bf16 and `out` is bf16 or None (float activations = the f32-storage mode and a float `out` = the f32 residual
+        stream keep the bf16 path);
+      * the weight carries no run-time LoRA factors (`set_lora`);
+      * the shape is eligible: M >= 1, K % 128 == 0, N % 16 == 0, 16-byte rows of `a` with a row stride <= 2^22, and the epilogue
+        is one of bias / gelu / gate_res."""
+    f8 = _fp8_of(w)
+    if not isinstance(f8, Fp8Weight) or f8.compute != "fp8" or f8.q.dtype != torch.float8_e4m3fn or f8.lora_A is not None:
+        return False
+    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
+        return False
+    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
+        return False
+    M, K = a.shape
+    N = f8.shape[0]
+    return M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)
+
+
+_fp8_act_scratch: dict = {}
+
+
+def _act_scratch(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-stream home of the activation codes [M, K] and their row scales [M] (as `_scratch`: stream order makes the reuse safe)."""
+    key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    q, s = _fp8_act_scratch.get(key, (None, None))
+    if q is None or q.numel() < M * K:
+        q = torch.empty(M * K, dtype=torch.uint8, device=dev)
+    if s is None or s.numel() < M:
+        s = torch.empty(M, dtype=torch.float32, device=dev)
+    _fp8_act_scratch[key] = (q, s)
+    return q[:M * K].view(M, K), s[:M]
+
+
+def quant_rows_fp8(a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-row e4m3 quantisation of bf16 `a` [M, K] (row stride free, K % 128 == 0) -> (codes uint8 [M, K] = float8_e4m3fn bit
+    patterns, scales float32 [M]).  Per row, in IEEE float32 with every operation rounded on its own (true division, no FMA):
+        absmax = max |a|;  scale = 1 if absmax == 0 else absmax / 448;  code = e4m3fn_rne(clamp(a / scale, -448, 448))
+    An all-zero row has scale 1 and zero codes; no code is NaN.  Inputs must be finite."""
+    _req(a, torch.bfloat16, "quant_rows_fp8.a")
+    assert a.dim() == 2 and a.stride(1) == 1
+    M, K = a.shape
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.uint8, device=a.device)
+    if scale_out is None:
+        scale_out = torch.empty(M, dtype=torch.float32, device=a.device)
+    _req(out, torch.uint8, "quant_rows_fp8.out")
+    _req(scale_out, torch.float32, "quant_rows_fp8.scale_out")
+    assert out.shape == (M, K) and out.stride(1) == 1 and scale_out.is_contiguous() and scale_out.numel() == M
+    _l.check(_l.load().apexmi_quant_rows_fp8(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
+                                             _stream()), "quant_rows_fp8")
+    return out, scale_out
+
+
+def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
+             residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] (bf16) = epi((codes . w.q^T) * scales[m] * w.scale[n] + bias): e4m3 x e4m3 with f32 accumulation, both scales
+    applied in the f32 epilogue.  `codes` / `scales` as `quant_rows_fp8` returns them; `w` an e4m3 `Fp8Weight` (e5m2 raises);
+    epilogue bias / gelu / gate_res."""
+    _req(codes, torch.uint8, "gemm_fp8.codes")
+    _req(scales, torch.float32, "gemm_fp8.scales")
+    if not isinstance(w, Fp8Weight):
+        raise _l.ApexMIError(f"gemm_fp8: expected an Fp8Weight, got {type(w).__name__}")
+    if epilogue not in _FP8_EPI:
+        raise _l.ApexMIError(f"gemm_fp8: epilogue '{epilogue}' is not one of {_FP8_EPI}")
+    assert codes.dim() == 2 and codes.stride(1) == 1 and scales.is_contiguous()
+    M, K = codes.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and scales.numel() == M
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
+    else:
+        assert out.shape == (M, N) and out.stride(1) == 1
+    fmt = 0 if w.q.dtype == torch.float8_e4m3fn else 1
+    epi = _EPI[epilogue]
+    if out.dtype == torch.float32:           # rejected by the entry point with its own message
+        epi |= _l.EPI_F32_IO
+    else:
+        _req(out, torch.bfloat16, "gemm_fp8.out")
+    if bias is not None:
+        _req(bias, torch.bfloat16, "gemm_fp8.bias")
+        assert bias.is_contiguous() and bias.numel() == N
+    ldr = 0
+    if epilogue == "gate_res":
+        _req(gate, torch.float32, "gemm_fp8.gate")
+        _req(residual, out.dtype, "gemm_fp8.residual")
+        assert gate.is_contiguous() and gate.numel() == N
+        assert residual.shape == (M, N) and residual.stride(1) == 1
+        ldr = residual.stride(0)
+    rc = _l.load().apexmi_gemm_fp8(codes.data_ptr(), codes.stride(0), scales.data_ptr(), w.q.data_ptr(), w.q.stride(0), fmt,
+                                   w.scale.data_ptr(), w.scale.numel(), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K, epi,
+                                   _ptr(gate), _ptr(residual), ldr, _stream())
+    _l.check(rc, "gemm_fp8")
+    return out
+
+
 _EPI = {"bias": _l.EPI_BIAS, "gelu": _l.EPI_BIAS_GELU, "gate_res": _l.EPI_BIAS_GATE_RES,
         "gelu_erf": _l.EPI_BIAS_GELU_ERF, "silu": _l.EPI_BIAS_SILU, "quick_gelu": _l.EPI_BIAS_QUICK_GELU}
 
@@ -317,9 +426,19 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  2-D operands, last dim contiguous; a / out / residual bf16, or float32
     in the f32-storage verification mode (w and bias stay bf16).  A bf16 `a` with a float32 `out` (and `residual`) is the
     f32 RESIDUAL STREAM: the same launch with the float epilogue, no split of `a`.  `lora_buf`: see _gemm_fp8_lora (ignored
-    unless `w` is a resident-fp8 weight with run-time LoRA factors)."""
+    unless `w` is a resident-fp8 weight with run-time LoRA factors).
+
+    OPT-IN FP8 COMPUTE: a resident e4m3 `Fp8Weight` with `compute == "fp8"` takes `quant_rows_fp8` (codes and
+    scales in a per-stream scratch) + `gemm_fp8` instead of dequantise + bf16 GEMM when `fp8_compute_route` says so.  Today's
+    path, unchanged, is taken by everything else: `compute == "bf16"` (the default), run-time LoRA factors attached, e5m2
+    weights, GGUF records, float activations (the f32-storage mode), a float `out` (the f32 residual stream), K not a multiple
+    of 128 or N not a multiple of 16, and epilogues other than bias / gelu / gate_res.  `gemm_grouped` never routes."""
     _req_act(a, "gemm.a")
     f8 = _fp8_of(w)
+    if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
+        qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
+        quant_rows_fp8(a, out=qa, scale_out=sa)
+        return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     if f8 is not None and f8.lora_A is not None:
         return _gemm_fp8_lora(a, f8, bias, out, epilogue, gate, residual, lora_buf)
     w = _bf16_weight(w, a.dtype == torch.float32)

@@ -204,6 +204,22 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         self._window_plans = {}
         return self
 
+    def set_fp8_compute(self, on: bool):
+        """Opt-in approximation: the block Linears whose weights are RESIDENT e4m3 records (a `keep_fp8=True` load:
+        the fused q|k|v, the attention outputs, the cross-attention q and k|v, the two FFN Linears) quantise their activations per
+        row to e4m3 and multiply in fp8 (`ops.gemm_fp8`) instead of dequantising the weight and multiplying in bf16.  Everything
+        else — embedders, modulation GEMVs, proj_out, attention — stays bf16, and so does any such Linear `ops.gemm` cannot route
+        (run-time LoRA attached, e5m2 records, the f32 residual stream).  False restores today's launches bit for bit.  A speed
+        option: about 3.7e-2 rel-L2 per GEMM against the f32 product."""
+        recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values() if isinstance(r, ops.Fp8Weight)}
+        if not recs:
+            raise _l.ApexMIError("wan.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
+                                 "fp8-scaled checkpoint with keep_fp8=True")
+        for r in recs.values():
+            r.compute = "fp8" if on else "bf16"
+        self._fp8_compute = bool(on)
+        return self
+
     def _grid_ids(self, grid) -> torch.Tensor:
         """(frame, row, column) of every token in sequence order: what RoPE rotates by and what the attention window measures"""
         f, h, w = grid

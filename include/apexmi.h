@@ -587,6 +587,33 @@ int apexmi_cast_bf16_to_f32(const void* x, float* out, int64_t n, apexmi_stream_
 int apexmi_dequant_fp8_scaled(const void* w, int format, const void* scale, int64_t scale_count, int64_t rows,
                               int64_t cols, void* out, int64_t ldo, apexmi_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * OPT-IN FP8 compute for resident fp8-scaled weights.  Replaces, for a Linear whose e4m3fn weight stays
+ * resident, the per-call `apexmi_dequant_fp8_scaled` + `apexmi_gemm_bf16` pair (the reference's FPScaledLinear.forward:
+ * `weight.to(bf16) * scale.to(bf16)`, then a bf16 matmul) by a per-row activation quantiser and an e4m3 x e4m3 GEMM.  Narrower
+ * arithmetic than the reference's: never the default path.
+ *
+ * apexmi_quant_rows_fp8 — replaces the bf16 activation operand of that matmul.  a bf16 [M, K], row stride lda (elements);
+ * codes uint8 [M, K] (float8_e4m3fn bit patterns), row stride ldq (bytes); scales f32 [M].  Per row, in IEEE float32 with every
+ * operation rounded separately (true division, no reciprocal, no FMA):
+ *     absmax = max_k |a[k]|;   scale = absmax == 0 ? 1 : absmax / 448;
+ *     code[k] = e4m3fn( min(max(a[k] / scale, -448), 448) )     round to nearest even, e4m3 subnormals kept, sign of zero kept
+ * so an all-zero row has scale 1 and zero codes and no code is NaN.  Inputs are finite.  K % 128 == 0, M >= 1, 16-byte rows. */
+int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, float* scales,
+                          apexmi_stream_t stream);
+
+/* apexmi_gemm_fp8 — replaces apexmi_dequant_fp8_scaled + apexmi_gemm_bf16 for such a Linear:
+ *     C[m, n] = epi( (sum_k qa[m, k] qw[n, k]) * sa[m] * sw[n] + bias[n] )     bf16 out, f32 accumulation and epilogue
+ * qa [M, K] e4m3fn codes (row stride lda bytes) with f32 row scales sa [M] (apexmi_quant_rows_fp8); qw [N, K] e4m3fn codes
+ * (row stride ldw bytes) with bf16 scales sw: sw_count = 1 (one value) or N (one per row) — what an fp8-scaled checkpoint holds.
+ * w_format: 0 = float8_e4m3fn; 1 (float8_e5m2) is rejected.  epilogue: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU (tanh form) or
+ * APEXMI_EPI_BIAS_GATE_RES (C = R + gate[n] * y; R bf16 [M, N] with row stride ldr, may alias C); f32 output (APEXMI_EPI_F32_IO,
+ * APEXMI_EPI_BIAS_F32) is rejected.  bias bf16 [N] or NULL.  Any M >= 1; N % 16 == 0; K % 128 == 0; lda, ldw % 16 == 0 and
+ * <= 2^22; ldc, ldr % 4 == 0. */
+int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format, const void* sw,
+                    int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
+                    const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
