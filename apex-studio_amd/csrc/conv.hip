@@ -1552,12 +1552,51 @@ bool slab_eligible(const ConvArgs& a) {
     return g_conv_slab && a.kH == 3 && a.kW == 3 && a.py == 1 && a.px == 1 && a.kT <= 3 && (slab48(a) || slab64(a));
 }
 
-int launch_slab(const ConvArgs& a, hipStream_t stream) {
+// The ONE dispatch rule of the convolution family (conv3d_cl_impl launches by it, apexmi_conv3d_cl_family reports it):
+// which tile family a filled ConvArgs takes under the current conv.* settings.  *bn = the N extent of the conv-shaped tile
+// (CONV_FAMILY_V2 only, 0 otherwise).  tile choice: the N extent that wastes the fewest matrix columns; v2 only where it
+// fills the chip.  Stacked clips (Tc > 0) stay on the 128x128 kernel: the clip boundary lives in its gather only (the
+// conv-shaped / slab tiles walk frames).
+enum { CONV_FAMILY_128 = 0, CONV_FAMILY_V2 = 1, CONV_FAMILY_SLAB48 = 2, CONV_FAMILY_SLAB64 = 3, CONV_FAMILY_SLAB96 = 4 };
+int conv_family(const ConvArgs& a, int* bn) {
+    *bn = 0;
+    const int64_t M = (int64_t)a.T * a.H * a.W;
+    if (a.Tc > 0) return CONV_FAMILY_128;
+    if (!g_conv_v2 || (a.replicate && (a.up || a.H > 65535 || a.W > 65535)) || a.sy != 1 || a.sx != 1 || a.st != 1 || a.t0 != 0 || a.To != a.T || a.Ho != a.H || a.Wo != a.W || a.ntaps > 27 ||
+        (int64_t)a.T * a.Hin * a.Win * a.Cin * 2 >= ((int64_t)1 << 31))   // 32-bit byte offsets in the gather
+        return CONV_FAMILY_128;
+    const int c = a.Cout;
+    if (slab_eligible(a) && !(a.out_norm != nullptr && c > (slab48(a) ? 192 : 128))) {
+        // the slab kernels need a round of workgroups and mostly full tiles, not 65536 positions: e.g. the 32 x 32 x 61-frame
+        // stages of the HunyuanVideo-1.5 decoder (62464 positions, 1024 channels = 1952 workgroups)
+        const bool two_rows = slab48(a) && c <= 96;
+        const int th = two_rows ? 16 : 8;
+        const int nty = (a.H + th - 1) / th, ntx = (a.W + 31) / 32;
+        const int64_t wgs = (int64_t)a.T * nty * ntx * (two_rows ? 1 : (c + (slab48(a) ? 191 : 127)) / (slab48(a) ? 192 : 128));
+        const double fill = (double)a.H * a.W / ((double)nty * th * ntx * 32);
+        if (M >= 65536 || (wgs >= 256 && fill >= 0.7)) {
+            if (!slab48(a)) return CONV_FAMILY_SLAB64;
+            return g_conv_slab == 1 && a.Cin == 96 && c <= 96 && !a.up ? CONV_FAMILY_SLAB96 : CONV_FAMILY_SLAB48;
+        }
+    }
+    if (M < 65536) return CONV_FAMILY_128;
+    if (c <= 32) *bn = 32;
+    else if (c <= 64) *bn = 64;
+    else if (c <= 96) *bn = 96;
+    else if (c <= 128) return CONV_FAMILY_128;   // 256 x 128 (64 x 64 wave tiles) measured 9 % slower than the 128 x 128 kernel: stay on it
+    else if (c % 192 == 0 || (c > 128 && c <= 192)) *bn = 192;
+    else if (c % 256 == 0) *bn = 256;
+    else if (c % 128 == 0) *bn = 128;
+    else *bn = 192;
+    return CONV_FAMILY_V2;
+}
+
+int launch_slab(const ConvArgs& a, int family, hipStream_t stream) {
     const bool norm = a.out_norm != nullptr;
     // conv.pp: 1 (shipped) = per shape, whichever schedule measured faster (profiles/r03_vae_conv_schedules.md): the register-
     // prefetch kernel on the 192-channel-wide tiles (+4..10 %), the serial-chunk kernel elsewhere; 0 / 2 = one of them
     // everywhere it exists; 3 = the prefetch kernel as 4 waves of twice the tile (A/B only, no fused norm)
-    if (!slab48(a)) {     // 64-channel slices
+    if (family == CONV_FAMILY_SLAB64) {     // 64-channel slices
         if (norm && a.Cout > 128) {
             apexmi_set_error("conv3d_cl_norm: Cout=%d does not fit one N tile of the slab kernel", a.Cout);
             return 1;
@@ -1565,7 +1604,7 @@ int launch_slab(const ConvArgs& a, hipStream_t stream) {
         if (g_conv_pp == 2) return norm ? launch_slabp_inst<2, 2, 2, 1, 64>(a, stream) : launch_slabp_inst<2, 2, 2, 0, 64>(a, stream);
         return norm ? launch_slab_inst<4, 1, 1, 64>(a, stream) : launch_slab_inst<4, 1, 0, 64>(a, stream);
     }
-    if (g_conv_slab == 1 && a.Cin == 96 && a.Cout <= 96 && !a.up) {
+    if (family == CONV_FAMILY_SLAB96) {
         const int nt = (a.Cout + 31) / 32;
         if (norm) return nt == 1 ? launch_slab96_inst<1, 1>(a, stream) : nt == 2 ? launch_slab96_inst<2, 1>(a, stream) : launch_slab96_inst<3, 1>(a, stream);
         return nt == 1 ? launch_slab96_inst<1, 0>(a, stream) : nt == 2 ? launch_slab96_inst<2, 0>(a, stream) : launch_slab96_inst<3, 0>(a, stream);
@@ -1614,40 +1653,19 @@ int launch_v2(const ConvArgs& a, hipStream_t stream) {
     return a.up ? launch_v2_inst<CFG, 1, 0>(a, stream, nm * nn) : launch_v2_inst<CFG, 0, 0>(a, stream, nm * nn);
 }
 
-// tile choice: the N extent that wastes the fewest matrix columns; v2 only where it fills the chip
-int launch_v2_for(const ConvArgs& a, hipStream_t stream, bool* taken) {
-    *taken = false;
-    const int64_t M = (int64_t)a.T * a.H * a.W;
-    if (!g_conv_v2 || (a.replicate && (a.up || a.H > 65535 || a.W > 65535)) || a.sy != 1 || a.sx != 1 || a.st != 1 || a.t0 != 0 || a.To != a.T || a.Ho != a.H || a.Wo != a.W || a.ntaps > 27 ||
-        (int64_t)a.T * a.Hin * a.Win * a.Cin * 2 >= ((int64_t)1 << 31))   // 32-bit byte offsets in the gather
-        return 0;
-    const int c = a.Cout;
-    *taken = true;
-    if (slab_eligible(a) && !(a.out_norm != nullptr && c > (slab48(a) ? 192 : 128))) {
-        // the slab kernels need a round of workgroups and mostly full tiles, not 65536 positions: e.g. the 32 x 32 x 61-frame
-        // stages of the HunyuanVideo-1.5 decoder (62464 positions, 1024 channels = 1952 workgroups)
-        const bool two_rows = slab48(a) && c <= 96;
-        const int th = two_rows ? 16 : 8;
-        const int nty = (a.H + th - 1) / th, ntx = (a.W + 31) / 32;
-        const int64_t wgs = (int64_t)a.T * nty * ntx * (two_rows ? 1 : (c + (slab48(a) ? 191 : 127)) / (slab48(a) ? 192 : 128));
-        const double fill = (double)a.H * a.W / ((double)nty * th * ntx * 32);
-        if (M >= 65536 || (wgs >= 256 && fill >= 0.7)) return launch_slab(a, stream);
+// launches what conv_family chose; *taken = false leaves the call to the 128x128 kernel
+int launch_v2_for(const ConvArgs& a, int family, int bn, hipStream_t stream, bool* taken) {
+    *taken = family != CONV_FAMILY_128;
+    if (family == CONV_FAMILY_128) return 0;
+    if (family != CONV_FAMILY_V2) return launch_slab(a, family, stream);
+    switch (bn) {
+    case 32: return launch_v2<CV_N32, true>(a, stream);
+    case 64: return launch_v2<CV_N64, true>(a, stream);
+    case 96: return launch_v2<CV_N96, true>(a, stream);
+    case 128: return launch_v2<CV_N128>(a, stream);
+    case 256: return launch_v2<CV_N256>(a, stream);
+    default: return launch_v2<CV_N192, true>(a, stream);   // (the fused norm needs one N tile: launch_v2 refuses Cout > 192)
     }
-    if (M < 65536) {
-        *taken = false;
-        return 0;
-    }
-    if (c <= 32) return launch_v2<CV_N32, true>(a, stream);
-    if (c <= 64) return launch_v2<CV_N64, true>(a, stream);
-    if (c <= 96) return launch_v2<CV_N96, true>(a, stream);
-    if (c <= 128) {           // 256 x 128 (64 x 64 wave tiles) measured 9 % slower than the 128 x 128 kernel: stay on it
-        *taken = false;
-        return 0;
-    }
-    if (c % 192 == 0 || (c > 128 && c <= 192)) return launch_v2<CV_N192, true>(a, stream);
-    if (c % 256 == 0) return launch_v2<CV_N256>(a, stream);
-    if (c % 128 == 0) return launch_v2<CV_N128>(a, stream);
-    return launch_v2<CV_N192>(a, stream);
 }
 
 // ---- channels-last elementwise companions --------------------------------------------------------
@@ -1982,7 +2000,10 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
                           int replicate, apexmi_stream_t stream_, int sy = 1, int sx = 1, int py = -1, int px = -1,
                           int Ho = 0, int Wo = 0, int independent = 0, int up = 0, const void* norm_gamma = nullptr,
                           void* out_norm = nullptr, int norm_silu = 0, int act = 0, float act_slope = 0.0f, int st = 1,
-                          int t0 = 0, int To = 0, int f32io = 0, int clip_frames = 0) {
+                          int t0 = 0, int To = 0, int f32io = 0, int clip_frames = 0, int* family_query = nullptr,
+                          int* family_bn = nullptr) {
+    // family_query != nullptr: launch nothing, report the tile family this call would take (apexmi_conv3d_cl_family; the
+    // operands are not looked at, a non-null out_norm only says "with the fused norm")
     const int Hin = H, Win = W;
     if (up) {          // H, W arrive as the STORED extents; the convolution runs over the 2x upsampled image
         H *= 2;
@@ -1993,7 +2014,7 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
     if (Ho <= 0) Ho = H;
     if (Wo <= 0) Wo = W;
     hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(in && w && (out || out_norm) && zeros, "conv3d_cl: null operand");
+    APEXMI_REQUIRE(family_query || (in && w && (out || out_norm) && zeros), "conv3d_cl: null operand");
     APEXMI_REQUIRE(T > 0 && H > 0 && W > 0, "conv3d_cl: empty volume");
     APEXMI_REQUIRE(Cin % 8 == 0 && Cout % 4 == 0, "conv3d_cl: Cin=%d must be a multiple of 8, Cout=%d of 4", Cin, Cout);
     const int ntaps = kT * kH * kW;
@@ -2030,7 +2051,7 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
                    "conv3d_cl_frames: Kpad=%d leaves no room to address the last temporal slice (need >= %d; pack the "
                    "weight with apexmi's packing rule)", Kpad, skip + kspatial);
     if ((T == 1 || independent) && kT > 1 && !replicate && skip % 8 == 0 && skip + kspatial <= Kpad) {
-        a.w += skip;
+        if (w) a.w += skip;
         Kext = kspatial;
         kT_eff = 1;
         ntaps_eff = kH * kW;
@@ -2059,6 +2080,13 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
     a.prof = (unsigned long long*)g_conv_prof;
     a.dbg = g_conv_dbg;
     a.torder = g_conv_torder;
+    int bn = 0;
+    const int family = f32io ? CONV_FAMILY_128 : conv_family(a, &bn);
+    if (family_query) {
+        *family_query = family;
+        if (family_bn) *family_bn = bn;
+        return 0;
+    }
     const int64_t M = (int64_t)To * Ho * Wo;
     const int nm = (int)((M + BM - 1) / BM), nn = (Cout + BN - 1) / BN;
     ApexmiProfScope prof(0, stream, 2.0 * M * Cout * (double)ntaps_eff * Cin,
@@ -2070,8 +2098,7 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
         return apexmi_check_launch("conv3d_cl_f32");
     }
     bool taken = false;
-    // stacked clips: the clip boundary lives in the 128x128 kernel's gather only (the conv-shaped / slab tiles walk frames)
-    const int rc2 = a.Tc > 0 ? 0 : launch_v2_for(a, stream, &taken);
+    const int rc2 = launch_v2_for(a, family, bn, stream, &taken);
     if (taken) return rc2;
     APEXMI_REQUIRE(out_norm == nullptr, "conv3d_cl_norm: this convolution does not run on the fused-norm tiles "
                                         "(ask apexmi_conv3d_cl_norm_fusable first)");
@@ -2105,6 +2132,19 @@ extern "C" int apexmi_conv3d_cl_norm_fusable(int T, int H, int W, int Cin, int C
     const int64_t M = (int64_t)T * H * W * (up ? 4 : 1);
     return g_conv_v2 && M >= 65536 && (int64_t)T * H * W * Cin * 2 < ((int64_t)1 << 31) && Cout % 8 == 0 &&
            (Cout <= 96 || (Cout > 128 && Cout <= 192));
+}
+
+extern "C" int apexmi_conv3d_cl_family(int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH, int kW, int replicate,
+                                       int independent, int up, int norm, int clip_frames, int stride_h, int stride_w,
+                                       int pad_top, int pad_left, int Ho, int Wo, int stride_t, int t_first, int To,
+                                       int* n_extent) {
+    int family = -1, bn = 0;
+    static char norm_flag;   // never written: a non-null out_norm selects the fused-norm side of the rule
+    const int rc = conv3d_cl_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T, H, W, Cin, Cout, Kpad, kT, kH, kW,
+                                  replicate, nullptr, stride_h, stride_w, pad_top, pad_left, Ho, Wo, independent, up, nullptr,
+                                  norm ? &norm_flag : nullptr, 0, 0, 0.0f, stride_t, t_first, To, 0, clip_frames, &family, &bn);
+    if (n_extent) *n_extent = rc ? 0 : bn;
+    return rc ? -1 : family;
 }
 
 extern "C" int apexmi_conv3d_cl_norm(const void* in, const void* w, const void* bias, const void* residual, void* out,

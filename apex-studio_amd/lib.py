@@ -93,6 +93,7 @@ SIGNATURES = {
     "apexmi_conv3d_cl_frames": (C.c_int, [vp, vp, vp, vp, vp, vp] + [C.c_int] * 9 + [vp]),
     "apexmi_conv3d_cl_up2": (C.c_int, [vp, vp, vp, vp, vp, vp] + [C.c_int] * 10 + [vp]),
     "apexmi_conv3d_cl_norm_fusable": (C.c_int, [C.c_int] * 6),
+    "apexmi_conv3d_cl_family": (C.c_int, [C.c_int] * 23 + [vp]),
     "apexmi_conv3d_cl_norm": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp] + [C.c_int] * 11 + [vp]),
     "apexmi_add_bf16": (C.c_int, [vp, vp, vp, C.c_int64, vp]),
     "apexmi_add_f32": (C.c_int, [vp, vp, vp, C.c_int64, vp]),

@@ -1679,6 +1679,31 @@ def conv3d_cl_norm_fusable(x: torch.Tensor, cout: int, upsample2x: bool = False)
     return bool(_l.load().apexmi_conv3d_cl_norm_fusable(T, H, W, cin, cout, 1 if upsample2x else 0))
 
 
+CONV_FAMILIES = ("128x128", "v2", "slab48", "slab64", "slab96")
+
+
+def conv3d_cl_family(x_shape, w_packed_shape, ksize, replicate: bool = False, independent_frames: bool = False,
+                     upsample2x: bool = False, norm: bool = False, clip_frames: int = 0, stride=(1, 1), pad=(-1, -1),
+                     out_hw=(0, 0), tstride=(1, 0, 0)) -> Tuple[str, int]:
+    """Which tile family a bf16 convolution call of these shapes takes under the current `conv.*` tune settings, from the
+    launch's own decision function (`apexmi_conv3d_cl_family`; nothing runs): (one of CONV_FAMILIES, N extent of the v2 tile
+    or 0).  x_shape [T, H, W, Cin] as stored, w_packed_shape [Cout4, Kpad]; the keywords as conv3d_cl / conv3d_cl_norm
+    (norm) / conv2d_cl_strided (stride, pad, out_hw) / conv3d_cl_tstrided (tstride = (stride_t, t_first, out_frames))."""
+    import ctypes
+    T, H, W, cin = (int(v) for v in x_shape)
+    cout, kpad = (int(v) for v in w_packed_shape)
+    if clip_frames == T:
+        clip_frames = 0
+    n = ctypes.c_int(0)
+    fam = _l.load().apexmi_conv3d_cl_family(T, H, W, cin, cout, kpad, int(ksize[0]), int(ksize[1]), int(ksize[2]),
+                                            1 if replicate else 0, 1 if independent_frames else 0, 1 if upsample2x else 0,
+                                            1 if norm else 0, int(clip_frames), int(stride[0]), int(stride[1]), int(pad[0]),
+                                            int(pad[1]), int(out_hw[0]), int(out_hw[1]), int(tstride[0]), int(tstride[1]),
+                                            int(tstride[2]), ctypes.addressof(n))
+    _l.check(0 if fam >= 0 else 1, "conv3d_cl_family")
+    return CONV_FAMILIES[fam], n.value
+
+
 def conv3d_cl_norm(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], ksize, gamma: torch.Tensor,
                    silu: bool = True, residual: Optional[torch.Tensor] = None, want_raw: bool = True,
                    upsample2x: bool = False, independent_frames: bool = False):

@@ -434,6 +434,17 @@ int apexmi_conv3d_cl_up2(const void* in, const void* w, const void* bias, const 
  * apexmi_conv3d_cl_norm_fusable(T, H, W, Cin, Cout, up) != 0 (H, W = stored extents).  up != 0: read through the nearest
  * 2x upsample as apexmi_conv3d_cl_up2. */
 int apexmi_conv3d_cl_norm_fusable(int T, int H, int W, int Cin, int Cout, int up);
+/* Read-only: which tile family a convolution call takes under the current "conv.*" settings — the same decision function
+ * the launch goes through, nothing runs.  Arguments as the entry points above take them (H, W = stored extents; Kpad of the
+ * packed weight; replicate / independent / up / norm (the fused RMS norm) as flags; clip_frames as apexmi_conv3d_cl_clips,
+ * 0 = one clip; stride_h .. Wo as apexmi_conv3d_cl_strided with 1, 1, -1, -1, 0, 0 = the "same" convolution; stride_t,
+ * t_first, To as apexmi_conv3d_cl_tstrided with 1, 0, 0 = every frame).  Returns 0 the 128x128 implicit GEMM | 1 a
+ * conv-shaped v2 tile, *n_extent (may be NULL) = its N extent 32 / 64 / 96 / 128 / 192 / 256 | 2 the direct "slab"
+ * convolution on 48-channel slices | 3 on 64-channel slices | 4 the order-preserving 8 x 32 slab of Cin = 96 (conv.slab = 1);
+ * -1 for arguments the convolution refuses (apexmi_last_error).  *n_extent = 0 unless the family is 1. */
+int apexmi_conv3d_cl_family(int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH, int kW, int replicate,
+                            int independent, int up, int norm, int clip_frames, int stride_h, int stride_w, int pad_top,
+                            int pad_left, int Ho, int Wo, int stride_t, int t_first, int To, int* n_extent);
 int apexmi_conv3d_cl_norm(const void* in, const void* w, const void* bias, const void* residual, void* out, void* out_norm,
                           const void* gamma, int silu, const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad,
                           int kT, int kH, int kW, int independent, int up, apexmi_stream_t stream);
