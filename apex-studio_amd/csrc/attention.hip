@@ -5,20 +5,11 @@
 //
 // MFMA kernels (bf16, D = 128), per workgroup NW = 4..8 waves x 32 query rows, KV tile = 64 keys (169-238 VGPRs: two
 // waves per SIMD, ONE workgroup per CU).  Launches that fill the chip use the 8-wave 4-cluster ping-pong kernel
-// (attn_fwd_d128_c4_kernel, below); the plain loop (attn_fwd_d128_kernel) serves small launches and A/B:
-//   S^T = K Q^T      (MFMA "A" = K rows from LDS, "B" = Q rows held in registers)
-//   O^T = V^T P^T    (MFMA "A" = V^T rows from LDS, "B" = P, straight out of the S^T accumulators)
-// Both products are "swapped" so lane l owns query row (l & 31): the row max / row sum of the
-// online softmax are 31 in-lane ops + one v_permlane32_swap with lane l^32, and the O rescale
-// is lane-local.  K tiles are staged with their rows permuted (bits 2 and 3 of the row index
-// swapped) so that the 8 scores a lane holds for one PV k-step are 8 CONSECUTIVE keys: the
-// V^T fragment is then a single ds_read_b128 and P needs no cross-lane shuffle at all.
-// V arrives pre-transposed ([B,H,128,Skp], produced by apexmi_qkv_prepare / apexmi_v_transpose),
-// so K and V^T tiles are both contraction-contiguous and are staged by 16-byte global_load_lds
-// into a double-buffered 64 KiB LDS image, XOR-swizzled on the source address and the read.
-// Workgroup ids are remapped so all query blocks of one (batch, head) run on one XCD and share
-// its L2 copy of K / V^T.
-#include "common.h"
+// (attn_fwd_d128_c4_kernel, below); the plain loop (attn_fwd_d128_kernel) serves small launches and A/B.  The tile layout, the
+// products and the rounding rule of the online softmax are attn_tile.h's.  V arrives pre-transposed ([B,H,128,Skp], produced by
+// apexmi_qkv_prepare / apexmi_v_transpose), K and V^T tiles are staged by 16-byte global_load_lds into a double-buffered 64 KiB
+// LDS image.  Workgroup ids are remapped so all query blocks of one (batch, head) run on one XCD and share its L2 copy of K / V^T.
+#include "attn_tile.h"
 
 // Per-workgroup timeline of the shipped flash kernel (tools/attn_tile_trace.py): compiled in only with -DAPEXMI_ATTN_TRACE=1 into a side
 // library; the host reads a device pointer from the environment variable APEXMI_ATTN_TRACE_PTR (hex) at every launch.  8 u64 per
@@ -44,28 +35,13 @@ __device__ unsigned int d_attn_w64_fallbacks = 0;
 
 namespace {
 
-constexpr int KV = 64;    // keys per tile
 constexpr int HD = 128;   // head dim
 constexpr int K_TILE_BYTES = KV * HD * 2;   // 16 KiB
 constexpr int V_TILE_BYTES = HD * KV * 2;   // 16 KiB
 constexpr int ATT_STAGE = K_TILE_BYTES + V_TILE_BYTES;
 
-// row i of a 32-row K sub-tile holds key perm32(i): swap bits 2 and 3
-APEXMI_DEVICE int perm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
-
-// NW = waves per workgroup (4 or 8); every wave owns 32 query rows and reads the whole K / V^T tile,
-// so 8 waves halve the LDS-DMA instructions each wave has to issue per tile.
-// Online softmax with a deferred rescale: the running max is only raised (and O, l rescaled) when
-// some row's tile max exceeds it by more than DEFER (log2 units), so p = 2^(s c - m) stays <= 2^DEFER;
-// in steady state the 64-register O rescale is skipped.  Every P of a tile is exponentiated after the
-// decision that covers it (no pending P V is split by a rescale).
-// The running max is kept an INTEGER (ceil, base-2 domain): every rescale factor 2^(m_old - m_new) is then an exact
-// power of two and bf16(2^k p) = 2^k bf16(p), so the bf16 rounding of P — and with it the result — does not depend
-// on the key-tile order, the deferral threshold or a key-range split: O = sum_j bf16(2^(s_j c - M)) v_j / sum_j
-// 2^(s_j c - M) for ANY integer M, up to f32 summation order.  That is what lets the CPU oracle reproduce the
-// kernel's rounding points (oracle.layers.sdpa, bf16 policy) without replaying its schedule.
-constexpr float DEFER = 6.0f;
-
+// NW = waves per workgroup (4..8); every wave owns 32 query rows and reads the whole K / V^T tile, so 8 waves halve the LDS-DMA
+// instructions each wave has to issue per tile.  Keys past Sk get SENTINEL on the raw score, 1 / l is unguarded, scale > 0.
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
@@ -86,36 +62,19 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_kernel(
     const bf16_t* Kp = K + (int64_t)hb * Sk * HD;
     const bf16_t* Vp = Vt + (int64_t)hb * HD * Skp;
 
-    constexpr int QB = NW * 32;
-    constexpr int LD = (16 + NW - 1) / NW;  // 1 KiB LDS-DMA pieces per wave per tile image (16 pieces each for K and V^T)
+    using E = ElemBf16;
+    constexpr int QB = NW * 32, LD = PIECES<HD, NW>;
     const int qrow = qb * QB + wave * 32 + l31;
     const int qrow_c = min(qrow, Sq - 1);
-
-    // Q fragments: B operand of S^T, lane supplies Q[qrow][16 ks + 8 hi .. +7]
-    bf16x8 qf[8];
+    bf16x8 qf[8];   // B operand of S^T: lane supplies Q[qrow][16 ks + 8 hi .. +7]
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-        qf[ks] = *(const bf16x8*)(Qp + (int64_t)qrow_c * HD + ks * 16 + hi * 8);
+    for (int ks = 0; ks < 8; ++ks) qf[ks] = *(const bf16x8*)(Qp + (int64_t)qrow_c * HD + ks * 16 + hi * 8);
 
-    // staging sources.  Piece p = i NW + wave (p < 16).  K image: [64 rows][16 chunks], chunk ^= row & 15,
-    // row i <- key perm(i).  V^T image: [128 rows (d)][8 chunks], chunk ^= (row >> 1) & 7.
-    int k_key[LD], k_c[LD];
-    const char* v_src[LD];
+    int k_key[LD], k_c[LD], v_row[LD], v_c[LD];
+    stage_sources<HD, NW>(wave, lane, k_key, k_c, v_row, v_c);
+    const bf16_t* v_src[LD];
 #pragma unroll
-    for (int i = 0; i < LD; ++i) {
-        const int p = (i * NW + wave) * 64 + lane;
-        {
-            const int row = (p >> 4) & 63, pc = p & 15;
-            k_c[i] = (pc ^ (row & 15)) * 8;
-            k_key[i] = (row & 32) + perm32(row & 31);
-        }
-        {
-            const int row = (p >> 3) & 127, pc = p & 7;
-            const int c = pc ^ ((row >> 1) & 7);
-            v_src[i] = (const char*)(Vp + (int64_t)row * Skp + c * 8);
-        }
-    }
-
+    for (int i = 0; i < LD; ++i) v_src[i] = Vp + (int64_t)v_row[i] * Skp + v_c[i];
     auto stage = [&](int buf, int t) {
         char* base = smem + buf * ATT_STAGE + wave * 1024;
         const int kv0 = t * KV;
@@ -127,31 +86,15 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_kernel(
             }
 #pragma unroll
         for (int i = 0; i < LD; ++i)
-            if (i * NW + wave < 16) glds16(v_src[i] + (int64_t)kv0 * 2, base + K_TILE_BYTES + i * (NW * 1024));
+            if (i * NW + wave < 16) glds16(v_src[i] + kv0, base + K_TILE_BYTES + i * (NW * 1024));
     };
 
-    // LDS read offsets
-    int k_off[2], k_sw[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-        const int row = kt * 32 + l31;
-        k_off[kt] = row * 256;
-        k_sw[kt] = row & 15;
-    }
-    int v_off[4], v_sw[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-        const int row = dt * 32 + l31;
-        v_off[dt] = row * 128;
-        v_sw[dt] = (row >> 1) & 7;
-    }
+    int k_off[2], k_sw[2], v_off[4], v_sw[4];
+    fragment_offsets<HD>(l31, k_off, k_sw, v_off, v_sw);
 
     f32x16 oacc[4];
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
-    float m_run = -1.0e30f;  // running max, already in the scaled (log2) domain
+    clear(oacc);
+    float m_run = SENTINEL;  // running max, already in the scaled (log2) domain
     float l_run = 0.0f;      // this lane's partial row sum (its 32 keys of every tile)
 
     const int nt = (Sk + KV - 1) / KV;
@@ -164,100 +107,26 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_kernel(
         __syncthreads();
         if (t + 1 < nt) stage((t + 1) & 1, t + 1);
         const char* Ks = smem + (t & 1) * ATT_STAGE;
-        const char* Vs = Ks + K_TILE_BYTES;
 
-        // ---- S^T = K Q^T : sacc[kt][r] = score(q = l31, key row i = (r&3) + 8 (r>>2) + 4 hi) ----
         f32x16 sacc[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[kt][r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            const int c = ks * 2 + hi;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                const bf16x8 kf = *(const bf16x8*)(Ks + k_off[kt] + ((c ^ k_sw[kt]) << 4));
-                sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt], 0, 0, 0);
-            }
-        }
-
-        // ---- mask keys past Sk (last tile only; wave-uniform branch) ----
-        if (t == nt - 1 && (Sk & (KV - 1)) != 0) {
-            const int kv0 = t * KV;
+        scores<E, HD>(Ks, k_off, k_sw, hi, qf, sacc);
+        if (t == nt - 1 && (Sk & (KV - 1)) != 0) {   // keys past Sk (last tile only; wave-uniform branch)
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int a = r >> 2, bb = r & 3;
-                    const int key = kv0 + kt * 32 + 16 * (a >> 1) + 8 * hi + 4 * (a & 1) + bb;
-                    if (key >= Sk) sacc[kt][r] = -1.0e30f;
-                }
+                for (int r = 0; r < 16; ++r)
+                    if (t * KV + tile_key(kt, r, hi) >= Sk) sacc[kt][r] = SENTINEL;
         }
+        raise_max(max_xor32(tile_max(sacc)) * scale_log2e, m_run, l_run, oacc);     // always raises on the first tile
+        l_run += exp2_fused(sacc, scale_log2e, m_run);
 
-        // ---- online softmax (base-2 domain: p = 2^(s*c - m)) ----
-        float mx = sacc[0][0];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kt][r]);
-        mx = max_xor32(mx) * scale_log2e;
-        if (__any(mx > m_run + DEFER)) {  // wave-uniform; always taken on the first tile
-            const float m_new = ceilf(fmaxf(m_run, mx));   // integer: see the note above DEFER
-            const float alpha = fast_exp2(m_run - m_new);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
-        }
-        float psum = 0.0f;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float p = fast_exp2(fmaf(sacc[kt][r], scale_log2e, -m_run));
-                sacc[kt][r] = p;
-                psum += p;
-            }
-        l_run += psum;
-
-        // ---- P -> bf16 B-fragments: k-step kk takes regs 8 (kk & 1) .. +7 of sacc[kk >> 1],
-        //      which are keys 16 kk + 8 hi .. +7 of the tile ----
         bf16x8 pf[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[kk][j] = (__bf16)sacc[kk >> 1][8 * (kk & 1) + j];
-
-        // ---- O^T += V^T P^T ----
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int c = kk * 2 + hi;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const bf16x8 vf = *(const bf16x8*)(Vs + v_off[dt] + ((c ^ v_sw[dt]) << 4));
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kk], oacc[dt], 0, 0, 0);
-            }
-        }
+        p_fragments<E>(sacc, pf);
+        accumulate<E, HD>(Ks + K_TILE_BYTES, v_off, v_sw, hi, pf, oacc);
     }
 
-    // ---- epilogue: O[q][d] = O^T / l ; lane holds d = 32 dt + 8 g + 4 hi + (0..3) ----
-    const float l_tot = sum_xor32(l_run);
-    const float inv = 1.0f / l_tot;
-    if (qrow < Sq) {
-        bf16_t* op = O + (int64_t)b * o_sb + (int64_t)qrow * o_ss + (int64_t)h * o_sh;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 o;
-                o[0] = pack_bf16(oacc[dt][4 * g + 0] * inv, oacc[dt][4 * g + 1] * inv);
-                o[1] = pack_bf16(oacc[dt][4 * g + 2] * inv, oacc[dt][4 * g + 3] * inv);
-                *(u32x2*)(op + dt * 32 + g * 8 + hi * 4) = o;
-            }
-    }
+    const float inv = 1.0f / sum_xor32(l_run);
+    if (qrow < Sq) store_row<E>(O + (int64_t)b * o_sb + (int64_t)qrow * o_ss + (int64_t)h * o_sh, hi, oacc, inv);
 }
 
 // ---- 4-cluster ping-pong variant (8 waves) ---------------------------------------------------------------
@@ -393,7 +262,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_c4_kernel(
     for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
-    float m_run = -1.0e30f;  // running max, already in the scaled (log2) domain
+    float m_run = SENTINEL;  // running max, already in the scaled (log2) domain
     float l_run = 0.0f;      // this lane's partial row sum (its 32 keys of every tile)
 
     // ---- 4-cluster ping-pong (8 waves; wave w and w + 4 share a SIMD) -------------------------------------------
@@ -535,7 +404,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_c4_kernel(
                 for (int r = 0; r < 16; ++r) {
                     const int a = r >> 2, bb = r & 3;
                     const int key = kv0 + kt * 32 + 16 * (a >> 1) + 8 * hi + 4 * (a & 1) + bb;
-                    if (key >= Sk) sacc[kt][r] = -1.0e30f;
+                    if (key >= Sk) sacc[kt][r] = SENTINEL;
                 }
         }
         {
@@ -560,7 +429,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_c4_kernel(
                 TR_MID2(mx);
             }
             if (__any(mx > m_run + DEFER)) {
-                const float m_new = ceilf(fmaxf(m_run, mx));   // integer: see the note above DEFER
+                const float m_new = ceilf(fmaxf(m_run, mx));   // integer: attn_tile.h
                 const float alpha = fast_exp2(m_run - m_new);
                 m_run = m_new;
                 l_run *= alpha;
@@ -840,10 +709,9 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_c4_kernel(
 //   phase X(t): S(t+1) = K(t+1) Q^T  (32 MFMAs)  beside  exp2 / row-sum terms / bf16 pairs of tile t
 //   phase Y(t): O^T += V^T(t) P(t)^T (32 MFMAs)  beside  row max / running-max decision / scaling of tile t+1
 // One s_barrier per tile, LDS ring of four stages.  The running max is per ROW here (a row is raised when ITS tile max exceeds it
-// by more than DEFER): with the integer max any choice gives the same result up to f32 summation order (note above DEFER).
+// by more than DEFER): with the integer max any choice gives the same result up to f32 summation order (attn_tile.h).
 // The loop is ONE asm statement generated by tools/gen_attn_w64.py (register map, instruction placement, wait counts and the
 // MFMA -> VALU hazards are the generator's): hipcc's allocator spilled 160-220 registers on every C++ form of it.
-APEXMI_DEVICE int w64_perm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
 // Shipped (round 6): the loop WITHOUT a per-tile running maximum (attn_w64_first.inc: every row keeps the integer maximum of tile
 // 0), checked at the end, with the running-maximum loop (attn_w64_body.inc) as the workgroup's fallback — attn_w64_kernel.h.
@@ -1009,7 +877,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_mi16_kernel(
     for (int dt = 0; dt < 8; ++dt)
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) oacc[dt][qt] = f4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {-1.0e30f, -1.0e30f};
+    float m_run[2] = {SENTINEL, SENTINEL};
     float l_run[2] = {0.0f, 0.0f};
 
     const int nt = (Sk + KV - 1) / KV;
@@ -1044,8 +912,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_mi16_kernel(
                 for (int r = 0; r < 4; ++r) {
                     const int key = kv0 + 32 * (kt >> 1) + 8 * g4 + 4 * (kt & 1) + r;
                     if (key >= Sk) {
-                        sacc[kt][0][r] = -1.0e30f;
-                        sacc[kt][1][r] = -1.0e30f;
+                        sacc[kt][0][r] = SENTINEL;
+                        sacc[kt][1][r] = SENTINEL;
                     }
                 }
         }
@@ -1063,7 +931,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_mi16_kernel(
         if (__any(mx[0] > m_run[0] + DEFER || mx[1] > m_run[1] + DEFER)) {
 #pragma unroll
             for (int qt = 0; qt < 2; ++qt) {
-                const float m_new = ceilf(fmaxf(m_run[qt], mx[qt]));   // integer: see the note above DEFER
+                const float m_new = ceilf(fmaxf(m_run[qt], mx[qt]));   // integer: attn_tile.h
                 const float alpha = fast_exp2(m_run[qt] - m_new);
                 m_run[qt] = m_new;
                 l_run[qt] *= alpha;
@@ -1223,7 +1091,6 @@ __global__ __launch_bounds__(256) void softmax_bias_rows_kernel(const float* __r
     bf16_t* orow = out + row * ldo;
     const int lim = causal ? min(cols, (int)blockIdx.x + 1) : cols;
     const int myseg = seg ? seg[blockIdx.x] : 0;   // block-diagonal attention: a query sees the keys of its own segment
-    constexpr float LOG2E = 1.4426950408889634f;
     auto score = [&](int c) -> float {
         if (c >= lim || (keep && !keep[c]) || (seg && seg[c] != myseg)) return -1.0e30f;
         return fmaf(xr[c], scale_log2e, br ? br[c] * LOG2E : 0.0f);
@@ -1509,7 +1376,7 @@ static int attn_fwd_prepared_impl(const void* q, const void* k, const void* vt, 
                    "attn_fwd_prepared: operands must be 16-byte aligned");
     APEXMI_REQUIRE(o_strides[0] % 8 == 0 && o_strides[1] % 8 == 0 && o_strides[2] % 8 == 0,
                    "attn_fwd_prepared: output strides must be multiples of 8 elements");
-    const float c = softmax_scale * 1.4426950408889634f;
+    const float c = softmax_scale * LOG2E;
     ApexmiProfScope prof(1, stream, 4.0 * B * H * (double)Sq * Sk * HD,
                          2.0 * B * H * HD * (2.0 * Sq + 2.0 * Sk));
     // Workgroup height: NW waves x 32 query rows, two workgroups resident per CU (64 KiB LDS each).
@@ -1725,7 +1592,7 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, void* out,
         bf16_t* pb = (bf16_t*)((char*)workspace + (size_t)Sq * sk8 * 4);
         bf16_t* vt = pb + (size_t)Sq * skp;
         bf16_t* kpad = vt + (size_t)D * skp;
-        const float c = softmax_scale * 1.4426950408889634f;
+        const float c = softmax_scale * LOG2E;
         for (int b = 0; b < B; ++b)
             for (int h = 0; h < H; ++h) {
                 const bf16_t* qp = (const bf16_t*)q + b * q_strides[0] + h * q_strides[1];
@@ -1884,7 +1751,7 @@ extern "C" int apexmi_attn_fwd_bias(const void* q, int64_t ldq, const void* k, i
     {
         ApexmiProfScope prof(1, stream, 0.0, (double)H * Sq * Sk * 10.0);
         hipLaunchKernelGGL(softmax_bias_rows_kernel, dim3(Sq, H), dim3(256), 0, stream, sc, (int64_t)sk8, Sq, Sk,
-                           softmax_scale * 1.4426950408889634f, bias, (int64_t)Sk, keep, seg, causal, pb, (int64_t)skp, skp);
+                           softmax_scale * LOG2E, bias, (int64_t)Sk, keep, seg, causal, pb, (int64_t)skp, skp);
         if (int rc = apexmi_check_launch("softmax_bias_rows")) return rc;
     }
     // V^T [Hkv*D, skp] by 128-column slices of V (independent of the head size), zero-padded key columns

@@ -3,28 +3,22 @@
 // the text keys and the image keys in two SEPARATE softmaxes; each branch result is a bf16 tensor and the two are added in bf16:
 //   out = bf16( bf16(softmax(q k_t^T s) v_t) + bf16(softmax(q k_i^T s) v_i) )
 //
-// One-pass flash kernel built like attn_masked_kernel (attention_masked.hip) without a mask: 4 waves x 32 query rows per
-// workgroup, 64-key tiles, swapped products on v_mfma_f32_32x32x16_bf16 so lane l owns query row (l & 31), K and V^T tiles staged
-// by 16-byte global_load_lds into a double-buffered XOR-swizzled LDS image, workgroups of one (batch, head) kept on one XCD.
-// The workgroup reads its query block ONCE and walks one list of tiles: the text tiles, then the image tiles (the staging of the
-// first image tile overlaps the last text tile).  Each key set has its own online softmax with a RUNNING maximum (image keys are
-// not near-uniform, so the w64 kernel's first-tile maximum does not apply), starting from a finite sentinel.  At the seam the text
+// One-pass flash kernel on the shared tile step (attn_tile.h: layout, rounding), 4 waves, packed bf16 operands, D = 128, workgroups
+// of one (batch, head) kept on one XCD.  The workgroup reads its query block ONCE and walks one list of tiles: the text tiles, then
+// the image tiles (the staging of the first image tile overlaps the last text tile).  Each key set has its own online softmax with
+// a RUNNING maximum (image keys are not near-uniform, so the w64 kernel's first-tile maximum does not apply).  At the seam the text
 // branch is normalised and rounded to bf16 (kept packed, 32 VGPRs); at the end the image branch is normalised, rounded to bf16,
-// the two are summed in f32 and stored as bf16 once.  The last tile of each set is masked in-kernel; an empty image set
-// (Sk_i = 0) stores the text branch alone.
-#include "common.h"
+// the two are summed in f32 and stored as bf16 once.  The last tile of each set excludes the keys past its end (-inf after
+// scaling); an empty image set (Sk_i = 0) stores the text branch alone.
+#include "attn_tile.h"
 
 #include <cstdint>
 
 namespace {
 
-constexpr int DKV = 64;            // keys per tile
 constexpr int DNW = 4;             // waves per workgroup
 constexpr int DQB = DNW * 32;      // query rows per workgroup
 constexpr int DD = 128;            // head dim
-constexpr float DSENTINEL = -1.0e30f;
-constexpr float DDEFER = 6.0f;     // as attention.hip: rescale only when a row maximum grows by more than 2^6
-constexpr float DLOG2E = 1.4426950408889634f;
 
 struct DualArgs {
     const uint16_t* q;
@@ -37,16 +31,11 @@ struct DualArgs {
     float c;                // |scale| * log2(e)
 };
 
-// row i of a 32-row K sub-tile holds key dperm32(i): bits 2 and 3 swapped (as attention.hip's perm32)
-APEXMI_DEVICE int dperm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
-
 __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int K_TILE = DKV * DD * 2, V_TILE = DD * DKV * 2, STAGE = K_TILE + V_TILE;
-    constexpr int CH = DD / 8;                  // 16-byte chunks per K row
-    constexpr int NP = DD / 8;                  // 1 KiB LDS-DMA pieces per image (K and V^T alike)
-    constexpr int LD = NP / DNW;                // pieces per wave per image
-    constexpr int NKS = DD / 16, NDT = DD / 32;
+    using E = ElemBf16;
+    constexpr int K_TILE = KV * DD * 2, V_TILE = DD * KV * 2, STAGE = K_TILE + V_TILE;
+    constexpr int LD = PIECES<DD, DNW>, NDT = DD / 32;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -62,35 +51,24 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
     const uint16_t* Kp1 = a.k[1] + (int64_t)hb * a.Sk[1] * DD;
     const uint16_t* Vp0 = a.vt[0] + (int64_t)hb * DD * a.Skp[0];
     const uint16_t* Vp1 = a.vt[1] + (int64_t)hb * DD * a.Skp[1];
-    const int n0 = (a.Sk[0] + DKV - 1) / DKV;
-    const int n = n0 + (a.Sk[1] + DKV - 1) / DKV;
+    const int n0 = (a.Sk[0] + KV - 1) / KV;
+    const int n = n0 + (a.Sk[1] + KV - 1) / KV;
 
-    const int q0 = qb * DQB;
-    const int qrow = q0 + wave * 32 + l31;
+    const int qrow = qb * DQB + wave * 32 + l31;
     const int qrow_c = min(qrow, a.Sq - 1);
 
     // Q fragments (B operand of S^T): lane supplies Q[qrow][16 ks + 8 hi .. +7]; a negative scale flips their signs (exact)
-    bf16x8 qf[NKS];
+    // (kept in the kernel: behind a helper that fills qf the allocation moves, 255 -> 230 VGPRs; see attention_masked.hip)
+    bf16x8 qf[DD / 16];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
+    for (int ks = 0; ks < DD / 16; ++ks) {
         u32x4 raw = *(const u32x4*)(Qp + (int64_t)qrow_c * DD + ks * 16 + hi * 8);
         if (a.neg) raw ^= u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
         qf[ks] = __builtin_bit_cast(bf16x8, raw);
     }
 
-    // staging sources.  K image: [64 rows][CH chunks], chunk ^= row & (CH - 1), row i <- key dperm32(i).
-    // V^T image: [D rows][8 chunks], chunk ^= (row >> 1) & 7.
     int k_key[LD], k_c[LD], v_row[LD], v_c[LD];
-#pragma unroll
-    for (int i = 0; i < LD; ++i) {
-        const int p = (i * DNW + wave) * 64 + lane;
-        const int krow = (p / CH) & 63, kpc = p % CH;
-        k_c[i] = (kpc ^ (krow & (CH - 1))) * 8;
-        k_key[i] = (krow & 32) + dperm32(krow & 31);
-        const int vrow = (p >> 3) & (DD - 1), vpc = p & 7;
-        v_row[i] = vrow;
-        v_c[i] = (vpc ^ ((vrow >> 1) & 7)) * 8;
-    }
+    stage_sources<DD, DNW>(wave, lane, k_key, k_c, v_row, v_c);
     // tile `it` of the combined list: text tiles [0, n0), image tiles [n0, n)
     auto stage = [&](int buf, int it) {
         char* base = smem + buf * STAGE + wave * 1024;
@@ -98,7 +76,7 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
         const uint16_t* Kp = img ? Kp1 : Kp0;
         const uint16_t* Vp = img ? Vp1 : Vp0;
         const int sk = img ? a.Sk[1] : a.Sk[0], skp = img ? a.Skp[1] : a.Skp[0];
-        const int kv0 = (img ? it - n0 : it) * DKV;
+        const int kv0 = (img ? it - n0 : it) * KV;
 #pragma unroll
         for (int i = 0; i < LD; ++i) {
             const int key = min(kv0 + k_key[i], sk - 1);
@@ -109,33 +87,17 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
             glds16(Vp + (int64_t)v_row[i] * skp + kv0 + v_c[i], base + K_TILE + i * (DNW * 1024));
     };
 
-    int k_off[2], k_sw[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-        const int row = kt * 32 + l31;
-        k_off[kt] = row * (DD * 2);
-        k_sw[kt] = row & (CH - 1);
-    }
-    int v_off[NDT], v_sw[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-        const int row = dt * 32 + l31;
-        v_off[dt] = row * 128;
-        v_sw[dt] = (row >> 1) & 7;
-    }
+    int k_off[2], k_sw[2], v_off[NDT], v_sw[NDT];
+    fragment_offsets<DD>(l31, k_off, k_sw, v_off, v_sw);
 
     f32x16 oacc[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
-    float m_run = DSENTINEL;   // running maximum, base-2 domain, an integer (see attention.hip above DEFER)
+    clear(oacc);
+    float m_run = SENTINEL;     // running maximum, base-2 domain, an integer
     float l_run = 0.0f;
     uint32_t txt[NDT][8];       // the text branch, normalised and rounded to bf16 (lane's d = 32 dt + 8 g + 4 hi + 0..3)
 
     auto finish = [&](uint32_t (&r)[NDT][8]) {
-        const float l_tot = sum_xor32(l_run);
-        const float inv = 1.0f / l_tot;
+        const float inv = 1.0f / sum_xor32(l_run);
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
@@ -147,39 +109,22 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
         const bool img = it >= n0;
         if (it == n0) {   // seam (workgroup-uniform): keep the text branch, start the image softmax
             finish(txt);
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
-            m_run = DSENTINEL;
+            clear(oacc);
+            m_run = SENTINEL;
             l_run = 0.0f;
         }
         const int sk = img ? a.Sk[1] : a.Sk[0];
-        const int kv0 = (img ? it - n0 : it) * DKV;
+        const int kv0 = (img ? it - n0 : it) * KV;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's LDS-DMA has landed (see attention.hip)
         __syncthreads();
         if (it + 1 < n) stage((it + 1) & 1, it + 1);
         const char* Ks = smem + (it & 1) * STAGE;
-        const char* Vs = Ks + K_TILE;
 
-        // ---- S^T = K Q^T : sacc[kt][r] = score(q = l31, key kv0 + kt 32 + 16 (g >> 1) + 8 hi + 4 (g & 1) + (r & 3), g = r >> 2) ----
         f32x16 sacc[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[kt][r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int c = ks * 2 + hi;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                const bf16x8 kf = *(const bf16x8*)(Ks + k_off[kt] + ((c ^ k_sw[kt]) << 4));
-                sacc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], sacc[kt], 0, 0, 0);
-            }
-        }
+        scores<E, DD>(Ks, k_off, k_sw, hi, qf, sacc);
 
-        // the last tile of a set masks the keys past its end (workgroup-uniform)
-        const bool tail = kv0 + DKV > sk;
+        // the last tile of a set excludes the keys past its end (workgroup-uniform)
+        const bool tail = kv0 + KV > sk;
         float mx;
         if (tail) {
             mx = -__builtin_inff();
@@ -187,69 +132,19 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int g = r >> 2;
-                    const int key = kv0 + kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3);
-                    sacc[kt][r] = key < sk ? sacc[kt][r] * a.c : -__builtin_inff();
+                    sacc[kt][r] = kv0 + tile_key(kt, r, hi) < sk ? sacc[kt][r] * a.c : -__builtin_inff();
                     mx = fmaxf(mx, sacc[kt][r]);
                 }
         } else {
-            mx = sacc[0][0];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kt][r]);
-            mx *= a.c;
+            mx = tile_max(sacc) * a.c;
         }
-        mx = max_xor32(mx);
-        if (__any(mx > m_run + DDEFER)) {   // wave-uniform
-            const float m_new = ceilf(fmaxf(m_run, mx));
-            const float alpha = fast_exp2(m_run - m_new);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
-        }
-        float psum = 0.0f;
-        if (tail) {
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float p = fast_exp2(sacc[kt][r] - m_run);
-                    sacc[kt][r] = p;
-                    psum += p;
-                }
-        } else {
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float p = fast_exp2(fmaf(sacc[kt][r], a.c, -m_run));
-                    sacc[kt][r] = p;
-                    psum += p;
-                }
-        }
-        l_run += psum;
+        raise_max(max_xor32(mx), m_run, l_run, oacc);
+        if (tail) l_run += exp2_scaled(sacc, m_run);
+        else l_run += exp2_fused(sacc, a.c, m_run);
 
-        // ---- P -> B-fragments: k-step kk takes regs 8 (kk & 1) .. +7 of sacc[kk >> 1] (keys 16 kk + 8 hi .. +7) ----
-        bf16x8 pf[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[kk][j] = (__bf16)sacc[kk >> 1][8 * (kk & 1) + j];
-
-        // ---- O^T += V^T P^T ----
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int c = kk * 2 + hi;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                const bf16x8 vf = *(const bf16x8*)(Vs + v_off[dt] + ((c ^ v_sw[dt]) << 4));
-                oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[kk], oacc[dt], 0, 0, 0);
-            }
-        }
+        E::v8 pf[4];
+        p_fragments<E>(sacc, pf);
+        accumulate<E, DD>(Ks + K_TILE, v_off, v_sw, hi, pf, oacc);
     }
 
     // ---- epilogue: bf16(text) + bf16(image) in f32, one bf16 store; the text branch alone when the image set is empty ----
@@ -260,11 +155,8 @@ __global__ __launch_bounds__(DNW * 64, 2) void attn_dual_kernel(const DualArgs a
 #pragma unroll
         for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float lo = __builtin_bit_cast(float, txt[dt][j] << 16) + __builtin_bit_cast(float, im[dt][j] << 16);
-                const float hi_ = __builtin_bit_cast(float, txt[dt][j] & 0xffff0000u) + __builtin_bit_cast(float, im[dt][j] & 0xffff0000u);
-                res[dt][j] = pack_bf16(lo, hi_);
-            }
+            for (int j = 0; j < 8; ++j)
+                res[dt][j] = pack_bf16(bf16_lo(txt[dt][j]) + bf16_lo(im[dt][j]), bf16_hi(txt[dt][j]) + bf16_hi(im[dt][j]));
     } else {
         finish(res);
     }
@@ -287,9 +179,9 @@ extern "C" int apexmi_attn_fwd_prepared_dual(const void* q, const void* k_t, con
     APEXMI_REQUIRE(Sk_i == 0 || (k_i && vt_i), "attn_fwd_prepared_dual: null image operand with Sk_i=%d", Sk_i);
     APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk_t > 0 && Sk_i >= 0,
                    "attn_fwd_prepared_dual: empty problem (B=%d H=%d Sq=%d Sk_t=%d Sk_i=%d)", B, H, Sq, Sk_t, Sk_i);
-    APEXMI_REQUIRE(Skp_t >= (Sk_t + DKV - 1) / DKV * DKV && Skp_t % 8 == 0 &&
-                       (Sk_i == 0 || (Skp_i >= (Sk_i + DKV - 1) / DKV * DKV && Skp_i % 8 == 0)),
-                   "attn_fwd_prepared_dual: V^T widths Skp_t=%d / Skp_i=%d must cover Sk rounded up to %d", Skp_t, Skp_i, DKV);
+    APEXMI_REQUIRE(Skp_t >= (Sk_t + KV - 1) / KV * KV && Skp_t % 8 == 0 &&
+                       (Sk_i == 0 || (Skp_i >= (Sk_i + KV - 1) / KV * KV && Skp_i % 8 == 0)),
+                   "attn_fwd_prepared_dual: V^T widths Skp_t=%d / Skp_i=%d must cover Sk rounded up to %d", Skp_t, Skp_i, KV);
     APEXMI_REQUIRE((int64_t)B * H * ((Sq + DQB - 1) / DQB) < (1ll << 31), "attn_fwd_prepared_dual: too many query blocks");
     bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k_t % 16) == 0 && ((uintptr_t)vt_t % 16) == 0 &&
                    ((uintptr_t)k_i % 16) == 0 && ((uintptr_t)vt_i % 16) == 0 && ((uintptr_t)out % 8) == 0;
@@ -305,9 +197,9 @@ extern "C" int apexmi_attn_fwd_prepared_dual(const void* q, const void* k_t, con
     a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
     a.H = H, a.Sq = Sq, a.nqb = (Sq + DQB - 1) / DQB, a.total = B * H * a.nqb;
     a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * DLOG2E;
+    a.c = fabsf(softmax_scale) * LOG2E;
 
-    constexpr int LDS = 2 * (DKV * DD * 2 + DD * DKV * 2);
+    constexpr int LDS = 2 * (KV * DD * 2 + DD * KV * 2);
     static uint64_t attr_done = 0;
     APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_dual_kernel,
                                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS));

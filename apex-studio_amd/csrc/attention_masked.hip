@@ -4,13 +4,12 @@
 //   optionally AND-ed with the top-left causal mask (key j <= query i), grouped-query heads (query head h reads kv head
 //   h / (Hq / Hkv)), bf16 or f16, D = 64 or 128.  A query row without any allowed key yields zeros.
 //
-// One-pass flash kernel built like the plain attn_fwd_d128_kernel (attention.hip): 4 waves x 32 query rows per workgroup, 64-key
-// tiles, swapped products on v_mfma_f32_32x32x16_{bf16,f16} so lane l owns query row (l & 31), K and V^T tiles staged by 16-byte
-// global_load_lds into a double-buffered XOR-swizzled LDS image, workgroups of one (batch, head) kept on one XCD.  Differences:
+// One-pass flash kernel on the shared tile step (attn_tile.h: layout, rounding), 4 waves, bf16 or f16, D = 64 or 128, workgroups of
+// one (batch, head) kept on one XCD.  Specific to this kernel:
 //   * q and k are read in place through their strides (no packing); V^T [B, Hkv, D, Skp] is staged in the workspace.
-//   * the online softmax keeps a RUNNING maximum (an additive mask can move a score by any amount), starting from a finite
-//     sentinel; excluded scores are -inf, so a row whose keys are all excluded so far never produces a NaN, and a row whose
-//     sum stays 0 stores zeros.  Consequence of the sentinel: an allowed score below -1e30 (base-2 units) counts as excluded.
+//   * an additive mask can move a score by any amount and excluded scores are -inf, so a row whose keys are all excluded so far
+//     never produces a NaN, and a row whose sum stays 0 stores zeros.  Consequence of the finite sentinel the running maximum
+//     starts from: an allowed score below -1e30 (base-2 units) counts as excluded.
 //   * per (query block, key tile) the kernel walks a list built at entry from the BLOCK MAP (attn_mask_map_kernel): SKIP tiles
 //     are never loaded nor multiplied, DENSE tiles (all allowed, additive value 0) run exactly the unmasked arithmetic, only
 //     PARTIAL tiles read the mask (4 runs of 8 keys per lane, issued ahead of the QK^T MFMAs).
@@ -26,41 +25,16 @@
 // row's coordinates from entry, the tile's 64 key records arrive in LDS with the tile (one 8-byte load per key, wave 0, issued
 // with the tile's staging and written before the barrier that publishes the tile).  Excluded scores become -inf through the
 // same fmaf as a bool mask's, so the result equals apexmi_attn_fwd_masked on the equivalent dense bool mask bit for bit.
-#include "common.h"
+#include "attn_tile.h"
 
 #include <cstdint>
 
 namespace {
 
-constexpr int MKV = 64;            // keys per tile
 constexpr int MNW = 4;             // waves per workgroup
 constexpr int MQB = MNW * 32;      // query rows per workgroup (= rows of one block-map entry)
 constexpr int MAP_SKIP = 0, MAP_DENSE = 1, MAP_PARTIAL = 2;
 constexpr int MAX_TILES = 1 << 14;  // tile index + 2-bit code in the 16-bit LDS list entries
-constexpr float SENTINEL_MAX = -1.0e30f;
-constexpr float DEFER_MAX = 6.0f;     // as attention.hip: rescale only when a row maximum grows by more than 2^6
-constexpr float LOG2E_F = 1.4426950408889634f;
-
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-
-struct ElemBf16 {
-    using v8 = bf16x8;
-    static APEXMI_DEVICE f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-    static APEXMI_DEVICE void cvt(v8& r, int j, float x) { r[j] = (__bf16)x; }
-    static APEXMI_DEVICE uint32_t pack2(float a, float b) { return pack_bf16(a, b); }
-};
-struct ElemF16 {
-    using v8 = f16x8;
-    static APEXMI_DEVICE f32x16 mfma(v8 a, v8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-    static APEXMI_DEVICE void cvt(v8& r, int j, float x) { r[j] = (_Float16)x; }
-    static APEXMI_DEVICE uint32_t pack2(float a, float b) {
-        f16x2 r;
-        r[0] = (_Float16)a;
-        r[1] = (_Float16)b;
-        return __builtin_bit_cast(uint32_t, r);
-    }
-};
 
 // mask element -> additive value in natural units (bool: 0 keep / -inf drop)
 template <int MK>
@@ -113,7 +87,7 @@ __global__ __launch_bounds__(256) void attn_window_map_kernel(const u32x2* __res
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6), qb = blockIdx.y;
     if (t >= nkt) return;   // wave-uniform; no barrier below
     const int q_lo = qb * MQB, q_n = min(Sq - q_lo, MQB);      // q_n >= 1
-    const int k_lo = t * MKV, k_n = min(Sk - k_lo, MKV);        // k_n >= 1
+    const int k_lo = t * KV, k_n = min(Sk - k_lo, KV);        // k_n >= 1
     const u32x2 kc = wk[k_lo + min(lane, k_n - 1)];
     const u32x2 qa = wq[q_lo + min(lane, q_n - 1)], qc = wq[q_lo + min(lane + 64, q_n - 1)];
     const int k0 = wcoord0(kc), k1 = wcoord1(kc), k2 = wcoord2(kc);
@@ -164,9 +138,9 @@ __global__ __launch_bounds__(256) void attn_mask_map_kernel(const void* __restri
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)(z / Hm) * m_sb + (int64_t)(z % Hm) * m_sh;
     int any = 0, dense = 1;
-    if (VEC && (t + 1) * MKV <= Sk) {
-        constexpr int NE = 16 / sizeof(ET), LPR = MKV / NE, RPS = 256 / LPR;   // elements per lane, lanes per row, rows per step
-        const int key = t * MKV + (tid % LPR) * NE;
+    if (VEC && (t + 1) * KV <= Sk) {
+        constexpr int NE = 16 / sizeof(ET), LPR = KV / NE, RPS = 256 / LPR;   // elements per lane, lanes per row, rows per step
+        const int key = t * KV + (tid % LPR) * NE;
         for (int r = qb * MQB + tid / LPR; r < min(Sq, (qb + 1) * MQB); r += RPS) {
             const u32x4 raw = *(const u32x4*)((const ET*)mask + base + (int64_t)r * m_sq + key);
             const ET* e = (const ET*)&raw;
@@ -179,7 +153,7 @@ __global__ __launch_bounds__(256) void attn_mask_map_kernel(const void* __restri
             }
         }
     } else {
-        const int key = t * MKV + (tid & 63);
+        const int key = t * KV + (tid & 63);
         if (key < Sk) {
             const int64_t kof = base + (int64_t)key * m_sk;
             for (int r = qb * MQB + (tid >> 6); r < min(Sq, (qb + 1) * MQB); r += 4) {
@@ -225,18 +199,12 @@ __global__ __launch_bounds__(256) void v_transpose64_kernel(const uint16_t* __re
     }
 }
 
-// row i of a 32-row K sub-tile holds key mperm32(i): bits 2 and 3 swapped (as attention.hip's perm32)
-APEXMI_DEVICE int mperm32(int i) { return (i & ~0xC) | ((i & 4) << 1) | ((i & 8) >> 1); }
-
 template <typename E, int D, bool WIN>
 __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using v8 = typename E::v8;
-    constexpr int K_TILE = MKV * D * 2, V_TILE = D * MKV * 2, STAGE = K_TILE + V_TILE;
-    constexpr int CH = D / 8;                   // 16-byte chunks per K row
-    constexpr int NP = D / 8;                   // 1 KiB LDS-DMA pieces per image (K and V^T alike)
-    constexpr int LD = (NP + MNW - 1) / MNW;    // pieces per wave per image
-    constexpr int NKS = D / 16, NDT = D / 32;
+    constexpr int K_TILE = KV * D * 2, V_TILE = D * KV * 2, STAGE = K_TILE + V_TILE;
+    constexpr int NP = D / 8, LD = PIECES<D, MNW>, NDT = D / 32;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -263,8 +231,8 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
     // ---- tile list: the key tiles this workgroup visits, with their block-map code (wave 0 builds it, LDS) ----
     int* list_n = (int*)(smem + 2 * STAGE);
     uint16_t* list = (uint16_t*)(smem + 2 * STAGE + 16);
-    const int nt = (a.Sk + MKV - 1) / MKV;
-    const int t_end = a.causal ? min(nt, min(q0 + MQB - 1, a.Sq - 1) / MKV + 1) : nt;
+    const int nt = (a.Sk + KV - 1) / KV;
+    const int t_end = a.causal ? min(nt, min(q0 + MQB - 1, a.Sq - 1) / KV + 1) : nt;
     if (wave == 0) {
         const uint8_t* mrow = nullptr;
         if (a.map) {
@@ -284,34 +252,24 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
     }
 
     // Q fragments (B operand of S^T): lane supplies Q[qrow][16 ks + 8 hi .. +7]; a negative scale flips their signs (exact)
-    v8 qf[NKS];
+    // (kept in the kernel: behind a helper that fills qf this load costs the masked and dual kernels 18-35 VGPRs, and at D = 64
+    // the third workgroup per CU that the parent's 186 VGPRs rule out)
+    v8 qf[D / 16];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
+    for (int ks = 0; ks < D / 16; ++ks) {
         u32x4 raw = *(const u32x4*)(Qp + (int64_t)qrow_c * a.q_ss + ks * 16 + hi * 8);
         if (a.neg) raw ^= u32x4{0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};
         qf[ks] = __builtin_bit_cast(v8, raw);
     }
 
-    // staging sources.  K image: [64 rows][CH chunks], chunk ^= row & (CH - 1), row i <- key mperm32(i).
-    // V^T image: [D rows][8 chunks], chunk ^= (row >> 1) & 7.
-    int k_key[LD], k_c[LD];
+    int k_key[LD], k_c[LD], v_row[LD], v_c[LD];
+    stage_sources<D, MNW>(wave, lane, k_key, k_c, v_row, v_c);
     const uint16_t* v_src[LD];
 #pragma unroll
-    for (int i = 0; i < LD; ++i) {
-        const int p = (i * MNW + wave) * 64 + lane;
-        {
-            const int row = (p / CH) & 63, pc = p % CH;
-            k_c[i] = (pc ^ (row & (CH - 1))) * 8;
-            k_key[i] = (row & 32) + mperm32(row & 31);
-        }
-        {
-            const int row = (p >> 3) & (D - 1), pc = p & 7;
-            v_src[i] = Vp + (int64_t)row * a.Skp + (pc ^ ((row >> 1) & 7)) * 8;
-        }
-    }
+    for (int i = 0; i < LD; ++i) v_src[i] = Vp + (int64_t)v_row[i] * a.Skp + v_c[i];
     auto stage = [&](int buf, int t) {
         char* base = smem + buf * STAGE + wave * 1024;
-        const int kv0 = t * MKV;
+        const int kv0 = t * KV;
 #pragma unroll
         for (int i = 0; i < LD; ++i)
             if (i * MNW + wave < NP) {   // wave-uniform
@@ -323,20 +281,8 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
             if (i * MNW + wave < NP) glds16(v_src[i] + kv0, base + K_TILE + i * (MNW * 1024));
     };
 
-    int k_off[2], k_sw[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-        const int row = kt * 32 + l31;
-        k_off[kt] = row * (D * 2);
-        k_sw[kt] = row & (CH - 1);
-    }
-    int v_off[NDT], v_sw[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt) {
-        const int row = dt * 32 + l31;
-        v_off[dt] = row * 128;
-        v_sw[dt] = (row >> 1) & 7;
-    }
+    int k_off[2], k_sw[2], v_off[NDT], v_sw[NDT];
+    fragment_offsets<D>(l31, k_off, k_sw, v_off, v_sw);
     const int64_t m_row = (int64_t)b * a.m_sb + (int64_t)h * a.m_sh + (int64_t)qrow_c * a.m_sq;
 
     // coordinate window: |cq - ck| <= r  <=>  (unsigned)(cq + r - ck) <= 2 r; the lane keeps cq + r of its query row.  The key
@@ -351,26 +297,23 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
     const uint32_t w2r0 = 2u * (uint32_t)a.wr0, w2r1 = 2u * (uint32_t)a.wr1, w2r2 = 2u * (uint32_t)a.wr2;
 
     f32x16 oacc[NDT];
-#pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[dt][r] = 0.0f;
-    float m_run = SENTINEL_MAX;  // running maximum, base-2 domain, an integer (see attention.hip above DEFER)
+    clear(oacc);
+    float m_run = SENTINEL;  // running maximum, base-2 domain, an integer
     float l_run = 0.0f;
 
     __syncthreads();
     const int n = *list_n;
     if (n > 0) {
         stage(0, list[0] & (MAX_TILES - 1));
-        if (WIN && wave == 0 && (list[0] >> 14) == MAP_PARTIAL) wk_next = a.wk[min((list[0] & (MAX_TILES - 1)) * MKV + lane, a.Sk - 1)];
+        if (WIN && wave == 0 && (list[0] >> 14) == MAP_PARTIAL) wk_next = a.wk[min((list[0] & (MAX_TILES - 1)) * KV + lane, a.Sk - 1)];
     }
     for (int it = 0; it < n; ++it) {
         const int ent = list[it];
         const int t = ent & (MAX_TILES - 1), code = ent >> 14;
-        const int kv0 = t * MKV;
+        const int kv0 = t * KV;
         // window: this tile's key records (loaded with its staging) into the image of its stage; the image was last read two
         // tiles ago, before the barrier every wave has passed since
-        if (WIN && wave == 0 && code == MAP_PARTIAL) wk_lds[(it & 1) * MKV + lane] = wk_next;
+        if (WIN && wave == 0 && code == MAP_PARTIAL) wk_lds[(it & 1) * KV + lane] = wk_next;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the tile's LDS-DMA has landed (see attention.hip)
         __syncthreads();
 
@@ -379,9 +322,8 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
         if (!WIN && code == MAP_PARTIAL) {
 #define MASK_LOADS(MK)                                                                                          \
     _Pragma("unroll") for (int kt = 0; kt < 2; ++kt) _Pragma("unroll") for (int r = 0; r < 16; ++r) {           \
-        const int g = r >> 2;                                                                                   \
-        const int key = min(kv0 + kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3), a.Sk - 1);         \
-        mv[kt][r] = mask_value<MK>(a.mask, m_row + (int64_t)key * a.m_sk) * LOG2E_F;                            \
+        const int key = min(kv0 + tile_key(kt, r, hi), a.Sk - 1);                                               \
+        mv[kt][r] = mask_value<MK>(a.mask, m_row + (int64_t)key * a.m_sk) * LOG2E;                              \
     }
             switch (a.mkind) {
                 case APEXMI_MASK_BOOL: MASK_LOADS(APEXMI_MASK_BOOL); break;
@@ -394,42 +336,27 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
         if (it + 1 < n) {
             stage((it + 1) & 1, list[it + 1] & (MAX_TILES - 1));
             if (WIN && wave == 0 && (list[it + 1] >> 14) == MAP_PARTIAL)
-                wk_next = a.wk[min((list[it + 1] & (MAX_TILES - 1)) * MKV + lane, a.Sk - 1)];
+                wk_next = a.wk[min((list[it + 1] & (MAX_TILES - 1)) * KV + lane, a.Sk - 1)];
         }
         const char* Ks = smem + (it & 1) * STAGE;
-        const char* Vs = Ks + K_TILE;
 
-        // ---- S^T = K Q^T : sacc[kt][r] = score(q = l31, key kv0 + kt 32 + 16 (g >> 1) + 8 hi + 4 (g & 1) + (r & 3), g = r >> 2) ----
         f32x16 sacc[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[kt][r] = 0.0f;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) {
-            const int c = ks * 2 + hi;
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt) {
-                const v8 kf = *(const v8*)(Ks + k_off[kt] + ((c ^ k_sw[kt]) << 4));
-                sacc[kt] = E::mfma(kf, qf[ks], sacc[kt]);
-            }
-        }
+        scores<E, D>(Ks, k_off, k_sw, hi, qf, sacc);
 
         // per-element path (workgroup-uniform): PARTIAL tiles, tiles crossing the causal diagonal, the key tail
-        const bool elem = code == MAP_PARTIAL || (a.causal && kv0 + MKV - 1 > q0) || kv0 + MKV > a.Sk;
+        const bool elem = code == MAP_PARTIAL || (a.causal && kv0 + KV - 1 > q0) || kv0 + KV > a.Sk;
         float mx;
         if (elem) {
             const bool part = code == MAP_PARTIAL;
             const int lim = a.causal ? min(a.Sk - 1, qrow) : a.Sk - 1;
             mx = -__builtin_inff();
             if (WIN && part) {   // the rule, evaluated on the tile's key records: 0 (keep) or -inf, as a bool mask's values
-                const u32x2* kc = wk_lds + (it & 1) * MKV;
+                const u32x2* kc = wk_lds + (it & 1) * KV;
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int g = r >> 2;
-                        const u32x2 c = kc[kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3)];
+                        const u32x2 c = kc[tile_key(kt, r, hi)];
                         const bool ok = (uint32_t)(wqa0 - wcoord0(c)) <= w2r0 && (uint32_t)(wqa1 - wcoord1(c)) <= w2r1 &&
                                         (uint32_t)(wqa2 - wcoord2(c)) <= w2r2;
                         mv[kt][r] = ok ? 0.0f : -__builtin_inff();
@@ -439,31 +366,16 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int g = r >> 2;
-                    const int key = kv0 + kt * 32 + 16 * (g >> 1) + 8 * hi + 4 * (g & 1) + (r & 3);
                     const float x = fmaf(sacc[kt][r], a.c, part ? mv[kt][r] : 0.0f);
-                    sacc[kt][r] = key <= lim ? x : -__builtin_inff();
+                    sacc[kt][r] = kv0 + tile_key(kt, r, hi) <= lim ? x : -__builtin_inff();
                     mx = fmaxf(mx, sacc[kt][r]);
                 }
         } else {
-            mx = sacc[0][0];
-#pragma unroll
-            for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kt][r]);
-            mx *= a.c;
+            mx = tile_max(sacc) * a.c;
         }
-        mx = max_xor32(mx);
-        if (__any(mx > m_run + DEFER_MAX)) {   // wave-uniform; -inf (nothing allowed yet) never raises the sentinel
-            const float m_new = ceilf(fmaxf(m_run, mx));
-            const float alpha = fast_exp2(m_run - m_new);
-            m_run = m_new;
-            l_run *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oacc[dt][r] *= alpha;
-        }
+        raise_max(max_xor32(mx), m_run, l_run, oacc);   // -inf (nothing allowed yet) never raises the sentinel
+        // the two exponent forms of attn_tile.h (exp2_scaled / exp2_fused), written out: through the helpers this kernel's D = 64
+        // tile loop is scheduled differently and measures 0.2-0.6 % slower (profiles/attn_tile_refactor.md)
         float psum = 0.0f;
         if (elem) {
 #pragma unroll
@@ -486,53 +398,28 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
         }
         l_run += psum;
 
-        // ---- P -> B-fragments: k-step kk takes regs 8 (kk & 1) .. +7 of sacc[kk >> 1] (keys 16 kk + 8 hi .. +7) ----
         v8 pf[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) E::cvt(pf[kk], j, sacc[kk >> 1][8 * (kk & 1) + j]);
-
-        // ---- O^T += V^T P^T ----
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int c = kk * 2 + hi;
-#pragma unroll
-            for (int dt = 0; dt < NDT; ++dt) {
-                const v8 vf = *(const v8*)(Vs + v_off[dt] + ((c ^ v_sw[dt]) << 4));
-                oacc[dt] = E::mfma(vf, pf[kk], oacc[dt]);
-            }
-        }
+        p_fragments<E>(sacc, pf);
+        accumulate<E, D>(Ks + K_TILE, v_off, v_sw, hi, pf, oacc);
     }
 
-    // ---- epilogue: O[q][d] = O^T / l (0 for a row without an allowed key); lane holds d = 32 dt + 8 g + 4 hi + (0..3) ----
+    // ---- epilogue: O[q][d] = O^T / l, 0 for a row without an allowed key ----
     const float l_tot = sum_xor32(l_run);
     const float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
-    if (qrow < a.Sq) {
-        uint16_t* op = a.o + (int64_t)b * a.o_sb + (int64_t)qrow * a.o_ss + (int64_t)h * a.o_sh;
-#pragma unroll
-        for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 o;
-                o[0] = E::pack2(oacc[dt][4 * g + 0] * inv, oacc[dt][4 * g + 1] * inv);
-                o[1] = E::pack2(oacc[dt][4 * g + 2] * inv, oacc[dt][4 * g + 3] * inv);
-                *(u32x2*)(op + dt * 32 + g * 8 + hi * 4) = o;
-            }
-    }
+    if (qrow < a.Sq) store_row<E>(a.o + (int64_t)b * a.o_sb + (int64_t)qrow * a.o_ss + (int64_t)h * a.o_sh, hi, oacc, inv);
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 size_t vt_bytes(int B, int Hkv, int Sk, int D) {
-    const size_t skp = (size_t)((Sk + MKV - 1) / MKV) * MKV;
+    const size_t skp = (size_t)((Sk + KV - 1) / KV) * KV;
     return align256((size_t)B * Hkv * D * skp * 2);
 }
 
 template <typename E, int D, bool WIN = false>
 int launch_masked(const MaskedArgs& a, hipStream_t stream) {
-    constexpr int STAGE = 2 * MKV * D * 2;
-    constexpr int WK = WIN ? 2 * MKV * 8 : 0;   // the two key-record images of a window launch
+    constexpr int STAGE = 2 * KV * D * 2;
+    constexpr int WK = WIN ? 2 * KV * 8 : 0;   // the two key-record images of a window launch
     static uint64_t attr_done = 0;
     APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D, WIN>,
                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -581,7 +468,7 @@ void launch_map(const MaskedArgs& a, int Bm, int Hm, uint8_t* map, hipStream_t s
 
 extern "C" size_t apexmi_attn_masked_workspace_bytes(int B, int Hq, int Hkv, int Sq, int Sk, int D) {
     if (B <= 0 || Hq <= 0 || Hkv <= 0 || Sq <= 0 || Sk <= 0 || (D != 64 && D != 128)) return 0;
-    const size_t nqb = (size_t)((Sq + MQB - 1) / MQB), nkt = (size_t)((Sk + MKV - 1) / MKV);
+    const size_t nqb = (size_t)((Sq + MQB - 1) / MQB), nkt = (size_t)((Sk + KV - 1) / KV);
     return vt_bytes(B, Hkv, Sk, D) + align256((size_t)B * Hq * nqb * nkt);
 }
 
@@ -603,7 +490,7 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
                    "attn_fwd_masked: mask dtype code %d unsupported (bool, f32, bf16, f16)", mask_dtype);
     APEXMI_REQUIRE(!mask || mask_strides[3] == 0 || mask_strides[3] == 1,
                    "attn_fwd_masked: mask key stride %lld must be 0 or 1", (long long)(mask ? mask_strides[3] : 0));
-    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_masked: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_masked: Sk=%d above %d keys", Sk, MAX_TILES * KV);
     APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_masked: too many query blocks");
     bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
     for (int i = 0; i < 3; ++i)
@@ -620,11 +507,11 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
     a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
     a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
     a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
-    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + MKV - 1) / MKV) * MKV;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * Hq * a.nqb;
+    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + KV - 1) / KV) * KV;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * Hq * a.nqb;
     a.causal = is_causal ? 1 : 0;
     a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E_F;
+    a.c = fabsf(softmax_scale) * LOG2E;
 
     // V^T [B, Hkv, D, Skp]
     uint16_t* vt = (uint16_t*)workspace;
@@ -657,14 +544,14 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
 
 extern "C" size_t apexmi_attn_window_map_bytes(int Sq, int Sk) {
     if (Sq <= 0 || Sk <= 0) return 0;
-    return (size_t)((Sq + MQB - 1) / MQB) * (size_t)((Sk + MKV - 1) / MKV);
+    return (size_t)((Sq + MQB - 1) / MQB) * (size_t)((Sk + KV - 1) / KV);
 }
 
 extern "C" int apexmi_attn_window_map(const void* q_coords, const void* k_coords, int Sq, int Sk, int r0, int r1, int r2,
                                       void* map, size_t map_bytes, apexmi_stream_t stream_) {
     APEXMI_REQUIRE(Sq > 0 && Sk > 0, "attn_window_map: empty problem (Sq=%d Sk=%d)", Sq, Sk);
-    const int nqb = (Sq + MQB - 1) / MQB, nkt = (Sk + MKV - 1) / MKV;
-    APEXMI_REQUIRE(nkt <= MAX_TILES, "attn_window_map: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    const int nqb = (Sq + MQB - 1) / MQB, nkt = (Sk + KV - 1) / KV;
+    APEXMI_REQUIRE(nkt <= MAX_TILES, "attn_window_map: Sk=%d above %d keys", Sk, MAX_TILES * KV);
     APEXMI_REQUIRE(nqb <= 65535, "attn_window_map: Sq=%d above %d query rows", Sq, 65535 * MQB);
     APEXMI_REQUIRE(map && map_bytes >= apexmi_attn_window_map_bytes(Sq, Sk), "attn_window_map: map buffer too small (%zu < %zu)",
                    map_bytes, apexmi_attn_window_map_bytes(Sq, Sk));
@@ -687,7 +574,7 @@ extern "C" int apexmi_attn_fwd_window(const void* q, const void* k, const void* 
     APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_window: head dim %d unsupported (64 or 128)", D);
     APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_window: dtype %d unsupported (bf16 or f16)", dtype);
     APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_window: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
-    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_window: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_window: Sk=%d above %d keys", Sk, MAX_TILES * KV);
     APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_window: too many query blocks");
     bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
     for (int i = 0; i < 3; ++i)
@@ -704,10 +591,10 @@ extern "C" int apexmi_attn_fwd_window(const void* q, const void* k, const void* 
     a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
     a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
     a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
-    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + MKV - 1) / MKV) * MKV;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * Hq * a.nqb;
+    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + KV - 1) / KV) * KV;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * Hq * a.nqb;
     a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E_F;
+    a.c = fabsf(softmax_scale) * LOG2E;
     uint16_t* vt = (uint16_t*)workspace;
     a.vt = vt;
     if (int rc = transpose_v(v, v_strides, B, Hkv, Sk, a.Skp, D, vt, stream_)) return rc;
@@ -726,12 +613,12 @@ extern "C" int apexmi_attn_fwd_prepared_window(const void* q, const void* k, con
     constexpr int D = 128;
     APEXMI_REQUIRE(q && k && vt && out && o_strides, "attn_fwd_prepared_window: null operand");
     APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attn_fwd_prepared_window: empty problem");
-    APEXMI_REQUIRE(Skp % MKV == 0 && Skp >= Sk, "attn_fwd_prepared_window: Skp=%d must be Sk=%d rounded up to 64", Skp, Sk);
+    APEXMI_REQUIRE(Skp % KV == 0 && Skp >= Sk, "attn_fwd_prepared_window: Skp=%d must be Sk=%d rounded up to 64", Skp, Sk);
     APEXMI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 && ((uintptr_t)out % 8) == 0,
                    "attn_fwd_prepared_window: operands must be 16-byte aligned");
     APEXMI_REQUIRE(o_strides[0] % 4 == 0 && o_strides[1] % 4 == 0 && o_strides[2] % 4 == 0,
                    "attn_fwd_prepared_window: output strides must be multiples of 4 elements");
-    APEXMI_REQUIRE((Sk + MKV - 1) / MKV <= MAX_TILES, "attn_fwd_prepared_window: Sk=%d above %d keys", Sk, MAX_TILES * MKV);
+    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_prepared_window: Sk=%d above %d keys", Sk, MAX_TILES * KV);
     APEXMI_REQUIRE((int64_t)B * H * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_prepared_window: too many query blocks");
 
     MaskedArgs a{};
@@ -744,9 +631,9 @@ extern "C" int apexmi_attn_fwd_prepared_window(const void* q, const void* k, con
     a.k_sb = (int64_t)H * Sk * D, a.k_sh = (int64_t)Sk * D, a.k_ss = D;
     a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
     a.Hq = H, a.group = 1, a.Sq = Sq, a.Sk = Sk, a.Skp = Skp;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + MKV - 1) / MKV, a.total = B * H * a.nqb;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * H * a.nqb;
     a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E_F;
+    a.c = fabsf(softmax_scale) * LOG2E;
     ApexmiProfScope prof(1, stream, 4.0 * B * H * (double)Sq * Sk * D, 0.0);
     return launch_masked<ElemBf16, 128, true>(a, stream);
 }

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
     const int wbase = wave * 4096;
 #else
     const int krow0 = 4 * wave + (lane >> 4);
-    const int voff_k = w64_perm32(krow0) * (HD * 2) + (((lane & 15) ^ krow0) << 4);
+    const int voff_k = perm32(krow0) * (HD * 2) + (((lane & 15) ^ krow0) << 4);
     const int vrow0 = 8 * wave + (lane >> 3);
     const int voff_v = vrow0 * Skp * 2 + (((lane & 7) ^ ((vrow0 >> 1) & 7)) << 4);
     const int v_piece = __builtin_amdgcn_readfirstlane(32 * Skp * 2);

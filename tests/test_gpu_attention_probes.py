@@ -230,6 +230,34 @@ def test_dual_selection(Sk_i):
     measured(f"probe B dual Sk_t={P.DUAL_SK_T} Sk_i={Sk_i}", P.selection_ratio(out.permute(0, 2, 1, 3).cpu(), expect, bound), 1.0)
 
 
+# ----------------------------------------------------------------------- one tile step (csrc/attn_tile.h) behind three kernels
+@pytest.mark.parametrize("Sk", [64, 192, 65, 200])
+def test_plain_masked_and_dual_kernels_agree_bit_for_bit(Sk):
+    """Without a mask and with a positive scale the 4-wave plain kernel, the masked kernel and the dual kernel with an empty image
+    set run the same arithmetic in the same order: the same MFMA and summation order, and the multiply by c > 0 commutes exactly
+    with the row maximum.  On a ragged last tile (Sk = 65, 200) the plain kernel's finite sentinel and the others' -inf both give
+    p = 0 and leave the row maximum alone.  Sq = 160 is one full and one ragged query block."""
+    B, H, Sq, D = 1, 2, 160, 128
+    g = torch.Generator().manual_seed(Sk)
+    q, k, v = (torch.randn(B, H, S, D, generator=g).to(BF) for S in (Sq, Sk, Sk))
+    qd, (kd, vt) = q.to(DEV), _prepared(k, v)
+    plain, dual = (torch.empty(B, Sq, H, D, dtype=BF, device=DEV) for _ in range(2))
+    lib.tune_set("attn.waves", 4)
+    try:
+        ops.attention_prepared(qd, kd, vt, plain, Sk)
+        torch.cuda.synchronize()
+    finally:
+        lib.tune_set("attn.waves", 0)
+    masked = ops.attention_masked(qd, kd, v.to(DEV))
+    ops.attention_prepared_dual(qd, kd, vt, Sk, None, None, 0, dual)
+    torch.cuda.synchronize()
+    plain, dual = plain.permute(0, 2, 1, 3), dual.permute(0, 2, 1, 3)
+    assert torch.isfinite(plain.float()).all() and plain.float().abs().max() > 0
+    assert torch.equal(plain, masked), "plain (attn.waves = 4) vs masked without a mask"
+    assert torch.equal(masked, dual), "masked without a mask vs dual with Sk_i = 0"
+    assert torch.equal(plain, dual), "plain (attn.waves = 4) vs dual with Sk_i = 0"
+
+
 # ------------------------------------------------------------------------- ops.attention_bias / ops.attention_framecausal: probe A
 # These two materialise P: the row softmax stores bf16(p / l), the NORMALISED probability, so P = bf16(1 / n) is rounded (<= u),
 # a rounding the flash kernels' derivation (P exactly 1) does not have; the store adds its own u.  The worst case is 2 u (1 + u / 2),
