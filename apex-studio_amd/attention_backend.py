@@ -20,7 +20,9 @@ attention are not on any call site of the path: they raise, th
 any attn_mask broadcastable to [B, Hq, Sq, Sk] (bool keep-mask, or additive float32 / q's dtype), is_causal (top-left
 aligned, AND-ed with the mask), grouped-query heads with enable_gqa, bf16 / f16, D = 64 or 128.  A query row with no allowed
 key returns zeros (as torch's CPU sdpa).  No host sync for any input.  Dropout, other dtypes or head sizes and CPU tensors
-raise ApexMIError; nothing falls back to torch.
+raise ApexMIError; nothing falls back to torch.  `return_lse=True` (flash-attn's convention) returns (out, lse): lse [B, Hq, Sq]
+float32, the natural-log row normaliser, -inf for a row with no allowed key; ops.attention_merge combines such pairs over
+separate key sets.
 
 "hip_mfma_window" (KEY_WINDOW) is coordinate-window sparse attention (ops.attention_window): the reference
 calling convention plus `window_plan=` (an ops.WindowPlan from ops.window_plan) in **kwargs.  An opt-in approximation of the
@@ -68,10 +70,12 @@ def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = 
 
 
 def hip_mfma_sdpa(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None,
-                  enable_gqa: bool = False, **kwargs):
+                  enable_gqa: bool = False, return_lse: bool = False, **kwargs):
     if dropout_p > 0:
         raise ApexMIError("hip_mfma_sdpa: dropout is not supported (inference only)")
-    return ops.attention_masked(q, k, v, attn_mask, is_causal=is_causal, softmax_scale=softmax_scale, enable_gqa=enable_gqa)
+    # return_lse: (out, lse [B,Hq,Sq] float32), the partial result ops.attention_merge combines over key sets
+    return ops.attention_masked(q, k, v, attn_mask, is_causal=is_causal, softmax_scale=softmax_scale, enable_gqa=enable_gqa,
+                                return_lse=return_lse)
 
 
 def hip_mfma_window(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None,

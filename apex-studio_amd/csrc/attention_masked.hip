@@ -35,6 +35,7 @@ constexpr int MNW = 4;             // waves per workgroup
 constexpr int MQB = MNW * 32;      // query rows per workgroup (= rows of one block-map entry)
 constexpr int MAP_SKIP = 0, MAP_DENSE = 1, MAP_PARTIAL = 2;
 constexpr int MAX_TILES = 1 << 14;  // tile index + 2-bit code in the 16-bit LDS list entries
+constexpr float LN2 = 0.6931471805599453f;
 
 // mask element -> additive value in natural units (bool: 0 keep / -inf drop)
 template <int MK>
@@ -67,6 +68,9 @@ struct MaskedArgs {
     const u32x2* wq;
     const u32x2* wk;
     int wr0, wr1, wr2;
+    // log-sum-exp output (LSE kernels only): f32 [B, Hq, Sq] through element strides (b, h, q)
+    float* lse;
+    int64_t l_sb, l_sh, l_sq;
 };
 
 // coordinate a (0..2) of a packed record, sign-extended
@@ -199,7 +203,9 @@ __global__ __launch_bounds__(256) void v_transpose64_kernel(const uint16_t* __re
     }
 }
 
-template <typename E, int D, bool WIN>
+// LSE (apexmi_attn_fwd_masked_lse) is a compile-time variant: the instantiations without it keep their registers (at D = 64
+// the 186 VGPRs noted below), the ones with it run the same loop and add one logf and one f32 store per row to the epilogue.
+template <typename E, int D, bool WIN, bool LSE = false>
 __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using v8 = typename E::v8;
@@ -407,6 +413,96 @@ __global__ __launch_bounds__(MNW * 64, 2) void attn_masked_kernel(const MaskedAr
     const float l_tot = sum_xor32(l_run);
     const float inv = l_tot > 0.0f ? 1.0f / l_tot : 0.0f;
     if (qrow < a.Sq) store_row<E>(a.o + (int64_t)b * a.o_sb + (int64_t)qrow * a.o_ss + (int64_t)h * a.o_sh, hi, oacc, inv);
+    // ln sum_j exp(scale q k_j + mask_j) = m ln 2 + ln l from the row's (integer, base-2) maximum and its sum, -inf for a row
+    // without an allowed key; the row's low-half lane stores it
+    if constexpr (LSE) {
+        if (hi == 0 && qrow < a.Sq)
+            a.lse[(int64_t)b * a.l_sb + (int64_t)h * a.l_sh + (int64_t)qrow * a.l_sq] =
+                l_tot > 0.0f ? fmaf(m_run, LN2, logf(l_tot)) : -__builtin_inff();
+    }
+}
+
+// ---- merge of partial results over key chunks (apexmi_attn_merge) ----
+// out = sum_p w_p o_p / sum_p w_p,  lse = m + ln sum_p w_p  with  m = max_p lse_p,  w_p = exp(lse_p - m)  (0 for lse_p = -inf, so
+// a row whose partials are all -inf gives 0 and -inf and (-inf) - (-inf) is never formed).  One lane per 16 bytes of an output
+// row: it reads its 8 elements of every partial once (all loads issued before the first use) and the row's N lse values (shared
+// by the D / 8 lanes of the row through the cache), f32 arithmetic, one rounding at the store.  The lane reads what it
+// overwrites before it writes, so `out` may be one of the partials.  The pointer tables travel in the kernel arguments.
+constexpr int MERGE_MAX = 8;
+
+struct MergeArgs {
+    const uint16_t* o[MERGE_MAX];
+    const float* l[MERGE_MAX];
+    uint16_t* out;
+    float* lse_out;          // nullptr: not wanted
+    int64_t o_sb, o_ss, o_sh, l_sb, l_sh, l_sq;
+    int64_t total;           // lanes: B Sq H (D / 8)
+    int H, Sq, CH;           // CH = D / 8
+};
+
+template <typename E>
+APEXMI_DEVICE void unpack8_as(const u32x4 v, float* f);
+template <>
+APEXMI_DEVICE void unpack8_as<ElemBf16>(const u32x4 v, float* f) { unpack8(v, f); }
+template <>
+APEXMI_DEVICE void unpack8_as<ElemF16>(const u32x4 v, float* f) {
+    const f16x8 x = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = (float)x[i];
+}
+
+template <typename E, int N>
+__global__ __launch_bounds__(256) void attn_merge_kernel(const MergeArgs a) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.total) return;
+    const int c = (int)(t % a.CH);
+    int64_t r = t / a.CH;
+    const int h = (int)(r % a.H);
+    r /= a.H;
+    const int sq = (int)(r % a.Sq);
+    const int64_t b = r / a.Sq;
+    const int64_t oo = b * a.o_sb + (int64_t)sq * a.o_ss + (int64_t)h * a.o_sh + c * 8;
+    const int64_t lo = b * a.l_sb + (int64_t)h * a.l_sh + (int64_t)sq * a.l_sq;
+    float ls[N];
+    u32x4 raw[N];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+        ls[p] = a.l[p][lo];
+        raw[p] = *(const u32x4*)(a.o[p] + oo);
+    }
+    float m = ls[0];
+#pragma unroll
+    for (int p = 1; p < N; ++p) m = fmaxf(m, ls[p]);
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float den = 0.0f;
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+        const float w = ls[p] == -__builtin_inff() ? 0.0f : expf(ls[p] - m);
+        float f[8];
+        unpack8_as<E>(raw[p], f);
+        den += w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += w > 0.0f ? w * f[i] : 0.0f;   // a partial of weight 0 contributes nothing, whatever it holds
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = den > 0.0f ? acc[i] / den : 0.0f;
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = E::pack2(acc[2 * i], acc[2 * i + 1]);
+    *(u32x4*)(a.out + oo) = o;
+    if (c == 0 && a.lse_out) a.lse_out[lo] = den > 0.0f ? m + logf(den) : -__builtin_inff();
+}
+
+template <typename E>
+int launch_merge(int n, const MergeArgs& a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
+    switch (n) {
+#define MERGE_CASE(N) \
+    case N: hipLaunchKernelGGL((attn_merge_kernel<E, N>), grid, block, 0, stream, a); break;
+        MERGE_CASE(1) MERGE_CASE(2) MERGE_CASE(3) MERGE_CASE(4) MERGE_CASE(5) MERGE_CASE(6) MERGE_CASE(7) MERGE_CASE(8)
+#undef MERGE_CASE
+    }
+    return apexmi_check_launch("attn_merge");
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -416,17 +512,17 @@ size_t vt_bytes(int B, int Hkv, int Sk, int D) {
     return align256((size_t)B * Hkv * D * skp * 2);
 }
 
-template <typename E, int D, bool WIN = false>
+template <typename E, int D, bool WIN = false, bool LSE = false>
 int launch_masked(const MaskedArgs& a, hipStream_t stream) {
     constexpr int STAGE = 2 * KV * D * 2;
     constexpr int WK = WIN ? 2 * KV * 8 : 0;   // the two key-record images of a window launch
     static uint64_t attr_done = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D, WIN>,
+    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D, WIN, LSE>,
                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
                                                               2 * STAGE + 16 + 2 * MAX_TILES + WK));
     const int lds = 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15) + WK;
-    hipLaunchKernelGGL((attn_masked_kernel<E, D, WIN>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
-    return apexmi_check_launch(WIN ? "attn_fwd_window" : "attn_fwd_masked");
+    hipLaunchKernelGGL((attn_masked_kernel<E, D, WIN, LSE>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
+    return apexmi_check_launch(WIN ? "attn_fwd_window" : LSE ? "attn_fwd_masked_lse" : "attn_fwd_masked");
 }
 
 // V [B, Hkv, Sk, D] (strided rows) -> V^T [B, Hkv, D, Skp] zero padded
@@ -472,32 +568,34 @@ extern "C" size_t apexmi_attn_masked_workspace_bytes(int B, int Hq, int Hkv, int
     return vt_bytes(B, Hkv, Sk, D) + align256((size_t)B * Hq * nqb * nkt);
 }
 
-extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq,
-                                      int Sk, int D, const int64_t q_strides[3], const int64_t k_strides[3],
-                                      const int64_t v_strides[3], const int64_t o_strides[3], const void* mask,
-                                      int mask_dtype, const int64_t mask_strides[4], int is_causal, float softmax_scale,
-                                      int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+// apexmi_attn_fwd_masked and apexmi_attn_fwd_masked_lse: one argument check, one set of pre-passes, two families of instantiations
+static int fwd_masked(const char* who, bool want_lse, float* lse, const int64_t* lse_strides, const void* q, const void* k,
+                      const void* v, void* out, int B, int Hq, int Hkv, int Sq, int Sk, int D,
+                      const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                      const void* mask, int mask_dtype, const int64_t mask_strides[4], int is_causal, float softmax_scale, int dtype,
+                      void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides,
-                   "attn_fwd_masked: null operand");
-    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "attn_fwd_masked: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)",
+                   "%s: null operand", who);
+    APEXMI_REQUIRE(!want_lse || (lse && lse_strides && ((uintptr_t)lse % 4) == 0), "%s: null or misaligned lse operand", who);
+    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "%s: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)", who,
                    B, Hq, Hkv, Sq, Sk);
-    APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_masked: head dim %d unsupported (64 or 128)", D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_masked: dtype %d unsupported (bf16 or f16)", dtype);
-    APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_masked: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
+    APEXMI_REQUIRE(D == 64 || D == 128, "%s: head dim %d unsupported (64 or 128)", who, D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "%s: dtype %d unsupported (bf16 or f16)", who, dtype);
+    APEXMI_REQUIRE(Hq % Hkv == 0, "%s: head ratio Hq=%d / Hkv=%d is not whole", who, Hq, Hkv);
     APEXMI_REQUIRE(!mask || (mask_strides && (mask_dtype == APEXMI_MASK_BOOL || mask_dtype == APEXMI_F32 ||
                                               mask_dtype == APEXMI_BF16 || mask_dtype == APEXMI_F16)),
-                   "attn_fwd_masked: mask dtype code %d unsupported (bool, f32, bf16, f16)", mask_dtype);
+                   "%s: mask dtype code %d unsupported (bool, f32, bf16, f16)", who, mask_dtype);
     APEXMI_REQUIRE(!mask || mask_strides[3] == 0 || mask_strides[3] == 1,
-                   "attn_fwd_masked: mask key stride %lld must be 0 or 1", (long long)(mask ? mask_strides[3] : 0));
-    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_masked: Sk=%d above %d keys", Sk, MAX_TILES * KV);
-    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_masked: too many query blocks");
+                   "%s: mask key stride %lld must be 0 or 1", who, (long long)(mask ? mask_strides[3] : 0));
+    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "%s: Sk=%d above %d keys", who, Sk, MAX_TILES * KV);
+    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "%s: too many query blocks", who);
     bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
     for (int i = 0; i < 3; ++i)
         aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "attn_fwd_masked: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
+    APEXMI_REQUIRE(aligned, "%s: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)", who);
     const size_t need = apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D);
-    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "attn_fwd_masked: workspace too small (%zu < %zu)", workspace_bytes,
+    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
                    need);
 
     MaskedArgs a{};
@@ -512,6 +610,7 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
     a.causal = is_causal ? 1 : 0;
     a.neg = softmax_scale < 0.0f;
     a.c = fabsf(softmax_scale) * LOG2E;
+    if (want_lse) a.lse = lse, a.l_sb = lse_strides[0], a.l_sh = lse_strides[1], a.l_sq = lse_strides[2];
 
     // V^T [B, Hkv, D, Skp]
     uint16_t* vt = (uint16_t*)workspace;
@@ -525,7 +624,7 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
         a.m_sb = B > 1 ? mask_strides[0] : 0, a.m_sh = Hq > 1 ? mask_strides[1] : 0;
         a.m_sq = Sq > 1 ? mask_strides[2] : 0, a.m_sk = Sk > 1 ? mask_strides[3] : 0;
         const int Bm = a.m_sb ? B : 1, Hm = a.m_sh ? Hq : 1;
-        APEXMI_REQUIRE((int64_t)Bm * Hm <= 65535 && a.nqb <= 65535, "attn_fwd_masked: block map grid too large");
+        APEXMI_REQUIRE((int64_t)Bm * Hm <= 65535 && a.nqb <= 65535, "%s: block map grid too large", who);
         switch (mask_dtype) {
             case APEXMI_MASK_BOOL: launch_map<APEXMI_MASK_BOOL, uint8_t>(a, Bm, Hm, map, stream); break;
             case APEXMI_F32: launch_map<APEXMI_F32, float>(a, Bm, Hm, map, stream); break;
@@ -536,8 +635,63 @@ extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* 
     }
 
     ApexmiProfScope prof(1, stream, 4.0 * B * Hq * (double)Sq * Sk * D, 0.0);
+    if (want_lse) {
+        if (dtype == APEXMI_BF16)
+            return D == 128 ? launch_masked<ElemBf16, 128, false, true>(a, stream) : launch_masked<ElemBf16, 64, false, true>(a, stream);
+        return D == 128 ? launch_masked<ElemF16, 128, false, true>(a, stream) : launch_masked<ElemF16, 64, false, true>(a, stream);
+    }
     if (dtype == APEXMI_BF16) return D == 128 ? launch_masked<ElemBf16, 128>(a, stream) : launch_masked<ElemBf16, 64>(a, stream);
     return D == 128 ? launch_masked<ElemF16, 128>(a, stream) : launch_masked<ElemF16, 64>(a, stream);
+}
+
+extern "C" int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* out, int B, int Hq, int Hkv, int Sq,
+                                      int Sk, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                                      const int64_t v_strides[3], const int64_t o_strides[3], const void* mask,
+                                      int mask_dtype, const int64_t mask_strides[4], int is_causal, float softmax_scale,
+                                      int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    return fwd_masked("attn_fwd_masked", false, nullptr, nullptr, q, k, v, out, B, Hq, Hkv, Sq, Sk, D, q_strides, k_strides, v_strides,
+                      o_strides, mask, mask_dtype, mask_strides, is_causal, softmax_scale, dtype, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int apexmi_attn_fwd_masked_lse(const void* q, const void* k, const void* v, void* out, float* lse, int B, int Hq,
+                                          int Hkv, int Sq, int Sk, int D, const int64_t q_strides[3],
+                                          const int64_t k_strides[3], const int64_t v_strides[3], const int64_t o_strides[3],
+                                          const int64_t lse_strides[3], const void* mask, int mask_dtype,
+                                          const int64_t mask_strides[4], int is_causal, float softmax_scale, int dtype,
+                                          void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    return fwd_masked("attn_fwd_masked_lse", true, lse, lse_strides, q, k, v, out, B, Hq, Hkv, Sq, Sk, D, q_strides, k_strides,
+                      v_strides, o_strides, mask, mask_dtype, mask_strides, is_causal, softmax_scale, dtype, workspace,
+                      workspace_bytes, stream_);
+}
+
+extern "C" int apexmi_attn_merge(int n, const void* const* outs, const float* const* lses, void* out, float* lse_out, int B, int H,
+                                 int Sq, int D, const int64_t o_strides[3], const int64_t lse_strides[3], int dtype,
+                                 apexmi_stream_t stream_) {
+    APEXMI_REQUIRE(n >= 1 && n <= MERGE_MAX, "attn_merge: n=%d partials unsupported (1 to %d)", n, MERGE_MAX);
+    APEXMI_REQUIRE(outs && lses && out && o_strides && lse_strides, "attn_merge: null operand");
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && D > 0, "attn_merge: empty problem (B=%d H=%d Sq=%d D=%d)", B, H, Sq, D);
+    APEXMI_REQUIRE(D % 8 == 0, "attn_merge: head dim %d must be a multiple of 8", D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_merge: dtype %d unsupported (bf16 or f16)", dtype);
+    MergeArgs a{};
+    bool aligned = ((uintptr_t)out % 16) == 0 && ((uintptr_t)lse_out % 4) == 0;
+    for (int p = 0; p < n; ++p) {
+        APEXMI_REQUIRE(outs[p] && lses[p], "attn_merge: null partial %d", p);
+        // the row's D / 8 lanes all read lses[p]; the one that writes lse_out does not wait for the others
+        APEXMI_REQUIRE(lses[p] != lse_out, "attn_merge: lse_out must not be lses[%d]", p);
+        aligned = aligned && ((uintptr_t)outs[p] % 16) == 0 && ((uintptr_t)lses[p] % 4) == 0;
+        a.o[p] = (const uint16_t*)outs[p], a.l[p] = lses[p];
+    }
+    for (int i = 0; i < 3; ++i) aligned = aligned && o_strides[i] % 8 == 0;
+    APEXMI_REQUIRE(aligned, "attn_merge: out rows must be 16-byte aligned (strides multiples of 8 elements), lse 4-byte aligned");
+    a.out = (uint16_t*)out, a.lse_out = lse_out;
+    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    a.l_sb = lse_strides[0], a.l_sh = lse_strides[1], a.l_sq = lse_strides[2];
+    a.H = H, a.Sq = Sq, a.CH = D / 8;
+    a.total = (int64_t)B * Sq * H * a.CH;
+    APEXMI_REQUIRE((a.total + 255) / 256 < (1ll << 31), "attn_merge: too many rows");
+    hipStream_t stream = (hipStream_t)stream_;
+    ApexmiProfScope prof(5, stream, 0.0, (double)a.total * 16.0 * (n + 1));
+    return dtype == APEXMI_BF16 ? launch_merge<ElemBf16>(n, a, stream) : launch_merge<ElemF16>(n, a, stream);
 }
 
 // ---- coordinate window ------------------------------------------------------------------------------------------------------

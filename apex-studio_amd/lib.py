@@ -38,6 +38,9 @@ SIGNATURES = {
     "apexmi_attn_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "apexmi_attn_fwd_masked": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 4 + [vp, C.c_int, c_i64p, C.c_int,
                                                                                         C.c_float, C.c_int, vp, C.c_size_t, vp]),
+    "apexmi_attn_fwd_masked_lse": (C.c_int, [vp, vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 5 + [vp, C.c_int, c_i64p, C.c_int,
+                                                                                                C.c_float, C.c_int, vp, C.c_size_t, vp]),
+    "apexmi_attn_merge": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp] + [C.c_int] * 4 + [c_i64p, c_i64p, C.c_int, vp]),
     "apexmi_attn_window_map_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "apexmi_attn_window_map": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp, C.c_size_t, vp]),
     "apexmi_attn_fwd_window": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 4 + [vp, vp, C.c_int, C.c_int, C.c_int, vp,

@@ -950,12 +950,17 @@ def _mask_operand(attn_mask: Optional[torch.Tensor], B: int, Hq: int, Sq: int, S
 
 def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: Optional[torch.Tensor] = None,
                      is_causal: bool = False, softmax_scale: Optional[float] = None,
-                     enable_gqa: bool = False) -> torch.Tensor:
+                     enable_gqa: bool = False, return_lse: bool = False):
     """F.scaled_dot_product_attention without dropout (the reference's "sdpa", R/src/attention/functions.py:338-377):
     q [B,Hq,Sq,D], k / v [B,Hkv,Sk,D] bf16 or f16 (permuted views welcome), D = 64 or 128; attn_mask bool or additive,
     broadcastable to [B,Hq,Sq,Sk]; is_causal top-left aligned, AND-ed with the mask; grouped-query heads with enable_gqa (or
     Hkv == 1).  A row without any allowed key is zero.  Returns a [B,Hq,Sq,D] view of a [B,Sq,Hq,D] buffer.  Shapes alone
-    size every launch: no host synchronisation."""
+    size every launch: no host synchronisation.
+
+    return_lse=True returns (out, lse): lse [B,Hq,Sq] float32, contiguous, the natural-log row normaliser
+    ln sum_j exp(scale q_i k_j + mask_ij) over the allowed keys (causal rule included; -inf for a row without an allowed key),
+    flash-attn's softmax_lse.  It is what attention_merge needs to combine calls over separate key sets.  `out` is bit-identical
+    to the call without it."""
     _req(q, None, "attention_masked.q")
     _req(k, None, "attention_masked.k")
     _req(v, None, "attention_masked.v")
@@ -993,6 +998,17 @@ def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mas
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)
         _ws_cache[key] = ws
+    if return_lse:
+        lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
+        rc = lib.apexmi_attn_fwd_masked_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), B, Hq, Hkv,
+                                            Sq, Sk, D, _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
+                                            _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
+                                            _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
+                                            _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), _l.i64x3(lse.stride()),
+                                            _ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale),
+                                            _DT[q.dtype], ws.data_ptr(), need, _stream())
+        _l.check(rc, "attn_fwd_masked_lse")
+        return out.permute(0, 2, 1, 3), lse
     rc = lib.apexmi_attn_fwd_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
                                     _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
                                     _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
@@ -1002,6 +1018,82 @@ def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mas
                                     _DT[q.dtype], ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_masked")
     return out.permute(0, 2, 1, 3)
+
+
+MERGE_MAX = 8
+
+
+def attention_merge(outs, lses, out: Optional[torch.Tensor] = None):
+    """Merge 1..8 partial attention results over disjoint key sets into the attention over their union.  outs[p] [B,H,Sq,D] and
+    lses[p] [B,H,Sq] float32 are what attention_masked(..., return_lse=True) returns ([B,H,Sq,D] views of [B,Sq,H,D] buffers; any
+    other layout costs a copy), bf16 or f16, D a multiple of 8.  In f32, with m = max_p lse_p and w_p = exp(lse_p - m) (0 for
+    lse_p = -inf):  out = sum_p w_p out_p / sum_p w_p rounded once,  lse = m + ln sum_p w_p.  A row whose lse_p are all -inf gives
+    out = 0 and lse = -inf.  `out` (optional, the layout of the partials) may be outs[0].  Returns (out, lse); one launch, no
+    host synchronisation."""
+    outs, lses = list(outs), list(lses)
+    n = len(outs)
+    if not 1 <= n <= MERGE_MAX or len(lses) != n:
+        raise _l.ApexMIError(f"attention_merge: {n} partial outs and {len(lses)} lses (1 to {MERGE_MAX} of each, equally many)")
+    o0 = outs[0]
+    if o0.dtype not in (torch.bfloat16, torch.float16):
+        raise _l.ApexMIError(f"attention_merge: dtype {o0.dtype} unsupported (bf16 or f16)")
+    if o0.dim() != 4 or o0.shape[3] % 8 != 0 or o0.numel() == 0:
+        raise _l.ApexMIError(f"attention_merge: outs must be non-empty [B, H, Sq, D] with D a multiple of 8, got {tuple(o0.shape)}")
+    B, H, Sq, D = o0.shape
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        if tuple(o.shape) != (B, H, Sq, D) or o.dtype != o0.dtype or o.device != o0.device:
+            raise _l.ApexMIError(f"attention_merge: outs[{i}] {tuple(o.shape)} {o.dtype} on {o.device} does not match outs[0] "
+                                 f"{tuple(o0.shape)} {o0.dtype} on {o0.device}")
+        if tuple(l.shape) != (B, H, Sq) or l.dtype != torch.float32 or l.device != o0.device:
+            raise _l.ApexMIError(f"attention_merge: lses[{i}] {tuple(l.shape)} {l.dtype} on {l.device} does not match [B, H, Sq] = "
+                                 f"{(B, H, Sq)} float32 on {o0.device}")
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        _req(o, None, f"attention_merge.outs[{i}]")
+        _req(l, None, f"attention_merge.lses[{i}]")
+
+    def bshd(t):   # the return layout of attention_masked: a [B,H,Sq,D] view of a contiguous [B,Sq,H,D] buffer
+        return t if t.permute(0, 2, 1, 3).is_contiguous() else t.permute(0, 2, 1, 3).contiguous().permute(0, 2, 1, 3)
+
+    if out is None:
+        out = torch.empty((B, Sq, H, D), dtype=o0.dtype, device=o0.device).permute(0, 2, 1, 3)
+    else:
+        _req(out, o0.dtype, "attention_merge.out")
+        if tuple(out.shape) != (B, H, Sq, D) or out.device != o0.device or not out.permute(0, 2, 1, 3).is_contiguous():
+            raise _l.ApexMIError(f"attention_merge: out must be a [B, H, Sq, D] = {(B, H, Sq, D)} view of a contiguous "
+                                 f"[B, Sq, H, D] buffer on {o0.device}")
+    outs = [bshd(o) for o in outs]
+    lses = [l.contiguous() for l in lses]
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=o0.device)
+    optr = (_l.vp * n)(*[o.data_ptr() for o in outs])
+    lptr = (_l.vp * n)(*[l.data_ptr() for l in lses])
+    rc = _l.load().apexmi_attn_merge(n, optr, lptr, out.data_ptr(), lse.data_ptr(), B, H, Sq, D,
+                                     _l.i64x3((out.stride(0), out.stride(2), out.stride(1))), _l.i64x3(lse.stride()),
+                                     _DT[o0.dtype], _stream())
+    _l.check(rc, "attn_merge")
+    return out, lse
+
+
+def attention_chunked(q: torch.Tensor, ks, vs, attn_masks=None, softmax_scale: Optional[float] = None,
+                      enable_gqa: bool = False):
+    """Attention of q over the union of 1..8 key/value chunks that live in separate buffers, without concatenating them:
+    ks[p] / vs[p] [B,Hkv,Sk_p,D] (the Sk_p may differ), attn_masks (optional) one mask or None per chunk, each broadcastable
+    to [B,Hq,Sq,Sk_p] as in attention_masked.  One attention_masked(..., return_lse=True) launch per chunk and one
+    attention_merge.  Returns (out, lse) of the whole key set, out as attention_masked returns it.
+
+    is_causal is not offered: the causal rule of a chunk depends on the offset of its keys in the whole sequence, which a chunk
+    does not carry.  A causal caller passes per-chunk masks (the chunk's columns of the causal mask)."""
+    ks, vs = list(ks), list(vs)
+    n = len(ks)
+    if not 1 <= n <= MERGE_MAX or len(vs) != n:
+        raise _l.ApexMIError(f"attention_chunked: {n} key and {len(vs)} value chunks (1 to {MERGE_MAX} of each, equally many)")
+    masks = [None] * n if attn_masks is None else list(attn_masks)
+    if len(masks) != n:
+        raise _l.ApexMIError(f"attention_chunked: {len(masks)} masks for {n} chunks (one per chunk, None for no mask)")
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    parts = [attention_masked(q, k, v, m, softmax_scale=softmax_scale, enable_gqa=enable_gqa, return_lse=True)
+             for k, v, m in zip(ks, vs, masks)]
+    return attention_merge([p[0] for p in parts], [p[1] for p in parts], out=parts[0][0])
 
 
 class WindowPlan:

@@ -148,6 +148,29 @@ int apexmi_attn_fwd_masked(const void* q, const void* k, const void* v, void* ou
                            int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
                            apexmi_stream_t stream);
 
+/* apexmi_attn_fwd_masked that also returns the row normaliser, so that attention over several key sets can be combined:
+ *     lse[b,h,i] = ln sum_j exp(softmax_scale * q_i k_j + mask_ij)   over the allowed keys (the causal rule included),
+ * natural log, f32, written through element strides lse_strides (b, h, q) of a [B,Hq,Sq] array.  A query row without any allowed
+ * key gets lse = -inf (and out = 0).  Every other argument, check and the workspace are those of apexmi_attn_fwd_masked, and
+ * `out` is bit-identical to what it writes.  The value comes from the row maximum and row sum the kernel holds at its end: no
+ * second pass over the keys. */
+int apexmi_attn_fwd_masked_lse(const void* q, const void* k, const void* v, void* out, float* lse, int B, int Hq, int Hkv, int Sq,
+                               int Sk, int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                               const int64_t v_strides[3], const int64_t o_strides[3], const int64_t lse_strides[3],
+                               const void* mask, int mask_dtype, const int64_t mask_strides[4], int is_causal,
+                               float softmax_scale, int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream);
+
+/* Merge n (1..8) partial attention results over disjoint key sets into the attention over their union.  outs[p] are [B,Sq,H,D]
+ * arrays (bf16 or f16 by `dtype`, D a multiple of 8) that share the element strides o_strides (b, s, h), lses[p] f32 [B,H,Sq]
+ * arrays that share lse_strides (b, h, q); the two tables are HOST arrays of device pointers (they travel in the kernel
+ * arguments).  In f32:
+ *     m = max_p lse_p,  w_p = exp(lse_p - m)  (0 for lse_p = -inf),  out = sum_p w_p out_p / sum_p w_p,  lse_out = m + ln sum_p w_p
+ * rounded once to `dtype`.  A row whose lse_p are all -inf gives out = 0 and lse_out = -inf; a partial of weight 0 contributes
+ * nothing whatever it holds.  out (strides o_strides) may be outs[0]; lse_out (strides lse_strides) may be NULL, and must not be
+ * or overlap any lses[p] (the lanes of a row all read them; lse_out = lses[p] is refused).  One pass. */
+int apexmi_attn_merge(int n, const void* const* outs, const float* const* lses, void* out, float* lse_out, int B, int H, int Sq,
+                      int D, const int64_t o_strides[3], const int64_t lse_strides[3], int dtype, apexmi_stream_t stream);
+
 /* Coordinate-window sparse attention: apexmi_attn_fwd_masked with the mask given as a RULE instead of an array.  Every query and
  * key token carries three integer coordinates, stored as one 8-byte record of 4 x int16 {c0, c1, c2, 0} (q_coords [Sq], k_coords
  * [Sk], device memory; the same pointer twice for self-attention).  Key j is allowed for query i iff
