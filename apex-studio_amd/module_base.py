@@ -181,6 +181,43 @@ class HipModule(nn.Module):
         return self
 
 
+MID_ATTENTION_MODES = ("materialised", "flash")
+
+
+class MidAttentionMixin:
+    """The VAEs' choice of kernel for the one-head mid-block attention (C = 384 / 512 / ...): "materialised" (default: the calls
+    made before the setting existed, to the bit) or "flash" (`ops.attention_wide`: one launch, no O(S^2) workspace, the flash
+    kernels' rounding — DESIGN.md §3.4.3).  A per-object setting, not a process-global knob."""
+
+    mid_attention = "materialised"
+
+    def _mid_attention_widths(self) -> tuple:      # channels of every mid block this object runs (encoder, decoder)
+        raise NotImplementedError
+
+    def set_mid_attention(self, mode: str):
+        if mode not in MID_ATTENTION_MODES:
+            raise ValueError(f"mid_attention must be one of {MID_ATTENTION_MODES}, got {mode!r}")
+        if mode == "flash":
+            if self.storage_dtype != torch.bfloat16:
+                raise NotImplementedError("the f32-storage verification mode has no flash mid-block attention; keep "
+                                          "set_mid_attention('materialised') or set_storage_dtype(torch.bfloat16)")
+            widths = tuple(self._mid_attention_widths())
+            if any(w not in (256, 384, 512) for w in widths):
+                raise ValueError(f"mid_attention='flash' covers mid blocks of 256, 384 or 512 channels (ops.attention_wide); this "
+                                 f"model's are {widths} wide and stay on the materialised path: only 'materialised' is accepted")
+        self.mid_attention = mode
+        return self
+
+    def _flash_mid(self, x: torch.Tensor) -> bool:
+        """True when this call goes through ops.attention_wide; the verification mode set after the mode raises here."""
+        if self.mid_attention != "flash":
+            return False
+        if x.dtype != torch.bfloat16:
+            raise NotImplementedError("the f32-storage verification mode has no flash mid-block attention; "
+                                      "set_mid_attention('materialised')")
+        return True
+
+
 # ---- the text / vision encoders --------------------------------------------------------------------------------------
 
 def _cfg_dict(config, kwargs) -> dict:

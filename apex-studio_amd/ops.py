@@ -1271,6 +1271,61 @@ def attention_framecausal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tok
     return out.permute(0, 2, 1, 3)
 
 
+WIDE_HEAD_DIMS = (256, 384, 512)
+
+
+def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_scale: Optional[float] = None,
+                   frame_tokens: int = 0) -> torch.Tensor:
+    """softmax(q k^T scale) v for wide heads in one launch: q [B,H,Sq,D], k / v [B,H,Sk,D] bf16 or f16 views, D = 256, 384 or
+    512, read in place (column slices of one fused buffer welcome; rows that are not 16-byte aligned cost a copy).
+    frame_tokens > 0: key j is allowed for query i iff j // frame_tokens <= i // frame_tokens (Sq == Sk, whole frames).
+    Same return convention as `attention`: a [B,H,Sq,D] view of a [B,Sq,H,D] buffer.  The workspace is V^T only, linear in Sk.
+    It rounds as the flash kernels do (oracle.layers.sdpa's storage policy), not as `attention`'s materialised path for these
+    head sizes does, so the two differ in the last bits."""
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        _req(t, None, f"attention_wide.{name}")
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"attention_wide: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise _l.ApexMIError("attention_wide: q, k, v must be 4-D [B, H, S, D]")
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if D not in WIDE_HEAD_DIMS:
+        raise _l.ApexMIError(f"attention_wide: head dim {D} unsupported {WIDE_HEAD_DIMS}; other head sizes go through `attention`")
+    if tuple(k.shape) != (B, H, Sk, D) or tuple(v.shape) != tuple(k.shape):
+        raise _l.ApexMIError(f"attention_wide: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    if min(B, H, Sq, Sk) == 0:
+        raise _l.ApexMIError("attention_wide: empty problem")
+    frame_tokens = int(frame_tokens)
+    if frame_tokens < 0 or (frame_tokens and (Sq != Sk or Sq % frame_tokens)):
+        raise _l.ApexMIError(f"attention_wide: frame_tokens={frame_tokens} needs Sq == Sk and a whole number of frames "
+                             f"(Sq={Sq}, Sk={Sk})")
+
+    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
+        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
+        return t if ok else t.contiguous()
+
+    q, k, v = rows16(q), rows16(k), rows16(v)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    lib = _l.load()
+    need = lib.apexmi_attn_wide_workspace_bytes(B, H, Sk, D)
+    key = ("wide", q.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        _ws_cache[key] = ws
+    rc = lib.apexmi_attn_fwd_wide(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
+                                  _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
+                                  _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
+                                  _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
+                                  _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                  float(softmax_scale), _DT[q.dtype], frame_tokens, ws.data_ptr(), need, _stream())
+    _l.check(rc, "attn_fwd_wide")
+    return out.permute(0, 2, 1, 3)
+
+
 def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, softmax_scale: float,
                    bias: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
                    causal: bool = False, out: Optional[torch.Tensor] = None, kv_heads: Optional[int] = None,

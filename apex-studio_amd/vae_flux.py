@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import HipModule, _Config, _Conv, _Linear
+from .module_base import HipModule, MidAttentionMixin, _Config, _Conv, _Linear
 
 
 class _GN(nn.Module):
@@ -85,7 +85,7 @@ class _Decoder2D(nn.Module):
         self.conv_out = _Conv(rev[-1], out_channels, (3, 3), **kw)
 
 
-class AutoencoderKL(HipModule):
+class AutoencoderKL(MidAttentionMixin, HipModule):
     _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
 
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 16,
@@ -106,6 +106,9 @@ class AutoencoderKL(HipModule):
 
     def _anchor(self):
         return self.decoder.conv_in.weight
+
+    def _mid_attention_widths(self):
+        return (self.decoder.mid_block.attentions[0].to_q.weight.shape[1],)
 
     def enable_tiling(self, *a, **k):   # 1024^2 latents equal tile_latent_min_size: untiled (model.py:229-236)
         return None
@@ -144,7 +147,8 @@ class AutoencoderKL(HipModule):
         q = ops.gemm(n, a.to_q.weight.data, a.to_q.bias.data)
         k = ops.gemm(n, a.to_k.weight.data, a.to_k.bias.data)
         v = ops.gemm(n, a.to_v.weight.data, a.to_v.bias.data)
-        o = ops.attention(q.view(1, 1, H * W, Cc), k.view(1, 1, H * W, Cc), v.view(1, 1, H * W, Cc))
+        attn = ops.attention_wide if self._flash_mid(x) else ops.attention      # set_mid_attention
+        o = attn(q.view(1, 1, H * W, Cc), k.view(1, 1, H * W, Cc), v.view(1, 1, H * W, Cc))
         o = o.permute(0, 2, 1, 3).reshape(H * W, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)
         out = ops.gemm(o, a.to_out[0].weight.data, a.to_out[0].bias.data, epilogue="gate_res", gate=ones,

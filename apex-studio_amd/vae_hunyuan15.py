@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import HipModule, _Config
+from .module_base import HipModule, MidAttentionMixin, _Config
 
 
 class _CConv(nn.Module):
@@ -180,7 +180,7 @@ def _rearrange_cl(x: torch.Tensor, r1: int, r2: int, r3: int) -> torch.Tensor:
     return x.view(T, H, W, r1, r2, r3, c).permute(0, 3, 1, 4, 2, 5, 6).reshape(T * r1, H * r2, W * r3, c)
 
 
-class AutoencoderKLHunyuanVideo15(HipModule):
+class AutoencoderKLHunyuanVideo15(MidAttentionMixin, HipModule):
     """`set_storage_dtype(float32)` here is the verification mode of the decoder AND the encoder: the convolutions on the exact
     three-way bf16 split, and the frame-causal mid-block attention as one f32 attention call per frame over the keys of the frames
     up to it — the same softmax, without the bf16 probabilities of the materialised production path.  The encoder's moments come
@@ -236,6 +236,9 @@ class AutoencoderKLHunyuanVideo15(HipModule):
 
     def _anchor(self):
         return self.decoder.conv_in.conv.weight
+
+    def _mid_attention_widths(self):
+        return tuple(m.attentions[0].to_q.weight.shape[1] for m in (self.encoder.mid_block, self.decoder.mid_block))
 
     def _ensure_light_vae_loaded(self) -> None:
         """model.py:821-846."""
@@ -324,10 +327,13 @@ class AutoencoderKLHunyuanVideo15(HipModule):
         S = T * H * W
         n = ops.rmsnorm_cl(x, self._g(blk.norm)).view(S, Cc)
         q, k, v = (self._conv1(m, n).view(1, 1, S, Cc) for m in (blk.to_q, blk.to_k, blk.to_v))
+        flash = self._flash_mid(x)       # raises in the verification mode, as the other VAEs do
         if x.dtype == torch.float32:     # verification mode: frame f's queries over the keys of frames <= f, f32 softmax
             hw = H * W
             o = torch.cat([ops.attention(q[:, :, f * hw:(f + 1) * hw], k[:, :, :(f + 1) * hw], v[:, :, :(f + 1) * hw])
                            for f in range(T)], dim=2).permute(0, 2, 1, 3).reshape(S, Cc)
+        elif flash:                          # set_mid_attention("flash"): the frame rule evaluated in the one-launch kernel
+            o = ops.attention_wide(q, k, v, frame_tokens=H * W).permute(0, 2, 1, 3).reshape(S, Cc)
         else:
             o = ops.attention_framecausal(q, k, v, H * W).permute(0, 2, 1, 3).reshape(S, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)

@@ -31,7 +31,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import HipModule, _Config, _Conv
+from .module_base import HipModule, MidAttentionMixin, _Config, _Conv
 
 WAN_LATENTS_MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508, 0.4134, -0.0715,
                     0.5517, -0.3632, -0.1922, -0.9497, 0.2503, -0.2921]
@@ -154,7 +154,7 @@ class DiagonalGaussianDistribution:
         return self.mean + self.std * noise
 
 
-class AutoencoderKLWan(HipModule):
+class AutoencoderKLWan(MidAttentionMixin, HipModule):
     _drops = {"moved": ("_packed",), "loaded": ("_packed",), "written": ("_packed",)}      # the packed conv-weight cache
 
     def __init__(self, base_dim: int = 96, decoder_base_dim: Optional[int] = None, z_dim: int = 16,
@@ -196,6 +196,9 @@ class AutoencoderKLWan(HipModule):
 
     def _anchor(self):
         return self.post_quant_conv.weight
+
+    def _mid_attention_widths(self):
+        return tuple(m.attentions[0].to_qkv.weight.shape[1] for m in (self.encoder.mid_block, self.decoder.mid_block))
 
     def enable_tiling(self, tile_sample_min_height=None, tile_sample_min_width=None,
                       tile_sample_stride_height=None, tile_sample_stride_width=None):
@@ -326,7 +329,8 @@ class AutoencoderKLWan(HipModule):
             n = ops.rmsnorm_cl(x, blk.norm.gamma.data.reshape(-1).contiguous())
         qkv = ops.gemm(n.view(T * H * W, Cc), blk.to_qkv.weight.data.reshape(3 * Cc, Cc), blk.to_qkv.bias.data)
         qkv = qkv.view(T, 1, H * W, 3 * Cc)
-        o = ops.attention(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:])     # [T,1,HW,C] view
+        attn = ops.attention_wide if self._flash_mid(x) else ops.attention      # set_mid_attention; both read the three slices in place
+        o = attn(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:])     # [T,1,HW,C] view
         o = o.permute(0, 2, 1, 3).reshape(T * H * W, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)
         out = ops.gemm(o, blk.proj.weight.data.reshape(Cc, Cc), blk.proj.bias.data, epilogue="gate_res",

@@ -132,6 +132,23 @@ int apexmi_attn_fwd_framecausal(const void* q, const void* k, const void* v, voi
                                 const int64_t v_strides[3], const int64_t o_strides[3], float softmax_scale,
                                 void* workspace, size_t workspace_bytes, apexmi_stream_t stream);
 
+/* Wide heads in ONE launch (attention_wide.hip): out = softmax(q k^T * softmax_scale) v for D = 256, 384 or 512, bf16 or f16,
+ * q [B,H,Sq,D], k / v [B,H,Sk,D] read in place through element strides (b, h, s) that are multiples of 8 (D contiguous, column
+ * slices of one fused buffer welcome), out written as [B,Sq,H,D] with o_strides (b, s, h).  frame_tokens > 0 adds the
+ * frame-causal rule of apexmi_attn_fwd_framecausal (key j allowed for query i iff j / frame_tokens <= i / frame_tokens; needs
+ * Sq == Sk, a whole number of frames).  Rounding: the flash kernels' contract (attn_tile.h) — p is rounded to the storage type
+ * as the P V operand and the row sum runs over the unrounded p — NOT the materialised path's of apexmi_attn_fwd, which rounds
+ * the normalised P; the two differ in the last bits, so nothing routes here on its own.  The workspace is V^T [B,H,D,Skp]
+ * (Skp = Sk rounded up to 64) rounded up to 256 bytes and nothing else: linear in Sk.  D > 512 is an error here; such heads stay
+ * on apexmi_attn_fwd.  The key row stride is at least D (rows do not overlap) and the keys of one (batch, head) span less than
+ * 4 GiB.  Launches: one apexmi_v_transpose per batch (per (batch, head) unless the heads of V follow each other at distance D),
+ * then the one attention launch. */
+size_t apexmi_attn_wide_workspace_bytes(int B, int H, int Sk, int D);
+int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+                         const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                         const int64_t o_strides[3], float softmax_scale, int dtype, int frame_tokens, void* workspace,
+                         size_t workspace_bytes, apexmi_stream_t stream);
+
 /* The whole "sdpa" contract (R/src/attention/functions.py:338-377: F.scaled_dot_product_attention without dropout):
  *     out = softmax(q k^T * softmax_scale + mask) v
  * q [B,Hq,Sq,D], k / v [B,Hkv,Sk,D] with element strides (b, h, s) that are multiples of 8, D contiguous; bf16 or f16
