@@ -1,4 +1,4 @@
-"""The "hip_mfma", "hip_mfma_sdpa" and "hip_mfma_window" attention backends — B-op plug-in point.
+"""The "hip_mfma", "hip_mfma_sdpa", "hip_mfma_window" and "hip_mfma_varlen" attention backends — B-op plug-in point.
 
 Honours the calling convention of every backend in the reference's attention_register
 (apps/api/src/attention/functions.py:84, e.g. `sdpa` :338-377):
@@ -28,6 +28,14 @@ separate key sets.
 calling convention plus `window_plan=` (an ops.WindowPlan from ops.window_plan) in **kwargs.  An opt-in approximation of the
 caller's choosing: keys outside the window are not attended.  attn_mask, is_causal, dropout and a missing plan raise; nothing
 falls back to dense attention.
+
+"hip_mfma_varlen" (KEY_VARLEN) is attention over a packed variable-length batch (ops.attention_varlen), the
+job of the reference's "sdpa_varlen" / "flash_varlen": the reference calling convention plus `cu_seqlens_q=, cu_seqlens_k=`
+(int32 [n + 1] on the operands' device), `max_seqlen_q=, max_seqlen_k=` (host integers) and `enable_gqa=, return_lse=` in
+**kwargs.  The operands are packed [T, H, D], or the registry's [1, H, T, D] views of such a batch; the result comes back in the
+layout it was given ([T, Hq, D], or [1, Hq, T, D]; lse [Hq, T] or [1, Hq, T]).  One launch, no host sync: every sequence attends
+its own keys only.  is_causal is top-left aligned per sequence.  attn_mask, dropout, a batch dimension other than 1 and missing
+cu_seqlens / max_seqlen raise ApexMIError; nothing falls back to a per-sequence loop.
 """
 from __future__ import annotations
 
@@ -39,6 +47,7 @@ from .lib import ApexMIError
 KEY = "hip_mfma"
 KEY_SDPA = "hip_mfma_sdpa"
 KEY_WINDOW = "hip_mfma_window"
+KEY_VARLEN = "hip_mfma_varlen"
 
 
 def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False,
@@ -91,6 +100,34 @@ def hip_mfma_window(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: 
     return ops.attention_window(q, k, v, window_plan, softmax_scale=softmax_scale, enable_gqa=enable_gqa)
 
 
+def hip_mfma_varlen(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None,
+                    cu_seqlens_q=None, cu_seqlens_k=None, max_seqlen_q=None, max_seqlen_k=None, enable_gqa: bool = False,
+                    return_lse: bool = False, **kwargs):
+    if dropout_p:
+        raise ApexMIError("hip_mfma_varlen: dropout is not supported (inference only)")
+    if attn_mask is not None:
+        raise ApexMIError("hip_mfma_varlen: attn_mask is not supported next to cu_seqlens (use hip_mfma_sdpa with a mask)")
+    if cu_seqlens_q is None or cu_seqlens_k is None or max_seqlen_q is None or max_seqlen_k is None:
+        raise ApexMIError("hip_mfma_varlen: cu_seqlens_q=, cu_seqlens_k=, max_seqlen_q= and max_seqlen_k= are required; there is "
+                          "no dense fallback")
+    dims = (q.dim(), k.dim(), v.dim())
+    if dims not in ((3, 3, 3), (4, 4, 4)):
+        raise ApexMIError(f"hip_mfma_varlen: q, k, v must all be packed [T, H, D] or all [1, H, T, D], got {dims} dims")
+    batched = dims[0] == 4
+    if batched:
+        if q.shape[0] != 1 or k.shape[0] != 1 or v.shape[0] != 1:
+            raise ApexMIError(f"hip_mfma_varlen: a packed batch has batch dimension 1, got {q.shape[0]} / {k.shape[0]} / {v.shape[0]} "
+                              "(the sequences are told apart by cu_seqlens)")
+        q, k, v = q[0].permute(1, 0, 2), k[0].permute(1, 0, 2), v[0].permute(1, 0, 2)      # [T, H, D] views
+    res = ops.attention_varlen(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, softmax_scale=softmax_scale,
+                               is_causal=is_causal, enable_gqa=enable_gqa, return_lse=return_lse)
+    if not batched:
+        return res
+    if return_lse:
+        return res[0][None].permute(0, 2, 1, 3), res[1][None]
+    return res[None].permute(0, 2, 1, 3)
+
+
 def _key_keep_mask(attn_mask: torch.Tensor, B: int, Sk: int) -> torch.Tensor:
     """attn_mask (bool keep-mask, or additive: finite-and-not-hugely-negative = keep) -> bool [B, Sk]; raises unless the mask
     is constant along the head and query dimensions."""
@@ -120,13 +157,16 @@ def available() -> bool:
     return torch.cuda.is_available()
 
 
-def register(attention_register, set_default: bool = False, overwrite: bool = True):
+def register(attention_register, set_default: bool = False, overwrite: bool = True, varlen: bool = False):
     """Register under KEY, KEY_SDPA and KEY_WINDOW in the given FunctionRegister (the reference's, or register.attention_register);
-    set_default makes KEY the default."""
+    set_default makes KEY the default.  varlen=True adds KEY_VARLEN next to them: the key takes packed operands and cu_seqlens,
+    so a manifest asks for it."""
     ok = available()
     attention_register(KEY, overwrite=overwrite, available=ok)(hip_mfma)
     attention_register(KEY_SDPA, overwrite=overwrite, available=ok)(hip_mfma_sdpa)
     attention_register(KEY_WINDOW, overwrite=overwrite, available=ok)(hip_mfma_window)
+    if varlen:
+        attention_register(KEY_VARLEN, overwrite=overwrite, available=ok)(hip_mfma_varlen)
     if set_default:
         attention_register.set_default(KEY)
     return attention_register

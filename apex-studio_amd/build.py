@@ -15,7 +15,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_NAME = "libapex_mi355.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
-SOURCES = ["runtime.hip", "gemm.hip", "attention.hip", "attention_masked.hip", "attention_dual.hip", "attention_wide.hip", "elementwise.hip", "dequant_gguf.hip",
+SOURCES = ["runtime.hip", "gemm.hip", "attention.hip", "attention_masked.hip", "attention_varlen.hip", "attention_dual.hip", "attention_wide.hip", "elementwise.hip", "dequant_gguf.hip",
            "conv.hip", "gemm_fp8.hip"]
 ARCH = "gfx950"
 
@@ -39,7 +39,8 @@ if os.environ.get("APEXMI_DEBUG", "0") not in ("", "0"):
 # the build or spills — the second is silent, so every build parses `-Rpass-analysis=kernel-resource-usage` and refuses a binary
 # whose listed kernels use scratch or spill (source file -> substrings of the mangled kernel names).
 NO_SPILL = {"attention.hip": ["attn_fwd_d128_w64_kernel", "attn_fwd_d128_w64r_kernel"],
-            "attention_masked.hip": ["attn_masked_kernel", "attn_window_map_kernel"], "attention_dual.hip": ["attn_dual_kernel"], "attention_wide.hip": ["attn_wide_kernel"],
+            "attention_masked.hip": ["attn_masked_kernel", "attn_window_map_kernel"],
+            "attention_varlen.hip": ["attn_varlen_kernel", "attn_varlen_vt_kernel"], "attention_dual.hip": ["attn_dual_kernel"], "attention_wide.hip": ["attn_wide_kernel"],
             "gemm_fp8.hip": ["gemm_fp8_kernel"]}
 REMARKS = "-Rpass-analysis=kernel-resource-usage"
 

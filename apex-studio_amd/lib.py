@@ -43,6 +43,8 @@ SIGNATURES = {
     "apexmi_attn_fwd_masked_lse": (C.c_int, [vp, vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 5 + [vp, C.c_int, c_i64p, C.c_int,
                                                                                                 C.c_float, C.c_int, vp, C.c_size_t, vp]),
     "apexmi_attn_merge": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(vp), vp, vp] + [C.c_int] * 4 + [c_i64p, c_i64p, C.c_int, vp]),
+    "apexmi_attn_varlen_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "apexmi_attn_fwd_varlen": (C.c_int, [vp] * 7 + [C.c_int] * 8 + [c_i64p] * 5 + [C.c_int, C.c_float, C.c_int, vp, C.c_size_t, vp]),
     "apexmi_attn_window_map_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "apexmi_attn_window_map": (C.c_int, [vp, vp] + [C.c_int] * 5 + [vp, C.c_size_t, vp]),
     "apexmi_attn_fwd_window": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 4 + [vp, vp, C.c_int, C.c_int, C.c_int, vp,
@@ -205,6 +207,10 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().apexmi_last_error().decode("utf-8", "replace")
         raise ApexMIError(f"{what or 'apexmi'} failed (rc={rc}): {msg}")
+
+
+def i64x2(vals):
+    return (C.c_int64 * 2)(*[int(v) for v in vals])
 
 
 def i64x3(vals):

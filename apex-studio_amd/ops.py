@@ -1096,6 +1096,84 @@ def attention_chunked(q: torch.Tensor, ks, vs, attn_masks=None, softmax_scale: O
     return attention_merge([p[0] for p in parts], [p[1] for p in parts], out=parts[0][0])
 
 
+def attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                     max_seqlen_q: int, max_seqlen_k: int, softmax_scale: Optional[float] = None, is_causal: bool = False,
+                     enable_gqa: bool = False, return_lse: bool = False):
+    """Attention over a PACKED variable-length batch in one launch (the reference's "sdpa_varlen" / "flash_varlen",
+    R/src/attention/functions.py:580-745, :932-1089): q [Tq,Hq,D], k / v [Tk,Hkv,D] bf16 or f16 (strided views welcome), D = 64
+    or 128; cu_seqlens_q / cu_seqlens_k int32 [n + 1] on q's device; sequence i owns query rows cu_seqlens_q[i] ..
+    cu_seqlens_q[i+1] - 1 and attends keys cu_seqlens_k[i] .. cu_seqlens_k[i+1] - 1 only.  max_seqlen_q / max_seqlen_k (host
+    integers, at least the longest sequence) size the launch; the cu arrays are read on the device only: no host
+    synchronisation, and a wrong cu array or a too-small max_seqlen truncates the result without reading or writing out of
+    range.  Grouped-query heads with enable_gqa (or Hkv == 1).
+
+    is_causal is top-left aligned per sequence (local key j <= local query i), as attention_masked and the reference's
+    sdpa_varlen (per-sequence F.scaled_dot_product_attention(is_causal=True)); flash-attn >= 2.1 aligns bottom-right instead,
+    which differs whenever a sequence has different query and key lengths.
+
+    Returns out [Tq,Hq,D] (contiguous), or (out, lse) with return_lse=True: lse [Hq,Tq] float32, the natural-log row
+    normaliser (flash-attn's varlen layout).  A sequence with queries and no keys gives zero rows and lse = -inf; rows at or past
+    cu_seqlens_q[n] are not written.  A sequence's rows are bit-identical to attention_masked on that sequence alone, and `out`
+    is bit-identical with and without return_lse.  out[None].permute(0, 2, 1, 3) and lse[None] are what attention_merge accepts
+    (no copy), so varlen partials over separate key sets merge like any others."""
+    # shapes and types first, the device last: every refusal below is reachable without a device
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"attention_varlen: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise _l.ApexMIError("attention_varlen: q, k, v must be 3-D packed [T, H, D]")
+    Tq, Hq, D = q.shape
+    Tk, Hkv, Dk = k.shape
+    if D not in (64, 128):
+        raise _l.ApexMIError(f"attention_varlen: head dim {D} unsupported (64 or 128)")
+    if Dk != D or tuple(v.shape) != tuple(k.shape):
+        raise _l.ApexMIError(f"attention_varlen: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    if min(Tq, Hq, Tk, Hkv) == 0:
+        raise _l.ApexMIError("attention_varlen: empty problem")
+    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
+        raise _l.ApexMIError(f"attention_varlen: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
+                             "whole ratio")
+    if k.device != q.device or v.device != q.device:
+        raise _l.ApexMIError(f"attention_varlen: k / v are on {k.device} / {v.device}, q on {q.device}")
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
+        if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int32 or cu.dim() != 1 or not cu.is_contiguous():
+            raise _l.ApexMIError(f"attention_varlen: {name} must be a contiguous 1-D int32 tensor")
+        if cu.device != q.device:
+            raise _l.ApexMIError(f"attention_varlen: {name} is on {cu.device}, q on {q.device}")
+    if cu_seqlens_q.numel() != cu_seqlens_k.numel() or cu_seqlens_q.numel() < 2:
+        raise _l.ApexMIError(f"attention_varlen: cu_seqlens_q has {cu_seqlens_q.numel()} entries, cu_seqlens_k "
+                             f"{cu_seqlens_k.numel()} (n + 1 of each, n >= 1)")
+    max_seqlen_q, max_seqlen_k = int(max_seqlen_q), int(max_seqlen_k)
+    if max_seqlen_q < 1 or max_seqlen_k < 1:
+        raise _l.ApexMIError(f"attention_varlen: max_seqlen_q={max_seqlen_q} / max_seqlen_k={max_seqlen_k} must be at least 1")
+    n = cu_seqlens_q.numel() - 1
+    _req(q, None, "attention_varlen.q")
+    max_seqlen_q, max_seqlen_k = min(max_seqlen_q, Tq), min(max_seqlen_k, Tk)   # a sequence is never longer than its array
+
+    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
+        ok = t.stride(2) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:2])
+        return t if ok else t.contiguous()
+
+    q, k, v = rows16(q), rows16(k), rows16(v)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    out = torch.empty((Tq, Hq, D), dtype=q.dtype, device=q.device)
+    lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
+    lib = _l.load()
+    need = lib.apexmi_attn_varlen_workspace_bytes(Tk, n, Hkv, D)
+    key = ("varlen", q.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        _ws_cache[key] = ws
+    i64x2 = lambda t: _l.i64x2((t.stride(0), t.stride(1)))   # noqa: E731
+    rc = lib.apexmi_attn_fwd_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
+                                    cu_seqlens_k.data_ptr(), n, Tq, Tk, Hq, Hkv, D, max_seqlen_q, max_seqlen_k, i64x2(q), i64x2(k),
+                                    i64x2(v), i64x2(out), i64x2(lse) if return_lse else None, 1 if is_causal else 0,
+                                    float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
+    _l.check(rc, "attn_fwd_varlen")
+    return (out, lse) if return_lse else out
+
+
 class WindowPlan:
     """A coordinate window, ready to launch (window_plan): the packed coordinates `q_coords` [Sq, 4] / `k_coords` [Sk, 4] int16
     ({c0, c1, c2, 0} per token; one tensor for self-attention), the clamped `radius` and the `block_map` uint8 [ceil(Sq / 128),

@@ -188,6 +188,33 @@ int apexmi_attn_fwd_masked_lse(const void* q, const void* k, const void* v, void
 int apexmi_attn_merge(int n, const void* const* outs, const float* const* lses, void* out, float* lse_out, int B, int H, int Sq,
                       int D, const int64_t o_strides[3], const int64_t lse_strides[3], int dtype, apexmi_stream_t stream);
 
+/* Variable-length attention over a PACKED batch in one launch: the contract of the reference's "sdpa_varlen" and "flash_varlen"
+ * backends (R/src/attention/functions.py:580-745, :932-1089), replacing their per-sequence loop.  n sequences are packed along
+ * the token dimension: q [Tq,Hq,D], k / v [Tk,Hkv,D] with element strides (token, head) that are multiples of 8, D contiguous,
+ * 16-byte aligned rows; bf16 or f16 (`dtype`), D = 64 or 128; Hq a multiple of Hkv (query head h reads key/value head
+ * h / (Hq / Hkv)).  cu_seqlens_q / cu_seqlens_k are int32 DEVICE arrays of n + 1 entries; sequence i owns query rows
+ * cu_seqlens_q[i] .. cu_seqlens_q[i+1] - 1 and keys cu_seqlens_k[i] .. cu_seqlens_k[i+1] - 1:
+ *     out[cu_q[i] + r] = softmax(softmax_scale * q[cu_q[i] + r] K_i^T) V_i
+ * is_causal: local key j <= local query r (top-left aligned per sequence, as apexmi_attn_fwd_masked and the reference's
+ * sdpa_varlen; flash-attn >= 2.1 aligns bottom-right).  out is [Tq,Hq,D] through o_strides (token, head).  lse (NULL = not
+ * wanted) is f32 [Hq,Tq] through lse_strides (head, token): the natural-log row normaliser, flash-attn's varlen layout; `out`
+ * is bit-identical with and without it.  A sequence with queries and no keys stores zero rows and lse = -inf; an empty query
+ * sequence does no work; rows at or past cu_seqlens_q[n] are not written.  A sequence's rows are bit-identical to
+ * apexmi_attn_fwd_masked(_lse) on that sequence alone.
+ * The host never reads the cu arrays (no synchronisation): max_seqlen_q / max_seqlen_k >= 1 size the launches, and the kernels
+ * clamp every sequence into [0, T] (start = clamp(cu[i], 0, T), end = clamp(cu[i+1], start, T)) and its length to max_seqlen, so
+ * a wrong cu_seqlens or a too-small max_seqlen truncates the result but never forms an out-of-range address.
+ * workspace >= apexmi_attn_varlen_workspace_bytes(Tk, n, Hkv, D), 16-byte aligned: V^T [Hkv, D, align64(Tk) + 64 n], one
+ * zero-padded slot per sequence, and nothing else.  Launches: one V^T pass, one attention launch of n * Hq *
+ * ceil(max_seqlen_q / 128) workgroups (below 2^31; n and Hkv at most 65535). */
+size_t apexmi_attn_varlen_workspace_bytes(int Tk, int n, int Hkv, int D);
+int apexmi_attn_fwd_varlen(const void* q, const void* k, const void* v, void* out, float* lse, const int* cu_seqlens_q,
+                           const int* cu_seqlens_k, int n, int Tq, int Tk, int Hq, int Hkv, int D, int max_seqlen_q,
+                           int max_seqlen_k, const int64_t q_strides[2], const int64_t k_strides[2],
+                           const int64_t v_strides[2], const int64_t o_strides[2], const int64_t lse_strides[2],
+                           int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
+                           apexmi_stream_t stream);
+
 /* Coordinate-window sparse attention: apexmi_attn_fwd_masked with the mask given as a RULE instead of an array.  Every query and
  * key token carries three integer coordinates, stored as one 8-byte record of 4 x int16 {c0, c1, c2, 0} (q_coords [Sq], k_coords
  * [Sk], device memory; the same pointer twice for self-attention).  Key j is allowed for query i iff
