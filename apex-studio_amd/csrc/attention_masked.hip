@@ -505,6 +505,74 @@ int launch_merge(int n, const MergeArgs& a, hipStream_t stream) {
     return apexmi_check_launch("attn_merge");
 }
 
+// The same merge over the wide-head kernel's own partials (attention_wide.hip, key_splits > 1): N f32 partials [N, B, Sq, H, D]
+// and lses [N, B, H, Sq] in one workspace, the result rounded once into the caller's strided out.  A partial of weight 0 (an
+// empty key range, whose rows were never written) contributes nothing, whatever it holds.
+struct MergeF32Args {
+    const float* part;
+    const float* lse;
+    uint16_t* out;
+    float* lse_out;          // nullptr: not wanted
+    int64_t o_sb, o_ss, o_sh, l_sb, l_sh, l_sq;
+    int64_t total;           // lanes: B Sq H (D / 8)
+    int64_t p_stride, l_stride;   // elements between two partials: B Sq H D, B H Sq
+    int H, Sq, CH;           // CH = D / 8
+};
+
+template <typename E, int N>
+__global__ __launch_bounds__(256) void attn_merge_f32_kernel(const MergeF32Args a) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= a.total) return;
+    const int c = (int)(t % a.CH);
+    int64_t r = t / a.CH;
+    const int h = (int)(r % a.H);
+    r /= a.H;
+    const int sq = (int)(r % a.Sq);
+    const int64_t b = r / a.Sq;
+    const float* pp = a.part + t * 8;                                   // [B, Sq, H, D / 8] lanes of 8 elements
+    const float* lp = a.lse + (b * a.H + h) * a.Sq + sq;
+    float ls[N];
+    f32x4 raw[N][2];
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+        ls[p] = lp[p * a.l_stride];
+        raw[p][0] = *(const f32x4*)(pp + p * a.p_stride);
+        raw[p][1] = *(const f32x4*)(pp + p * a.p_stride + 4);
+    }
+    float m = ls[0];
+#pragma unroll
+    for (int p = 1; p < N; ++p) m = fmaxf(m, ls[p]);
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    float den = 0.0f;
+#pragma unroll
+    for (int p = 0; p < N; ++p) {
+        const float w = ls[p] == -__builtin_inff() ? 0.0f : expf(ls[p] - m);
+        den += w;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] += w > 0.0f ? w * raw[p][i >> 2][i & 3] : 0.0f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = den > 0.0f ? acc[i] / den : 0.0f;
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = E::pack2(acc[2 * i], acc[2 * i + 1]);
+    *(u32x4*)(a.out + b * a.o_sb + (int64_t)sq * a.o_ss + (int64_t)h * a.o_sh + c * 8) = o;
+    if (c == 0 && a.lse_out)
+        a.lse_out[b * a.l_sb + (int64_t)h * a.l_sh + (int64_t)sq * a.l_sq] = den > 0.0f ? m + logf(den) : -__builtin_inff();
+}
+
+template <typename E>
+int launch_merge_f32(int n, const MergeF32Args& a, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
+    switch (n) {
+#define MERGE_CASE(N) \
+    case N: hipLaunchKernelGGL((attn_merge_f32_kernel<E, N>), grid, block, 0, stream, a); break;
+        MERGE_CASE(2) MERGE_CASE(3) MERGE_CASE(4) MERGE_CASE(5) MERGE_CASE(6) MERGE_CASE(7) MERGE_CASE(8)
+#undef MERGE_CASE
+    }
+    return apexmi_check_launch("attn_merge_f32");
+}
+
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 size_t vt_bytes(int B, int Hkv, int Sk, int D) {
@@ -662,6 +730,27 @@ extern "C" int apexmi_attn_fwd_masked_lse(const void* q, const void* k, const vo
     return fwd_masked("attn_fwd_masked_lse", true, lse, lse_strides, q, k, v, out, B, Hq, Hkv, Sq, Sk, D, q_strides, k_strides,
                       v_strides, o_strides, mask, mask_dtype, mask_strides, is_causal, softmax_scale, dtype, workspace,
                       workspace_bytes, stream_);
+}
+
+int apexmi_attn_merge_f32(int n, const float* parts, const float* lses, void* out, float* lse_out, int B, int H, int Sq, int D,
+                          const int64_t* o_strides, const int64_t* lse_strides, int dtype, hipStream_t stream) {
+    APEXMI_REQUIRE(n >= 2 && n <= MERGE_MAX, "attn_merge_f32: n=%d partials unsupported (2 to %d)", n, MERGE_MAX);
+    APEXMI_REQUIRE(parts && lses && out && o_strides && (!lse_out || lse_strides), "attn_merge_f32: null operand");
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && D > 0 && D % 8 == 0, "attn_merge_f32: bad problem (B=%d H=%d Sq=%d D=%d)", B, H, Sq, D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_merge_f32: dtype %d unsupported (bf16 or f16)", dtype);
+    bool aligned = ((uintptr_t)out % 16) == 0 && ((uintptr_t)parts % 16) == 0 && ((uintptr_t)lses % 4) == 0 && ((uintptr_t)lse_out % 4) == 0;
+    for (int i = 0; i < 3; ++i) aligned = aligned && o_strides[i] % 8 == 0;
+    APEXMI_REQUIRE(aligned, "attn_merge_f32: out rows must be 16-byte aligned (strides multiples of 8 elements), lse 4-byte aligned");
+    MergeF32Args a{};
+    a.part = parts, a.lse = lses, a.out = (uint16_t*)out, a.lse_out = lse_out;
+    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    if (lse_out) a.l_sb = lse_strides[0], a.l_sh = lse_strides[1], a.l_sq = lse_strides[2];
+    a.H = H, a.Sq = Sq, a.CH = D / 8;
+    a.total = (int64_t)B * Sq * H * a.CH;
+    a.p_stride = (int64_t)B * Sq * H * D, a.l_stride = (int64_t)B * H * Sq;
+    APEXMI_REQUIRE((a.total + 255) / 256 < (1ll << 31), "attn_merge_f32: too many rows");
+    ApexmiProfScope prof(5, stream, 0.0, (double)a.total * 8 * (4.0 * n + 2.0));   // apexmi_attn_merge's class
+    return dtype == APEXMI_BF16 ? launch_merge_f32<ElemBf16>(n, a, stream) : launch_merge_f32<ElemF16>(n, a, stream);
 }
 
 extern "C" int apexmi_attn_merge(int n, const void* const* outs, const float* const* lses, void* out, float* lse_out, int B, int H,

@@ -26,8 +26,20 @@
 //     last (longest) first.
 //   * rows past Sq and keys past Sk use clamped indices (qrow_c, min(key, Sk - 1)): no out-of-range address is formed; the clamped
 //     keys' scores are -inf (the key tail takes the per-element form), the clamped rows are not stored.
+//   * MODE (apexmi_attn_fwd_wide_split) is a compile-time variant: the MODE 0 instantiations keep their device code.  MODE 1 and 2
+//     take a grid of units x n (n = 1 .. 8 key splits): workgroup (unit, split) walks tiles [t_beg, t_lim) of the unit's own t_end
+//     tiles, per = ceil(t_end / n), t_beg = min(split per, t_end), t_lim = min(t_beg + per, t_end), and every row stores its lse =
+//     m ln 2 + ln l (-inf for l = 0).  MODE 1 (n == 1) stores `out` as MODE 0 does; MODE 2 (n > 1) stores the NORMALISED O in f32
+//     as partial [split][b][q][h][d] instead (two epilogues in one kernel spill at D = 512), which attn_merge_f32 (attention_masked.hip, a plain second launch) combines: no workgroup
+//     waits on, counts or signals another.  The units of one split are adjacent in launch order (split = id / units): an XCD's
+//     neighbours walk the same key tiles of one (batch, head) and share them in its L2; under the frame rule each split's query
+//     blocks still run longest first.  What "no row is empty" rules out above happens here: a workgroup whose range is empty
+//     (fewer tiles than splits) stores lse = -inf and leaves its partial rows unwritten (weight 0 in the merge), and under the
+//     frame rule a row may find every key of the range excluded beside live rows of its wave: its maximum stays SENTINEL
+//     (wide_raise_max: m_new = SENTINEL, alpha = 2^0), every p is 2^(-inf) = 0, the partial is 0 and the lse -inf.
 #include "attn_tile.h"
 
+#include <algorithm>
 #include <cstdint>
 
 namespace {
@@ -44,6 +56,16 @@ struct WideArgs {
     int H, Sq, Sk, Skp, nqb, total, neg, ft;
     float c;                // |scale| * log2(e)
 };
+
+// the SPLIT variant's own arguments behind the shared ones
+struct WideSplitArgs : WideArgs {
+    float* lse;             // n == 1: the caller's; n > 1: the workspace's [n, B, H, Sq]
+    float* part;            // n > 1: f32 partials [n, B, Sq, H, D]
+    int64_t l_sp, l_sb, l_sh, l_sq;   // lse element strides (split, b, h, q)
+    int B, n;
+};
+
+constexpr float LN2 = 0.6931471805599453f;
 
 // Staging sources of a lane.  Piece i (1 KiB) of wave `wave` is positions (4 i + wave) 64 + lane of an image, 16 bytes each.
 // K image, CH = D / 8 chunks a row: PER = D / 128 pieces of a wave step through 16 rows (4 PER 64 positions = 16 CH), so piece
@@ -151,8 +173,15 @@ APEXMI_DEVICE void wide_raise_max(float mx, float& m_run, float& l_run, f32x16 (
         __builtin_amdgcn_sched_barrier(0);     \
     } while (0)
 
-template <typename E, int D>
-__global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const WideArgs a) {
+template <int MODE>
+struct WideArgsOf { using type = WideSplitArgs; };
+template <>
+struct WideArgsOf<0> { using type = WideArgs; };
+
+// MODE 0: out;  1: out and lse (n == 1);  2: f32 partial and lse (n > 1)
+template <typename E, int D, int MODE = 0>
+__global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const typename WideArgsOf<MODE>::type a) {
+    constexpr bool SPLIT = MODE != 0;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using v8 = typename E::v8;
     constexpr int K_TILE = KV * D * 2;
@@ -164,7 +193,14 @@ __global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const WideArgs a
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // consecutive units of one (batch, head) stay on one XCD; under the frame rule its query blocks run longest first
-    const int s = xcd_remap(blockIdx.x, a.total);
+    int s, split = 0;
+    if constexpr (SPLIT) {   // the units of one split are adjacent
+        s = xcd_remap(blockIdx.x, a.total * a.n);
+        split = s / a.total;
+        s -= split * a.total;
+    } else {
+        s = xcd_remap(blockIdx.x, a.total);
+    }
     const int hb = s / a.nqb;
     const int qb = a.ft ? a.nqb - 1 - s % a.nqb : s % a.nqb;
     const int b = hb / a.H, h = hb % a.H;
@@ -184,6 +220,12 @@ __global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const WideArgs a
         lim = (qrow_c / a.ft + 1) * a.ft - 1;
     }
     const int t_end = (k_end + KV - 1) / KV;   // >= 1
+    int t_beg = 0, t_lim = t_end;              // the workgroup's tiles; SPLIT: its share of the unit's, possibly none
+    if constexpr (SPLIT) {
+        const int per = (t_end + a.n - 1) / a.n;
+        t_beg = min(split * per, t_end);
+        t_lim = min(t_beg + per, t_end);
+    }
 
     // Q fragments (B operand of S^T): lane supplies Q[qrow][16 ks + 8 hi .. +7]; a negative scale flips their signs (exact)
     v8 qf[D / 16];
@@ -237,10 +279,10 @@ __global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const WideArgs a
     float m_run = SENTINEL;  // running maximum, base-2 domain, an integer
     float l_run = 0.0f;
 
-    stage_k(0);
-    for (int t = 0; t < t_end; ++t) {
+    if (!SPLIT || t_beg < t_lim) stage_k(t_beg * KV);
+    for (int t = t_beg; t < t_lim; ++t) {
         const int kv0 = t * KV;
-        const bool more = t + 1 < t_end;
+        const bool more = t + 1 < t_lim;
         asm volatile("" : "+v"(lane_o));
         if constexpr (D != 512) {
 #pragma unroll
@@ -299,6 +341,31 @@ __global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const WideArgs a
     // attn_tile.h's store_row one d-tile at a time: left to itself the compiler reads all of O out of the AGPRs first
     asm volatile("" : "+v"(lane_o));
     const int qrow = q0 + wave * 32 + (lane_o & 31), hi = lane_o >> 5;
+    if constexpr (SPLIT) {
+        // ln sum_j exp(scale q k_j) over the workgroup's keys = m ln 2 + ln l, -inf for a row without one (attn_masked_kernel's
+        // line); the row's low-half lane stores it
+        if (hi == 0 && qrow < a.Sq)
+            a.lse[(int64_t)split * a.l_sp + (int64_t)b * a.l_sb + (int64_t)h * a.l_sh + (int64_t)qrow * a.l_sq] =
+                l_tot > 0.0f ? fmaf(m_run, LN2, logf(l_tot)) : -__builtin_inff();
+        if constexpr (MODE == 2) {   // the normalised partial in f32; an empty range leaves its rows unwritten (weight 0 in the merge)
+            if (qrow < a.Sq && t_beg < t_lim) {
+                float* pp = a.part + ((((int64_t)split * a.B + b) * a.Sq + qrow) * a.H + h) * D;
+#pragma unroll
+                for (int dt = 0; dt < NDT; ++dt) {
+                    // O stays in the AGPRs up to here: the 16-byte stores hold four times the bf16 epilogue's data in flight, and
+                    // at D = 512 the compiler otherwise copies all of O out before the first store and spills
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) asm volatile("" : "+a"(oacc[dt][r]));
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *(f32x4*)(pp + dt * 32 + g * 8 + hi * 4) = f32x4{oacc[dt][4 * g + 0] * inv, oacc[dt][4 * g + 1] * inv,
+                                                                         oacc[dt][4 * g + 2] * inv, oacc[dt][4 * g + 3] * inv};
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            return;
+        }
+    }
     if (qrow < a.Sq) {
         uint16_t* op = a.o + (int64_t)b * a.o_sb + (int64_t)qrow * a.o_ss + (int64_t)h * a.o_sh;
 #pragma unroll
@@ -325,52 +392,76 @@ int launch_wide(const WideArgs& a, hipStream_t stream) {
     return apexmi_check_launch("attn_fwd_wide");
 }
 
-template <typename E>
-int launch_wide_d(int D, const WideArgs& a, hipStream_t stream) {
+template <typename E, int D>
+int launch_wide(const WideSplitArgs& a, hipStream_t stream) {
+    constexpr int LDS = 2 * KV * D * 2;
+    static uint64_t attr_done = 0;
+    if (a.n == 1) {
+        APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_wide_kernel<E, D, 1>,
+                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        hipLaunchKernelGGL((attn_wide_kernel<E, D, 1>), dim3(a.total), dim3(WNW * 64), LDS, stream, a);
+        return apexmi_check_launch("attn_fwd_wide_split (lse)");
+    }
+    static uint64_t attr_done2 = 0;
+    APEXMI_SET_ATTR_ONCE(attr_done2, (void)hipFuncSetAttribute((const void*)attn_wide_kernel<E, D, 2>,
+                                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    hipLaunchKernelGGL((attn_wide_kernel<E, D, 2>), dim3(a.total * a.n), dim3(WNW * 64), LDS, stream, a);
+    return apexmi_check_launch("attn_fwd_wide_split");
+}
+
+template <typename E, typename A>
+int launch_wide_d(int D, const A& a, hipStream_t stream) {
     return D == 256 ? launch_wide<E, 256>(a, stream) : D == 384 ? launch_wide<E, 384>(a, stream) : launch_wide<E, 512>(a, stream);
 }
 
 bool wide_dim(int D) { return D == 256 || D == 384 || D == 512; }
 
-}  // namespace
+constexpr int WIDE_SPLITS_MAX = 8;
 
-// V^T [B, H, D, Skp] (Skp = Sk rounded up to 64), rounded up to 256 bytes: linear in Sk, no term in Sq
-extern "C" size_t apexmi_attn_wide_workspace_bytes(int B, int H, int Sk, int D) {
-    if (B <= 0 || H <= 0 || Sk <= 0 || !wide_dim(D)) return 0;
-    const size_t skp = (size_t)((Sk + KV - 1) / KV) * KV;
-    return ((size_t)B * H * D * skp * 2 + 255) & ~(size_t)255;
-}
-
-extern "C" int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
-                                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
-                                    const int64_t o_strides[3], float softmax_scale, int dtype, int frame_tokens,
-                                    void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attn_fwd_wide: null operand");
-    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attn_fwd_wide: empty problem (B=%d H=%d Sq=%d Sk=%d)", B, H, Sq, Sk);
-    APEXMI_REQUIRE(wide_dim(D), "attn_fwd_wide: head dim %d unsupported (256, 384 or 512; wider heads stay on apexmi_attn_fwd's "
-                   "materialised path)", D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_wide: dtype %d unsupported (bf16 or f16)", dtype);
-    APEXMI_REQUIRE(frame_tokens >= 0, "attn_fwd_wide: negative frame_tokens %d", frame_tokens);
+// apexmi_attn_fwd_wide and apexmi_attn_fwd_wide_split: one argument check, one V^T pre-pass, two families of instantiations.
+// key_splits and lse belong to the second entry point only (the first passes 1 and nullptr and launches what it always did).
+int fwd_wide(const char* who, const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+             float softmax_scale, int dtype, int frame_tokens, float* lse, const int64_t* lse_strides, int key_splits,
+             void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "%s: null operand", who);
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "%s: empty problem (B=%d H=%d Sq=%d Sk=%d)", who, B, H, Sq, Sk);
+    APEXMI_REQUIRE(wide_dim(D), "%s: head dim %d unsupported (256, 384 or 512; wider heads stay on apexmi_attn_fwd's "
+                   "materialised path)", who, D);
+    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "%s: dtype %d unsupported (bf16 or f16)", who, dtype);
+    APEXMI_REQUIRE(frame_tokens >= 0, "%s: negative frame_tokens %d", who, frame_tokens);
     APEXMI_REQUIRE(frame_tokens == 0 || (Sq == Sk && Sq % frame_tokens == 0),
-                   "attn_fwd_wide: the frame rule needs Sq == Sk and a whole number of frames of %d tokens (Sq=%d Sk=%d)",
+                   "%s: the frame rule needs Sq == Sk and a whole number of frames of %d tokens (Sq=%d Sk=%d)", who,
                    frame_tokens, Sq, Sk);
-    APEXMI_REQUIRE((int64_t)B * H * ((Sq + WQB - 1) / WQB) < (1ll << 31), "attn_fwd_wide: too many query blocks");
+    const int64_t units = (int64_t)B * H * ((Sq + WQB - 1) / WQB);
+    APEXMI_REQUIRE(units < (1ll << 31), "%s: too many query blocks", who);
     // the kernel addresses a (batch, head)'s K rows and V^T image with 32-bit byte offsets
-    APEXMI_REQUIRE(k_strides[2] >= D, "attn_fwd_wide: key row stride %lld below the head dim %d (rows must not overlap)",
+    APEXMI_REQUIRE(k_strides[2] >= D, "%s: key row stride %lld below the head dim %d (rows must not overlap)", who,
                    (long long)k_strides[2], D);
     APEXMI_REQUIRE((int64_t)Sk * k_strides[2] < (1ll << 31) && (int64_t)D * (Sk + KV) < (1ll << 31),
-                   "attn_fwd_wide: the keys of one (batch, head) span 4 GiB or more (Sk=%d, row stride %lld)", Sk,
+                   "%s: the keys of one (batch, head) span 4 GiB or more (Sk=%d, row stride %lld)", who, Sk,
                    (long long)k_strides[2]);
     bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
     for (int i = 0; i < 3; ++i)
         aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "attn_fwd_wide: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
-    const size_t need = apexmi_attn_wide_workspace_bytes(B, H, Sk, D);
+    APEXMI_REQUIRE(aligned, "%s: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)", who);
+    APEXMI_REQUIRE(key_splits >= 0 && key_splits <= WIDE_SPLITS_MAX, "%s: key_splits=%d unsupported (0 = auto, 1 to %d)", who,
+                   key_splits, WIDE_SPLITS_MAX);
+    APEXMI_REQUIRE(!lse || (lse_strides && ((uintptr_t)lse % 4) == 0), "%s: lse without strides, or misaligned", who);
+    int n = key_splits;
+    if (n == 0) {   // shape-only: the CU count of the current device and the pure rule
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            cus = 0;
+        APEXMI_REQUIRE(cus > 0, "%s: key_splits = auto needs the device's compute-unit count, which the runtime did not give", who);
+        n = apexmi_attn_wide_auto_splits((int)units, (Sk + KV - 1) / KV, cus);
+    }
+    APEXMI_REQUIRE(units * n < (1ll << 31), "%s: too many workgroups (%lld query blocks x %d key splits)", who, (long long)units, n);
+    const size_t need = apexmi_attn_wide_split_workspace_bytes(B, H, Sq, Sk, D, n);
     APEXMI_REQUIRE(workspace && ((uintptr_t)workspace % 16) == 0 && workspace_bytes >= need,
-                   "attn_fwd_wide: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
+                   "%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, need);
 
-    WideArgs a{};
+    WideSplitArgs a{};
     a.q = (const uint16_t*)q;
     a.k = (const uint16_t*)k;
     a.o = (uint16_t*)out;
@@ -382,6 +473,7 @@ extern "C" int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v,
     a.neg = softmax_scale < 0.0f;
     a.c = fabsf(softmax_scale) * LOG2E;
     a.ft = frame_tokens;
+    a.B = B, a.n = n;
 
     // V^T [B, H, D, Skp]: the 128-wide transpose over the D / 128 column slices of a head (a pure 16-bit move: f16 too); heads
     // that follow each other at distance D in memory are slices of one launch
@@ -392,12 +484,72 @@ extern "C" int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v,
         for (int h = 0; h < (heads_adjacent ? 1 : H); ++h)
             if (int rc = apexmi_v_transpose((const uint16_t*)v + b * v_strides[0] + h * v_strides[1], 128, v_strides[2], Sk,
                                             (heads_adjacent ? H : 1) * (D / 128), 128,
-                                            vt + ((size_t)b * H + h) * D * a.Skp, a.Skp, 0, stream_))
+                                            vt + ((size_t)b * H + h) * D * a.Skp, a.Skp, 0, (apexmi_stream_t)stream))
                 return rc;
 
     // under the frame rule frame f's queries see f + 1 frames of keys: half the square plus half the diagonal
     const double nf = frame_tokens ? (double)(Sq / frame_tokens) : 0.0;
     const double pairs = frame_tokens ? (double)frame_tokens * frame_tokens * nf * (nf + 1.0) * 0.5 : (double)Sq * Sk;
-    ApexmiProfScope prof(1, stream, 4.0 * B * H * pairs * D, 0.0);
-    return dtype == APEXMI_BF16 ? launch_wide_d<ElemBf16>(D, a, stream) : launch_wide_d<ElemF16>(D, a, stream);
+    const int64_t part_elems = (int64_t)n * B * Sq * H * D;
+    {
+        ApexmiProfScope prof(1, stream, 4.0 * B * H * pairs * D, 0.0);   // the attention launch: the useful flops, whatever n
+        if (n == 1 && !lse) {   // the launch this entry point has always made
+            const WideArgs& plain = a;
+            return dtype == APEXMI_BF16 ? launch_wide_d<ElemBf16>(D, plain, stream) : launch_wide_d<ElemF16>(D, plain, stream);
+        }
+        if (n == 1) {
+            a.lse = lse, a.l_sp = 0, a.l_sb = lse_strides[0], a.l_sh = lse_strides[1], a.l_sq = lse_strides[2];
+            return dtype == APEXMI_BF16 ? launch_wide_d<ElemBf16>(D, a, stream) : launch_wide_d<ElemF16>(D, a, stream);
+        }
+        // n > 1: f32 partials [n, B, Sq, H, D] and their lses [n, B, H, Sq] behind V^T, then the merge launch
+        a.part = (float*)((char*)workspace + apexmi_attn_wide_workspace_bytes(B, H, Sk, D));
+        a.lse = a.part + part_elems;
+        a.l_sp = (int64_t)B * H * Sq, a.l_sb = (int64_t)H * Sq, a.l_sh = Sq, a.l_sq = 1;
+        if (int rc = dtype == APEXMI_BF16 ? launch_wide_d<ElemBf16>(D, a, stream) : launch_wide_d<ElemF16>(D, a, stream)) return rc;
+    }
+    return apexmi_attn_merge_f32(n, a.part, a.lse, out, lse, B, H, Sq, D, o_strides, lse_strides, dtype, stream);
+}
+
+}  // namespace
+
+// V^T [B, H, D, Skp] (Skp = Sk rounded up to 64), rounded up to 256 bytes: linear in Sk, no term in Sq
+extern "C" size_t apexmi_attn_wide_workspace_bytes(int B, int H, int Sk, int D) {
+    if (B <= 0 || H <= 0 || Sk <= 0 || !wide_dim(D)) return 0;
+    const size_t skp = (size_t)((Sk + KV - 1) / KV) * KV;
+    return ((size_t)B * H * D * skp * 2 + 255) & ~(size_t)255;
+}
+
+// V^T as above; key_splits > 1 adds the f32 partials [n, B, Sq, H, D] and their lses [n, B, H, Sq], no padding between them
+extern "C" size_t apexmi_attn_wide_split_workspace_bytes(int B, int H, int Sq, int Sk, int D, int key_splits) {
+    const size_t vt = apexmi_attn_wide_workspace_bytes(B, H, Sk, D);
+    if (vt == 0 || Sq <= 0 || key_splits < 1 || key_splits > WIDE_SPLITS_MAX) return 0;
+    if (key_splits == 1) return vt;
+    return vt + (size_t)key_splits * B * Sq * H * ((size_t)D + 1) * 4;
+}
+
+// The split count of key_splits = 0.  One workgroup is one CU's whole register file, so `units` workgroups fill units / cus of the
+// device: no split once the launch is more than half full (2 units > cus); otherwise as many splits as fill it (cus / units), at
+// least 4 key tiles (256 keys) a split, at most 8 (the merge's limit).  Pure: no device, the same answer for the same numbers.
+extern "C" int apexmi_attn_wide_auto_splits(int units, int key_tiles, int cus) {
+    if (units <= 0 || key_tiles <= 0 || cus <= 0 || 2 * (int64_t)units > cus) return 1;
+    const int n = std::min(std::min(WIDE_SPLITS_MAX, cus / units), key_tiles / 4);
+    return std::max(n, 1);
+}
+
+extern "C" int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+                                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                                    const int64_t o_strides[3], float softmax_scale, int dtype, int frame_tokens,
+                                    void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    return fwd_wide("attn_fwd_wide", q, k, v, out, B, H, Sq, Sk, D, q_strides, k_strides, v_strides, o_strides, softmax_scale,
+                    dtype, frame_tokens, nullptr, nullptr, 1, workspace, workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int apexmi_attn_fwd_wide_split(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk,
+                                          int D, const int64_t q_strides[3], const int64_t k_strides[3],
+                                          const int64_t v_strides[3], const int64_t o_strides[3], float softmax_scale, int dtype,
+                                          int frame_tokens, float* lse, const int64_t lse_strides[3], int key_splits,
+                                          void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    return fwd_wide("attn_fwd_wide_split", q, k, v, out, B, H, Sq, Sk, D, q_strides, k_strides, v_strides, o_strides,
+                    softmax_scale, dtype, frame_tokens, lse, lse_strides, key_splits, workspace, workspace_bytes,
+                    (hipStream_t)stream_);
 }

@@ -231,6 +231,13 @@ static inline void apexmi_attr_done(uint64_t& mask) {
     } while (0)
 void apexmi_set_error(const char* fmt, ...);
 int apexmi_check_launch(const char* what);
+// merge of the wide-head kernel's f32 partials [n, B, Sq, H, D] and lses [n, B, H, Sq] (attention_masked.hip, beside attn_merge_kernel;
+// called by attention_wide.hip, not a public entry): apexmi_attn_merge's arithmetic, one rounding at the store into the caller's
+// strided `out` (b, s, h), lse_out (strides b, h, q) may be nullptr
+__attribute__((visibility("hidden"))) int apexmi_attn_merge_f32(int n, const float* parts, const float* lses, void* out,
+                                                                 float* lse_out, int B, int H, int Sq, int D,
+                                                                 const int64_t* o_strides, const int64_t* lse_strides, int dtype,
+                                                                 hipStream_t stream);
 // device pointer of the live clock probe's two counters on the current device, or nullptr while the probe is off (runtime.hip)
 unsigned long long* apexmi_clk_ptr();
 

@@ -37,6 +37,10 @@ SIGNATURES = {
                                               c_i64p, c_i64p, c_i64p, c_i64p, C.c_float, vp, C.c_size_t, vp]),
     "apexmi_attn_wide_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
     "apexmi_attn_fwd_wide": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [c_i64p] * 4 + [C.c_float, C.c_int, C.c_int, vp, C.c_size_t, vp]),
+    "apexmi_attn_wide_auto_splits": (C.c_int, [C.c_int] * 3),
+    "apexmi_attn_wide_split_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "apexmi_attn_fwd_wide_split": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [c_i64p] * 4 + [C.c_float, C.c_int, C.c_int, vp, c_i64p,
+                                                                                            C.c_int, vp, C.c_size_t, vp]),
     "apexmi_attn_masked_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "apexmi_attn_fwd_masked": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 6 + [c_i64p] * 4 + [vp, C.c_int, c_i64p, C.c_int,
                                                                                         C.c_float, C.c_int, vp, C.c_size_t, vp]),

@@ -187,16 +187,23 @@ MID_ATTENTION_MODES = ("materialised", "flash")
 class MidAttentionMixin:
     """The VAEs' choice of kernel for the one-head mid-block attention (C = 384 / 512 / ...): "materialised" (default: the calls
     made before the setting existed, to the bit) or "flash" (`ops.attention_wide`: one launch, no O(S^2) workspace, the flash
-    kernels' rounding — DESIGN.md §3.4.3).  A per-object setting, not a process-global knob."""
+    kernels' rounding — DESIGN.md §3.4.3).  A per-object setting, not a process-global knob.  key_splits (with "flash" only: an
+    int 1 .. 8 or "auto") is ops.attention_wide's: a launch split over keys for mid blocks too short to fill the device."""
 
     mid_attention = "materialised"
+    mid_attention_key_splits = 1
 
     def _mid_attention_widths(self) -> tuple:      # channels of every mid block this object runs (encoder, decoder)
         raise NotImplementedError
 
-    def set_mid_attention(self, mode: str):
+    def set_mid_attention(self, mode: str, key_splits=1):
         if mode not in MID_ATTENTION_MODES:
             raise ValueError(f"mid_attention must be one of {MID_ATTENTION_MODES}, got {mode!r}")
+        if key_splits != "auto" and (isinstance(key_splits, (bool, str)) or not isinstance(key_splits, int) or not 1 <= key_splits <= 8):
+            raise ValueError(f"key_splits must be an int 1 to 8 or \"auto\", got {key_splits!r}")
+        if mode != "flash" and key_splits != 1:
+            raise ValueError(f"key_splits={key_splits!r} belongs to mid_attention='flash' (ops.attention_wide); the "
+                             f"'{mode}' path has no key splits")
         if mode == "flash":
             if self.storage_dtype != torch.bfloat16:
                 raise NotImplementedError("the f32-storage verification mode has no flash mid-block attention; keep "
@@ -206,6 +213,7 @@ class MidAttentionMixin:
                 raise ValueError(f"mid_attention='flash' covers mid blocks of 256, 384 or 512 channels (ops.attention_wide); this "
                                  f"model's are {widths} wide and stay on the materialised path: only 'materialised' is accepted")
         self.mid_attention = mode
+        self.mid_attention_key_splits = key_splits
         return self
 
     def _flash_mid(self, x: torch.Tensor) -> bool:

@@ -1078,7 +1078,9 @@ def attention_chunked(q: torch.Tensor, ks, vs, attn_masks=None, softmax_scale: O
     """Attention of q over the union of 1..8 key/value chunks that live in separate buffers, without concatenating them:
     ks[p] / vs[p] [B,Hkv,Sk_p,D] (the Sk_p may differ), attn_masks (optional) one mask or None per chunk, each broadcastable
     to [B,Hq,Sq,Sk_p] as in attention_masked.  One attention_masked(..., return_lse=True) launch per chunk and one
-    attention_merge.  Returns (out, lse) of the whole key set, out as attention_masked returns it.
+    attention_merge.  Returns (out, lse) of the whole key set, out as attention_masked returns it.  Wide heads (D = 256, 384 or
+    512) go through attention_wide(..., return_lse=True) per chunk instead; that kernel has neither masks nor grouped-query
+    heads, so both are refused there.
 
     is_causal is not offered: the causal rule of a chunk depends on the offset of its keys in the whole sequence, which a chunk
     does not carry.  A causal caller passes per-chunk masks (the chunk's columns of the causal mask)."""
@@ -1091,6 +1093,14 @@ def attention_chunked(q: torch.Tensor, ks, vs, attn_masks=None, softmax_scale: O
         raise _l.ApexMIError(f"attention_chunked: {len(masks)} masks for {n} chunks (one per chunk, None for no mask)")
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(q.shape[-1])
+    if q.dim() == 4 and q.shape[-1] in WIDE_HEAD_DIMS:
+        if any(m is not None for m in masks):
+            raise _l.ApexMIError(f"attention_chunked: head dim {q.shape[-1]} runs on the wide-head kernel, which takes no masks")
+        if enable_gqa or any(kk.dim() != 4 or kk.shape[1] != q.shape[1] for kk in ks):
+            raise _l.ApexMIError(f"attention_chunked: head dim {q.shape[-1]} runs on the wide-head kernel, which has no "
+                                 "grouped-query heads (every chunk needs q's head count, enable_gqa=False)")
+        parts = [attention_wide(q, k, v, softmax_scale=softmax_scale, return_lse=True) for k, v in zip(ks, vs)]
+        return attention_merge([p[0] for p in parts], [p[1] for p in parts], out=parts[0][0])
     parts = [attention_masked(q, k, v, m, softmax_scale=softmax_scale, enable_gqa=enable_gqa, return_lse=True)
              for k, v, m in zip(ks, vs, masks)]
     return attention_merge([p[0] for p in parts], [p[1] for p in parts], out=parts[0][0])
@@ -1352,14 +1362,36 @@ def attention_framecausal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tok
 WIDE_HEAD_DIMS = (256, 384, 512)
 
 
+WIDE_SPLITS_MAX = 8
+
+
+def _wide_key_splits(key_splits, who: str):
+    """1 .. 8 or "auto" (returned as 0, the C ABI's code), anything else refused"""
+    if isinstance(key_splits, str):
+        if key_splits != "auto":
+            raise _l.ApexMIError(f"{who}: key_splits={key_splits!r} unsupported (an int 1 to {WIDE_SPLITS_MAX}, or \"auto\")")
+        return 0
+    if isinstance(key_splits, bool) or not isinstance(key_splits, int) or not 1 <= key_splits <= WIDE_SPLITS_MAX:
+        raise _l.ApexMIError(f"{who}: key_splits={key_splits!r} unsupported (an int 1 to {WIDE_SPLITS_MAX}, or \"auto\")")
+    return key_splits
+
+
 def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_scale: Optional[float] = None,
-                   frame_tokens: int = 0) -> torch.Tensor:
+                   frame_tokens: int = 0, key_splits=1, return_lse: bool = False):
     """softmax(q k^T scale) v for wide heads in one launch: q [B,H,Sq,D], k / v [B,H,Sk,D] bf16 or f16 views, D = 256, 384 or
     512, read in place (column slices of one fused buffer welcome; rows that are not 16-byte aligned cost a copy).
     frame_tokens > 0: key j is allowed for query i iff j // frame_tokens <= i // frame_tokens (Sq == Sk, whole frames).
     Same return convention as `attention`: a [B,H,Sq,D] view of a [B,Sq,H,D] buffer.  The workspace is V^T only, linear in Sk.
     It rounds as the flash kernels do (oracle.layers.sdpa's storage policy), not as `attention`'s materialised path for these
-    head sizes does, so the two differ in the last bits."""
+    head sizes does, so the two differ in the last bits.
+
+    key_splits (an int 1 .. 8, or "auto"): n > 1 launches n workgroups per 128-row query block, each over a share of the key
+    tiles, and merges their f32 partial results in a second launch (a short sequence fills more compute units; the workspace
+    grows by the partials, n B Sq H (D + 1) 4 bytes).  "auto" picks n from the shape and the device's compute-unit count
+    (apexmi_attn_wide_auto_splits), without a host synchronisation.  return_lse=True returns (out, lse): lse [B,H,Sq] float32,
+    contiguous, the natural-log row normaliser, -inf for a row without an allowed key: attention_masked's convention, what
+    attention_merge takes.  With key_splits=1 `out` is bit-identical with and without the lse, and the defaults make the call
+    this function always made."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         _req(t, None, f"attention_wide.{name}")
     if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
@@ -1378,6 +1410,7 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_sc
     if frame_tokens < 0 or (frame_tokens and (Sq != Sk or Sq % frame_tokens)):
         raise _l.ApexMIError(f"attention_wide: frame_tokens={frame_tokens} needs Sq == Sk and a whole number of frames "
                              f"(Sq={Sq}, Sk={Sk})")
+    n = _wide_key_splits(key_splits, "attention_wide")
 
     def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
         ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
@@ -1388,12 +1421,27 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_sc
         softmax_scale = 1.0 / math.sqrt(D)
     out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
     lib = _l.load()
-    need = lib.apexmi_attn_wide_workspace_bytes(B, H, Sk, D)
+    # the workspace of the split count that runs: "auto" is the library's rule on this device's compute-unit count, here as there
+    n_ws = n or lib.apexmi_attn_wide_auto_splits(B * H * ((Sq + 127) // 128), (Sk + 63) // 64,
+                                                 torch.cuda.get_device_properties(q.device).multi_processor_count)
+    need = lib.apexmi_attn_wide_split_workspace_bytes(B, H, Sq, Sk, D, n_ws)
     key = ("wide", q.device.index, torch.cuda.current_stream().cuda_stream)
     ws = _ws_cache.get(key)
     if ws is None or ws.numel() < need:
         ws = torch.empty(need, dtype=torch.uint8, device=q.device)
         _ws_cache[key] = ws
+    if n != 1 or return_lse:
+        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if return_lse else None
+        with torch.cuda.device(q.device):      # "auto" reads the current device's compute-unit count
+            rc = lib.apexmi_attn_fwd_wide_split(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
+                                                _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
+                                                _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
+                                                _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
+                                                _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                                float(softmax_scale), _DT[q.dtype], frame_tokens, _ptr(lse),
+                                                _l.i64x3(lse.stride()) if return_lse else None, n, ws.data_ptr(), need, _stream())
+        _l.check(rc, "attn_fwd_wide_split")
+        return (out.permute(0, 2, 1, 3), lse) if return_lse else out.permute(0, 2, 1, 3)
     rc = lib.apexmi_attn_fwd_wide(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
                                   _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
                                   _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),

@@ -147,8 +147,9 @@ class AutoencoderKL(MidAttentionMixin, HipModule):
         q = ops.gemm(n, a.to_q.weight.data, a.to_q.bias.data)
         k = ops.gemm(n, a.to_k.weight.data, a.to_k.bias.data)
         v = ops.gemm(n, a.to_v.weight.data, a.to_v.bias.data)
-        attn = ops.attention_wide if self._flash_mid(x) else ops.attention      # set_mid_attention
-        o = attn(q.view(1, 1, H * W, Cc), k.view(1, 1, H * W, Cc), v.view(1, 1, H * W, Cc))
+        kw = dict(key_splits=self.mid_attention_key_splits) if self._flash_mid(x) else {}      # set_mid_attention
+        attn = ops.attention_wide if kw else ops.attention
+        o = attn(q.view(1, 1, H * W, Cc), k.view(1, 1, H * W, Cc), v.view(1, 1, H * W, Cc), **kw)
         o = o.permute(0, 2, 1, 3).reshape(H * W, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)
         out = ops.gemm(o, a.to_out[0].weight.data, a.to_out[0].bias.data, epilogue="gate_res", gate=ones,

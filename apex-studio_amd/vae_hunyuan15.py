@@ -333,7 +333,8 @@ class AutoencoderKLHunyuanVideo15(MidAttentionMixin, HipModule):
             o = torch.cat([ops.attention(q[:, :, f * hw:(f + 1) * hw], k[:, :, :(f + 1) * hw], v[:, :, :(f + 1) * hw])
                            for f in range(T)], dim=2).permute(0, 2, 1, 3).reshape(S, Cc)
         elif flash:                          # set_mid_attention("flash"): the frame rule evaluated in the one-launch kernel
-            o = ops.attention_wide(q, k, v, frame_tokens=H * W).permute(0, 2, 1, 3).reshape(S, Cc)
+            o = ops.attention_wide(q, k, v, frame_tokens=H * W, key_splits=self.mid_attention_key_splits)
+            o = o.permute(0, 2, 1, 3).reshape(S, Cc)
         else:
             o = ops.attention_framecausal(q, k, v, H * W).permute(0, 2, 1, 3).reshape(S, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)

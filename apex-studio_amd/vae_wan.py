@@ -329,8 +329,10 @@ class AutoencoderKLWan(MidAttentionMixin, HipModule):
             n = ops.rmsnorm_cl(x, blk.norm.gamma.data.reshape(-1).contiguous())
         qkv = ops.gemm(n.view(T * H * W, Cc), blk.to_qkv.weight.data.reshape(3 * Cc, Cc), blk.to_qkv.bias.data)
         qkv = qkv.view(T, 1, H * W, 3 * Cc)
-        attn = ops.attention_wide if self._flash_mid(x) else ops.attention      # set_mid_attention; both read the three slices in place
-        o = attn(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:])     # [T,1,HW,C] view
+        # set_mid_attention; both read the three slices in place
+        kw = dict(key_splits=self.mid_attention_key_splits) if self._flash_mid(x) else {}
+        attn = ops.attention_wide if kw else ops.attention
+        o = attn(qkv[..., :Cc], qkv[..., Cc:2 * Cc], qkv[..., 2 * Cc:], **kw)     # [T,1,HW,C] view
         o = o.permute(0, 2, 1, 3).reshape(T * H * W, Cc)
         ones = torch.ones(Cc, dtype=torch.float32, device=x.device)
         out = ops.gemm(o, blk.proj.weight.data.reshape(Cc, Cc), blk.proj.bias.data, epilogue="gate_res",

@@ -149,6 +149,29 @@ int apexmi_attn_fwd_wide(const void* q, const void* k, const void* v, void* out,
                          const int64_t o_strides[3], float softmax_scale, int dtype, int frame_tokens, void* workspace,
                          size_t workspace_bytes, apexmi_stream_t stream);
 
+/* The same attention with the two things the other flash kernels have: the row normaliser and a launch split over keys.
+ * lse (nullable; f32, element strides lse_strides (b, h, q), 4-byte aligned) receives ln sum_j exp(softmax_scale q k_j) over the
+ * allowed keys, -inf for a row without one: what apexmi_attn_fwd_masked_lse returns and apexmi_attn_merge takes.  key_splits
+ * n = 1 .. 8 launches units x n workgroups (units = B H ceil(Sq / 128)): split s of a unit walks tiles [min(s per, t),
+ * min(s per + per, t)) of the unit's t 64-key tiles, per = ceil(t / n), and stores its normalised result in f32; a second, plain
+ * launch merges the n partials as apexmi_attn_merge does (one rounding at the store) into out / lse.  No workgroup waits on
+ * another.  key_splits = 0 takes apexmi_attn_wide_auto_splits(units, ceil(Sk / 64), compute units of the current device):
+ * shape-only, no host synchronisation.  With key_splits = 1 out is bit-identical to apexmi_attn_fwd_wide's, with or without lse
+ * (lse = NULL makes that very launch).  The workspace is apexmi_attn_wide_split_workspace_bytes of the split count that runs:
+ * V^T as above, and for n > 1 the f32 partials [n,B,Sq,H,D] and their lses [n,B,H,Sq] right behind it with no padding
+ * (n B Sq H D 4 + n B H Sq 4 bytes); 0 for unsupported arguments (D, n outside 1 .. 8, empty shapes).  Every refusal of
+ * apexmi_attn_fwd_wide applies, and key_splits outside 0 .. 8, an lse without strides or misaligned, units x n >= 2^31 and a
+ * workspace that is too small are errors.
+ * apexmi_attn_wide_auto_splits is a pure host function: 1 when the launch is more than half full (2 units > cus), otherwise
+ * min(8, cus / units, key_tiles / 4) and at least 1. */
+int apexmi_attn_wide_auto_splits(int units, int key_tiles, int cus);
+size_t apexmi_attn_wide_split_workspace_bytes(int B, int H, int Sq, int Sk, int D, int key_splits);
+int apexmi_attn_fwd_wide_split(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+                               const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                               const int64_t o_strides[3], float softmax_scale, int dtype, int frame_tokens, float* lse,
+                               const int64_t lse_strides[3], int key_splits, void* workspace, size_t workspace_bytes,
+                               apexmi_stream_t stream);
+
 /* The whole "sdpa" contract (R/src/attention/functions.py:338-377: F.scaled_dot_product_attention without dropout):
  *     out = softmax(q k^T * softmax_scale + mask) v
  * q [B,Hq,Sq,D], k / v [B,Hkv,Sk,D] with element strides (b, h, s) that are multiples of 8, D contiguous; bf16 or f16
