@@ -25,6 +25,7 @@
 // row's coordinates from entry, the tile's 64 key records arrive in LDS with the tile (one 8-byte load per key, wave 0, issued
 // with the tile's staging and written before the barrier that publishes the tile).  Excluded scores become -inf through the
 // same fmaf as a bool mask's, so the result equals apexmi_attn_fwd_masked on the equivalent dense bool mask bit for bit.
+#include "attn_host.h"
 #include "attn_tile.h"
 
 #include <cstdint>
@@ -584,13 +585,9 @@ template <typename E, int D, bool WIN = false, bool LSE = false>
 int launch_masked(const MaskedArgs& a, hipStream_t stream) {
     constexpr int STAGE = 2 * KV * D * 2;
     constexpr int WK = WIN ? 2 * KV * 8 : 0;   // the two key-record images of a window launch
-    static uint64_t attr_done = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_masked_kernel<E, D, WIN, LSE>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                              2 * STAGE + 16 + 2 * MAX_TILES + WK));
-    const int lds = 2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15) + WK;
-    hipLaunchKernelGGL((attn_masked_kernel<E, D, WIN, LSE>), dim3(a.total), dim3(MNW * 64), lds, stream, a);
-    return apexmi_check_launch(WIN ? "attn_fwd_window" : LSE ? "attn_fwd_masked_lse" : "attn_fwd_masked");
+    return launch_flash<attn_masked_kernel<E, D, WIN, LSE>>(dim3(a.total), dim3(MNW * 64), 2 * STAGE + 16 + 2 * MAX_TILES + WK,
+                                                            2 * STAGE + 16 + ((2 * a.nkt + 15) & ~15) + WK, stream, a,
+                                                            WIN ? "attn_fwd_window" : LSE ? "attn_fwd_masked_lse" : "attn_fwd_masked");
 }
 
 // V [B, Hkv, Sk, D] (strided rows) -> V^T [B, Hkv, D, Skp] zero padded
@@ -620,6 +617,27 @@ int window_args(MaskedArgs& a, const void* q_coords, const void* k_coords, int r
     return 0;
 }
 
+// the shape fields of a launch (the prepared entry point has no grouped heads and takes Skp from its caller)
+void set_shape(MaskedArgs& a, int B, int Hq, int group, int Sq, int Sk, int Skp) {
+    a.Hq = Hq, a.group = group, a.Sq = Sq, a.Sk = Sk, a.Skp = Skp;
+    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * Hq * a.nqb;
+}
+
+// the checks apexmi_attn_fwd_masked(_lse) and apexmi_attn_fwd_window make between their own: the problem, then the launch limits
+int require_problem(const char* who, int B, int Hq, int Hkv, int Sq, int Sk, int D, int dtype) {
+    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "%s: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)", who,
+                   B, Hq, Hkv, Sq, Sk);
+    if (int rc = require_head_dim(who, D, D == 64 || D == 128, "64 or 128")) return rc;
+    if (int rc = require_dtype(who, dtype)) return rc;
+    return require_head_ratio(who, Hq, Hkv);
+}
+
+int require_launch_limits(const char* who, int B, int H, int Sq, int Sk) {
+    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "%s: Sk=%d above %d keys", who, Sk, MAX_TILES * KV);
+    APEXMI_REQUIRE((int64_t)B * H * ((Sq + MQB - 1) / MQB) < (1ll << 31), "%s: too many query blocks", who);
+    return 0;
+}
+
 template <int MK, typename ET>
 void launch_map(const MaskedArgs& a, int Bm, int Hm, uint8_t* map, hipStream_t stream) {
     constexpr int64_t NE = 16 / sizeof(ET);
@@ -643,41 +661,25 @@ static int fwd_masked(const char* who, bool want_lse, float* lse, const int64_t*
                       const void* mask, int mask_dtype, const int64_t mask_strides[4], int is_causal, float softmax_scale, int dtype,
                       void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides,
-                   "%s: null operand", who);
-    APEXMI_REQUIRE(!want_lse || (lse && lse_strides && ((uintptr_t)lse % 4) == 0), "%s: null or misaligned lse operand", who);
-    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "%s: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)", who,
-                   B, Hq, Hkv, Sq, Sk);
-    APEXMI_REQUIRE(D == 64 || D == 128, "%s: head dim %d unsupported (64 or 128)", who, D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "%s: dtype %d unsupported (bf16 or f16)", who, dtype);
-    APEXMI_REQUIRE(Hq % Hkv == 0, "%s: head ratio Hq=%d / Hkv=%d is not whole", who, Hq, Hkv);
+    if (int rc = require_operands(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides)) return rc;
+    if (int rc = require_lse(who, want_lse, lse, lse_strides, "null or misaligned lse operand")) return rc;
+    if (int rc = require_problem(who, B, Hq, Hkv, Sq, Sk, D, dtype)) return rc;
     APEXMI_REQUIRE(!mask || (mask_strides && (mask_dtype == APEXMI_MASK_BOOL || mask_dtype == APEXMI_F32 ||
                                               mask_dtype == APEXMI_BF16 || mask_dtype == APEXMI_F16)),
                    "%s: mask dtype code %d unsupported (bool, f32, bf16, f16)", who, mask_dtype);
     APEXMI_REQUIRE(!mask || mask_strides[3] == 0 || mask_strides[3] == 1,
                    "%s: mask key stride %lld must be 0 or 1", who, (long long)(mask ? mask_strides[3] : 0));
-    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "%s: Sk=%d above %d keys", who, Sk, MAX_TILES * KV);
-    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "%s: too many query blocks", who);
-    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
-    for (int i = 0; i < 3; ++i)
-        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "%s: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)", who);
-    const size_t need = apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D);
-    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
-                   need);
+    if (int rc = require_launch_limits(who, B, Hq, Sq, Sk)) return rc;
+    if (int rc = require_aligned(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides, 3)) return rc;
+    // not required to be 16-byte aligned here, unlike the varlen and wide entry points
+    if (int rc = require_workspace(who, workspace, workspace_bytes, apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D), false))
+        return rc;
 
     MaskedArgs a{};
-    a.q = (const uint16_t*)q;
-    a.k = (const uint16_t*)k;
-    a.o = (uint16_t*)out;
-    a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
-    a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
-    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
-    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + KV - 1) / KV) * KV;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * Hq * a.nqb;
+    set_qko(a, q, k, out, q_strides, k_strides, o_strides);
+    set_shape(a, B, Hq, Hq / Hkv, Sq, Sk, ((Sk + KV - 1) / KV) * KV);
     a.causal = is_causal ? 1 : 0;
-    a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E;
+    set_scale(a, softmax_scale);
     if (want_lse) a.lse = lse, a.l_sb = lse_strides[0], a.l_sh = lse_strides[1], a.l_sq = lse_strides[2];
 
     // V^T [B, Hkv, D, Skp]
@@ -811,33 +813,18 @@ extern "C" int apexmi_attn_fwd_window(const void* q, const void* k, const void* 
                                       const void* k_coords, int r0, int r1, int r2, const void* map, float softmax_scale,
                                       int dtype, void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attn_fwd_window: null operand");
-    APEXMI_REQUIRE(B > 0 && Hq > 0 && Hkv > 0 && Sq > 0 && Sk > 0, "attn_fwd_window: empty problem (B=%d Hq=%d Hkv=%d Sq=%d Sk=%d)",
-                   B, Hq, Hkv, Sq, Sk);
-    APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_window: head dim %d unsupported (64 or 128)", D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_window: dtype %d unsupported (bf16 or f16)", dtype);
-    APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_window: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
-    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_window: Sk=%d above %d keys", Sk, MAX_TILES * KV);
-    APEXMI_REQUIRE((int64_t)B * Hq * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_window: too many query blocks");
-    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
-    for (int i = 0; i < 3; ++i)
-        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "attn_fwd_window: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
-    const size_t need = vt_bytes(B, Hkv, Sk, D);
-    APEXMI_REQUIRE(workspace && workspace_bytes >= need, "attn_fwd_window: workspace too small (%zu < %zu)", workspace_bytes, need);
+    const char* who = "attn_fwd_window";
+    if (int rc = require_operands(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides)) return rc;
+    if (int rc = require_problem(who, B, Hq, Hkv, Sq, Sk, D, dtype)) return rc;
+    if (int rc = require_launch_limits(who, B, Hq, Sq, Sk)) return rc;
+    if (int rc = require_aligned(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides, 3)) return rc;
+    if (int rc = require_workspace(who, workspace, workspace_bytes, vt_bytes(B, Hkv, Sk, D), false)) return rc;
 
     MaskedArgs a{};
-    if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, "attn_fwd_window")) return rc;
-    a.q = (const uint16_t*)q;
-    a.k = (const uint16_t*)k;
-    a.o = (uint16_t*)out;
-    a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
-    a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
-    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
-    a.Hq = Hq, a.group = Hq / Hkv, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + KV - 1) / KV) * KV;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * Hq * a.nqb;
-    a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E;
+    if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, who)) return rc;
+    set_qko(a, q, k, out, q_strides, k_strides, o_strides);
+    set_shape(a, B, Hq, Hq / Hkv, Sq, Sk, ((Sk + KV - 1) / KV) * KV);
+    set_scale(a, softmax_scale);
     uint16_t* vt = (uint16_t*)workspace;
     a.vt = vt;
     if (int rc = transpose_v(v, v_strides, B, Hkv, Sk, a.Skp, D, vt, stream_)) return rc;
@@ -861,22 +848,16 @@ extern "C" int apexmi_attn_fwd_prepared_window(const void* q, const void* k, con
                    "attn_fwd_prepared_window: operands must be 16-byte aligned");
     APEXMI_REQUIRE(o_strides[0] % 4 == 0 && o_strides[1] % 4 == 0 && o_strides[2] % 4 == 0,
                    "attn_fwd_prepared_window: output strides must be multiples of 4 elements");
-    APEXMI_REQUIRE((Sk + KV - 1) / KV <= MAX_TILES, "attn_fwd_prepared_window: Sk=%d above %d keys", Sk, MAX_TILES * KV);
-    APEXMI_REQUIRE((int64_t)B * H * ((Sq + MQB - 1) / MQB) < (1ll << 31), "attn_fwd_prepared_window: too many query blocks");
+    if (int rc = require_launch_limits("attn_fwd_prepared_window", B, H, Sq, Sk)) return rc;
 
     MaskedArgs a{};
     if (int rc = window_args(a, q_coords, k_coords, r0, r1, r2, map, "attn_fwd_prepared_window")) return rc;
-    a.q = (const uint16_t*)q;
-    a.k = (const uint16_t*)k;
+    const int64_t q_packed[3] = {(int64_t)H * Sq * D, (int64_t)Sq * D, D};
+    const int64_t k_packed[3] = {(int64_t)H * Sk * D, (int64_t)Sk * D, D};
+    set_qko(a, q, k, out, q_packed, k_packed, o_strides);
     a.vt = (const uint16_t*)vt;
-    a.o = (uint16_t*)out;
-    a.q_sb = (int64_t)H * Sq * D, a.q_sh = (int64_t)Sq * D, a.q_ss = D;
-    a.k_sb = (int64_t)H * Sk * D, a.k_sh = (int64_t)Sk * D, a.k_ss = D;
-    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
-    a.Hq = H, a.group = 1, a.Sq = Sq, a.Sk = Sk, a.Skp = Skp;
-    a.nqb = (Sq + MQB - 1) / MQB, a.nkt = (Sk + KV - 1) / KV, a.total = B * H * a.nqb;
-    a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E;
+    set_shape(a, B, H, 1, Sq, Sk, Skp);
+    set_scale(a, softmax_scale);
     ApexmiProfScope prof(1, stream, 4.0 * B * H * (double)Sq * Sk * D, 0.0);
     return launch_masked<ElemBf16, 128, true>(a, stream);
 }

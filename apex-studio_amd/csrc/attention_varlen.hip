@@ -25,6 +25,7 @@
 // end = clamp(cu[i + 1], start, T), and its length to the max_seqlen they were launched for: a wrong cu_seqlens or a too-small
 // max_seqlen truncates the result and never forms an address outside q / k / v / out / lse or the workspace.  Query rows past
 // the end of a block's sequence are clamped to that sequence's LAST row and not stored.
+#include "attn_host.h"
 #include "attn_tile.h"
 
 #include <cstdint>
@@ -223,11 +224,7 @@ int64_t vt_pitch(int Tk, int n) { return (((int64_t)Tk + KV - 1) / KV) * KV + (i
 template <typename E, int D, bool LSE>
 int launch_varlen(const VarlenArgs& a, hipStream_t stream) {
     constexpr int LDS = 2 * (2 * KV * D * 2);
-    static uint64_t attr_done = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_varlen_kernel<E, D, LSE>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    hipLaunchKernelGGL((attn_varlen_kernel<E, D, LSE>), dim3(a.total), dim3(VNW * 64), LDS, stream, a);
-    return apexmi_check_launch("attn_fwd_varlen");
+    return launch_flash<attn_varlen_kernel<E, D, LSE>>(dim3(a.total), dim3(VNW * 64), LDS, LDS, stream, a, "attn_fwd_varlen");
 }
 
 template <typename E, int D>
@@ -249,29 +246,25 @@ extern "C" int apexmi_attn_fwd_varlen(const void* q, const void* k, const void* 
                                       int is_causal, float softmax_scale, int dtype, void* workspace, size_t workspace_bytes,
                                       apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attn_fwd_varlen: null operand");
+    const char* who = "attn_fwd_varlen";
+    if (int rc = require_operands(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides)) return rc;
     APEXMI_REQUIRE(cu_seqlens_q && cu_seqlens_k && ((uintptr_t)cu_seqlens_q % 4) == 0 && ((uintptr_t)cu_seqlens_k % 4) == 0,
                    "attn_fwd_varlen: null or misaligned cu_seqlens operand");
-    APEXMI_REQUIRE(!lse || (lse_strides && ((uintptr_t)lse % 4) == 0), "attn_fwd_varlen: misaligned lse operand or null lse strides");
+    if (int rc = require_lse(who, lse != nullptr, lse, lse_strides, "misaligned lse operand or null lse strides")) return rc;
     APEXMI_REQUIRE(n > 0 && Tq > 0 && Tk > 0 && Hq > 0 && Hkv > 0, "attn_fwd_varlen: empty problem (n=%d Tq=%d Tk=%d Hq=%d Hkv=%d)", n,
                    Tq, Tk, Hq, Hkv);
     APEXMI_REQUIRE(max_seqlen_q > 0 && max_seqlen_k > 0, "attn_fwd_varlen: max_seqlen_q=%d / max_seqlen_k=%d must be at least 1",
                    max_seqlen_q, max_seqlen_k);
-    APEXMI_REQUIRE(D == 64 || D == 128, "attn_fwd_varlen: head dim %d unsupported (64 or 128)", D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "attn_fwd_varlen: dtype %d unsupported (bf16 or f16)", dtype);
-    APEXMI_REQUIRE(Hq % Hkv == 0, "attn_fwd_varlen: head ratio Hq=%d / Hkv=%d is not whole", Hq, Hkv);
+    if (int rc = require_head_dim(who, D, D == 64 || D == 128, "64 or 128")) return rc;
+    if (int rc = require_dtype(who, dtype)) return rc;
+    if (int rc = require_head_ratio(who, Hq, Hkv)) return rc;
     // a sequence is never longer than its array: the clamped max_seqlen sizes the same launches
     const int max_q = max_seqlen_q < Tq ? max_seqlen_q : Tq, max_k = max_seqlen_k < Tk ? max_seqlen_k : Tk;
     const int nqb = (max_q + VQB - 1) / VQB;
     APEXMI_REQUIRE((int64_t)n * Hq * nqb < (1ll << 31) && n <= 65535 && Hkv <= 65535,
                    "attn_fwd_varlen: grid too large (n=%d sequences, Hq=%d, Hkv=%d, %d query blocks each)", n, Hq, Hkv, nqb);
-    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
-    for (int i = 0; i < 2; ++i)
-        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "attn_fwd_varlen: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)");
-    const size_t need = apexmi_attn_varlen_workspace_bytes(Tk, n, Hkv, D);
-    APEXMI_REQUIRE(workspace && ((uintptr_t)workspace % 16) == 0 && workspace_bytes >= need,
-                   "attn_fwd_varlen: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
+    if (int rc = require_aligned(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides, 2)) return rc;
+    if (int rc = require_workspace(who, workspace, workspace_bytes, apexmi_attn_varlen_workspace_bytes(Tk, n, Hkv, D), true)) return rc;
 
     VarlenArgs a{};
     a.q = (const uint16_t*)q, a.k = (const uint16_t*)k, a.vt = (const uint16_t*)workspace, a.o = (uint16_t*)out, a.lse = lse;
@@ -283,8 +276,7 @@ extern "C" int apexmi_attn_fwd_varlen(const void* q, const void* k, const void* 
     a.Tq = Tq, a.Tk = Tk, a.Hq = Hq, a.group = Hq / Hkv, a.nqb = nqb, a.total = n * Hq * nqb;
     a.max_q = max_q, a.max_k = max_k;
     a.causal = is_causal ? 1 : 0;
-    a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E;
+    set_scale(a, softmax_scale);
 
     const dim3 vgrid((max_k + KV - 1) / KV, Hkv, n);
     if (D == 128)

@@ -37,6 +37,7 @@
 //     (fewer tiles than splits) stores lse = -inf and leaves its partial rows unwritten (weight 0 in the merge), and under the
 //     frame rule a row may find every key of the range excluded beside live rows of its wave: its maximum stays SENTINEL
 //     (wide_raise_max: m_new = SENTINEL, alpha = 2^0), every p is 2^(-inf) = 0, the partial is 0 and the lse -inf.
+#include "attn_host.h"
 #include "attn_tile.h"
 
 #include <algorithm>
@@ -385,28 +386,15 @@ __global__ __launch_bounds__(WNW * 64, 1) void attn_wide_kernel(const typename W
 template <typename E, int D>
 int launch_wide(const WideArgs& a, hipStream_t stream) {
     constexpr int LDS = 2 * KV * D * 2;
-    static uint64_t attr_done = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_wide_kernel<E, D>,
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    hipLaunchKernelGGL((attn_wide_kernel<E, D>), dim3(a.total), dim3(WNW * 64), LDS, stream, a);
-    return apexmi_check_launch("attn_fwd_wide");
+    return launch_flash<attn_wide_kernel<E, D>>(dim3(a.total), dim3(WNW * 64), LDS, LDS, stream, a, "attn_fwd_wide");
 }
 
 template <typename E, int D>
 int launch_wide(const WideSplitArgs& a, hipStream_t stream) {
     constexpr int LDS = 2 * KV * D * 2;
-    static uint64_t attr_done = 0;
-    if (a.n == 1) {
-        APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_wide_kernel<E, D, 1>,
-                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        hipLaunchKernelGGL((attn_wide_kernel<E, D, 1>), dim3(a.total), dim3(WNW * 64), LDS, stream, a);
-        return apexmi_check_launch("attn_fwd_wide_split (lse)");
-    }
-    static uint64_t attr_done2 = 0;
-    APEXMI_SET_ATTR_ONCE(attr_done2, (void)hipFuncSetAttribute((const void*)attn_wide_kernel<E, D, 2>,
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    hipLaunchKernelGGL((attn_wide_kernel<E, D, 2>), dim3(a.total * a.n), dim3(WNW * 64), LDS, stream, a);
-    return apexmi_check_launch("attn_fwd_wide_split");
+    if (a.n == 1)
+        return launch_flash<attn_wide_kernel<E, D, 1>>(dim3(a.total), dim3(WNW * 64), LDS, LDS, stream, a, "attn_fwd_wide_split (lse)");
+    return launch_flash<attn_wide_kernel<E, D, 2>>(dim3(a.total * a.n), dim3(WNW * 64), LDS, LDS, stream, a, "attn_fwd_wide_split");
 }
 
 template <typename E, typename A>
@@ -424,11 +412,11 @@ int fwd_wide(const char* who, const void* q, const void* k, const void* v, void*
              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
              float softmax_scale, int dtype, int frame_tokens, float* lse, const int64_t* lse_strides, int key_splits,
              void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    APEXMI_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "%s: null operand", who);
+    if (int rc = require_operands(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides)) return rc;
     APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "%s: empty problem (B=%d H=%d Sq=%d Sk=%d)", who, B, H, Sq, Sk);
-    APEXMI_REQUIRE(wide_dim(D), "%s: head dim %d unsupported (256, 384 or 512; wider heads stay on apexmi_attn_fwd's "
-                   "materialised path)", who, D);
-    APEXMI_REQUIRE(dtype == APEXMI_BF16 || dtype == APEXMI_F16, "%s: dtype %d unsupported (bf16 or f16)", who, dtype);
+    if (int rc = require_head_dim(who, D, wide_dim(D), "256, 384 or 512; wider heads stay on apexmi_attn_fwd's materialised path"))
+        return rc;
+    if (int rc = require_dtype(who, dtype)) return rc;
     APEXMI_REQUIRE(frame_tokens >= 0, "%s: negative frame_tokens %d", who, frame_tokens);
     APEXMI_REQUIRE(frame_tokens == 0 || (Sq == Sk && Sq % frame_tokens == 0),
                    "%s: the frame rule needs Sq == Sk and a whole number of frames of %d tokens (Sq=%d Sk=%d)", who,
@@ -441,13 +429,10 @@ int fwd_wide(const char* who, const void* q, const void* k, const void* v, void*
     APEXMI_REQUIRE((int64_t)Sk * k_strides[2] < (1ll << 31) && (int64_t)D * (Sk + KV) < (1ll << 31),
                    "%s: the keys of one (batch, head) span 4 GiB or more (Sk=%d, row stride %lld)", who, Sk,
                    (long long)k_strides[2]);
-    bool aligned = ((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0 && ((uintptr_t)out % 8) == 0;
-    for (int i = 0; i < 3; ++i)
-        aligned = aligned && q_strides[i] % 8 == 0 && k_strides[i] % 8 == 0 && v_strides[i] % 8 == 0 && o_strides[i] % 4 == 0;
-    APEXMI_REQUIRE(aligned, "%s: q / k / v rows must be 16-byte aligned (strides multiples of 8 elements)", who);
+    if (int rc = require_aligned(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides, 3)) return rc;
     APEXMI_REQUIRE(key_splits >= 0 && key_splits <= WIDE_SPLITS_MAX, "%s: key_splits=%d unsupported (0 = auto, 1 to %d)", who,
                    key_splits, WIDE_SPLITS_MAX);
-    APEXMI_REQUIRE(!lse || (lse_strides && ((uintptr_t)lse % 4) == 0), "%s: lse without strides, or misaligned", who);
+    if (int rc = require_lse(who, lse != nullptr, lse, lse_strides, "lse without strides, or misaligned")) return rc;
     int n = key_splits;
     if (n == 0) {   // shape-only: the CU count of the current device and the pure rule
         int dev = 0, cus = 0;
@@ -457,21 +442,14 @@ int fwd_wide(const char* who, const void* q, const void* k, const void* v, void*
         n = apexmi_attn_wide_auto_splits((int)units, (Sk + KV - 1) / KV, cus);
     }
     APEXMI_REQUIRE(units * n < (1ll << 31), "%s: too many workgroups (%lld query blocks x %d key splits)", who, (long long)units, n);
-    const size_t need = apexmi_attn_wide_split_workspace_bytes(B, H, Sq, Sk, D, n);
-    APEXMI_REQUIRE(workspace && ((uintptr_t)workspace % 16) == 0 && workspace_bytes >= need,
-                   "%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, need);
+    if (int rc = require_workspace(who, workspace, workspace_bytes, apexmi_attn_wide_split_workspace_bytes(B, H, Sq, Sk, D, n), true))
+        return rc;
 
     WideSplitArgs a{};
-    a.q = (const uint16_t*)q;
-    a.k = (const uint16_t*)k;
-    a.o = (uint16_t*)out;
-    a.q_sb = q_strides[0], a.q_sh = q_strides[1], a.q_ss = q_strides[2];
-    a.k_sb = k_strides[0], a.k_sh = k_strides[1], a.k_ss = k_strides[2];
-    a.o_sb = o_strides[0], a.o_ss = o_strides[1], a.o_sh = o_strides[2];
+    set_qko(a, q, k, out, q_strides, k_strides, o_strides);
     a.H = H, a.Sq = Sq, a.Sk = Sk, a.Skp = ((Sk + KV - 1) / KV) * KV;
     a.nqb = (Sq + WQB - 1) / WQB, a.total = B * H * a.nqb;
-    a.neg = softmax_scale < 0.0f;
-    a.c = fabsf(softmax_scale) * LOG2E;
+    set_scale(a, softmax_scale);
     a.ft = frame_tokens;
     a.B = B, a.n = n;
 

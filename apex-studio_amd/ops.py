@@ -28,6 +28,63 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+_I64N = {2: type(_l.i64x2((0, 0))), 3: type(_l.i64x3((0, 0, 0)))}
+
+
+def _st(t: torch.Tensor, n: int = 3):
+    """t's first n element strides as the int64[n] the C entry points take"""
+    return _I64N[n](*t.stride()[:n])
+
+
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """t itself where the attention kernels can read it in place, else one contiguous copy: they take 16 bytes of a row at a
+    time, so the last dim is contiguous, the data 16-byte aligned and every other stride a multiple of 8 elements"""
+    st = t.stride()
+    ok = st[-1] == 1 and t.data_ptr() % 16 == 0 and all(x % 8 == 0 for x in st[:-1])
+    return t if ok else t.contiguous()
+
+
+# attention workspaces, one per key: (tag, device index, stream) with the tag of a kernel family ("masked" serves the masked and
+# the window wrappers, "varlen", "wide", "prep"), (device index, stream) for attention / attention_framecausal / attention_bias
+_ws_cache: dict = {}
+
+
+def _workspace(key, device, need: int, at_least: int = 0) -> torch.Tensor:
+    """the cached uint8 buffer of `key`, replaced by a larger one when it holds fewer than max(need, at_least) bytes"""
+    if need < at_least:
+        need = at_least
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _ws_cache[key] = ws
+    return ws
+
+
+def _flash_qkv(who: str, q, k, v, rank: int, head_dims, enable_gqa):
+    """The type and shape refusals the flash wrappers share, for q / k / v [B,H,S,D] (rank 4) or packed [T,H,D] (rank 3);
+    returns (Hq, Hkv, Sq, Sk, D).  enable_gqa=None: a kernel without grouped-query heads (k and v need q's head count).  No
+    device check: each wrapper places its own."""
+    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"{who}: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
+    if q.dim() != rank or k.dim() != rank or v.dim() != rank:
+        raise _l.ApexMIError(f"{who}: q, k, v must be " + ("4-D [B, H, S, D]" if rank == 4 else "3-D packed [T, H, D]"))
+    qs, ks, seq = q.shape, k.shape, 2 if rank == 4 else 0
+    Hq, Hkv, Sq, Sk, D = qs[1], ks[1], qs[seq], ks[seq], qs[-1]
+    if D not in head_dims:
+        if enable_gqa is None:
+            raise _l.ApexMIError(f"{who}: head dim {D} unsupported {head_dims}; other head sizes go through `attention`")
+        raise _l.ApexMIError(f"{who}: head dim {D} unsupported (64 or 128)")
+    if ks[:rank - 3] != qs[:rank - 3] or ks[-1] != D or v.shape != ks or (enable_gqa is None and Hkv != Hq):
+        raise _l.ApexMIError(f"{who}: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    empty = q.numel() == 0 or k.numel() == 0
+    # the 4-D wrappers refuse a ratio before an empty problem, the packed one an empty problem first
+    if enable_gqa is not None and not (empty and rank == 3) and (Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1)):
+        raise _l.ApexMIError(f"{who}: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a whole ratio")
+    if empty:
+        raise _l.ApexMIError(f"{who}: empty problem")
+    return Hq, Hkv, Sq, Sk, D
+
+
 # ---- activation storage type -----------------------------------------------------------------------------------------
 # Production stores activations as bf16.  A float32 activation tensor selects the f32-STORAGE VERIFICATION MODE of the
 # library (include/apexmi.h, last section; DESIGN.md §1.2): the same kernels instantiated with float storage, the MFMA
@@ -802,20 +859,14 @@ def attention_prepared(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: 
         for t_ in (k, vt, out):
             _req(t_, torch.float32, "attention operand")
         rc = lib.apexmi_attn_fwd_prepared_f32(q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), B, H, Sq, Sk,
-                                              vt.shape[3], _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                              vt.shape[3], _st(out),
                                               float(scale), _stream())
         _l.check(rc, "attn_fwd_prepared_f32")
         return out
     need = lib.apexmi_attn_prepared_workspace_bytes(B, H, Sq, Sk)     # scratch of the tail split, usually 0
-    ws = None
-    if need:
-        key = ("prep", q.device.index, torch.cuda.current_stream().cuda_stream)
-        ws = _ws_cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            _ws_cache[key] = ws
+    ws = _workspace(("prep", q.device.index, _stream()), q.device, need) if need else None
     rc = lib.apexmi_attn_fwd_prepared_ws(q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), B, H, Sq, Sk,
-                                         vt.shape[3], _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                         vt.shape[3], _st(out),
                                          float(scale), _ptr(ws), need, _stream())
     _l.check(rc, "attn_fwd_prepared")
     return out
@@ -841,7 +892,7 @@ def attention_prepared_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor
         scale = 1.0 / math.sqrt(D)
     rc = _l.load().apexmi_attn_fwd_prepared_window(
         q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), B, H, Sq, Sk, vt.shape[3],
-        _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), plan.q_coords.data_ptr(), plan.k_coords.data_ptr(),
+        _st(out), plan.q_coords.data_ptr(), plan.k_coords.data_ptr(),
         *plan.radius, plan.block_map.data_ptr(), float(scale), _stream())
     _l.check(rc, "attn_fwd_prepared_window")
     return out
@@ -873,13 +924,12 @@ def attention_prepared_dual(q: torch.Tensor, k_t: torch.Tensor, vt_t: torch.Tens
     rc = _l.load().apexmi_attn_fwd_prepared_dual(
         q.data_ptr(), k_t.data_ptr(), vt_t.data_ptr(), int(Sk_t), vt_t.shape[3],
         _ptr(k_i) if Sk_i else None, _ptr(vt_i) if Sk_i else None, int(Sk_i), vt_i.shape[3] if Sk_i else 0,
-        out.data_ptr(), B, H, Sq, _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), float(scale), _stream())
+        out.data_ptr(), B, H, Sq, _st(out), float(scale), _stream())
     _l.check(rc, "attn_fwd_prepared_dual")
     return out
 
 
 _DT ={torch.bfloat16: _l.BF16, torch.float16: _l.F16, torch.float32: _l.F32}
-_ws_cache: dict = {}
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -903,18 +953,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
     lib = _l.load()
     need = lib.apexmi_attn_workspace_bytes(B, H, Sq, Sk, D, _DT[q.dtype])
-    ws = None
-    if need:
-        key = (q.device.index, torch.cuda.current_stream().cuda_stream)
-        ws = _ws_cache.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-            _ws_cache[key] = ws
+    ws = _workspace((q.device.index, _stream()), q.device, need) if need else None
     rc = lib.apexmi_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
-                             _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                             _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                             _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                             _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                             _st(q), _st(k), _st(v), _st(out),
                              float(softmax_scale), _DT[q.dtype], _ptr(ws), need, _stream())
     _l.check(rc, "attn_fwd")
     return out.permute(0, 2, 1, 3)
@@ -964,59 +1005,27 @@ def attention_masked(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mas
     _req(q, None, "attention_masked.q")
     _req(k, None, "attention_masked.k")
     _req(v, None, "attention_masked.v")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _l.ApexMIError(f"attention_masked: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise _l.ApexMIError("attention_masked: q, k, v must be 4-D [B, H, S, D]")
-    B, Hq, Sq, D = q.shape
-    Bk, Hkv, Sk, Dk = k.shape
-    if D not in (64, 128):
-        raise _l.ApexMIError(f"attention_masked: head dim {D} unsupported (64 or 128)")
-    if Bk != B or Dk != D or tuple(v.shape) != tuple(k.shape):
-        raise _l.ApexMIError(f"attention_masked: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
-    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
-        raise _l.ApexMIError(f"attention_masked: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
-                             "whole ratio")
-    if min(B, Hq, Sq, Sk) == 0:
-        raise _l.ApexMIError("attention_masked: empty problem")
+    Hq, Hkv, Sq, Sk, D = _flash_qkv("attention_masked", q, k, v, 4, (64, 128), bool(enable_gqa))
+    B = q.shape[0]
     m, mcode, mst = _mask_operand(attn_mask, B, Hq, Sq, Sk, q.dtype)
     if m is not None and m.device != q.device:
         raise _l.ApexMIError(f"attention_masked: attn_mask is on {m.device}, q on {q.device}")
-
-    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
-        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
-        return t if ok else t.contiguous()
-
-    q, k, v = rows16(q), rows16(k), rows16(v)
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lib = _l.load()
     need = lib.apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D)
-    key = ("masked", q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
+    ws = _workspace(("masked", q.device.index, _stream()), q.device, need)
+    # the two entry points differ by the lse pointer behind `out` and its strides behind out's
+    ptrs = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr())
+    shape = (B, Hq, Hkv, Sq, Sk, D, _st(q), _st(k), _st(v), _st(out))
+    rest = (_ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
     if return_lse:
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device)
-        rc = lib.apexmi_attn_fwd_masked_lse(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), B, Hq, Hkv,
-                                            Sq, Sk, D, _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                            _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                            _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                            _l.i64x3((out.stride(0), out.stride(1), out.stride(2))), _l.i64x3(lse.stride()),
-                                            _ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale),
-                                            _DT[q.dtype], ws.data_ptr(), need, _stream())
-        _l.check(rc, "attn_fwd_masked_lse")
+        _l.check(lib.apexmi_attn_fwd_masked_lse(*ptrs, lse.data_ptr(), *shape, _st(lse), *rest), "attn_fwd_masked_lse")
         return out.permute(0, 2, 1, 3), lse
-    rc = lib.apexmi_attn_fwd_masked(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
-                                    _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                    _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                    _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                    _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
-                                    _ptr(m), mcode, _l.i64x4(mst), 1 if is_causal else 0, float(softmax_scale),
-                                    _DT[q.dtype], ws.data_ptr(), need, _stream())
-    _l.check(rc, "attn_fwd_masked")
+    _l.check(lib.apexmi_attn_fwd_masked(*ptrs, *shape, *rest), "attn_fwd_masked")
     return out.permute(0, 2, 1, 3)
 
 
@@ -1067,7 +1076,7 @@ def attention_merge(outs, lses, out: Optional[torch.Tensor] = None):
     optr = (_l.vp * n)(*[o.data_ptr() for o in outs])
     lptr = (_l.vp * n)(*[l.data_ptr() for l in lses])
     rc = _l.load().apexmi_attn_merge(n, optr, lptr, out.data_ptr(), lse.data_ptr(), B, H, Sq, D,
-                                     _l.i64x3((out.stride(0), out.stride(2), out.stride(1))), _l.i64x3(lse.stride()),
+                                     _l.i64x3((out.stride(0), out.stride(2), out.stride(1))), _st(lse),
                                      _DT[o0.dtype], _stream())
     _l.check(rc, "attn_merge")
     return out, lse
@@ -1127,21 +1136,7 @@ def attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
     is bit-identical with and without return_lse.  out[None].permute(0, 2, 1, 3) and lse[None] are what attention_merge accepts
     (no copy), so varlen partials over separate key sets merge like any others."""
     # shapes and types first, the device last: every refusal below is reachable without a device
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _l.ApexMIError(f"attention_varlen: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
-    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
-        raise _l.ApexMIError("attention_varlen: q, k, v must be 3-D packed [T, H, D]")
-    Tq, Hq, D = q.shape
-    Tk, Hkv, Dk = k.shape
-    if D not in (64, 128):
-        raise _l.ApexMIError(f"attention_varlen: head dim {D} unsupported (64 or 128)")
-    if Dk != D or tuple(v.shape) != tuple(k.shape):
-        raise _l.ApexMIError(f"attention_varlen: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
-    if min(Tq, Hq, Tk, Hkv) == 0:
-        raise _l.ApexMIError("attention_varlen: empty problem")
-    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
-        raise _l.ApexMIError(f"attention_varlen: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
-                             "whole ratio")
+    Hq, Hkv, Tq, Tk, D = _flash_qkv("attention_varlen", q, k, v, 3, (64, 128), bool(enable_gqa))
     if k.device != q.device or v.device != q.device:
         raise _l.ApexMIError(f"attention_varlen: k / v are on {k.device} / {v.device}, q on {q.device}")
     for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_seqlens_k)):
@@ -1158,27 +1153,17 @@ def attention_varlen(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
     n = cu_seqlens_q.numel() - 1
     _req(q, None, "attention_varlen.q")
     max_seqlen_q, max_seqlen_k = min(max_seqlen_q, Tq), min(max_seqlen_k, Tk)   # a sequence is never longer than its array
-
-    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
-        ok = t.stride(2) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:2])
-        return t if ok else t.contiguous()
-
-    q, k, v = rows16(q), rows16(k), rows16(v)
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     out = torch.empty((Tq, Hq, D), dtype=q.dtype, device=q.device)
     lse = torch.empty((Hq, Tq), dtype=torch.float32, device=q.device) if return_lse else None
     lib = _l.load()
     need = lib.apexmi_attn_varlen_workspace_bytes(Tk, n, Hkv, D)
-    key = ("varlen", q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
-    i64x2 = lambda t: _l.i64x2((t.stride(0), t.stride(1)))   # noqa: E731
+    ws = _workspace(("varlen", q.device.index, _stream()), q.device, need)
     rc = lib.apexmi_attn_fwd_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _ptr(lse), cu_seqlens_q.data_ptr(),
-                                    cu_seqlens_k.data_ptr(), n, Tq, Tk, Hq, Hkv, D, max_seqlen_q, max_seqlen_k, i64x2(q), i64x2(k),
-                                    i64x2(v), i64x2(out), i64x2(lse) if return_lse else None, 1 if is_causal else 0,
+                                    cu_seqlens_k.data_ptr(), n, Tq, Tk, Hq, Hkv, D, max_seqlen_q, max_seqlen_k, _st(q, 2), _st(k, 2),
+                                    _st(v, 2), _st(out, 2), _st(lse, 2) if return_lse else None, 1 if is_causal else 0,
                                     float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_varlen")
     return (out, lse) if return_lse else out
@@ -1288,43 +1273,18 @@ def attention_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, plan: Wi
     _req(v, None, "attention_window.v")
     if not isinstance(plan, WindowPlan):
         raise _l.ApexMIError(f"attention_window: plan must be an ops.WindowPlan (ops.window_plan), got {type(plan).__name__}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _l.ApexMIError(f"attention_window: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise _l.ApexMIError("attention_window: q, k, v must be 4-D [B, H, S, D]")
-    B, Hq, Sq, D = q.shape
-    Bk, Hkv, Sk, Dk = k.shape
-    if D not in (64, 128):
-        raise _l.ApexMIError(f"attention_window: head dim {D} unsupported (64 or 128)")
-    if Bk != B or Dk != D or tuple(v.shape) != tuple(k.shape):
-        raise _l.ApexMIError(f"attention_window: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
-    if Hq % Hkv != 0 or (Hkv != Hq and not enable_gqa and Hkv != 1):
-        raise _l.ApexMIError(f"attention_window: {Hq} query heads over {Hkv} key/value heads needs enable_gqa=True and a "
-                             "whole ratio")
-    if min(B, Hq, Sq, Sk) == 0:
-        raise _l.ApexMIError("attention_window: empty problem")
+    Hq, Hkv, Sq, Sk, D = _flash_qkv("attention_window", q, k, v, 4, (64, 128), bool(enable_gqa))
+    B = q.shape[0]
     plan.check(Sq, Sk, q.device, "attention_window")
-
-    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
-        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
-        return t if ok else t.contiguous()
-
-    q, k, v = rows16(q), rows16(k), rows16(v)
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     out = torch.empty((B, Sq, Hq, D), dtype=q.dtype, device=q.device)
     lib = _l.load()
     need = lib.apexmi_attn_masked_workspace_bytes(B, Hq, Hkv, Sq, Sk, D)
-    key = ("masked", q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
+    ws = _workspace(("masked", q.device.index, _stream()), q.device, need)
     rc = lib.apexmi_attn_fwd_window(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
-                                    _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                    _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                    _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                    _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                    _st(q), _st(k), _st(v), _st(out),
                                     plan.q_coords.data_ptr(), plan.k_coords.data_ptr(), *plan.radius,
                                     plan.block_map.data_ptr(), float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_window")
@@ -1343,17 +1303,10 @@ def attention_framecausal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tok
     out = torch.empty((B, S, H, D), dtype=q.dtype, device=q.device)
     lib = _l.load()
     need = lib.apexmi_attn_framecausal_workspace_bytes(S, D)
-    key = (q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < max(need, 1):
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
+    ws = _workspace((q.device.index, _stream()), q.device, need, at_least=1)
     rc = lib.apexmi_attn_fwd_framecausal(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, S, D,
                                          int(tokens_per_frame),
-                                         _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                         _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                         _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                         _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
+                                         _st(q), _st(k), _st(v), _st(out),
                                          float(softmax_scale), ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_framecausal")
     return out.permute(0, 2, 1, 3)
@@ -1394,29 +1347,14 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_sc
     this function always made."""
     for t, name in ((q, "q"), (k, "k"), (v, "v")):
         _req(t, None, f"attention_wide.{name}")
-    if q.dtype not in (torch.bfloat16, torch.float16) or k.dtype != q.dtype or v.dtype != q.dtype:
-        raise _l.ApexMIError(f"attention_wide: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 or f16, all equal)")
-    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
-        raise _l.ApexMIError("attention_wide: q, k, v must be 4-D [B, H, S, D]")
-    B, H, Sq, D = q.shape
-    Sk = k.shape[2]
-    if D not in WIDE_HEAD_DIMS:
-        raise _l.ApexMIError(f"attention_wide: head dim {D} unsupported {WIDE_HEAD_DIMS}; other head sizes go through `attention`")
-    if tuple(k.shape) != (B, H, Sk, D) or tuple(v.shape) != tuple(k.shape):
-        raise _l.ApexMIError(f"attention_wide: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
-    if min(B, H, Sq, Sk) == 0:
-        raise _l.ApexMIError("attention_wide: empty problem")
+    H, _, Sq, Sk, D = _flash_qkv("attention_wide", q, k, v, 4, WIDE_HEAD_DIMS, None)      # None: no grouped-query heads
+    B = q.shape[0]
     frame_tokens = int(frame_tokens)
     if frame_tokens < 0 or (frame_tokens and (Sq != Sk or Sq % frame_tokens)):
         raise _l.ApexMIError(f"attention_wide: frame_tokens={frame_tokens} needs Sq == Sk and a whole number of frames "
                              f"(Sq={Sq}, Sk={Sk})")
     n = _wide_key_splits(key_splits, "attention_wide")
-
-    def rows16(t):   # in-place reads need 16-byte rows: D contiguous, strides multiples of 8 elements
-        ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(st % 8 == 0 for st in t.stride()[:3])
-        return t if ok else t.contiguous()
-
-    q, k, v = rows16(q), rows16(k), rows16(v)
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
     if softmax_scale is None:
         softmax_scale = 1.0 / math.sqrt(D)
     out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
@@ -1425,30 +1363,17 @@ def attention_wide(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, softmax_sc
     n_ws = n or lib.apexmi_attn_wide_auto_splits(B * H * ((Sq + 127) // 128), (Sk + 63) // 64,
                                                  torch.cuda.get_device_properties(q.device).multi_processor_count)
     need = lib.apexmi_attn_wide_split_workspace_bytes(B, H, Sq, Sk, D, n_ws)
-    key = ("wide", q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
+    ws = _workspace(("wide", q.device.index, _stream()), q.device, need)
+    common = (q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D, _st(q), _st(k), _st(v), _st(out),
+              float(softmax_scale), _DT[q.dtype], frame_tokens)
     if n != 1 or return_lse:
         lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device) if return_lse else None
         with torch.cuda.device(q.device):      # "auto" reads the current device's compute-unit count
-            rc = lib.apexmi_attn_fwd_wide_split(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
-                                                _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                                _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                                _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                                _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
-                                                float(softmax_scale), _DT[q.dtype], frame_tokens, _ptr(lse),
-                                                _l.i64x3(lse.stride()) if return_lse else None, n, ws.data_ptr(), need, _stream())
+            rc = lib.apexmi_attn_fwd_wide_split(*common, _ptr(lse), _st(lse) if return_lse else None, n, ws.data_ptr(), need,
+                                                _stream())
         _l.check(rc, "attn_fwd_wide_split")
         return (out.permute(0, 2, 1, 3), lse) if return_lse else out.permute(0, 2, 1, 3)
-    rc = lib.apexmi_attn_fwd_wide(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D,
-                                  _l.i64x3((q.stride(0), q.stride(1), q.stride(2))),
-                                  _l.i64x3((k.stride(0), k.stride(1), k.stride(2))),
-                                  _l.i64x3((v.stride(0), v.stride(1), v.stride(2))),
-                                  _l.i64x3((out.stride(0), out.stride(1), out.stride(2))),
-                                  float(softmax_scale), _DT[q.dtype], frame_tokens, ws.data_ptr(), need, _stream())
-    _l.check(rc, "attn_fwd_wide")
+    _l.check(lib.apexmi_attn_fwd_wide(*common, ws.data_ptr(), need, _stream()), "attn_fwd_wide")
     return out.permute(0, 2, 1, 3)
 
 
@@ -1488,11 +1413,7 @@ def attention_bias(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int
         _l.check(rc, "attn_fwd_bias_f32")
         return out
     need = lib.apexmi_attn_bias_workspace_bytes(heads, Sq, Sk, D)
-    key = (q.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        _ws_cache[key] = ws
+    ws = _workspace((q.device.index, _stream()), q.device, need)
     rc = lib.apexmi_attn_fwd_bias(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
                                   out.data_ptr(), out.stride(0), heads, hkv, Sq, Sk, D, float(softmax_scale), _ptr(bias),
                                   _ptr(keep), _ptr(seg), 1 if causal else 0, ws.data_ptr(), need, _stream())
