@@ -111,6 +111,15 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(
     }
 }
 
+// s + a * a with the product rounded on its own, never contracted to an fma.  The square of a float is inexact, so the two forms
+// give different sums; the kernels that are documented to agree bit for bit on float rows (ln_modulate_wave_kernel and
+// qk_rms_rope_rows_kernel) square through this, so that their agreement is not the compiler's choice.
+APEXMI_DEVICE float add_square_unfused(float s, float a) {
+#pragma clang fp contract(off)
+    const float p = a * a;
+    return s + p;
+}
+
 // Wave-per-row variant for C = 64 * 8 * NCH (3072, 3584, 5120): a lane owns NCH 16-byte chunks, the two
 // statistics are wave reductions (no LDS, no barrier), four rows per workgroup.  Same arithmetic order per lane
 // as the block kernel's per-thread part; the cross-lane sums differ in shape, both are f32.
@@ -154,7 +163,8 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float d = v[r][it][j] - mean;
-                sq += d * d;
+                if constexpr (sizeof(T) == 4) sq = add_square_unfused(sq, d);
+                else sq += d * d;
             }
         const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
         TO* op = out + (int64_t)row * ldo;
@@ -452,7 +462,10 @@ __global__ __launch_bounds__(256) void qk_rms_rope_rows_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float d = x[it][j] - 0.0f;
-            sq += d * d;
+            // as ln_modulate_wave_kernel: left to the compiler, most of these products were fused here and none there, and the f32
+            // form missed the documented bit identity by one ulp of rstd on a few rows in a hundred (a bf16 x squares exactly)
+            if constexpr (sizeof(T) == 4) sq = add_square_unfused(sq, d);
+            else sq += d * d;
         }
     const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
     const int srow = row0 + s;
@@ -998,7 +1011,7 @@ extern "C" int apexmi_ln_modulate(const void* x, int64_t ldx, void* out, int64_t
                                nullptr, stream_);
 }
 
-int g_ln_wave = 1;  // apexmi_tune_set("ln.wave", 0/1): wave-per-row kernel for C in {3072, 3584, 5120}
+int g_ln_wave = 1;  // apexmi_tune_set("ln.wave", 0/1/2) for C in {3072, 3584, 5120}: 0 row-per-workgroup kernel | 1 one row per wave | 2 two rows per wave (bf16 x; bit-identical to 1)
 void apexmi_set_ln_wave(int v) { g_ln_wave = v; }
 
 template <typename T, typename TO = T>
@@ -1203,7 +1216,9 @@ static int qk_rms_rope_rows_impl(const void* q, const void* k, const void* v, in
                        ((uintptr_t)wq % 16) == 0 && ((uintptr_t)wk % 16) == 0 && ((uintptr_t)rope % 16) == 0,
                    "qk_rms_rope_rows: operands must be 16-byte aligned");
     APEXMI_REQUIRE(row0 >= 0 && row0 + S <= S_out && (rope_mode == APEXMI_ROPE_NONE || rope != nullptr), "qk_rms_rope_rows: rows / rope");
-    APEXMI_REQUIRE(vt == nullptr || (Skp >= row0 + S && Skp % 8 == 0 && row0 % 8 == 0), "qk_rms_rope_rows: V^T needs Skp >= rows, 8-aligned");
+    // the V^T workgroups write whole 64-key tiles (v_transpose_body), up to column row0 + round_up(S, 64): as v_transpose_impl
+    APEXMI_REQUIRE(vt == nullptr || (row0 % 64 == 0 && Skp % 64 == 0 && row0 + ((S + 63) / 64) * 64 <= Skp),
+                   "qk_rms_rope_rows: V^T row0=%d S=%d Skp=%d not tile aligned", row0, S, Skp);
     const int nst = (S + 63) / 64;
     const int nb_v = vt ? nst * H : 0;
     const int64_t units = (int64_t)S * (k ? 2 : 1);

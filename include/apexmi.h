@@ -399,7 +399,8 @@ int apexmi_attn_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk,
  *   "attn.w64"     1 (default): main launch of >= 140 workgroups on the one-wave-per-SIMD kernel, first-tile maximum + checked
  *                  fallback (apexmi_attn_w64_fallbacks) | 8: the same kernel with the per-tile running maximum | 0: 4-cluster kernel
  *   "qk.group"     1: q/k norm + RoPE four heads per lane group with the V transpose in the same launch | 2: without | 0: one head
- *   "ln.wave"      1: wave-per-row LayerNorm kernel for C in {3072, 3584, 5120}
+ *   "ln.wave"      LayerNorm kernel for C in {3072, 3584, 5120}.  1: one row per wave | 2: two rows per wave (bf16 x only; same bits as 1)
+ *                  | 0: the row-per-workgroup kernel of every other width
  * Returns non-zero for an unknown key. */
 int apexmi_tune_set(const char* key, int value);
 
@@ -446,7 +447,8 @@ int apexmi_ln_modulate2_f32in(const float* x, int64_t ldx, void* out, int64_t ld
  * transformer/efficiency/mod.py:24-35; apply_wan_rope_inplace, transformer/efficiency/ops.py:112-160): RMSNorm over ALL H * 128
  * channels of every q and k row (affine weights wq / wk of H * 128 elements, bf16), the result rounded to the storage type where
  * the reference's in-place norm writes it, rotary embedding (rope_mode as apexmi_qkv_prepare), layout [H, S_out, 128]; v (optional)
- * leaves transposed [H, 128, Skp].  Equals apexmi_ln_modulate2(rms) on q, on k, then apexmi_qkv_prepare without norm weights, bit
+ * leaves transposed [H, 128, Skp] in whole 64-key tiles (row0 % 64 == 0, Skp % 64 == 0, row0 + round_up(S, 64) <= Skp; columns
+ * [row0 + S, row0 + round_up(S, 64)) are zero-filled).  Equals apexmi_ln_modulate2(rms) on q, on k, then apexmi_qkv_prepare without norm weights, bit
  * for bit, in one read of the projection.  k / ko and v / vt may be NULL together (the query side of cross-attention).
  * H * 128 in {3072, 5120} (the widths whose stand-alone norm uses the same one-wave-per-row reduction).  _f32: float q / k / v / outputs (f32-storage verification mode). */
 int apexmi_qk_rms_rope_rows(const void* q, const void* k, const void* v, int64_t ld_in, int S, int H, const void* wq, const void* wk,
