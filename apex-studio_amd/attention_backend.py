@@ -1,4 +1,4 @@
-"""The "hip_mfma", "hip_mfma_sdpa", "hip_mfma_window" and "hip_mfma_varlen" attention backends — B-op plug-in point.
+"""The "hip_mfma", "hip_mfma_sdpa", "hip_mfma_window", "hip_mfma_varlen" and "hip_mfma_band" attention backends — B-op plug-in point.
 
 Honours the calling convention of every backend in the reference's attention_register
 (apps/api/src/attention/functions.py:84, e.g. `sdpa` :338-377):
@@ -36,6 +36,12 @@ job of the reference's "sdpa_varlen" / "flash_varlen": the reference calling con
 layout it was given ([T, Hq, D], or [1, Hq, T, D]; lse [Hq, T] or [1, Hq, T]).  One launch, no host sync: every sequence attends
 its own keys only.  is_causal is top-left aligned per sequence.  attn_mask, dropout, a batch dimension other than 1 and missing
 cu_seqlens / max_seqlen raise ApexMIError; nothing falls back to a per-sequence loop.
+
+"hip_mfma_band" (KEY_BAND) is attention over per-block key bands (ops.attention_band): the reference calling
+convention plus `band_plan=` (an ops.BandPlan from ops.band_plan / ops.frame_band_plan) in **kwargs.  Every block of 256 query
+rows attends one contiguous key range, on the dense large-attention kernel: bf16, D = 128.  An opt-in approximation of the
+caller's choosing, like the window.  attn_mask, is_causal, dropout and a missing plan raise; nothing falls back to dense
+attention.  Registered on request (register(..., band=True)).
 """
 from __future__ import annotations
 
@@ -48,6 +54,7 @@ KEY = "hip_mfma"
 KEY_SDPA = "hip_mfma_sdpa"
 KEY_WINDOW = "hip_mfma_window"
 KEY_VARLEN = "hip_mfma_varlen"
+KEY_BAND = "hip_mfma_band"
 
 
 def hip_mfma(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False,
@@ -128,6 +135,20 @@ def hip_mfma_varlen(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: 
     return res[None].permute(0, 2, 1, 3)
 
 
+def hip_mfma_band(q, k, v, attn_mask=None, dropout_p: float = 0.0, is_causal: bool = False, softmax_scale=None, band_plan=None,
+                  **kwargs):
+    if dropout_p:
+        raise ApexMIError("hip_mfma_band: dropout is not supported (inference only)")
+    if is_causal:
+        raise ApexMIError("hip_mfma_band: causal attention is not supported (use hip_mfma_sdpa)")
+    if attn_mask is not None:
+        raise ApexMIError("hip_mfma_band: attn_mask is not supported next to a band plan (use hip_mfma_sdpa with a mask)")
+    if band_plan is None:
+        raise ApexMIError("hip_mfma_band: band_plan= (ops.band_plan(...) / ops.frame_band_plan(...)) is required; there is no "
+                          "dense fallback")
+    return ops.attention_band(q, k, v, band_plan, softmax_scale=softmax_scale)
+
+
 def _key_keep_mask(attn_mask: torch.Tensor, B: int, Sk: int) -> torch.Tensor:
     """attn_mask (bool keep-mask, or additive: finite-and-not-hugely-negative = keep) -> bool [B, Sk]; raises unless the mask
     is constant along the head and query dimensions."""
@@ -157,16 +178,18 @@ def available() -> bool:
     return torch.cuda.is_available()
 
 
-def register(attention_register, set_default: bool = False, overwrite: bool = True, varlen: bool = False):
+def register(attention_register, set_default: bool = False, overwrite: bool = True, varlen: bool = False, band: bool = False):
     """Register under KEY, KEY_SDPA and KEY_WINDOW in the given FunctionRegister (the reference's, or register.attention_register);
     set_default makes KEY the default.  varlen=True adds KEY_VARLEN next to them: the key takes packed operands and cu_seqlens,
-    so a manifest asks for it."""
+    so a manifest asks for it.  band=True adds KEY_BAND in the same way: the key needs a band plan."""
     ok = available()
     attention_register(KEY, overwrite=overwrite, available=ok)(hip_mfma)
     attention_register(KEY_SDPA, overwrite=overwrite, available=ok)(hip_mfma_sdpa)
     attention_register(KEY_WINDOW, overwrite=overwrite, available=ok)(hip_mfma_window)
     if varlen:
         attention_register(KEY_VARLEN, overwrite=overwrite, available=ok)(hip_mfma_varlen)
+    if band:
+        attention_register(KEY_BAND, overwrite=overwrite, available=ok)(hip_mfma_band)
     if set_default:
         attention_register.set_default(KEY)
     return attention_register

@@ -9,6 +9,7 @@
 // products and the rounding rule of the online softmax are attn_tile.h's.  V arrives pre-transposed ([B,H,128,Skp], produced by
 // apexmi_qkv_prepare / apexmi_v_transpose), K and V^T tiles are staged by 16-byte global_load_lds into a double-buffered 64 KiB
 // LDS image.  Workgroup ids are remapped so all query blocks of one (batch, head) run on one XCD and share its L2 copy of K / V^T.
+#include "attn_host.h"
 #include "attn_tile.h"
 
 // Per-workgroup timeline of the shipped flash kernel (tools/attn_tile_trace.py): compiled in only with -DAPEXMI_ATTN_TRACE=1 into a side
@@ -728,6 +729,17 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_d128_c4_kernel(
 #include "attn_w64_kernel.h"
 #undef W64_NAME
 #undef W64_BODY
+// per-block key bands (apexmi_attn_fwd_prepared_band): the shipped pair of loops behind a shell that reads the
+// workgroup's key range [lo, hi) from a plan and points the two descriptors, nt and rem at it (attn_w64_kernel.h, W64_BANDS)
+#define W64_NAME attn_fwd_d128_w64_band_kernel
+#define W64_BODY "attn_w64_first.inc"
+#define W64_FALLBACK "attn_w64_body.inc"
+#define W64_BANDS 1
+#include "attn_w64_kernel.h"
+#undef W64_NAME
+#undef W64_BODY
+#undef W64_FALLBACK
+#undef W64_BANDS
 #ifdef APEXMI_ATTN_W64_ABLATE   // timing-only variants of the loop (WRONG results): tools/attn_w64_ablate.sh
 // attn.w64 = 9: the shipped loops behind round 5's 8-byte epilogue stores (A/B of the 16-byte stores)
 #define W64_NAME attn_fwd_d128_w64x2_kernel
@@ -1515,6 +1527,91 @@ static int attn_fwd_prepared_impl(const void* q, const void* k, const void* vt, 
                        (const bf16_t*)k, (const bf16_t*)vt, (bf16_t*)out, H, Sq, Sk, Skp, nqb, total,
                        o_strides[0], o_strides[1], o_strides[2], c);
     return apexmi_check_launch("attn_fwd_d128");
+}
+
+// ---- per-block key bands on the w64 kernel --------------------------------------------------------------
+// Always the band kernel, one 256-row workgroup per query block: no 4-wave form, no tail split.
+extern "C" int apexmi_attn_fwd_prepared_band(const void* q, const void* k, const void* vt, void* out, int B, int H, int Sq,
+                                             int Sk, int Skp, const int64_t o_strides[3], const void* bands, int Hb,
+                                             float softmax_scale, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(q && k && vt && out && o_strides, "attn_fwd_prepared_band: null operand");
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attn_fwd_prepared_band: empty problem");
+    APEXMI_REQUIRE(Skp % KV == 0 && Skp >= Sk, "attn_fwd_prepared_band: Skp=%d must be Sk=%d rounded up to 64", Skp, Sk);
+    APEXMI_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)vt % 16) == 0 &&
+                       ((uintptr_t)out % 16) == 0,
+                   "attn_fwd_prepared_band: operands must be 16-byte aligned");
+    APEXMI_REQUIRE(o_strides[0] % 8 == 0 && o_strides[1] % 8 == 0 && o_strides[2] % 8 == 0,
+                   "attn_fwd_prepared_band: output strides must be multiples of 8 elements");
+    // the descriptors hold byte ranges in 32 bits: 128 x Skp x 2 bytes of V^T
+    APEXMI_REQUIRE(Sk <= (1 << 20) && Skp <= (1 << 20) + KV, "attn_fwd_prepared_band: Sk=%d above 1048576 keys", Sk);
+    const int nqb = (Sq + 255) / 256;
+    APEXMI_REQUIRE((int64_t)nqb * H * B < (int64_t)1 << 31, "attn_fwd_prepared_band: too many query blocks");
+    APEXMI_REQUIRE(bands && ((uintptr_t)bands % 8) == 0, "attn_fwd_prepared_band: null or misaligned band plan (int32 pairs, 8-byte aligned)");
+    APEXMI_REQUIRE(Hb == 1 || Hb == H, "attn_fwd_prepared_band: plan of %d heads for %d heads (1 or H)", Hb, H);
+    const int total = nqb * H * B;
+    // the work is not known on the host (the plan lives on the device): the profile counts the dense launch's
+    ApexmiProfScope prof(1, stream, 4.0 * B * H * (double)Sq * Sk * HD, 2.0 * B * H * HD * (2.0 * Sq + 2.0 * Sk));
+    const int lds = 4 * ATT_STAGE + 16;              // the rings + the fallback vote's word
+    static uint64_t attr_done = 0;
+    APEXMI_SET_ATTR_ONCE(attr_done, (void)hipFuncSetAttribute((const void*)attn_fwd_d128_w64_band_kernel,
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(attn_fwd_d128_w64_band_kernel, dim3(total), dim3(256), lds, stream, (const bf16_t*)q, (const bf16_t*)k,
+                       (const bf16_t*)vt, (bf16_t*)out, H, Sq, Sk, Skp, nqb, total, o_strides[0], o_strides[1], o_strides[2],
+                       softmax_scale * LOG2E, (const int*)bands, Hb == 1 ? 0 : nqb);
+    return apexmi_check_launch("attn_fwd_d128_w64_band");
+}
+
+extern "C" size_t apexmi_attn_band_workspace_bytes(int B, int H, int Sq, int Sk) {
+    if (B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0) return 0;
+    const size_t skp = (size_t)((Sk + KV - 1) / KV) * KV;
+    // V^T plus packed copies of q and k (used only when the caller's views are not packed)
+    return (size_t)B * H * HD * skp * 2 + (size_t)B * H * ((size_t)Sq + Sk) * HD * 2;
+}
+
+int apexmi_pack_bhsd(const void* x, const int64_t* st, int B, int H, int S, int D, void* out, hipStream_t stream);
+
+extern "C" int apexmi_attn_fwd_band(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+                                    const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                                    const int64_t o_strides[3], const void* bands, int Hb, float softmax_scale, int dtype,
+                                    void* workspace, size_t workspace_bytes, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* who = "attn_fwd_band";
+    if (int rc = require_operands(who, q, k, v, out, q_strides, k_strides, v_strides, o_strides)) return rc;
+    APEXMI_REQUIRE(B > 0 && H > 0 && Sq > 0 && Sk > 0, "attn_fwd_band: empty problem (B=%d H=%d Sq=%d Sk=%d)", B, H, Sq, Sk);
+    if (int rc = require_head_dim(who, D, D == HD, "128 only: the band kernel is the D = 128 flash kernel")) return rc;
+    APEXMI_REQUIRE(dtype == APEXMI_BF16, "attn_fwd_band: dtype %d unsupported (bf16 only)", dtype);
+    APEXMI_REQUIRE(q_strides[2] >= D && k_strides[2] >= D && v_strides[2] >= D,
+                   "attn_fwd_band: row strides below the head dim %d (rows must not overlap)", D);
+    if (int rc = require_workspace(who, workspace, workspace_bytes, apexmi_attn_band_workspace_bytes(B, H, Sq, Sk), true)) return rc;
+    const int skp = ((Sk + KV - 1) / KV) * KV;
+    char* ws = (char*)workspace;
+    void* vt = ws;
+    ws += (size_t)B * H * HD * skp * 2;
+    const void* qp = q;
+    const void* kp = k;
+    // the other refusals (plan, output alignment, limits) are the prepared entry's: nothing is launched before they pass
+    APEXMI_REQUIRE(bands && ((uintptr_t)bands % 8) == 0, "attn_fwd_band: null or misaligned band plan (int32 pairs, 8-byte aligned)");
+    APEXMI_REQUIRE(Hb == 1 || Hb == H, "attn_fwd_band: plan of %d heads for %d heads (1 or H)", Hb, H);
+    APEXMI_REQUIRE(((uintptr_t)out % 16) == 0 && o_strides[0] % 8 == 0 && o_strides[1] % 8 == 0 && o_strides[2] % 8 == 0,
+                   "attn_fwd_band: out must be 16-byte aligned with strides multiples of 8 elements");
+    APEXMI_REQUIRE(Sk <= (1 << 20), "attn_fwd_band: Sk=%d above 1048576 keys", Sk);
+    APEXMI_REQUIRE((int64_t)((Sq + 255) / 256) * H * B < (int64_t)1 << 31, "attn_fwd_band: too many query blocks");
+    if (!packed_bhsd(q_strides, H, Sq, D) || ((uintptr_t)q % 16) != 0) {
+        if (int rc = apexmi_pack_bhsd(q, q_strides, B, H, Sq, D, ws, stream)) return rc;
+        qp = ws;
+    }
+    ws += (size_t)B * H * Sq * HD * 2;
+    if (!packed_bhsd(k_strides, H, Sk, D) || ((uintptr_t)k % 16) != 0) {
+        if (int rc = apexmi_pack_bhsd(k, k_strides, B, H, Sk, D, ws, stream)) return rc;
+        kp = ws;
+    }
+    for (int b = 0; b < B; ++b) {
+        const bf16_t* vb = (const bf16_t*)v + b * v_strides[0];
+        bf16_t* vtb = (bf16_t*)vt + (size_t)b * H * HD * skp;
+        if (int rc = apexmi_v_transpose(vb, v_strides[1], v_strides[2], Sk, H, D, vtb, skp, 0, stream)) return rc;
+    }
+    return apexmi_attn_fwd_prepared_band(qp, kp, vt, out, B, H, Sq, Sk, skp, o_strides, bands, Hb, softmax_scale, stream_);
 }
 
 void apexmi_set_attn_waves(int v) { g_attn_waves = v; }

@@ -11,10 +11,19 @@
 // and a workgroup in which any row fails (scores that tower > 41 nats above the first 64 keys' best, inf, NaN) runs the
 // W64_FALLBACK loop from scratch.  The workgroups' vote goes through
 // one LDS word behind the rings (the launch allocates 4 * ATT_STAGE + 16 bytes); d_attn_w64_fallbacks counts the re-runs.
+// W64_BANDS (optional) = per-block key bands (attn_fwd_d128_w64_band_kernel): two more arguments, the plan as
+// int32 pairs {lo, hi} [Hb, nqb] and its head stride in pairs (0: every head shares the bands, nqb: one set per head).  The
+// workgroup attends the keys [lo, hi) of its (batch, head): the same loop on a K descriptor that starts at key lo and spans
+// n = hi - lo keys, a V^T descriptor that starts at column lo (row stride still Skp), nt = ceil(n / 64) tiles and rem = n & 63.
+// The pair is clamped the way the varlen kernel clamps cu_seqlens, so a wrong plan truncates and never reads past an operand.
 __global__ __launch_bounds__(256, 1) void W64_NAME(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ Vt,
     bf16_t* __restrict__ O, int H, int Sq, int Sk, int Skp, int nqb, int total, int64_t o_sb,
-    int64_t o_ss, int64_t o_sh, float scale_log2e) {
+    int64_t o_ss, int64_t o_sh, float scale_log2e
+#ifdef W64_BANDS
+    , const int* __restrict__ bands, int band_hs
+#endif
+    ) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -22,10 +31,26 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
     const int s = xcd_remap(blockIdx.x, total);
     const int hb = s / nqb, qb = s % nqb;
     const bf16_t* Qp = Q + (int64_t)hb * Sq * HD;
+#ifdef W64_BANDS
+#ifdef W64_DMA_WAVE
+#error "W64_BANDS is written for the shipped piece order, not for dma=wave"
+#endif
+    // the block's pair, wave-uniform, then clamped: lo a multiple of 64 below Sk, 1 <= n <= Sk - lo
+    const int* bp = bands + 2 * ((hb % H) * band_hs + qb);
+    int klo = __builtin_amdgcn_readfirstlane(bp[0]), khi = __builtin_amdgcn_readfirstlane(bp[1]);
+    klo = min(max(klo, 0) & ~(KV - 1), (Sk - 1) & ~(KV - 1));
+    const int kn = min(max(min(max(khi, 0), Sk) - klo, 1), Sk - klo);
+    const bf16_t* Kp = K + ((int64_t)hb * Sk + klo) * HD;
+    const bf16_t* Vp = Vt + (int64_t)hb * HD * Skp + klo;
+    const int nt = __builtin_amdgcn_readfirstlane((kn + KV - 1) / KV);
+    const int rem = __builtin_amdgcn_readfirstlane(kn & (KV - 1));
+    const uint32_t k_bytes = (uint32_t)(kn * (HD * 2)), v_bytes = (uint32_t)(((int64_t)HD * Skp - klo) * 2);
+#else
     const bf16_t* Kp = K + (int64_t)hb * Sk * HD;
     const bf16_t* Vp = Vt + (int64_t)hb * HD * Skp;
     const int nt = __builtin_amdgcn_readfirstlane((Sk + KV - 1) / KV);
     const int rem = __builtin_amdgcn_readfirstlane(Sk & (KV - 1));
+#endif
     const int row_a = qb * 256 + wave * 64 + l31;
     const bf16_t* qa = Qp + (int64_t)min(row_a, Sq - 1) * HD + hi * 8;
     const bf16_t* qbp = Qp + (int64_t)min(row_a + 32, Sq - 1) * HD + hi * 8;
@@ -34,8 +59,13 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
     // (lane >> 4) <- keys 16 i + perm32(4 wave + (lane >> 4)), chunk (lane & 15) ^ row; V^T piece i = rows (d) 32 i + 8 wave +
     // (lane >> 3), chunk (lane & 7) ^ ((row >> 1) & 7)
     const uint64_t kb = (uint64_t)Kp, vb = (uint64_t)Vp;
+#ifdef W64_BANDS
+    u32x4 rk = {(uint32_t)kb, (uint32_t)(kb >> 32) & 0xffffu, k_bytes, 0x00020000u};
+    u32x4 rv = {(uint32_t)vb, (uint32_t)(vb >> 32) & 0xffffu, v_bytes, 0x00020000u};
+#else
     u32x4 rk = {(uint32_t)kb, (uint32_t)(kb >> 32) & 0xffffu, (uint32_t)(Sk * (HD * 2)), 0x00020000u};
     u32x4 rv = {(uint32_t)vb, (uint32_t)(vb >> 32) & 0xffffu, (uint32_t)((int64_t)HD * Skp * 2), 0x00020000u};
+#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         rk[j] = __builtin_amdgcn_readfirstlane(rk[j]);

@@ -24,7 +24,8 @@ class WanT2VEngine(EngineLoraMixin):
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
-                 residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False):
+                 residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
+                 attention_band: Optional[int] = None):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -41,6 +42,12 @@ class WanT2VEngine(EngineLoraMixin):
         if attention_window is not None:
             for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
                 tr.set_attention_window(self.attention_window)
+        # frames: both experts' self-attention stays inside per-block key bands of that temporal radius (`set_attention_band`,
+        # an opt-in approximation, exclusive with the window); None = dense
+        self.attention_band = attention_band
+        if attention_band is not None:
+            for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
+                tr.set_attention_band(attention_band)
         # resident fp8 block weights multiply as fp8 (`set_fp8_compute`, DESIGN.md §3.6: an opt-in approximation; needs a
         # keep_fp8=True load of both experts); False = dequantise per call and multiply in bf16
         self.fp8_compute = bool(fp8_compute)
@@ -237,10 +244,12 @@ class WanI2VEngine(WanT2VEngine):
     def __init__(self, high_noise_transformer, low_noise_transformer=None, vae=None,
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
-                 residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False):
+                 residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
+                 attention_band: Optional[int] = None):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
                          vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
-                         attention_window=attention_window, fp8_compute=fp8_compute)
+                         attention_window=attention_window, fp8_compute=fp8_compute,
+                         attention_band=attention_band)
         self.image_encoder = image_encoder
 
     @property

@@ -55,6 +55,10 @@ SIGNATURES = {
                                                                                         C.c_float, C.c_int, vp, C.c_size_t, vp]),
     "apexmi_attn_fwd_prepared_window": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [c_i64p, vp, vp, C.c_int, C.c_int, C.c_int, vp,
                                                                                      C.c_float, vp]),
+    "apexmi_attn_fwd_prepared_band": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [c_i64p, vp, C.c_int, C.c_float, vp]),
+    "apexmi_attn_band_workspace_bytes": (C.c_size_t, [C.c_int] * 4),
+    "apexmi_attn_fwd_band": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 5 + [c_i64p] * 4 + [vp, C.c_int, C.c_float, C.c_int, vp,
+                                                                                      C.c_size_t, vp]),
     "apexmi_attn_fwd_prepared_dual": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int,
                                                 C.c_int, c_i64p, C.c_float, vp]),
     "apexmi_gemm_bf16": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,

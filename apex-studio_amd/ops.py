@@ -6,6 +6,7 @@ libapex_mi355.so.  Every wrapper refuses CPU tensors: the product path has no fa
 from __future__ import annotations
 
 import math
+import operator
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -45,7 +46,7 @@ def _rows16(t: torch.Tensor) -> torch.Tensor:
 
 
 # attention workspaces, one per key: (tag, device index, stream) with the tag of a kernel family ("masked" serves the masked and
-# the window wrappers, "varlen", "wide", "prep"), (device index, stream) for attention / attention_framecausal / attention_bias
+# the window wrappers, "varlen", "wide", "prep", "band"), (device index, stream) for attention / attention_framecausal / attention_bias
 _ws_cache: dict = {}
 
 
@@ -898,6 +899,33 @@ def attention_prepared_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor
     return out
 
 
+def attention_prepared_band(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, Sk: int,
+                            plan: "BandPlan", scale: Optional[float] = None) -> torch.Tensor:
+    """attention_prepared restricted to the per-block key bands of `plan` (band_plan / frame_band_plan): q [B,H,Sq,128],
+    k [B,H,Sk,128], vt [B,H,128,Skp] packed bf16; out [B,Sq,H,128] (strided ok).  Every 256-row query block attends the keys
+    [lo, hi) of its band; bit-identical, block by block, to attention_prepared on the large-attention kernel over that block's
+    rows and the key slice.  bf16 only (the f32-storage verification mode has no band kernel).  No host synchronisation."""
+    _req(q, None, "attention_band.q")
+    if q.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"attention_prepared_band: bf16 operands only, got {q.dtype} (the f32-storage verification mode "
+                             "has no band attention)")
+    for t_ in (k, vt, out):
+        _req(t_, torch.bfloat16, "attention_band operand")
+    B, H, Sq, D = q.shape
+    assert D == 128 and q.is_contiguous() and k.is_contiguous() and vt.is_contiguous()
+    assert k.shape == (B, H, Sk, D) and vt.shape[:3] == (B, H, D) and vt.shape[3] >= (Sk + 63) // 64 * 64
+    assert out.shape == (B, Sq, H, D) and out.stride(3) == 1
+    if not isinstance(plan, BandPlan):
+        raise _l.ApexMIError(f"attention_prepared_band: plan must be an ops.BandPlan (ops.band_plan), got {type(plan).__name__}")
+    plan.check(Sq, Sk, H, q.device, "attention_prepared_band")
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    rc = _l.load().apexmi_attn_fwd_prepared_band(q.data_ptr(), k.data_ptr(), vt.data_ptr(), out.data_ptr(), B, H, Sq, Sk,
+                                                 vt.shape[3], _st(out), plan.bands.data_ptr(), plan.Hb, float(scale), _stream())
+    _l.check(rc, "attn_fwd_prepared_band")
+    return out
+
+
 def attention_prepared_dual(q: torch.Tensor, k_t: torch.Tensor, vt_t: torch.Tensor, Sk_t: int,
                             k_i: Optional[torch.Tensor], vt_i: Optional[torch.Tensor], Sk_i: int, out: torch.Tensor,
                             scale: Optional[float] = None) -> torch.Tensor:
@@ -1288,6 +1316,167 @@ def attention_window(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, plan: Wi
                                     plan.q_coords.data_ptr(), plan.k_coords.data_ptr(), *plan.radius,
                                     plan.block_map.data_ptr(), float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need, _stream())
     _l.check(rc, "attn_fwd_window")
+    return out.permute(0, 2, 1, 3)
+
+
+class BandPlan:
+    """Per-block key bands, ready to launch (band_plan / frame_band_plan): query rows in blocks of 256 counted from row 0 of each
+    (batch, head), block b attends the keys [lo[b], hi[b]).  `bands` is the device copy, int32 [Hb, nqb, 2] ({lo, hi} pairs),
+    uploaded once; `lo` / `hi` are the host copies [Hb, nqb] (lists of lists) behind dense_mask() and kept_fraction.  Hb = 1:
+    every head shares the bands; Hb = H: one set per head.  Batches share the plan."""
+
+    def __init__(self, lo, hi, Sq: int, Sk: int, bands: torch.Tensor):
+        self.lo, self.hi, self.Sq, self.Sk, self.bands = lo, hi, int(Sq), int(Sk), bands
+        self.Hb, self.nqb = len(lo), len(lo[0])
+
+    @property
+    def device(self):
+        return self.bands.device
+
+    @property
+    def kept_fraction(self) -> float:
+        """attended (query, key) pairs over Sq * Sk, mean over the plan's heads (host arithmetic)"""
+        kept = 0
+        for lo_h, hi_h in zip(self.lo, self.hi):
+            for b, (lo, hi) in enumerate(zip(lo_h, hi_h)):
+                kept += (min(256, self.Sq - 256 * b)) * (hi - lo)
+        return kept / (self.Hb * self.Sq * self.Sk)
+
+    def dense_mask(self) -> torch.Tensor:
+        """the bool mask [Hb, Sq, Sk] of the plan (True = attended), on the CPU: tests and small sizes only"""
+        m = torch.zeros((self.Hb, self.Sq, self.Sk), dtype=torch.bool)
+        for h, (lo_h, hi_h) in enumerate(zip(self.lo, self.hi)):
+            for b, (lo, hi) in enumerate(zip(lo_h, hi_h)):
+                m[h, 256 * b:256 * b + 256, lo:hi] = True
+        return m
+
+    def check(self, Sq: int, Sk: int, H: int, device, who: str) -> None:
+        if (Sq, Sk) != (self.Sq, self.Sk):
+            raise _l.ApexMIError(f"{who}: the band plan is for (Sq, Sk) = ({self.Sq}, {self.Sk}), the operands have ({Sq}, {Sk})")
+        if self.Hb not in (1, H):
+            raise _l.ApexMIError(f"{who}: the band plan has bands for {self.Hb} heads, the operands have {H} (1 or H)")
+        if device != self.device:
+            raise _l.ApexMIError(f"{who}: the band plan is on {self.device}, the operands on {device}")
+
+
+def _band_rows(x, name: str):
+    """host integers [nqb] or [H, nqb] (list, tuple, numpy array, CPU integer tensor) -> list of lists of int"""
+    if isinstance(x, torch.Tensor):
+        if x.dtype not in _INT_DTYPES:
+            raise _l.ApexMIError(f"band_plan: {name} must hold integers, got {x.dtype}")
+        if x.is_cuda:
+            raise _l.ApexMIError(f"band_plan: {name} must be a host array (the plan is validated on the host and uploaded once)")
+    x = x.tolist() if hasattr(x, "tolist") else x
+    try:
+        rows = [list(r) for r in x] if len(x) and hasattr(x[0], "__len__") else [list(x)]
+        return [[operator.index(v) for v in r] for r in rows]
+    except TypeError as err:
+        raise _l.ApexMIError(f"band_plan: {name} must be [nqb] or [H, nqb] integers, got {x!r}") from err
+
+
+def band_plan(lo, hi, Sq: int, Sk: int, device=None) -> BandPlan:
+    """Plan of per-block key bands for attention_band / attention_prepared_band: `lo`, `hi` are host integer arrays [nqb] (every
+    head shares the bands) or [H, nqb] (one set per head), nqb = ceil(Sq / 256); every row of query block b (rows 256 b ...) attends
+    exactly the keys lo[b] <= j < hi[b].  Rules, checked here on the host: 0 <= lo < hi <= Sk (no band is empty), lo a multiple of
+    64, hi a multiple of 64 or Sk.  The pairs are uploaded once; every launch only reads them."""
+    Sq, Sk = int(Sq), int(Sk)
+    if Sq < 1 or Sk < 1:
+        raise _l.ApexMIError(f"band_plan: empty problem (Sq={Sq} Sk={Sk})")
+    lo_r, hi_r = _band_rows(lo, "lo"), _band_rows(hi, "hi")
+    nqb = (Sq + 255) // 256
+    if len(lo_r) != len(hi_r) or any(len(a) != len(b) for a, b in zip(lo_r, hi_r)):
+        raise _l.ApexMIError(f"band_plan: lo and hi differ in shape ({len(lo_r)} x {[len(r) for r in lo_r]} against "
+                             f"{len(hi_r)} x {[len(r) for r in hi_r]})")
+    for r in lo_r:
+        if len(r) != nqb:
+            raise _l.ApexMIError(f"band_plan: {len(r)} bands for {nqb} query blocks of 256 rows (Sq={Sq})")
+    for h, (lo_h, hi_h) in enumerate(zip(lo_r, hi_r)):
+        for b, (a, e) in enumerate(zip(lo_h, hi_h)):
+            if a % 64 != 0:
+                raise _l.ApexMIError(f"band_plan: lo={a} of block {b} (head row {h}) is not a multiple of 64")
+            if e % 64 != 0 and e != Sk:
+                raise _l.ApexMIError(f"band_plan: hi={e} of block {b} (head row {h}) is neither a multiple of 64 nor Sk={Sk}")
+            if not 0 <= a < e <= Sk:
+                raise _l.ApexMIError(f"band_plan: band [{a}, {e}) of block {b} (head row {h}) is empty or outside [0, {Sk})")
+    if device is None:
+        if not torch.cuda.is_available():
+            raise _l.ApexMIError("band_plan: no ROCm device to put the plan on (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    else:
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None and torch.cuda.is_available():
+            dev = torch.device("cuda", torch.cuda.current_device())
+    if dev.type != "cuda":
+        raise _l.ApexMIError(f"band_plan: expected a ROCm device, got {dev} (no CPU fallback)")
+    pairs = torch.tensor([[[a, e] for a, e in zip(lo_h, hi_h)] for lo_h, hi_h in zip(lo_r, hi_r)], dtype=torch.int32)
+    return BandPlan(lo_r, hi_r, Sq, Sk, pairs.to(dev))
+
+
+def frame_bands(frames: int, tokens_per_frame: int, radius: int):
+    """the (lo, hi) lists of frame_band_plan, host arithmetic only"""
+    frames, tpf, radius = int(frames), int(tokens_per_frame), int(radius)
+    if frames < 1 or tpf < 1:
+        raise _l.ApexMIError(f"frame_band_plan: frames={frames} and tokens_per_frame={tpf} must be at least 1")
+    if radius < 0:
+        raise _l.ApexMIError(f"frame_band_plan: radius={radius} must not be negative")
+    S = frames * tpf
+    lo, hi = [], []
+    for b in range((S + 255) // 256):
+        f0, f1 = (256 * b) // tpf, (min(256 * b + 256, S) - 1) // tpf
+        lo.append(max(0, f0 - radius) * tpf // 64 * 64)
+        hi.append(min(S, ((f1 + radius + 1) * tpf + 63) // 64 * 64))
+    return lo, hi
+
+
+def frame_band_plan(frames: int, tokens_per_frame: int, radius: int, device=None) -> BandPlan:
+    """Band plan of a temporal window over FRAME-MAJOR tokens (self-attention, S = frames * tokens_per_frame, token i belongs to
+    frame i // tokens_per_frame; all heads share it).  For the block b that holds rows of the frames f0 ... f1:
+        lo = floor64(max(0, f0 - radius) * tokens_per_frame)
+        hi = min(S, ceil64((f1 + radius + 1) * tokens_per_frame)).
+    This is a SUPERSET of the exact +-radius frame window |frame(i) - frame(j)| <= radius, never less: a band is one range for all
+    256 rows of its block, so it is coarser than the exact window by at most the frames one block straddles (a row of frame f1
+    also sees the frames f0 - radius ... and a row of frame f0 the frames ... f1 + radius) plus less than one 64-key tile at each
+    end (the rounding of lo and hi)."""
+    lo, hi = frame_bands(frames, tokens_per_frame, radius)
+    S = int(frames) * int(tokens_per_frame)
+    return band_plan(lo, hi, S, S, device)
+
+
+def attention_band(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, plan: BandPlan,
+                   softmax_scale: Optional[float] = None) -> torch.Tensor:
+    """softmax(q k^T scale over the keys of the query block's band) v: q [B,H,Sq,128], k / v [B,H,Sk,128] bf16 (permuted views
+    welcome), `plan` an ops.BandPlan (band_plan / frame_band_plan).  Equal to F.scaled_dot_product_attention with
+    plan.dense_mask() as the bool mask; block by block bit-identical to the large-attention kernel on the key slice.  Returns a
+    [B,H,Sq,128] view of a [B,Sq,H,128] buffer, as `attention` does.  No host synchronisation."""
+    _req(q, None, "attention_band.q")
+    _req(k, None, "attention_band.k")
+    _req(v, None, "attention_band.v")
+    if not isinstance(plan, BandPlan):
+        raise _l.ApexMIError(f"attention_band: plan must be an ops.BandPlan (ops.band_plan), got {type(plan).__name__}")
+    if q.dtype != torch.bfloat16 or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise _l.ApexMIError(f"attention_band: dtypes {q.dtype}/{k.dtype}/{v.dtype} unsupported (bf16 only)")
+    if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+        raise _l.ApexMIError("attention_band: q, k, v must be 4-D [B, H, S, D]")
+    B, H, Sq, D = q.shape
+    Sk = k.shape[2]
+    if D != 128:
+        raise _l.ApexMIError(f"attention_band: head dim {D} unsupported (128 only)")
+    if k.shape != (B, H, Sk, D) or v.shape != k.shape:
+        raise _l.ApexMIError(f"attention_band: shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} do not match")
+    if q.numel() == 0 or k.numel() == 0:
+        raise _l.ApexMIError("attention_band: empty problem")
+    plan.check(Sq, Sk, H, q.device, "attention_band")
+    q, k, v = _rows16(q), _rows16(k), _rows16(v)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(D)
+    out = torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    lib = _l.load()
+    need = lib.apexmi_attn_band_workspace_bytes(B, H, Sq, Sk)
+    ws = _workspace(("band", q.device.index, _stream()), q.device, need)
+    rc = lib.apexmi_attn_fwd_band(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), B, H, Sq, Sk, D, _st(q), _st(k), _st(v),
+                                  _st(out), plan.bands.data_ptr(), plan.Hb, float(softmax_scale), _DT[q.dtype], ws.data_ptr(), need,
+                                  _stream())
+    _l.check(rc, "attn_fwd_band")
     return out.permute(0, 2, 1, 3)
 
 

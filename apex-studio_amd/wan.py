@@ -113,7 +113,7 @@ class _Conv3dParams(nn.Module):
 class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "wan.mi355"
-    _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
+    _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans", "_band_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
     _no_split_modules = ["_WanBlock"]
 
     def __init__(self, patch_size: Tuple[int, int, int] = (1, 2, 2), num_attention_heads: int = 40,
@@ -161,6 +161,8 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         self._rope: Dict[Any, torch.Tensor] = {}
         self._attention_window: Optional[Tuple[int, int, int]] = None     # set_attention_window
         self._window_plans: Dict[Any, Any] = {}
+        self._attention_band: Optional[int] = None     # set_attention_band
+        self._band_plans: Dict[Any, Any] = {}
 
     # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, the no-op knobs, ...) ----
     def _anchor(self):
@@ -200,8 +202,27 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
                 raise ValueError(f"wan.mi355: attention window radius must be (frames, rows, cols), got {radius!r}") from err
             if len(radius) != 3 or any(r < 0 for r in radius):
                 raise ValueError(f"wan.mi355: attention window radius must be three non-negative integers, got {radius!r}")
+            if self._attention_band is not None:
+                raise ValueError("wan.mi355: an attention band is set (set_attention_band); clear it (set_attention_band(None)) "
+                                 "before setting a window: the two are mutually exclusive")
         self._attention_window = radius
         self._window_plans = {}
+        return self
+
+    def set_attention_band(self, frames: Optional[int]):
+        """Opt-in approximation: self-attention attends only the keys within about `frames` latent frames of the
+        query, as per-block key bands on the dense large-attention kernel (ops.frame_band_plan over the post-patch token grid,
+        which is frame-major: a superset of the exact +-frames window, coarser by the frames one 256-row block straddles and
+        one 64-key tile at each end); None restores dense attention.  Cross-attention and everything else is untouched.
+        Mutually exclusive with set_attention_window.  Not a quality claim: the caller picks the radius."""
+        if frames is not None:
+            if isinstance(frames, bool) or not isinstance(frames, int) or frames < 0:
+                raise ValueError(f"wan.mi355: attention band radius must be a non-negative integer number of frames, got {frames!r}")
+            if self._attention_window is not None:
+                raise ValueError("wan.mi355: an attention window is set (set_attention_window); clear it "
+                                 "(set_attention_window(None)) before setting a band: the two are mutually exclusive")
+        self._attention_band = frames
+        self._band_plans = {}
         return self
 
     def set_fp8_compute(self, on: bool):
@@ -233,6 +254,14 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         if plan is None:
             plan = ops.window_plan(self._grid_ids(grid), radius=self._attention_window)
             self._window_plans = {key: plan}
+        return plan
+
+    def _band_plan(self, grid):
+        key = (grid, self._attention_band)
+        plan = self._band_plans.get(key)
+        if plan is None:
+            plan = ops.frame_band_plan(grid[0], grid[1] * grid[2], self._attention_band, device=self.device)
+            self._band_plans = {key: plan}
         return plan
 
     def init_synthetic(self, seed: int = 0, std: float = 0.02):
@@ -459,6 +488,12 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
                 raise NotImplementedError("wan.mi355: the f32-storage verification mode has no window attention; clear the "
                                           "window (set_attention_window(None)) or run with bfloat16 storage")
             wplan = self._window_plan(grid)
+        bplan = None
+        if self._attention_band is not None:
+            if self.storage_dtype != torch.bfloat16:
+                raise NotImplementedError("wan.mi355: the f32-storage verification mode has no band attention; clear the "
+                                          "band (set_attention_band(None)) or run with bfloat16 storage")
+            bplan = self._band_plan(grid)
 
         q_in, k_in, v_in = QKV[:, :dim], QKV[:, dim:2 * dim], QKV[:, 2 * dim:]
         att_v = ATT.unflatten(-1, (H, 128)).unsqueeze(0)
@@ -479,7 +514,9 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
                 ops.ln_modulate(k_in, gamma=a1.norm_k.weight, out=k_in, eps=eps, rms=True)
                 ops.qkv_prepare(q_in, k_in, v_in, H, ws.Q[0], ws.K[0], ws.VT[0], rope=rope,
                                 rope_mode=_l.ROPE_INTERLEAVED)
-            if wplan is None:
+            if bplan is not None:
+                ops.attention_prepared_band(ws.Q, ws.K, ws.VT, att_v, S, bplan)
+            elif wplan is None:
                 ops.attention_prepared(ws.Q, ws.K, ws.VT, att_v, S)
             else:
                 ops.attention_prepared_window(ws.Q, ws.K, ws.VT, att_v, S, wplan)

@@ -264,6 +264,32 @@ int apexmi_attn_fwd_prepared_window(const void* q, const void* k, const void* vt
                                     int Skp, const int64_t o_strides[3], const void* q_coords, const void* k_coords, int r0,
                                     int r1, int r2, const void* map, float softmax_scale, apexmi_stream_t stream);
 
+/* Per-block key bands on the large-attention kernel: query rows are cut into blocks of 256 (one workgroup of
+ * attn_fwd_d128_w64_kernel, counted from row 0 of each (batch, head); nqb = ceil(Sq / 256)), and a BAND PLAN gives every block b
+ * one contiguous key range [lo[b], hi[b]): every row of the block attends exactly those keys,
+ *     out = softmax(q k[lo:hi]^T * softmax_scale) v[lo:hi].
+ * `bands` is the plan on the device: int32 pairs {lo, hi}, [Hb, nqb, 2], 8-byte aligned; Hb = 1 (every head shares the bands) or
+ * H (one set per head); batches share the plan.  0 <= lo < hi <= Sk, lo a multiple of 64, hi a multiple of 64 or Sk.  The kernel
+ * clamps every pair to those rules (lo rounded down to 64 and held below Sk, the key count to 1 .. Sk - lo), so a wrong plan
+ * truncates and never reads outside the operands.  A block's result is bit-identical to apexmi_attn_fwd_prepared (on the same
+ * kernel) over that block's query rows and the key slice: same loop, tile order, first-tile maximum and fallback rule
+ * (apexmi_attn_w64_fallbacks counts its re-runs too).  An opt-in approximation of the caller's choosing, e.g. a temporal window
+ * over frame-major video tokens; nothing of size Sq x Sk exists.
+ *   apexmi_attn_fwd_prepared_band  takes the prepared operands of apexmi_attn_fwd_prepared (same alignment rules).  Always the
+ *       band kernel, one workgroup per block: no 4-wave form, no tail split, no workspace.
+ *   apexmi_attn_fwd_band  takes strided q / k / v [B,H,S,D] (element strides b, h, s; last dim contiguous) as apexmi_attn_fwd
+ *       does, bf16 and D = 128 only (anything else is refused); it packs q / k and transposes V into `workspace`
+ *       (>= apexmi_attn_band_workspace_bytes(B, H, Sq, Sk), 16-byte aligned), then makes the launch above.
+ * No call synchronises with the host. */
+int apexmi_attn_fwd_prepared_band(const void* q, const void* k, const void* vt, void* out, int B, int H, int Sq, int Sk,
+                                  int Skp, const int64_t o_strides[3], const void* bands, int Hb, float softmax_scale,
+                                  apexmi_stream_t stream);
+size_t apexmi_attn_band_workspace_bytes(int B, int H, int Sq, int Sk);
+int apexmi_attn_fwd_band(const void* q, const void* k, const void* v, void* out, int B, int H, int Sq, int Sk, int D,
+                         const int64_t q_strides[3], const int64_t k_strides[3], const int64_t v_strides[3],
+                         const int64_t o_strides[3], const void* bands, int Hb, float softmax_scale, int dtype,
+                         void* workspace, size_t workspace_bytes, apexmi_stream_t stream);
+
 /* Two-context cross-attention on prepared operands (bf16, D = 128): the image branch of Wan-2.1 I2V / FLF2V cross-attention,
  * replacing the reference's two attention calls and their sum (R/src/transformer/wan/base/model.py:207, 391-394; diffusers
  * WanAttnProcessor with add_k_proj).  The query attends the text keys and the image keys in two separate softmaxes:
