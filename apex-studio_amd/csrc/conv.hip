@@ -1841,52 +1841,62 @@ __global__ __launch_bounds__(256) void crossfade_kernel(const TS* __restrict__ a
 // GroupNorm(32, C, eps=1e-6) (+ SiLU) (reference vae/auto/model.py:35-41 takes the
 // Decoder from diffusers).  Three deterministic passes: per-block per-channel partial sums, a f64
 // combine into per-group mean / rstd, and the apply (+ affine, + optional SiLU).
+// The sums of x and x^2 are float64 from the first addition: a float squares exactly in float64 and a block's 1024-row chain is
+// then off by < 2^-42, so var = E[x^2] - mean^2 is accurate relative to the SPREAD of the group even when the mean is hundreds
+// of spreads away (f32 sums, which this kernel had, lose mean^2 / var units of the last place there: 1 % of rstd at mean /
+// spread = 400).  The pass stays HBM-bound: 8 conversions and 16 float64 operations per 16-byte load.
 template <typename TS>
-__global__ __launch_bounds__(256) void gn_partial_kernel(const TS* __restrict__ x, float* __restrict__ part,
+__global__ __launch_bounds__(256) void gn_partial_kernel(const TS* __restrict__ x, double* __restrict__ part,
                                                          int64_t P, int C, int rows_per_block) {
-    __shared__ float red[16][256];           // [statistic][thread]: lane-contiguous, no bank conflicts either way
+    __shared__ double red[8][256];           // [channel of the chunk][thread], used for the sums, then again for the squares
     const int ncol = C >> 3;                 // 16-byte chunks per position (<= 64)
     const int col = threadIdx.x % ncol, r0 = threadIdx.x / ncol, rstep = 256 / ncol;
     const int64_t p0 = (int64_t)blockIdx.x * rows_per_block;
-    float s[8], q[8];
+    double s[8], q[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.0f;
-    if (r0 < rstep) {
-        for (int r = r0; r < rows_per_block; r += rstep) {
-            const int64_t p = p0 + r;
-            if (p >= P) break;
-            float v[8];
-            load8<TS>(x + p * C + col * 8, v);
+    for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.0;
+    const int nrow = (int)(P - p0 < rows_per_block ? P - p0 : rows_per_block);      // rows of this block (>= 1)
+    // four rows of the thread in flight per step (the float64 operations hide under the loads); a row past the block's end reads
+    // the step's first row again and counts as zero, so the rows are added in ascending order whatever nrow is
+    for (int r = r0; r < nrow; r += 4 * rstep) {
+        float v[4][8];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int ru = r + u * rstep;
+            load8<TS>(x + (p0 + (ru < nrow ? ru : r)) * C + col * 8, v[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool live = r + u * rstep < nrow;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                s[j] += v[j];
-                q[j] += v[j] * v[j];
+                const double d = live ? (double)v[u][j] : 0.0;
+                s[j] += d;
+                q[j] = fma(d, d, q[j]);
             }
         }
     }
+    double* o = part + ((int64_t)blockIdx.x * C + threadIdx.x * 8) * 2;      // used by the threads < ncol only
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[j][threadIdx.x] = s[j];
-        red[8 + j][threadIdx.x] = q[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < ncol) {                // fixed-order sum over the threads of this column
-        float acc[16];
+    for (int h = 0; h < 2; ++h) {            // h = 0: sums of x, h = 1: sums of x^2
+        if (h) __syncthreads();
 #pragma unroll
-        for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
-        for (int t = threadIdx.x; t < rstep * ncol; t += ncol)
+        for (int j = 0; j < 8; ++j) red[j][threadIdx.x] = h ? q[j] : s[j];
+        __syncthreads();
+        if (threadIdx.x < ncol) {            // fixed-order sum over the threads of this column
+            double acc[8];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j] += red[j][t];
-        float* o = part + ((int64_t)blockIdx.x * C + threadIdx.x * 8) * 2;
+            for (int j = 0; j < 8; ++j) acc[j] = 0.0;
+            for (int t = threadIdx.x; t < rstep * ncol; t += ncol)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            o[2 * j] = acc[j];
-            o[2 * j + 1] = acc[8 + j];
+                for (int j = 0; j < 8; ++j) acc[j] += red[j][t];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[2 * j + h] = acc[j];
         }
     }
 }
 
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, float* __restrict__ stats,
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats,
                                                           int nblk, int C, int G, int64_t P, float eps) {
     // one workgroup per group; thread t sums items t, t + 256, ... of the group's nblk x cpg partials in f64, then a
     // fixed-shape tree in LDS: the result does not depend on scheduling (run-to-run bit-identical)
@@ -1924,20 +1934,21 @@ template <typename TS>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const TS* __restrict__ x, TS* __restrict__ y,
                                                        const float* __restrict__ stats,
                                                        const bf16_t* __restrict__ gamma,
-                                                       const bf16_t* __restrict__ beta, int64_t P, int C, int G,
-                                                       int silu) {
+                                                       const bf16_t* __restrict__ beta, int64_t P, int C,
+                                                       int cpg_shift, int silu) {
+    // C / 8 divides 256, so C, every G that divides it and cpg = C / G = 1 << cpg_shift are powers of two: the chunk of a thread
+    // and the group of a channel are a mask and a shift (eight integer divisions a thread put this pass at the VALU's limit)
     const int ncol = C >> 3;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= P * ncol) return;
-    const int col = (int)(idx % ncol);
-    const int cpg = C / G;
+    const int col = (int)(idx & (ncol - 1));
     float v[8], gm[8], bt[8];
     load8<TS>(x + idx * 8, v);
     unpack8(*(const u32x4*)(gamma + col * 8), gm);
     unpack8(*(const u32x4*)(beta + col * 8), bt);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int g = (col * 8 + j) / cpg;
+        const int g = (col * 8 + j) >> cpg_shift;
         float r = (v[j] - stats[2 * g]) * stats[2 * g + 1] * gm[j] + bt[j];
         if (silu) r = silu_f(r);
         v[j] = r;
@@ -1958,7 +1969,7 @@ void apexmi_set_conv_prof(int half, int v) {
 
 extern "C" size_t apexmi_groupnorm_workspace_bytes(int64_t P, int C) {
     const int nblk = (int)((P + 1023) / 1024);
-    return ((size_t)nblk * C * 2 + 2 * 64) * sizeof(float);
+    return (size_t)nblk * C * 2 * sizeof(double) + 2 * 64 * sizeof(float);     // f64 partials, then (mean, rstd) per group
 }
 
 template <typename TS>
@@ -1972,14 +1983,17 @@ static int groupnorm_cl_impl(const void* x, void* y, const void* gamma, const vo
     APEXMI_REQUIRE(workspace_bytes >= apexmi_groupnorm_workspace_bytes(P, C), "groupnorm_cl: workspace too small");
     const int rows = 1024;
     const int nblk = (int)((P + rows - 1) / rows);
-    float* part = (float*)workspace;
-    float* stats = part + (size_t)nblk * C * 2;
+    APEXMI_REQUIRE(((uintptr_t)workspace % 8) == 0, "groupnorm_cl: workspace must be 8-byte aligned");
+    double* part = (double*)workspace;
+    float* stats = (float*)(part + (size_t)nblk * C * 2);
     ApexmiProfScope prof(3, stream, 0.0, 6.0 * (double)P * C);
     hipLaunchKernelGGL(gn_partial_kernel<TS>, dim3(nblk), dim3(256), 0, stream, (const TS*)x, part, P, C, rows);
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(G), dim3(256), 0, stream, part, stats, nblk, C, G, P, eps);
     const int64_t n = P * (C / 8);
+    const int cpg = C / G;
+    APEXMI_REQUIRE((cpg & (cpg - 1)) == 0, "groupnorm_cl: C / G = %d is no power of two", cpg);      // implied by the above
     hipLaunchKernelGGL(gn_apply_kernel<TS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const TS*)x,
-                       (TS*)y, stats, (const bf16_t*)gamma, (const bf16_t*)beta, P, C, G, silu);
+                       (TS*)y, stats, (const bf16_t*)gamma, (const bf16_t*)beta, P, C, __builtin_ctz((unsigned)cpg), silu);
     return apexmi_check_launch("groupnorm_cl");
 }
 

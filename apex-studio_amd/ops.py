@@ -2192,6 +2192,7 @@ def conv2d_cl_strided(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[to
 def rmsnorm_cl(x: torch.Tensor, gamma: torch.Tensor, silu: bool = False,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _req_act(x, "rmsnorm_cl.x")
+    _req(gamma, torch.bfloat16, "rmsnorm_cl.gamma")      # bf16 weights in both storage modes: a float gamma would be read as bf16
     assert x.is_contiguous() and gamma.is_contiguous() and gamma.numel() == x.shape[-1]
     if out is None:
         out = torch.empty_like(x)
@@ -2248,11 +2249,18 @@ _gn_ws: dict = {}
 
 def groupnorm_cl(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: int = 32, eps: float = 1e-6,
                  silu: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """GroupNorm over a channels-last image [..., C] (all leading dims are positions)."""
+    """GroupNorm (+ SiLU) over ONE channels-last sample [..., C]: every leading dimension is a position of that sample, so the
+    statistics of a group run over all of them (a batch is normalised sample by sample, as AutoencoderKL.decode does).
+    gamma, beta: bf16 [C] on x's device.  The sums of x and x^2 are taken in float64, so the result is accurate relative to the
+    spread of a group however far its mean is from zero (the envelope is in tests/vae_pass_probes.py)."""
     _req_act(x, "groupnorm_cl.x")
     _req(gamma, torch.bfloat16, "groupnorm_cl.gamma")
-    assert x.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
+    _req(beta, torch.bfloat16, "groupnorm_cl.beta")
     Cc = x.shape[-1]
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t.numel() != Cc or t.device != x.device:
+            raise _l.ApexMIError(f"groupnorm_cl.{name}: expected {Cc} values on {x.device}, got {t.numel()} on {t.device}")
+    assert x.is_contiguous() and gamma.is_contiguous() and beta.is_contiguous()
     P = x.numel() // Cc
     if out is None:
         out = torch.empty_like(x)

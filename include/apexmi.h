@@ -625,7 +625,11 @@ int apexmi_upsample2x_cl(const void* x, void* y, int T, int H, int W, int C, ape
 int apexmi_time_interleave_cl(const void* x, void* y, int T, int64_t HW, int C, apexmi_stream_t stream);
 /* GroupNorm(G, C, eps) [+ SiLU] over a channels-last image x [P, C] (P = H*W positions) for the Flux 2-D
  * VAE decoder (diffusers Decoder / ResnetBlock2D; reference vae/auto/model.py:35-41).
- * gamma, beta bf16 [C]; workspace: apexmi_groupnorm_workspace_bytes(P, C) device bytes. */
+ * gamma, beta bf16 [C]; workspace: apexmi_groupnorm_workspace_bytes(P, C) device bytes, 8-byte aligned.  x is ONE sample: the
+ * statistics of a group run over all P positions.  C / 8 must divide 256 (C a power of two, 8 .. 512), G <= 64 divide C.
+ * Three deterministic launches (run-to-run bit-identical): 1024-row blocks of per-channel sums of x and x^2 in float64, a
+ * float64 combine per group into mean and 1 / sqrt(max(E[x^2] - mean^2, 0) + eps) (stored as f32), the apply in f32.  The
+ * result is accurate relative to the spread of a group, whatever its mean (envelope: tests/vae_pass_probes.py). */
 size_t apexmi_groupnorm_workspace_bytes(int64_t P, int C);
 int apexmi_groupnorm_cl(const void* x, void* y, const void* gamma, const void* beta, int64_t P, int C, int G,
                         float eps, int silu, void* workspace, size_t workspace_bytes, apexmi_stream_t stream);
