@@ -7,8 +7,11 @@
 // proj_mlp / proj_out of the single block (:180-182), x_embedder / context_embedder (:439-440),
 // and the gate * y + residual tails of FluxTransformerBlock.forward (:296-297, :305-307).
 //
-// One kernel template, five tilings (gfx950, BK = 64); `apexmi_tune_set("gemm.config", n)` forces one:
+// One kernel template (gemm_tile) in eight tilings (gfx950, BK = 64) and two kernels of their own; `apexmi_tune_set("gemm.config", n)`
+// forces one of the eight, `gemm.large` picks the one the auto path takes for large problems:
 //   1 CFG_128    : 128x128 block, 4 waves (2x2) of 64x64, 2 blocks/CU — small / ragged problems
+//   8 CFG_128E   : 128x128 block on 8 waves (2x4) of 64x32: half the LDS-DMA pieces per wave and K-tile — SHIPPED for the small
+//                  tail problem of a grouped launch (`gemm.tail` = 2)
 //   2 CFG_256    : 256x256 block, 8 waves (2x4) of 128x64, plain double buffer (baseline for A/B)
 //   3 CFG_256P   : ping-pong schedule on v_mfma_f32_32x32x16_bf16: the K-tile is cut into 4 quadrant
 //                  phases of {ds_read sub-tile | barrier | 8 MFMA | barrier}; the M-halves of the block
@@ -21,11 +24,15 @@
 //                  mfma_power.hip); in the Flux step it is 8 % faster per GEMM, 6.5 % per step.
 //   9 CFG_256R   : free-running ring on v_mfma_f32_16x16x32_bf16 (round 4): 32-deep sub-tiles in a four-slot LDS ring, fragments
 //                  read one step ahead into a second register set, two barriers per K-tile — see the SCHED 7 branch.
+//  10 CFG_256R5  : the same ring with five slots (160 KiB, the whole LDS of a CU), pieces four sub-tiles ahead (SCHED 8)
 //   6 CFG_256W   : 4 waves (2x2) of 128x128, one wave per SIMD, accumulators in AGPRs, LDS-DMA through
 //                  buffer_load with scalar piece offsets.  17 % fewer cycles than CFG_256P and faster in
 //                  an isolated loop, but not in the step: the chip answers the denser instruction
 //                  stream with a lower clock (1.30 vs 1.57 GHz under the profiler).  Kept for the record
 //                  and for shapes that are not power-bound.
+//   288 x 192 (gemm_bf16_x288_kernel, `gemm.x288`): the exact-fill tiling of round 5 — measured slower, not shipped, selectable
+//   384 x 256 (gemm_bf16_x384_kernel, `gemm.x384`): fewer staged bytes per flop — SHIPPED where the launch is several full rounds
+//                  of tiles (x384_pays), fused q/k/v launches included
 // Both operands are K-contiguous, so A and W tiles are staged identically with 16-byte
 // global_load_lds into a double-buffered LDS image; the XOR swizzle (chunk ^= (row >> 1) & 7: two 128-byte rows share a 256-byte bank
 // row, and a 32-row MFMA fragment read must spread each 16-lane group over all 16 slots) is applied on
@@ -37,39 +44,33 @@
 #include "common.h"
 
 #include <cstring>
-#include <mutex>
-#include <tuple>
 #include <type_traits>
-#include <vector>
 
 namespace {
 
-// Ablation build of the ring schedule (tools/gemm_ring_ablate.sh; WRONG results, timing only): bit 1 no barriers, 2 no vmcnt waits,
-// 4 no LDS-DMA pieces, 8 no fragment reads.  0 in every shipped library.
-#ifndef APEXMI_GEMM_ABLATE
-#define APEXMI_GEMM_ABLATE 0
-#endif
-// Stream-K launches (round 4 experiment, profiles/r04_gemm_streamk_ab.log): compiled in only with -DAPEXMI_GEMM_STREAMK=1
-// (APEXMI_GEMM_STREAMK=1 python -m apex_studio_amd.build).  Correct and deterministic, but 6 .. 40 % SLOWER than the tile launch:
-// the persistent workgroups lose the dispatcher's dynamic load balancing (+8 us per tile even without a split tile) and a split
-// tile's hand-over costs ~15 us.  The shipped library does not contain the persistent path (its kernel allocates scratch).
-// Those figures are from the commit that built it (git log -S APEXMI_GEMM_STREAMK); since the epilogue rewrite later in round 4
-// (one instantiation per activation mode, both residual slabs pre-loaded) the persistent item loop spills 64-191 VGPRs and runs at
-// half the tile launch's rate (profiles/r04_gemm_persistent_probe_b.log) — the build flag is kept for the record, not maintained.
-// 2 (shipped, round 6): the pieces of the 256x256 ping-pong kernel go out in the scalar-base form of global_load_lds; 1: the builtin's
-// 64-bit vector addresses (round 5's form; the A/B arm of profiles/r06_gemm_peel_ab.log)
-#ifndef APEXMI_GEMM_PEEL
-#define APEXMI_GEMM_PEEL 2
-#endif
-#ifndef APEXMI_GEMM_STREAMK
-#define APEXMI_GEMM_STREAMK 0
-#endif
+// Stream-K (round 4: 256 persistent workgroups, the part-filled last round of tiles cut along K) was correct but 6 .. 40 % slower than
+// the tile launch and is gone: profiles/r04_gemm_streamk_ab.log, profiles/r04_gemm_persistent_probe_b.log, git log -S GEMM_STREAMK.
 // Per-workgroup timeline of the shipped schedule (tools/gemm_tile_trace.py, profiles/r04_gemm_tile_trace.log): compiled in only with
 // -DAPEXMI_GEMM_TRACE=1 into a side library; tune keys "gemm.trace_lo" / "gemm.trace_hi" = halves of a device pointer to 8 u64 per
 // workgroup: {HW_ID, XCC_ID, t_entry, t_loop_begin, t_loop_end, t_stores_issued, t_stores_acknowledged} in s_memrealtime ticks (10 ns).
 #ifndef APEXMI_GEMM_TRACE
 #define APEXMI_GEMM_TRACE 0
 #endif
+// Barrier and wait of the ping-pong schedules (SCHED 1, SCHED 5, 288 x 192, 384 x 256).  The sched_barriers keep hipcc from moving
+// anything across the workgroup barrier; PP_SYNC also retires the wave's fragment reads first.  VMCNT(n): at most n of the wave's
+// LDS-DMA pieces still in flight.
+#define PP_BAR()                               \
+    do {                                       \
+        __builtin_amdgcn_sched_barrier(0);     \
+        __builtin_amdgcn_s_barrier();          \
+        __builtin_amdgcn_sched_barrier(0);     \
+    } while (0)
+#define PP_SYNC()                                                                   \
+    do {                                                                            \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                          \
+        PP_BAR();                                                                   \
+    } while (0)
+#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 constexpr int BK = 64;
 constexpr int GROUP_M = 6;   // tiles tall per group: an XCD's 32 concurrent tiles as ~6 x 5.3 (squarer than 8 x 4: fewer panel fetches per
                              // tile; interleaved A/B, profiles/r03_ab_gemm_group_m.log: Flux -0.4 %, Qwen -1.1 %, Wan -0.6 % vs 8)
@@ -119,19 +120,6 @@ struct GemmGroup {
     // EXPERIMENT (tune key gemm.wpacked, tools/gemm_wpacked_ab.py): every W operand of the launch is TILE-MAJOR packed —
     // [N / 256][K / 64][256 rows][64] — so that an LDS-DMA piece (8 rows x 128 B) is 1 KiB contiguous; SCHED 5 only
     int wpacked;
-    // stream-K (round 4; SCHED 5 launches whose last round of 256 tiles is part-filled, `gemm.streamk`): the launch is 256
-    // PERSISTENT workgroups; the sk_r tiles past the last full round are cut along K into 256 equal unit ranges (see
-    // gemm_bf16_kernel), partial sums travel through sk_slab (256 KiB of f32 per workgroup) guarded by sk_flag
-    int sk_r, sk_tfull;
-    float* sk_slab;
-    unsigned* sk_flag;
-};
-// what a call of gemm_tile() does with its accumulators
-enum { TILE_FULL = 0, TILE_WRITER = 1, TILE_OWNER = 2 };
-struct SkCtx {
-    int mode, kt0, kt1;          // K-tile range [kt0, kt1) of this call
-    int cu;                      // this workgroup's slot: WRITER stores slab[cu] and raises flag[cu]
-    int nparts;                  // OWNER: adds slab[cu - 1] .. slab[cu - nparts] (the workgroups holding the tile's earlier K-tiles)
 };
 
 template <int BM_, int BN_, int WM_, int WN_, int SCHED_>
@@ -739,8 +727,45 @@ APEXMI_DEVICE void qkv_epilogue16(f32x4_t (&acc16)[4][MT], const GemmProblem& P,
 #define APEXMI_TRACE_END() do { } while (0)
 #endif
 
+// tile id inside a problem -> tile row pm, tile column pn: groups of group_m tile rows, column by column inside a group
+struct TileCoord {
+    int pm, pn;
+};
+__device__ __forceinline__ TileCoord tile_coord(int s, int nm, int nn, int group_m) {
+    const int width = group_m * nn;
+    const int first_m = (s / width) * group_m;
+    const int gsz = min(nm - first_m, group_m);
+    return TileCoord{first_m + (s % width) % gsz, (s % width) / gsz};
+}
+
+// ---- the scalar-base form of global_load_lds (SCHED 0 and SCHED 5) ----
+// a pointer that is workgroup-uniform, but not provably so for the compiler, pinned to scalar registers
+__device__ __forceinline__ const char* uniform_ptr(const char* p) {
+    const uint64_t u = (uint64_t)p;
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32)), lo = __builtin_amdgcn_readfirstlane((uint32_t)u);
+    return (const char*)(((uint64_t)hi << 32) | lo);
+}
+// One 16-byte-per-lane LDS-DMA piece from `sbase` (SGPR pair) + `voff` (32-bit lane offset) to LDS address `la` (uniform).  hipcc
+// selects the 64-bit vector-address form for the builtin whatever the pointer looks like, hence by hand: M0 = the piece's LDS
+// address, one state between the M0 write and the load.  M0 is on the clobber list so that hipcc's own M0 bookkeeping (it merges
+// and hoists identical M0 initialisations of its LDS-DMA builtins) sees a definition here; clang flags a reserved register on a
+// clobber list, which is the point
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+__device__ __forceinline__ void glds16_s(const char* sbase, uint32_t voff, uint32_t la) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+                 :: "v"(voff), "s"(sbase), "s"(la) : "memory", "m0");
+}
+#pragma clang diagnostic pop
+
+// K-tile range [kt0, kt1) of a tile: always [0, K / BK).  A remnant of stream-K, which handed part ranges to gemm_tile: with the
+// SCHED 5 trip count written as kt1 - kt0 of this struct hipcc emits the instruction streams it emitted then; a plain int, by value
+// or by reference, or a one-member struct, moves the register allocation of the SCHED 5 kernels (and of others) by a few instructions.
+struct KRange {
+    int kt0, kt1;
+};
 template <typename CFG, int EPI>
-__device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s, const SkCtx& sk) {
+__device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s, const KRange& kr) {
     constexpr int BM = CFG::BM, BN = CFG::BN, TM = CFG::TM, TN = CFG::TN;
 
 #if APEXMI_GEMM_TRACE
@@ -748,8 +773,10 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
     if (G.trace != nullptr) tr_in = __builtin_amdgcn_s_memrealtime();
 #endif
     int tid_ = threadIdx.x;
-    // opaque per call: the persistent (stream-K) launch calls this in a loop, and everything derived from the lane id in the
-    // epilogue would otherwise be hoisted out of that loop and held across the K-loop (+40 VGPRs: 160-220 spilled dwords)
+    // opaque: behind this statement the compiler no longer knows that the value is the workitem id (its range, what is uniform in
+    // it), so everything derived from the lane id is computed where the source puts it.  Written for the stream-K item loop, but
+    // the plain launch depends on it too: without this pin and the one on acc16 below, 32 kernels of this file compile differently
+    // and the SCHED 5 / 7 / 8 kernels grow by 120 to 260 instructions.  The effect on time is not measured, so both stay.
     asm volatile("" : "+v"(tid_));
     const int tid = tid_;
     const int lane = tid & 63;
@@ -757,7 +784,7 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
     const int wm = wave / CFG::WN, wn = wave % CFG::WN;
     const int l31 = lane & 31, hi = lane >> 5;
 
-    // ---- tile id -> problem, (pm, pn): XCD-contiguous, grouped GROUP_M tall ----
+    // ---- tile id -> problem, (pm, pn): XCD-contiguous, grouped group_m tall ----
     int gi = 0;
 #pragma unroll
     for (int i = 1; i < MAX_GROUPS; ++i)
@@ -770,13 +797,9 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
         P.C = (bf16_t*)((char*)P.C + z * G.bsC_bytes);
     }
     s -= P.tile0;
-    const int nn = P.nn, N = P.N, M = P.M;
-    const int GM = G.group_m;
-    const int width = GM * nn;
-    const int first_m = (s / width) * GM;
-    const int gsz = min(P.nm - first_m, GM);
-    const int pm = first_m + (s % width) % gsz;
-    const int pn = (s % width) / gsz;
+    const int N = P.N, M = P.M;
+    const TileCoord tc = tile_coord(s, P.nm, P.nn, G.group_m);
+    const int pm = tc.pm, pn = tc.pn;
     const int m0 = pm * BM, n0 = pn * BN;
 
     // ---- per-lane staging sources (rows clamped at the edges; OOB rows are never stored) ----
@@ -810,13 +833,13 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 acc16[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                // opaque: inside the persistent (stream-K) item loop the allocator otherwise fails to keep the accumulators in place
-                // across the K-loop's back edge and copies all 128 registers once per K-tile (64 v_mov_b64: +50 % time)
+                // opaque: every accumulator tile is a value the compiler has to hold in VGPRs from here on (see the pin on tid_
+                // above: removing this one changes the register allocation of the shipped kernel)
                 asm volatile("" : "+v"(acc16[i][j]));
             }
     }
     const int nkt_all = G.K / BK;
-    const int nkt = (CFG::SCHED == 5) ? sk.kt1 - sk.kt0 : nkt_all;    // K-tiles of THIS call (stream-K segments: SCHED 5 only)
+    const int nkt = (CFG::SCHED == 5) ? kr.kt1 - kr.kt0 : nkt_all;    // the same number: see KRange
     unsigned long long clk_c0 = 0, clk_r0 = 0;
     if (G.clk != nullptr) {          // kernel-uniform
         clk_c0 = __builtin_readcyclecounter();
@@ -825,16 +848,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
 #if APEXMI_GEMM_TRACE
     if (G.trace != nullptr) tr_l0 = __builtin_amdgcn_s_memrealtime();
 #endif
-
-    auto stage = [&](int buf, int kt) {
-        char* base = smem + buf * CFG::STAGE + wave * 1024;
-        const int64_t koff = (int64_t)kt * (BK * 2);
-#pragma unroll
-        for (int i = 0; i < CFG::A_LD; ++i) glds16(a_src[i] + koff, base + i * (CFG::NW * 1024));
-#pragma unroll
-        for (int i = 0; i < CFG::W_LD; ++i)
-            glds16(w_src[i] + koff, base + CFG::A_BYTES + i * (CFG::NW * 1024));
-    };
 
     // fragment read offsets (bytes) inside a tile image; k-step ks selects chunk (2 ks + hi) ^ sw
     int a_off[TM], a_sw[TM], w_off[TN], w_sw[TN];
@@ -852,37 +865,27 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
     }
 
     if constexpr (CFG::SCHED == 0) {
-#if APEXMI_GEMM_PEEL >= 2 && !defined(APEXMI_GEMM_SMALL_VECTOR)   // (-DAPEXMI_GEMM_SMALL_VECTOR: the A/B arm with the builtin's vector addresses)
         // the pieces in the scalar-base form of global_load_lds (as in the SCHED 5 loop below: uniform tile base in SGPRs + constant
         // 32-bit lane offsets): these launches put at most a workgroup or two on a CU, and their K-tile is a chain of piece issues
-        const uint64_t a_u64 = (uint64_t)(P.A + (int64_t)min(m0, M - 1) * P.lda), w_u64 = (uint64_t)(P.W + (int64_t)min(n0, N - 1) * P.ldw);
-        const char* const a_u = (const char*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a_u64 >> 32)) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a_u64));
-        const char* const w_u = (const char*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_u64 >> 32)) << 32) |
-                                              (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w_u64));
+        const char* const a_p = (const char*)(P.A + (int64_t)min(m0, M - 1) * P.lda);
+        const char* const w_p = (const char*)(P.W + (int64_t)min(n0, N - 1) * P.ldw);
+        const char* const a_u = uniform_ptr(a_p);
+        const char* const w_u = uniform_ptr(w_p);
         uint32_t a_o[CFG::A_LD], w_o[CFG::W_LD];
 #pragma unroll
         for (int i = 0; i < CFG::A_LD; ++i) a_o[i] = (uint32_t)(a_src[i] - a_u);
 #pragma unroll
         for (int i = 0; i < CFG::W_LD; ++i) w_o[i] = (uint32_t)(w_src[i] - w_u);
         const uint32_t smem_lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem);
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-        auto piece = [&](const char* sbase, uint32_t voff, uint32_t la) {
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                         :: "v"(voff), "s"(sbase), "s"(la) : "memory", "m0");
-        };
-#pragma clang diagnostic pop
         auto stage = [&](int buf, int kt) {
             const uint32_t base = smem_lds0 + buf * CFG::STAGE + wave * 1024;
             const char* ga = a_u + (int64_t)kt * (BK * 2);
             const char* gw = w_u + (int64_t)kt * (BK * 2);
 #pragma unroll
-            for (int i = 0; i < CFG::A_LD; ++i) piece(ga, a_o[i], base + i * (CFG::NW * 1024));
+            for (int i = 0; i < CFG::A_LD; ++i) glds16_s(ga, a_o[i], base + i * (CFG::NW * 1024));
 #pragma unroll
-            for (int i = 0; i < CFG::W_LD; ++i) piece(gw, w_o[i], base + CFG::A_BYTES + i * (CFG::NW * 1024));
+            for (int i = 0; i < CFG::W_LD; ++i) glds16_s(gw, w_o[i], base + CFG::A_BYTES + i * (CFG::NW * 1024));
         };
-#endif
         stage(0, 0);
         for (int kt = 0; kt < nkt; ++kt) {
             // tile kt's LDS-DMA landed (explicit: hipcc's __syncthreads() does not reliably wait for
@@ -1096,14 +1099,8 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
         // THIS step's fragments (read a step ago; the 12 newer reads fly on) | 32 MFMAs | vmcnt: own pieces of sub-tile st + 2
         // landed, the four of st + 3 stay in flight across the barrier | barrier.  RD / DMA are literals: the last steps have
         // nothing left to read / stage.
-#define RING_VM(n)                                                                       \
-    do {                                                                                 \
-        if (!(APEXMI_GEMM_ABLATE & 2)) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory"); \
-    } while (0)
-#define RING_BAR()                                                      \
-    do {                                                                \
-        if (!(APEXMI_GEMM_ABLATE & 1)) __builtin_amdgcn_s_barrier();    \
-    } while (0)
+#define RING_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+#define RING_BAR() __builtin_amdgcn_s_barrier()
         // One step of a wave = two barrier intervals: ISSUE (fragment reads of sub-tile st + 1 into the other set, the wave's pieces of
         // sub-tile st + RD_, the counted vmcnt) | barrier | MMA (32 MFMAs on this step's set, then lgkmcnt(0): the reads issued in
         // ISSUE have had the whole MFMA segment to land) | barrier.  The M-halves run ONE INTERVAL APART (waves w and w + 4 share a
@@ -1118,9 +1115,9 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
 #define RING_STEP(st_, set, RD, DMA)                                        \
     do {                                                                    \
         RING_FENCE();                                                       \
-        if (RD && !(APEXMI_GEMM_ABLATE & 8)) RING_RD(s_rd, (set) ^ 1);      \
+        if (RD) RING_RD(s_rd, (set) ^ 1);                                   \
         RING_FENCE();                                                       \
-        if (DMA && !(APEXMI_GEMM_ABLATE & 4)) dma((st_) + RD_, s_dma);      \
+        if (DMA) dma((st_) + RD_, s_dma);                                   \
         RING_FENCE();                                                       \
         if (DMA) {                                                          \
             if (RD_ == 3) RING_VM(4);                                       \
@@ -1223,20 +1220,7 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
                             wf[nt][u][ks], af[t][ks], acc16[nt * 2 + u][half * 4 + t], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
         };
-#define PP_SYNC()                                                                   \
-    do {                                                                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                          \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        __builtin_amdgcn_s_barrier();                                               \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-    } while (0)
-#define PP_BAR()                               \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-        // staging by global_load_lds with per-lane 64-bit pointers (buffer_load .. lds with scalar piece
+        // staging by global_load_lds; these are the lane's source addresses at K-tile 0 (buffer_load .. lds with scalar piece
         // offsets measured 1.7 % slower in the Flux step: 72.3 vs 71.1 ms)
         const char* ra_src[2][2];
         const char* rw_src[2][2];
@@ -1260,27 +1244,11 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
             }
         const int64_t w_kstep = (G.wpacked & 1) ? 256 * 128 : BK * 2;     // bytes between consecutive K-tiles of a W / A row
         const int64_t a_kstep = (G.wpacked & 2) ? 256 * 128 : BK * 2;
-        if (sk.kt0) {                                       // a stream-K segment starts inside the tile's K range
-#pragma unroll
-            for (int reg = 0; reg < 2; ++reg)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    ra_src[reg][j] += (int64_t)sk.kt0 * a_kstep;
-                    rw_src[reg][j] += (int64_t)sk.kt0 * w_kstep;
-                }
-        }
-#if APEXMI_GEMM_PEEL >= 2
-        // Round 6 (shipped): a piece's address = a UNIFORM base in scalar registers (the tile's first row at the segment's first
+        // Round 6 (shipped): a piece's address = a UNIFORM base in scalar registers (the tile's first row at the first
         // K-tile, advanced per K-tile by scalar adds) + a 32-bit lane offset that never changes, issued as the scalar-base form of
         // global_load_lds — no 64-bit vector add per piece (8 per K-tile and wave before).  The lane offsets stay inside the tile's
         // 256 rows (row clamps included), so 32 bits hold them for any leading dimension below 2^22 elements.
-        // (the tile's coordinates are workgroup-uniform but not always provably so for the compiler — the persistent forms read
-        // them from an atomic —: v_readfirstlane pins the bases to scalar registers.)
-        auto uniform_ptr = [](const char* p) {
-            const uint64_t u = (uint64_t)p;
-            const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-            return (const char*)(((uint64_t)hi << 32) | lo);
-        };
+        // (the tile's coordinates are workgroup-uniform but not provably so for the compiler: uniform_ptr pins the bases.)
         const char* const a_base_u = uniform_ptr((G.wpacked & 2) ? (const char*)(P.A + (int64_t)pm * nkt_all * 256 * 64)
                                                                  : (const char*)(P.A + (int64_t)min(m0, M - 1) * P.lda));
         const char* const w_base_u = uniform_ptr((G.wpacked & 1) ? (const char*)(P.W + (int64_t)pn * nkt_all * 256 * 64)
@@ -1293,21 +1261,10 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
                 ra_off[reg][j] = (uint32_t)(ra_src[reg][j] - a_base_u);
                 rw_off[reg][j] = (uint32_t)(rw_src[reg][j] - w_base_u);
             }
-        // hipcc selects the 64-bit vector-address form for the builtin whatever the pointer looks like: the scalar-base form by hand
-        // (M0 = the piece's LDS address, one state between the M0 write and the load)
         const uint32_t smem_lds = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem);
-        // M0 is on the clobber list so that hipcc's own M0 bookkeeping (it merges and hoists identical M0 initialisations of its
-        // LDS-DMA builtins) sees a definition here; clang flags a reserved register on a clobber list, which is the point
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"
-        auto glds16_s = [&](const char* sbase, uint32_t voff, uint32_t la) {
-            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                         :: "v"(voff), "s"(sbase), "s"(la) : "memory", "m0");
-        };
-#pragma clang diagnostic pop
         auto stage_a = [&](int buf, int kt, int reg) {
             const uint32_t base = smem_lds + buf * CFG::STAGE;
-            const char* gb = a_base_u + (int64_t)kt * a_kstep;          // (ra_off holds the segment's first K-tile, sk.kt0)
+            const char* gb = a_base_u + (int64_t)kt * a_kstep;
 #pragma unroll
             for (int j = 0; j < 2; ++j) glds16_s(gb, ra_off[reg][j], base + ra_row[reg][j] * 128);
         };
@@ -1317,23 +1274,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
 #pragma unroll
             for (int j = 0; j < 2; ++j) glds16_s(gb, rw_off[reg][j], base + rw_row[reg][j] * 128);
         };
-#else
-        auto stage_a = [&](int buf, int kt, int reg) {
-            char* base = smem + buf * CFG::STAGE;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                glds16(ra_src[reg][j] + (int64_t)kt * a_kstep, base + ra_row[reg][j] * 128);
-            }
-        };
-        auto stage_w = [&](int buf, int kt, int reg) {
-            char* base = smem + buf * CFG::STAGE + CFG::A_BYTES;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                glds16(rw_src[reg][j] + (int64_t)kt * w_kstep, base + rw_row[reg][j] * 128);
-            }
-        };
-#endif
-#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
         stage_a(0, 0, 0);
         stage_w(0, 0, 0);
         stage_w(0, 0, 1);
@@ -1374,9 +1314,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
         for (int kt = 0; kt + 1 < nkt; ++kt) ktile(kt, std::true_type{});
         if (nkt > 0) ktile(nkt - 1, std::false_type{});
         if (wm == 0) PP_BAR();
-#undef VMCNT
-#undef PP_SYNC
-#undef PP_BAR
     } else {
         // ---- ping-pong schedule (TM = 4, TN = 2): 4 phases per K-tile ----
         static_assert(!CFG::PP || (TM == 4 && TN == 2), "ping-pong schedule is written for 128x64 wave tiles");
@@ -1403,19 +1340,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
                         __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks], af[t][ks], acc[nt][half * 2 + t], 0, 0, 0);
             __builtin_amdgcn_s_setprio(0);
         };
-#define PP_SYNC()                                                                   \
-    do {                                                                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                          \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        __builtin_amdgcn_s_barrier();                                               \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-    } while (0)
-#define PP_BAR()                               \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
 
         // Region-wise staging: the tile image is cut into the four sub-tiles the phases read
         //   RA0/RA1 = activation rows with (row & 64) == 0 / != 0   (m-half 0 / 1 of every wave)
@@ -1450,7 +1374,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
 #pragma unroll
             for (int j = 0; j < 2; ++j) glds16(rw_src[reg][j] + koff, base + rw_lds[reg][j]);
         };
-#define VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 
         stage_a(0, 0, 0);
         stage_w(0, 0, 0);
@@ -1502,9 +1425,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
             PP_BAR();
         }
         if (wm == 0) PP_BAR();    // balance the barrier count of the two halves
-#undef VMCNT
-#undef PP_SYNC
-#undef PP_BAR
     }
 
 #if APEXMI_GEMM_TRACE
@@ -1519,50 +1439,6 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
         if (tid == 0) {
             atomicAdd(G.clk, c1 - clk_c0);
             atomicAdd(G.clk + 1, r1 - clk_r0);
-        }
-    }
-
-    // ---- stream-K hand-over (SCHED 5): partial sums in accumulator order, 16 bytes per lane, fully coalesced ----
-    // CDNA guide §6 Guideline 16, the fence-free form: write-through (sc1) slab stores -> every wave vmcnt(0) -> workgroup barrier
-    // -> ONE lane raises the flag (relaxed, agent scope); the owner polls relaxed, then reads the slab with sc1 loads.  No
-    // release / acquire fence: an agent-scope release writes the XCD's whole L2 back (every dirty output line of the launch) and
-    // cost ~20 us per hand-over here.  Slab addressing through a buffer descriptor: one VGPR offset (16 * tid) + a scalar offset per
-    // 8 KiB row, instead of thirty-two 64-bit address pairs (which the allocator spilled the accumulators for).
-    if constexpr (CFG::SCHED == 5 && APEXMI_GEMM_STREAMK) {
-        typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_;
-        if (sk.mode == TILE_WRITER) {
-            auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(G.sk_slab + (size_t)sk.cu * 65536), 0, 262144, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, acc16[i][j]), rs, tid * 16, (i * 8 + j) * 8192, 16);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) __hip_atomic_store(G.sk_flag + sk.cu, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        if (sk.mode == TILE_OWNER) {
-            if (tid == 0)
-                for (int p = 1; p <= sk.nparts; ++p)
-                    while (__hip_atomic_load(G.sk_flag + sk.cu - p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) __builtin_amdgcn_s_sleep(2);
-            __syncthreads();
-            // fixed order: own K range + the range before it + the one before that (deterministic, launch to launch)
-            for (int p = 1; p <= sk.nparts; ++p) {
-                auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(G.sk_slab + (size_t)(sk.cu - p) * 65536), 0, 262144, 0x00020000);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {           // eight 16-byte loads in flight at a time (the accumulators hold 128 VGPRs)
-                    u32x4_ v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, (i * 8 + j) * 8192, 16);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc16[i][j] += __builtin_bit_cast(f32x4_t, v[j]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();
-            if (tid == 0)            // every slab has exactly one reader: lower its flag for the next launch on this stream
-                for (int p = 1; p <= sk.nparts; ++p) __hip_atomic_store(G.sk_flag + sk.cu - p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 
@@ -1616,92 +1492,13 @@ __device__ __forceinline__ void gemm_tile(const GemmGroup& G, char* smem, int s,
                             store_ntile<EPI, TM, ACT>(acc[nt], P, N, mrow, n0 + wn * (BN / CFG::WN) + nt * 32, hi));
 }
 
-// The launch.  Normally one workgroup per tile.  STREAM-K (G.sk_r > 0, SCHED 5): 256 persistent workgroups, 32 per XCD.
-// Launches whose tile count is not a multiple of the 256 CUs end in a part-filled round — 216 tiles (attention-out, FF-down,
-// the single block's proj_out: 42 % of the Flux step's GEMM flops) leave 40 CUs idle for the whole launch, 648 tiles (QKV of a
-// double block) run a third round at 53 % — and the live clock probe shows the GEMM is NOT power-bound (2.05 GHz), so those idle
-// CUs are lost time, not clock given back.  Here the sk_r tiles past the last full round are shared out by K: XCD x takes
-// r_x = sk_r / 8 (+1) of them, its 32 workgroups cut the r_x * nkt K-tiles into 32 equal unit ranges.  A workgroup's range is
-// [tail of a tile begun by the workgroup before it | whole tiles | head of a tile the next workgroup finishes]:
-//   * the HEAD (a tile whose last K-tiles lie in a higher workgroup) is computed FIRST and leaves as an f32 slab + flag (WRITER);
-//   * then whole tiles of the range and the workgroup's tiles of the full rounds (ordinary epilogue);
-//   * the TAIL (the tile's last K-tiles are here) is computed LAST, adds the slabs of the one or two workgroups before it, and runs
-//     the epilogue (OWNER).
-// An owner only ever waits for workgroups with a LOWER block id on its own XCD (dispatched before it, slab written at the start of
-// their work), so the hand-over is deadlock-free whatever else shares the chip, slabs stay in the XCD's L2, and the f32 sum order
-// (own range, then the ranges before it) is fixed: results are deterministic; they differ from the one-workgroup-per-tile launch
-// by f32 summation order only.
+// One workgroup per tile, over the whole K range (see KRange for why the range travels as a struct).
 template <typename CFG, int EPI>
 __global__ __launch_bounds__(CFG::NT, CFG::OCC) void gemm_bf16_kernel(const GemmGroup G) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int nkt = G.K / BK;
-    SkCtx sk{TILE_FULL, 0, nkt, 0, 0};
-    if constexpr (CFG::SCHED != 5) {
-        gemm_tile<CFG, EPI>(G, smem, xcd_remap(blockIdx.x, G.total), sk);
-    } else {
-        if (!APEXMI_GEMM_STREAMK || (G.sk_r <= 0 && G.sk_tfull <= 0)) {
-            gemm_tile<CFG, EPI>(G, smem, xcd_remap(blockIdx.x, G.total), sk);
-            return;
-        }
-        // The work list of this workgroup is RE-DERIVED from (block id, item index) at the top of every iteration, behind an opaque
-        // copy of the block id: a dozen scalars kept live across the K-loop instead cost SGPR spills into VGPR lanes and, with
-        // them, VGPR spills inside the K-loop (whose scratch loads would also break the counted vmcnt waits).
-        for (int it = 0;; ++it) {
-            int bid = blockIdx.x;
-            asm volatile("" : "+s"(bid));
-            const int x = bid & 7, i = bid >> 3;                                // XCD, workgroup within it (dispatch order)
-            const int rx = G.sk_r / 8 + (x < G.sk_r % 8 ? 1 : 0);               // remainder tiles of this XCD ...
-            const int r0 = G.sk_tfull + x * (G.sk_r / 8) + min(x, G.sk_r % 8);  // ... starting at this sequence index
-            const int64_t units = (int64_t)rx * nkt;
-            auto ustart = [&](int w) { return (int)((units * w) / 32); };
-            const int u0 = ustart(i), u1 = ustart(i + 1);
-            int j0 = 0, j1 = -1;                                                // first / last remainder tile the range touches
-            if (u1 > u0) {
-                j0 = u0 / nkt;
-                j1 = (u1 - 1) / nkt;
-            }
-            // in order: [head -> WRITER] [whole tiles of the range] [its tiles of the full rounds] [tail -> OWNER]
-            const bool has_head = u1 > u0 && u1 < (j1 + 1) * nkt;               // the range's LAST tile is finished by a higher workgroup
-            const bool has_tail = u1 > u0 && u0 > j0 * nkt && !(has_head && j0 == j1);   // its FIRST tile was begun by lower ones
-            const int w_lo = j0 + ((u1 > u0 && u0 > j0 * nkt) ? 1 : 0);         // whole tiles of the range: [w_lo, w_hi]
-            const int w_hi = j1 - (has_head ? 1 : 0);
-            const int n_whole = max(w_hi - w_lo + 1, 0);
-            const int per_xcd = G.sk_tfull / 8;
-            const int n_full = per_xcd > i ? (per_xcd - i + 31) / 32 : 0;
-            const int n_items = (has_head ? 1 : 0) + n_whole + n_full + (has_tail ? 1 : 0);
-            if (it >= n_items) break;
-            int k = it, tile;
-            sk.mode = TILE_FULL;
-            sk.kt0 = 0;
-            sk.kt1 = nkt;
-            sk.nparts = 0;
-            sk.cu = x * 32 + i;
-            if (has_head && k == 0) {
-                sk.mode = TILE_WRITER;
-                sk.kt0 = max(u0, j1 * nkt) - j1 * nkt;
-                sk.kt1 = u1 - j1 * nkt;
-                tile = r0 + j1;
-            } else {
-                k -= has_head ? 1 : 0;
-                if (k < n_whole) {
-                    tile = r0 + w_lo + k;
-                } else if (k < n_whole + n_full) {
-                    tile = x * per_xcd + i + 32 * (k - n_whole);
-                } else {
-                    sk.mode = TILE_OWNER;
-                    sk.kt0 = u0 - j0 * nkt;
-                    sk.kt1 = min(u1, (j0 + 1) * nkt) - j0 * nkt;
-                    for (int w = i - 1; w >= 0 && sk.nparts < 3; --w) {         // workgroups holding K-tiles [0, kt0) of tile j0
-                        if (ustart(w + 1) <= j0 * nkt) break;
-                        ++sk.nparts;
-                    }
-                    tile = r0 + j0;
-                }
-            }
-            if (it) __syncthreads();            // the staging LDS (and the QKV epilogue's scratch) of the previous item is free
-            gemm_tile<CFG, EPI>(G, smem, tile, sk);
-        }
-    }
+    const KRange kr{0, nkt};
+    gemm_tile<CFG, EPI>(G, smem, xcd_remap(blockIdx.x, G.total), kr);
 }
 
 // ---- exact bf16 split of an f32 operand (f32-storage verification mode) ------------------------------------------
@@ -1808,14 +1605,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x288_kernel(const GemmGroup 
         if (i < G.count && s >= G.p[i].tile0) gi = i;
     const GemmProblem P = G.p[gi];
     s -= P.tile0;
-    const int nn = P.nn, N = P.N, M = P.M;
-    const int GM = G.group_m;
-    const int width = GM * nn;
-    const int first_m = (s / width) * GM;
-    const int gsz = min(P.nm - first_m, GM);
-    const int pm = first_m + (s % width) % gsz;
-    const int pn = (s % width) / gsz;
-    const int m0 = pm * XBM, n0 = pn * XBN;
+    const int N = P.N, M = P.M;
+    const TileCoord tc = tile_coord(s, P.nm, P.nn, G.group_m);
+    const int m0 = tc.pm * XBM, n0 = tc.pn * XBN;
 
     // ---- the wave's 8 LDS-DMA pieces of a K-tile (8 rows x 128 B each), in need order ----
     const char* src[8];
@@ -1885,25 +1677,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x288_kernel(const GemmGroup 
                         __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt][ks], af[t][ks], acc[nt][grp * 3 + t], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     };
-#define X_SYNC()                                                                    \
-    do {                                                                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                          \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        __builtin_amdgcn_s_barrier();                                               \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-    } while (0)
-#define X_BAR()                                \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-#define X_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #pragma unroll
     for (int j = 0; j < 8; ++j) stage(0, 0, j);
-    X_VMCNT(0);
-    X_BAR();
-    if (wm == 1) X_BAR();
+    VMCNT(0);
+    PP_BAR();
+    if (wm == 1) PP_BAR();
     for (int kt = 0; kt < nkt; ++kt) {
         const char* St = smem + (kt & 1) * X_STAGE;
         const bool more = kt + 1 < nkt;
@@ -1915,41 +1693,38 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x288_kernel(const GemmGroup 
             stage(nb, kt + 1, 0);
             stage(nb, kt + 1, 1);
             stage(nb, kt + 1, 2);
-            X_VMCNT(4);                           // in flight at most: j = 7 of this K-tile + the three just issued -> m-group 1 landed
+            VMCNT(4);                           // in flight at most: j = 7 of this K-tile + the three just issued -> m-group 1 landed
         } else {
-            X_VMCNT(1);
+            VMCNT(1);
         }
-        X_SYNC();
+        PP_SYNC();
         mma(0);
-        X_BAR();
+        PP_BAR();
         // phase 1: m-group 1
         rd_a(St, 1);
         if (more) {
             stage(nb, kt + 1, 3);
             stage(nb, kt + 1, 4);
             stage(nb, kt + 1, 5);
-            X_VMCNT(6);                           // the six pieces of the next K-tile only -> m-group 2 landed
+            VMCNT(6);                           // the six pieces of the next K-tile only -> m-group 2 landed
         } else {
-            X_VMCNT(0);
+            VMCNT(0);
         }
-        X_SYNC();
+        PP_SYNC();
         mma(1);
-        X_BAR();
+        PP_BAR();
         // phase 2: m-group 2
         rd_a(St, 2);
         if (more) {
             stage(nb, kt + 1, 6);
             stage(nb, kt + 1, 7);
-            X_VMCNT(3);                           // j = 5, 6, 7 of the next K-tile may fly: its weights and m-group 0 landed
+            VMCNT(3);                           // j = 5, 6, 7 of the next K-tile may fly: its weights and m-group 0 landed
         }
-        X_SYNC();
+        PP_SYNC();
         mma(2);
-        X_BAR();
+        PP_BAR();
     }
-    if (wm == 0) X_BAR();                         // balance the barrier count of the two halves
-#undef X_VMCNT
-#undef X_SYNC
-#undef X_BAR
+    if (wm == 0) PP_BAR();                         // balance the barrier count of the two halves
 
     if (G.clk != nullptr) {
         const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -2021,14 +1796,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
         if (i < G.count && s >= G.p[i].tile0) gi = i;
     const GemmProblem P = G.p[gi];
     s -= P.tile0;
-    const int nn = P.nn, N = P.N, M = P.M;
-    const int GM = G.group_m;
-    const int width = GM * nn;
-    const int first_m = (s / width) * GM;
-    const int gsz = min(P.nm - first_m, GM);
-    const int pm = first_m + (s % width) % gsz;
-    const int pn = (s % width) / gsz;
-    const int m0 = pm * YBM, n0 = pn * YBN;
+    const int N = P.N, M = P.M;
+    const TileCoord tc = tile_coord(s, P.nm, P.nn, G.group_m);
+    const int m0 = tc.pm * YBM, n0 = tc.pn * YBN;
 
     // ---- LDS-DMA: two buffer descriptors, one per-lane offset each, scalar piece offsets ----
     const int rows_a = min(M - m0, YBM), rows_w = min(N - n0, YBN);
@@ -2114,25 +1884,11 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
                 acc[nt][h * 6 + t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt], af[t], acc[nt][h * 6 + t], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     };
-#define Y_SYNC()                                                                    \
-    do {                                                                            \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                          \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-        __builtin_amdgcn_s_barrier();                                               \
-        __builtin_amdgcn_sched_barrier(0);                                          \
-    } while (0)
-#define Y_BAR()                                \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-#define Y_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #pragma unroll
     for (int j = 0; j < 10; ++j) stage(0, 0, j);
-    Y_VMCNT(0);
-    Y_BAR();
-    if (wm == 1) Y_BAR();
+    VMCNT(0);
+    PP_BAR();
+    if (wm == 1) PP_BAR();
     // last K-tile peeled off: no `more` test in the steady-state body (round 6)
     auto ktile = [&](int kt, auto more_c) {
         constexpr bool more = decltype(more_c)::value;
@@ -2150,16 +1906,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
             stage(nb, kt + 1, 1);
             if (DIST == 0) {
                 stage(nb, kt + 1, 2);
-                Y_VMCNT(3);
+                VMCNT(3);
             } else {
-                Y_VMCNT(2);
+                VMCNT(2);
             }
         } else {
-            Y_VMCNT(0);
+            VMCNT(0);
         }
-        Y_SYNC();
+        PP_SYNC();
         mma(0);
-        Y_BAR();
+        PP_BAR();
         // phase 1: k-step 0, m-half 1
         rd_a(St, 1, 0);
         if constexpr (more) {
@@ -2168,9 +1924,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
             stage(nb, kt + 1, 4);
             if (DIST == 0) stage(nb, kt + 1, 5);
         }
-        Y_SYNC();
+        PP_SYNC();
         mma(1);
-        Y_BAR();
+        PP_BAR();
         // phase 2: k-step 1, m-half 0
         rd_w(St, 1);
         rd_a(St, 0, 1);
@@ -2179,27 +1935,24 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_x384_kernel(const GemmGroup 
             stage(nb, kt + 1, 6);
             if (DIST == 0) stage(nb, kt + 1, 7);
         }
-        Y_SYNC();
+        PP_SYNC();
         mma(0);
-        Y_BAR();
+        PP_BAR();
         // phase 3: k-step 1, m-half 1
         rd_a(St, 1, 1);
         if constexpr (more) {
             if (DIST != 0) stage(nb, kt + 1, 7);
             stage(nb, kt + 1, 8);
             stage(nb, kt + 1, 9);
-            Y_VMCNT(3);
+            VMCNT(3);
         }
-        Y_SYNC();
+        PP_SYNC();
         mma(1);
-        Y_BAR();
+        PP_BAR();
     };
     for (int kt = 0; kt + 1 < nkt; ++kt) ktile(kt, std::true_type{});
     if (nkt > 0) ktile(nkt - 1, std::false_type{});
-    if (wm == 0) Y_BAR();
-#undef Y_VMCNT
-#undef Y_SYNC
-#undef Y_BAR
+    if (wm == 0) PP_BAR();
 
     if (G.clk != nullptr) {
         const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
@@ -2269,38 +2022,30 @@ int g_x384 = 1;       // tune key gemm.x384: the 384 x 256 tiling — 0 never | 
 int g_small_max = 112; // tune key gemm.small_max: launches of at most this many 256 x 256 tiles go out on the 128 x 128 tiling (0: never)
 int g_tail_split = 2; // tune key gemm.tail: a small last problem of a grouped launch goes out on the 128x128 tiling (1: four waves, 2: eight)
 
-// stream-K workspace: 256 slabs of 256 x 256 f32 + 256 flags per (device, stream) — launches on different streams may overlap and
-// must not share slabs; allocated (and the flags zeroed) at the first stream-K launch on that stream, kept for the process
-int g_streamk = 1;    // tune key gemm.streamk (APEXMI_GEMM_STREAMK builds only): 0 off | 1 launches with 88..232 tiles in their last round | 2 persistent always
-struct SkWorkspace {
-    float* slab;
-    unsigned* flag;
-};
-static int sk_workspace(hipStream_t stream, SkWorkspace* out) {
-    static std::mutex mu;
-    static std::vector<std::tuple<int, hipStream_t, SkWorkspace>> all;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : all)
-        if (std::get<0>(e) == dev && std::get<1>(e) == stream) {
-            *out = std::get<2>(e);
-            return 0;
-        }
-    SkWorkspace w{nullptr, nullptr};
-    if (hipMalloc((void**)&w.slab, (size_t)256 * 65536 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&w.flag, 256 * sizeof(unsigned)) != hipSuccess || hipMemset(w.flag, 0, 256 * sizeof(unsigned)) != hipSuccess) {
-        apexmi_set_error("gemm_bf16: stream-K workspace allocation failed");
-        return 1;
+// Host side common to the three launchers: numbers the tiles of the launch's problems for a (BM x BN) tiling — G.p[i].tile0 = first
+// tile id of problem i, G.total = their count, which is returned — and fills the fields every kernel reads.  group_m, the function
+// attributes and the launch itself are the launcher's.
+int number_tiles(GemmGroup& G, const int* Ms, int BM, int BN) {
+    int t = 0;
+    for (int i = 0; i < G.count; ++i) {
+        G.p[i].M = Ms[i];
+        G.p[i].nm = (Ms[i] + BM - 1) / BM;
+        G.p[i].nn = (G.p[i].N + BN - 1) / BN;
+        G.p[i].tile0 = t;
+        t += G.p[i].nm * G.p[i].nn;
     }
-    all.emplace_back(dev, stream, w);
-    *out = w;
-    return 0;
+    G.total = t;
+    G.clk = apexmi_clk_ptr();
+#if APEXMI_GEMM_TRACE
+    G.trace = (unsigned long long*)g_gemm_trace;
+#endif
+    G.wpacked = 0;
+    return t;
 }
 
 template <typename CFG, int EPI>
 int launch_cfg(GemmGroup& G, const int* Ms, hipStream_t stream) {
-    if constexpr (APEXMI_GEMM_PEEL >= 2 && (CFG::SCHED == 0 || CFG::SCHED == 5)) {
+    if constexpr (CFG::SCHED == 0 || CFG::SCHED == 5) {
         // the scalar-base pieces carry 32-bit lane offsets inside a tile: 256 rows x leading dimension x 2 bytes must stay below 2^32
         for (int i = 0; i < G.count; ++i)
             if (G.p[i].lda > (1 << 22) || G.p[i].ldw > (1 << 22)) {
@@ -2313,41 +2058,9 @@ int launch_cfg(GemmGroup& G, const int* Ms, hipStream_t stream) {
     APEXMI_SET_ATTR_ONCE(attr_set,
         (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<CFG, EPI>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS));
-    int t = 0;
-    for (int i = 0; i < G.count; ++i) {
-        G.p[i].M = Ms[i];
-        G.p[i].nm = (Ms[i] + CFG::BM - 1) / CFG::BM;
-        G.p[i].nn = (G.p[i].N + CFG::BN - 1) / CFG::BN;
-        G.p[i].tile0 = t;
-        t += G.p[i].nm * G.p[i].nn;
-    }
-    G.total = t;
+    const int t = number_tiles(G, Ms, CFG::BM, CFG::BN);
     G.group_m = g_group_m;
-    G.clk = apexmi_clk_ptr();
-#if APEXMI_GEMM_TRACE
-    G.trace = (unsigned long long*)g_gemm_trace;
-#endif
-    G.wpacked = (CFG::SCHED == 5) ? g_wpacked : 0;
-    G.sk_r = 0;
-    G.sk_tfull = 0;
-    G.sk_slab = nullptr;
-    G.sk_flag = nullptr;
-    if constexpr (CFG::SCHED == 5 && APEXMI_GEMM_STREAMK) {
-        // stream-K when the last round of 256 tiles is part-filled enough to matter and full enough that a tile is shared by at
-        // most four workgroups (the owner adds at most three slabs): 11..29 remainder tiles per XCD
-        const int r = t % 256;
-        const bool forced = g_streamk == 2 && G.batch == 1 && t >= 256 && (r == 0 || (r >= 88 && r <= 232));   // experiment: persistent always
-        if (forced || (g_streamk && G.batch == 1 && r >= 88 && r <= 232 && G.K / BK >= 8)) {
-            SkWorkspace w;
-            if (sk_workspace(stream, &w)) return 1;
-            G.sk_r = r;
-            G.sk_tfull = t - r;
-            G.sk_slab = w.slab;
-            G.sk_flag = w.flag;
-            hipLaunchKernelGGL((gemm_bf16_kernel<CFG, EPI>), dim3(256, 1), dim3(CFG::NT), CFG::LDS, stream, G);
-            return apexmi_check_launch("gemm_bf16");
-        }
-    }
+    if (CFG::SCHED == 5) G.wpacked = g_wpacked;
     hipLaunchKernelGGL((gemm_bf16_kernel<CFG, EPI>), dim3(t, G.batch), dim3(CFG::NT), CFG::LDS, stream, G);
     return apexmi_check_launch("gemm_bf16");
 }
@@ -2357,21 +2070,8 @@ int launch_x288(GemmGroup& G, const int* Ms, hipStream_t stream) {
     static uint64_t attr_set = 0;
     APEXMI_SET_ATTR_ONCE(attr_set,
         (void)hipFuncSetAttribute((const void*)gemm_bf16_x288_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS));
-    int t = 0;
-    for (int i = 0; i < G.count; ++i) {
-        G.p[i].M = Ms[i];
-        G.p[i].nm = (Ms[i] + XBM - 1) / XBM;
-        G.p[i].nn = (G.p[i].N + XBN - 1) / XBN;
-        G.p[i].tile0 = t;
-        t += G.p[i].nm * G.p[i].nn;
-    }
-    G.total = t;
+    const int t = number_tiles(G, Ms, XBM, XBN);
     G.group_m = g_group_m;
-    G.clk = apexmi_clk_ptr();
-    G.wpacked = 0;
-    G.sk_r = G.sk_tfull = 0;
-    G.sk_slab = nullptr;
-    G.sk_flag = nullptr;
     hipLaunchKernelGGL((gemm_bf16_x288_kernel<EPI>), dim3(t, 1), dim3(512), X_LDS, stream, G);
     return apexmi_check_launch("gemm_bf16 (288x192)");
 }
@@ -2384,26 +2084,10 @@ int launch_x384(GemmGroup& G, const int* Ms, hipStream_t stream) {
         (void)hipFuncSetAttribute((const void*)gemm_bf16_x384_kernel<EPI, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, Y_LDS);
         if constexpr (EPI == APEXMI_EPI_BIAS)
             (void)hipFuncSetAttribute((const void*)gemm_bf16_x384_kernel<EPI, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, Y_LDS));
-    int t = 0;
-    for (int i = 0; i < G.count; ++i) {
-        G.p[i].M = Ms[i];
-        G.p[i].nm = (Ms[i] + YBM - 1) / YBM;
-        G.p[i].nn = (G.p[i].N + YBN - 1) / YBN;
-        G.p[i].tile0 = t;
-        t += G.p[i].nm * G.p[i].nn;
-    }
-    G.total = t;
+    const int t = number_tiles(G, Ms, YBM, YBN);
     // tile groups 3 tall: an XCD's 32 concurrent tiles as 3 x 10.7 = 1152 activation rows x 2730 weight rows per K-slice (6 tall: 2304 x
     // 1365) — on the 75 600-row launches +2..4 % (profiles/r05_gemm_x384_group_m.log), the same on the 12-row-tile Flux launch
     G.group_m = g_x384_group_m;
-    G.clk = apexmi_clk_ptr();
-#if APEXMI_GEMM_TRACE
-    G.trace = (unsigned long long*)g_gemm_trace;
-#endif
-    G.wpacked = 0;
-    G.sk_r = G.sk_tfull = 0;
-    G.sk_slab = nullptr;
-    G.sk_flag = nullptr;
     bool any_qkv = false;
     for (int i = 0; i < G.count; ++i) any_qkv |= G.p[i].qkv != 0;
     if constexpr (EPI == APEXMI_EPI_BIAS) {
@@ -2788,7 +2472,6 @@ int apexmi_set_gemm_key(const char* key, int value) {
     else if (!strcmp(key, "gemm.trace_lo")) g_gemm_trace = (g_gemm_trace & ~(uintptr_t)0xffffffffu) | (uint32_t)value;
     else if (!strcmp(key, "gemm.trace_hi")) g_gemm_trace = (g_gemm_trace & (uintptr_t)0xffffffffu) | ((uintptr_t)(uint32_t)value << 32);
 #endif
-    else if (!strcmp(key, "gemm.streamk")) g_streamk = value;
     else return 1;
     return 0;
 }

@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-# APEX_MI355_LIB: load another build of the library (the ablation builds of tools/gemm_ring_ablate.sh); default = the in-tree one
+# APEX_MI355_LIB: load another build of the library (the side builds of tools/gemm_qk_ablate.sh); default = the in-tree one
 LIB_PATH = os.environ.get("APEX_MI355_LIB") or os.path.join(_PKG_DIR, "libapex_mi355.so")
 
 _lib = None

@@ -404,8 +404,20 @@ int apexmi_attn_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk,
                          apexmi_stream_t stream);
 
 /* Tuning knobs for A/B measurements (bench.py --tune, tests); defaults are the shipped choices:
- *   "gemm.config"  0 auto | 1 128x128 | 2 256x256 | 3 256x256 ping-pong 32x32x16 | 6 one wave per SIMD | 7 ping-pong 16x16x32
- *   "gemm.large"   tiling the auto rule picks for large problems (7)      "gemm.group_m"  rows of a tile-order group (8)
+ *   "gemm.config"  0 auto (default) | 1 128x128, four waves | 2 256x256 plain double buffer | 3 256x256 ping-pong 32x32x16 |
+ *                  6 256x256 one wave per SIMD | 7 256x256 ping-pong 16x16x32 | 8 128x128, eight waves | 9 256x256 free-running
+ *                  ring, four slots | 10 the same, five slots
+ *   "gemm.large"   tiling the auto rule picks for large problems (7)      "gemm.group_m"  rows of a tile-order group (6)
+ *   "gemm.small_max"  112: gate / residual launches of at most this many 256x256 tiles go out on the 128x128 tiling (0: never)
+ *   "gemm.x288"    0 (default) never | 1 where it saves a round's worth of tile-work | 2 always: the 288x192 tiling (see
+ *                  apexmi_gemm_uses_x288)
+ *   "gemm.x384"    1 (default): the 384x256 tiling where the launch is several full rounds of nearly full tiles | 0 never | 2 always
+ *   "gemm.x384_dist"  how a wave's 10 LDS-DMA pieces of a 384x256 K-tile are spread over its 4 phases: 0 3+3+2+2 | 1 2+3+2+3 |
+ *                  -1 (default) by launch size (0 from 2048 tiles)
+ *   "gemm.x384_group_m"  rows of a tile-order group of the 384x256 launches (3)
+ *   "gemm.x384_qkv"   1 (default): launches with the fused q/k/v epilogue may take the 384x256 tiling too | 0: 256x256 only
+ *   "gemm.wpacked" 0 (default).  Experiment: bit 0 / bit 1 = the W / A operands of the ping-pong 16x16x32 launches are tile-major
+ *                  packed, [rows / 256][K / 64][256][64]
  *   "conv.v2"      1 (default): stride-1 zero-padded convolutions over >= 65536 positions use the conv-shaped tiles
  *                  (conv3d_v2_kernel: 512x96 / 256x192 / 256x256 / 512x32|64 by Cout); 0: always the 128x128 kernel.
  *                  Bit-identical results either way.
@@ -416,7 +428,9 @@ int apexmi_attn_fwd_bias(const void* q, int64_t ldq, const void* k, int64_t ldk,
  *                  same products as the implicit GEMM, f32 sums in another order (<= 1 bf16 ulp on a few 1e-4 of the outputs).
  *                  1: Cin = 96 / Cout <= 96 layers on the order-preserving 8 x 32 form (bit-identical to the implicit GEMM).
  *                  0: implicit GEMM only.
- *   "gemm.tail"    1: a small last problem of a grouped launch after whole rounds of tiles goes out on the 128x128 tiling
+ *   "gemm.tail"    a small last problem (at most "gemm.tail_max" 256x256 tiles) of a grouped launch after whole rounds of tiles
+ *                  goes out as its own launch on the 128x128 tiling: 2 (default) eight waves | 1 four waves | 0 stays in the launch
+ *   "gemm.tail_max"   96: the largest such tail problem, in 256x256 tiles
  *   "attn.waves"   0 auto | 4..8 waves per attention workgroup            "attn.mfma"     32 | 16
  *   "attn.c4"      0: plain loop | 1 + bits: 4-cluster ping-pong kernel, bit 0 s_setprio around the matrix clusters, bit 1
  *                  packed-f32 softmax (v_pk_fma_f32 / v_pk_add_f32), bit 2 static priority for waves 4..7.  Default 3

@@ -808,7 +808,8 @@ def test_attention_operator_uses_the_tail_split():
 
 def test_gemm_grouped_tail_problem_on_small_tiling():
     """Grouped launch = image stream filling whole rounds (8 x 32 tiles = 256) + a small text stream: the text problem
-    goes out on the 128x128 tiling (`gemm.tail`); both ways agree with the reference."""
+    goes out on the 128x128 tiling (`gemm.tail`: 2 eight waves, the shipped value; 1 four waves; 0 stays in the launch); every
+    way agrees with the reference."""
     ops = _ops()
     from apex_studio_amd import lib
     K, N, Mi, Mt = 512, 8192, 2048, 256
@@ -817,18 +818,19 @@ def test_gemm_grouped_tail_problem_on_small_tiling():
     bi, bt = _bf(seeded((N,), 5)).to(DEV), _bf(seeded((N,), 6)).to(DEV)
     outs = {}
     try:
-        for tail in (1, 0):
+        for tail in (2, 1, 0):
             lib.tune_set("gemm.tail", tail)
             out = torch.full((Mt + Mi, N), float("nan"), dtype=torch.bfloat16, device=DEV)
             ops.gemm_grouped([ai, at], [wi, wt], [bi, bt], [out[Mt:], out[:Mt]], epilogue="gelu")
             outs[tail] = out.clone()
     finally:
-        lib.tune_set("gemm.tail", 1)
+        lib.tune_set("gemm.tail", 2)
     ref = torch.cat([torch.nn.functional.gelu(at.float() @ wt.float().T + bt.float(), approximate="tanh"),
                      torch.nn.functional.gelu(ai.float() @ wi.float().T + bi.float(), approximate="tanh")])
-    for tail in (1, 0):
+    for tail in (2, 1, 0):
         _check(outs[tail], ref.cpu(), 3e-3, f"grouped tail={tail}")
     assert torch.equal(outs[1][Mt:], outs[0][Mt:])          # the image rows come from the same kernel either way
+    assert torch.equal(outs[2][Mt:], outs[0][Mt:])
 
 
 def test_attention_backend_key_padding_masks():
