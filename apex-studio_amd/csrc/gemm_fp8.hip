@@ -1,7 +1,9 @@
 // Opt-in FP8 GEMM for resident fp8-scaled weights: a per-row e4m3 quantiser for the activations and a GEMM on
 // the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 x e4m3 at twice the bf16 rate per clock) with UNIT block scales; the
-// per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.
+// per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.  The run-time LoRA form
+// (apexmi_gemm_fp8_lora) applies them to the accumulators instead and adds the adapter term t . B'^T by a bf16 MFMA tail.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -107,6 +109,14 @@ struct Fp8Gemm {
     unsigned long long* clk;
 };
 
+// the run-time LoRA form (apexmi_gemm_fp8_lora): the adapter operands of the bf16 tail
+struct Fp8LoraGemm : Fp8Gemm {
+    const bf16_t* T;      // t = a A^T [M, Rp]
+    const bf16_t* LB;     // B' [N, Rp]
+    int64_t ldt, ldb;
+    int Rp;               // padded rank, a multiple of 64
+};
+
 APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
     const int sw = (row >> 1) & 7;
     const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece ^ sw) << 4));
@@ -114,8 +124,19 @@ APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
     return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
-template <int EPI>     // APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
-__global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
+// a 16-byte piece of a staged tile as the operand of one v_mfma_f32_32x32x16_bf16 k-step: lane l holds the 8 bf16 k = 8 (l >> 5) + 0..7
+// of row (A) / column (B) l & 31 (gemm.hip's fragment reads), so k-step ks of a 64-wide rank tile is piece 2 ks + (l >> 5)
+APEXMI_DEVICE bf16x8 lds_frag16(const uint8_t* tile, int row, int piece) {
+    return *(const bf16x8*)(tile + row * FBK + ((piece ^ ((row >> 1) & 7)) << 4));
+}
+
+// LORA (G is an Fp8LoraGemm): after the fp8 K-loop the accumulators are scaled IN PLACE, acc = (acc * sa[m]) * sw[n], and a bf16 MFMA
+// tail adds sum_r t[m, r] B'[n, r] into the same registers, rank ascending: both MFMA shapes write the same 32 x 32 layout.  A rank
+// tile of 64 bf16 is 128 bytes per row — the geometry of a K-tile of codes — so t takes the activation half and B' the weight half
+// of a buffer, staged and swizzled as they are; the first rank tile is requested during the last K-tile.
+// ONE kernel name for both forms: build.py's no-spill check matches "gemm_fp8_kernel" and so covers every instantiation.
+template <int EPI, bool LORA>     // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
+__global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional_t<LORA, Fp8LoraGemm, Fp8Gemm> G) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * FOPB];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
@@ -145,6 +166,18 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
             glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
         }
     };
+    auto stage_rank = [&](int rt, int buf) {     // LORA: rank tile rt of t (rows) and B' (columns), same rows, pieces and swizzle
+        if constexpr (LORA) {
+            uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = 32 * wid + 8 * i + (lane >> 3);
+                const int c = (lane & 7) ^ ((r >> 1) & 7);
+                glds16((const char*)(G.T + (int64_t)min(m0 + r, G.M - 1) * G.ldt) + c * 16 + rt * FBK, da + 8 * i * FBK);
+                glds16((const char*)(G.LB + (int64_t)min(n0 + r, G.N - 1) * G.ldb) + c * 16 + rt * FBK, da + FOPB + 8 * i * FBK);
+            }
+        }
+    };
 
     unsigned long long clk_c0 = 0, clk_r0 = 0;
     if (G.clk != nullptr) {          // kernel-uniform
@@ -167,6 +200,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
+        else stage_rank(0, buf ^ 1);
         const uint8_t* ta = lds + buf * 2 * FOPB;
         const uint8_t* tw = ta + FOPB;
 #pragma unroll
@@ -188,19 +222,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
         __syncthreads();
     }
 
-    if (G.clk != nullptr) {
-        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            atomicAdd(G.clk, c1 - clk_c0);
-            atomicAdd(G.clk + 1, r1 - clk_r0);
-        }
-    }
-
-    // ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float sw[4][4], bs[4][4];
-        f32x4 gt[4];
+    // the weight scales of weight tile i: 4 column groups of 4 per lane, loaded from clamped addresses
+    auto load_sw = [&](int i, float (&sw)[4][4]) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
@@ -211,9 +234,66 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
                 const uint32_t one = G.sw[0];
                 s = u32x2{one * 0x10001u, one * 0x10001u};
             }
+            sw[g][0] = bf16_lo(s[0]), sw[g][1] = bf16_hi(s[0]), sw[g][2] = bf16_lo(s[1]), sw[g][3] = bf16_hi(s[1]);
+        }
+    };
+
+    if constexpr (LORA) {
+        float sa[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) sa[j] = G.sa[min(m0 + 64 * wr + 32 * j + fr, G.M - 1)];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float sw[4][4];
+            load_sw(i, sw);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * sa[j]) * sw[r >> 2][r & 3];
+        }
+        const int nr = G.Rp / 64;
+        for (int rt = 0; rt < nr; ++rt) {
+            const int buf = (nk + rt) & 1;
+            if (rt + 1 < nr) stage_rank(rt + 1, buf ^ 1);
+            const uint8_t* tt = lds + buf * 2 * FOPB;
+            const uint8_t* tb = tt + FOPB;
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                bf16x8 ft[2], fb[2];
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    ft[i] = lds_frag16(tt, 64 * wr + 32 * i + fr, 2 * ks + fh);
+                    fb[i] = lds_frag16(tb, 64 * wc + 32 * i + fr, 2 * ks + fh);
+                }
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[i], ft[j], acc[i][j], 0, 0, 0);
+            }
+            __syncthreads();
+        }
+    }
+
+    if (G.clk != nullptr) {
+        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
+        if (tid == 0) {
+            atomicAdd(G.clk, c1 - clk_c0);
+            atomicAdd(G.clk + 1, r1 - clk_r0);
+        }
+    }
+
+    // ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
+    // LORA: the scales are in acc already, out = epi(acc + bias[n])
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float sw[4][4], bs[4][4];
+        f32x4 gt[4];
+        if constexpr (!LORA) load_sw(i, sw);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
             u32x2 b = {0u, 0u};
             if (G.bias != nullptr) b = *(const u32x2*)(G.bias + n);
-            sw[g][0] = bf16_lo(s[0]), sw[g][1] = bf16_hi(s[0]), sw[g][2] = bf16_lo(s[1]), sw[g][3] = bf16_hi(s[1]);
             bs[g][0] = bf16_lo(b[0]), bs[g][1] = bf16_hi(b[0]), bs[g][2] = bf16_lo(b[1]), bs[g][3] = bf16_hi(b[1]);
             if (EPI == APEXMI_EPI_BIAS_GATE_RES) gt[g] = *(const f32x4*)(G.gate + n);
         }
@@ -221,7 +301,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
         for (int j = 0; j < 2; ++j) {
             const int m = m0 + 64 * wr + 32 * j + fr;
             const int mc = min(m, G.M - 1);
-            const float sa = G.sa[mc];
+            float sa = 1.f;
+            if constexpr (!LORA) sa = G.sa[mc];
             u32x2 rr[4];
             if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
 #pragma unroll
@@ -236,7 +317,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8Gemm G) {
                 float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                    if constexpr (LORA) o[e] = acc[i][j][4 * g + e] + bs[g][e];
+                    else o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
                     if (EPI == APEXMI_EPI_BIAS_GELU) o[e] = gelu_tanh_f(o[e]);
                 }
                 if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
@@ -270,10 +352,18 @@ extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, v
     return apexmi_check_launch("quant_rows_fp8");
 }
 
-extern "C" int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format,
-                               const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K,
-                               int epilogue, const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// both entry points: every check before any launch; lora = the adapter operands of apexmi_gemm_fp8_lora, or null for apexmi_gemm_fp8
+struct Fp8LoraArgs {
+    const void* t;
+    int64_t ldt;
+    const void* lb;
+    int64_t ldb;
+    int Rp;
+};
+
+static int gemm_fp8_run(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format, const void* sw,
+                        int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
+                        const float* gate, const void* R, int64_t ldr, const Fp8LoraArgs* lora, hipStream_t stream) {
     APEXMI_REQUIRE(qa && sa && qw && sw && C, "gemm_fp8: null operand");
     APEXMI_REQUIRE(w_format == 0, "gemm_fp8: weight format %d is not e4m3fn (0): e5m2 weights take the bf16 path "
                                   "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16)", w_format);
@@ -302,11 +392,49 @@ extern "C" int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, con
     APEXMI_REQUIRE(tiles < (1ll << 31), "gemm_fp8: too many output tiles");
     Fp8Gemm G{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
               lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, (M + FBM - 1) / FBM, (N + FBN - 1) / FBN, apexmi_clk_ptr()};
+    if (lora != nullptr) {
+        const int Rp = lora->Rp;
+        APEXMI_REQUIRE(Rp >= 64 && Rp % 64 == 0, "gemm_fp8_lora: the padded rank Rp=%d must be a multiple of 64 (set_lora pads to that)", Rp);
+        APEXMI_REQUIRE(lora->t && lora->lb, "gemm_fp8_lora: null adapter operand (t %p, B' %p)", lora->t, lora->lb);
+        APEXMI_REQUIRE(lora->ldt >= Rp && lora->ldb >= Rp, "gemm_fp8_lora: rows of t and B' must be at least Rp=%d wide (ldt %lld, ldb %lld)",
+                       Rp, (long long)lora->ldt, (long long)lora->ldb);
+        APEXMI_REQUIRE(lora->ldt % 8 == 0 && lora->ldb % 8 == 0 && ((uintptr_t)lora->t % 16) == 0 && ((uintptr_t)lora->lb % 16) == 0,
+                       "gemm_fp8_lora: t and B' must be 16-byte aligned with leading dimensions that are multiples of 8 (ldt %lld, ldb %lld)",
+                       (long long)lora->ldt, (long long)lora->ldb);
+        APEXMI_REQUIRE(lora->ldt <= (1 << 22) && lora->ldb <= (1 << 22),
+                       "gemm_fp8_lora: leading dimensions above 2^22 elements are not supported (ldt %lld, ldb %lld)", (long long)lora->ldt,
+                       (long long)lora->ldb);
+        Fp8LoraGemm L{G, (const bf16_t*)lora->t, (const bf16_t*)lora->lb, lora->ldt, lora->ldb, Rp};
+        ApexmiProfScope prof(0, stream, 2.0 * M * N * ((double)K + Rp),
+                             (double)M * K + (double)N * K + 2.0 * ((double)M + N) * Rp + 2.0 * (double)M * N);
+        switch (epilogue) {
+            case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
+            case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
+            default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
+        }
+        return apexmi_check_launch("gemm_fp8_lora");
+    }
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (double)M * K + (double)N * K + 2.0 * (double)M * N);
     switch (epilogue) {
-        case APEXMI_EPI_BIAS: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
-        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
-        default: hipLaunchKernelGGL(gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES>, dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+        case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
+        default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
     }
     return apexmi_check_launch("gemm_fp8");
+}
+
+extern "C" int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format,
+                               const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K,
+                               int epilogue, const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
+    return gemm_fp8_run(qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, nullptr,
+                        (hipStream_t)stream_);
+}
+
+extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format,
+                                    const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K,
+                                    int epilogue, const float* gate, const void* R, int64_t ldr, const void* t, int64_t ldt,
+                                    const void* lb, int64_t ldb, int Rp, apexmi_stream_t stream_) {
+    const Fp8LoraArgs lora{t, ldt, lb, ldb, Rp};
+    return gemm_fp8_run(qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &lora,
+                        (hipStream_t)stream_);
 }

@@ -151,6 +151,8 @@ SIGNATURES = {
     "apexmi_quant_rows_fp8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp]),
     "apexmi_gemm_fp8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
                                   C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "apexmi_gemm_fp8_lora": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, vp, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, vp]),
     "apexmi_dequant_gguf": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_euler_step": (C.c_int, [vp, vp, vp, C.c_int64, C.c_float, C.c_int, vp]),
     "apexmi_prof_enable": (C.c_int, [C.c_int]),

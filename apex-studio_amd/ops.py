@@ -242,6 +242,9 @@ class Fp8Weight(ResidentWeight):
     activations per row to e4m3 and multiplies the resident codes directly (`gemm_fp8`), where `fp8_compute_route` allows it."""
 
     compute = "bf16"
+    # with compute == "fp8": what a record carrying run-time LoRA factors does.  "bf16" (the default) = the bf16 path above
+    # (_gemm_fp8_lora), "fp8" = the fp8 GEMM with the adapter tail (`fp8_lora_route`, `gemm_fp8(lora_t=, lora_B=)`)
+    lora_compute = "bf16"
 
     def __init__(self, q: torch.Tensor, scale: torch.Tensor):
         if q.dtype not in (torch.float8_e4m3fn, torch.float8_e5m2) or q.dim() != 2:
@@ -329,6 +332,13 @@ def _scratch(dev, n: int) -> torch.Tensor:
     return buf
 
 
+def _is_lora_buf(a, f8: "ResidentWeight", lora_buf) -> bool:
+    """Whether `lora_buf` is the padded activation buffer of `a` that run-time LoRA needs: same storage, rows and row stride,
+    at least K + Rp columns."""
+    return lora_buf is not None and lora_buf.data_ptr() == a.data_ptr() and lora_buf.stride(0) == a.stride(0) \
+        and lora_buf.shape[1] >= a.shape[1] + f8.lora_A.shape[0] and lora_buf.shape[0] == a.shape[0]
+
+
 def _gemm_fp8_lora(a, f8: "ResidentWeight", bias, out, epilogue, gate, residual, lora_buf):
     """epi(a W^T + (a A^T) B'^T + bias) for a resident-fp8 weight W with run-time LoRA factors, as TWO launches:
          t = a A^T                      [M, Rp] bf16 — the reference's `lora_A(x)` output, rounded as it is there — written into
@@ -343,8 +353,7 @@ def _gemm_fp8_lora(a, f8: "ResidentWeight", bias, out, epilogue, gate, residual,
     Rp = f8.lora_A.shape[0]
     if a.dtype != torch.bfloat16:
         raise NotImplementedError("run-time LoRA on resident-fp8 weights exists for bf16 activation storage only")
-    if lora_buf is None or lora_buf.data_ptr() != a.data_ptr() or lora_buf.stride(0) != a.stride(0) or lora_buf.shape[1] < K + Rp \
-            or lora_buf.shape[0] != M:
+    if not _is_lora_buf(a, f8, lora_buf):
         raise _l.ApexMIError(f"gemm: the weight carries run-time LoRA factors (rank {Rp} padded) and needs `lora_buf` = the activation "
                              f"buffer of `a` with >= {K + Rp} columns (got {None if lora_buf is None else tuple(lora_buf.shape)})")
     gemm(a, f8.lora_A, None, out=lora_buf[:, K:K + Rp])
@@ -394,6 +403,30 @@ def fp8_compute_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, ep
     return M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)
 
 
+def fp8_lora_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias",
+                   lora_buf: Optional[torch.Tensor] = None) -> bool:
+    """Whether `gemm(a, w, out=out, epilogue=epilogue, lora_buf=lora_buf)` on a record WITH run-time LoRA factors goes out as
+    skinny GEMM + quantise + `gemm_fp8(lora_t=, lora_B=)` (the fp8 GEMM with the bf16 adapter tail) instead of `_gemm_fp8_lora`.
+    Pure, like `fp8_compute_route`.  True only when ALL of these hold:
+      * `w` is (or carries) an e4m3 `Fp8Weight` with `compute == "fp8"` AND `lora_compute == "fp8"`, and it carries factors;
+      * `a` is bf16 and `out` is bf16 or None;
+      * the shape rules of `fp8_compute_route` hold;
+      * `lora_buf` is the padded activation buffer `_gemm_fp8_lora` requires (the skinny GEMM writes t behind `a`)."""
+    f8 = _fp8_of(w)
+    if not isinstance(f8, Fp8Weight) or f8.compute != "fp8" or f8.lora_compute != "fp8" or f8.q.dtype != torch.float8_e4m3fn \
+            or f8.lora_A is None:
+        return False
+    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
+        return False
+    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
+        return False
+    M, K = a.shape
+    N = f8.shape[0]
+    if not (M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)):
+        return False
+    return _is_lora_buf(a, f8, lora_buf)
+
+
 _fp8_act_scratch: dict = {}
 
 
@@ -432,10 +465,18 @@ def quant_rows_fp8(a: torch.Tensor, out: Optional[torch.Tensor] = None,
 
 def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
-             residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+             residual: Optional[torch.Tensor] = None, lora_t: Optional[torch.Tensor] = None,
+             lora_B: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M, N] (bf16) = epi((codes . w.q^T) * scales[m] * w.scale[n] + bias): e4m3 x e4m3 with f32 accumulation, both scales
     applied in the f32 epilogue.  `codes` / `scales` as `quant_rows_fp8` returns them; `w` an e4m3 `Fp8Weight` (e5m2 raises);
-    epilogue bias / gelu / gate_res."""
+    epilogue bias / gelu / gate_res.
+
+    `lora_t` [M, Rp] and `lora_B` [N, Rp] (bf16, both or neither, Rp a multiple of 64, row strides free): the run-time LoRA form,
+        out = epi(((codes . w.q^T) * scales[m]) * w.scale[n] + sum_r lora_t[m, r] lora_B[n, r] + bias)
+    — the scaled base product stays in the f32 accumulators, a bf16 MFMA tail adds the adapter term (rank ascending) into them,
+    and the result is rounded once."""
+    if (lora_t is None) != (lora_B is None):
+        raise _l.ApexMIError("gemm_fp8: lora_t and lora_B go together (both or neither)")
     _req(codes, torch.uint8, "gemm_fp8.codes")
     _req(scales, torch.float32, "gemm_fp8.scales")
     if not isinstance(w, Fp8Weight):
@@ -466,6 +507,18 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
         assert gate.is_contiguous() and gate.numel() == N
         assert residual.shape == (M, N) and residual.stride(1) == 1
         ldr = residual.stride(0)
+    if lora_t is not None:
+        _req(lora_t, torch.bfloat16, "gemm_fp8.lora_t")
+        _req(lora_B, torch.bfloat16, "gemm_fp8.lora_B")
+        assert lora_t.dim() == 2 and lora_B.dim() == 2 and lora_t.stride(1) == 1 and lora_B.stride(1) == 1
+        Rp = lora_t.shape[1]
+        assert lora_t.shape[0] == M and tuple(lora_B.shape) == (N, Rp)
+        rc = _l.load().apexmi_gemm_fp8_lora(codes.data_ptr(), codes.stride(0), scales.data_ptr(), w.q.data_ptr(), w.q.stride(0), fmt,
+                                            w.scale.data_ptr(), w.scale.numel(), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
+                                            epi, _ptr(gate), _ptr(residual), ldr, lora_t.data_ptr(), lora_t.stride(0),
+                                            lora_B.data_ptr(), lora_B.stride(0), Rp, _stream())
+        _l.check(rc, "gemm_fp8_lora")
+        return out
     rc = _l.load().apexmi_gemm_fp8(codes.data_ptr(), codes.stride(0), scales.data_ptr(), w.q.data_ptr(), w.q.stride(0), fmt,
                                    w.scale.data_ptr(), w.scale.numel(), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K, epi,
                                    _ptr(gate), _ptr(residual), ldr, _stream())
@@ -488,7 +541,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
 
     OPT-IN FP8 COMPUTE: a resident e4m3 `Fp8Weight` with `compute == "fp8"` takes `quant_rows_fp8` (codes and
     scales in a per-stream scratch) + `gemm_fp8` instead of dequantise + bf16 GEMM when `fp8_compute_route` says so.  Today's
-    path, unchanged, is taken by everything else: `compute == "bf16"` (the default), run-time LoRA factors attached, e5m2
+    path, unchanged, is taken by everything else: `compute == "bf16"` (the default), run-time LoRA factors attached (unless the
+    record also has `lora_compute == "fp8"` and `fp8_lora_route` says so: then the fp8 GEMM runs with the adapter tail), e5m2
     weights, GGUF records, float activations (the f32-storage mode), a float `out` (the f32 residual stream), K not a multiple
     of 128 or N not a multiple of 16, and epilogues other than bias / gelu / gate_res.  `gemm_grouped` never routes."""
     _req_act(a, "gemm.a")
@@ -498,6 +552,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         quant_rows_fp8(a, out=qa, scale_out=sa)
         return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     if f8 is not None and f8.lora_A is not None:
+        if fp8_lora_route(a, f8, out, epilogue, lora_buf):
+            K, Rp = a.shape[1], f8.lora_A.shape[0]
+            t = lora_buf[:, K:K + Rp]
+            gemm(a, f8.lora_A, None, out=t)                      # t = a A^T in bf16, as _gemm_fp8_lora produces it
+            qa, sa = _act_scratch(a.device, a.shape[0], K)
+            quant_rows_fp8(a, out=qa, scale_out=sa)
+            return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual, lora_t=t, lora_B=f8.lora_B)
         return _gemm_fp8_lora(a, f8, bias, out, epilogue, gate, residual, lora_buf)
     w = _bf16_weight(w, a.dtype == torch.float32)
     _req(w, torch.bfloat16, "gemm.w")

@@ -225,19 +225,27 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         self._band_plans = {}
         return self
 
-    def set_fp8_compute(self, on: bool):
+    def set_fp8_compute(self, on: bool, lora: bool = False):
         """Opt-in approximation: the block Linears whose weights are RESIDENT e4m3 records (a `keep_fp8=True` load:
         the fused q|k|v, the attention outputs, the cross-attention q and k|v, the two FFN Linears) quantise their activations per
         row to e4m3 and multiply in fp8 (`ops.gemm_fp8`) instead of dequantising the weight and multiplying in bf16.  Everything
         else — embedders, modulation GEMVs, proj_out, attention — stays bf16, and so does any such Linear `ops.gemm` cannot route
         (run-time LoRA attached, e5m2 records, the f32 residual stream).  False restores today's launches bit for bit.  A speed
-        option: about 3.7e-2 rel-L2 per GEMM against the f32 product."""
+        option: about 3.7e-2 rel-L2 per GEMM against the f32 product.
+
+        `lora=True` (needs `on=True`): a record that carries run-time LoRA factors stays on the fp8 GEMM as well — the adapter term
+        `(x A^T) B'^T` is added in bf16 x bf16 by a tail of the same kernel, into the scaled f32 accumulators
+        (`ops.fp8_lora_route`) — instead of falling back to the bf16 path.  The flag lives on the records, so adapters loaded
+        before or after this call both take it.  `lora=False` (the default) leaves every launch as it is today."""
+        if lora and not on:
+            raise ValueError("wan.mi355: set_fp8_compute(lora=True) needs on=True: the adapter tail belongs to the fp8 GEMM")
         recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values() if isinstance(r, ops.Fp8Weight)}
         if not recs:
             raise _l.ApexMIError("wan.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
                                  "fp8-scaled checkpoint with keep_fp8=True")
         for r in recs.values():
             r.compute = "fp8" if on else "bf16"
+            r.lora_compute = "fp8" if lora else "bf16"
         self._fp8_compute = bool(on)
         return self
 

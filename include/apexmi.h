@@ -761,6 +761,20 @@ int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, const void* qw
                     int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                     const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream);
 
+/* apexmi_gemm_fp8_lora — apexmi_gemm_fp8 with a RUN-TIME LoRA adapter term.  Replaces PEFT's `base(x) + scale * B(A(x))` around
+ * FPScaledLinear (R/src/lora/manager.py:454-606) for a resident e4m3fn weight, without dequantising it:
+ *     acc      = sum_k qa[m, k] qw[n, k]                 e4m3 x e4m3, f32 accumulation (as apexmi_gemm_fp8)
+ *     acc      = (acc * sa[m]) * sw[n]                   two f32 multiplies, in the accumulators
+ *     acc     += sum_r t[m, r] lb[n, r]                  bf16 x bf16, f32 accumulation, rank ascending, into the same accumulators
+ *     C[m, n]  = epi(acc + bias[n])                      one bf16 rounding
+ * t bf16 [M, Rp] (row stride ldt elements): the down projection a A^T, already rounded to bf16 as the reference's lora_A(x) is;
+ * lb bf16 [N, Rp] (row stride ldb elements): the up factors times the adapter scale.  Rp >= 64 and Rp % 64 == 0 (zero-padded);
+ * ldt, ldb >= Rp, % 8 == 0 and <= 2^22; t and lb 16-byte aligned.  Everything else as apexmi_gemm_fp8. */
+int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format, const void* sw,
+                         int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
+                         const float* gate, const void* R, int64_t ldr, const void* t, int64_t ldt, const void* lb, int64_t ldb,
+                         int Rp, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
