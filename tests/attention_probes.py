@@ -11,7 +11,12 @@ Probe B, selection: q_i = 8 e_a(i), k_j = 4 e_a'(j) with softmax_scale 1: the ta
 allowed key 0, so out[i] = V[pi(i)] up to one rounding of P and one of the store: |out - V[pi]| <= 2^-7 |V[pi]| + Sk 2^-40 max|V|
 (bf16; 2^-10 for f16).  Only a subset T of the keys (at most one per code) carries a code, the other keys are zero rows (score 0)
 or DECOYS: keys that score 64 for the rows of one code and that the rule excludes for every such row.  A rule error that admits
-a decoy, or a row that reads another K / V row, is visibly wrong."""
+a decoy, or a row that reads another K / V row, is visibly wrong.
+
+Neither lets the VALUE of a score or of a probability matter (A: every score 0; B: one column of D, a 46-binade argmax).  Probe C,
+graded weights, does: tests/attention_weight_probes.py (+-1 operands, integer scores over all D columns, weights graded over a
+dozen binades, the same V codes, weights_of and case tables as here; the bar (2 u + e_s) |ref| and the LSE bar e_l are derived
+there)."""
 import functools
 import math
 
