@@ -2,6 +2,7 @@
 // q/k RMSNorm + RoPE + layout pass, V transpose, conditioning GEMV, timestep embedding, casts and
 // the Euler scheduler axpy.  All of them move 16 bytes per lane and keep statistics in f32.
 #include "common.h"
+#include "fp8_quant.h"   // FP8_MAX, quant1: the norm that quantises its own output
 
 namespace {
 
@@ -25,90 +26,67 @@ APEXMI_DEVICE float block_sum_256(float x, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+APEXMI_DEVICE float block_max_256(float x, float* red) {
+    x = wave_max(x);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[w] = x;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+// 4 floats that hold bf16 values -> 4 e4m3fn codes in one dword: quant4 (fp8_quant.h) on values that are already unpacked
+APEXMI_DEVICE uint32_t quant4_f32(const float* f, float scale) {
+    int r = 0;
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(f[0], scale), quant1(f[1], scale), r, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(f[2], scale), quant1(f[3], scale), r, true);
+    return (uint32_t)r;
+}
+
+// The store step of the quantising norms (apexmi_ln_modulate_quant_fp8): the 8 values are rounded to bf16 by store8<bf16_t>'s
+// pack, stored only if `op` is not null, and the ROUNDED values replace the row registers `keep` — what apexmi_quant_rows_fp8
+// would read back — while `amax` follows their absolute maximum.
+APEXMI_DEVICE void ln_quant_keep8(bf16_t* op, const float* y, float* keep, float& amax) {
+    const u32x4 p = pack8(y);
+    if (op != nullptr) *(u32x4*)op = p;
+    unpack8(p, keep);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(keep[j]));
+}
+
+// apexmi_quant_rows_fp8's scale and codes from the rounded row registers: 8 codes (8 bytes) per lane and chunk
+APEXMI_DEVICE float quant_row_scale(float amax) { return amax == 0.f ? 1.0f : __fdiv_rn(amax, FP8_MAX); }
+APEXMI_DEVICE void quant_store8(uint8_t* q, const float* keep, float s) {
+    *(u32x2*)q = u32x2{quant4_f32(keep, s), quant4_f32(keep + 4, s)};
+}
+
+// The kernel bodies live in ln_modulate_row.inc / ln_modulate_wave_rows.inc, included once per kernel: the plain kernels and the
+// quantising ones (apexmi_ln_modulate_quant_fp8) share one source of the arithmetic, and the plain kernels' text is unchanged.
 template <typename T, int NIT, typename TO = T>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(
     const T* __restrict__ x, int64_t ldx, TO* __restrict__ out, int64_t ldo, int M, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2) {
-    __shared__ float red[4];
-    const int row = blockIdx.x;
-    if (row < split) {  // rows [0, split) take the second modulation set (text stream of a joint buffer)
-        scale = scale2;
-        shift = shift2;
-    }
-    const int nchunk = C >> 3;
-    const T* xp = x + (int64_t)row * ldx;
-    float v[NIT][8];
-    float sum = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int c = it * 256 + threadIdx.x;
-        if (c < nchunk) {
-            load8<T>(xp + c * 8, v[it]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum += v[it][j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[it][j] = 0.0f;
-        }
-    }
-    float mean = 0.0f;
-    if (!rms) mean = block_sum_256(sum, red) / (float)C;
-    float sq = 0.0f;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int c = it * 256 + threadIdx.x;
-        if (c < nchunk) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = v[it][j] - mean;
-                sq += d * d;
-            }
-        }
-    }
-    const float rstd = rsqrtf(block_sum_256(sq, red) / (float)C + eps);
-    TO* op = out + (int64_t)row * ldo;
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-        const int c = it * 256 + threadIdx.x;
-        if (c < nchunk) {
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = (v[it][j] - mean) * rstd;
-            if (gamma != nullptr) {
-                float g[8];
-                unpack8(*(const u32x4*)(gamma + c * 8), g);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] *= g[j];
-            }
-            if (beta != nullptr) {
-                float bt[8];
-                unpack8(*(const u32x4*)(beta + c * 8), bt);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] += bt[j];
-            }
-            if (scale != nullptr) {
-                const f32x4 s0 = *(const f32x4*)(scale + c * 8);
-                const f32x4 s1 = *(const f32x4*)(scale + c * 8 + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    y[j] *= 1.0f + s0[j];
-                    y[j + 4] *= 1.0f + s1[j];
-                }
-            }
-            if (shift != nullptr) {
-                const f32x4 s0 = *(const f32x4*)(shift + c * 8);
-                const f32x4 s1 = *(const f32x4*)(shift + c * 8 + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    y[j] += s0[j];
-                    y[j + 4] += s1[j];
-                }
-            }
-            store8<TO>(op + c * 8, y);
-        }
-    }
+#define LN_QUANT 0
+#include "ln_modulate_row.inc"
+#undef LN_QUANT
+}
+
+// norm + modulate + per-row e4m3 quantise in one pass (apexmi_ln_modulate_quant_fp8): ln_modulate_kernel<T, NIT, bf16_t>'s
+// arithmetic, then apexmi_quant_rows_fp8's on the rounded row, which never leaves the registers.  `out` may be null (no bf16 row
+// is stored); codes [M, C] uint8 (row stride ldq bytes), scales [M].
+template <typename T, int NIT>
+__global__ __launch_bounds__(256) void ln_modulate_quant_kernel(
+    const T* __restrict__ x, int64_t ldx, bf16_t* __restrict__ out, int64_t ldo, int M, int C,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
+    const float* __restrict__ scale2, const float* __restrict__ shift2, uint8_t* __restrict__ codes, int64_t ldq,
+    float* __restrict__ scales) {
+    typedef bf16_t TO;
+#define LN_QUANT 1
+#include "ln_modulate_row.inc"
+#undef LN_QUANT
 }
 
 // s + a * a with the product rounded on its own, never contracted to an fma.  The square of a float is inexact, so the two forms
@@ -131,82 +109,23 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2) {
-    // NR rows per wave (`ln.wave` = NR): all NR rows' loads are issued before the first reduction, so a wave has NR x NCH
-    // 16-byte loads in flight and the second row's statistics / stores overlap the first row's store drain.  Per row the
-    // arithmetic is the same for every NR (bit-identical outputs).
-    const int lane = threadIdx.x & 63;
-    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * NR;
-    if (row0 >= M) return;
-    float v[NR][NCH][8];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int row = min(row0 + r, M - 1);
-        const T* xp = x + (int64_t)row * ldx;
-#pragma unroll
-        for (int it = 0; it < NCH; ++it) load8<T>(xp + (it * 64 + lane) * 8, v[r][it]);
-    }
-#pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        const int row = row0 + r;
-        if (row >= M) break;
-        const float* sc = row < split ? scale2 : scale;
-        const float* sh = row < split ? shift2 : shift;
-        float sum = 0.0f;
-#pragma unroll
-        for (int it = 0; it < NCH; ++it)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sum += v[r][it][j];
-        const float mean = rms ? 0.0f : wave_sum(sum) / (float)C;
-        float sq = 0.0f;
-#pragma unroll
-        for (int it = 0; it < NCH; ++it)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d = v[r][it][j] - mean;
-                if constexpr (sizeof(T) == 4) sq = add_square_unfused(sq, d);
-                else sq += d * d;
-            }
-        const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-        TO* op = out + (int64_t)row * ldo;
-#pragma unroll
-        for (int it = 0; it < NCH; ++it) {
-            const int c = it * 64 + lane;
-            float y[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = (v[r][it][j] - mean) * rstd;
-            if (gamma != nullptr) {
-                float g[8];
-                unpack8(*(const u32x4*)(gamma + c * 8), g);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] *= g[j];
-            }
-            if (beta != nullptr) {
-                float bt[8];
-                unpack8(*(const u32x4*)(beta + c * 8), bt);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] += bt[j];
-            }
-            if (sc != nullptr) {
-                const f32x4 s0 = *(const f32x4*)(sc + c * 8);
-                const f32x4 s1 = *(const f32x4*)(sc + c * 8 + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    y[j] *= 1.0f + s0[j];
-                    y[j + 4] *= 1.0f + s1[j];
-                }
-            }
-            if (sh != nullptr) {
-                const f32x4 s0 = *(const f32x4*)(sh + c * 8);
-                const f32x4 s1 = *(const f32x4*)(sh + c * 8 + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    y[j] += s0[j];
-                    y[j + 4] += s1[j];
-                }
-            }
-            store8<TO>(op + c * 8, y);
-        }
-    }
+#define LN_QUANT 0
+#include "ln_modulate_wave_rows.inc"
+#undef LN_QUANT
+}
+
+// ln_modulate_quant_kernel's wave-per-row twin: ln_modulate_wave_kernel<T, NCH, NR, bf16_t>'s arithmetic, then the quantiser's
+template <typename T, int NCH, int NR>
+__global__ __launch_bounds__(256) void ln_modulate_wave_quant_kernel(
+    const T* __restrict__ x, int64_t ldx, bf16_t* __restrict__ out, int64_t ldo, int M, int C,
+    const float* __restrict__ scale, const float* __restrict__ shift,
+    const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
+    const float* __restrict__ scale2, const float* __restrict__ shift2, uint8_t* __restrict__ codes, int64_t ldq,
+    float* __restrict__ scales) {
+    typedef bf16_t TO;
+#define LN_QUANT 1
+#include "ln_modulate_wave_rows.inc"
+#undef LN_QUANT
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1014,6 +933,68 @@ extern "C" int apexmi_ln_modulate(const void* x, int64_t ldx, void* out, int64_t
 int g_ln_wave = 1;  // apexmi_tune_set("ln.wave", 0/1/2) for C in {3072, 3584, 5120}: 0 row-per-workgroup kernel | 1 one row per wave | 2 two rows per wave (bf16 x; bit-identical to 1)
 void apexmi_set_ln_wave(int v) { g_ln_wave = v; }
 
+// The dispatch of every norm entry point: which kernel family and how many rows per wave a (T, C, `ln.wave`) runs.  QUANT =
+// apexmi_ln_modulate_quant_fp8: the same choice, the chosen kernel's quantising twin (the two families sum in different shapes,
+// so the twin of the OTHER family would not reproduce apexmi_ln_modulate2's rows).
+template <typename T, typename TO, bool QUANT>
+static int ln_modulate2_launch(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
+                               const float* scale, const float* shift, const void* gamma,
+                               const void* beta, float eps, int rms, int split,
+                               const float* scale2, const float* shift2, void* codes, int64_t ldq, float* scales,
+                               hipStream_t stream) {
+    // QUANT: x in, 1 byte of codes out, the bf16 row only if asked for, 4 bytes of scale per row
+    ApexmiProfScope prof(3, stream, 0.0, QUANT ? (double)(sizeof(T) + 1 + (out ? sizeof(TO) : 0)) * (double)M * C + 4.0 * M
+                                               : (double)(sizeof(T) + sizeof(TO)) * (double)M * C);
+#define LNW_LAUNCH_R(N, R)                                                                                                      \
+    do {                                                                                                                        \
+        if constexpr (!QUANT)                                                                                                   \
+            hipLaunchKernelGGL((ln_modulate_wave_kernel<T, N, R, TO>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, (const T*)x, ldx, \
+                               (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms,          \
+                               split, scale2, shift2);                                                                          \
+        else if constexpr (R == 1 || sizeof(T) == 2)                                                                            \
+            hipLaunchKernelGGL((ln_modulate_wave_quant_kernel<T, N, R>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, \
+                               (const T*)x, ldx, (bf16_t*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                   \
+                               (const bf16_t*)beta, eps, rms, split, scale2, shift2, (uint8_t*)codes, ldq, scales);             \
+    } while (0)
+#define LNW_LAUNCH(N)                         \
+    do {                                      \
+        if (g_ln_wave >= 2 && sizeof(T) == 2) \
+            LNW_LAUNCH_R(N, 2);               \
+        else                                  \
+            LNW_LAUNCH_R(N, 1);               \
+    } while (0)
+    if (g_ln_wave && C % 512 == 0) {
+        bool done = true;
+        switch (C / 512) {
+            case 6: LNW_LAUNCH(6); break;
+            case 7: LNW_LAUNCH(7); break;
+            case 10: LNW_LAUNCH(10); break;
+            default: done = false;
+        }
+        if (done) return apexmi_check_launch(QUANT ? "ln_modulate_quant_fp8" : "ln_modulate");
+    }
+#undef LNW_LAUNCH_R
+#undef LNW_LAUNCH
+    const int nit = (C / 8 + 255) / 256;
+#define LN_LAUNCH(N)                                                                                                          \
+    do {                                                                                                                      \
+        if constexpr (!QUANT)                                                                                                 \
+            hipLaunchKernelGGL((ln_modulate_kernel<T, N, TO>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx,               \
+                               (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                                       \
+                               (const bf16_t*)beta, eps, rms, split, scale2, shift2);                                         \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((ln_modulate_quant_kernel<T, N>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx,             \
+                               (bf16_t*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms,    \
+                               split, scale2, shift2, (uint8_t*)codes, ldq, scales);                                          \
+    } while (0)
+    if (nit <= 1) LN_LAUNCH(1);
+    else if (nit <= 2) LN_LAUNCH(2);
+    else if (nit <= 3) LN_LAUNCH(3);
+    else LN_LAUNCH(4);
+#undef LN_LAUNCH
+    return apexmi_check_launch(QUANT ? "ln_modulate_quant_fp8" : "ln_modulate");
+}
+
 template <typename T, typename TO = T>
 static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
                              const float* scale, const float* shift, const void* gamma,
@@ -1031,41 +1012,47 @@ static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo,
                    "ln_modulate: rows must be 16-byte aligned");
     APEXMI_REQUIRE((!scale || ((uintptr_t)scale % 16) == 0) && (!shift || ((uintptr_t)shift % 16) == 0),
                    "ln_modulate: scale/shift must be 16-byte aligned");
-    ApexmiProfScope prof(3, stream, 0.0, (double)(sizeof(T) + sizeof(TO)) * (double)M * C);
-#define LNW_LAUNCH_R(N, R)                                                                                          \
-    hipLaunchKernelGGL((ln_modulate_wave_kernel<T, N, R, TO>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, (const T*)x, ldx, \
-                       (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms, \
-                       split, scale2, shift2)
-#define LNW_LAUNCH(N)                         \
-    do {                                      \
-        if (g_ln_wave >= 2 && sizeof(T) == 2) \
-            LNW_LAUNCH_R(N, 2);               \
-        else                                  \
-            LNW_LAUNCH_R(N, 1);               \
-    } while (0)
-    if (g_ln_wave && C % 512 == 0) {
-        bool done = true;
-        switch (C / 512) {
-            case 6: LNW_LAUNCH(6); break;
-            case 7: LNW_LAUNCH(7); break;
-            case 10: LNW_LAUNCH(10); break;
-            default: done = false;
-        }
-        if (done) return apexmi_check_launch("ln_modulate");
-    }
-#undef LNW_LAUNCH_R
-#undef LNW_LAUNCH
-    const int nit = (C / 8 + 255) / 256;
-#define LN_LAUNCH(N)                                                                                  \
-    hipLaunchKernelGGL((ln_modulate_kernel<T, N, TO>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx, \
-                       (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                   \
-                       (const bf16_t*)beta, eps, rms, split, scale2, shift2)
-    if (nit <= 1) LN_LAUNCH(1);
-    else if (nit <= 2) LN_LAUNCH(2);
-    else if (nit <= 3) LN_LAUNCH(3);
-    else LN_LAUNCH(4);
-#undef LN_LAUNCH
-    return apexmi_check_launch("ln_modulate");
+    return ln_modulate2_launch<T, TO, false>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2,
+                                             nullptr, 0, nullptr, stream);
+}
+
+template <typename T>
+static int ln_modulate_quant_impl(const void* x, int64_t ldx, void* out, int64_t ldo, void* codes, int64_t ldq, float* scales,
+                                  int M, int C, const float* scale, const float* shift, const void* gamma, const void* beta,
+                                  float eps, int rms, int split, const float* scale2, const float* shift2, hipStream_t stream) {
+    APEXMI_REQUIRE(ldx >= C && ldx % (16 / (int)sizeof(T)) == 0 && ((uintptr_t)x % 16) == 0 && ldq >= C && ldq % 16 == 0 &&
+                       ((uintptr_t)codes % 16) == 0 && (!out || (ldo >= C && ldo % 8 == 0 && ((uintptr_t)out % 16) == 0)),
+                   "ln_modulate_quant_fp8: rows must be 16-byte aligned and at least C wide (ldx %lld, ldq %lld, ldo %lld)",
+                   (long long)ldx, (long long)ldq, (long long)ldo);
+    return ln_modulate2_launch<T, bf16_t, true>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2,
+                                                codes, ldq, scales, stream);
+}
+
+// norm + modulate + per-row e4m3 quantise (include/apexmi.h): apexmi_ln_modulate2 / apexmi_ln_modulate2_f32in followed by
+// apexmi_quant_rows_fp8, as one launch of the kernel the norm alone would have run, in its quantising form
+extern "C" int apexmi_ln_modulate_quant_fp8(const void* x, int64_t ldx, int x_dtype, void* out, int64_t ldo, void* codes,
+                                            int64_t ldq, float* scales, int M, int C, const float* scale, const float* shift,
+                                            const void* gamma, const void* beta, float eps, int rms, int split,
+                                            const float* scale2, const float* shift2, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(x && codes && scales, "ln_modulate_quant_fp8: null operand");
+    APEXMI_REQUIRE(x_dtype == APEXMI_BF16 || x_dtype == APEXMI_F32, "ln_modulate_quant_fp8: x_dtype=%d must be APEXMI_BF16 or APEXMI_F32",
+                   x_dtype);
+    APEXMI_REQUIRE(M >= 1, "ln_modulate_quant_fp8: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(C >= 128 && C % 128 == 0 && C <= LN_MAX_C, "ln_modulate_quant_fp8: C=%d must be a multiple of 128 and <= %d", C,
+                   LN_MAX_C);
+    APEXMI_REQUIRE(split >= 0 && split <= M, "ln_modulate_quant_fp8: split=%d outside [0, M]", split);
+    APEXMI_REQUIRE((!scale || ((uintptr_t)scale % 16) == 0) && (!shift || ((uintptr_t)shift % 16) == 0),
+                   "ln_modulate_quant_fp8: scale/shift must be 16-byte aligned");
+    APEXMI_REQUIRE(split == 0 || ((!scale2 || ((uintptr_t)scale2 % 16) == 0) && (!shift2 || ((uintptr_t)shift2 % 16) == 0)),
+                   "ln_modulate_quant_fp8: scale2/shift2 must be 16-byte aligned");
+    APEXMI_REQUIRE((!gamma || ((uintptr_t)gamma % 16) == 0) && (!beta || ((uintptr_t)beta % 16) == 0),
+                   "ln_modulate_quant_fp8: gamma/beta must be 16-byte aligned");
+    if (x_dtype == APEXMI_F32)
+        return ln_modulate_quant_impl<float>(x, ldx, out, ldo, codes, ldq, scales, M, C, scale, shift, gamma, beta, eps, rms, split,
+                                             scale2, shift2, stream);
+    return ln_modulate_quant_impl<bf16_t>(x, ldx, out, ldo, codes, ldq, scales, M, C, scale, shift, gamma, beta, eps, rms, split,
+                                          scale2, shift2, stream);
 }
 
 extern "C" int apexmi_ln_modulate2(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,

@@ -3,13 +3,12 @@
 // per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.  The run-time LoRA form
 // (apexmi_gemm_fp8_lora) applies them to the accumulators instead and adds the adapter term t . B'^T by a bf16 MFMA tail.
 #include "common.h"
+#include "fp8_quant.h"   // FP8_MAX, quant1, quant4
 #include <type_traits>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-constexpr float FP8_MAX = 448.0f;        // largest finite e4m3fn value
 
 // ---- apexmi_quant_rows_fp8 ----------------------------------------------------------------------------------------------------
 // One wave per ROW PAIR (rows 2p, 2p + 1): the loads of both rows are in flight together.  Pass 1 reads the pair for its two
@@ -26,19 +25,6 @@ APEXMI_DEVICE float absmax16(const u32x4 a, const u32x4 b) {
         m = fmaxf(m, fmaxf(fabsf(bf16_lo(b[i])), fabsf(bf16_hi(b[i]))));
     }
     return m;
-}
-
-APEXMI_DEVICE float quant1(float x, float scale) {
-    const float y = __fdiv_rn(x, scale);
-    return fminf(fmaxf(y, -FP8_MAX), FP8_MAX);
-}
-
-// 4 bf16 (2 dwords) -> 4 e4m3fn codes in one dword (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950, round to nearest even)
-APEXMI_DEVICE uint32_t quant4(uint32_t lo, uint32_t hi, float scale) {
-    int r = 0;
-    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(bf16_lo(lo), scale), quant1(bf16_hi(lo), scale), r, false);
-    r = __builtin_amdgcn_cvt_pk_fp8_f32(quant1(bf16_lo(hi), scale), quant1(bf16_hi(hi), scale), r, true);
-    return (uint32_t)r;
 }
 
 __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __restrict__ a, int64_t lda, int M, int K,

@@ -149,6 +149,8 @@ SIGNATURES = {
     "apexmi_cast_bf16_to_f32": (C.c_int, [vp, vp, C.c_int64, vp]),
     "apexmi_dequant_fp8_scaled": (C.c_int, [vp, C.c_int, vp, C.c_int64, C.c_int64, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_quant_rows_fp8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, vp]),
+    "apexmi_ln_modulate_quant_fp8": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp,
+                                               vp, C.c_float, C.c_int, C.c_int, vp, vp, vp]),
     "apexmi_gemm_fp8": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
                                   C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
     "apexmi_gemm_fp8_lora": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,

@@ -427,6 +427,32 @@ def fp8_lora_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilo
     return _is_lora_buf(a, f8, lora_buf)
 
 
+def fp8_norm_quant_route(x: torch.Tensor, xn: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias",
+                         lora_buf: Optional[torch.Tensor] = None, row_read_later: bool = False) -> Tuple[bool, bool]:
+    """Whether the pair `ln_modulate(x, ..., out=xn)` -> `gemm(xn, w, out=out, epilogue=epilogue, lora_buf=lora_buf)` may go out as
+    `ln_modulate_quant_fp8` -> `gemm(..., quantised=)`, i.e. the norm writes the e4m3 codes and row scales itself and the GEMM's
+    own `quant_rows_fp8` launch disappears.  Returns (fuse, need_row).  Pure, like `fp8_compute_route`: dtypes, shapes and strides
+    only (CPU tensors are fine).
+      fuse      the GEMM takes its fp8 route (`fp8_compute_route` or `fp8_lora_route` on `xn`) AND the fused norm accepts the
+                pair: `x` bf16 or float32 (the f32 residual stream) [M, C] with 16-byte rows, `xn` bf16 of the same shape,
+                C % 128 == 0 and C <= 8192.  False = run today's launches.
+      need_row  the bf16 row must still be stored (pass `out=xn` to the fused norm): the weight carries run-time LoRA factors
+                (the skinny GEMM reads `xn`), or the caller says something else reads `xn` (`row_read_later`).  False only
+                with `fuse`."""
+    if x.dim() != 2 or xn.dim() != 2 or tuple(x.shape) != tuple(xn.shape) or x.stride(1) != 1 or xn.stride(1) != 1:
+        return False, True
+    if x.dtype not in (torch.bfloat16, torch.float32) or xn.dtype != torch.bfloat16:
+        return False, True
+    M, Cc = x.shape
+    if M < 1 or Cc % 128 != 0 or Cc > 8192 or x.stride(0) % (16 // x.element_size()) != 0 or xn.stride(0) % 8 != 0:
+        return False, True
+    if fp8_compute_route(xn, w, out, epilogue):
+        return True, bool(row_read_later)
+    if fp8_lora_route(xn, w, out, epilogue, lora_buf):
+        return True, True
+    return False, True
+
+
 _fp8_act_scratch: dict = {}
 
 
@@ -461,6 +487,60 @@ def quant_rows_fp8(a: torch.Tensor, out: Optional[torch.Tensor] = None,
     _l.check(_l.load().apexmi_quant_rows_fp8(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
                                              _stream()), "quant_rows_fp8")
     return out, scale_out
+
+
+def _check_quantised(a: torch.Tensor, quantised) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`gemm(quantised=)`: (codes, scales) must be what quant_rows_fp8(a) would return in shape and type."""
+    qa, sa = quantised
+    _req(qa, torch.uint8, "gemm.quantised codes")
+    _req(sa, torch.float32, "gemm.quantised scales")
+    if tuple(qa.shape) != tuple(a.shape) or qa.stride(1) != 1 or sa.numel() != a.shape[0] or not sa.is_contiguous():
+        raise _l.ApexMIError(f"gemm: quantised=(codes {tuple(qa.shape)}, scales {tuple(sa.shape)}) does not fit a {tuple(a.shape)}")
+    return qa, sa
+
+
+def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                          gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                          rms: bool = False, split: int = 0, scale2: Optional[torch.Tensor] = None,
+                          shift2: Optional[torch.Tensor] = None, codes: Optional[torch.Tensor] = None,
+                          scale_out: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`ln_modulate(x, ...)` into bf16 followed by `quant_rows_fp8` on its output, as ONE launch: -> (codes uint8 [M, C], scales
+    float32 [M]), bit-identical to the two launches.  `x` bf16, or float32 (the f32 residual stream); C % 128 == 0.  `out`
+    (optional, bf16 [M, C], row stride free): also receives the normalised rows, bit-identical to `ln_modulate(x, ..., out=out)`;
+    None = the bf16 rows are never stored (3 bytes per element moved instead of 7).  `codes` / `scale_out` default to the
+    per-stream activation scratch of `gemm`'s fp8 route, valid until that stream's next fp8 GEMM or fused norm."""
+    _req(x, None, "ln_modulate_quant_fp8.x")
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _l.ApexMIError(f"ln_modulate_quant_fp8.x: expected torch.bfloat16 or torch.float32, got {x.dtype}")
+    assert x.dim() == 2 and x.stride(1) == 1
+    M, Cc = x.shape
+    if codes is None and scale_out is None:
+        codes, scale_out = _act_scratch(x.device, M, Cc)
+    if codes is None:
+        codes = torch.empty((M, Cc), dtype=torch.uint8, device=x.device)
+    if scale_out is None:
+        scale_out = torch.empty(M, dtype=torch.float32, device=x.device)
+    _req(codes, torch.uint8, "ln_modulate_quant_fp8.codes")
+    _req(scale_out, torch.float32, "ln_modulate_quant_fp8.scale_out")
+    assert codes.shape == (M, Cc) and codes.stride(1) == 1 and scale_out.is_contiguous() and scale_out.numel() == M
+    if out is not None:
+        _req(out, torch.bfloat16, "ln_modulate_quant_fp8.out")
+        assert out.shape == (M, Cc) and out.stride(1) == 1
+    for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
+        if t is not None:
+            _req(t, torch.float32, "ln_modulate_quant_fp8." + nm)
+            assert t.is_contiguous() and t.numel() == Cc
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _req(t, torch.bfloat16, "ln_modulate_quant_fp8." + nm)
+            assert t.is_contiguous() and t.numel() == Cc
+    rc = _l.load().apexmi_ln_modulate_quant_fp8(
+        x.data_ptr(), x.stride(0), _l.F32 if x.dtype == torch.float32 else _l.BF16, _ptr(out), 0 if out is None else out.stride(0),
+        codes.data_ptr(), codes.stride(0), scale_out.data_ptr(), M, Cc, _ptr(scale), _ptr(shift), _ptr(gamma), _ptr(beta),
+        float(eps), 1 if rms else 0, int(split), _ptr(scale2), _ptr(shift2), _stream())
+    _l.check(rc, "ln_modulate_quant_fp8")
+    return codes, scale_out
 
 
 def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None,
@@ -533,7 +613,8 @@ _EPI = {"bias": _l.EPI_BIAS, "gelu": _l.EPI_BIAS_GELU, "gate_res": _l.EPI_BIAS_G
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, epilogue: str = "bias",
          gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-         lora_buf: Optional[torch.Tensor] = None) -> torch.Tensor:
+         lora_buf: Optional[torch.Tensor] = None,
+         quantised: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  2-D operands, last dim contiguous; a / out / residual bf16, or float32
     in the f32-storage verification mode (w and bias stay bf16).  A bf16 `a` with a float32 `out` (and `residual`) is the
     f32 RESIDUAL STREAM: the same launch with the float epilogue, no split of `a`.  `lora_buf`: see _gemm_fp8_lora (ignored
@@ -544,20 +625,35 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     path, unchanged, is taken by everything else: `compute == "bf16"` (the default), run-time LoRA factors attached (unless the
     record also has `lora_compute == "fp8"` and `fp8_lora_route` says so: then the fp8 GEMM runs with the adapter tail), e5m2
     weights, GGUF records, float activations (the f32-storage mode), a float `out` (the f32 residual stream), K not a multiple
-    of 128 or N not a multiple of 16, and epilogues other than bias / gelu / gate_res.  `gemm_grouped` never routes."""
+    of 128 or N not a multiple of 16, and epilogues other than bias / gelu / gate_res.  `gemm_grouped` never routes.
+
+    `quantised=(codes, scales)`: the activations of the fp8 route ALREADY quantised — what `quant_rows_fp8(a)` would return, as
+    `ln_modulate_quant_fp8` produces it in the norm's own launch — so the route skips its quantise launch.  With
+    `fp8_compute_route` only the shape and dtype of `a` are read (the norm may not have stored its rows at all); with
+    `fp8_lora_route` the skinny GEMM still reads the bf16 `a`.  The caller decides BEFOREHAND with `fp8_norm_quant_route`: a call
+    whose GEMM takes neither route raises instead of quietly multiplying an `a` that may never have been written."""
     _req_act(a, "gemm.a")
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
-        qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
-        quant_rows_fp8(a, out=qa, scale_out=sa)
+        if quantised is not None:
+            qa, sa = _check_quantised(a, quantised)
+        else:
+            qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
+            quant_rows_fp8(a, out=qa, scale_out=sa)
         return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
+    if quantised is not None and not (f8 is not None and f8.lora_A is not None and fp8_lora_route(a, f8, out, epilogue, lora_buf)):
+        raise _l.ApexMIError("gemm: `quantised` activations were passed but this call does not take the fp8 route "
+                             "(fp8_compute_route / fp8_lora_route are both False): decide with fp8_norm_quant_route first")
     if f8 is not None and f8.lora_A is not None:
         if fp8_lora_route(a, f8, out, epilogue, lora_buf):
             K, Rp = a.shape[1], f8.lora_A.shape[0]
             t = lora_buf[:, K:K + Rp]
             gemm(a, f8.lora_A, None, out=t)                      # t = a A^T in bf16, as _gemm_fp8_lora produces it
-            qa, sa = _act_scratch(a.device, a.shape[0], K)
-            quant_rows_fp8(a, out=qa, scale_out=sa)
+            if quantised is not None:
+                qa, sa = _check_quantised(a, quantised)
+            else:
+                qa, sa = _act_scratch(a.device, a.shape[0], K)
+                quant_rows_fp8(a, out=qa, scale_out=sa)
             return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual, lora_t=t, lora_B=f8.lora_B)
         return _gemm_fp8_lora(a, f8, bias, out, epilogue, gate, residual, lora_buf)
     w = _bf16_weight(w, a.dtype == torch.float32)

@@ -225,7 +225,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         self._band_plans = {}
         return self
 
-    def set_fp8_compute(self, on: bool, lora: bool = False):
+    def set_fp8_compute(self, on: bool, lora: bool = False, fused_quant: bool = False):
         """Opt-in approximation: the block Linears whose weights are RESIDENT e4m3 records (a `keep_fp8=True` load:
         the fused q|k|v, the attention outputs, the cross-attention q and k|v, the two FFN Linears) quantise their activations per
         row to e4m3 and multiply in fp8 (`ops.gemm_fp8`) instead of dequantising the weight and multiplying in bf16.  Everything
@@ -236,9 +236,21 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         `lora=True` (needs `on=True`): a record that carries run-time LoRA factors stays on the fp8 GEMM as well — the adapter term
         `(x A^T) B'^T` is added in bf16 x bf16 by a tail of the same kernel, into the scaled f32 accumulators
         (`ops.fp8_lora_route`) — instead of falling back to the bf16 path.  The flag lives on the records, so adapters loaded
-        before or after this call both take it.  `lora=False` (the default) leaves every launch as it is today."""
+        before or after this call both take it.  `lora=False` (the default) leaves every launch as it is today.
+
+        `fused_quant=True` (needs `on=True`): the three Linears that read a buffer a norm wrote one launch earlier — the fused
+        q|k|v, the cross-attention query behind an affine `norm2`, the FFN-up projection — get their e4m3 codes and row scales
+        from the norm kernel itself (`ops.ln_modulate_quant_fp8`, passed on through `ops.gemm(quantised=)`) wherever
+        `ops.fp8_norm_quant_route` allows it, so their `quant_rows_fp8` launch disappears and, without adapters, the bf16
+        normalised rows are never stored (3 bytes per element instead of 7; 5 with run-time LoRA, whose skinny GEMM reads them).
+        A launch and traffic change only: the forward is bit-identical to `set_fp8_compute(True, lora=...)` without it, and the
+        f32 residual stream takes it too.  The other four fp8 Linears, e5m2 / GGUF records, the f32-storage mode and the query
+        projection without an affine `norm2` run the launches they run today.  `fused_quant=False` (the default) leaves every
+        launch as it is today."""
         if lora and not on:
             raise ValueError("wan.mi355: set_fp8_compute(lora=True) needs on=True: the adapter tail belongs to the fp8 GEMM")
+        if fused_quant and not on:
+            raise ValueError("wan.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
         recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values() if isinstance(r, ops.Fp8Weight)}
         if not recs:
             raise _l.ApexMIError("wan.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
@@ -247,7 +259,20 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
             r.compute = "fp8" if on else "bf16"
             r.lora_compute = "fp8" if lora else "bf16"
         self._fp8_compute = bool(on)
+        self._fp8_fused_quant = bool(fused_quant)
         return self
+
+    def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", **norm):
+        """ln_modulate(x, **norm, out=xn) -> gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf); with
+        `set_fp8_compute(fused_quant=True)`, where `ops.fp8_norm_quant_route` allows it, the norm quantises for the GEMM in its own
+        launch (and stores `xn` only if the GEMM's adapter tail reads it).  Nothing else reads `xn` between the two."""
+        if getattr(self, "_fp8_fused_quant", False):
+            fuse, need_row = ops.fp8_norm_quant_route(x, xn, w, out, epilogue, lora_buf)
+            if fuse:
+                q = ops.ln_modulate_quant_fp8(x, out=xn if need_row else None, **norm)
+                return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf, quantised=q)
+        ops.ln_modulate(x, out=xn, **norm)
+        return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf)
 
     def _grid_ids(self, grid) -> torch.Tensor:
         """(frame, row, column) of every token in sequence order: what RoPE rotates by and what the attention window measures"""
@@ -512,8 +537,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
             a1, a2 = blk.attn1, blk.attn2
             m = lambda j: ws.MOD[i, j * dim:(j + 1) * dim]  # noqa: E731 shift, scale, gate, c_shift, c_scale, c_gate
             # 1. self attention
-            ops.ln_modulate(X, m(1), m(0), out=XN, eps=eps)
-            ops.gemm(XN, blk._wqkv, blk._bqkv, out=QKV, lora_buf=ws.XNf)
+            self._norm_gemm(X, XN, blk._wqkv, blk._bqkv, QKV, ws.XNf, scale=m(1), shift=m(0), eps=eps)
             if fuse:       # across-heads RMSNorm of q and k + RoPE + layout + V^T in one read of the projection
                 ops.qk_rms_rope_rows(q_in, k_in, v_in, H, ws.Q[0], ws.K[0], ws.VT[0], wq=a1.norm_q.weight, wk=a1.norm_k.weight,
                                      eps=eps, rope=rope, rope_mode=_l.ROPE_INTERLEAVED)
@@ -532,14 +556,15 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
                      residual=X, lora_buf=ws.ATTf)
             # 2. cross attention over the text tokens (no RoPE, ungated residual)
             if isinstance(blk.norm2, _AffineNorm):
-                ops.ln_modulate(X, gamma=blk.norm2.weight, beta=blk.norm2.bias, out=XN, eps=eps)
-                src = XN
-            elif X.dtype != XN.dtype:      # float residual stream without norm2: the query projection reads X rounded to bf16
-                XN.copy_(ops.to_bf16(X))
-                src = XN
+                self._norm_gemm(X, XN, a2.to_q.weight, a2.to_q.bias, q_in, ws.XNf, gamma=blk.norm2.weight, beta=blk.norm2.bias,
+                                eps=eps)
             else:
-                src = X
-            ops.gemm(src, a2.to_q.weight, a2.to_q.bias, out=q_in, lora_buf=ws.XNf if src is XN else None)
+                if X.dtype != XN.dtype:    # float residual stream without norm2: the query projection reads X rounded to bf16
+                    XN.copy_(ops.to_bf16(X))
+                    src = XN
+                else:
+                    src = X
+                ops.gemm(src, a2.to_q.weight, a2.to_q.bias, out=q_in, lora_buf=ws.XNf if src is XN else None)
             if fuse:
                 ops.qk_rms_rope_rows(q_in, None, None, H, ws.Q[0], None, None, wq=a2.norm_q.weight, eps=eps)
             else:
@@ -559,8 +584,8 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
             ops.gemm(ATT, a2.to_out[0].weight, a2.to_out[0].bias, out=X, epilogue="gate_res", gate=self._ones,
                      residual=X, lora_buf=ws.ATTf)
             # 3. feed-forward
-            ops.ln_modulate(X, m(4), m(3), out=XN, eps=eps)
-            ops.gemm(XN, blk.ffn.net[0].proj.weight, blk.ffn.net[0].proj.bias, out=FFH, epilogue="gelu", lora_buf=ws.XNf)
+            self._norm_gemm(X, XN, blk.ffn.net[0].proj.weight, blk.ffn.net[0].proj.bias, FFH, ws.XNf, epilogue="gelu",
+                            scale=m(4), shift=m(3), eps=eps)
             ops.gemm(FFH, blk.ffn.net[2].weight, blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5),
                      residual=X, lora_buf=ws.FFHf)
 

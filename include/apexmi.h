@@ -749,6 +749,20 @@ int apexmi_dequant_fp8_scaled(const void* w, int format, const void* scale, int6
 int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, float* scales,
                           apexmi_stream_t stream);
 
+/* apexmi_ln_modulate_quant_fp8 — replaces apexmi_ln_modulate2 (x_dtype APEXMI_BF16) or apexmi_ln_modulate2_f32in (x_dtype
+ * APEXMI_F32, ldx in floats) followed by apexmi_quant_rows_fp8 on its output, where a norm feeds an fp8 Linear (Wan: the fused
+ * q|k|v, the cross-attention query behind an affine norm2, the FFN-up projection): one launch that keeps the normalised row in
+ * registers, rounds it to bf16 as the norm's store does and quantises the ROUNDED values.  7 bytes per element become 3 (5 with
+ * `out`).  codes uint8 [M, C] (row stride ldq bytes), scales f32 [M]; out bf16 [M, C] (row stride ldo elements) or NULL: no bf16
+ * row is stored.  codes, scales and out are BIT-IDENTICAL to the two launches: the kernel is the quantising form of the one the
+ * norm alone would have run for this (x_dtype, C, `ln.wave`), same reduction shapes, and the quantiser's formula is shared
+ * (csrc/fp8_quant.h).  Every other operand as apexmi_ln_modulate2.  M >= 1; C % 128 == 0 and C <= 8192; 16-byte rows with
+ * ldx, ldq, ldo >= C; 16-byte aligned modulation and affine vectors; split in [0, M]. */
+int apexmi_ln_modulate_quant_fp8(const void* x, int64_t ldx, int x_dtype, void* out, int64_t ldo, void* codes, int64_t ldq,
+                                 float* scales, int M, int C, const float* scale, const float* shift, const void* gamma,
+                                 const void* beta, float eps, int rms, int split, const float* scale2, const float* shift2,
+                                 apexmi_stream_t stream);
+
 /* apexmi_gemm_fp8 — replaces apexmi_dequant_fp8_scaled + apexmi_gemm_bf16 for such a Linear:
  *     C[m, n] = epi( (sum_k qa[m, k] qw[n, k]) * sa[m] * sw[n] + bias[n] )     bf16 out, f32 accumulation and epilogue
  * qa [M, K] e4m3fn codes (row stride lda bytes) with f32 row scales sa [M] (apexmi_quant_rows_fp8); qw [N, K] e4m3fn codes
