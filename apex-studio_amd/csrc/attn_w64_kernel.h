@@ -1,6 +1,7 @@
 // The C++ shell of attn_fwd_d128_w64_kernel (attention.hip): address set-up, ONE asm statement (the generated loop, W64_BODY), the
-// normalising epilogue.  Included once per loop body: the shipped one, and the timing-only ablations of tools/attn_w64_ablate.sh
-// (-DAPEXMI_ATTN_W64_ABLATE, side library).  W64_NAME = kernel name, W64_BODY = the generated include.
+// normalising epilogue.  Included three times: the shipped kernel (W64_BODY without a running maximum, W64_FALLBACK with one), the
+// running-maximum loop alone (attn_fwd_d128_w64r_kernel) and the band kernel (W64_BANDS).  W64_NAME = kernel name, W64_BODY = the
+// generated include.
 // W64_FALLBACK (optional) = a second generated loop with the per-tile running maximum: W64_BODY is then the loop WITHOUT one (the
 // generator's max=first: every row keeps the integer maximum tile 0 gave it, so a tile carries no row-max chain, no raise test and
 // no rescale test).  An integer shift of the maximum scales every probability, row sum and numerator by the same power of two, so
@@ -32,9 +33,6 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
     const int hb = s / nqb, qb = s % nqb;
     const bf16_t* Qp = Q + (int64_t)hb * Sq * HD;
 #ifdef W64_BANDS
-#ifdef W64_DMA_WAVE
-#error "W64_BANDS is written for the shipped piece order, not for dma=wave"
-#endif
     // the block's pair, wave-uniform, then clamped: lo a multiple of 64 below Sk, 1 <= n <= Sk - lo
     const int* bp = bands + 2 * ((hb % H) * band_hs + qb);
     int klo = __builtin_amdgcn_readfirstlane(bp[0]), khi = __builtin_amdgcn_readfirstlane(bp[1]);
@@ -71,40 +69,19 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
         rk[j] = __builtin_amdgcn_readfirstlane(rk[j]);
         rv[j] = __builtin_amdgcn_readfirstlane(rv[j]);
     }
-#ifdef W64_DMA_WAVE
-    // the generator's dma=wave: a wave's four pieces of a tile are contiguous in the image (K rows 16 wave + 4 i + (lane >> 4), V^T
-    // rows 32 wave + 8 i + (lane >> 3)): one M0 write per four loads, the instruction offset i * 1024 moves the LDS address.  That
-    // offset enters the global address too, so the K descriptor's base stands 1024 bytes low (piece 2's lane offset is its key
-    // offset MINUS 1024) and every lane offset carries + 1024; the range grows by the same 1024.
-    rk[0] = __builtin_amdgcn_readfirstlane((uint32_t)(kb - 1024));
-    rk[1] = __builtin_amdgcn_readfirstlane((uint32_t)((kb - 1024) >> 32) & 0xffffu);
-    rk[2] = __builtin_amdgcn_readfirstlane((uint32_t)(Sk * (HD * 2) + 1024));
-    const int krow0 = 16 * wave + (lane >> 4);
-    const int voff_k = krow0 * (HD * 2) + (((lane & 15) ^ (lane >> 4)) << 4) + 1024;
-    const int vrow0 = 32 * wave + (lane >> 3);
-    const int voff_v = vrow0 * Skp * 2 + (((lane & 7) ^ ((vrow0 >> 1) & 3)) << 4);
-    const int v_piece = __builtin_amdgcn_readfirstlane(8 * Skp * 2 - 1024);
-    const int wbase = wave * 4096;
-#else
     const int krow0 = 4 * wave + (lane >> 4);
     const int voff_k = perm32(krow0) * (HD * 2) + (((lane & 15) ^ krow0) << 4);
     const int vrow0 = 8 * wave + (lane >> 3);
     const int voff_v = vrow0 * Skp * 2 + (((lane & 7) ^ ((vrow0 >> 1) & 7)) << 4);
     const int v_piece = __builtin_amdgcn_readfirstlane(32 * Skp * 2);
     const int wbase = wave * 1024;
-#endif
     // fragment reads: K image row l31 (+ 32 kt), chunk (2 ks + hi) ^ (row & 15) = ((hi ^ row) & 15) ^ 2 ks; V^T image row l31 (+ 32 dt),
     // chunk (2 kk + hi) ^ ((row >> 1) & 7)
     const int ka = l31 * 256 + (((hi ^ l31) & 15) << 4);
     const int va = l31 * 128 + ((hi ^ ((l31 >> 1) & 7)) << 4);
 
-#if APEXMI_ATTN_TRACE
-    unsigned long long* tp = d_attn_trace ? d_attn_trace + ((size_t)blockIdx.x * 4 + wave) * 4 : nullptr;
-    tp = (unsigned long long*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)tp >> 32)) << 32) |
-                               (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)tp));
-#else
+    // no generated loop reads %[tp] any more; without this two-SGPR input the allocator emits one or two fewer moves before each loop
     unsigned long long* tp = nullptr;
-#endif
     f32x16 o0, o1, o2, o3, o4, o5, o6, o7;
     float la, lb;
 #ifdef W64_FALLBACK
@@ -151,26 +128,6 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
     // (72 tiles) pays it once per 72 tiles ----
     const int b = hb / H, h = hb % H;
     const f32x16* oo[2][4] = {{&o0, &o1, &o2, &o3}, {&o4, &o5, &o6, &o7}};
-#ifdef W64_STORE_X2   // A/B arm (side library): the 8-byte stores of round 5
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-        const float inv = 1.0f / sum_xor32(e ? lb : la);
-        const int qrow = row_a + 32 * e;
-        if (qrow < Sq) {
-            bf16_t* op = O + (int64_t)b * o_sb + (int64_t)qrow * o_ss + (int64_t)h * o_sh;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x16& x = *oo[e][dt];
-                    u32x2 o;
-                    o[0] = pack_bf16(x[4 * g + 0] * inv, x[4 * g + 1] * inv);
-                    o[1] = pack_bf16(x[4 * g + 2] * inv, x[4 * g + 3] * inv);
-                    *(u32x2*)(op + dt * 32 + g * 8 + hi * 4) = o;
-                }
-        }
-    }
-#else
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         const float inv = 1.0f / sum_xor32(e ? lb : la);
@@ -193,6 +150,4 @@ __global__ __launch_bounds__(256, 1) void W64_NAME(
                 if (qrow < Sq) *(u32x4*)(op + dt * 32 + (2 * p + hi) * 8) = o;
             }
     }
-#endif
 }
-

@@ -350,3 +350,18 @@ def test_ops_attention_varlen_refuses_with_the_exact_message(fault, args, kwargs
     with pytest.raises(ApexMIError) as e:
         ops.attention_varlen(*args, **kwargs)
     assert str(e.value) == message
+
+
+@pytest.mark.parametrize("key,value", [("attn.xv", 1), ("attn.stages", 3)])
+def test_removed_attention_experiment_keys_are_unknown(key, value):
+    """`attn.xv` and `attn.stages` selected experiment arms of the 4-cluster kernel that are no longer built: the library refuses
+    them like any key it never had, while a surviving key of the same kernel (`attn.c4`) is still accepted (and restored)."""
+    L = lib.load()
+    assert L.apexmi_tune_set(key.encode(), value) != 0
+    assert L.apexmi_last_error().decode() == "tune_set: unknown key"
+    with pytest.raises(ApexMIError, match="unknown key"):
+        lib.tune_set(key, value)
+    try:
+        lib.tune_set("attn.c4", 1)
+    finally:
+        lib.tune_set("attn.c4", 3)       # the shipped default

@@ -28,11 +28,9 @@ stage offset is an immediate of the ds_read / an immediate of the M0 write
 import os
 import sys
 
-# timing-only ablations (WRONG results; tools/attn_w64_ablate.sh): which parts of the loop are emitted
-OPT = {"max": "run", "head": 0, "align": 6, "dma": "piece", "rowsum": "add", "mfma4_pos": "end", "pk_add": False, "pk_fma": False, "adds_in": "Y", "dma_in": "X", "vread_early": 8, "kread_early": 2, "pre_x": 0, "mix_y": 0, "drain": 2, "dummy_x": 0, "dummy_y": 0}   # schedule options (CLI --opt k=v)
-TRACE = False   # --trace: per-phase cycle accumulators (s_memtime), written through %[tp] at the end (side library)
-ABL = {"fill_x": True, "fill_y": True, "mfma": True, "drain": True, "dma": True, "reads": True, "barrier": True,
-       "exp": True, "add": True, "cvt": True, "max": True, "fma": True, "dec": True}
+# the one schedule option (CLI --opt=max=first): "run" = a running maximum per tile (attn_w64_body.inc), "first" = every row keeps
+# tile 0's maximum (attn_w64_first.inc; the kernel's shell checks the row sums at the end)
+OPT = {"max": "run"}
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "apex-studio_amd", "csrc", "attn_w64_body.inc")
 NEG_BIG = "0xf149f2ca"      # -1.0e30f
@@ -100,7 +98,6 @@ class Emit:
         self.lines = []
         self.lds = []          # destination base registers of outstanding ds_reads, issue order
         self.label_n = 0
-        self.in_loop = False
         self.pending_raise = None
         self.pending_rescale = None
 
@@ -112,8 +109,6 @@ class Emit:
         return f".Lw64_{stem}_{self.label_n}_%="
 
     def ds_read(self, dst, addr, off):
-        if not ABL["reads"]:
-            return
         self.i(f"ds_read_b128 {vr(dst, 4)}, {vr(addr)} offset:{off}")
         self.lds.append(dst)
 
@@ -132,8 +127,6 @@ class Emit:
 
 
 def mfma(em, dst, a, b, c, dst_a=False, b_a=False):
-    if not ABL["mfma"]:
-        return
     d = ar(dst, 16) if dst_a else vr(dst, 16)
     bb = ar(b, 4) if b_a else vr(b, 4)
     cc = "0" if c is None else d
@@ -141,8 +134,6 @@ def mfma(em, dst, a, b, c, dst_a=False, b_a=False):
 
 
 def drain(em, n=2):
-    if not ABL["drain"]:
-        return
     for _ in range(n):
         em.i("s_nop 15")
 
@@ -184,11 +175,10 @@ def dec_raise_ops(e):
             f"v_sub_f32 {vr(t3)}, {vr(M_(e))}, {vr(t2)}",
             f"v_mov_b32 {vr(M_(e))}, {vr(t2)}",
             f"v_exp_f32 {vr(AL_(e))}, {vr(t3)}",
-            "s_nop 0"] + \
-        ([] if OPT["rowsum"] == "mfma4" else      # mfma4: the partial sums live in AGPRs and take the factor with O^T (rescale_block)
-         [f"v_mul_f32 {vr(PS(e, 0))}, {vr(PS(e, 0))}, {vr(AL_(e))}",
-          f"v_mul_f32 {vr(PS(e, 1))}, {vr(PS(e, 1))}, {vr(AL_(e))}"]) + \
-        [f"v_cmp_neq_f32 s[{54 + 2 * e}:{55 + 2 * e}], 1.0, {vr(AL_(e))}"]
+            "s_nop 0",
+            f"v_mul_f32 {vr(PS(e, 0))}, {vr(PS(e, 0))}, {vr(AL_(e))}",
+            f"v_mul_f32 {vr(PS(e, 1))}, {vr(PS(e, 1))}, {vr(AL_(e))}",
+            f"v_cmp_neq_f32 s[{54 + 2 * e}:{55 + 2 * e}], 1.0, {vr(AL_(e))}"]
 
 
 def scale_ops(ns):
@@ -196,11 +186,8 @@ def scale_ops(ns):
     for e in range(2):
         for w in range(0, 32, 2):
             r = Sreg(ns, e * 32 + w)
-            if OPT["pk_fma"]:
-                q.append(f"v_pk_fma_f32 {vr(r, 2)}, {vr(r, 2)}, s[78:79], {vr(M_(e), 2)} op_sel_hi:[1,1,0] neg_lo:[0,0,1] neg_hi:[0,0,1]")
-            else:
-                q.append(f"v_fma_f32 {vr(r)}, {vr(r)}, %[sc], -{vr(M_(e))}")
-                q.append(f"v_fma_f32 {vr(r + 1)}, {vr(r + 1)}, %[sc], -{vr(M_(e))}")
+            q.append(f"v_fma_f32 {vr(r)}, {vr(r)}, %[sc], -{vr(M_(e))}")
+            q.append(f"v_fma_f32 {vr(r + 1)}, {vr(r + 1)}, %[sc], -{vr(M_(e))}")
     return q
 
 
@@ -223,46 +210,24 @@ def sm1_ops(ns, inline_raise):
 
 
 def add_ops(st):
-    """row-sum terms of set st (exponentiated) into the two partial sums of each block.
-    rowsum = "add": the unrounded f32 exponentials, one v_add_f32 each (64 per tile).
-    rowsum = "dot2c": the PACKED bf16 probabilities of the tile (what multiplies V), two per v_dot2c_f32_bf16 against a {1.0, 1.0}
-    bf16 pair in s79 — 32 issue slots per tile instead of 64, and the normaliser is the sum of exactly the weights of P V
-    (measured, profiles/r06_attn_w64_rowsum_ab.log: no faster — the dot is not a full-rate VALU op).
-    rowsum = "mfma4": no VALU at all — see rowsum_mfma()."""
+    """row-sum terms of set st (exponentiated) into the two partial sums of each block: the unrounded f32 exponentials, one v_add_f32
+    each (64 per tile).  Measured and no faster (profiles/r06_attn_w64_rowsum_ab.log): v_dot2c_f32_bf16 over the packed pairs, and
+    the sums on the matrix pipe (v_mfma_f32_4x4x4_16b_bf16 against all-ones)."""
     q = []
-    if OPT["rowsum"] == "mfma4":
-        return q
-    if OPT["rowsum"] == "dot2c":
-        assert not OPT["pk_fma"], "s79 holds the bf16 ones pair"
-        if OPT["adds_in"] == "X":      # pair order (block-major): sm2_ops places each behind the v_cvt_pk of its pair
-            return [f"v_dot2c_f32_bf16 {vr(PS(e, j & 1))}, s79, {vr(P(e, 0) + j)}" for e in range(2) for j in range(16)]
-        for j in range(16):            # four chains round robin
-            for e in range(2):
-                q.append(f"v_dot2c_f32_bf16 {vr(PS(e, j & 1))}, s79, {vr(P(e, 0) + j)}")
-        return q
     for v in range(0, 64, 2):
         e, r = v >> 5, Sreg(st, v)
-        if OPT["pk_add"]:
-            q.append(f"v_pk_add_f32 {vr(PS(e, 0), 2)}, {vr(PS(e, 0), 2)}, {vr(r, 2)}")
-        else:
-            q.append(f"v_add_f32 {vr(PS(e, 0))}, {vr(PS(e, 0))}, {vr(r)}")
-            q.append(f"v_add_f32 {vr(PS(e, 1))}, {vr(PS(e, 1))}, {vr(r + 1)}")
+        q.append(f"v_add_f32 {vr(PS(e, 0))}, {vr(PS(e, 0))}, {vr(r)}")
+        q.append(f"v_add_f32 {vr(PS(e, 1))}, {vr(PS(e, 1))}, {vr(r + 1)}")
     return q
 
 
-def sm2_ops(st, with_adds):
-    """exp2 of set st in place and the bf16 pairs (and the row-sum terms); the uses trail the exponentials by a pair"""
+def sm2_ops(st):
+    """exp2 of set st in place and the bf16 pairs; the uses trail the exponentials by a pair"""
     q = []
-    adds = add_ops(st)
-    per = len(adds) // 32
 
     def use(v):
         e, w = v >> 5, v & 31
-        u = [f"v_cvt_pk_bf16_f32 {vr(P(e, w >> 3) + ((w & 7) >> 1))}, {vr(Sreg(st, v))}, {vr(Sreg(st, v + 1))}"]
-        if with_adds:
-            mine = adds[(v >> 1) * per:(v >> 1) * per + per]
-            u = u + mine if OPT["rowsum"] == "dot2c" else mine + u      # dot2c reads the packed pair, the adds the exponentials
-        return u
+        return [f"v_cvt_pk_bf16_f32 {vr(P(e, w >> 3) + ((w & 7) >> 1))}, {vr(Sreg(st, v))}, {vr(Sreg(st, v + 1))}"]
     for v in range(0, 64, 2):
         q.append(f"v_exp_f32 {vr(Sreg(st, v))}, {vr(Sreg(st, v))}")
         q.append(f"v_exp_f32 {vr(Sreg(st, v + 1))}, {vr(Sreg(st, v + 1))}")
@@ -273,66 +238,18 @@ def sm2_ops(st, with_adds):
     return q
 
 
-def SACC(e, h):              # rowsum = "mfma4": two 4-register accumulators per block in the free AGPRs
-    return 192 + 8 * e + 4 * h
-
-
-ONES = 224                   # v[224:225]: the bf16 pair {1.0, 1.0} twice — the all-ones A operand of the 4x4x4 MFMA
-
-
-def rowsum_mfma(em, e, kk, h):
-    """rowsum = "mfma4": the row-sum terms on the matrix pipe.  v_mfma_f32_4x4x4_16b_bf16 is sixteen independent 4x4x4 products;
-    with an all-ones A every lane's four result registers receive the sum of ITS OWN four bf16 B values: one 2-pass MFMA adds four
-    packed probabilities of the lane to its partial row sum — 16 of them per tile (128 matrix-pipe cycles) replace 64 v_add_f32
-    (256 issue cycles).  Half h of the 8-key fragment P(e, kk)."""
-    if not ABL["add"]:
-        return
-    d = ar(SACC(e, h), 4)
-    em.i(f"v_mfma_f32_4x4x4_16b_bf16 {d}, {vr(ONES, 2)}, {vr(P(e, kk) + 2 * h, 2)}, {d}")
-
-
-DROP = {"exp": "v_exp_f32 v", "add": ("v_add_f32", "v_pk_add_f32", "v_dot2c_f32_bf16"), "cvt": "v_cvt_pk", "max": "v_max3", "fma": ("v_fma_f32", "v_pk_fma_f32")}
-
-
-def spread(q, nslots, first_extra=0):
-    """split queue q over nslots gaps as evenly as possible; `first_extra` ops go before the first MFMA"""
-    for k, pre in DROP.items():
-        if not ABL[k]:
-            q = [op for op in q if not op.startswith(pre)]   # pre: a prefix or a tuple of prefixes
-    if not ABL["dec"]:
-        q = [op for op in q if not op.endswith(";dec") and op != "@RAISE"]
-    if not q:
-        return [], [[] for _ in range(nslots)]
-    pre, rest = q[:first_extra], q[first_extra:]
+def spread(q, nslots):
+    """split queue q over nslots gaps as evenly as possible"""
     out = [[] for _ in range(nslots)]
-    for k, op in enumerate(rest):
-        out[k * nslots // len(rest)].append(op)
-    return pre, out
+    for k, op in enumerate(q):
+        out[k * nslots // len(q)].append(op)
+    return out
 
 
 def dma_piece(em, j, stage, part=3):
     """LDS-DMA piece j (0..3 K, 4..7 V^T) of a tile into ring stage `stage` (compile time): s45 / s46 = the tile's K / V^T byte
     offsets, v[238:243] = the per-lane offsets of pieces 1..3.  part 1 = the M0 write, 2 = the load (M0 needs one instruction between
     them: in the loop a gap's fillers stand there), 3 = both with an s_nop"""
-    if not ABL["dma"] and em.in_loop:
-        return
-    if OPT["dma"] == "wave":
-        # dma = "wave": a wave's four K (V^T) pieces are CONTIGUOUS in the LDS image (the wave owns image rows 16 wave + 4 i + .. /
-        # 32 wave + 8 i + ..), so one M0 write serves four loads through the instruction offset i * 1024 — 2 instead of 8 scalar
-        # writes per tile.  The offset also enters the global address: the per-piece lane offsets take it back (prologue), and the
-        # shell hands over a K descriptor whose base stands 1024 bytes low (attn_w64_kernel.h, W64_DMA_WAVE).  Same LDS image.
-        i = j & 3
-        if (part & 1) and i == 0:
-            em.i(f"s_add_i32 m0, %[w], {stage * 16384 + (0 if j < 4 else 65536)}")
-            if part == 3:
-                em.i("s_nop 0")
-        if part & 2:
-            io = f" offset:{i * 1024}" if i else ""
-            if j < 4:
-                em.i(f"buffer_load_dwordx4 {'%[vk]' if j == 0 else vr(237 + j)}, %[rk], s45 offen{io} lds")
-            else:
-                em.i(f"buffer_load_dwordx4 {'%[vv]' if j == 4 else vr(236 + j)}, %[rv], s46 offen{io} lds")
-        return
     if part & 1:
         off = stage * 16384 + (j * 4096 if j < 4 else 65536 + (j - 4) * 4096)
         em.i(f"s_add_i32 m0, %[w], {off}")
@@ -396,15 +313,6 @@ def rescale_block(em, go, back):
             em.i("s_nop 0")
             for u in range(4):
                 em.i(f"v_accvgpr_write_b32 {ar(e * 64 + k + u)}, {vr(T[u])}")
-        if OPT["rowsum"] == "mfma4":      # the block's partial row sums (register 0 of each accumulator is the one read at the end)
-            for h in range(2):
-                em.i(f"v_accvgpr_read_b32 {vr(T[h])}, {ar(SACC(e, h))}")
-            em.i("s_nop 0")
-            for h in range(2):
-                em.i(f"v_mul_f32 {vr(T[h])}, {vr(T[h])}, {vr(AL_(e))}")
-            em.i("s_nop 0")
-            for h in range(2):
-                em.i(f"v_accvgpr_write_b32 {ar(SACC(e, h))}, {vr(T[h])}")
         em.i("s_nop 7")
         em.i(f"{skip}:")
     em.i(f"s_branch {back}")
@@ -416,18 +324,9 @@ def tile(em, sg, more, more2, dma):
     end of phase Y); dma: tile t+3 exists (staged in phase Y)"""
     st, ns = sg & 1, (sg & 1) ^ 1
     kst, vst, k2st, dst = (sg + 1) & 3, sg, (sg + 2) & 3, (sg + 3) & 3      # K stage of t+1, V^T stage of t, K of t+2, DMA of t+3
-    # ---------------- phase X: S(t+1) = K(t+1) Q^T beside exp2 / bf16 pairs (/ row-sum terms) of tile t ----------------
-    em.in_loop = True
-    em.lds = [KF(0, 0), KF(0, 1)] if (more and ABL["reads"]) else []
-    if TRACE:
-        em.i("s_memtime s[80:81]")
-    q = sm2_ops(st, with_adds=OPT["adds_in"] == "X") if ABL["fill_x"] else []
-    pre, gaps = spread(q, 32, first_extra=OPT["pre_x"])
-    for k in range(OPT["dummy_x"]):   # experiment: independent VALU ops in the gaps
-        gaps[k * 32 // OPT["dummy_x"]].append(f"v_mov_b32 v{226 + (k & 3)}, 1.0")
-    for op in pre:
-        em.i(op)
-    vread_slot = 32 - OPT["vread_early"]
+    # ---------------- phase X: S(t+1) = K(t+1) Q^T beside exp2 / bf16 pairs of tile t ----------------
+    em.lds = [KF(0, 0), KF(0, 1)] if more else []
+    gaps = spread(sm2_ops(st), 32)
     for ks in range(8):
         if more and ks + 1 < 8:
             em.ds_read(KF((ks + 1) & 1, 0), KA(ks + 1), kst * 16384)
@@ -440,12 +339,10 @@ def tile(em, sg, more, more2, dma):
                 mfma(em, S(ns, e, kt), KF(ks & 1, kt), Q(e, ks), None if ks == 0 else 1, b_a=True)
             for op in gaps[slot]:
                 em.i(op)
-            if slot == vread_slot - 1:
+            if slot == 23:
                 # V^T fragments of the first step of phase Y: their latency rides under the tail of phase X
                 for dt in range(4):
                     em.ds_read(VF(0, dt), VA(0), vst * 16384 + dt * 4096)
-    if TRACE:
-        em.i("s_memtime s[82:83]")
     if more and not more2:
         # tile t + 1 is the last one (this body only): mask its keys past Sk if it is ragged.  No drain anywhere else: the first VALU
         # reads of S(t+1) (row max) follow the row-sum terms of tile t, ten MFMA gaps into phase Y
@@ -455,31 +352,20 @@ def tile(em, sg, more, more2, dma):
         drain(em, 3)
         mask_block(em, ns)
         em.i(f"{lm}:")
-    # ---------------- phase Y: O^T += V^T(t) P(t)^T beside (row-sum terms of tile t,) max / decision / scaling of tile t+1 ------
-    q = []
-    if ABL["fill_y"]:
-        adds = add_ops(st) if OPT["adds_in"] == "Y" else []
-        if OPT["max"] == "first":    # the running maximum stays what tile 0 made it (the kernel's shell checks the row sums at the end)
-            sm1 = scale_ops(ns) if more else []
-        else:
-            sm1 = sm1_ops(ns, inline_raise=False) if more else []
-        q += adds + sm1
-    _, gaps = spread(q, 32)
+    # ---------------- phase Y: O^T += V^T(t) P(t)^T beside row-sum terms of tile t, max / decision / scaling of tile t+1 ------
+    if OPT["max"] == "first":    # the running maximum stays what tile 0 made it (the kernel's shell checks the row sums at the end)
+        sm1 = scale_ops(ns) if more else []
+    else:
+        sm1 = sm1_ops(ns, inline_raise=False) if more else []
+    gaps = spread(add_ops(st) + sm1, 32)
     raise_lbl, raise_ret = em.label("raise"), em.label("raised")
-    for k in range(OPT["dummy_y"]):
-        gaps[k * 32 // OPT["dummy_y"]].append(f"v_mov_b32 v{226 + (k & 3)}, 1.0")
     for kk in range(4):
         if kk == 2:
             # ---- the tile's one barrier, in the MIDDLE of the phase: tile t + 2 (staged a tile ago) becomes visible, and every
             # wave has left phase Y(t - 1), whose V^T stage the LDS-DMA of tile t + 3 (below) overwrites.  The MFMAs of steps 0 / 1
             # are still in the pipe while the waves meet. ----
-            if TRACE:
-                em.i("s_memtime s[84:85]")
             em.i("s_waitcnt vmcnt(0)")
-            if ABL["barrier"]:
-                em.i("s_barrier")
-            if TRACE:
-                em.i("s_memtime s[86:87]")
+            em.i("s_barrier")
         if kk + 1 < 4:
             for dt in range(4):
                 em.ds_read(VF((kk + 1) & 1, dt), VA(kk + 1), vst * 16384 + dt * 4096)
@@ -488,8 +374,6 @@ def tile(em, sg, more, more2, dma):
             if qq == 0:
                 em.need(VF(kk & 1, 3))                   # one wait per step
             mfma(em, O(e, dt), VF(kk & 1, dt), P(e, kk), 1, dst_a=True)
-            if OPT["rowsum"] == "mfma4" and OPT["mfma4_pos"] == "start" and (qq & 1) == 1:
-                rowsum_mfma(em, qq >> 2, kk, (qq >> 1) & 1)
             piece = dma and slot >= 16 and (slot & 1) == 1
             if piece:
                 dma_piece(em, (slot - 16) >> 1, dst, part=1)
@@ -507,30 +391,15 @@ def tile(em, sg, more, more2, dma):
                     em.i(op)
             if piece:
                 dma_piece(em, (slot - 16) >> 1, dst, part=2)
-            if OPT["rowsum"] == "mfma4" and OPT["mfma4_pos"] == "end" and (qq & 1) == 1:      # behind the gap's VALU, right in front of the next P V MFMA
-                rowsum_mfma(em, qq >> 2, kk, (qq >> 1) & 1)
-            if more2 and slot == 31 - OPT["kread_early"]:
+            if more2 and slot == 29:
                 k_first_reads(em, k2st)                  # first K fragments of tile t + 2, for phase X of the next tile
     em.pending_rescale = rescale_test(em) if (more and OPT["max"] != "first") else None
     em.i("s_add_i32 s40, s40, 1")
     em.i("s_add_i32 s45, s45, 16384")                    # K / V^T byte offsets of the tile the NEXT body stages
     em.i("s_add_i32 s46, s46, 128")
-    em.pending_raise = (raise_lbl, raise_ret) if (more and ABL["fill_y"] and ABL["dec"] and OPT["max"] != "first") else None
-    if TRACE:   # s[64:65] += phase X, s[66:67] += phase Y (both halves), s[68:69] += DMA wait + barrier
-        em.i("s_memtime s[88:89]")
-        em.i("s_waitcnt lgkmcnt(0)")                     # (drains the early K reads too: the next body's counted waits stay valid)
-        for acc, (hi_, lo_) in ((64, (82, 80)), (66, (84, 82)), (68, (86, 84)), (66, (88, 86))):
-            em.i(f"s_sub_u32 s76, s{hi_}, s{lo_}")
-            em.i(f"s_subb_u32 s77, s{hi_ + 1}, s{lo_ + 1}")
-            em.i(f"s_add_u32 s{acc}, s{acc}, s76")
-            em.i(f"s_addc_u32 s{acc + 1}, s{acc + 1}, s77")
-        em.i("s_sub_u32 s76, s80, s74")                  # tile edge: from the previous tile's last stamp to this tile's first
-        em.i("s_subb_u32 s77, s81, s75")
-        em.i("s_add_u32 s70, s70, s76")
-        em.i("s_addc_u32 s71, s71, s77")
-        em.i("s_mov_b64 s[74:75], s[88:89]")
+    em.pending_raise = (raise_lbl, raise_ret) if (more and OPT["max"] != "first") else None
     # the scoreboard at the tile edge: the next body assumes exactly the early K reads (or nothing)
-    want = [KF(0, 0), KF(0, 1)] if (more2 and ABL["reads"]) else []
+    want = [KF(0, 0), KF(0, 1)] if more2 else []
     assert em.lds == want, (em.lds, want)
 
 
@@ -551,14 +420,12 @@ def main():
     for a in sys.argv[1:]:
         if a.startswith("--out="):
             out = a[6:]
-        elif a.startswith("--no-"):
-            ABL[a[5:]] = False
         elif a.startswith("--opt="):
             k, v = a[6:].split("=")
-            OPT[k] = type(OPT[k])(int(v)) if isinstance(OPT[k], (bool, int)) else v
-        elif a == "--trace":
-            global TRACE
-            TRACE = True
+            assert k in OPT and v in ("run", "first"), a
+            OPT[k] = v
+        elif a != "--clobbers":                      # read below
+            sys.exit(f"gen_attn_w64.py: unknown option {a} (--out=FILE, --opt=max=run|first, --clobbers)")
     em = Emit()
     # ---------------- prologue ----------------
     for e, a in ((0, "%[qa]"), (1, "%[qb]")):
@@ -574,38 +441,17 @@ def main():
     for kk in range(4):
         em.i(f"v_xor_b32 {vr(VA(kk))}, {kk << 5}, %[va]")
         em.i(f"v_add_u32 {vr(VA(kk))}, 65536, {vr(VA(kk))}")     # the V^T ring starts at 64 KiB
-    if OPT["dma"] == "wave":
-        # K piece i: image rows 16 wave + 4 i + (lane >> 4) <- keys 16 wave + 4 swap2(i) + (lane >> 4) (perm32 swaps bits 2, 3 of the
-        # row), chunk ^= 4 i; minus the instruction offset i * 1024.  %[vk] = piece 0's offset + 1024 (the descriptor's base is 1024 low)
-        em.i(f"v_xor_b32 {vr(238)}, 64, %[vk]")
-        em.i(f"v_add_u32 {vr(238)}, 1024, {vr(238)}")             # swap2(1) - 1 = +1
-        em.i(f"v_xor_b32 {vr(239)}, 128, %[vk]")
-        em.i(f"v_subrev_u32 {vr(239)}, 1024, {vr(239)}")          # swap2(2) - 2 = -1
-        em.i(f"v_xor_b32 {vr(240)}, 192, %[vk]")                  # swap2(3) - 3 = 0
-        # V^T piece i: image rows (d) 32 wave + 8 i + (lane >> 3), chunk ^= 4 (i & 1); %[vp] = 8 rows of V^T - 1024 bytes
-        em.i(f"v_xor_b32 {vr(241)}, 64, %[vv]")
-        em.i(f"v_add_u32 {vr(241)}, %[vp], {vr(241)}")
-        em.i(f"v_add_u32 {vr(242)}, %[vp], %[vv]")
-        em.i(f"v_add_u32 {vr(242)}, %[vp], {vr(242)}")
-        em.i(f"v_add_u32 {vr(243)}, %[vp], {vr(241)}")
-        em.i(f"v_add_u32 {vr(243)}, %[vp], {vr(243)}")
-    else:
-        for j in range(1, 4):                         # per-piece LDS-DMA offsets: no scalar offset arithmetic in the loop
-            em.i(f"v_add_u32 {vr(237 + j)}, {j * 4096}, %[vk]")
-        em.i(f"v_add_u32 {vr(241)}, %[vp], %[vv]")
-        em.i(f"v_add_u32 {vr(242)}, %[vp], {vr(241)}")
-        em.i(f"v_add_u32 {vr(243)}, %[vp], {vr(242)}")
-    em.i("s_mov_b32 s78, %[sc]")                      # {scale, scale} for v_pk_fma_f32
-    em.i("s_mov_b32 s79, 0x3f803f80" if OPT["rowsum"] == "dot2c" else "s_mov_b32 s79, %[sc]")     # dot2c: the bf16 pair {1.0, 1.0}
+    for j in range(1, 4):                             # per-piece LDS-DMA offsets: no scalar offset arithmetic in the loop
+        em.i(f"v_add_u32 {vr(237 + j)}, {j * 4096}, %[vk]")
+    em.i(f"v_add_u32 {vr(241)}, %[vp], %[vv]")
+    em.i(f"v_add_u32 {vr(242)}, %[vp], {vr(241)}")
+    em.i(f"v_add_u32 {vr(243)}, %[vp], {vr(242)}")
+    em.i("s_mov_b32 s78, %[sc]")                      # s[78:79]: read by nothing the generator emits any more; the two moves
+    em.i("s_mov_b32 s79, %[sc]")                      # stay so that the committed loops, and the shipped kernels, do not change
     for e in range(2):
         em.i(f"s_mov_b64 s[{54 + 2 * e}:{55 + 2 * e}], 0")
     for k in range(128):
         em.i(f"v_accvgpr_write_b32 {ar(k)}, 0")
-    if OPT["rowsum"] == "mfma4":
-        for k in range(192, 208):
-            em.i(f"v_accvgpr_write_b32 {ar(k)}, 0")
-        em.i(f"v_mov_b32 {vr(ONES)}, 0x3f803f80")
-        em.i(f"v_mov_b32 {vr(ONES + 1)}, 0x3f803f80")
     # tiles 0..2 staged
     for tt in range(3):
         skip = em.label("nost")
@@ -647,25 +493,10 @@ def main():
     em.i(f"s_cbranch_scc1 {lm}")
     mask_block(em, 0)
     em.i(f"{lm}:")
-    if OPT["max"] == "first":
-        # max=first: the row keeps ceil(tile 0's scaled maximum) + head for the whole loop.  The head room costs no precision (it
-        # shifts every probability, the row sum and the numerator by the same power of two) and moves the window the f32 range
-        # leaves: a later score may stand 60 + head binades above tile 0's best before the row sum passes the shell's 2^60 test,
-        # and everything down to -(126 - 24 - head) binades below it keeps all its bits
-        pre = [op for op in sm1_ops(0, inline_raise=True)]
-        nscale = len(scale_ops(0))
-        for op in pre[:-nscale]:
-            em.i(op.replace(' ;dec', ''))
-        if OPT["head"]:
-            import struct
-            lit = "0x%08x" % struct.unpack("<I", struct.pack("<f", float(OPT["head"])))[0]
-            for e in range(2):
-                em.i(f"v_add_f32 {vr(M_(e))}, {lit}, {vr(M_(e))}")
-        for op in pre[-nscale:]:
-            em.i(op)
-    else:
-        for op in sm1_ops(0, inline_raise=True):
-            em.i(op.replace(' ;dec', ''))
+    # tile 0 looks for its maximum in both forms: with max=first the row keeps ceil(tile 0's scaled maximum) for the whole loop; a later
+    # score may stand 60 binades above tile 0's best before the row sum passes the shell's 2^60 test
+    for op in sm1_ops(0, inline_raise=True):
+        em.i(op.replace(' ;dec', ''))
     for e in range(2):
         em.i(f"v_mov_b32 {vr(AL_(e))}, 1.0")          # O is still zero: nothing to rescale
     l8, lw = em.label("w0"), em.label("waited2")
@@ -686,11 +517,6 @@ def main():
     k_first_reads(em, 1)                              # first K fragments of tile 1: phase X of tile 0 expects them in flight
     em.i(f"{lk}:")
     em.lds = []
-    if TRACE:
-        for k in range(64, 72, 2):
-            em.i(f"s_mov_b64 s[{k}:{k + 1}], 0")
-        em.i("s_memtime s[74:75]")
-        em.i("s_waitcnt lgkmcnt(0)")
     # ---------------- tiles ----------------
     labels = {}
     for par in range(4):
@@ -700,8 +526,8 @@ def main():
     rare = []                            # (raise labels, rescale labels) of every body: emitted behind the bodies
 
     def body(k, sg, more, more2, dma):
-        if OPT["align"] and k == "f" and sg == 0:
-            em.i(f".p2align {OPT['align']}")        # the steady-state loop starts on a 2^align-byte boundary
+        if k == "f" and sg == 0:
+            em.i(".p2align 6")                      # the steady-state loop starts on a 64-byte boundary
         em.i(f"{labels[(k, sg)]}:")
         tile(em, sg, more, more2, dma)
         rare.append((em.pending_raise, em.pending_rescale))
@@ -737,28 +563,6 @@ def main():
     em.i(f"s_branch {done}")
     em.i(f"{done}:")
     drain(em)
-    if TRACE:   # lane 0 of every wave: {phase X, phase Y, DMA wait, barrier} cycles summed over the tiles
-        skip = em.label("notrace")
-        em.i("s_cmp_eq_u64 %[tp], 0")
-        em.i(f"s_cbranch_scc1 {skip}")
-        em.i(f"v_mbcnt_lo_u32_b32 {vr(T[0])}, -1, 0")
-        em.i(f"v_mbcnt_hi_u32_b32 {vr(T[0])}, -1, {vr(T[0])}")
-        em.i(f"v_cmp_eq_u32 vcc, 0, {vr(T[0])}")
-        em.i("s_and_saveexec_b64 s[76:77], vcc")
-        em.i(f"v_mov_b32 {vr(T[2])}, 0")
-        for k in range(4):
-            em.i(f"v_mov_b32 {vr(T[0])}, s{64 + 2 * k}")
-            em.i(f"v_mov_b32 {vr(T[1])}, s{65 + 2 * k}")
-            em.i(f"global_store_dwordx2 {vr(T[2])}, {vr(T[0], 2)}, %[tp] offset:{8 * k}")
-            em.i("s_nop 1")
-        em.i("s_waitcnt vmcnt(0)")
-        em.i("s_mov_b64 exec, s[76:77]")
-        em.i(f"{skip}:")
-    if OPT["rowsum"] == "mfma4":
-        for e in range(2):
-            for h in range(2):
-                em.i(f"v_accvgpr_read_b32 {vr(PS(e, h))}, {ar(SACC(e, h))}")
-        em.i("s_nop 1")
     for e, o in ((0, "%[la]"), (1, "%[lb]")):
         em.i(f"v_add_f32 {o}, {vr(PS(e, 0))}, {vr(PS(e, 1))}")
     with open(out, "w") as f:
