@@ -320,6 +320,9 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
     }
 }
 
+// the grouped form (apexmi_gemm_fp8_grouped, apexmi_gemm_fp8_grouped_qkv): Fp8Group, gemm_fp8_kernel_grouped
+#include "gemm_fp8_grouped.inc"
+
 }  // namespace
 
 extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, float* scales,
@@ -423,4 +426,131 @@ extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa
     const Fp8LoraArgs lora{t, ldt, lb, ldb, Rp};
     return gemm_fp8_run(qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &lora,
                         (hipStream_t)stream_);
+}
+
+// both grouped entry points: every check of gemm_fp8_run per problem, before the launch; qkv = the fused q/k/v operands of
+// apexmi_gemm_fp8_grouped_qkv, or null for apexmi_gemm_fp8_grouped
+struct Fp8QkvArgs {
+    const int* is_qkv;
+    const void* const* norm_q;
+    const void* const* norm_k;
+    const int* row0;
+    int H;
+    float eps;
+    const float* rope;
+    void* q_out;
+    void* k_out;
+    void* vt_out;
+    int S_out, Skp;
+};
+
+static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t* lda, const float* const* sa, const void* const* qw,
+                                const int64_t* ldw, const int* w_format, const void* const* sw, const int64_t* sw_count,
+                                const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                                const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                                const Fp8QkvArgs* qkv, hipStream_t stream) {
+    APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "gemm_fp8_grouped: count=%d not in [1,%d]", count, FP8_MAX_GROUPS);
+    APEXMI_REQUIRE(qa && lda && sa && qw && ldw && w_format && sw && sw_count && C && ldc && M && N && epilogue,
+                   "gemm_fp8_grouped: null argument array");
+    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8_grouped: K=%d must be a multiple of 128", K);
+    Fp8Group G{};
+    G.count = count;
+    G.K = K;
+    G.clk = apexmi_clk_ptr();
+    if (qkv != nullptr) {
+        APEXMI_REQUIRE(qkv->is_qkv && qkv->row0 && qkv->rope && qkv->q_out && qkv->k_out && qkv->vt_out && qkv->H > 0,
+                       "gemm_fp8_grouped_qkv: null argument");
+        APEXMI_REQUIRE(qkv->S_out > 0 && qkv->Skp >= qkv->S_out && qkv->Skp % 8 == 0,
+                       "gemm_fp8_grouped_qkv: Skp=%d must be a multiple of 8 >= S_out=%d", qkv->Skp, qkv->S_out);
+        APEXMI_REQUIRE(((uintptr_t)qkv->rope % 16) == 0 && ((uintptr_t)qkv->q_out % 16) == 0 && ((uintptr_t)qkv->k_out % 16) == 0 &&
+                           ((uintptr_t)qkv->vt_out % 16) == 0,
+                       "gemm_fp8_grouped_qkv: rope / outputs must be 16-byte aligned");
+        G.qs = Fp8QkvShared{(bf16_t*)qkv->q_out, (bf16_t*)qkv->k_out, (bf16_t*)qkv->vt_out, qkv->rope, qkv->S_out, qkv->Skp,
+                            qkv->H * 128, qkv->eps};
+    }
+    double flops = 0, bytes = 0;
+    int64_t tiles = 0;
+    for (int i = 0; i < count; ++i) {
+        const bool fused = qkv != nullptr && qkv->is_qkv[i] != 0;
+        const void* b = bias ? bias[i] : nullptr;
+        const float* g = gate ? gate[i] : nullptr;
+        const void* r = R ? R[i] : nullptr;
+        const int64_t lr = ldr ? ldr[i] : 0;
+        void* c = fused ? qkv->q_out : C[i];               // a fused problem writes no C
+        const int64_t lc = fused ? N[i] : ldc[i];
+        const int epi = epilogue[i];
+        APEXMI_REQUIRE(qa[i] && sa[i] && qw[i] && sw[i] && c, "gemm_fp8_grouped: null operand (problem %d)", i);
+        APEXMI_REQUIRE(w_format[i] == 0, "gemm_fp8_grouped: weight format %d of problem %d is not e4m3fn (0): e5m2 weights take the "
+                                         "bf16 path (apexmi_dequant_fp8_scaled + apexmi_gemm_bf16_grouped)", w_format[i], i);
+        APEXMI_REQUIRE(M[i] >= 1, "gemm_fp8_grouped: M=%d of problem %d must be at least 1", M[i], i);
+        APEXMI_REQUIRE(N[i] >= 16 && N[i] % 16 == 0, "gemm_fp8_grouped: N=%d of problem %d must be a multiple of 16", N[i], i);
+        APEXMI_REQUIRE((epi & APEXMI_EPI_F32_IO) == 0 && epi != APEXMI_EPI_BIAS_F32,
+                       "gemm_fp8_grouped: f32 output (epilogue %d of problem %d, the f32 residual stream) is not supported: the output "
+                       "is bf16", epi, i);
+        APEXMI_REQUIRE(epi == APEXMI_EPI_BIAS || epi == APEXMI_EPI_BIAS_GELU || epi == APEXMI_EPI_BIAS_GATE_RES,
+                       "gemm_fp8_grouped: epilogue %d of problem %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", epi, i);
+        APEXMI_REQUIRE(sw_count[i] == 1 || sw_count[i] == N[i], "gemm_fp8_grouped: the weight scale of problem %d has %lld values for N=%d rows",
+                       i, (long long)sw_count[i], N[i]);
+        APEXMI_REQUIRE(lda[i] % 16 == 0 && ldw[i] % 16 == 0 && lc % 4 == 0 && lda[i] >= K && ldw[i] >= K && lc >= N[i],
+                       "gemm_fp8_grouped: leading dimensions must keep rows 16-byte aligned (problem %d: lda %lld, ldw %lld, ldc %lld)", i,
+                       (long long)lda[i], (long long)ldw[i], (long long)lc);
+        APEXMI_REQUIRE(lda[i] <= (1 << 22) && ldw[i] <= (1 << 22),
+                       "gemm_fp8_grouped: leading dimensions above 2^22 elements are not supported (problem %d: lda %lld, ldw %lld)", i,
+                       (long long)lda[i], (long long)ldw[i]);
+        APEXMI_REQUIRE(((uintptr_t)qa[i] % 16) == 0 && ((uintptr_t)qw[i] % 16) == 0 && ((uintptr_t)c % 8) == 0 &&
+                           ((uintptr_t)sa[i] % 4) == 0 && ((uintptr_t)sw[i] % (sw_count[i] == 1 ? 2 : 8)) == 0 && ((uintptr_t)b % 8) == 0,
+                       "gemm_fp8_grouped: operands must be 16-byte aligned (scales and bias 8-byte; problem %d)", i);
+        if (epi == APEXMI_EPI_BIAS_GATE_RES) {
+            APEXMI_REQUIRE(g && r, "gemm_fp8_grouped: gate/residual epilogue needs gate and R (problem %d)", i);
+            APEXMI_REQUIRE(lr % 4 == 0 && lr >= N[i] && ((uintptr_t)g % 16) == 0 && ((uintptr_t)r % 8) == 0,
+                           "gemm_fp8_grouped: gate/R alignment (problem %d)", i);
+        }
+        const int tm = (M[i] + FBM - 1) / FBM, tn = (N[i] + FBN - 1) / FBN;
+        G.p[i] = Fp8Problem{(const uint8_t*)qa[i], (const uint8_t*)qw[i], sa[i], (const bf16_t*)sw[i], (const bf16_t*)b, (bf16_t*)c, g,
+                            (const bf16_t*)r, lda[i], ldw[i], lc, lr, M[i], N[i], sw_count[i] == 1 ? 0 : 1, epi, tm, tn, (int)tiles,
+                            0, 0, nullptr, nullptr};
+        if (fused) {
+            APEXMI_REQUIRE(N[i] == 3 * qkv->H * 128 && epi == APEXMI_EPI_BIAS,
+                           "gemm_fp8_grouped_qkv: a fused problem has N = 3 H 128 = %d (got %d) and the plain bias epilogue", 3 * qkv->H * 128,
+                           N[i]);
+            APEXMI_REQUIRE(qkv->row0[i] >= 0 && qkv->row0[i] + M[i] <= qkv->S_out,
+                           "gemm_fp8_grouped_qkv: rows [%d, %d) must lie inside S_out=%d", qkv->row0[i], qkv->row0[i] + M[i], qkv->S_out);
+            const void* nq = qkv->norm_q ? qkv->norm_q[i] : nullptr;
+            const void* nk = qkv->norm_k ? qkv->norm_k[i] : nullptr;
+            APEXMI_REQUIRE(((uintptr_t)nq % 16) == 0 && ((uintptr_t)nk % 16) == 0, "gemm_fp8_grouped_qkv: norm weights must be 16-byte aligned");
+            G.p[i].qkv = 1;
+            G.p[i].row0 = qkv->row0[i];
+            G.p[i].nq = (const bf16_t*)nq;
+            G.p[i].nk = (const bf16_t*)nk;
+        }
+        tiles += (int64_t)tm * tn;
+        APEXMI_REQUIRE(tiles < (1ll << 31), "gemm_fp8_grouped: too many output tiles");
+        flops += 2.0 * M[i] * N[i] * (double)K;
+        bytes += (double)M[i] * K + (double)N[i] * K + 2.0 * (double)M[i] * N[i];
+    }
+    G.total = (int)tiles;
+    ApexmiProfScope prof(0, stream, flops, bytes);
+    hipLaunchKernelGGL(gemm_fp8_kernel_grouped, dim3((unsigned)tiles), dim3(256), 0, stream, G);
+    return apexmi_check_launch(qkv ? "gemm_fp8_grouped_qkv" : "gemm_fp8_grouped");
+}
+
+extern "C" int apexmi_gemm_fp8_grouped(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                       const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                       const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                       const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                       const void* const* R, const int64_t* ldr, apexmi_stream_t stream_) {
+    return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr,
+                                nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int apexmi_gemm_fp8_grouped_qkv(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                           const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                           const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                           const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                           const void* const* R, const int64_t* ldr, const int* is_qkv, const void* const* norm_q,
+                                           const void* const* norm_k, const int* row0, int H, float eps, const float* rope,
+                                           void* q_out, void* k_out, void* vt_out, int S_out, int Skp, apexmi_stream_t stream_) {
+    const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
+    return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr,
+                                &qkv, (hipStream_t)stream_);
 }

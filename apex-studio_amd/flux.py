@@ -191,6 +191,7 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
         self._bstreams: List[Any] = []
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (see _forward_one; APEX_FLUX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FLUX_FUSE_QKV", "1") != "0"
+        self._fp8_compute = self._fp8_fused_quant = False      # set_fp8_compute
 
     # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, cache_context, ...) ----
     def _anchor(self):
@@ -205,6 +206,9 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
     def pack(self):
         if self._packed:
             return
+        if getattr(self, "_fp8_bytes", 0):
+            raise _l.ApexMIError("flux.mi355: the block weights are resident fp8 records (keep_fp8 load) and their bf16 storage is "
+                                 "gone; moving / re-packing such a model is not supported — construct and load again")
         self._scheds.clear()
         self._pack_target()
         mods = []
@@ -235,6 +239,165 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
         if self.transformer_blocks and len(offs) > 2:
             self._mod_first = offs[2]  # img + txt projections of double block 0
         self._packed = True
+
+    # ---- fp8-scaled block weights resident in HBM (weights.load_checkpoint_into(keep_fp8=True)) and opt-in FP8 compute on them
+    #  ------------------------------------------------------------------------------------------------------
+    _fp8_formats = ("fp8",)            # GGUF blocks have no resident mode here (keep_quantized keeps raising)
+    _FP8_QKV = (("to_q", "to_k", "to_v"), ("add_q_proj", "add_k_proj", "add_v_proj"))
+
+    @staticmethod
+    def _fp8_resident_key(key: str) -> bool:
+        """Which fp8-scaled checkpoint tensors a `keep_fp8=True` load keeps as stored: the Linear weights of the double and single
+        blocks (attention projections, feed-forwards, proj_mlp, proj_out).  Embedders, the AdaLN projections (`norm*.linear`) and
+        the final projection stay dequantised at load."""
+        return key.startswith(("transformer_blocks.", "single_transformer_blocks.")) and key.endswith(".weight") \
+            and ".norm" not in key and ".processor." not in key
+
+    @classmethod
+    def _fp8_preflight(cls, keys) -> None:
+        """Called by the loader on the CONVERTED key list before any tensor is written.  The resident mode fuses q | k | v into
+        one record with a scale per row, so every part needs a `scale_weight` of its own, as diffusers-keyed fp8-scaled files
+        have.  A BFL-format file stores one fused `qkv` / `linear1` tensor with ONE scale, which the key converter splits by
+        rows: such a file is refused here, whole, instead of being half-loaded."""
+        keys = set(keys)
+        scaled = {k[:-len("scale_weight")] for k in keys if k.endswith("scale_weight")}
+        if not any(k.endswith(".weight") and cls._fp8_resident_key(k) and k[:-len("weight")] in scaled for k in keys):
+            raise NotImplementedError("flux.mi355 keep_fp8: the files hold no fp8-scaled block Linear of this model (no "
+                                      "transformer_blocks.* / single_transformer_blocks.* weight with a scale_weight partner): "
+                                      "there is nothing to keep resident; load without keep_fp8")
+        for k in sorted(keys):
+            for group in cls._FP8_QKV:
+                if k.endswith(f".attn.{group[0]}.weight") and cls._fp8_resident_key(k):
+                    base = k[:-len(f"{group[0]}.weight")]
+                    have = [f"{base}{n}." in scaled for n in group if f"{base}{n}.weight" in keys]
+                    if not all(have):
+                        raise _l.ApexMIError(
+                            f"flux.mi355 keep_fp8: '{base}{{{'|'.join(group)}}}' do not each carry a scale_weight after key "
+                            "conversion.  This is what a BFL-format fp8 file gives (one fused qkv / linear1 tensor with ONE scale, "
+                            "split by the converter): the resident mode takes diffusers-keyed fp8-scaled files (a separate to_q / "
+                            "to_k / to_v with a scale_weight each).  Load it without keep_fp8 (dequantised at load) instead; "
+                            "nothing was loaded.")
+
+    @torch.no_grad()
+    def _fp8_adopt(self):
+        """After a keep_fp8 load: q | k | v become ONE fused `ops.Fp8Weight` (per-row scales) behind `_wqkv` / `_wqkv_c`, every
+        other block Linear keeps its record on the parameter, and the adopted parameters' bf16 storage is released.  The blocks'
+        GEMMs dequantise per call (`ops.gemm`, `ops.gemm_grouped`) until `set_fp8_compute(True)`."""
+        self.pack()
+        dev, dt = self.device, self.dtype
+        names = {id(p): k[:-len(".weight")] for k, p in self.named_parameters() if k.endswith(".weight")}
+        for p in self.parameters():            # every record knows which Linear its rows are
+            f = getattr(p, "_fp8", None)
+            if f is not None:
+                f.parts = [(names[id(p)], 0, int(f.shape[0]))]
+        todo = []                              # (holder, attribute or None, parameters): decided for every block BEFORE anything is released
+        for blk in self.transformer_blocks:
+            a, ff, ffc = blk.attn, blk.ff.net, blk.ff_context.net
+            todo += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]),
+                     (blk, "_wqkv_c", [a.add_q_proj.weight, a.add_k_proj.weight, a.add_v_proj.weight])]
+            todo += [(blk, None, [p]) for p in (a.to_out[0].weight, a.to_add_out.weight, ff[0].proj.weight, ff[2].weight,
+                                                 ffc[0].proj.weight, ffc[2].weight)]
+        for blk in self.single_transformer_blocks:
+            a = blk.attn
+            todo += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]), (blk, None, [blk.proj_mlp.weight]),
+                     (blk, None, [blk.proj_out.weight])]
+        for _, _, parts in todo:
+            f8 = [getattr(p, "_fp8", None) for p in parts]
+            if any(f is None for f in f8) != all(f is None for f in f8) or len({f.q.dtype for f in f8 if f is not None}) > 1:
+                raise _l.ApexMIError(f"flux.mi355 keep_fp8: the fused projection {[names[id(p)] for p in parts]} mixes fp8-scaled "
+                                     "and plain weights (or two fp8 formats)")
+        n = 0
+        self._fp8_records = {}                 # module path -> the record holding its rows
+        for holder, attr, parts in todo:
+            f8 = [getattr(p, "_fp8", None) for p in parts]
+            if f8[0] is None:
+                continue
+            if attr is not None:
+                rec = ops.Fp8Weight.cat(f8)
+                setattr(holder, attr, rec)     # the fused record is the one that is read
+                for p in parts:
+                    del p._fp8
+            else:
+                rec = f8[0]
+            for p in parts:
+                p.data = torch.empty(0, device=dev, dtype=dt)
+            n += rec.nbytes()
+            self._fp8_records.update({m: rec for m, _, _ in rec.parts})
+        self._fp8_bytes = n
+        torch.cuda.empty_cache()
+        return self
+
+    def state_dict(self, *a, **k):
+        if getattr(self, "_fp8_bytes", 0):
+            raise _l.ApexMIError("flux.mi355: this model was loaded with keep_fp8=True — its block weights live as fp8 records "
+                                 "(inference only); it has no bf16 state dict to save.  Load without keep_fp8 to serialise.")
+        return super().state_dict(*a, **k)
+
+    def _lora_param(self, module: str, what: str):
+        if module in (getattr(self, "_fp8_records", None) or {}):
+            raise _l.ApexMIError(f"flux.mi355: '{module}' is a resident fp8 Linear (keep_fp8 load): there is no bf16 weight to merge a "
+                                 "LoRA into, and run-time LoRA on resident Flux weights is not supported — load without keep_fp8 "
+                                 "to use adapters")
+        return super()._lora_param(module, what)
+
+    def set_fp8_compute(self, on: bool, fused_quant: bool = False):
+        """Opt-in approximation: the block launches whose weights are RESIDENT e4m3 records (a `keep_fp8=True`
+        load) quantise their activations per row to e4m3 and multiply in fp8 — `ops.gemm_fp8_grouped` for the grouped launches
+        (the QKV pair with the fused q/k/v epilogue when `fuse_qkv` is set and no IP adapter is active), `ops.gemm`'s fp8 route
+        for the single block's proj_out — wherever `ops.fp8_grouped_route` / `ops.fp8_compute_route` hold.  Launches they refuse
+        (the f32-storage mode, a float `out` = gate_res of the f32 residual stream, e5m2 records) run today's path, and so does
+        everything outside the blocks.  False restores today's launches bit for bit.
+
+        `fused_quant=True` (needs `on=True`): the norms in front of the QKV launches and of the double block's FF-up launch write
+        the e4m3 codes and row scales themselves (`ops.ln_modulate_quant_fp8`); the bf16 rows, which nothing else reads, are not
+        stored.  A launch and traffic change only: the forward is bit-identical to `fused_quant=False`."""
+        if fused_quant and not on:
+            raise ValueError("flux.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
+        recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values()}
+        if not recs:
+            raise _l.ApexMIError("flux.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
+                                 "fp8-scaled checkpoint with keep_fp8=True")
+        for r in recs.values():
+            r.compute = "fp8" if on else "bf16"
+        self._fp8_compute, self._fp8_fused_quant = bool(on), bool(fused_quant)
+        return self
+
+    def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, **kw):
+        """ln_modulate(X, *mod, out=XN, **kw) in front of a grouped launch (bf16 outputs) over the row ranges `rows` of XN and the
+        weights `w_list`, which is the ONLY reader of XN.  With `set_fp8_compute(fused_quant=True)`, where that launch takes its
+        fp8 route and the fused norm accepts the rows, the norm quantises in its own launch and does not store XN: returns
+        (codes, scales), else None.  An empty `w_list` = the caller already knows that the launch does not route."""
+        if self._fp8_fused_quant and w_list:
+            ws = [w if ops._fp8_of(w) is None else ops._fp8_of(w) for w in w_list]
+            probe = XN.new_empty((0,), dtype=torch.bfloat16)     # the predicates read the dtype of `out` only
+            epis = [epilogue] * len(ws) if isinstance(epilogue, str) else list(epilogue)
+            if ops.fp8_grouped_route([XN[r] for r in rows], ws, [probe] * len(ws), epis) \
+                    and ops.fp8_norm_quant_route(X, XN, ws[0], probe, epis[0])[0]:
+                return ops.ln_modulate_quant_fp8(X, *mod, **kw)
+        ops.ln_modulate(X, *mod, out=XN, **kw)
+        return None
+
+    def _rows_fp8(self, src, quantised):
+        """(codes, scales) of the rows of the joint buffer `src`: the fused norm's, or one `quant_rows_fp8` launch into the
+        per-stream scratch.  The codes of one joint buffer serve both streams as row slices."""
+        if quantised is not None:
+            return quantised
+        qa, sa = ops._act_scratch(src.device, src.shape[0], src.shape[1])
+        return ops.quant_rows_fp8(src, out=qa, scale_out=sa)
+
+    def _grouped(self, src, rows, w_list, bias_list, out_list, epilogue, gate_list=None, residual_list=None, quantised=None):
+        """One grouped launch whose problems read the row ranges `rows` (slices) of ONE activation buffer `src`: today's
+        `ops.gemm_grouped`, or — in fp8-compute mode, when `ops.fp8_grouped_route` holds for every problem — one quantise launch
+        over `src` (unless `quantised` brings the codes) and `ops.gemm_fp8_grouped`."""
+        w_list = [w if ops._fp8_of(w) is None else ops._fp8_of(w) for w in w_list]
+        a_list = [src[r] for r in rows]
+        if self._fp8_compute and ops.fp8_grouped_route(a_list, w_list, out_list, epilogue):
+            qa, sa = self._rows_fp8(src, quantised)
+            return ops.gemm_fp8_grouped([qa[r] for r in rows], [sa[r] for r in rows], w_list, bias_list, out_list, epilogue=epilogue,
+                                        gate_list=gate_list, residual_list=residual_list)
+        assert quantised is None, "the fused norm did not store the rows this launch reads"
+        return ops.gemm_grouped(a_list, w_list, bias_list, out_list, epilogue=epilogue, gate_list=gate_list,
+                                residual_list=residual_list)
 
     def _workspace(self, s_txt: int, s_img: int):
         # one workspace per (shape, HIP stream): two clips may run through one resident model on two streams
@@ -416,10 +579,22 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
         mixed = self.storage_dtype == torch.float32 and ops.shipped_verification()
         fuse = self.fuse_qkv and (self.storage_dtype == torch.bfloat16 or mixed) and self.transformer_blocks is not None
         # IP-adapter: the image queries are needed normalised but NOT rotated (attention.py:199) -> the two-pass q/k/v preparation
-        fuse_d = fuse and ip is None and len(self.transformer_blocks) > 0 and ops.qkv_fusable(
+        # resident fp8 weights: gemm_grouped_qkv needs bf16 weights, so bf16 compute on them takes the two-pass path; fp8 compute
+        # has its own fused form (gemm_fp8_grouped_qkv: any row count), decided per launch class by the routing predicate
+        resident = bool(getattr(self, "_fp8_bytes", 0))
+        fuse_d = fuse and not resident and ip is None and len(self.transformer_blocks) > 0 and ops.qkv_fusable(
             [XNi, XNt], [self.transformer_blocks[0]._wqkv, self.transformer_blocks[0]._wqkv_c], [s_txt, 0], H)
-        fuse_s = fuse and len(self.single_transformer_blocks) > 0 and ops.qkv_fusable(
+        fuse_s = fuse and not resident and len(self.single_transformer_blocks) > 0 and ops.qkv_fusable(
             [XN, XN], [self.single_transformer_blocks[0]._wqkv, self.single_transformer_blocks[0].proj_mlp.weight], [0, 0], H)
+        fp8 = resident and self._fp8_compute
+        rec = lambda w: w if ops._fp8_of(w) is None else ops._fp8_of(w)      # noqa: E731  (the resident record behind a parameter)
+        both, img_txt = [slice(None), slice(None)], [slice(s_txt, None), slice(0, s_txt)]
+        fp8_d = fp8 and len(self.transformer_blocks) > 0 and ops.fp8_grouped_route(
+            [XNi, XNt], [self.transformer_blocks[0]._wqkv, self.transformer_blocks[0]._wqkv_c], [QKV[s_txt:], QKV[:s_txt]], "bias")
+        fp8_s = fp8 and not overlap and len(self.single_transformer_blocks) > 0 and ops.fp8_grouped_route(
+            [XN, XN], [self.single_transformer_blocks[0]._wqkv, rec(self.single_transformer_blocks[0].proj_mlp.weight)],
+            [QKV, CAT[:, dim:]], ["bias", "gelu"])
+        fuse8_d, fuse8_s = fp8_d and self.fuse_qkv and ip is None, fp8_s and self.fuse_qkv
         if overlap and self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
         if mixed:        # the fused launches and the flash kernel behind them exchange bf16 q / k / v^T (ws.Qb ..), as in production
@@ -443,15 +618,22 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
             mi = lambda j: self._mod(MOD, ("d", i, "img"), j)  # noqa: E731
             mt = lambda j: self._mod(MOD, ("d", i, "txt"), j)  # noqa: E731
             # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-            ops.ln_modulate(X, mi(1), mi(0), out=XN, split=s_txt, scale2=mt(1), shift2=mt(0))
-            if fuse_d:
+            qn = self._norm_rows(X, XN, img_txt, [blk._wqkv, blk._wqkv_c] if fp8_d else [], "bias", mi(1), mi(0), split=s_txt,
+                                 scale2=mt(1), shift2=mt(0))
+            if fuse8_d:
+                qa, sa = self._rows_fp8(XN, qn)
+                ops.gemm_fp8_grouped_qkv([qa[s_txt:], qa[:s_txt]], [sa[s_txt:], sa[:s_txt]], [blk._wqkv, blk._wqkv_c],
+                                         [blk._bqkv, blk._bqkv_c], [None, None], "bias", [1, 1],
+                                         [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
+                                         [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
+            elif fuse_d:
                 # q/k norm + RoPE + [H, S, D] layout and V^T leave the QKV GEMM's epilogue: no [S, 3 dim] round trip
                 ops.gemm_grouped_qkv([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [None, None], "bias",
                                      [1, 1], [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
                                      [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
             else:
-                ops.gemm_grouped([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c],
-                                 [QKV[s_txt:], QKV[:s_txt]])
+                self._grouped(XN, img_txt, [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [QKV[s_txt:], QKV[:s_txt]], "bias",
+                              quantised=qn)
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VT[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, wq2=a.norm_added_q.weight, wk2=a.norm_added_k.weight,
                                 split=s_txt, eps=1e-6, rope=rope, rope_mode=_l.ROPE_INTERLEAVED)
@@ -460,17 +642,15 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
                     ws.IPQ = torch.empty(1, H, s_img, 128, device=X.device, dtype=self.storage_dtype)
                 ops.qkv_prepare(q_in[s_txt:], None, None, H, ws.IPQ[0], None, None, wq=a.norm_q.weight, eps=1e-6)
             ops.attention_prepared(Qp, Kp, VT, att_v, S)
-            ops.gemm_grouped([att[s_txt:], att[:s_txt]], [a.to_out[0].weight, a.to_add_out.weight],
-                             [a.to_out[0].bias, a.to_add_out.bias], [Xi, Xt], epilogue="gate_res",
-                             gate_list=[mi(2), mt(2)], residual_list=[Xi, Xt])
-            ops.ln_modulate(X, mi(4), mi(3), out=XN, split=s_txt, scale2=mt(4), shift2=mt(3))
+            self._grouped(att, img_txt, [a.to_out[0].weight, a.to_add_out.weight], [a.to_out[0].bias, a.to_add_out.bias], [Xi, Xt],
+                          "gate_res", gate_list=[mi(2), mt(2)], residual_list=[Xi, Xt])
             ff, ffc = blk.ff.net, blk.ff_context.net
-            ops.gemm_grouped([XNi, XNt], [ff[0].proj.weight, ffc[0].proj.weight],
-                             [ff[0].proj.bias, ffc[0].proj.bias], [FFH[s_txt:], FFH[:s_txt]],
-                             epilogue="gelu")
-            ops.gemm_grouped([FFH[s_txt:], FFH[:s_txt]], [ff[2].weight, ffc[2].weight],
-                             [ff[2].bias, ffc[2].bias], [Xi, Xt], epilogue="gate_res",
-                             gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt])
+            qn = self._norm_rows(X, XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight] if fp8 else [], "gelu", mi(4), mi(3),
+                                 split=s_txt, scale2=mt(4), shift2=mt(3))
+            self._grouped(XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight], [ff[0].proj.bias, ffc[0].proj.bias],
+                          [FFH[s_txt:], FFH[:s_txt]], "gelu", quantised=qn)
+            self._grouped(FFH, img_txt, [ff[2].weight, ffc[2].weight], [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res",
+                          gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt])
             if ip is not None:
                 # `hidden_states + ip_attn_output` AFTER the feed-forward (model.py:308-309); ip_attn_output = sum over adapters of
                 # scale x attention(image queries, to_k_ip(tokens), to_v_ip(tokens)) (attention.py:232-262): a few keys per adapter
@@ -494,7 +674,7 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
             a = blk.attn
             Qp, Kp, VT = qkv_s
             ms = lambda j: self._mod(MOD, ("s", i), j)  # noqa: E731  (shift, scale, gate)
-            ops.ln_modulate(X, ms(1), ms(0), out=XN)
+            qn = self._norm_rows(X, XN, both, [blk._wqkv, blk.proj_mlp.weight] if fp8_s else [], ["bias", "gelu"], ms(1), ms(0))
             if overlap:
                 # experiment (APEX_FLUX_OVERLAP=1): the MLP-up GEMM on the side stream underneath q/k prepare +
                 # attention, whose 1.69-round launch leaves 80 CUs idle in its second round
@@ -507,15 +687,20 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
                     mlp_done = torch.cuda.Event()
                     mlp_done.record(self._side)
                 ops.gemm(XN, blk._wqkv, blk._bqkv, out=QKV)
+            elif fuse8_s:
+                qa, sa = self._rows_fp8(XN, qn)
+                ops.gemm_fp8_grouped_qkv([qa, qa], [sa, sa], [blk._wqkv, rec(blk.proj_mlp.weight)], [blk._bqkv, blk.proj_mlp.bias],
+                                         [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
+                                         [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
             elif fuse_s:
                 ops.gemm_grouped_qkv([XN, XN], [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias],
                                      [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
                                      [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
             else:
                 # QKV and MLP-up read the same XN: one launch, 1512 tiles = 5.9 rounds of the 256 CUs
-                ops.gemm_grouped([XN, XN], [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias],
-                                 [QKV, CAT[:, dim:]], epilogue=["bias", "gelu"])
-            if overlap or not fuse_s:
+                self._grouped(XN, both, [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias], [QKV, CAT[:, dim:]],
+                              ["bias", "gelu"], quantised=qn)
+            if overlap or not (fuse_s or fuse8_s):
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VT[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, split=0, eps=1e-6, rope=rope,
                                 rope_mode=_l.ROPE_INTERLEAVED)

@@ -606,6 +606,141 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
     return out
 
 
+FP8_MAX_GROUPS = 4
+
+
+def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
+    """Whether a grouped launch over these problems may go out as quantise + `gemm_fp8_grouped`.  Pure, like `fp8_compute_route`
+    (dtypes, shapes and strides only; CPU tensors are fine): true only when EVERY problem satisfies `fp8_compute_route` — a
+    launch is all fp8 or all today's path, never mixed — and there are 1 to 4 of them sharing K.  `epilogues`: one name or one
+    per problem; `out_list`: None, or one tensor (or None) per problem."""
+    n = len(a_list)
+    if not 1 <= n <= FP8_MAX_GROUPS or len(w_list) != n:
+        return False
+    epis = [epilogues] * n if isinstance(epilogues, str) else list(epilogues)
+    outs = [None] * n if out_list is None else list(out_list)
+    if len(epis) != n or len(outs) != n or len({a.shape[-1] for a in a_list}) != 1:
+        return False
+    return all(fp8_compute_route(a, w, o, e) for a, w, o, e in zip(a_list, w_list, outs, epis))
+
+
+def fp8_grouped_tiles(shapes):
+    """The tile each workgroup of a `gemm_fp8_grouped` launch over problems `shapes` = [(M, N), ...] computes, restated from the
+    kernel (csrc/gemm_fp8.hip, gemm_fp8_kernel_grouped): a list over block ids of (problem, tile row, tile column).  The XCD remap
+    runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts, and inside a problem
+    bands of 8 tile rows are walked column by column."""
+    tm = [(m + 127) // 128 for m, _ in shapes]
+    tn = [(n + 127) // 128 for _, n in shapes]
+    tile0 = [sum(a * b for a, b in zip(tm[:i], tn[:i])) for i in range(len(shapes))]
+    total = sum(a * b for a, b in zip(tm, tn))
+    q, r = total >> 3, total & 7
+    out = []
+    for bid in range(total):
+        xcd, idx = bid & 7, bid >> 3
+        t = (xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q) + idx
+        pi = 0
+        for i in range(1, len(shapes)):
+            if t >= tile0[i]:
+                pi = i
+        t -= tile0[pi]
+        band = 8 * tn[pi]
+        first_m = (t // band) * 8
+        gsz = min(tm[pi] - first_m, 8)
+        out.append((pi, first_m + (t % band) % gsz, (t % band) // gsz))
+    return out
+
+
+def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None):
+    """ctypes arrays of a grouped fp8 launch after the per-problem checks of `gemm_fp8`; `fused[i]`: problem i writes no `out`.
+    Counts above 4, e5m2 records and float outputs are refused by the entry point with its own message."""
+    import ctypes as C
+    n = len(codes_list)
+    epis = [epilogue] * n if isinstance(epilogue, str) else list(epilogue)
+    none = [None] * n
+    bias_list, gate_list, residual_list = bias_list or none, gate_list or none, residual_list or none
+    fused = fused or [0] * n
+    K = codes_list[0].shape[1]
+    flags = []
+    for qa, sa, w, b, o, e, g, r, f in zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list, residual_list, fused):
+        _req(qa, torch.uint8, who + ".codes")
+        _req(sa, torch.float32, who + ".scales")
+        if not isinstance(w, Fp8Weight):
+            raise _l.ApexMIError(f"{who}: expected an Fp8Weight, got {type(w).__name__}")
+        if e not in _FP8_EPI:
+            raise _l.ApexMIError(f"{who}: epilogue '{e}' is not one of {_FP8_EPI}")
+        assert qa.dim() == 2 and qa.stride(1) == 1 and sa.is_contiguous() and sa.numel() == qa.shape[0]
+        assert qa.shape[1] == K and w.shape[1] == K
+        M, N = qa.shape[0], w.shape[0]
+        flag = 0
+        if not f:
+            _req(o, None, who + ".out")
+            assert o.shape == (M, N) and o.stride(1) == 1
+            if o.dtype == torch.float32:         # rejected by the entry point with its own message
+                flag = _l.EPI_F32_IO
+            else:
+                _req(o, torch.bfloat16, who + ".out")
+        flags.append(flag)
+        if b is not None:
+            _req(b, torch.bfloat16, who + ".bias")
+            assert b.is_contiguous() and b.numel() == N
+        if e == "gate_res":
+            _req(g, torch.float32, who + ".gate")
+            _req(r, o.dtype, who + ".residual")
+            assert g.is_contiguous() and g.numel() == N and r.shape == (M, N) and r.stride(1) == 1
+    VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
+    return (n, VP(*[t.data_ptr() for t in codes_list]), I64(*[t.stride(0) for t in codes_list]),
+            VP(*[t.data_ptr() for t in scales_list]), VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),
+            INT(*[0 if w.q.dtype == torch.float8_e4m3fn else 1 for w in w_list]), VP(*[w.scale.data_ptr() for w in w_list]),
+            I64(*[w.scale.numel() for w in w_list]), VP(*[_ptr(b) for b in bias_list]),
+            VP(*[None if f else o.data_ptr() for o, f in zip(out_list, fused)]),
+            I64(*[0 if f else o.stride(0) for o, f in zip(out_list, fused)]), INT(*[t.shape[0] for t in codes_list]),
+            INT(*[w.shape[0] for w in w_list]), K, INT(*[_EPI[e] | fl for e, fl in zip(epis, flags)]),
+            VP(*[_ptr(g) if e == "gate_res" else None for g, e in zip(gate_list, epis)]),
+            VP(*[_ptr(r) if e == "gate_res" else None for r, e in zip(residual_list, epis)]),
+            I64(*[(r.stride(0) if (r is not None and e == "gate_res") else 0) for r, e in zip(residual_list, epis)]))
+
+
+def gemm_fp8_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilogue="bias", gate_list=None,
+                     residual_list=None) -> None:
+    """Up to 4 `gemm_fp8` problems sharing K in ONE launch (img / txt streams; QKV + MLP-up of a single block): out_list[i] =
+    epi_i((codes_i . w_i.q^T) * scales_i[m] * w_i.scale[n] + bias_i), bit for bit what `gemm_fp8` leaves for that problem alone.
+    `epilogue` is one name or one per problem (bias / gelu / gate_res, freely mixed); a gate_res problem may have
+    residual_list[i] is out_list[i] (in place).  Several problems may share one (codes, scales) pair or row slices of it."""
+    args = _fp8_grouped_args("gemm_fp8_grouped", codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list,
+                             residual_list)
+    _l.check(_l.load().apexmi_gemm_fp8_grouped(*args, _stream()), "gemm_fp8_grouped")
+
+
+def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
+                         eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor) -> None:
+    """`gemm_fp8_grouped` with `qkv_prepare` fused into the epilogue of the problems flagged in `is_qkv` (fused QKV projections,
+    N = 3 H 128), mirroring `gemm_grouped_qkv`: q / k leave normalised per head, rotated and laid out [H, S_out, 128], v leaves
+    transposed [H, 128, Skp]; bit-identical to gemm_fp8_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
+    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count."""
+    import ctypes as C
+    n = len(codes_list)
+    args = _fp8_grouped_args("gemm_fp8_grouped_qkv", codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
+                             fused=[1 if f else 0 for f in is_qkv])
+    for t_ in (qo, ko, vt):
+        _req(t_, torch.bfloat16, "gemm_fp8_grouped_qkv output")
+        assert t_.is_contiguous()
+    _req(rope, torch.float32, "gemm_fp8_grouped_qkv.rope")
+    S_out = qo.shape[1]
+    assert qo.shape == ko.shape == (H, S_out, 128) and vt.shape[:2] == (H, 128) and rope.is_contiguous()
+    assert rope.shape == (2, S_out, 128)
+    none = [None] * n
+    for t_ in list(norm_q or none) + list(norm_k or none):
+        if t_ is not None:
+            _req(t_, torch.bfloat16, "gemm_fp8_grouped_qkv norm weight")
+            assert t_.is_contiguous() and t_.numel() == 128
+    VP, INT = C.c_void_p * n, C.c_int * n
+    rc = _l.load().apexmi_gemm_fp8_grouped_qkv(
+        *args, INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
+        VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
+        ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2], _stream())
+    _l.check(rc, "gemm_fp8_grouped_qkv")
+
+
 _EPI = {"bias": _l.EPI_BIAS, "gelu": _l.EPI_BIAS_GELU, "gate_res": _l.EPI_BIAS_GATE_RES,
         "gelu_erf": _l.EPI_BIAS_GELU_ERF, "silu": _l.EPI_BIAS_SILU, "quick_gelu": _l.EPI_BIAS_QUICK_GELU}
 
@@ -713,9 +848,9 @@ def gemm_grouped(a_list, w_list, bias_list, out_list, epilogue="bias", gate_list
             sizes = [0 if f is None else (f.shape[0] * f.shape[1] + 7) // 8 * 8 for f in f8s]
             dev = next(f for f in f8s if f is not None).device
             buf, off, ws = _scratch(dev, sum(sizes)), 0, []
-            for w, f, n in zip(w_list, f8s, sizes):
+            for w, f, sz in zip(w_list, f8s, sizes):      # (not `n`: that is the problem count the launch below takes)
                 ws.append(w if f is None else f.dequant(out=buf[off:off + f.shape[0] * f.shape[1]].view(f.shape[0], f.shape[1])))
-                off += n
+                off += sz
             w_list = ws
     # bf16 operands with float outputs (and residuals): the f32 residual stream (see gemm)
     f32_out = act == torch.bfloat16 and out_list[0].dtype == torch.float32

@@ -103,8 +103,8 @@ def load_checkpoint_into(model: torch.nn.Module, files: Sequence[str], key_map: 
     pass through the converter's own already-converted test), None = keys are taken as they are, or a converters.KeyConverter.
 
     `keep_fp8`: fp8-scaled weights the model can hold RESIDENT (`model._fp8_resident_key(key)`: the block Linears of
-    `wan.mi355`) stay float8 + scale in HBM — `ops.Fp8Weight`, dequantised per call as the reference's FPScaledLinear does
-    (scaled_layer.py:390-552) — instead of being dequantised once into the bf16 parameter; the parameter's bf16 storage is
+    `wan.mi355` and `flux.mi355`) stay float8 + scale in HBM — `ops.Fp8Weight`, dequantised per call as the reference's
+    FPScaledLinear does (scaled_layer.py:390-552) — instead of being dequantised once into the bf16 parameter; the parameter's bf16 storage is
     released (`model._fp8_adopt()`).  Forwards are bit-identical to the dequantise-at-load path; half the weight bytes.
 
     `keep_quantized`: the same for GGUF files — quantised tensors of those weights stay ggml blocks in HBM (`ops.GgufWeight`,
@@ -115,6 +115,8 @@ def load_checkpoint_into(model: torch.nn.Module, files: Sequence[str], key_map: 
     if (keep_fp8 or keep_quantized) and resident is None:
         raise NotImplementedError(f"{type(model).__name__} has no resident quantised weight mode "
                                   f"({'keep_fp8' if keep_fp8 else 'keep_quantized'}=True): wan.mi355 has")
+    if keep_quantized and "gguf" not in getattr(model, "_fp8_formats", ("fp8", "gguf")):
+        raise NotImplementedError(f"{type(model).__name__} has no resident quantised weight mode (keep_quantized=True): wan.mi355 has")
     targets: Dict[str, torch.Tensor] = dict(model.named_parameters())
     targets.update({k: v for k, v in model.named_buffers() if k not in targets})
     if any(not t.is_cuda for t in targets.values()):
@@ -125,6 +127,8 @@ def load_checkpoint_into(model: torch.nn.Module, files: Sequence[str], key_map: 
         if isinstance(converter, NoOpKeyConverter):
             converter = None
     entries = list(iter_checkpoint(files, converter, key_map, list(targets)))
+    if resident is not None and hasattr(model, "_fp8_preflight"):
+        model._fp8_preflight([k for k, _ in entries])      # a file the resident mode cannot take is refused before anything is written
     scales = {k[:-len("scale_weight")]: ld for k, ld in entries if k.endswith("scale_weight")}
     seen, unexpected = set(), []
     for key, ld in entries:

@@ -789,6 +789,41 @@ int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa, const voi
                          const float* gate, const void* R, int64_t ldr, const void* t, int64_t ldt, const void* lb, int64_t ldb,
                          int Rp, apexmi_stream_t stream);
 
+/* apexmi_gemm_fp8_grouped — up to 4 apexmi_gemm_fp8 problems that share K in ONE launch (the image and text streams of an MM-DiT
+ * double block; QKV + MLP-up of a single block): the fp8 counterpart of apexmi_gemm_bf16_grouped.  Arrays are host arrays of
+ * length `count`; problem i has its own codes qa[i] / lda[i] / sa[i], weight codes qw[i] / ldw[i] / w_format[i] / sw[i] /
+ * sw_count[i] (1 or N[i]), bias[i], C[i] / ldc[i], M[i], N[i], epilogue[i] (bias, tanh GELU and gate x y + residual may be MIXED
+ * in one launch), gate[i] and R[i] / ldr[i] (R[i] may alias C[i]: each element is read, then written, by the same lane).  bias,
+ * gate, R and ldr may be NULL, as may their entries.  Per output element the arithmetic is apexmi_gemm_fp8's, so every problem
+ * leaves the bits it would leave alone; the order in which tiles run affects no value, and every tile of every problem runs
+ * exactly once.  Every rule of apexmi_gemm_fp8 holds per problem and is checked for all problems before the launch: nothing is
+ * written when one is refused (float8_e5m2, f32 output, K % 128 != 0, N % 16 != 0, count outside [1, 4]). */
+int apexmi_gemm_fp8_grouped(int count, const void* const* qa, const int64_t* lda, const float* const* sa, const void* const* qw,
+                            const int64_t* ldw, const int* w_format, const void* const* sw, const int64_t* sw_count,
+                            const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                            const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                            apexmi_stream_t stream);
+
+/* apexmi_gemm_fp8_grouped with the q/k/v preparation fused into the epilogue of the problems flagged in is_qkv: the contract of
+ * apexmi_gemm_bf16_grouped_qkv on the fp8 kernel, for any total row count and any H >= 1.
+ *   is_qkv[i] != 0: problem i is a fused QKV projection, N[i] = 3 H 128 ([q | k | v] rows of the weight) with the plain bias
+ *     epilogue; a 128-column tile is one head of q, of k or of v.  Its M[i] rows are rows [row0[i], row0[i] + M[i]) of the joint
+ *     sequence (any alignment: a stream whose row0 | M is not a multiple of 8 stores its V^T element-wise); norm_q[i] / norm_k[i] =
+ *     the RMSNorm weights (bf16[128], or NULL: no norm) of its stream; C[i] / ldc[i] are ignored.
+ *   is_qkv[i] == 0: an ordinary problem of the same launch with its own epilogue (the single block's MLP up-projection with GELU).
+ *   q_out, k_out: bf16 [H, S_out, 128]; vt_out: bf16 [H, 128, Skp] (Skp >= S_out, a multiple of 8; columns >= S_out are not
+ *   written — allocate it zeroed); rope: f32 [2, S_out, 128] (cos | sin rows as apexmi_rope_table_axes writes them).
+ * The tile is rounded to bf16 exactly where apexmi_gemm_fp8_grouped stores it and the norm and rotation run in the order of
+ * apexmi_qkv_prepare: q_out, k_out and columns < S_out of vt_out are BIT-IDENTICAL to apexmi_gemm_fp8_grouped followed by
+ * apexmi_qkv_prepare (rope_mode interleaved) on the same codes. */
+int apexmi_gemm_fp8_grouped_qkv(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc, const int* M,
+                                const int* N, int K, const int* epilogue, const float* const* gate, const void* const* R,
+                                const int64_t* ldr, const int* is_qkv, const void* const* norm_q, const void* const* norm_k,
+                                const int* row0, int H, float eps, const float* rope, void* q_out, void* k_out, void* vt_out,
+                                int S_out, int Skp, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
