@@ -80,7 +80,10 @@ constexpr int FBM = 128, FBN = 128, FBK = 128;
 constexpr int FOPB = FBM * FBK;              // bytes of one operand tile
 constexpr int UNIT_E8M0 = 0x7f7f7f7f;        // 2^0 in every byte: the block scales are not used
 
-struct Fp8Gemm {
+constexpr int FP8_MAX_GROUPS = 4;
+
+// the operands of ONE product: what the staging, the K-loop and the epilogue read, in every form of the kernel
+struct Fp8Problem {
     const uint8_t* A;     // activation codes [M, K]
     const uint8_t* W;     // weight codes [N, K]
     const float* sa;      // [M]
@@ -92,6 +95,10 @@ struct Fp8Gemm {
     int64_t lda, ldw, ldc, ldr;
     int M, N, K, sw_rows;  // sw_rows: 1 = one scale per weight row, 0 = a single value
     int tiles_m, tiles_n;
+};
+
+// a single launch (apexmi_gemm_fp8)
+struct Fp8Gemm : Fp8Problem {
     unsigned long long* clk;
 };
 
@@ -101,6 +108,33 @@ struct Fp8LoraGemm : Fp8Gemm {
     const bf16_t* LB;     // B' [N, Rp]
     int64_t ldt, ldb;
     int Rp;               // padded rank, a multiple of 64
+};
+
+// The grouped form (apexmi_gemm_fp8_grouped, apexmi_gemm_fp8_grouped_qkv): up to 4 problems that share K in ONE launch (the img +
+// txt streams of a Flux double block, QKV + MLP-up of a single block).  The table travels by value in the kernel arguments.
+// xcd_remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts (tile0), and the
+// epilogue (bias | gelu | gate_res) is chosen per problem: a block-uniform branch.
+struct Fp8GroupProblem : Fp8Problem {
+    int epi, tile0;
+    // fused q/k/v preparation (apexmi_gemm_fp8_grouped_qkv): N = 3 H 128, rows [row0, row0 + M) of the joint sequence, nq / nk = the
+    // per-head RMSNorm weights of this problem's stream (or null).  C is not written.
+    int qkv, row0;
+    const bf16_t* nq;
+    const bf16_t* nk;
+};
+struct Fp8QkvShared {        // outputs of the fused preparation, shared by the problems of a launch
+    bf16_t* qo;              // [H, S_out, 128]
+    bf16_t* ko;              // [H, S_out, 128]
+    bf16_t* vt;              // [H, 128, Skp]
+    const float* rope;       // [2, S_out, 128] f32 (cos | sin), interleaved pairs
+    int S_out, Skp, inner;   // inner = H * 128
+    float eps;
+};
+struct Fp8Group {
+    Fp8GroupProblem p[FP8_MAX_GROUPS];
+    int count, total;
+    Fp8QkvShared qs;
+    unsigned long long* clk;
 };
 
 APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
@@ -116,22 +150,231 @@ APEXMI_DEVICE bf16x8 lds_frag16(const uint8_t* tile, int row, int piece) {
     return *(const bf16x8*)(tile + row * FBK + ((piece ^ ((row >> 1) & 7)) << 4));
 }
 
+// this workgroup's tile id `t` inside its problem, and the problem: the launch itself, or the table entry found by the prefix sums
+APEXMI_DEVICE const Fp8Gemm& fp8_problem(const Fp8Gemm& G, int& t) {
+    t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
+    return G;
+}
+APEXMI_DEVICE Fp8GroupProblem fp8_problem(const Fp8Group& G, int& t) {
+    t = xcd_remap(blockIdx.x, G.total);
+    int pi = 0;
+#pragma unroll
+    for (int i = 1; i < FP8_MAX_GROUPS; ++i)
+        if (i < G.count && t >= G.p[i].tile0) pi = i;
+    const Fp8GroupProblem P = G.p[pi];
+    t -= P.tile0;
+    return P;
+}
+
+// the weight scales / the bias of the 4 columns n .. n + 3 (n clamped by the caller; a null bias is 0)
+APEXMI_DEVICE void fp8_unpack4(const u32x2 v, float (&f)[4]) { f[0] = bf16_lo(v[0]), f[1] = bf16_hi(v[0]), f[2] = bf16_lo(v[1]), f[3] = bf16_hi(v[1]); }
+
+APEXMI_DEVICE void fp8_load_sw(const Fp8Problem& G, int n, float (&sw)[4]) {
+    u32x2 s;
+    if (G.sw_rows) {          // uniform condition
+        s = *(const u32x2*)(G.sw + n);
+    } else {
+        const uint32_t one = G.sw[0];
+        s = u32x2{one * 0x10001u, one * 0x10001u};
+    }
+    fp8_unpack4(s, sw);
+}
+
+APEXMI_DEVICE void fp8_load_bias(const Fp8Problem& G, int n, float (&bs)[4]) {
+    u32x2 b = {0u, 0u};
+    if (G.bias != nullptr) b = *(const u32x2*)(G.bias + n);
+    fp8_unpack4(b, bs);
+}
+
+// ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
+// not SCALED (the LoRA form): the scales are in acc already, out = epi(acc + bias[n]).  The problem travels BY VALUE: by reference the
+// address arithmetic is redone at every store.
+template <int EPI, bool SCALED>
+APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, int m0, int n0, int wr, int wc, int fr, int fh) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float sw[4][4], bs[4][4];
+        f32x4 gt[4];
+        if constexpr (SCALED) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) fp8_load_sw(G, min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4), sw[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
+            fp8_load_bias(G, n, bs[g]);
+            if (EPI == APEXMI_EPI_BIAS_GATE_RES) gt[g] = *(const f32x4*)(G.gate + n);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m = m0 + 64 * wr + 32 * j + fr;
+            const int mc = min(m, G.M - 1);
+            float sa = 1.f;
+            if constexpr (SCALED) sa = G.sa[mc];
+            u32x2 rr[4];
+            if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
+                    rr[g] = *(const u32x2*)(G.R + (int64_t)mc * G.ldr + n);
+                }
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (SCALED) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                    else o[e] = acc[i][j][4 * g + e] + bs[g][e];
+                    if (EPI == APEXMI_EPI_BIAS_GELU) o[e] = gelu_tanh_f(o[e]);
+                }
+                if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
+                    o[0] = bf16_lo(rr[g][0]) + gt[g][0] * o[0];
+                    o[1] = bf16_hi(rr[g][0]) + gt[g][1] * o[1];
+                    o[2] = bf16_lo(rr[g][1]) + gt[g][2] * o[2];
+                    o[3] = bf16_hi(rr[g][1]) + gt[g][3] * o[3];
+                }
+                if (m < G.M && n < G.N)
+                    *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+            }
+        }
+    }
+}
+
+// Fused q/k/v preparation on a tile of a problem flagged `qkv` (N = 3 H 128: a 128-column tile is exactly one head of q, of k or
+// of v, which = n0 / inner is block-uniform).  The tile y = bf16(acc * sa * sw + bias) — the value the two-pass path stores — goes
+// into the staging LDS (free after the K-loop's last barrier) as [128 rows][128 bf16], row r rotated by rot(r) = (r >> 3) +
+// 2 (r & 7) sixteen-byte chunks: the 16 consecutive rows of a store phase and the 8 position chunks of a transposed read each
+// land on different chunks.
+//   q / k: re-read in the layout of qk_norm_rope4_body (elementwise.hip): 16 lanes per row, 8 consecutive columns per lane, the
+//          sequential sum of squares, the xor butterfly 8, 4, 2, 1, rsqrtf(sq / 128 + eps), x * r * w, the two fmaf forms of the
+//          interleaved rotation and a 16-byte store into [H, S_out, 128] at row row0 + m: bit-identical to that pass.
+//   v:     read transposed, 8 consecutive positions per lane, 16-byte stores into [H, 128, Skp]; a stream whose row0 | M is not
+//          a multiple of 8 stores element-wise (a wave = 64 consecutive positions of one d-row).
+// Rows >= M store nothing; columns >= S_out of V^T are not written.
+APEXMI_DEVICE int fp8_qkv_rot(int r) { return (r >> 3) + 2 * (r & 7); }
+
+APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupProblem& G, const Fp8QkvShared& Q, int m0, int n0, int tid,
+                                    uint8_t* lds) {
+    bf16_t* tile = (bf16_t*)lds;
+    const int lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1, fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float sw[4][4], bs[4][4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;          // N % 128 == 0: every column of the tile exists
+            fp8_load_sw(G, n, sw[g]);
+            fp8_load_bias(G, n, bs[g]);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r = 64 * wr + 32 * j + fr;
+            const float sa = G.sa[min(m0 + r, G.M - 1)];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = 64 * wc + 32 * i + 8 * g + 4 * fh;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                *(u32x2*)(tile + r * 128 + ((((c >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (c & 4)) =
+                    u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+            }
+        }
+    }
+    __syncthreads();
+    const int which = n0 / Q.inner;                    // 0 q, 1 k, 2 v: block-uniform
+    const int h = (n0 - which * Q.inner) >> 7;
+    if (which == 2) {
+        bf16_t* vt = Q.vt + (int64_t)h * 128 * Q.Skp + G.row0 + m0;
+        if (((G.row0 | G.M) & 7) != 0) {
+            for (int i = 0; i < 64; ++i) {
+                const int idx = i * 256 + tid;
+                const int r = idx & 127, d = idx >> 7;
+                const bf16_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
+                if (m0 + r < G.M) vt[(int64_t)d * Q.Skp + r] = e;
+            }
+            return;
+        }
+#pragma unroll 2
+        for (int i = 0; i < 8; ++i) {
+            const int idx = i * 256 + tid;
+            const int sc = idx & 7, d = (idx >> 3) & 127, s8 = ((idx >> 10) * 8 + sc) * 8;     // 8 lanes = 8 position chunks of one d
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int r = s8 + j;
+                const uint32_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
+                if (j & 1) w[j >> 1] |= e << 16;
+                else w[j >> 1] = e;
+            }
+            if (m0 + s8 < G.M) *(u32x4*)(vt + (int64_t)d * Q.Skp + s8) = u32x4{w[0], w[1], w[2], w[3]};
+        }
+        return;
+    }
+    const bf16_t* nw = which ? G.nk : G.nq;
+    bf16_t* dst = (which ? Q.ko : Q.qo) + (int64_t)h * Q.S_out * 128;
+    const int l16 = tid & 15, d = l16 * 8;
+    float wv[8];
+    if (nw != nullptr) unpack8(*(const u32x4*)(nw + d), wv);
+#pragma unroll 2
+    for (int p = 0; p < 8; ++p) {
+        const int r = p * 16 + (tid >> 4);
+        const int srow = G.row0 + min(m0 + r, G.M - 1);
+        const float* cp = Q.rope + (int64_t)srow * 128 + d;
+        const float* sp = Q.rope + (int64_t)Q.S_out * 128 + (int64_t)srow * 128 + d;
+        const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
+        const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
+        float cs[8], sn[8], x[8], y[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cs[j] = c0[j];
+            cs[j + 4] = c1[j];
+            sn[j] = s0[j];
+            sn[j + 4] = s1[j];
+        }
+        unpack8(*(const u32x4*)(tile + r * 128 + (((l16 + fp8_qkv_rot(r)) & 15) << 3)), x);
+        if (nw != nullptr) {
+            float sq = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sq += x[j] * x[j];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+            const float rn = rsqrtf(sq * (1.0f / 128) + Q.eps);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = x[j] * rn * wv[j];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            y[2 * q] = fmaf(x[2 * q], cs[2 * q], -(x[2 * q + 1] * sn[2 * q]));
+            y[2 * q + 1] = fmaf(x[2 * q + 1], cs[2 * q + 1], x[2 * q] * sn[2 * q + 1]);
+        }
+        if (m0 + r < G.M) store8<bf16_t>(dst + (int64_t)srow * 128 + d, y);
+    }
+}
+
 // LORA (G is an Fp8LoraGemm): after the fp8 K-loop the accumulators are scaled IN PLACE, acc = (acc * sa[m]) * sw[n], and a bf16 MFMA
 // tail adds sum_r t[m, r] B'[n, r] into the same registers, rank ascending: both MFMA shapes write the same 32 x 32 layout.  A rank
 // tile of 64 bf16 is 128 bytes per row — the geometry of a K-tile of codes — so t takes the activation half and B' the weight half
 // of a buffer, staged and swizzled as they are; the first rank tile is requested during the last K-tile.
-// ONE kernel name for both forms: build.py's no-spill check matches "gemm_fp8_kernel" and so covers every instantiation.
-template <int EPI, bool LORA>     // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
-__global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional_t<LORA, Fp8LoraGemm, Fp8Gemm> G) {
+// ONE kernel for the three forms, chosen by the argument type (Fp8Gemm, Fp8LoraGemm, Fp8Group): build.py's no-spill check matches
+// "gemm_fp8_kernel" and so covers every instantiation.
+// EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
+template <int EPI, class Args>
+__global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
+    constexpr bool LORA = std::is_same_v<Args, Fp8LoraGemm>, GROUPED = std::is_same_v<Args, Fp8Group>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * FOPB];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
 
-    // XCD-grouped tile order: each XCD takes a contiguous run of tiles; inside a run, bands of 8 tile rows share the weight tiles
-    const int total = G.tiles_m * G.tiles_n;
-    const int t = xcd_remap(blockIdx.x, total);
-    const int band = 8 * G.tiles_n, first_m = (t / band) * 8;
-    const int gsz = min(G.tiles_m - first_m, 8);
+    // XCD-grouped tile order: each XCD takes a contiguous run of tiles; inside a run (of one problem), bands of 8 tile rows share
+    // the weight tiles
+    int t;
+    const auto& P = fp8_problem(G, t);
+    const int band = 8 * P.tiles_n, first_m = (t / band) * 8;
+    const int gsz = min(P.tiles_m - first_m, 8);
     const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
 
     // staging: wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 rows per instruction
@@ -141,8 +384,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
     for (int i = 0; i < 4; ++i) {
         const int r = 32 * wid + 8 * i + (lane >> 3);
         const int c = (lane & 7) ^ ((r >> 1) & 7);
-        a_src[i] = (const char*)(G.A + (int64_t)min(m0 + r, G.M - 1) * G.lda + c * 16);
-        w_src[i] = (const char*)(G.W + (int64_t)min(n0 + r, G.N - 1) * G.ldw + c * 16);
+        a_src[i] = (const char*)(P.A + (int64_t)min(m0 + r, P.M - 1) * P.lda + c * 16);
+        w_src[i] = (const char*)(P.W + (int64_t)min(n0 + r, P.N - 1) * P.ldw + c * 16);
     }
     auto stage = [&](int kt, int buf) {
         uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;     // wave-uniform; the hardware adds lane * 16
@@ -179,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nk = G.K / FBK;
+    const int nk = P.K / FBK;
     const int fr = lane & 31, fh = lane >> 5;
     stage(0, 0);
     __syncthreads();
@@ -208,22 +451,6 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
         __syncthreads();
     }
 
-    // the weight scales of weight tile i: 4 column groups of 4 per lane, loaded from clamped addresses
-    auto load_sw = [&](int i, float (&sw)[4][4]) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
-            u32x2 s;
-            if (G.sw_rows) {          // uniform condition
-                s = *(const u32x2*)(G.sw + n);
-            } else {
-                const uint32_t one = G.sw[0];
-                s = u32x2{one * 0x10001u, one * 0x10001u};
-            }
-            sw[g][0] = bf16_lo(s[0]), sw[g][1] = bf16_hi(s[0]), sw[g][2] = bf16_lo(s[1]), sw[g][3] = bf16_hi(s[1]);
-        }
-    };
-
     if constexpr (LORA) {
         float sa[2];
 #pragma unroll
@@ -231,7 +458,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             float sw[4][4];
-            load_sw(i, sw);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) fp8_load_sw(G, min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4), sw[g]);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -268,60 +496,15 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const std::conditional
         }
     }
 
-    // ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
-    // LORA: the scales are in acc already, out = epi(acc + bias[n])
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float sw[4][4], bs[4][4];
-        f32x4 gt[4];
-        if constexpr (!LORA) load_sw(i, sw);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
-            u32x2 b = {0u, 0u};
-            if (G.bias != nullptr) b = *(const u32x2*)(G.bias + n);
-            bs[g][0] = bf16_lo(b[0]), bs[g][1] = bf16_hi(b[0]), bs[g][2] = bf16_lo(b[1]), bs[g][3] = bf16_hi(b[1]);
-            if (EPI == APEXMI_EPI_BIAS_GATE_RES) gt[g] = *(const f32x4*)(G.gate + n);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int m = m0 + 64 * wr + 32 * j + fr;
-            const int mc = min(m, G.M - 1);
-            float sa = 1.f;
-            if constexpr (!LORA) sa = G.sa[mc];
-            u32x2 rr[4];
-            if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int n = min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4);
-                    rr[g] = *(const u32x2*)(G.R + (int64_t)mc * G.ldr + n);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if constexpr (LORA) o[e] = acc[i][j][4 * g + e] + bs[g][e];
-                    else o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
-                    if (EPI == APEXMI_EPI_BIAS_GELU) o[e] = gelu_tanh_f(o[e]);
-                }
-                if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
-                    o[0] = bf16_lo(rr[g][0]) + gt[g][0] * o[0];
-                    o[1] = bf16_hi(rr[g][0]) + gt[g][1] * o[1];
-                    o[2] = bf16_lo(rr[g][1]) + gt[g][2] * o[2];
-                    o[3] = bf16_hi(rr[g][1]) + gt[g][3] * o[3];
-                }
-                if (m < G.M && n < G.N)
-                    *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
-            }
-        }
+    if constexpr (GROUPED) {
+        if (P.qkv) fp8_qkv_epilogue(acc, P, G.qs, m0, n0, tid, lds);
+        else if (P.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else if (P.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, true>(acc, P, m0, n0, wr, wc, fr, fh);
+    } else {
+        fp8_epilogue<EPI, !LORA>(acc, P, m0, n0, wr, wc, fr, fh);
     }
 }
-
-// the grouped form (apexmi_gemm_fp8_grouped, apexmi_gemm_fp8_grouped_qkv): Fp8Group, gemm_fp8_kernel_grouped
-#include "gemm_fp8_grouped.inc"
 
 }  // namespace
 
@@ -341,7 +524,60 @@ extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, v
     return apexmi_check_launch("quant_rows_fp8");
 }
 
-// both entry points: every check before any launch; lora = the adapter operands of apexmi_gemm_fp8_lora, or null for apexmi_gemm_fp8
+// ONE problem of any entry point: every check, then its operand record.  `who` = the entry point's name; `i` = the problem's index
+// in a grouped launch, which the messages name, or -1 for a single launch; tile0 = the tiles of the problems before it.
+static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const float* sa, const void* qw,
+                             int64_t ldw, int w_format, const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M,
+                             int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Fp8Problem* P) {
+    char of[32] = "", paren[32] = "", colon[32] = "", semi[32] = "";
+    if (i >= 0) {
+        snprintf(of, sizeof(of), " of problem %d", i);
+        snprintf(paren, sizeof(paren), " (problem %d)", i);
+        snprintf(colon, sizeof(colon), "problem %d: ", i);
+        snprintf(semi, sizeof(semi), "; problem %d", i);
+    }
+    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand%s", who, paren);
+    APEXMI_REQUIRE(w_format == 0, "%s: weight format %d%s is not e4m3fn (0): e5m2 weights take the bf16 path "
+                                  "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16%s)", who, w_format, of, i >= 0 ? "_grouped" : "");
+    APEXMI_REQUIRE(M >= 1, "%s: M=%d%s must be at least 1", who, M, of);
+    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "%s: N=%d%s must be a multiple of 16", who, N, of);
+    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "%s: K=%d must be a multiple of 128", who, K);
+    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
+                   "%s: f32 output (epilogue %d%s, the f32 residual stream) is not supported: the output is bf16", who, epilogue, of);
+    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
+                   "%s: epilogue %d%s is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue, of);
+    APEXMI_REQUIRE(sw_count == 1 || sw_count == N, "%s: the weight scale%s has %lld values for N=%d rows", who, of, (long long)sw_count, N);
+    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K && ldw >= K && ldc >= N,
+                   "%s: leading dimensions must keep rows 16-byte aligned (%slda %lld, ldw %lld, ldc %lld)", who, colon, (long long)lda,
+                   (long long)ldw, (long long)ldc);
+    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22), "%s: leading dimensions above 2^22 elements are not supported (%slda %lld, ldw %lld)",
+                   who, colon, (long long)lda, (long long)ldw);
+    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)sa % 4) == 0 &&
+                       ((uintptr_t)sw % (sw_count == 1 ? 2 : 8)) == 0 && ((uintptr_t)bias % 8) == 0,
+                   "%s: operands must be 16-byte aligned (scales and bias 8-byte%s)", who, semi);
+    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
+        APEXMI_REQUIRE(gate && R, "%s: gate/residual epilogue needs gate and R%s", who, paren);
+        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "%s: gate/R alignment%s", who, paren);
+    }
+    const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
+    APEXMI_REQUIRE(tile0 + (int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
+    *P = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
+                    lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, tm, tn};
+    return 0;
+}
+
+// a single launch of the kernel form that takes `Args`, with its compile-time epilogue
+template <class Args>
+static void fp8_launch(int epilogue, const Args& G, hipStream_t stream) {
+    const dim3 grid((unsigned)(G.tiles_m * G.tiles_n));
+    switch (epilogue) {
+        case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, Args>), grid, dim3(256), 0, stream, G); break;
+        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, Args>), grid, dim3(256), 0, stream, G); break;
+        default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, Args>), grid, dim3(256), 0, stream, G); break;
+    }
+}
+
+// both single entry points: every check before any launch; lora = the adapter operands of apexmi_gemm_fp8_lora, or null for apexmi_gemm_fp8
 struct Fp8LoraArgs {
     const void* t;
     int64_t ldt;
@@ -353,34 +589,10 @@ struct Fp8LoraArgs {
 static int gemm_fp8_run(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format, const void* sw,
                         int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                         const float* gate, const void* R, int64_t ldr, const Fp8LoraArgs* lora, hipStream_t stream) {
-    APEXMI_REQUIRE(qa && sa && qw && sw && C, "gemm_fp8: null operand");
-    APEXMI_REQUIRE(w_format == 0, "gemm_fp8: weight format %d is not e4m3fn (0): e5m2 weights take the bf16 path "
-                                  "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16)", w_format);
-    APEXMI_REQUIRE(M >= 1, "gemm_fp8: M=%d must be at least 1", M);
-    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "gemm_fp8: N=%d must be a multiple of 16", N);
-    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8: K=%d must be a multiple of 128", K);
-    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
-                   "gemm_fp8: f32 output (epilogue %d, the f32 residual stream) is not supported: the output is bf16", epilogue);
-    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
-                   "gemm_fp8: epilogue %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", epilogue);
-    APEXMI_REQUIRE(sw_count == 1 || sw_count == N, "gemm_fp8: the weight scale has %lld values for N=%d rows", (long long)sw_count, N);
-    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K && ldw >= K && ldc >= N,
-                   "gemm_fp8: leading dimensions must keep rows 16-byte aligned (lda %lld, ldw %lld, ldc %lld)", (long long)lda,
-                   (long long)ldw, (long long)ldc);
-    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22),
-                   "gemm_fp8: leading dimensions above 2^22 elements are not supported (lda %lld, ldw %lld)", (long long)lda,
-                   (long long)ldw);
-    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)sa % 4) == 0 &&
-                       ((uintptr_t)sw % (sw_count == 1 ? 2 : 8)) == 0 && ((uintptr_t)bias % 8) == 0,
-                   "gemm_fp8: operands must be 16-byte aligned (scales and bias 8-byte)");
-    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
-        APEXMI_REQUIRE(gate && R, "gemm_fp8: gate/residual epilogue needs gate and R");
-        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "gemm_fp8: gate/R alignment");
-    }
-    const int64_t tiles = (int64_t)((M + FBM - 1) / FBM) * ((N + FBN - 1) / FBN);
-    APEXMI_REQUIRE(tiles < (1ll << 31), "gemm_fp8: too many output tiles");
-    Fp8Gemm G{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
-              lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, (M + FBM - 1) / FBM, (N + FBN - 1) / FBN, apexmi_clk_ptr()};
+    Fp8Gemm G{};
+    if (fp8_check_problem("gemm_fp8", -1, 0, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G))
+        return 1;
+    G.clk = apexmi_clk_ptr();
     if (lora != nullptr) {
         const int Rp = lora->Rp;
         APEXMI_REQUIRE(Rp >= 64 && Rp % 64 == 0, "gemm_fp8_lora: the padded rank Rp=%d must be a multiple of 64 (set_lora pads to that)", Rp);
@@ -396,19 +608,11 @@ static int gemm_fp8_run(const void* qa, int64_t lda, const float* sa, const void
         Fp8LoraGemm L{G, (const bf16_t*)lora->t, (const bf16_t*)lora->lb, lora->ldt, lora->ldb, Rp};
         ApexmiProfScope prof(0, stream, 2.0 * M * N * ((double)K + Rp),
                              (double)M * K + (double)N * K + 2.0 * ((double)M + N) * Rp + 2.0 * (double)M * N);
-        switch (epilogue) {
-            case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
-            case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
-            default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, true>), dim3((unsigned)tiles), dim3(256), 0, stream, L); break;
-        }
+        fp8_launch(epilogue, L, stream);
         return apexmi_check_launch("gemm_fp8_lora");
     }
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (double)M * K + (double)N * K + 2.0 * (double)M * N);
-    switch (epilogue) {
-        case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
-        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
-        default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, false>), dim3((unsigned)tiles), dim3(256), 0, stream, G); break;
-    }
+    fp8_launch(epilogue, G, stream);
     return apexmi_check_launch("gemm_fp8");
 }
 
@@ -428,7 +632,7 @@ extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa
                         (hipStream_t)stream_);
 }
 
-// both grouped entry points: every check of gemm_fp8_run per problem, before the launch; qkv = the fused q/k/v operands of
+// both grouped entry points: fp8_check_problem per problem, before the launch; qkv = the fused q/k/v operands of
 // apexmi_gemm_fp8_grouped_qkv, or null for apexmi_gemm_fp8_grouped
 struct Fp8QkvArgs {
     const int* is_qkv;
@@ -455,7 +659,6 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
     APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8_grouped: K=%d must be a multiple of 128", K);
     Fp8Group G{};
     G.count = count;
-    G.K = K;
     G.clk = apexmi_clk_ptr();
     if (qkv != nullptr) {
         APEXMI_REQUIRE(qkv->is_qkv && qkv->row0 && qkv->rope && qkv->q_out && qkv->k_out && qkv->vt_out && qkv->H > 0,
@@ -472,45 +675,16 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
     int64_t tiles = 0;
     for (int i = 0; i < count; ++i) {
         const bool fused = qkv != nullptr && qkv->is_qkv[i] != 0;
-        const void* b = bias ? bias[i] : nullptr;
-        const float* g = gate ? gate[i] : nullptr;
-        const void* r = R ? R[i] : nullptr;
-        const int64_t lr = ldr ? ldr[i] : 0;
-        void* c = fused ? qkv->q_out : C[i];               // a fused problem writes no C
-        const int64_t lc = fused ? N[i] : ldc[i];
-        const int epi = epilogue[i];
-        APEXMI_REQUIRE(qa[i] && sa[i] && qw[i] && sw[i] && c, "gemm_fp8_grouped: null operand (problem %d)", i);
-        APEXMI_REQUIRE(w_format[i] == 0, "gemm_fp8_grouped: weight format %d of problem %d is not e4m3fn (0): e5m2 weights take the "
-                                         "bf16 path (apexmi_dequant_fp8_scaled + apexmi_gemm_bf16_grouped)", w_format[i], i);
-        APEXMI_REQUIRE(M[i] >= 1, "gemm_fp8_grouped: M=%d of problem %d must be at least 1", M[i], i);
-        APEXMI_REQUIRE(N[i] >= 16 && N[i] % 16 == 0, "gemm_fp8_grouped: N=%d of problem %d must be a multiple of 16", N[i], i);
-        APEXMI_REQUIRE((epi & APEXMI_EPI_F32_IO) == 0 && epi != APEXMI_EPI_BIAS_F32,
-                       "gemm_fp8_grouped: f32 output (epilogue %d of problem %d, the f32 residual stream) is not supported: the output "
-                       "is bf16", epi, i);
-        APEXMI_REQUIRE(epi == APEXMI_EPI_BIAS || epi == APEXMI_EPI_BIAS_GELU || epi == APEXMI_EPI_BIAS_GATE_RES,
-                       "gemm_fp8_grouped: epilogue %d of problem %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", epi, i);
-        APEXMI_REQUIRE(sw_count[i] == 1 || sw_count[i] == N[i], "gemm_fp8_grouped: the weight scale of problem %d has %lld values for N=%d rows",
-                       i, (long long)sw_count[i], N[i]);
-        APEXMI_REQUIRE(lda[i] % 16 == 0 && ldw[i] % 16 == 0 && lc % 4 == 0 && lda[i] >= K && ldw[i] >= K && lc >= N[i],
-                       "gemm_fp8_grouped: leading dimensions must keep rows 16-byte aligned (problem %d: lda %lld, ldw %lld, ldc %lld)", i,
-                       (long long)lda[i], (long long)ldw[i], (long long)lc);
-        APEXMI_REQUIRE(lda[i] <= (1 << 22) && ldw[i] <= (1 << 22),
-                       "gemm_fp8_grouped: leading dimensions above 2^22 elements are not supported (problem %d: lda %lld, ldw %lld)", i,
-                       (long long)lda[i], (long long)ldw[i]);
-        APEXMI_REQUIRE(((uintptr_t)qa[i] % 16) == 0 && ((uintptr_t)qw[i] % 16) == 0 && ((uintptr_t)c % 8) == 0 &&
-                           ((uintptr_t)sa[i] % 4) == 0 && ((uintptr_t)sw[i] % (sw_count[i] == 1 ? 2 : 8)) == 0 && ((uintptr_t)b % 8) == 0,
-                       "gemm_fp8_grouped: operands must be 16-byte aligned (scales and bias 8-byte; problem %d)", i);
-        if (epi == APEXMI_EPI_BIAS_GATE_RES) {
-            APEXMI_REQUIRE(g && r, "gemm_fp8_grouped: gate/residual epilogue needs gate and R (problem %d)", i);
-            APEXMI_REQUIRE(lr % 4 == 0 && lr >= N[i] && ((uintptr_t)g % 16) == 0 && ((uintptr_t)r % 8) == 0,
-                           "gemm_fp8_grouped: gate/R alignment (problem %d)", i);
-        }
-        const int tm = (M[i] + FBM - 1) / FBM, tn = (N[i] + FBN - 1) / FBN;
-        G.p[i] = Fp8Problem{(const uint8_t*)qa[i], (const uint8_t*)qw[i], sa[i], (const bf16_t*)sw[i], (const bf16_t*)b, (bf16_t*)c, g,
-                            (const bf16_t*)r, lda[i], ldw[i], lc, lr, M[i], N[i], sw_count[i] == 1 ? 0 : 1, epi, tm, tn, (int)tiles,
-                            0, 0, nullptr, nullptr};
+        Fp8GroupProblem& P = G.p[i];
+        // a fused problem writes no C: its q_out stands in, N wide
+        if (fp8_check_problem("gemm_fp8_grouped", i, tiles, qa[i], lda[i], sa[i], qw[i], ldw[i], w_format[i], sw[i], sw_count[i],
+                              bias ? bias[i] : nullptr, fused ? qkv->q_out : C[i], fused ? N[i] : ldc[i], M[i], N[i], K, epilogue[i],
+                              gate ? gate[i] : nullptr, R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P))
+            return 1;
+        P.epi = epilogue[i];
+        P.tile0 = (int)tiles;
         if (fused) {
-            APEXMI_REQUIRE(N[i] == 3 * qkv->H * 128 && epi == APEXMI_EPI_BIAS,
+            APEXMI_REQUIRE(N[i] == 3 * qkv->H * 128 && P.epi == APEXMI_EPI_BIAS,
                            "gemm_fp8_grouped_qkv: a fused problem has N = 3 H 128 = %d (got %d) and the plain bias epilogue", 3 * qkv->H * 128,
                            N[i]);
             APEXMI_REQUIRE(qkv->row0[i] >= 0 && qkv->row0[i] + M[i] <= qkv->S_out,
@@ -518,19 +692,18 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
             const void* nq = qkv->norm_q ? qkv->norm_q[i] : nullptr;
             const void* nk = qkv->norm_k ? qkv->norm_k[i] : nullptr;
             APEXMI_REQUIRE(((uintptr_t)nq % 16) == 0 && ((uintptr_t)nk % 16) == 0, "gemm_fp8_grouped_qkv: norm weights must be 16-byte aligned");
-            G.p[i].qkv = 1;
-            G.p[i].row0 = qkv->row0[i];
-            G.p[i].nq = (const bf16_t*)nq;
-            G.p[i].nk = (const bf16_t*)nk;
+            P.qkv = 1;
+            P.row0 = qkv->row0[i];
+            P.nq = (const bf16_t*)nq;
+            P.nk = (const bf16_t*)nk;
         }
-        tiles += (int64_t)tm * tn;
-        APEXMI_REQUIRE(tiles < (1ll << 31), "gemm_fp8_grouped: too many output tiles");
+        tiles += (int64_t)P.tiles_m * P.tiles_n;
         flops += 2.0 * M[i] * N[i] * (double)K;
         bytes += (double)M[i] * K + (double)N[i] * K + 2.0 * (double)M[i] * N[i];
     }
     G.total = (int)tiles;
     ApexmiProfScope prof(0, stream, flops, bytes);
-    hipLaunchKernelGGL(gemm_fp8_kernel_grouped, dim3((unsigned)tiles), dim3(256), 0, stream, G);
+    hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8Group>), dim3((unsigned)tiles), dim3(256), 0, stream, G);
     return apexmi_check_launch(qkv ? "gemm_fp8_grouped_qkv" : "gemm_fp8_grouped");
 }
 

@@ -35,7 +35,7 @@ from . import lib as _l
 from .schedule import ModulationSchedule, ScheduleRegistry
 from . import ops
 # the parameter holders live in module_base; they stay importable from here (the name older code and checkpoints' tools use)
-from .module_base import (F32ResidualMixin, HipTransformer, _AdaNorm, _Config, _FF, _Linear, _Norm, _TimestepEmbedding,  # noqa: F401
+from .module_base import (F32ResidualMixin, Fp8ResidentMixin, HipTransformer, _AdaNorm, _Config, _FF, _Linear, _Norm, _TimestepEmbedding,  # noqa: F401
                           _fuse_linears, _repoint)
 
 
@@ -146,7 +146,7 @@ class _TimeTextEmbed(nn.Module):
         self.text_embedder = _TimestepEmbedding(pooled_dim, dim, **kw)
 
 
-class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
+class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
     _converter_base = "flux.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "flux.mi355"
     _drops = {"moved": ("_packed", "_ws"), "loaded": ("_packed",), "storage": ("_ws",)}
@@ -206,9 +206,7 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
     def pack(self):
         if self._packed:
             return
-        if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("flux.mi355: the block weights are resident fp8 records (keep_fp8 load) and their bf16 storage is "
-                                 "gone; moving / re-packing such a model is not supported — construct and load again")
+        self._fp8_guard("pack")
         self._scheds.clear()
         self._pack_target()
         mods = []
@@ -278,59 +276,22 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
                             "to_k / to_v with a scale_weight each).  Load it without keep_fp8 (dequantised at load) instead; "
                             "nothing was loaded.")
 
-    @torch.no_grad()
-    def _fp8_adopt(self):
-        """After a keep_fp8 load: q | k | v become ONE fused `ops.Fp8Weight` (per-row scales) behind `_wqkv` / `_wqkv_c`, every
-        other block Linear keeps its record on the parameter, and the adopted parameters' bf16 storage is released.  The blocks'
-        GEMMs dequantise per call (`ops.gemm`, `ops.gemm_grouped`) until `set_fp8_compute(True)`."""
-        self.pack()
-        dev, dt = self.device, self.dtype
-        names = {id(p): k[:-len(".weight")] for k, p in self.named_parameters() if k.endswith(".weight")}
-        for p in self.parameters():            # every record knows which Linear its rows are
-            f = getattr(p, "_fp8", None)
-            if f is not None:
-                f.parts = [(names[id(p)], 0, int(f.shape[0]))]
-        todo = []                              # (holder, attribute or None, parameters): decided for every block BEFORE anything is released
+    def _fp8_plan(self):
+        plan = []
         for blk in self.transformer_blocks:
             a, ff, ffc = blk.attn, blk.ff.net, blk.ff_context.net
-            todo += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]),
+            plan += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]),
                      (blk, "_wqkv_c", [a.add_q_proj.weight, a.add_k_proj.weight, a.add_v_proj.weight])]
-            todo += [(blk, None, [p]) for p in (a.to_out[0].weight, a.to_add_out.weight, ff[0].proj.weight, ff[2].weight,
+            plan += [(blk, None, [p]) for p in (a.to_out[0].weight, a.to_add_out.weight, ff[0].proj.weight, ff[2].weight,
                                                  ffc[0].proj.weight, ffc[2].weight)]
         for blk in self.single_transformer_blocks:
             a = blk.attn
-            todo += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]), (blk, None, [blk.proj_mlp.weight]),
+            plan += [(blk, "_wqkv", [a.to_q.weight, a.to_k.weight, a.to_v.weight]), (blk, None, [blk.proj_mlp.weight]),
                      (blk, None, [blk.proj_out.weight])]
-        for _, _, parts in todo:
-            f8 = [getattr(p, "_fp8", None) for p in parts]
-            if any(f is None for f in f8) != all(f is None for f in f8) or len({f.q.dtype for f in f8 if f is not None}) > 1:
-                raise _l.ApexMIError(f"flux.mi355 keep_fp8: the fused projection {[names[id(p)] for p in parts]} mixes fp8-scaled "
-                                     "and plain weights (or two fp8 formats)")
-        n = 0
-        self._fp8_records = {}                 # module path -> the record holding its rows
-        for holder, attr, parts in todo:
-            f8 = [getattr(p, "_fp8", None) for p in parts]
-            if f8[0] is None:
-                continue
-            if attr is not None:
-                rec = ops.Fp8Weight.cat(f8)
-                setattr(holder, attr, rec)     # the fused record is the one that is read
-                for p in parts:
-                    del p._fp8
-            else:
-                rec = f8[0]
-            for p in parts:
-                p.data = torch.empty(0, device=dev, dtype=dt)
-            n += rec.nbytes()
-            self._fp8_records.update({m: rec for m, _, _ in rec.parts})
-        self._fp8_bytes = n
-        torch.cuda.empty_cache()
-        return self
+        return plan
 
     def state_dict(self, *a, **k):
-        if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("flux.mi355: this model was loaded with keep_fp8=True — its block weights live as fp8 records "
-                                 "(inference only); it has no bf16 state dict to save.  Load without keep_fp8 to serialise.")
+        self._fp8_guard("state_dict")
         return super().state_dict(*a, **k)
 
     def _lora_param(self, module: str, what: str):
@@ -353,12 +314,7 @@ class FluxTransformer2DModel(F32ResidualMixin, HipTransformer):
         stored.  A launch and traffic change only: the forward is bit-identical to `fused_quant=False`."""
         if fused_quant and not on:
             raise ValueError("flux.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
-        recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values()}
-        if not recs:
-            raise _l.ApexMIError("flux.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
-                                 "fp8-scaled checkpoint with keep_fp8=True")
-        for r in recs.values():
-            r.compute = "fp8" if on else "bf16"
+        self._fp8_set_compute(on)
         self._fp8_compute, self._fp8_fused_quant = bool(on), bool(fused_quant)
         return self
 

@@ -412,3 +412,87 @@ class F32ResidualMixin:
         self.residual_dtype = dtype
         self._invalidate("storage")
         return self
+
+
+class Fp8ResidentMixin:
+    """Quantised block weights RESIDENT in HBM (`weights.load_checkpoint_into(keep_fp8=True / keep_quantized=True)`: fp8-scaled,
+    SURVEY.md §8f-2, and GGUF blocks) of the Flux and Wan transformers, in front of HipTransformer in the bases: adopting the
+    records after the load, the refusals of a resident model and the switch of the opt-in FP8 compute.  The
+    `_fp8*` names date from the first of the two formats; a parameter's `_fp8` slot holds any ops.ResidentWeight.
+
+    A class supplies `_fp8_resident_key` (which checkpoint tensors stay as stored), `_fp8_plan()` and, without a resident mode
+    for GGUF blocks, `_fp8_formats = ("fp8",)`.  The messages start with the class's `_tag`."""
+
+    _fp8_formats = ("fp8", "gguf")
+
+    def _fp8_plan(self):
+        """[(holder, attribute or None, [weight parameters])] over the blocks: a projection fused from several Linears, read
+        through `holder.attribute`, or (None) one Linear, which keeps its record on the parameter."""
+        raise NotImplementedError
+
+    def _fp8_options(self) -> str:      # the load options of the class's resident modes, as the messages name them
+        return "keep_fp8 / keep_quantized" if "gguf" in self._fp8_formats else "keep_fp8"
+
+    @torch.no_grad()
+    def _fp8_adopt(self):
+        """After a keep_fp8 / keep_quantized load: every fused projection of the plan becomes ONE fused record (`ops.Fp8Weight`:
+        per-row scales; `ops.GgufWeight`: row segments), every other Linear keeps its record on the parameter, and the adopted
+        parameters' bf16 storage is released.  The blocks' GEMMs then dequantise per call (`ops._bf16_weight`) until
+        `set_fp8_compute(True)`.  Every group is checked BEFORE anything is released: a refusal leaves the model as loaded."""
+        self.pack()
+        dev, dt = self.device, self.dtype
+        names = {id(p): k[:-len(".weight")] for k, p in self.named_parameters() if k.endswith(".weight")}
+        for p in self.parameters():            # every record knows which Linear its rows are (run-time LoRA addresses them by name)
+            f = getattr(p, "_fp8", None)
+            if f is not None:
+                f.parts = [(names[id(p)], 0, int(f.shape[0]))]
+                p._fp8_shape = tuple(f.shape)
+        plan = self._fp8_plan()
+        for _, _, parts in plan:
+            f8 = [getattr(p, "_fp8", None) for p in parts]
+            if any(f is None for f in f8) != all(f is None for f in f8) or len({type(f) for f in f8}) > 1 \
+                    or len({f.q.dtype for f in f8 if isinstance(f, ops.Fp8Weight)}) > 1:
+                raise _l.ApexMIError(f"{self._tag} {self._fp8_options()}: the fused projection {[names[id(p)] for p in parts]} mixes "
+                                     "quantised and plain weights (or two quantised formats)")
+        n = 0
+        self._fp8_records = {}                 # module path -> the record holding its rows
+        for holder, attr, parts in plan:
+            f8 = [getattr(p, "_fp8", None) for p in parts]
+            if f8[0] is None:
+                continue
+            if attr is not None:
+                rec = type(f8[0]).cat(f8)
+                setattr(holder, attr, rec)     # the fused record is the one that is read; the parts' views of the bf16 buffer go
+                for p in parts:
+                    del p._fp8
+            else:
+                rec = f8[0]
+            for p in parts:
+                p.data = torch.empty(0, device=dev, dtype=dt)
+            n += rec.nbytes()
+            self._fp8_records.update({m: rec for m, _, _ in rec.parts})
+        self._fp8_bytes = n
+        torch.cuda.empty_cache()
+        return self
+
+    def _fp8_guard(self, what: str):
+        """`pack()` and `state_dict()` call this first: a model whose block weights are resident records has neither."""
+        if not getattr(self, "_fp8_bytes", 0):
+            return
+        opts = self._fp8_options()
+        kind = "quantised" if "gguf" in self._fp8_formats else "fp8"
+        if what == "pack":
+            raise _l.ApexMIError(f"{self._tag}: the block weights are resident {kind} records ({opts} load) and their bf16 storage is "
+                                 "gone; moving / re-packing such a model is not supported — construct and load again")
+        raise _l.ApexMIError(f"{self._tag}: this model was loaded with {opts.replace(' /', '=True /')}=True — its block weights live as "
+                             f"{kind} records (inference only); it has no bf16 state dict to save.  Load without {opts} to serialise.")
+
+    def _fp8_set_compute(self, on: bool) -> list:
+        """The distinct resident fp8 records (GGUF records have no fp8 compute), switched to fp8 or back to bf16 compute."""
+        recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values() if isinstance(r, ops.Fp8Weight)}
+        if not recs:
+            raise _l.ApexMIError(f"{self._tag}: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
+                                 "fp8-scaled checkpoint with keep_fp8=True")
+        for r in recs.values():
+            r.compute = "fp8" if on else "bf16"
+        return list(recs.values())

@@ -543,6 +543,40 @@ def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
     return codes, scale_out
 
 
+def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=None, fused=False, alloc=False):
+    """The checks of ONE fp8 GEMM problem, for `gemm_fp8` and for every problem of a grouped launch (`K`: the K they share).
+    Returns (out, flag): `out` (made here if None and `alloc`) and the epilogue flag of a float `out`, which the entry point
+    rejects with its own message, as it does e5m2 records.  `fused`: the problem writes no `out`."""
+    _req(codes, torch.uint8, who + ".codes")
+    _req(scales, torch.float32, who + ".scales")
+    if not isinstance(w, Fp8Weight):
+        raise _l.ApexMIError(f"{who}: expected an Fp8Weight, got {type(w).__name__}")
+    if epilogue not in _FP8_EPI:
+        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
+    assert codes.dim() == 2 and codes.stride(1) == 1 and scales.is_contiguous()
+    M, N = codes.shape[0], w.shape[0]
+    K = codes.shape[1] if K is None else K
+    assert codes.shape[1] == K and w.shape[1] == K and scales.numel() == M
+    flag = 0
+    if not fused:
+        if out is None and alloc:
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
+        _req(out, None, who + ".out")
+        assert out.shape == (M, N) and out.stride(1) == 1
+        if out.dtype == torch.float32:
+            flag = _l.EPI_F32_IO
+        else:
+            _req(out, torch.bfloat16, who + ".out")
+    if bias is not None:
+        _req(bias, torch.bfloat16, who + ".bias")
+        assert bias.is_contiguous() and bias.numel() == N
+    if epilogue == "gate_res":
+        _req(gate, torch.float32, who + ".gate")
+        _req(residual, out.dtype, who + ".residual")
+        assert gate.is_contiguous() and gate.numel() == N and residual.shape == (M, N) and residual.stride(1) == 1
+    return out, flag
+
+
 def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
              residual: Optional[torch.Tensor] = None, lora_t: Optional[torch.Tensor] = None,
@@ -557,36 +591,11 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
     and the result is rounded once."""
     if (lora_t is None) != (lora_B is None):
         raise _l.ApexMIError("gemm_fp8: lora_t and lora_B go together (both or neither)")
-    _req(codes, torch.uint8, "gemm_fp8.codes")
-    _req(scales, torch.float32, "gemm_fp8.scales")
-    if not isinstance(w, Fp8Weight):
-        raise _l.ApexMIError(f"gemm_fp8: expected an Fp8Weight, got {type(w).__name__}")
-    if epilogue not in _FP8_EPI:
-        raise _l.ApexMIError(f"gemm_fp8: epilogue '{epilogue}' is not one of {_FP8_EPI}")
-    assert codes.dim() == 2 and codes.stride(1) == 1 and scales.is_contiguous()
-    M, K = codes.shape
-    N = w.shape[0]
-    assert w.shape[1] == K and scales.numel() == M
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
-    else:
-        assert out.shape == (M, N) and out.stride(1) == 1
+    out, flag = _fp8_problem("gemm_fp8", codes, scales, w, bias, out, epilogue, gate, residual, alloc=True)
+    (M, K), N = codes.shape, w.shape[0]
     fmt = 0 if w.q.dtype == torch.float8_e4m3fn else 1
-    epi = _EPI[epilogue]
-    if out.dtype == torch.float32:           # rejected by the entry point with its own message
-        epi |= _l.EPI_F32_IO
-    else:
-        _req(out, torch.bfloat16, "gemm_fp8.out")
-    if bias is not None:
-        _req(bias, torch.bfloat16, "gemm_fp8.bias")
-        assert bias.is_contiguous() and bias.numel() == N
-    ldr = 0
-    if epilogue == "gate_res":
-        _req(gate, torch.float32, "gemm_fp8.gate")
-        _req(residual, out.dtype, "gemm_fp8.residual")
-        assert gate.is_contiguous() and gate.numel() == N
-        assert residual.shape == (M, N) and residual.stride(1) == 1
-        ldr = residual.stride(0)
+    epi = _EPI[epilogue] | flag
+    ldr = residual.stride(0) if epilogue == "gate_res" else 0
     if lora_t is not None:
         _req(lora_t, torch.bfloat16, "gemm_fp8.lora_t")
         _req(lora_B, torch.bfloat16, "gemm_fp8.lora_B")
@@ -626,7 +635,7 @@ def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
 
 def fp8_grouped_tiles(shapes):
     """The tile each workgroup of a `gemm_fp8_grouped` launch over problems `shapes` = [(M, N), ...] computes, restated from the
-    kernel (csrc/gemm_fp8.hip, gemm_fp8_kernel_grouped): a list over block ids of (problem, tile row, tile column).  The XCD remap
+    kernel (csrc/gemm_fp8.hip, fp8_problem and gemm_fp8_kernel): a list over block ids of (problem, tile row, tile column).  The XCD remap
     runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts, and inside a problem
     bands of 8 tile rows are walked column by column."""
     tm = [(m + 127) // 128 for m, _ in shapes]
@@ -651,7 +660,7 @@ def fp8_grouped_tiles(shapes):
 
 
 def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None):
-    """ctypes arrays of a grouped fp8 launch after the per-problem checks of `gemm_fp8`; `fused[i]`: problem i writes no `out`.
+    """ctypes arrays of a grouped fp8 launch after the per-problem checks (`_fp8_problem`); `fused[i]`: problem i writes no `out`.
     Counts above 4, e5m2 records and float outputs are refused by the entry point with its own message."""
     import ctypes as C
     n = len(codes_list)
@@ -660,33 +669,8 @@ def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list,
     bias_list, gate_list, residual_list = bias_list or none, gate_list or none, residual_list or none
     fused = fused or [0] * n
     K = codes_list[0].shape[1]
-    flags = []
-    for qa, sa, w, b, o, e, g, r, f in zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list, residual_list, fused):
-        _req(qa, torch.uint8, who + ".codes")
-        _req(sa, torch.float32, who + ".scales")
-        if not isinstance(w, Fp8Weight):
-            raise _l.ApexMIError(f"{who}: expected an Fp8Weight, got {type(w).__name__}")
-        if e not in _FP8_EPI:
-            raise _l.ApexMIError(f"{who}: epilogue '{e}' is not one of {_FP8_EPI}")
-        assert qa.dim() == 2 and qa.stride(1) == 1 and sa.is_contiguous() and sa.numel() == qa.shape[0]
-        assert qa.shape[1] == K and w.shape[1] == K
-        M, N = qa.shape[0], w.shape[0]
-        flag = 0
-        if not f:
-            _req(o, None, who + ".out")
-            assert o.shape == (M, N) and o.stride(1) == 1
-            if o.dtype == torch.float32:         # rejected by the entry point with its own message
-                flag = _l.EPI_F32_IO
-            else:
-                _req(o, torch.bfloat16, who + ".out")
-        flags.append(flag)
-        if b is not None:
-            _req(b, torch.bfloat16, who + ".bias")
-            assert b.is_contiguous() and b.numel() == N
-        if e == "gate_res":
-            _req(g, torch.float32, who + ".gate")
-            _req(r, o.dtype, who + ".residual")
-            assert g.is_contiguous() and g.numel() == N and r.shape == (M, N) and r.stride(1) == 1
+    flags = [_fp8_problem(who, qa, sa, w, b, o, e, g, r, K=K, fused=bool(f))[1]
+             for qa, sa, w, b, o, e, g, r, f in zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list, residual_list, fused)]
     VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
     return (n, VP(*[t.data_ptr() for t in codes_list]), I64(*[t.stride(0) for t in codes_list]),
             VP(*[t.data_ptr() for t in scales_list]), VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),

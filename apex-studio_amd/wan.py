@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import F32ResidualMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
+from .module_base import F32ResidualMixin, Fp8ResidentMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
 
 
 class _WanAttn(nn.Module):
@@ -110,7 +110,7 @@ class _Conv3dParams(nn.Module):
         self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
 
 
-class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
+class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "wan.mi355"
     _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans", "_band_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
@@ -251,12 +251,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
             raise ValueError("wan.mi355: set_fp8_compute(lora=True) needs on=True: the adapter tail belongs to the fp8 GEMM")
         if fused_quant and not on:
             raise ValueError("wan.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
-        recs = {id(r): r for r in (getattr(self, "_fp8_records", None) or {}).values() if isinstance(r, ops.Fp8Weight)}
-        if not recs:
-            raise _l.ApexMIError("wan.mi355: set_fp8_compute needs resident fp8 weight records and this model has none — load an "
-                                 "fp8-scaled checkpoint with keep_fp8=True")
-        for r in recs.values():
-            r.compute = "fp8" if on else "bf16"
+        for r in self._fp8_set_compute(on):
             r.lora_compute = "fp8" if lora else "bf16"
         self._fp8_compute = bool(on)
         self._fp8_fused_quant = bool(fused_quant)
@@ -307,10 +302,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
     def pack(self):
         if self._packed:
             return
-        if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("wan.mi355: the block weights are resident quantised records (keep_fp8 / keep_quantized load) and their "
-                                 "bf16 storage is gone; "
-                                 "moving / re-packing such a model is not supported — construct and load again")
+        self._fp8_guard("pack")
         dev, _ = self._pack_target()
         for blk in self.blocks:
             a1, a2 = blk.attn1, blk.attn2
@@ -331,50 +323,14 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         modulation tables are f32 copies: those stay dequantised.  The image branch's add_k_proj / add_v_proj stay bf16."""
         return key.startswith("blocks.") and key.endswith(".weight") and ".norm" not in key and ".add_" not in key
 
-    @torch.no_grad()
-    def _fp8_adopt(self):
-        """After a keep_fp8 / keep_quantized load: fused projections become fused `ops.Fp8Weight`s (per-row scales) or
-        `ops.GgufWeight`s (row segments), every adopted parameter's bf16 storage is released.  The blocks' GEMMs then dequantise per call (`ops._bf16_weight`)."""
-        self.pack()
-        dev, dt = self.device, self.dtype
-
-        names = {id(p): k[:-len(".weight")] for k, p in self.named_parameters() if k.endswith(".weight")}
-        for p in self.parameters():            # every record knows which Linear its rows are (run-time LoRA addresses them by name)
-            f = getattr(p, "_fp8", None)
-            if f is not None:
-                f.parts = [(names[id(p)], 0, int(f.shape[0]))]
-                p._fp8_shape = tuple(f.shape)
-
-        def fused(parts):
-            f8 = [getattr(p, "_fp8", None) for p in parts]
-            if all(f is None for f in f8):
-                return None
-            if any(f is None for f in f8):
-                raise _l.ApexMIError("wan.mi355 keep_fp8 / keep_quantized: a fused projection mixes quantised and plain weights")
-            if len({type(f) for f in f8}) != 1:
-                raise _l.ApexMIError("wan.mi355: a fused projection mixes fp8-scaled and GGUF-quantised weights")
-            return type(f8[0]).cat(f8)
-        n = 0
-        self._fp8_records = {}                 # module path -> the record holding its rows
+    def _fp8_plan(self):
+        plan = []
         for blk in self.blocks:
             a1, a2 = blk.attn1, blk.attn2
-            for name, parts in (("_wqkv", [a1.to_q.weight, a1.to_k.weight, a1.to_v.weight]), ("_wkv2", [a2.to_k.weight, a2.to_v.weight])):
-                f = fused(parts)
-                if f is not None:
-                    setattr(blk, name, f)
-                    for p in parts:
-                        del p._fp8           # the fused record is the one that is read; the parts' views of the bf16 buffer go
-                        p.data = torch.empty(0, device=dev, dtype=dt)
-                    n += f.nbytes()
-                    self._fp8_records.update({m: f for m, _, _ in f.parts})
-            for p in (a1.to_out[0].weight, a2.to_q.weight, a2.to_out[0].weight, blk.ffn.net[0].proj.weight, blk.ffn.net[2].weight):
-                if getattr(p, "_fp8", None) is not None:
-                    p.data = torch.empty(0, device=dev, dtype=dt)
-                    n += p._fp8.nbytes()
-                    self._fp8_records[p._fp8.parts[0][0]] = p._fp8
-        self._fp8_bytes = n
-        torch.cuda.empty_cache()
-        return self
+            plan += [(blk, "_wqkv", [a1.to_q.weight, a1.to_k.weight, a1.to_v.weight]), (blk, "_wkv2", [a2.to_k.weight, a2.to_v.weight])]
+            plan += [(blk, None, [p]) for p in (a1.to_out[0].weight, a2.to_q.weight, a2.to_out[0].weight, blk.ffn.net[0].proj.weight,
+                                                 blk.ffn.net[2].weight)]
+        return plan
 
     # ---- LoRA on resident-fp8 weights: applied at RUN TIME, as the reference does (R/src/lora/manager.py:454-606 around
     # FPScaledLinear) — there is no bf16 weight to merge into.  Modules whose weights are ordinary bf16 parameters still merge.
@@ -402,10 +358,7 @@ class WanTransformer3DModel(F32ResidualMixin, HipTransformer):
         super()._lora_remerge(modules - resident)
 
     def state_dict(self, *a, **k):
-        if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError("wan.mi355: this model was loaded with keep_fp8=True / keep_quantized=True — its block weights live as "
-                                 "quantised records (inference only); it has no bf16 state dict to save.  Load without keep_fp8 / "
-                                 "keep_quantized to serialise.")
+        self._fp8_guard("state_dict")
         return super().state_dict(*a, **k)
 
     @torch.no_grad()

@@ -50,6 +50,15 @@ def test_argument_validation_reports_a_reason():
     bad(gemm(epi=lib.EPI_BIAS_SILU), "epilogue 5")
     bad(gemm(lda=1 << 23), "2^22")
     bad(L.apexmi_gemm_fp8(P, 128, P, P, 128, 0, P, 3, None, P, 16, 8, 16, 128, 0, None, None, 0, None), "3 values")
+    # the remaining refusals of a single launch, at the smallest legal shape (M 1, N 16, K 128) with one argument wrong
+    one = dict(qa=P, lda=128, sa=P, qw=P, ldw=128, fmt=0, sw=P, nsw=1, bias=None, C=P, ldc=16, M=1, N=16, K=128, epi=lib.EPI_BIAS,
+               gate=None, R=None, ldr=0)
+    for change, needle in ((dict(qw=None), "gemm_fp8: null operand"), (dict(lda=136), "rows 16-byte aligned (lda 136, ldw 128, ldc 16)"),
+                           (dict(ldc=8), "rows 16-byte aligned (lda 128, ldw 128, ldc 8)"), (dict(C=P + 4), "operands must be 16-byte aligned"),
+                           (dict(bias=P + 2), "(scales and bias 8-byte)"),
+                           (dict(epi=lib.EPI_BIAS_GATE_RES, gate=P, R=P, ldr=8), "gemm_fp8: gate/R alignment"),
+                           (dict(epi=lib.EPI_BIAS_GATE_RES, gate=P + 4, R=P, ldr=16), "gemm_fp8: gate/R alignment")):
+        bad(L.apexmi_gemm_fp8(*{**one, **change}.values(), None), needle)
     bad(L.apexmi_quant_rows_fp8(P, 100, 4, 100, P, 112, P, None), "K=100")
     bad(L.apexmi_quant_rows_fp8(P, 128, 0, 128, P, 128, P, None), "M=0")
     bad(L.apexmi_quant_rows_fp8(None, 128, 4, 128, P, 128, P, None), "null")
@@ -109,6 +118,51 @@ def test_set_fp8_compute_needs_resident_records():
                               device="cpu", dtype=torch.bfloat16)
     with pytest.raises(lib.ApexMIError, match="keep_fp8=True"):
         m.set_fp8_compute(True)
+
+
+def _tiny(which):
+    import apex_studio_amd  # noqa: F401
+    if which == "wan":
+        from apex_studio_amd.wan import WanTransformer3DModel
+        m = WanTransformer3DModel(patch_size=(1, 2, 2), num_attention_heads=1, attention_head_dim=128, in_channels=16, out_channels=16,
+                                  text_dim=64, freq_dim=256, ffn_dim=256, num_layers=1, cross_attn_norm=True, eps=1e-6,
+                                  device="cpu", dtype=torch.bfloat16)
+        a1, a2 = m.blocks[0].attn1, m.blocks[0].attn2
+        return m, [a1.to_q, a1.to_k, a1.to_v], [a2.to_k, a2.to_v]
+    from apex_studio_amd.flux import FluxTransformer2DModel
+    m = FluxTransformer2DModel(patch_size=1, in_channels=64, num_layers=1, num_single_layers=1, attention_head_dim=128,
+                               num_attention_heads=1, joint_attention_dim=128, pooled_projection_dim=64, guidance_embeds=False,
+                               axes_dims_rope=(16, 56, 56), device="cpu", dtype=torch.bfloat16)
+    a = m.transformer_blocks[0].attn
+    return m, [a.to_q, a.to_k, a.to_v], [a.add_q_proj, a.add_k_proj, a.add_v_proj]
+
+
+@pytest.mark.parametrize("case", ["first-group", "later-group"])
+@pytest.mark.parametrize("which", ["wan", "flux"])
+def test_adopt_refuses_a_mixed_group_and_releases_nothing(which, case):
+    """A fused projection with a record on ONE of its parts is refused, and the refusal leaves every parameter's bf16 storage in
+    place: every group is checked before any is released.  first-group: a record on to_q only.  later-group: q | k | v all
+    resident (a group that would be released if groups were adopted one by one) and a record on the first part of the next
+    group only.  `_packed` is set by hand: `pack()` itself needs a ROCm device and is not what is tested."""
+    from apex_studio_amd import lib, ops
+    m, first, second = _tiny(which)
+    m._packed = True
+
+    def record(lin):
+        lin.weight._fp8 = ops.Fp8Weight(torch.zeros(lin.weight.shape).to(torch.float8_e4m3fn), torch.ones(1))
+    if case == "first-group":
+        record(first[0])
+    else:
+        for lin in first:
+            record(lin)
+        record(second[0])
+    sizes = {k: p.numel() for k, p in m.named_parameters()}
+    assert all(n > 0 for n in sizes.values())
+    with pytest.raises(lib.ApexMIError, match="mixes"):
+        m._fp8_adopt()
+    assert {k: p.numel() for k, p in m.named_parameters()} == sizes, "a refused adopt released bf16 storage"
+    assert not getattr(m, "_fp8_bytes", 0) and not getattr(m, "_fp8_records", None)
+    assert all(hasattr(lin.weight, "_fp8") for lin in (first if case == "later-group" else first[:1]))
 
 
 def test_engines_take_the_switch():

@@ -1,5 +1,5 @@
 """Host-side checks of the grouped fp8 GEMM: the pure routing predicate `ops.fp8_grouped_route`, the tile ->
-problem lookup of `gemm_fp8_kernel_grouped` restated in Python (`ops.fp8_grouped_tiles`) against a brute-force cover, and the two
+problem lookup of the grouped `gemm_fp8_kernel` (`fp8_problem`) restated in Python (`ops.fp8_grouped_tiles`) against a brute-force cover, and the two
 exported names in the header and in `lib.SIGNATURES`.  No GPU."""
 import os
 
@@ -76,6 +76,47 @@ def test_exported_names_in_the_header_and_the_signatures():
     for name, nargs in (("apexmi_gemm_fp8_grouped", 20), ("apexmi_gemm_fp8_grouped_qkv", 32)):
         assert f"int {name}(" in header
         assert name in lib.SIGNATURES and len(lib.SIGNATURES[name][1]) == nargs
+
+
+def test_both_entry_forms_word_a_refusal_the_same_and_the_grouped_one_names_the_problem():
+    """One validation routine serves the single and the grouped entry points: the same wrong argument is refused with the same
+    sentence, the grouped form adding which problem.  Dummy (never dereferenced) pointers; every call is refused before a launch."""
+    import ctypes as C
+    from apex_studio_amd import lib
+    L = lib.load()
+    P = 0x100000
+
+    def single(M=1, N=16, K=128, fmt=0, epi=lib.EPI_BIAS, nsw=1, lda=128):
+        assert L.apexmi_gemm_fp8(P, lda, P, P, K, fmt, P, nsw, None, P, N, M, N, K, epi, None, None, 0, None) != 0
+        return L.apexmi_last_error().decode()
+
+    def grouped(M=1, N=16, K=128, fmt=0, epi=lib.EPI_BIAS, nsw=1, lda=128):
+        """two problems, the second one wrong"""
+        VP, I64, INT = C.c_void_p * 2, C.c_int64 * 2, C.c_int * 2
+        rc = L.apexmi_gemm_fp8_grouped(2, VP(P, P), I64(K, lda), VP(P, P), VP(P, P), I64(K, K), INT(0, fmt), VP(P, P), I64(1, nsw),
+                                       VP(None, None), VP(P, P), I64(16, N), INT(1, M), INT(16, N), K, INT(lib.EPI_BIAS, epi),
+                                       VP(None, None), VP(None, None), I64(0, 0), None)
+        assert rc != 0
+        return L.apexmi_last_error().decode()
+
+    assert single(M=0) == "gemm_fp8: M=0 must be at least 1"
+    assert grouped(M=0) == "gemm_fp8_grouped: M=0 of problem 1 must be at least 1"
+    assert single(N=24) == "gemm_fp8: N=24 must be a multiple of 16"
+    assert grouped(N=24) == "gemm_fp8_grouped: N=24 of problem 1 must be a multiple of 16"
+    assert single(fmt=1) == ("gemm_fp8: weight format 1 is not e4m3fn (0): e5m2 weights take the bf16 path "
+                             "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16)")
+    assert grouped(fmt=1) == ("gemm_fp8_grouped: weight format 1 of problem 1 is not e4m3fn (0): e5m2 weights take the bf16 path "
+                              "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16_grouped)")
+    assert single(epi=lib.EPI_BIAS_F32) == (f"gemm_fp8: f32 output (epilogue {lib.EPI_BIAS_F32}, the f32 residual stream) is not "
+                                            "supported: the output is bf16")
+    assert grouped(epi=lib.EPI_BIAS_F32) == (f"gemm_fp8_grouped: f32 output (epilogue {lib.EPI_BIAS_F32} of problem 1, the f32 residual "
+                                             "stream) is not supported: the output is bf16")
+    assert single(nsw=3) == "gemm_fp8: the weight scale has 3 values for N=16 rows"
+    assert grouped(nsw=3) == "gemm_fp8_grouped: the weight scale of problem 1 has 3 values for N=16 rows"
+    assert single(lda=136) == "gemm_fp8: leading dimensions must keep rows 16-byte aligned (lda 136, ldw 128, ldc 16)"
+    assert grouped(lda=136) == "gemm_fp8_grouped: leading dimensions must keep rows 16-byte aligned (problem 1: lda 136, ldw 128, ldc 16)"
+    assert single(K=100) == "gemm_fp8: K=100 must be a multiple of 128"
+    assert grouped(K=100) == "gemm_fp8_grouped: K=100 must be a multiple of 128"
 
 
 def test_preflight_refuses_a_fused_tensor_with_one_scale():

@@ -201,7 +201,9 @@ def test_header_bindings_and_kernel_name():
         src = f.read()
     kernels = re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", src)
     assert sorted(kernels) == ["gemm_fp8_kernel", "quant_rows_fp8_kernel"], kernels
-    assert "gemm_fp8_kernel" in build.NO_SPILL["gemm_fp8.hip"] and re.search(r"gemm_fp8_kernel<\w+, true>", src)
+    # (the form is chosen by the argument type: LORA = the kernel was given an Fp8LoraGemm, which gemm_fp8_run launches it with)
+    assert "gemm_fp8_kernel" in build.NO_SPILL["gemm_fp8.hip"] and re.search(r"gemm_fp8_kernel<\w+, Args>", src)
+    assert "LORA = std::is_same_v<Args, Fp8LoraGemm>" in src and re.search(r"Fp8LoraGemm L\{.*\n(.*\n)*?\s*fp8_launch\(epilogue, L, stream\)", src)
 
 
 def test_argument_validation_reports_a_reason():
