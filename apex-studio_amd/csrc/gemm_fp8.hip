@@ -3,7 +3,7 @@
 // per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.  The run-time LoRA form
 // (apexmi_gemm_fp8_lora) applies them to the accumulators instead and adds the adapter term t . B'^T by a bf16 MFMA tail.
 #include "common.h"
-#include "fp8_quant.h"   // FP8_MAX, quant1, quant4
+#include "fp8_quant.h"   // FP8_MAX, quant1, quant4, the MX block quantiser
 #include <type_traits>
 
 namespace {
@@ -62,6 +62,8 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
     }
 }
 
+#include "quant_blocks_mxfp8.inc"   // apexmi_quant_blocks_mxfp8's streaming kernel (uses absmax16 above)
+
 // ---- apexmi_gemm_fp8 ----------------------------------------------------------------------------------------------------------
 // 128 x 128 output tile, K-tile of 128 codes, 256 threads = 2 x 2 waves of 64 x 64 (2 x 2 MFMA tiles of 32 x 32, 64 accumulator
 // registers).  Both operands are K-contiguous bytes and staged by global_load_lds (16 bytes per lane) into ONE __shared__ array:
@@ -95,12 +97,22 @@ struct Fp8Problem {
     int64_t lda, ldw, ldc, ldr;
     int M, N, K, sw_rows;  // sw_rows: 1 = one scale per weight row, 0 = a single value
     int tiles_m, tiles_n;
+    // MX forms (apexmi_gemm_fp8_mx, apexmi_gemm_fp8_grouped_mx; read by the MX instantiations only)
+    const uint8_t* abs;   // e8m0 block scales of the activation [M, K / 32], or null = per-row scales `sa`
+    uint8_t* Q;           // MX output codes [M, N], or null = the bf16 output C
+    uint8_t* QS;          // MX output block scales [M, N / 32]
+    int64_t ldabs, ldq, ldqs;
 };
 
 // a single launch (apexmi_gemm_fp8)
 struct Fp8Gemm : Fp8Problem {
     unsigned long long* clk;
 };
+
+// The MX forms of the single and the grouped launch: the same operands, chosen by type so that the kernel's unit-scale K-loop and
+// epilogue compile from the code they always did.  Per problem: `abs` = the activation carries one e8m0 scale per 32 k (passed to
+// the MFMA as the B-side block scale; the epilogue then uses sa = 1), `Q` = the output leaves as MX codes + block scales.
+struct Fp8MxGemm : Fp8Gemm {};
 
 // the run-time LoRA form (apexmi_gemm_fp8_lora): the adapter operands of the bf16 tail
 struct Fp8LoraGemm : Fp8Gemm {
@@ -136,11 +148,25 @@ struct Fp8Group {
     Fp8QkvShared qs;
     unsigned long long* clk;
 };
+struct Fp8MxGroup : Fp8Group {};
 
 APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
     const int sw = (row >> 1) & 7;
     const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece ^ sw) << 4));
     const u32x4 hi = *(const u32x4*)(tile + row * FBK + (((piece + 1) ^ sw) << 4));
+    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+}
+
+// The fragment of a BLOCK-SCALED k-step (the MX instantiations, problems with `abs`).  The instruction's two scale blocks are not
+// the two lane halves: block 0 = registers 0..3 of BOTH halves, scaled by byte 0 (op-sel 0) of lane l & 31's scale register, block
+// 1 = registers 4..7 of both halves, scaled by lane 32 + (l & 31)'s (measured with one-hot operands and a lane / byte code in the
+// scale register; tests/test_gpu_gemm_fp8_mx.py pins it).  A dot product does not care where a k sits as long as both operands
+// agree, so for these problems BOTH operands put the step's memory block b (32 codes) into scale block b: lane half h holds codes
+// 16 h + 0..15 of block 0 in registers 0..3 and codes 16 h + 0..15 of block 1 in registers 4..7 = 16-byte pieces h and 2 + h.
+APEXMI_DEVICE i32x8 lds_frag_blocks(const uint8_t* tile, int row, int piece0, int piece1) {
+    const int sw = (row >> 1) & 7;
+    const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece0 ^ sw) << 4));
+    const u32x4 hi = *(const u32x4*)(tile + row * FBK + ((piece1 ^ sw) << 4));
     return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
@@ -189,7 +215,10 @@ APEXMI_DEVICE void fp8_load_bias(const Fp8Problem& G, int n, float (&bs)[4]) {
 // ---- epilogue: out = epi(acc * sa[m] * sw[n] + bias[n]).  Loads go to clamped addresses; out-of-range lanes store nothing ----
 // not SCALED (the LoRA form): the scales are in acc already, out = epi(acc + bias[n]).  The problem travels BY VALUE: by reference the
 // address arithmetic is redone at every store.
-template <int EPI, bool SCALED>
+// MXIN (the MX instantiations): a problem with block-scaled activations (G.abs, block-uniform) uses sa = 1.  MXOUT (bias / gelu, N % 128 == 0): the value pack_bf16 would
+// store is quantised per 32-column block instead — a lane holds 16 of the block's columns of its row in acc[i][j], lane l ^ 32 the
+// other 16 — and leaves as 4 codes per register group plus one scale byte per block and row (the fh == 0 lane); C is not written.
+template <int EPI, bool SCALED, bool MXIN = false, bool MXOUT = false>
 APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, int m0, int n0, int wr, int wc, int fr, int fh) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -210,8 +239,13 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
             const int m = m0 + 64 * wr + 32 * j + fr;
             const int mc = min(m, G.M - 1);
             float sa = 1.f;
-            if constexpr (SCALED) sa = G.sa[mc];
+            if constexpr (SCALED) {
+                if constexpr (MXIN) sa = G.abs != nullptr ? 1.f : G.sa[mc];
+                else sa = G.sa[mc];
+            }
             u32x2 rr[4];
+            [[maybe_unused]] float mxv[16];
+            [[maybe_unused]] float mxm = 0.f;
             if (EPI == APEXMI_EPI_BIAS_GATE_RES) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -235,8 +269,28 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
                     o[2] = bf16_lo(rr[g][1]) + gt[g][2] * o[2];
                     o[3] = bf16_hi(rr[g][1]) + gt[g][3] * o[3];
                 }
-                if (m < G.M && n < G.N)
-                    *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+                if constexpr (MXOUT) {
+                    const uint32_t p0 = pack_bf16(o[0], o[1]), p1 = pack_bf16(o[2], o[3]);
+                    mxv[4 * g] = bf16_lo(p0), mxv[4 * g + 1] = bf16_hi(p0), mxv[4 * g + 2] = bf16_lo(p1), mxv[4 * g + 3] = bf16_hi(p1);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) mxm = fmaxf(mxm, fabsf(mxv[4 * g + e]));
+                } else {
+                    if (m < G.M && n < G.N)
+                        *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+                }
+            }
+            if constexpr (MXOUT) {
+                mxm = fmaxf(mxm, __shfl_xor(mxm, 32, 64));       // every lane takes part: rows >= M compute on clamped loads
+                const int sb = mx_scale_byte(mxm);
+                const float inv = mx_inv_scale(sb);
+                const int nb = n0 + 64 * wc + 32 * i;           // N % 128 == 0: every column of the tile exists
+                if (m < G.M) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        *(uint32_t*)(G.Q + (int64_t)m * G.ldq + nb + 8 * g + 4 * fh) =
+                            mx_quant4f(mxv[4 * g], mxv[4 * g + 1], mxv[4 * g + 2], mxv[4 * g + 3], inv);
+                    if (fh == 0) G.QS[(int64_t)m * G.ldqs + (nb >> 5)] = (uint8_t)sb;
+                }
             }
         }
     }
@@ -364,7 +418,8 @@ APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupPro
 // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
 template <int EPI, class Args>
 __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
-    constexpr bool LORA = std::is_same_v<Args, Fp8LoraGemm>, GROUPED = std::is_same_v<Args, Fp8Group>;
+    constexpr bool LORA = std::is_same_v<Args, Fp8LoraGemm>, GROUPED = std::is_base_of_v<Fp8Group, Args>;
+    constexpr bool MX = std::is_same_v<Args, Fp8MxGemm> || std::is_same_v<Args, Fp8MxGroup>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * FOPB];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
@@ -424,29 +479,93 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
 
     const int nk = P.K / FBK;
     const int fr = lane & 31, fh = lane >> 5;
+    // MX: the lane's activation block scales.  Its row 64 wr + 32 j + fr of the tile has one e8m0 byte per 32 k = one dword per
+    // K-tile; lane half fh supplies the scale of block 2 kk + fh of k-step kk (lds_frag_blocks).  A wave's 64 rows are 64 cache
+    // lines, so the dwords are fetched FOUR K-tiles at a time (one 16-byte load per row where the rows are 16-byte aligned, else
+    // and for the last part-filled group dword by dword), one group ahead, by plain global loads (a global-address-space pointer: a
+    // flat load would count in lgkmcnt too and hold the K-tile's first LDS wait for HBM).  A problem without block scales
+    // (block-uniform) passes 2^0, keeps sa[m] in the epilogue and reads its fragments as the unit-scale kernel does, so it leaves
+    // that kernel's bits.
+    typedef const __attribute__((address_space(1))) uint32_t* bs_ptr_t;
+    typedef const __attribute__((address_space(1))) u32x4* bs_ptr4_t;
+    [[maybe_unused]] bs_ptr_t bs_src[2];
+    [[maybe_unused]] u32x4 bs_cur[2], bs_nxt[2];
+    [[maybe_unused]] bool bs_wide = false;
+    [[maybe_unused]] auto bs_load = [&](int t0, u32x4 (&g)[2]) {      // dwords t0 .. t0 + 3 (those below nk) of the lane's two rows
+        const bool full = bs_wide && t0 + 4 <= nk;                     // block-uniform
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            if (full) {
+                g[j] = *(bs_ptr4_t)(bs_src[j] + t0);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (t0 + q < nk) g[j][q] = bs_src[j][t0 + q];
+            }
+        }
+    };
+    if constexpr (MX) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) bs_cur[j] = bs_nxt[j] = u32x4{(uint32_t)UNIT_E8M0, (uint32_t)UNIT_E8M0, (uint32_t)UNIT_E8M0, (uint32_t)UNIT_E8M0};
+        if (P.abs != nullptr) {
+            bs_wide = ((uintptr_t)P.abs % 16) == 0 && (P.ldabs % 16) == 0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                bs_src[j] = (bs_ptr_t)(uintptr_t)(P.abs + (int64_t)min(m0 + 64 * wr + 32 * j + fr, P.M - 1) * P.ldabs);
+            bs_load(0, bs_cur);
+        }
+    }
     stage(0, 0);
     __syncthreads();
     for (int kt = 0; kt < nk; ++kt) {
         const int buf = kt & 1;
         if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
         else stage_rank(0, buf ^ 1);
+        [[maybe_unused]] uint32_t bs[2];
+        if constexpr (MX) {
+            if (P.abs != nullptr && (kt & 3) == 0 && kt + 4 < nk) bs_load(kt + 4, bs_nxt);
+            const int q = kt & 3;                                       // uniform
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bs[j] = q == 0 ? bs_cur[j][0] : q == 1 ? bs_cur[j][1] : q == 2 ? bs_cur[j][2] : bs_cur[j][3];
+        }
         const uint8_t* ta = lds + buf * 2 * FOPB;
         const uint8_t* tw = ta + FOPB;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const int piece = 4 * kk + 2 * fh;
             i32x8 fa[2], fw[2];
+            if constexpr (MX) {
+                const bool blk = P.abs != nullptr;
+                const int p0 = blk ? 4 * kk + fh : piece, p1 = blk ? 4 * kk + 2 + fh : piece + 1;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                fa[i] = lds_frag(ta, 64 * wr + 32 * i + fr, piece);
-                fw[i] = lds_frag(tw, 64 * wc + 32 * i + fr, piece);
+                for (int i = 0; i < 2; ++i) {
+                    fa[i] = lds_frag_blocks(ta, 64 * wr + 32 * i + fr, p0, p1);
+                    fw[i] = lds_frag_blocks(tw, 64 * wc + 32 * i + fr, p0, p1);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    fa[i] = lds_frag(ta, 64 * wr + 32 * i + fr, piece);
+                    fw[i] = lds_frag(tw, 64 * wc + 32 * i + fr, piece);
+                }
             }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, UNIT_E8M0, 0,
-                                                                               UNIT_E8M0);
+                for (int j = 0; j < 2; ++j) {
+                    if constexpr (MX)       // the B-side scale: byte 0 (op-sel 0) of the lane's register = block 2 kk + fh
+                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, UNIT_E8M0, 0,
+                                                                                   (int)(bs[j] >> (16 * kk + 8 * fh)));
+                    else
+                        acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[i], fa[j], acc[i][j], 0, 0, 0, UNIT_E8M0, 0,
+                                                                                   UNIT_E8M0);
+                }
+        }
+        if constexpr (MX) {
+            if ((kt & 3) == 3) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bs_cur[j] = bs_nxt[j];
+            }
         }
         __syncthreads();
     }
@@ -496,7 +615,17 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
         }
     }
 
-    if constexpr (GROUPED) {
+    if constexpr (MX) {
+        // block-uniform choices: bf16 or MX out; the epilogue of a grouped problem by its table entry
+        int epi = EPI;
+        if constexpr (GROUPED) epi = P.epi;
+        const bool mxo = P.Q != nullptr;
+        if (epi == APEXMI_EPI_BIAS_GATE_RES) fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else if (epi == APEXMI_EPI_BIAS_GELU && mxo) fp8_epilogue<APEXMI_EPI_BIAS_GELU, true, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else if (epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else if (mxo) fp8_epilogue<APEXMI_EPI_BIAS, true, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        else fp8_epilogue<APEXMI_EPI_BIAS, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
+    } else if constexpr (GROUPED) {
         if (P.qkv) fp8_qkv_epilogue(acc, P, G.qs, m0, n0, tid, lds);
         else if (P.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, true>(acc, P, m0, n0, wr, wc, fr, fh);
         else if (P.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, true>(acc, P, m0, n0, wr, wc, fr, fh);
@@ -524,11 +653,40 @@ extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, v
     return apexmi_check_launch("quant_rows_fp8");
 }
 
+extern "C" int apexmi_quant_blocks_mxfp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* block_scales,
+                                         int64_t ldbs, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(a && codes && block_scales, "quant_blocks_mxfp8: null operand");
+    APEXMI_REQUIRE(M >= 1, "quant_blocks_mxfp8: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "quant_blocks_mxfp8: K=%d must be a multiple of 128", K);
+    APEXMI_REQUIRE(lda >= K && ldq >= K && lda % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 16) == 0,
+                   "quant_blocks_mxfp8: rows must be 16-byte aligned and at least K wide (lda %lld, ldq %lld)", (long long)lda,
+                   (long long)ldq);
+    APEXMI_REQUIRE(ldbs >= K / 32, "quant_blocks_mxfp8: rows of the block scales must be at least K / 32 = %d wide (ldbs %lld)", K / 32,
+                   (long long)ldbs);
+    ApexmiProfScope prof(5, stream, 0.0, (3.0 + 1.0 / 32) * (double)M * K);
+    const int64_t threads = (int64_t)M * (K / 16);
+    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "quant_blocks_mxfp8: M=%d x K=%d is too large for one launch", M, K);
+    hipLaunchKernelGGL(quant_blocks_mxfp8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M,
+                       K, (uint8_t*)codes, ldq, (uint8_t*)block_scales, ldbs);
+    return apexmi_check_launch("quant_blocks_mxfp8");
+}
+
+// the MX operands of one problem (apexmi_gemm_fp8_mx, apexmi_gemm_fp8_grouped_mx); null members = not used
+struct Fp8MxOperands {
+    const void* abs;      // activation block scales [M, K / 32] (then sa is null)
+    int64_t ldabs;
+    void* Q;              // MX output codes [M, N] (then C may be null)
+    int64_t ldq;
+    void* QS;             // MX output block scales [M, N / 32]
+    int64_t ldqs;
+};
+
 // ONE problem of any entry point: every check, then its operand record.  `who` = the entry point's name; `i` = the problem's index
 // in a grouped launch, which the messages name, or -1 for a single launch; tile0 = the tiles of the problems before it.
 static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const float* sa, const void* qw,
                              int64_t ldw, int w_format, const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M,
-                             int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Fp8Problem* P) {
+                             int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Fp8Problem* P, const Fp8MxOperands* mx = nullptr) {
     char of[32] = "", paren[32] = "", colon[32] = "", semi[32] = "";
     if (i >= 0) {
         snprintf(of, sizeof(of), " of problem %d", i);
@@ -536,7 +694,9 @@ static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* 
         snprintf(colon, sizeof(colon), "problem %d: ", i);
         snprintf(semi, sizeof(semi), "; problem %d", i);
     }
-    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand%s", who, paren);
+    const bool blk = mx != nullptr && mx->abs != nullptr, mxo = mx != nullptr && (mx->Q != nullptr || mx->QS != nullptr);
+    APEXMI_REQUIRE(qa && (sa || blk) && qw && sw && (C || mxo), "%s: null operand%s", who, paren);
+    APEXMI_REQUIRE(!(sa && blk), "%s: row scales and block scales were both given%s: an activation carries one kind", who, paren);
     APEXMI_REQUIRE(w_format == 0, "%s: weight format %d%s is not e4m3fn (0): e5m2 weights take the bf16 path "
                                   "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16%s)", who, w_format, of, i >= 0 ? "_grouped" : "");
     APEXMI_REQUIRE(M >= 1, "%s: M=%d%s must be at least 1", who, M, of);
@@ -561,8 +721,23 @@ static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* 
     }
     const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
     APEXMI_REQUIRE(tile0 + (int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
+    if (blk)
+        APEXMI_REQUIRE(mx->ldabs >= K / 32 && mx->ldabs % 4 == 0 && ((uintptr_t)mx->abs % 4) == 0,
+                       "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldabs %lld)", who, of, K / 32,
+                       (long long)mx->ldabs);
+    if (mxo) {
+        APEXMI_REQUIRE(mx->Q && mx->QS, "%s: the MX output%s needs codes and block scales", who, of);
+        APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU,
+                       "%s: the MX output%s exists for the bias (0) and tanh GELU (1) epilogues, not epilogue %d", who, of, epilogue);
+        APEXMI_REQUIRE(N % 128 == 0, "%s: N=%d%s must be a multiple of 128 for the MX output", who, N, of);
+        APEXMI_REQUIRE(mx->ldq >= N && mx->ldq % 4 == 0 && ((uintptr_t)mx->Q % 4) == 0 && mx->ldqs >= N / 32,
+                       "%s: the MX output%s needs 4-byte aligned code rows at least N wide and scale rows at least N / 32 wide "
+                       "(ldq %lld, ldqs %lld)", who, of, (long long)mx->ldq, (long long)mx->ldqs);
+    }
     *P = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
                     lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, tm, tn};
+    if (blk) P->abs = (const uint8_t*)mx->abs, P->ldabs = mx->ldabs;
+    if (mxo) P->Q = (uint8_t*)mx->Q, P->QS = (uint8_t*)mx->QS, P->ldq = mx->ldq, P->ldqs = mx->ldqs;
     return 0;
 }
 
@@ -623,6 +798,24 @@ extern "C" int apexmi_gemm_fp8(const void* qa, int64_t lda, const float* sa, con
                         (hipStream_t)stream_);
 }
 
+// replaces apexmi_gemm_fp8 + apexmi_quant_rows_fp8 around an activation that stays in fp8 between two GEMMs
+extern "C" int apexmi_gemm_fp8_mx(const void* qa, int64_t lda, const float* sa, const void* abs, int64_t ldabs, const void* qw,
+                                  int64_t ldw, int w_format, const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc,
+                                  void* mx_codes, int64_t ldmc, void* mx_scales, int64_t ldms, int M, int N, int K, int epilogue,
+                                  const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const Fp8MxOperands mx{abs, ldabs, mx_codes, ldmc, mx_scales, ldms};
+    Fp8MxGemm G{};
+    if (fp8_check_problem("gemm_fp8_mx", -1, 0, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, C ? ldc : N, M, N, K, epilogue, gate, R,
+                          ldr, &G, &mx))
+        return 1;
+    G.clk = apexmi_clk_ptr();
+    const double out_bytes = mx_codes ? (1.0 + 1.0 / 32) * (double)M * N : 2.0 * (double)M * N;
+    ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (abs ? 1.0 + 1.0 / 32 : 1.0) * (double)M * K + (double)N * K + out_bytes);
+    fp8_launch(epilogue, G, stream);
+    return apexmi_check_launch("gemm_fp8_mx");
+}
+
 extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format,
                                     const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K,
                                     int epilogue, const float* gate, const void* R, int64_t ldr, const void* t, int64_t ldt,
@@ -652,12 +845,12 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
                                 const int64_t* ldw, const int* w_format, const void* const* sw, const int64_t* sw_count,
                                 const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
                                 const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
-                                const Fp8QkvArgs* qkv, hipStream_t stream) {
+                                const Fp8QkvArgs* qkv, hipStream_t stream, const Fp8MxOperands* mx = nullptr) {
     APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "gemm_fp8_grouped: count=%d not in [1,%d]", count, FP8_MAX_GROUPS);
     APEXMI_REQUIRE(qa && lda && sa && qw && ldw && w_format && sw && sw_count && C && ldc && M && N && epilogue,
                    "gemm_fp8_grouped: null argument array");
     APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8_grouped: K=%d must be a multiple of 128", K);
-    Fp8Group G{};
+    Fp8MxGroup G{};          // launched as the Fp8Group it is unless `mx`
     G.count = count;
     G.clk = apexmi_clk_ptr();
     if (qkv != nullptr) {
@@ -678,8 +871,8 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
         Fp8GroupProblem& P = G.p[i];
         // a fused problem writes no C: its q_out stands in, N wide
         if (fp8_check_problem("gemm_fp8_grouped", i, tiles, qa[i], lda[i], sa[i], qw[i], ldw[i], w_format[i], sw[i], sw_count[i],
-                              bias ? bias[i] : nullptr, fused ? qkv->q_out : C[i], fused ? N[i] : ldc[i], M[i], N[i], K, epilogue[i],
-                              gate ? gate[i] : nullptr, R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P))
+                              bias ? bias[i] : nullptr, fused ? qkv->q_out : C[i], fused || !C[i] ? N[i] : ldc[i], M[i], N[i], K,
+                              epilogue[i], gate ? gate[i] : nullptr, R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P, mx ? mx + i : nullptr))
             return 1;
         P.epi = epilogue[i];
         P.tile0 = (int)tiles;
@@ -703,7 +896,11 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
     }
     G.total = (int)tiles;
     ApexmiProfScope prof(0, stream, flops, bytes);
-    hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8Group>), dim3((unsigned)tiles), dim3(256), 0, stream, G);
+    if (mx != nullptr) {
+        hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8MxGroup>), dim3((unsigned)tiles), dim3(256), 0, stream, G);
+        return apexmi_check_launch("gemm_fp8_grouped_mx");
+    }
+    hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8Group>), dim3((unsigned)tiles), dim3(256), 0, stream, (const Fp8Group&)G);
     return apexmi_check_launch(qkv ? "gemm_fp8_grouped_qkv" : "gemm_fp8_grouped");
 }
 
@@ -726,4 +923,21 @@ extern "C" int apexmi_gemm_fp8_grouped_qkv(int count, const void* const* qa, con
     const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
     return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr,
                                 &qkv, (hipStream_t)stream_);
+}
+
+// replaces apexmi_gemm_fp8_grouped + apexmi_quant_rows_fp8 per problem: per problem i, abs[i] (then sa[i] is null) = block-scaled
+// activations, mx_codes[i] / mx_scales[i] (then C[i] may be null) = MX output; null entries = that problem as apexmi_gemm_fp8_grouped
+extern "C" int apexmi_gemm_fp8_grouped_mx(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                          const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                          const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                          const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                          const void* const* R, const int64_t* ldr, const void* const* abs, const int64_t* ldabs,
+                                          void* const* mx_codes, const int64_t* ldmc, void* const* mx_scales, const int64_t* ldms,
+                                          apexmi_stream_t stream_) {
+    APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "gemm_fp8_grouped_mx: count=%d not in [1,%d]", count, FP8_MAX_GROUPS);
+    APEXMI_REQUIRE(abs && ldabs && mx_codes && ldmc && mx_scales && ldms, "gemm_fp8_grouped_mx: null argument array");
+    Fp8MxOperands mx[FP8_MAX_GROUPS];
+    for (int i = 0; i < count; ++i) mx[i] = Fp8MxOperands{abs[i], ldabs[i], mx_codes[i], ldmc[i], mx_scales[i], ldms[i]};
+    return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, nullptr,
+                                (hipStream_t)stream_, mx);
 }

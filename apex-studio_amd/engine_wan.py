@@ -25,7 +25,8 @@ class WanT2VEngine(EngineLoraMixin):
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
-                 attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False):
+                 attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
+                 fp8_mx_ffn: bool = False):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -54,14 +55,21 @@ class WanT2VEngine(EngineLoraMixin):
         # back to the bf16 path; needs fp8_compute
         # fp8_fused_quant: the norms in front of the q|k|v, cross-attention query and FFN-up Linears write the e4m3 codes
         # themselves (`set_fp8_compute(fused_quant=True)`: fewer launches and bytes, the same numbers); needs fp8_compute
+        # fp8_mx_ffn: the FFN hidden state stays in MX fp8 between the two FFN Linears (`set_fp8_compute(mx_ffn=True)`: one
+        # quantise launch and the bf16 round trip fewer per block; block scales, so the numbers change); needs fp8_compute
         self.fp8_compute, self.fp8_lora, self.fp8_fused_quant = bool(fp8_compute), bool(fp8_lora), bool(fp8_fused_quant)
+        self.fp8_mx_ffn = bool(fp8_mx_ffn)
+        if self.fp8_mx_ffn and not self.fp8_compute:
+            raise ValueError("fp8_mx_ffn=True needs fp8_compute=True: the MX hidden state belongs to the FP8 GEMMs")
         if self.fp8_lora and not self.fp8_compute:
             raise ValueError("fp8_lora=True needs fp8_compute=True: it keeps adapter-carrying Linears on the FP8 compute path")
         if self.fp8_fused_quant and not self.fp8_compute:
             raise ValueError("fp8_fused_quant=True needs fp8_compute=True: the fused norm quantises for the FP8 GEMM")
         if self.fp8_compute:
             for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
-                if self.fp8_fused_quant:
+                if self.fp8_mx_ffn:
+                    tr.set_fp8_compute(True, lora=self.fp8_lora, fused_quant=self.fp8_fused_quant, mx_ffn=True)
+                elif self.fp8_fused_quant:
                     tr.set_fp8_compute(True, lora=self.fp8_lora, fused_quant=True)
                 elif self.fp8_lora:
                     tr.set_fp8_compute(True, lora=True)
@@ -258,11 +266,13 @@ class WanI2VEngine(WanT2VEngine):
                  scheduler: Optional[UniPCMultistepScheduler] = None, boundary_ratio: Optional[float] = 0.875,
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
-                 attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False):
+                 attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
+                 fp8_mx_ffn: bool = False):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
                          vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
                          attention_window=attention_window, fp8_compute=fp8_compute,
-                         attention_band=attention_band, fp8_lora=fp8_lora, fp8_fused_quant=fp8_fused_quant)
+                         attention_band=attention_band, fp8_lora=fp8_lora, fp8_fused_quant=fp8_fused_quant,
+                         fp8_mx_ffn=fp8_mx_ffn)
         self.image_encoder = image_encoder
 
     @property

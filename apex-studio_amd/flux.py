@@ -191,7 +191,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         self._bstreams: List[Any] = []
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (see _forward_one; APEX_FLUX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FLUX_FUSE_QKV", "1") != "0"
-        self._fp8_compute = self._fp8_fused_quant = False      # set_fp8_compute
+        self._fp8_compute = self._fp8_fused_quant = self._fp8_mx_ffn = False      # set_fp8_compute
 
     # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, cache_context, ...) ----
     def _anchor(self):
@@ -301,7 +301,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                                  "to use adapters")
         return super()._lora_param(module, what)
 
-    def set_fp8_compute(self, on: bool, fused_quant: bool = False):
+    def set_fp8_compute(self, on: bool, fused_quant: bool = False, mx_ffn: bool = False):
         """Opt-in approximation: the block launches whose weights are RESIDENT e4m3 records (a `keep_fp8=True`
         load) quantise their activations per row to e4m3 and multiply in fp8 — `ops.gemm_fp8_grouped` for the grouped launches
         (the QKV pair with the fused q/k/v epilogue when `fuse_qkv` is set and no IP adapter is active), `ops.gemm`'s fp8 route
@@ -311,11 +311,23 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
 
         `fused_quant=True` (needs `on=True`): the norms in front of the QKV launches and of the double block's FF-up launch write
         the e4m3 codes and row scales themselves (`ops.ln_modulate_quant_fp8`); the bf16 rows, which nothing else reads, are not
-        stored.  A launch and traffic change only: the forward is bit-identical to `fused_quant=False`."""
+        stored.  A launch and traffic change only: the forward is bit-identical to `fused_quant=False`.
+
+        `mx_ffn=True` (needs `on=True`, composes with `fused_quant`): the double block's FF hidden state stays in fp8 between the
+        FF-up pair and the FF-down pair.  Where `ops.fp8_mx_route` holds for both streams, the FF-up pair quantises its own GELU
+        output per 32-column block in the epilogue (`ops.gemm_fp8_grouped(out_mx_list=)`: e4m3 codes + one e8m0 scale byte per
+        block, both streams as row slices of one buffer) and the FF-down pair multiplies those codes with the hardware block
+        scales (`block_scales_list=`), so the `quant_rows_fp8` launch of the hidden state and its bf16 round trip disappear.
+        Codes and scale bytes live in the storage of the bf16 hidden buffer, which is not written in this mode.  This CHANGES
+        the numbers (block scales instead of one scale per row of the hidden state).  The single block (its MLP-up output shares
+        proj_out's K with the attention output) and the f32 residual stream keep today's launches; `mx_ffn=False` (the default)
+        leaves every launch as it is."""
+        if mx_ffn and not on:
+            raise ValueError("flux.mi355: set_fp8_compute(mx_ffn=True) needs on=True: the MX hidden state belongs to the fp8 GEMMs")
         if fused_quant and not on:
             raise ValueError("flux.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
         self._fp8_set_compute(on)
-        self._fp8_compute, self._fp8_fused_quant = bool(on), bool(fused_quant)
+        self._fp8_compute, self._fp8_fused_quant, self._fp8_mx_ffn = bool(on), bool(fused_quant), bool(mx_ffn)
         return self
 
     def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, **kw):
@@ -551,6 +563,14 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             [XN, XN], [self.single_transformer_blocks[0]._wqkv, rec(self.single_transformer_blocks[0].proj_mlp.weight)],
             [QKV, CAT[:, dim:]], ["bias", "gelu"])
         fuse8_d, fuse8_s = fp8_d and self.fuse_qkv and ip is None, fp8_s and self.fuse_qkv
+        # mx_ffn: the FF hidden state of the double blocks as MX codes + block scales in the bytes of FFH (no bf16 row is stored)
+        mlp = FFH.shape[1]
+        mx_d = fp8 and self._fp8_mx_ffn and len(self.transformer_blocks) > 0 and all(
+            ops.fp8_mx_route(xn, net[0].proj.weight, net[2].weight, "gelu", "gate_res", out=x) for xn, net, x in
+            ((XNi, self.transformer_blocks[0].ff.net, Xi), (XNt, self.transformer_blocks[0].ff_context.net, Xt)))
+        if mx_d:
+            raw = FFH.view(torch.uint8)
+            hq, hs = raw[:, :mlp], raw[:, mlp:mlp + mlp // 32]
         if overlap and self._side is None:
             self._side = torch.cuda.Stream(device=self.device)
         if mixed:        # the fused launches and the flash kernel behind them exchange bf16 q / k / v^T (ws.Qb ..), as in production
@@ -603,10 +623,19 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             ff, ffc = blk.ff.net, blk.ff_context.net
             qn = self._norm_rows(X, XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight] if fp8 else [], "gelu", mi(4), mi(3),
                                  split=s_txt, scale2=mt(4), shift2=mt(3))
-            self._grouped(XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight], [ff[0].proj.bias, ffc[0].proj.bias],
-                          [FFH[s_txt:], FFH[:s_txt]], "gelu", quantised=qn)
-            self._grouped(FFH, img_txt, [ff[2].weight, ffc[2].weight], [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res",
-                          gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt])
+            if mx_d:
+                qa, sa = self._rows_fp8(XN, qn)
+                ops.gemm_fp8_grouped([qa[r] for r in img_txt], [sa[r] for r in img_txt], [rec(ff[0].proj.weight), rec(ffc[0].proj.weight)],
+                                     [ff[0].proj.bias, ffc[0].proj.bias], [None, None], "gelu",
+                                     out_mx_list=[(hq[r], hs[r]) for r in img_txt])
+                ops.gemm_fp8_grouped([hq[r] for r in img_txt], [None, None], [rec(ff[2].weight), rec(ffc[2].weight)],
+                                     [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res", gate_list=[mi(5), mt(5)],
+                                     residual_list=[Xi, Xt], block_scales_list=[hs[r] for r in img_txt])
+            else:
+                self._grouped(XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight], [ff[0].proj.bias, ffc[0].proj.bias],
+                              [FFH[s_txt:], FFH[:s_txt]], "gelu", quantised=qn)
+                self._grouped(FFH, img_txt, [ff[2].weight, ffc[2].weight], [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res",
+                              gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt])
             if ip is not None:
                 # `hidden_states + ip_attn_output` AFTER the feed-forward (model.py:308-309); ip_attn_output = sum over adapters of
                 # scale x attention(image queries, to_k_ip(tokens), to_v_ip(tokens)) (attention.py:232-262): a few keys per adapter

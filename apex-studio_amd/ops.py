@@ -489,6 +489,57 @@ def quant_rows_fp8(a: torch.Tensor, out: Optional[torch.Tensor] = None,
     return out, scale_out
 
 
+def quant_blocks_mxfp8(a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MX block quantisation of bf16 `a` [M, K] (row stride free, K % 128 == 0) -> (codes uint8 [M, K] = float8_e4m3fn bit
+    patterns, block_scales uint8 [M, K / 32] = e8m0 exponents; row strides free).  Per block of 32 consecutive columns:
+        amax = max |a| with unbiased f32 exponent E and mantissa bits man;  e = clamp(E - 8 + (man > 0x600000), -126, 127)
+        (0 for a zero block);  scale byte = e + 127;  code = e4m3fn_rne(clamp(a * 2^-e, -448, 448))
+    2^e is the smallest power of two with amax / 2^e <= 448, so the clamp clips nothing; a zero block has byte 127 and no byte is
+    255; no code is NaN.  Inputs must be finite.  One launch, no row reduction: what `gemm_fp8(block_scales=)` reads, and what
+    `gemm_fp8(out_mx=)` writes from its epilogue."""
+    if a.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"quant_blocks_mxfp8.a: expected torch.bfloat16, got {a.dtype}")
+    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 128 != 0 or a.shape[0] < 1:
+        raise _l.ApexMIError(f"quant_blocks_mxfp8.a: expected [M >= 1, K % 128 == 0] with contiguous rows, got {tuple(a.shape)}")
+    M, K = a.shape
+    if out is None:
+        out = torch.empty((M, K), dtype=torch.uint8, device=a.device)
+    if scale_out is None:
+        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
+    _check_mx_pair("quant_blocks_mxfp8.out", (out, scale_out), M, K)
+    _req(a, torch.bfloat16, "quant_blocks_mxfp8.a")
+    _l.check(_l.load().apexmi_quant_blocks_mxfp8(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
+                                                 scale_out.stride(0), _stream()), "quant_blocks_mxfp8")
+    return out, scale_out
+
+
+def _check_mx_pair(who: str, pair, M: int, N: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """An MX (codes [M, N], block_scales [M, N / 32]) pair, both uint8 with contiguous rows: dtype and shape first, then device."""
+    try:
+        q, s = pair
+    except (TypeError, ValueError):
+        raise _l.ApexMIError(f"{who}: expected a (codes, block_scales) pair") from None
+    for t, nm in ((q, "codes"), (s, "block_scales")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise _l.ApexMIError(f"{who} {nm}: expected torch.uint8, got {getattr(t, 'dtype', type(t).__name__)}")
+    if q.dim() != 2 or tuple(q.shape) != (M, N) or q.stride(1) != 1:
+        raise _l.ApexMIError(f"{who} codes: expected [{M}, {N}] with contiguous rows, got {tuple(q.shape)}")
+    _check_block_scales(who + " block_scales", s, M, N)
+    _req(q, torch.uint8, who + " codes")
+    return q, s
+
+
+def _check_block_scales(who: str, s: torch.Tensor, M: int, K: int) -> torch.Tensor:
+    """The e8m0 block scales [M, K / 32] (uint8, contiguous rows) of an activation [M, K]: dtype and shape first, then device."""
+    if not isinstance(s, torch.Tensor) or s.dtype != torch.uint8:
+        raise _l.ApexMIError(f"{who}: expected torch.uint8, got {getattr(s, 'dtype', type(s).__name__)}")
+    if s.dim() != 2 or tuple(s.shape) != (M, K // 32) or s.stride(1) != 1:
+        raise _l.ApexMIError(f"{who}: expected [{M}, {K // 32}] (one byte per 32 columns) with contiguous rows, got {tuple(s.shape)}")
+    _req(s, torch.uint8, who)
+    return s
+
+
 def _check_quantised(a: torch.Tensor, quantised) -> Tuple[torch.Tensor, torch.Tensor]:
     """`gemm(quantised=)`: (codes, scales) must be what quant_rows_fp8(a) would return in shape and type."""
     qa, sa = quantised
@@ -543,20 +594,37 @@ def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
     return codes, scale_out
 
 
-def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=None, fused=False, alloc=False):
+def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=None, fused=False, alloc=False,
+                 block_scales=None, out_mx=None):
     """The checks of ONE fp8 GEMM problem, for `gemm_fp8` and for every problem of a grouped launch (`K`: the K they share).
     Returns (out, flag): `out` (made here if None and `alloc`) and the epilogue flag of a float `out`, which the entry point
-    rejects with its own message, as it does e5m2 records.  `fused`: the problem writes no `out`."""
+    rejects with its own message, as it does e5m2 records.  `fused`: the problem writes no `out`.  `block_scales` (then `scales`
+    is None) / `out_mx` (then `out` is not written): the MX forms, see `gemm_fp8`."""
+    if block_scales is not None:
+        if scales is not None:
+            raise _l.ApexMIError(f"{who}: `scales` (one per row) and `block_scales` (one per 32 columns) were both given: "
+                                 "an activation carries one kind")
+        if codes.dim() == 2:
+            _check_block_scales(who + ".block_scales", block_scales, codes.shape[0], codes.shape[1])
+    if out_mx is not None:
+        if epilogue not in ("bias", "gelu"):
+            raise _l.ApexMIError(f"{who}: out_mx exists for the bias and gelu epilogues, not '{epilogue}'")
+        if isinstance(w, Fp8Weight) and w.shape[0] % 128 != 0:
+            raise _l.ApexMIError(f"{who}: out_mx needs N % 128 == 0, got N={w.shape[0]}")
+        if isinstance(w, Fp8Weight) and codes.dim() == 2:
+            _check_mx_pair(who + ".out_mx", out_mx, codes.shape[0], w.shape[0])
+        fused = True
     _req(codes, torch.uint8, who + ".codes")
-    _req(scales, torch.float32, who + ".scales")
+    if block_scales is None:
+        _req(scales, torch.float32, who + ".scales")
     if not isinstance(w, Fp8Weight):
         raise _l.ApexMIError(f"{who}: expected an Fp8Weight, got {type(w).__name__}")
     if epilogue not in _FP8_EPI:
         raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
-    assert codes.dim() == 2 and codes.stride(1) == 1 and scales.is_contiguous()
+    assert codes.dim() == 2 and codes.stride(1) == 1 and (scales is None or scales.is_contiguous())
     M, N = codes.shape[0], w.shape[0]
     K = codes.shape[1] if K is None else K
-    assert codes.shape[1] == K and w.shape[1] == K and scales.numel() == M
+    assert codes.shape[1] == K and w.shape[1] == K and (scales is None or scales.numel() == M)
     flag = 0
     if not fused:
         if out is None and alloc:
@@ -580,7 +648,7 @@ def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=N
 def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Optional[torch.Tensor] = None,
              out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
              residual: Optional[torch.Tensor] = None, lora_t: Optional[torch.Tensor] = None,
-             lora_B: Optional[torch.Tensor] = None) -> torch.Tensor:
+             lora_B: Optional[torch.Tensor] = None, block_scales: Optional[torch.Tensor] = None, out_mx=None):
     """out[M, N] (bf16) = epi((codes . w.q^T) * scales[m] * w.scale[n] + bias): e4m3 x e4m3 with f32 accumulation, both scales
     applied in the f32 epilogue.  `codes` / `scales` as `quant_rows_fp8` returns them; `w` an e4m3 `Fp8Weight` (e5m2 raises);
     epilogue bias / gelu / gate_res.
@@ -588,10 +656,33 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
     `lora_t` [M, Rp] and `lora_B` [N, Rp] (bf16, both or neither, Rp a multiple of 64, row strides free): the run-time LoRA form,
         out = epi(((codes . w.q^T) * scales[m]) * w.scale[n] + sum_r lora_t[m, r] lora_B[n, r] + bias)
     — the scaled base product stays in the f32 accumulators, a bf16 MFMA tail adds the adapter term (rank ascending) into them,
-    and the result is rounded once."""
+    and the result is rounded once.
+
+    MX forms (not with `lora_t`):
+    `block_scales` (uint8 [M, K / 32], `scales` must be None): `codes` carry one e8m0 scale per 32 columns, as
+        `quant_blocks_mxfp8` or an `out_mx` launch writes them; the block-scaled MFMA applies them and the epilogue uses
+        scales[m] = 1.  All bytes 127 give the bits of `scales = 1`.  Every epilogue takes it.
+    `out_mx=(codes_out uint8 [M, N], block_scales_out uint8 [M, N / 32])` (bias / gelu, N % 128 == 0): the launch quantises its
+        own output in the epilogue and writes those instead of `out` (which is ignored); bit-identical to the bf16 launch
+        followed by `quant_blocks_mxfp8`.  Returns the pair."""
     if (lora_t is None) != (lora_B is None):
         raise _l.ApexMIError("gemm_fp8: lora_t and lora_B go together (both or neither)")
-    out, flag = _fp8_problem("gemm_fp8", codes, scales, w, bias, out, epilogue, gate, residual, alloc=True)
+    if lora_t is not None and (block_scales is not None or out_mx is not None):
+        raise _l.ApexMIError("gemm_fp8: the run-time LoRA form (lora_t / lora_B) takes per-row scales and writes bf16: "
+                             "block_scales / out_mx are not supported with it")
+    out, flag = _fp8_problem("gemm_fp8", codes, scales, w, bias, out, epilogue, gate, residual, alloc=True,
+                             block_scales=block_scales, out_mx=out_mx)
+    if block_scales is not None or out_mx is not None:
+        (M, K), N = codes.shape, w.shape[0]
+        mq, ms = out_mx if out_mx is not None else (None, None)
+        rc = _l.load().apexmi_gemm_fp8_mx(
+            codes.data_ptr(), codes.stride(0), _ptr(scales), _ptr(block_scales), 0 if block_scales is None else block_scales.stride(0),
+            w.q.data_ptr(), w.q.stride(0), 0 if w.q.dtype == torch.float8_e4m3fn else 1, w.scale.data_ptr(), w.scale.numel(),
+            _ptr(bias), None if out_mx is not None else out.data_ptr(), 0 if out_mx is not None else out.stride(0), _ptr(mq),
+            0 if mq is None else mq.stride(0), _ptr(ms), 0 if ms is None else ms.stride(0), M, N, K, _EPI[epilogue] | flag,
+            _ptr(gate), _ptr(residual), residual.stride(0) if epilogue == "gate_res" else 0, _stream())
+        _l.check(rc, "gemm_fp8_mx")
+        return out_mx if out_mx is not None else out
     (M, K), N = codes.shape, w.shape[0]
     fmt = 0 if w.q.dtype == torch.float8_e4m3fn else 1
     epi = _EPI[epilogue] | flag
@@ -633,6 +724,24 @@ def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
     return all(fp8_compute_route(a, w, o, e) for a, w, o, e in zip(a_list, w_list, outs, epis))
 
 
+def fp8_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_down: str = "gate_res",
+                 out: Optional[torch.Tensor] = None) -> bool:
+    """Whether the pair `h = gemm(a, w_up, epilogue=epilogue_up)` -> `gemm(h, w_down, out=out, epilogue=epilogue_down)` may keep
+    `h` in MX fp8 between the two launches: `gemm_fp8(out_mx=)` -> `gemm_fp8(block_scales=)`.  Pure, like `fp8_compute_route`
+    (dtypes, shapes and strides; CPU tensors are fine).  `a_or_shape`: the bf16 input [M, K] of the up projection, or its shape.
+    True only when BOTH Linears take `fp8_compute_route` (so neither record carries run-time LoRA factors), N_up % 128 == 0, the
+    up epilogue is bias or gelu, and `out` (the down projection's output and, for gate_res, its residual) is bf16 or None."""
+    a = a_or_shape if isinstance(a_or_shape, torch.Tensor) else torch.empty(tuple(a_or_shape), dtype=torch.bfloat16, device="meta")
+    f_up = _fp8_of(w_up)
+    if epilogue_up not in ("bias", "gelu") or not fp8_compute_route(a, f_up, None, epilogue_up):
+        return False
+    n_up = f_up.shape[0]
+    if n_up % 128 != 0:
+        return False
+    h = torch.empty((a.shape[0], n_up), dtype=torch.bfloat16, device="meta")
+    return fp8_compute_route(h, w_down, out, epilogue_down)
+
+
 def fp8_grouped_tiles(shapes):
     """The tile each workgroup of a `gemm_fp8_grouped` launch over problems `shapes` = [(M, N), ...] computes, restated from the
     kernel (csrc/gemm_fp8.hip, fp8_problem and gemm_fp8_kernel): a list over block ids of (problem, tile row, tile column).  The XCD remap
@@ -659,7 +768,8 @@ def fp8_grouped_tiles(shapes):
     return out
 
 
-def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None):
+def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None,
+                      block_scales_list=None, out_mx_list=None):
     """ctypes arrays of a grouped fp8 launch after the per-problem checks (`_fp8_problem`); `fused[i]`: problem i writes no `out`.
     Counts above 4, e5m2 records and float outputs are refused by the entry point with its own message."""
     import ctypes as C
@@ -668,12 +778,15 @@ def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list,
     none = [None] * n
     bias_list, gate_list, residual_list = bias_list or none, gate_list or none, residual_list or none
     fused = fused or [0] * n
+    bsl, oml = block_scales_list or none, out_mx_list or none
+    fused = [1 if (f or om is not None) else 0 for f, om in zip(fused, oml)]
     K = codes_list[0].shape[1]
-    flags = [_fp8_problem(who, qa, sa, w, b, o, e, g, r, K=K, fused=bool(f))[1]
-             for qa, sa, w, b, o, e, g, r, f in zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list, residual_list, fused)]
+    flags = [_fp8_problem(who, qa, sa, w, b, o, e, g, r, K=K, fused=bool(f), block_scales=bs, out_mx=om)[1]
+             for qa, sa, w, b, o, e, g, r, f, bs, om in zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list,
+                                                            residual_list, fused, bsl, oml)]
     VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
     return (n, VP(*[t.data_ptr() for t in codes_list]), I64(*[t.stride(0) for t in codes_list]),
-            VP(*[t.data_ptr() for t in scales_list]), VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),
+            VP(*[_ptr(t) for t in scales_list]), VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),
             INT(*[0 if w.q.dtype == torch.float8_e4m3fn else 1 for w in w_list]), VP(*[w.scale.data_ptr() for w in w_list]),
             I64(*[w.scale.numel() for w in w_list]), VP(*[_ptr(b) for b in bias_list]),
             VP(*[None if f else o.data_ptr() for o, f in zip(out_list, fused)]),
@@ -685,23 +798,41 @@ def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list,
 
 
 def gemm_fp8_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilogue="bias", gate_list=None,
-                     residual_list=None) -> None:
+                     residual_list=None, block_scales_list=None, out_mx_list=None) -> None:
     """Up to 4 `gemm_fp8` problems sharing K in ONE launch (img / txt streams; QKV + MLP-up of a single block): out_list[i] =
     epi_i((codes_i . w_i.q^T) * scales_i[m] * w_i.scale[n] + bias_i), bit for bit what `gemm_fp8` leaves for that problem alone.
     `epilogue` is one name or one per problem (bias / gelu / gate_res, freely mixed); a gate_res problem may have
-    residual_list[i] is out_list[i] (in place).  Several problems may share one (codes, scales) pair or row slices of it."""
+    residual_list[i] is out_list[i] (in place).  Several problems may share one (codes, scales) pair or row slices of it.
+
+    `block_scales_list[i]` (then scales_list[i] is None) / `out_mx_list[i]` (then out_list[i] is ignored and may be None): the MX
+    forms of `gemm_fp8`, per problem; None entries are ordinary problems, so a launch may mix MX and bf16 outputs."""
     args = _fp8_grouped_args("gemm_fp8_grouped", codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list,
-                             residual_list)
+                             residual_list, block_scales_list=block_scales_list, out_mx_list=out_mx_list)
+    n = len(codes_list)
+    bsl, oml = list(block_scales_list or [None] * n), list(out_mx_list or [None] * n)
+    if any(t is not None for t in bsl + oml):
+        import ctypes as C
+        VP, I64 = C.c_void_p * n, C.c_int64 * n
+        mq, ms = [None if o is None else o[0] for o in oml], [None if o is None else o[1] for o in oml]
+        st = lambda ts: I64(*[0 if t is None else t.stride(0) for t in ts])  # noqa: E731
+        rc = _l.load().apexmi_gemm_fp8_grouped_mx(*args, VP(*[_ptr(t) for t in bsl]), st(bsl), VP(*[_ptr(t) for t in mq]), st(mq),
+                                                  VP(*[_ptr(t) for t in ms]), st(ms), _stream())
+        _l.check(rc, "gemm_fp8_grouped_mx")
+        return
     _l.check(_l.load().apexmi_gemm_fp8_grouped(*args, _stream()), "gemm_fp8_grouped")
 
 
 def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
-                         eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor) -> None:
+                         eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor,
+                         block_scales_list=None, out_mx_list=None) -> None:
     """`gemm_fp8_grouped` with `qkv_prepare` fused into the epilogue of the problems flagged in `is_qkv` (fused QKV projections,
     N = 3 H 128), mirroring `gemm_grouped_qkv`: q / k leave normalised per head, rotated and laid out [H, S_out, 128], v leaves
     transposed [H, 128, Skp]; bit-identical to gemm_fp8_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
     written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count."""
     import ctypes as C
+    if block_scales_list is not None or out_mx_list is not None:
+        raise _l.ApexMIError("gemm_fp8_grouped_qkv: the fused q/k/v epilogue takes per-row scales and writes bf16: "
+                             "block_scales_list / out_mx_list are not supported with it")
     n = len(codes_list)
     args = _fp8_grouped_args("gemm_fp8_grouped_qkv", codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
                              fused=[1 if f else 0 for f in is_qkv])
@@ -733,7 +864,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, epilogue: str = "bias",
          gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
          lora_buf: Optional[torch.Tensor] = None,
-         quantised: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> torch.Tensor:
+         quantised: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_mx=None) -> torch.Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  2-D operands, last dim contiguous; a / out / residual bf16, or float32
     in the f32-storage verification mode (w and bias stay bf16).  A bf16 `a` with a float32 `out` (and `residual`) is the
     f32 RESIDUAL STREAM: the same launch with the float epilogue, no split of `a`.  `lora_buf`: see _gemm_fp8_lora (ignored
@@ -750,7 +881,10 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     `ln_modulate_quant_fp8` produces it in the norm's own launch — so the route skips its quantise launch.  With
     `fp8_compute_route` only the shape and dtype of `a` are read (the norm may not have stored its rows at all); with
     `fp8_lora_route` the skinny GEMM still reads the bf16 `a`.  The caller decides BEFOREHAND with `fp8_norm_quant_route`: a call
-    whose GEMM takes neither route raises instead of quietly multiplying an `a` that may never have been written."""
+    whose GEMM takes neither route raises instead of quietly multiplying an `a` that may never have been written.
+
+    `out_mx=(codes, block_scales)`: the fp8 route writes its output as MX codes and block scales (`gemm_fp8(out_mx=)`) instead of
+    `out`, and returns the pair.  The caller decides beforehand with `fp8_mx_route`; any other route raises."""
     _req_act(a, "gemm.a")
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
@@ -759,7 +893,12 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         else:
             qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
             quant_rows_fp8(a, out=qa, scale_out=sa)
+        if out_mx is not None:
+            return gemm_fp8(qa, sa, f8, bias, epilogue=epilogue, out_mx=out_mx)
         return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
+    if out_mx is not None:
+        raise _l.ApexMIError("gemm: `out_mx` was passed but this call does not take the fp8 route (fp8_compute_route is False): "
+                             "decide with fp8_mx_route first")
     if quantised is not None and not (f8 is not None and f8.lora_A is not None and fp8_lora_route(a, f8, out, epilogue, lora_buf)):
         raise _l.ApexMIError("gemm: `quantised` activations were passed but this call does not take the fp8 route "
                              "(fp8_compute_route / fp8_lora_route are both False): decide with fp8_norm_quant_route first")

@@ -225,7 +225,7 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         self._band_plans = {}
         return self
 
-    def set_fp8_compute(self, on: bool, lora: bool = False, fused_quant: bool = False):
+    def set_fp8_compute(self, on: bool, lora: bool = False, fused_quant: bool = False, mx_ffn: bool = False):
         """Opt-in approximation: the block Linears whose weights are RESIDENT e4m3 records (a `keep_fp8=True` load:
         the fused q|k|v, the attention outputs, the cross-attention q and k|v, the two FFN Linears) quantise their activations per
         row to e4m3 and multiply in fp8 (`ops.gemm_fp8`) instead of dequantising the weight and multiplying in bf16.  Everything
@@ -246,7 +246,17 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         A launch and traffic change only: the forward is bit-identical to `set_fp8_compute(True, lora=...)` without it, and the
         f32 residual stream takes it too.  The other four fp8 Linears, e5m2 / GGUF records, the f32-storage mode and the query
         projection without an affine `norm2` run the launches they run today.  `fused_quant=False` (the default) leaves every
-        launch as it is today."""
+        launch as it is today.
+
+        `mx_ffn=True` (needs `on=True`, composes with `fused_quant`): the FFN hidden state stays in fp8 between the two FFN Linears.
+        Where `ops.fp8_mx_route` holds, FFN-up quantises its own GELU output per 32-column block in the epilogue
+        (`ops.gemm_fp8(out_mx=)`: e4m3 codes + one e8m0 scale byte per block) and FFN-down multiplies those codes with the hardware
+        block scales (`ops.gemm_fp8(block_scales=)`), so the `quant_rows_fp8` launch of the hidden state and its bf16 round trip
+        disappear.  Codes and scale bytes live in the storage of the bf16 hidden buffer, which is not written in this mode.  This
+        CHANGES the numbers (block scales instead of one scale per row of the hidden state).  Blocks with run-time LoRA on either
+        FFN Linear and the f32 residual stream keep today's launches; `mx_ffn=False` (the default) leaves every launch as it is."""
+        if mx_ffn and not on:
+            raise ValueError("wan.mi355: set_fp8_compute(mx_ffn=True) needs on=True: the MX hidden state belongs to the fp8 GEMMs")
         if lora and not on:
             raise ValueError("wan.mi355: set_fp8_compute(lora=True) needs on=True: the adapter tail belongs to the fp8 GEMM")
         if fused_quant and not on:
@@ -255,19 +265,22 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
             r.lora_compute = "fp8" if lora else "bf16"
         self._fp8_compute = bool(on)
         self._fp8_fused_quant = bool(fused_quant)
+        self._fp8_mx_ffn = bool(mx_ffn)
         return self
 
-    def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", **norm):
+    def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", out_mx=None, **norm):
         """ln_modulate(x, **norm, out=xn) -> gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf); with
         `set_fp8_compute(fused_quant=True)`, where `ops.fp8_norm_quant_route` allows it, the norm quantises for the GEMM in its own
-        launch (and stores `xn` only if the GEMM's adapter tail reads it).  Nothing else reads `xn` between the two."""
+        launch (and stores `xn` only if the GEMM's adapter tail reads it).  Nothing else reads `xn` between the two.  `out_mx`: see
+        `ops.gemm` (the caller has asked `ops.fp8_mx_route`)."""
+        mx = {} if out_mx is None else {"out_mx": out_mx}
         if getattr(self, "_fp8_fused_quant", False):
             fuse, need_row = ops.fp8_norm_quant_route(x, xn, w, out, epilogue, lora_buf)
             if fuse:
                 q = ops.ln_modulate_quant_fp8(x, out=xn if need_row else None, **norm)
-                return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf, quantised=q)
+                return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf, quantised=q, **mx)
         ops.ln_modulate(x, out=xn, **norm)
-        return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf)
+        return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf, **mx)
 
     def _grid_ids(self, grid) -> torch.Tensor:
         """(frame, row, column) of every token in sequence order: what RoPE rotates by and what the attention window measures"""
@@ -537,9 +550,20 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
             ops.gemm(ATT, a2.to_out[0].weight, a2.to_out[0].bias, out=X, epilogue="gate_res", gate=self._ones,
                      residual=X, lora_buf=ws.ATTf)
             # 3. feed-forward
-            self._norm_gemm(X, XN, blk.ffn.net[0].proj.weight, blk.ffn.net[0].proj.bias, FFH, ws.XNf, epilogue="gelu",
+            w_up, w_down = blk.ffn.net[0].proj.weight, blk.ffn.net[2].weight
+            if getattr(self, "_fp8_mx_ffn", False) and ops.fp8_mx_route(XN, w_up, w_down, "gelu", "gate_res", out=X):
+                # the hidden state as MX codes + block scales in the bytes of FFHf, which holds no bf16 row in this mode
+                raw = ws.FFHf.view(torch.uint8)
+                ffn = FFH.shape[1]
+                hq, hs = raw[:, :ffn], raw[:, ffn:ffn + ffn // 32]
+                self._norm_gemm(X, XN, w_up, blk.ffn.net[0].proj.bias, None, ws.XNf, epilogue="gelu", out_mx=(hq, hs),
+                                scale=m(4), shift=m(3), eps=eps)
+                ops.gemm_fp8(hq, None, ops._fp8_of(w_down), blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5), residual=X,
+                             block_scales=hs)
+                continue
+            self._norm_gemm(X, XN, w_up, blk.ffn.net[0].proj.bias, FFH, ws.XNf, epilogue="gelu",
                             scale=m(4), shift=m(3), eps=eps)
-            ops.gemm(FFH, blk.ffn.net[2].weight, blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5),
+            ops.gemm(FFH, w_down, blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5),
                      residual=X, lora_buf=ws.FFHf)
 
         # (scale_shift_table + temb).chunk(2): shift first, then scale (model.py:1849-1856)

@@ -824,6 +824,45 @@ int apexmi_gemm_fp8_grouped_qkv(int count, const void* const* qa, const int64_t*
                                 const int* row0, int H, float eps, const float* rope, void* q_out, void* k_out, void* vt_out,
                                 int S_out, int Skp, apexmi_stream_t stream);
 
+/* MX block-scaled activations (opt-in): one e8m0 scale byte per 32 consecutive k of a row, which the block-scaled
+ * MFMA applies itself, instead of one f32 scale per row.  A block's scale needs only the block, so a GEMM epilogue that holds a
+ * tile of the row can quantise its own output.  Per block of 32 columns (aligned to 32), on the bf16 values:
+ *     amax = max |x|, E = its unbiased f32 exponent, man = its 23 mantissa bits;
+ *     e = clamp(E - 8 + (man > 0x600000), -126, 127), 0 for a zero block      (448 = 1.75 x 2^8: the smallest 2^e with amax / 2^e <= 448)
+ *     scale byte = e + 127 (127 for a zero block, never 255);   code = e4m3fn( min(max(x * 2^-e, -448), 448) )   nearest even
+ * with 2^-e built from exponent bits (no division).  Inputs are finite; no code is NaN.
+ *
+ * apexmi_quant_blocks_mxfp8 — replaces apexmi_quant_rows_fp8 for an activation no GEMM produced, and is the reference the fused
+ * epilogue is held to.  a bf16 [M, K] (row stride lda elements); codes uint8 [M, K] (row stride ldq bytes); block_scales uint8
+ * [M, K / 32] (row stride ldbs bytes).  K % 128 == 0, M >= 1, 16-byte rows of a and codes. */
+int apexmi_quant_blocks_mxfp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* block_scales, int64_t ldbs,
+                              apexmi_stream_t stream);
+
+/* apexmi_gemm_fp8_mx — replaces apexmi_gemm_fp8 and the apexmi_quant_rows_fp8 launch around an activation that stays in fp8 between
+ * two GEMMs.  Every operand and rule of apexmi_gemm_fp8, and:
+ *   abs != NULL (then sa must be NULL): the activation carries block scales abs uint8 [M, K / 32] (row stride ldabs bytes, a
+ *     multiple of 4, 4-byte aligned) as apexmi_quant_blocks_mxfp8 writes them; the MFMA scales each 32-wide k block by 2^(byte - 127)
+ *     and the epilogue uses sa = 1.  All 127 = the bits of apexmi_gemm_fp8 with sa = 1.  Every epilogue takes it.
+ *   mx_codes != NULL (with mx_scales; C may be NULL and is not written): the output leaves as MX codes uint8 [M, N] (row stride
+ *     ldmc bytes, a multiple of 4) and block scales uint8 [M, N / 32] (row stride ldms bytes): each value is rounded to bf16 as the
+ *     bf16 store would and quantised by the formula above — BIT-IDENTICAL to the bf16 launch followed by
+ *     apexmi_quant_blocks_mxfp8.  N % 128 == 0; epilogue APEXMI_EPI_BIAS or APEXMI_EPI_BIAS_GELU.  Rows >= M store nothing. */
+int apexmi_gemm_fp8_mx(const void* qa, int64_t lda, const float* sa, const void* abs, int64_t ldabs, const void* qw, int64_t ldw,
+                       int w_format, const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, void* mx_codes,
+                       int64_t ldmc, void* mx_scales, int64_t ldms, int M, int N, int K, int epilogue, const float* gate,
+                       const void* R, int64_t ldr, apexmi_stream_t stream);
+
+/* apexmi_gemm_fp8_grouped_mx — replaces apexmi_gemm_fp8_grouped where problems take block-scaled activations or write MX output:
+ * abs[i] / ldabs[i] and mx_codes[i] / ldmc[i] / mx_scales[i] / ldms[i] per problem as in apexmi_gemm_fp8_mx (NULL entries = that
+ * problem exactly as in apexmi_gemm_fp8_grouped, so one launch may mix MX and bf16 outputs).  Every problem leaves the bits its
+ * single launch leaves. */
+int apexmi_gemm_fp8_grouped_mx(int count, const void* const* qa, const int64_t* lda, const float* const* sa, const void* const* qw,
+                               const int64_t* ldw, const int* w_format, const void* const* sw, const int64_t* sw_count,
+                               const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                               const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                               const void* const* abs, const int64_t* ldabs, void* const* mx_codes, const int64_t* ldmc,
+                               void* const* mx_scales, const int64_t* ldms, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
