@@ -1,7 +1,8 @@
 // Opt-in FP8 GEMM for resident fp8-scaled weights: a per-row e4m3 quantiser for the activations and a GEMM on
 // the block-scaled v_mfma_scale_f32_32x32x64_f8f6f4 (e4m3 x e4m3 at twice the bf16 rate per clock) with UNIT block scales; the
 // per-row activation scales and the per-row / single weight scales are applied in the f32 epilogue.  The run-time LoRA form
-// (apexmi_gemm_fp8_lora) applies them to the accumulators instead and adds the adapter term t . B'^T by a bf16 MFMA tail.
+// (apexmi_gemm_fp8_lora) applies them to the accumulators instead and adds the adapter term t . B'^T by a bf16 MFMA tail; the grouped
+// LoRA form (apexmi_gemm_fp8_grouped_lora, apexmi_gemm_fp8_grouped_qkv_lora) does so per problem of a grouped launch.
 #include "common.h"
 #include "fp8_quant.h"   // FP8_MAX, quant1, quant4, the MX block quantiser
 #include <type_traits>
@@ -150,6 +151,19 @@ struct Fp8Group {
 };
 struct Fp8MxGroup : Fp8Group {};
 
+// The grouped run-time LoRA form (apexmi_gemm_fp8_grouped_lora, apexmi_gemm_fp8_grouped_qkv_lora): one adapter entry per problem,
+// by value like the table.  Rp == 0 = the problem has no adapter and is computed as the Fp8Group kernel computes it; Rp > 0 = the
+// arithmetic of Fp8LoraGemm.  Both are block-uniform branches.
+struct Fp8LoraEntry {
+    const bf16_t* T;      // t = a A^T [M, Rp]
+    const bf16_t* LB;     // B' [N, Rp]
+    int64_t ldt, ldb;
+    int Rp;               // padded rank, a multiple of 64, or 0
+};
+struct Fp8LoraGroup : Fp8Group {
+    Fp8LoraEntry lora[FP8_MAX_GROUPS];
+};
+
 APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
     const int sw = (row >> 1) & 7;
     const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece ^ sw) << 4));
@@ -176,14 +190,16 @@ APEXMI_DEVICE bf16x8 lds_frag16(const uint8_t* tile, int row, int piece) {
     return *(const bf16x8*)(tile + row * FBK + ((piece ^ ((row >> 1) & 7)) << 4));
 }
 
-// this workgroup's tile id `t` inside its problem, and the problem: the launch itself, or the table entry found by the prefix sums
-APEXMI_DEVICE const Fp8Gemm& fp8_problem(const Fp8Gemm& G, int& t) {
+// this workgroup's tile id `t` inside its problem, and the problem (index `pi`): the launch itself, or the table entry found by the
+// prefix sums
+APEXMI_DEVICE const Fp8Gemm& fp8_problem(const Fp8Gemm& G, int& t, int& pi) {
     t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
+    pi = 0;
     return G;
 }
-APEXMI_DEVICE Fp8GroupProblem fp8_problem(const Fp8Group& G, int& t) {
+APEXMI_DEVICE Fp8GroupProblem fp8_problem(const Fp8Group& G, int& t, int& pi) {
     t = xcd_remap(blockIdx.x, G.total);
-    int pi = 0;
+    pi = 0;
 #pragma unroll
     for (int i = 1; i < FP8_MAX_GROUPS; ++i)
         if (i < G.count && t >= G.p[i].tile0) pi = i;
@@ -191,6 +207,12 @@ APEXMI_DEVICE Fp8GroupProblem fp8_problem(const Fp8Group& G, int& t) {
     t -= P.tile0;
     return P;
 }
+
+// the adapter operands of this workgroup's problem: the launch's own (Fp8LoraGemm) or entry `pi` of the table (Fp8LoraGroup)
+APEXMI_DEVICE const Fp8LoraGemm& fp8_lora_entry(const Fp8LoraGemm& G, int) { return G; }
+APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8LoraGroup& G, int pi) { return G.lora[pi]; }
+APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8Problem&, int) { return Fp8LoraEntry{}; }
+APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8Group&, int) { return Fp8LoraEntry{}; }
 
 // the weight scales / the bias of the 4 columns n .. n + 3 (n clamped by the caller; a null bias is 0)
 APEXMI_DEVICE void fp8_unpack4(const u32x2 v, float (&f)[4]) { f[0] = bf16_lo(v[0]), f[1] = bf16_hi(v[0]), f[2] = bf16_lo(v[1]), f[3] = bf16_hi(v[1]); }
@@ -307,8 +329,11 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
 //   v:     read transposed, 8 consecutive positions per lane, 16-byte stores into [H, 128, Skp]; a stream whose row0 | M is not
 //          a multiple of 8 stores element-wise (a wave = 64 consecutive positions of one d-row).
 // Rows >= M store nothing; columns >= S_out of V^T are not written.
+// not SCALED (a problem of the grouped LoRA form that carried an adapter): the scales and the adapter term are in acc already, y =
+// bf16(acc + bias), and the staging LDS is free after the TAIL's last barrier.
 APEXMI_DEVICE int fp8_qkv_rot(int r) { return (r >> 3) + 2 * (r & 7); }
 
+template <bool SCALED>
 APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupProblem& G, const Fp8QkvShared& Q, int m0, int n0, int tid,
                                     uint8_t* lds) {
     bf16_t* tile = (bf16_t*)lds;
@@ -320,19 +345,23 @@ APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupPro
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;          // N % 128 == 0: every column of the tile exists
-            fp8_load_sw(G, n, sw[g]);
+            if constexpr (SCALED) fp8_load_sw(G, n, sw[g]);
             fp8_load_bias(G, n, bs[g]);
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int r = 64 * wr + 32 * j + fr;
-            const float sa = G.sa[min(m0 + r, G.M - 1)];
+            float sa = 1.f;
+            if constexpr (SCALED) sa = G.sa[min(m0 + r, G.M - 1)];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int c = 64 * wc + 32 * i + 8 * g + 4 * fh;
                 float o[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (SCALED) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                    else o[e] = acc[i][j][4 * g + e] + bs[g][e];
+                }
                 *(u32x2*)(tile + r * 128 + ((((c >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (c & 4)) =
                     u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
             }
@@ -413,12 +442,14 @@ APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupPro
 // tail adds sum_r t[m, r] B'[n, r] into the same registers, rank ascending: both MFMA shapes write the same 32 x 32 layout.  A rank
 // tile of 64 bf16 is 128 bytes per row — the geometry of a K-tile of codes — so t takes the activation half and B' the weight half
 // of a buffer, staged and swizzled as they are; the first rank tile is requested during the last K-tile.
-// ONE kernel for the three forms, chosen by the argument type (Fp8Gemm, Fp8LoraGemm, Fp8Group): build.py's no-spill check matches
-// "gemm_fp8_kernel" and so covers every instantiation.
+// The grouped LoRA form (G is an Fp8LoraGroup) does the same for the problems whose table entry has Rp > 0 and leaves the others to
+// the SCALED epilogue, so those keep the bits of the plain grouped launch.
+// ONE kernel for all forms, chosen by the argument type (Fp8Gemm, Fp8LoraGemm, Fp8Group, Fp8LoraGroup and the MX pair): build.py's
+// no-spill check matches "gemm_fp8_kernel" and so covers every instantiation.
 // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
 template <int EPI, class Args>
 __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
-    constexpr bool LORA = std::is_same_v<Args, Fp8LoraGemm>, GROUPED = std::is_base_of_v<Fp8Group, Args>;
+    constexpr bool LORA = std::is_same_v<Args, Fp8LoraGemm> || std::is_same_v<Args, Fp8LoraGroup>, GROUPED = std::is_base_of_v<Fp8Group, Args>;
     constexpr bool MX = std::is_same_v<Args, Fp8MxGemm> || std::is_same_v<Args, Fp8MxGroup>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[4 * FOPB];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -426,8 +457,9 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
 
     // XCD-grouped tile order: each XCD takes a contiguous run of tiles; inside a run (of one problem), bands of 8 tile rows share
     // the weight tiles
-    int t;
-    const auto& P = fp8_problem(G, t);
+    int t, pi;
+    const auto& P = fp8_problem(G, t, pi);
+    [[maybe_unused]] const auto& L = fp8_lora_entry(G, pi);     // LORA: the adapter operands; Rp == 0 (grouped) = none, block-uniform
     const int band = 8 * P.tiles_n, first_m = (t / band) * 8;
     const int gsz = min(P.tiles_m - first_m, 8);
     const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
@@ -452,13 +484,14 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
     };
     auto stage_rank = [&](int rt, int buf) {     // LORA: rank tile rt of t (rows) and B' (columns), same rows, pieces and swizzle
         if constexpr (LORA) {
+            if (GROUPED && L.Rp == 0) return;
             uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int r = 32 * wid + 8 * i + (lane >> 3);
                 const int c = (lane & 7) ^ ((r >> 1) & 7);
-                glds16((const char*)(G.T + (int64_t)min(m0 + r, G.M - 1) * G.ldt) + c * 16 + rt * FBK, da + 8 * i * FBK);
-                glds16((const char*)(G.LB + (int64_t)min(n0 + r, G.N - 1) * G.ldb) + c * 16 + rt * FBK, da + FOPB + 8 * i * FBK);
+                glds16((const char*)(L.T + (int64_t)min(m0 + r, P.M - 1) * L.ldt) + c * 16 + rt * FBK, da + 8 * i * FBK);
+                glds16((const char*)(L.LB + (int64_t)min(n0 + r, P.N - 1) * L.ldb) + c * 16 + rt * FBK, da + FOPB + 8 * i * FBK);
             }
         }
     };
@@ -570,21 +603,21 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
         __syncthreads();
     }
 
-    if constexpr (LORA) {
+    if constexpr (LORA) if (!GROUPED || L.Rp > 0) {     // a grouped problem without an adapter skips the tail: block-uniform
         float sa[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) sa[j] = G.sa[min(m0 + 64 * wr + 32 * j + fr, G.M - 1)];
+        for (int j = 0; j < 2; ++j) sa[j] = P.sa[min(m0 + 64 * wr + 32 * j + fr, P.M - 1)];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             float sw[4][4];
 #pragma unroll
-            for (int g = 0; g < 4; ++g) fp8_load_sw(G, min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, G.N - 4), sw[g]);
+            for (int g = 0; g < 4; ++g) fp8_load_sw(P, min(n0 + 64 * wc + 32 * i + 8 * g + 4 * fh, P.N - 4), sw[g]);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][j][r] = (acc[i][j][r] * sa[j]) * sw[r >> 2][r & 3];
         }
-        const int nr = G.Rp / 64;
+        const int nr = L.Rp / 64;
         for (int rt = 0; rt < nr; ++rt) {
             const int buf = (nk + rt) & 1;
             if (rt + 1 < nr) stage_rank(rt + 1, buf ^ 1);
@@ -626,10 +659,19 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
         else if (mxo) fp8_epilogue<APEXMI_EPI_BIAS, true, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
         else fp8_epilogue<APEXMI_EPI_BIAS, true, true>(acc, P, m0, n0, wr, wc, fr, fh);
     } else if constexpr (GROUPED) {
-        if (P.qkv) fp8_qkv_epilogue(acc, P, G.qs, m0, n0, tid, lds);
-        else if (P.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, true>(acc, P, m0, n0, wr, wc, fr, fh);
-        else if (P.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, true>(acc, P, m0, n0, wr, wc, fr, fh);
-        else fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, true>(acc, P, m0, n0, wr, wc, fr, fh);
+        auto group_epilogue = [&](auto scaled) {
+            constexpr bool S = decltype(scaled)::value;
+            if (P.qkv) fp8_qkv_epilogue<S>(acc, P, G.qs, m0, n0, tid, lds);
+            else if (P.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, S>(acc, P, m0, n0, wr, wc, fr, fh);
+            else if (P.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, S>(acc, P, m0, n0, wr, wc, fr, fh);
+            else fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, S>(acc, P, m0, n0, wr, wc, fr, fh);
+        };
+        if constexpr (LORA) {
+            if (L.Rp > 0) group_epilogue(std::false_type{});      // the scales and the adapter term are in acc
+            else group_epilogue(std::true_type{});
+        } else {
+            group_epilogue(std::true_type{});
+        }
     } else {
         fp8_epilogue<EPI, !LORA>(acc, P, m0, n0, wr, wc, fr, fh);
     }
@@ -761,6 +803,22 @@ struct Fp8LoraArgs {
     int Rp;
 };
 
+// the adapter operands of one problem with Rp > 0 (`of` = " of problem i" in a grouped launch)
+static int fp8_check_lora(const char* who, const char* of, const Fp8LoraArgs& lora) {
+    const int Rp = lora.Rp;
+    APEXMI_REQUIRE(Rp >= 64 && Rp % 64 == 0, "%s: the padded rank Rp=%d%s must be a multiple of 64 (set_lora pads to that)", who, Rp, of);
+    APEXMI_REQUIRE(lora.t && lora.lb, "%s: null adapter operand%s (t %p, B' %p)", who, of, lora.t, lora.lb);
+    APEXMI_REQUIRE(lora.ldt >= Rp && lora.ldb >= Rp, "%s: rows of t and B'%s must be at least Rp=%d wide (ldt %lld, ldb %lld)", who, of,
+                   Rp, (long long)lora.ldt, (long long)lora.ldb);
+    APEXMI_REQUIRE(lora.ldt % 8 == 0 && lora.ldb % 8 == 0 && ((uintptr_t)lora.t % 16) == 0 && ((uintptr_t)lora.lb % 16) == 0,
+                   "%s: t and B'%s must be 16-byte aligned with leading dimensions that are multiples of 8 (ldt %lld, ldb %lld)", who, of,
+                   (long long)lora.ldt, (long long)lora.ldb);
+    APEXMI_REQUIRE(lora.ldt <= (1 << 22) && lora.ldb <= (1 << 22),
+                   "%s: leading dimensions%s above 2^22 elements are not supported (ldt %lld, ldb %lld)", who, of, (long long)lora.ldt,
+                   (long long)lora.ldb);
+    return 0;
+}
+
 static int gemm_fp8_run(const void* qa, int64_t lda, const float* sa, const void* qw, int64_t ldw, int w_format, const void* sw,
                         int64_t sw_count, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                         const float* gate, const void* R, int64_t ldr, const Fp8LoraArgs* lora, hipStream_t stream) {
@@ -770,16 +828,7 @@ static int gemm_fp8_run(const void* qa, int64_t lda, const float* sa, const void
     G.clk = apexmi_clk_ptr();
     if (lora != nullptr) {
         const int Rp = lora->Rp;
-        APEXMI_REQUIRE(Rp >= 64 && Rp % 64 == 0, "gemm_fp8_lora: the padded rank Rp=%d must be a multiple of 64 (set_lora pads to that)", Rp);
-        APEXMI_REQUIRE(lora->t && lora->lb, "gemm_fp8_lora: null adapter operand (t %p, B' %p)", lora->t, lora->lb);
-        APEXMI_REQUIRE(lora->ldt >= Rp && lora->ldb >= Rp, "gemm_fp8_lora: rows of t and B' must be at least Rp=%d wide (ldt %lld, ldb %lld)",
-                       Rp, (long long)lora->ldt, (long long)lora->ldb);
-        APEXMI_REQUIRE(lora->ldt % 8 == 0 && lora->ldb % 8 == 0 && ((uintptr_t)lora->t % 16) == 0 && ((uintptr_t)lora->lb % 16) == 0,
-                       "gemm_fp8_lora: t and B' must be 16-byte aligned with leading dimensions that are multiples of 8 (ldt %lld, ldb %lld)",
-                       (long long)lora->ldt, (long long)lora->ldb);
-        APEXMI_REQUIRE(lora->ldt <= (1 << 22) && lora->ldb <= (1 << 22),
-                       "gemm_fp8_lora: leading dimensions above 2^22 elements are not supported (ldt %lld, ldb %lld)", (long long)lora->ldt,
-                       (long long)lora->ldb);
+        if (fp8_check_lora("gemm_fp8_lora", "", *lora)) return 1;
         Fp8LoraGemm L{G, (const bf16_t*)lora->t, (const bf16_t*)lora->lb, lora->ldt, lora->ldb, Rp};
         ApexmiProfScope prof(0, stream, 2.0 * M * N * ((double)K + Rp),
                              (double)M * K + (double)N * K + 2.0 * ((double)M + N) * Rp + 2.0 * (double)M * N);
@@ -825,8 +874,8 @@ extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa
                         (hipStream_t)stream_);
 }
 
-// both grouped entry points: fp8_check_problem per problem, before the launch; qkv = the fused q/k/v operands of
-// apexmi_gemm_fp8_grouped_qkv, or null for apexmi_gemm_fp8_grouped
+// every grouped entry point: fp8_check_problem per problem, before the launch; qkv = the fused q/k/v operands of
+// apexmi_gemm_fp8_grouped_qkv(_lora), or null; lora = the five adapter arrays of the _lora entry points, or null
 struct Fp8QkvArgs {
     const int* is_qkv;
     const void* const* norm_q;
@@ -840,18 +889,33 @@ struct Fp8QkvArgs {
     void* vt_out;
     int S_out, Skp;
 };
+struct Fp8LoraArrays {
+    const void* const* t;
+    const int64_t* ldt;
+    const void* const* lb;
+    const int64_t* ldb;
+    const int* Rp;
+};
 
 static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t* lda, const float* const* sa, const void* const* qw,
                                 const int64_t* ldw, const int* w_format, const void* const* sw, const int64_t* sw_count,
                                 const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
                                 const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
-                                const Fp8QkvArgs* qkv, hipStream_t stream, const Fp8MxOperands* mx = nullptr) {
+                                const Fp8QkvArgs* qkv, hipStream_t stream, const Fp8MxOperands* mx = nullptr,
+                                const Fp8LoraArrays* lora = nullptr) {
     APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "gemm_fp8_grouped: count=%d not in [1,%d]", count, FP8_MAX_GROUPS);
     APEXMI_REQUIRE(qa && lda && sa && qw && ldw && w_format && sw && sw_count && C && ldc && M && N && epilogue,
                    "gemm_fp8_grouped: null argument array");
     APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "gemm_fp8_grouped: K=%d must be a multiple of 128", K);
-    Fp8MxGroup G{};          // launched as the Fp8Group it is unless `mx`
+    Fp8Group G{};            // the table every form shares; copied into the derived struct that is launched
+    Fp8LoraEntry entries[FP8_MAX_GROUPS] = {};
     G.count = count;
+    const char* lwho = qkv ? "gemm_fp8_grouped_qkv_lora" : "gemm_fp8_grouped_lora";
+    if (lora != nullptr) {
+        APEXMI_REQUIRE(mx == nullptr, "%s: the MX forms are not combined with run-time LoRA", lwho);
+        APEXMI_REQUIRE(lora->t && lora->ldt && lora->lb && lora->ldb && lora->Rp, "%s: null adapter argument array", lwho);
+    }
+    bool any_lora = false;
     G.clk = apexmi_clk_ptr();
     if (qkv != nullptr) {
         APEXMI_REQUIRE(qkv->is_qkv && qkv->row0 && qkv->rope && qkv->q_out && qkv->k_out && qkv->vt_out && qkv->H > 0,
@@ -893,14 +957,35 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
         tiles += (int64_t)P.tiles_m * P.tiles_n;
         flops += 2.0 * M[i] * N[i] * (double)K;
         bytes += (double)M[i] * K + (double)N[i] * K + 2.0 * (double)M[i] * N[i];
+        if (lora != nullptr && lora->Rp[i] != 0) {          // Rp == 0: no adapter on this problem, t / B' may be null
+            char of[32];
+            snprintf(of, sizeof(of), " of problem %d", i);
+            const Fp8LoraArgs la{lora->t[i], lora->ldt[i], lora->lb[i], lora->ldb[i], lora->Rp[i]};
+            if (fp8_check_lora(lwho, of, la)) return 1;
+            entries[i] = Fp8LoraEntry{(const bf16_t*)la.t, (const bf16_t*)la.lb, la.ldt, la.ldb, la.Rp};
+            any_lora = true;
+            flops += 2.0 * M[i] * N[i] * (double)la.Rp;
+            bytes += 2.0 * ((double)M[i] + N[i]) * la.Rp;
+        }
     }
     G.total = (int)tiles;
+    if (lora != nullptr)
+        APEXMI_REQUIRE(any_lora, "%s: no problem carries an adapter (every Rp is 0): use apexmi_gemm_fp8_grouped%s", lwho, qkv ? "_qkv" : "");
     ApexmiProfScope prof(0, stream, flops, bytes);
+    if (lora != nullptr) {
+        Fp8LoraGroup L{};
+        (Fp8Group&)L = G;
+        for (int i = 0; i < count; ++i) L.lora[i] = entries[i];
+        hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8LoraGroup>), dim3((unsigned)tiles), dim3(256), 0, stream, L);
+        return apexmi_check_launch(lwho);
+    }
     if (mx != nullptr) {
-        hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8MxGroup>), dim3((unsigned)tiles), dim3(256), 0, stream, G);
+        Fp8MxGroup X{};
+        (Fp8Group&)X = G;
+        hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8MxGroup>), dim3((unsigned)tiles), dim3(256), 0, stream, X);
         return apexmi_check_launch("gemm_fp8_grouped_mx");
     }
-    hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8Group>), dim3((unsigned)tiles), dim3(256), 0, stream, (const Fp8Group&)G);
+    hipLaunchKernelGGL((gemm_fp8_kernel<0, Fp8Group>), dim3((unsigned)tiles), dim3(256), 0, stream, G);
     return apexmi_check_launch(qkv ? "gemm_fp8_grouped_qkv" : "gemm_fp8_grouped");
 }
 
@@ -940,4 +1025,34 @@ extern "C" int apexmi_gemm_fp8_grouped_mx(int count, const void* const* qa, cons
     for (int i = 0; i < count; ++i) mx[i] = Fp8MxOperands{abs[i], ldabs[i], mx_codes[i], ldmc[i], mx_scales[i], ldms[i]};
     return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, nullptr,
                                 (hipStream_t)stream_, mx);
+}
+
+// apexmi_gemm_fp8_grouped with a run-time LoRA adapter per problem: t[i] [M_i, Rp_i], lb[i] = B' [N_i, Rp_i]; Rp[i] == 0 (t[i] / lb[i]
+// may be null) = no adapter on problem i.  Every problem leaves the bits of its own single launch: apexmi_gemm_fp8_lora with an
+// adapter, apexmi_gemm_fp8 without.
+extern "C" int apexmi_gemm_fp8_grouped_lora(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                            const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                            const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                            const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                            const void* const* R, const int64_t* ldr, const void* const* t, const int64_t* ldt,
+                                            const void* const* lb, const int64_t* ldb, const int* Rp, apexmi_stream_t stream_) {
+    const Fp8LoraArrays lora{t, ldt, lb, ldb, Rp};
+    return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, nullptr,
+                                (hipStream_t)stream_, nullptr, &lora);
+}
+
+// apexmi_gemm_fp8_grouped_qkv with the same five arrays: bit-identical to apexmi_gemm_fp8_grouped_lora + apexmi_qkv_prepare
+extern "C" int apexmi_gemm_fp8_grouped_qkv_lora(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                                const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                                const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                                const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                                const void* const* R, const int64_t* ldr, const int* is_qkv, const void* const* norm_q,
+                                                const void* const* norm_k, const int* row0, int H, float eps, const float* rope,
+                                                void* q_out, void* k_out, void* vt_out, int S_out, int Skp, const void* const* t,
+                                                const int64_t* ldt, const void* const* lb, const int64_t* ldb, const int* Rp,
+                                                apexmi_stream_t stream_) {
+    const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
+    const Fp8LoraArrays lora{t, ldt, lb, ldb, Rp};
+    return gemm_fp8_grouped_run(count, qa, lda, sa, qw, ldw, w_format, sw, sw_count, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &qkv,
+                                (hipStream_t)stream_, nullptr, &lora);
 }

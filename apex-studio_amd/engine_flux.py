@@ -79,7 +79,7 @@ class FluxT2IEngine(EngineLoraMixin):
     def __init__(self, transformer, scheduler: Optional[FlowMatchEulerDiscreteScheduler] = None,
                  decode_fn: Optional[Callable[[torch.Tensor], object]] = None, vae_scale_factor: int = 8,
                  text_encoder=None, text_encoder_2=None, residual_dtype: Optional[torch.dtype] = None,
-                 fp8_compute: bool = False, fp8_fused_quant: bool = False, fp8_mx_ffn: bool = False):
+                 fp8_compute: bool = False, fp8_fused_quant: bool = False, fp8_mx_ffn: bool = False, fp8_lora: bool = False):
         from .prompt import TextEncoder
         self.transformer = transformer
         # float32: the transformer keeps its residual stream in float (`set_residual_dtype`); None = bf16
@@ -92,16 +92,19 @@ class FluxT2IEngine(EngineLoraMixin):
         # fp8_mx_ffn: the double block's FF hidden state stays in MX fp8 between the FF-up and FF-down pairs
         # (`set_fp8_compute(mx_ffn=True)`: one quantise launch and the bf16 round trip fewer per double block; block scales, so the
         # numbers change); needs fp8_compute
+        # fp8_lora: run-time LoRA on the resident records inside the fp8 GEMMs (`set_fp8_compute(lora=True)`): `apply_loras` then
+        # works on a keep_fp8 model instead of refusing adapters that touch a resident Linear; needs fp8_compute
         self.fp8_compute, self.fp8_fused_quant, self.fp8_mx_ffn = bool(fp8_compute), bool(fp8_fused_quant), bool(fp8_mx_ffn)
+        self.fp8_lora = bool(fp8_lora)
+        if self.fp8_lora and not self.fp8_compute:
+            raise ValueError("fp8_lora=True needs fp8_compute=True: the adapter tail belongs to the FP8 GEMM")
         if self.fp8_mx_ffn and not self.fp8_compute:
             raise ValueError("fp8_mx_ffn=True needs fp8_compute=True: the MX hidden state belongs to the FP8 GEMMs")
         if self.fp8_fused_quant and not self.fp8_compute:
             raise ValueError("fp8_fused_quant=True needs fp8_compute=True: the fused norm quantises for the FP8 GEMM")
         if self.fp8_compute:
-            if self.fp8_mx_ffn:
-                transformer.set_fp8_compute(True, fused_quant=self.fp8_fused_quant, mx_ffn=True)
-            else:
-                transformer.set_fp8_compute(True, fused_quant=self.fp8_fused_quant)
+            more = {k: True for k, v in (("mx_ffn", self.fp8_mx_ffn), ("lora", self.fp8_lora)) if v}
+            transformer.set_fp8_compute(True, fused_quant=self.fp8_fused_quant, **more)
         self.scheduler = scheduler or FlowMatchEulerDiscreteScheduler.flux_dev()
         self.decode_fn = decode_fn
         self.vae_scale_factor = vae_scale_factor

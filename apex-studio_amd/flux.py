@@ -191,7 +191,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         self._bstreams: List[Any] = []
         # q/k/v preparation in the QKV GEMM's epilogue where the launch allows it (see _forward_one; APEX_FLUX_FUSE_QKV=0: A/B)
         self.fuse_qkv = os.environ.get("APEX_FLUX_FUSE_QKV", "1") != "0"
-        self._fp8_compute = self._fp8_fused_quant = self._fp8_mx_ffn = False      # set_fp8_compute
+        self._fp8_compute = self._fp8_fused_quant = self._fp8_mx_ffn = self._fp8_lora = False      # set_fp8_compute
 
     # ---- reference-compatible plumbing: module_base (from_config, set_storage_dtype / set_residual_dtype, cache_context, ...) ----
     def _anchor(self):
@@ -296,12 +296,65 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
 
     def _lora_param(self, module: str, what: str):
         if module in (getattr(self, "_fp8_records", None) or {}):
-            raise _l.ApexMIError(f"flux.mi355: '{module}' is a resident fp8 Linear (keep_fp8 load): there is no bf16 weight to merge a "
-                                 "LoRA into, and run-time LoRA on resident Flux weights is not supported — load without keep_fp8 "
-                                 "to use adapters")
+            if not self._fp8_lora:
+                raise _l.ApexMIError(f"flux.mi355: '{module}' is a resident fp8 Linear (keep_fp8 load): there is no bf16 weight to merge a "
+                                     "LoRA into, and run-time LoRA on resident Flux weights is not supported — load without keep_fp8 "
+                                     "to use adapters, or `set_fp8_compute(True, lora=True)` first")
+            # what load_lora_adapter validates the factors against: a resident parameter has no bf16 storage, only `_fp8_shape`
+            return next(p for k, p in self.named_parameters() if k == f"{module}.weight")
         return super()._lora_param(module, what)
 
-    def set_fp8_compute(self, on: bool, fused_quant: bool = False, mx_ffn: bool = False):
+    def _fp8_factors(self) -> bool:
+        """whether any resident record carries run-time LoRA factors, or a registered adapter (active or not) could give it some"""
+        recs = getattr(self, "_fp8_records", None) or {}
+        return any(r.lora_A is not None for r in recs.values()) or \
+            any(m in recs for d in getattr(self, "_lora_adapters", {}).values() for m in d)
+
+    # ---- LoRA on resident fp8 weights: applied at RUN TIME inside the fp8 GEMMs (`set_fp8_compute(True, lora=True)`), as the
+    # reference does around FPScaledLinear (R/src/lora/manager.py:454-606).  Modules whose weights are bf16 parameters still merge.
+    def _lora_validate(self, adapter_name, mods):
+        """the refusals of an adapter that touches resident records, before it is registered: the model stays as it is"""
+        recs = getattr(self, "_fp8_records", None) or {}
+        hit = [m for m in mods if m in recs]
+        if not hit:
+            return
+        for m in hit:
+            if "bias" in mods[m]:
+                raise NotImplementedError(f"flux.mi355: adapter '{adapter_name}' carries a lora_B.bias for the resident-fp8 Linear "
+                                          f"'{m}', which is not supported — drop the bias, or load without keep_fp8")
+        if self.residual_dtype == torch.float32:
+            raise _l.ApexMIError("flux.mi355: run-time LoRA on resident fp8 weights needs the bf16 residual stream (the float-output "
+                                 "launches cannot take the fp8 route and there is no bf16 run-time-LoRA path): "
+                                 "set_residual_dtype(torch.bfloat16) first")
+        if self.storage_dtype == torch.float32:
+            raise _l.ApexMIError("flux.mi355: run-time LoRA on resident fp8 weights needs bf16 storage (float activations cannot take the "
+                                 "fp8 route and there is no bf16 run-time-LoRA path): set_storage_dtype(torch.bfloat16) first")
+
+    @torch.no_grad()
+    def _lora_remerge(self, modules):
+        recs = getattr(self, "_fp8_records", None) or {}
+        modules = set(modules)
+        resident = {m for m in modules if m in recs}
+        for rec in {id(recs[m]): recs[m] for m in resident}.values():
+            rec.set_lora([(m, d[m]["A"], d[m]["B"], self._lora_scales[n]) for m, _, _ in rec.parts
+                          for n, d in self._lora_adapters.items() if m in d and self._lora_scales[n] != 0.0 and self._lora_enabled])
+        super()._lora_remerge(modules - resident)
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and self._fp8_factors():
+            raise _l.ApexMIError("flux.mi355: resident fp8 records carry run-time LoRA factors, which need bf16 storage (the float "
+                                 "activations of set_storage_dtype(torch.float32) cannot take the fp8 route and there is no bf16 "
+                                 "run-time-LoRA path): delete or unload the adapters first")
+        return super().set_storage_dtype(dtype)
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and self._fp8_factors():
+            raise _l.ApexMIError("flux.mi355: resident fp8 records carry run-time LoRA factors, which need the bf16 residual stream "
+                                 "(the float-output launches of set_residual_dtype(torch.float32) cannot take the fp8 route and there "
+                                 "is no bf16 run-time-LoRA path): delete or unload the adapters first")
+        return super().set_residual_dtype(dtype)
+
+    def set_fp8_compute(self, on: bool, fused_quant: bool = False, mx_ffn: bool = False, lora: bool = False):
         """Opt-in approximation: the block launches whose weights are RESIDENT e4m3 records (a `keep_fp8=True`
         load) quantise their activations per row to e4m3 and multiply in fp8 — `ops.gemm_fp8_grouped` for the grouped launches
         (the QKV pair with the fused q/k/v epilogue when `fuse_qkv` is set and no IP adapter is active), `ops.gemm`'s fp8 route
@@ -321,13 +374,35 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         Codes and scale bytes live in the storage of the bf16 hidden buffer, which is not written in this mode.  This CHANGES
         the numbers (block scales instead of one scale per row of the hidden state).  The single block (its MLP-up output shares
         proj_out's K with the attention output) and the f32 residual stream keep today's launches; `mx_ffn=False` (the default)
-        leaves every launch as it is."""
+        leaves every launch as it is.  An FF pair in which either record carries run-time LoRA factors keeps the per-row launches
+        (`ops.fp8_mx_route` refuses factors).
+
+        `lora=True` (needs `on=True`): RUN-TIME LoRA on the resident records.  `load_lora_adapter` / `set_adapters` /
+        `delete_adapters` / `disable_lora` / `enable_lora` then give every resident record the active adapters of its parts
+        (`ResidentWeight.set_lora`: block-diagonal B' for the fused q|k|v records) instead of refusing them; adapters on
+        non-resident modules merge as always.  A launch with such a record stays on the fp8 GEMM: one grouped skinny GEMM
+        (`ops.gemm_grouped` over the problems' `lora_A`; QKV and MLP-up of a single block share it) writes t = x A^T into a
+        per-stream workspace, and the grouped / fused-qkv launch adds t B'^T per problem by the bf16 MFMA tail
+        (`lora_t_list=` / `lora_B_list=`, where `ops.fp8_grouped_lora_route` holds; the single block's proj_out through
+        `ops.gemm_fp8(lora_t=, lora_B=)`).  With `fused_quant` the norm also stores the bf16 rows a skinny GEMM reads.  The flag
+        lives on the records (`lora_compute`); adapters that touch a resident module must be loaded AFTER this call (before it
+        they are refused, as always).  Adapters on resident Flux
+        weights exist in this mode ONLY: there is no bf16-compute run-time-LoRA path, so switching fp8 compute or `lora` off
+        while records carry factors is refused (delete or unload the adapters first), as is the f32 residual stream together
+        with factors and a `lora_B.bias` on a resident module.  `lora=False` (the default) leaves every launch as it is."""
+        if lora and not on:
+            raise ValueError("flux.mi355: set_fp8_compute(lora=True) needs on=True: the adapter tail belongs to the fp8 GEMM")
+        if not (on and lora) and self._fp8_factors():
+            raise _l.ApexMIError("flux.mi355: resident fp8 records carry run-time LoRA factors, which exist in fp8-compute mode only "
+                                 f"(set_fp8_compute(True, lora=True)); set_fp8_compute({bool(on)}, lora={bool(lora)}) would leave them "
+                                 "without a launch — delete or unload the adapters first (delete_adapters / unload_lora_weights)")
         if mx_ffn and not on:
             raise ValueError("flux.mi355: set_fp8_compute(mx_ffn=True) needs on=True: the MX hidden state belongs to the fp8 GEMMs")
         if fused_quant and not on:
             raise ValueError("flux.mi355: set_fp8_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp8 GEMM")
-        self._fp8_set_compute(on)
-        self._fp8_compute, self._fp8_fused_quant, self._fp8_mx_ffn = bool(on), bool(fused_quant), bool(mx_ffn)
+        for r in self._fp8_set_compute(on):
+            r.lora_compute = "fp8" if lora else "bf16"
+        self._fp8_compute, self._fp8_fused_quant, self._fp8_mx_ffn, self._fp8_lora = bool(on), bool(fused_quant), bool(mx_ffn), bool(lora)
         return self
 
     def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, **kw):
@@ -342,8 +417,27 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             if ops.fp8_grouped_route([XN[r] for r in rows], ws, [probe] * len(ws), epis) \
                     and ops.fp8_norm_quant_route(X, XN, ws[0], probe, epis[0])[0]:
                 return ops.ln_modulate_quant_fp8(X, *mod, **kw)
+            # a reader with run-time LoRA factors: its skinny GEMM reads the bf16 rows, so the norm stores them too (need_row)
+            if self._fp8_lora and ops.fp8_grouped_lora_route([XN[r] for r in rows], ws, [probe] * len(ws), epis) \
+                    and ops.fp8_norm_quant_rows(X, XN):
+                return ops.ln_modulate_quant_fp8(X, *mod, out=XN, **kw)
         ops.ln_modulate(X, *mod, out=XN, **kw)
         return None
+
+    def _lora_t(self, a_list, w_list):
+        """(lora_t_list, lora_B_list) of a launch whose records `w_list` may carry run-time LoRA factors: t_i = a_i A_i^T for every
+        problem with factors, by ONE grouped skinny GEMM (the problems share K), into the per-stream workspace — valid until this
+        stream's next call.  None entries = no adapter on that problem."""
+        idx = [i for i, w in enumerate(w_list) if w.lora_A is not None]
+        sizes = [a_list[i].shape[0] * w_list[i].lora_A.shape[0] for i in idx]
+        dev = a_list[0].device
+        buf = ops._workspace(("flux_lora_t", dev.index, torch.cuda.current_stream().cuda_stream), dev, 2 * sum(sizes)).view(torch.bfloat16)
+        ts, off = [None] * len(w_list), 0
+        for i, n in zip(idx, sizes):
+            ts[i] = buf[off:off + n].view(a_list[i].shape[0], w_list[i].lora_A.shape[0])
+            off += n
+        ops.gemm_grouped([a_list[i] for i in idx], [w_list[i].lora_A for i in idx], None, [ts[i] for i in idx])
+        return ts, [w.lora_B for w in w_list]
 
     def _rows_fp8(self, src, quantised):
         """(codes, scales) of the rows of the joint buffer `src`: the fused norm's, or one `quant_rows_fp8` launch into the
@@ -363,6 +457,11 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             qa, sa = self._rows_fp8(src, quantised)
             return ops.gemm_fp8_grouped([qa[r] for r in rows], [sa[r] for r in rows], w_list, bias_list, out_list, epilogue=epilogue,
                                         gate_list=gate_list, residual_list=residual_list)
+        if self._fp8_compute and self._fp8_lora and ops.fp8_grouped_lora_route(a_list, w_list, out_list, epilogue):
+            lt, lb = self._lora_t(a_list, w_list)          # the skinny launch first: it reads the bf16 rows
+            qa, sa = self._rows_fp8(src, quantised)
+            return ops.gemm_fp8_grouped([qa[r] for r in rows], [sa[r] for r in rows], w_list, bias_list, out_list, epilogue=epilogue,
+                                        gate_list=gate_list, residual_list=residual_list, lora_t_list=lt, lora_B_list=lb)
         assert quantised is None, "the fused norm did not store the rows this launch reads"
         return ops.gemm_grouped(a_list, w_list, bias_list, out_list, epilogue=epilogue, gate_list=gate_list,
                                 residual_list=residual_list)
@@ -562,12 +661,27 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         fp8_s = fp8 and not overlap and len(self.single_transformer_blocks) > 0 and ops.fp8_grouped_route(
             [XN, XN], [self.single_transformer_blocks[0]._wqkv, rec(self.single_transformer_blocks[0].proj_mlp.weight)],
             [QKV, CAT[:, dim:]], ["bias", "gelu"])
-        fuse8_d, fuse8_s = fp8_d and self.fuse_qkv and ip is None, fp8_s and self.fuse_qkv
-        # mx_ffn: the FF hidden state of the double blocks as MX codes + block scales in the bytes of FFH (no bf16 row is stored)
+        # run-time LoRA on resident records (set_fp8_compute(lora=True)): which blocks carry factors is the adapter's business, so
+        # with factors anywhere every launch class is decided PER BLOCK: False = the plain fp8 launch, True = the fp8 launch with
+        # the adapter tail (one grouped skinny GEMM in front of it), None = not routed.  Without factors the block-0 decisions
+        # above hold for every block, as they always did.
+        lora_live = fp8 and self._fp8_lora and any(r.lora_A is not None for r in self._fp8_records.values())
+        if lora_live and overlap:
+            raise _l.ApexMIError("flux.mi355: the APEX_FLUX_OVERLAP=1 experiment has no launch for resident records with run-time LoRA "
+                                 "factors — unset it, or delete / unload the adapters")
+
+        def fp8_kind(a_list, w_list, out_list, epis):
+            if ops.fp8_grouped_route(a_list, w_list, out_list, epis):
+                return False
+            return True if ops.fp8_grouped_lora_route(a_list, w_list, out_list, epis) else None
+
+        def mx_route(blk):
+            return all(ops.fp8_mx_route(xn, net[0].proj.weight, net[2].weight, "gelu", "gate_res", out=x) for xn, net, x in
+                       ((XNi, blk.ff.net, Xi), (XNt, blk.ff_context.net, Xt)))
+        # mx_ffn: the FF hidden state of the double blocks as MX codes + block scales in the bytes of FFH (no bf16 row is stored);
+        # a block whose FF records carry factors keeps the per-row launches (mx_route refuses factors)
         mlp = FFH.shape[1]
-        mx_d = fp8 and self._fp8_mx_ffn and len(self.transformer_blocks) > 0 and all(
-            ops.fp8_mx_route(xn, net[0].proj.weight, net[2].weight, "gelu", "gate_res", out=x) for xn, net, x in
-            ((XNi, self.transformer_blocks[0].ff.net, Xi), (XNt, self.transformer_blocks[0].ff_context.net, Xt)))
+        mx_d = fp8 and self._fp8_mx_ffn and len(self.transformer_blocks) > 0 and (lora_live or mx_route(self.transformer_blocks[0]))
         if mx_d:
             raw = FFH.view(torch.uint8)
             hq, hs = raw[:, :mlp], raw[:, mlp:mlp + mlp // 32]
@@ -594,14 +708,18 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             mi = lambda j: self._mod(MOD, ("d", i, "img"), j)  # noqa: E731
             mt = lambda j: self._mod(MOD, ("d", i, "txt"), j)  # noqa: E731
             # chunk order: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-            qn = self._norm_rows(X, XN, img_txt, [blk._wqkv, blk._wqkv_c] if fp8_d else [], "bias", mi(1), mi(0), split=s_txt,
+            kind = fp8_kind([XNi, XNt], [blk._wqkv, blk._wqkv_c], [QKV[s_txt:], QKV[:s_txt]], "bias") if lora_live else \
+                (False if fp8_d else None)
+            fuse8_d = kind is not None and self.fuse_qkv and ip is None
+            qn = self._norm_rows(X, XN, img_txt, [blk._wqkv, blk._wqkv_c] if kind is not None else [], "bias", mi(1), mi(0), split=s_txt,
                                  scale2=mt(1), shift2=mt(0))
             if fuse8_d:
+                lt, lb = self._lora_t([XNi, XNt], [blk._wqkv, blk._wqkv_c]) if kind else (None, None)
                 qa, sa = self._rows_fp8(XN, qn)
                 ops.gemm_fp8_grouped_qkv([qa[s_txt:], qa[:s_txt]], [sa[s_txt:], sa[:s_txt]], [blk._wqkv, blk._wqkv_c],
                                          [blk._bqkv, blk._bqkv_c], [None, None], "bias", [1, 1],
                                          [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
-                                         [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
+                                         [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0], lora_t_list=lt, lora_B_list=lb)
             elif fuse_d:
                 # q/k norm + RoPE + [H, S, D] layout and V^T leave the QKV GEMM's epilogue: no [S, 3 dim] round trip
                 ops.gemm_grouped_qkv([XNi, XNt], [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [None, None], "bias",
@@ -623,7 +741,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             ff, ffc = blk.ff.net, blk.ff_context.net
             qn = self._norm_rows(X, XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight] if fp8 else [], "gelu", mi(4), mi(3),
                                  split=s_txt, scale2=mt(4), shift2=mt(3))
-            if mx_d:
+            if mx_d and (not lora_live or mx_route(blk)):
                 qa, sa = self._rows_fp8(XN, qn)
                 ops.gemm_fp8_grouped([qa[r] for r in img_txt], [sa[r] for r in img_txt], [rec(ff[0].proj.weight), rec(ffc[0].proj.weight)],
                                      [ff[0].proj.bias, ffc[0].proj.bias], [None, None], "gelu",
@@ -659,7 +777,10 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             a = blk.attn
             Qp, Kp, VT = qkv_s
             ms = lambda j: self._mod(MOD, ("s", i), j)  # noqa: E731  (shift, scale, gate)
-            qn = self._norm_rows(X, XN, both, [blk._wqkv, blk.proj_mlp.weight] if fp8_s else [], ["bias", "gelu"], ms(1), ms(0))
+            kind = (False if fp8_s else None) if not lora_live else fp8_kind(
+                [XN, XN], [blk._wqkv, rec(blk.proj_mlp.weight)], [QKV, CAT[:, dim:]], ["bias", "gelu"])
+            fuse8_s = kind is not None and self.fuse_qkv
+            qn = self._norm_rows(X, XN, both, [blk._wqkv, blk.proj_mlp.weight] if kind is not None else [], ["bias", "gelu"], ms(1), ms(0))
             if overlap:
                 # experiment (APEX_FLUX_OVERLAP=1): the MLP-up GEMM on the side stream underneath q/k prepare +
                 # attention, whose 1.69-round launch leaves 80 CUs idle in its second round
@@ -673,10 +794,13 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                     mlp_done.record(self._side)
                 ops.gemm(XN, blk._wqkv, blk._bqkv, out=QKV)
             elif fuse8_s:
+                # with adapters: QKV and MLP-up read the same rows, so their two skinny problems share one launch
+                lt, lb = self._lora_t([XN, XN], [blk._wqkv, rec(blk.proj_mlp.weight)]) if kind else (None, None)
                 qa, sa = self._rows_fp8(XN, qn)
                 ops.gemm_fp8_grouped_qkv([qa, qa], [sa, sa], [blk._wqkv, rec(blk.proj_mlp.weight)], [blk._bqkv, blk.proj_mlp.bias],
                                          [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
-                                         [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
+                                         [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0],
+                                         lora_t_list=lt, lora_B_list=lb)
             elif fuse_s:
                 ops.gemm_grouped_qkv([XN, XN], [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias],
                                      [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
@@ -692,8 +816,19 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             ops.attention_prepared(Qp, Kp, VT, att_v, S)
             if overlap:
                 torch.cuda.current_stream().wait_event(mlp_done)
-            ops.gemm(CAT, blk.proj_out.weight, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2),
-                     residual=X)
+            po = rec(blk.proj_out.weight)
+            if lora_live and getattr(po, "lora_A", None) is not None:
+                # the single-problem route with the adapter tail: t from the same kind of workspace as the grouped launches
+                if not ops.fp8_grouped_lora_route([CAT], [po], [X], "gate_res"):
+                    raise _l.ApexMIError("flux.mi355: the single block's proj_out carries run-time LoRA factors and its launch cannot "
+                                         "take the fp8 route (bf16 storage and the bf16 residual stream are required)")
+                lt, lb = self._lora_t([CAT], [po])
+                qa, sa = self._rows_fp8(CAT, None)
+                ops.gemm_fp8(qa, sa, po, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2), residual=X, lora_t=lt[0],
+                             lora_B=lb[0])
+            else:
+                ops.gemm(CAT, blk.proj_out.weight, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2),
+                         residual=X)
             if cn_s is not None:
                 ops.add(Xi, cn_s[i], out=Xi)
 

@@ -163,6 +163,16 @@ SIGNATURES = {
                                               C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p,
                                               C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_int, C.c_float,
                                               vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "apexmi_gemm_fp8_grouped_lora": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(C.c_int),
+                                               C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p,
+                                               C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(C.c_int), vp]),
+    "apexmi_gemm_fp8_grouped_qkv_lora": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p,
+                                                   C.POINTER(C.c_int), C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p,
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp),
+                                                   C.POINTER(vp), c_i64p, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp),
+                                                   C.POINTER(C.c_int), C.c_int, C.c_float, vp, vp, vp, vp, C.c_int, C.c_int,
+                                                   C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(C.c_int), vp]),
     "apexmi_quant_blocks_mxfp8": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_gemm_fp8_mx": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp,
                                      C.c_int64, vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

@@ -187,10 +187,14 @@ class LoraAdapterMixin:
             if tuple(d["B"].shape[:1]) + tuple(d["A"].shape[1:]) != tuple(wshape):
                 raise ValueError(f"adapter '{adapter_name}', module '{m}': delta {d['B'].shape[0]}x{d['A'].shape[1]} "
                                  f"does not fit weight {tuple(wshape)}")
+        self._lora_validate(adapter_name, mods)
         ads[adapter_name] = mods
         self._lora_scales[adapter_name] = 1.0 if activate else 0.0
         if activate:
             self._lora_remerge(mods.keys())
+
+    def _lora_validate(self, adapter_name: str, mods: Dict[str, Dict[str, torch.Tensor]]) -> None:
+        """A model's own refusals of an adapter (module -> factors), raised BEFORE it is registered; the default accepts it."""
 
     def set_adapters(self, adapter_names, weights=None) -> None:
         """Activate exactly `adapter_names` with `weights` (default 1.0); others get scale 0 (manager.py:588-597)."""

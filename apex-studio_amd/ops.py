@@ -413,6 +413,11 @@ def fp8_lora_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilo
       * the shape rules of `fp8_compute_route` hold;
       * `lora_buf` is the padded activation buffer `_gemm_fp8_lora` requires (the skinny GEMM writes t behind `a`)."""
     f8 = _fp8_of(w)
+    return _fp8_lora_problem_route(a, f8, out, epilogue) and _is_lora_buf(a, f8, lora_buf)
+
+
+def _fp8_lora_problem_route(a: torch.Tensor, f8, out: Optional[torch.Tensor], epilogue: str) -> bool:
+    """The rules of `fp8_lora_route` that do not concern `lora_buf` (shared with `fp8_grouped_lora_route`)."""
     if not isinstance(f8, Fp8Weight) or f8.compute != "fp8" or f8.lora_compute != "fp8" or f8.q.dtype != torch.float8_e4m3fn \
             or f8.lora_A is None:
         return False
@@ -422,9 +427,18 @@ def fp8_lora_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilo
         return False
     M, K = a.shape
     N = f8.shape[0]
-    if not (M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)):
+    return M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)
+
+
+def fp8_norm_quant_rows(x: torch.Tensor, xn: torch.Tensor) -> bool:
+    """Whether the fused norm `ln_modulate_quant_fp8` accepts the pair (input rows `x`, normalised rows `xn`), whatever reads the
+    codes: the rules of `fp8_norm_quant_route` that concern the rows alone.  Pure."""
+    if x.dim() != 2 or xn.dim() != 2 or tuple(x.shape) != tuple(xn.shape) or x.stride(1) != 1 or xn.stride(1) != 1:
         return False
-    return _is_lora_buf(a, f8, lora_buf)
+    if x.dtype not in (torch.bfloat16, torch.float32) or xn.dtype != torch.bfloat16:
+        return False
+    M, Cc = x.shape
+    return not (M < 1 or Cc % 128 != 0 or Cc > 8192 or x.stride(0) % (16 // x.element_size()) != 0 or xn.stride(0) % 8 != 0)
 
 
 def fp8_norm_quant_route(x: torch.Tensor, xn: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias",
@@ -439,12 +453,7 @@ def fp8_norm_quant_route(x: torch.Tensor, xn: torch.Tensor, w, out: Optional[tor
       need_row  the bf16 row must still be stored (pass `out=xn` to the fused norm): the weight carries run-time LoRA factors
                 (the skinny GEMM reads `xn`), or the caller says something else reads `xn` (`row_read_later`).  False only
                 with `fuse`."""
-    if x.dim() != 2 or xn.dim() != 2 or tuple(x.shape) != tuple(xn.shape) or x.stride(1) != 1 or xn.stride(1) != 1:
-        return False, True
-    if x.dtype not in (torch.bfloat16, torch.float32) or xn.dtype != torch.bfloat16:
-        return False, True
-    M, Cc = x.shape
-    if M < 1 or Cc % 128 != 0 or Cc > 8192 or x.stride(0) % (16 // x.element_size()) != 0 or xn.stride(0) % 8 != 0:
+    if not fp8_norm_quant_rows(x, xn):
         return False, True
     if fp8_compute_route(xn, w, out, epilogue):
         return True, bool(row_read_later)
@@ -724,6 +733,33 @@ def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
     return all(fp8_compute_route(a, w, o, e) for a, w, o, e in zip(a_list, w_list, outs, epis))
 
 
+def fp8_grouped_lora_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
+    """Whether a grouped launch over these problems, some of whose records carry run-time LoRA factors, may go out as skinny
+    `gemm_grouped` + quantise + `gemm_fp8_grouped(lora_t_list=, lora_B_list=)`.  Pure, like `fp8_compute_route` (dtypes, shapes and
+    strides only; CPU tensors are fine).  True only when EVERY problem satisfies either `fp8_compute_route` (a record without
+    factors) or the rules of `fp8_lora_route` without its `lora_buf` condition (an e4m3 record with `compute == "fp8"` AND
+    `lora_compute == "fp8"` that carries factors; t lives in a tensor of its own, so no padded activation buffer is needed), AT
+    LEAST ONE problem carries factors (otherwise `fp8_grouped_route` is the question), and there are 1 to 4 problems sharing K.  A
+    launch is all fp8 or not routed, never mixed."""
+    n = len(a_list)
+    if not 1 <= n <= FP8_MAX_GROUPS or len(w_list) != n:
+        return False
+    epis = [epilogues] * n if isinstance(epilogues, str) else list(epilogues)
+    outs = [None] * n if out_list is None else list(out_list)
+    if len(epis) != n or len(outs) != n or len({a.shape[-1] for a in a_list}) != 1:
+        return False
+    any_lora = False
+    for a, w, o, e in zip(a_list, w_list, outs, epis):
+        f8 = _fp8_of(w)
+        if isinstance(f8, Fp8Weight) and f8.lora_A is not None:
+            any_lora = True
+            if not _fp8_lora_problem_route(a, f8, o, e):
+                return False
+        elif not fp8_compute_route(a, w, o, e):
+            return False
+    return any_lora
+
+
 def fp8_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_down: str = "gate_res",
                  out: Optional[torch.Tensor] = None) -> bool:
     """Whether the pair `h = gemm(a, w_up, epilogue=epilogue_up)` -> `gemm(h, w_down, out=out, epilogue=epilogue_down)` may keep
@@ -797,15 +833,53 @@ def _fp8_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list,
             I64(*[(r.stride(0) if (r is not None and e == "gate_res") else 0) for r, e in zip(residual_list, epis)]))
 
 
+def _fp8_grouped_lora_args(who, codes_list, w_list, lora_t_list, lora_B_list):
+    """ctypes arrays (t, ldt, lb, ldb, Rp) of the grouped LoRA entry points; None entries = no adapter on that problem."""
+    import ctypes as C
+    n = len(codes_list)
+    tl, bl = list(lora_t_list or [None] * n), list(lora_B_list or [None] * n)
+    if len(tl) != n or len(bl) != n:
+        raise _l.ApexMIError(f"{who}: lora_t_list / lora_B_list must have one entry (or None) per problem")
+    rp = []
+    for i, (t, b) in enumerate(zip(tl, bl)):
+        if (t is None) != (b is None):
+            raise _l.ApexMIError(f"{who}: lora_t_list[{i}] and lora_B_list[{i}] go together (both or neither)")
+        if t is None:
+            rp.append(0)
+            continue
+        _req(t, torch.bfloat16, f"{who}.lora_t_list[{i}]")
+        _req(b, torch.bfloat16, f"{who}.lora_B_list[{i}]")
+        assert t.dim() == 2 and b.dim() == 2 and t.stride(1) == 1 and b.stride(1) == 1
+        assert t.shape[0] == codes_list[i].shape[0] and tuple(b.shape) == (w_list[i].shape[0], t.shape[1])
+        rp.append(int(t.shape[1]))
+    VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
+    st = lambda ts: I64(*[0 if t is None else t.stride(0) for t in ts])  # noqa: E731
+    return VP(*[_ptr(t) for t in tl]), st(tl), VP(*[_ptr(b) for b in bl]), st(bl), INT(*rp)
+
+
 def gemm_fp8_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilogue="bias", gate_list=None,
-                     residual_list=None, block_scales_list=None, out_mx_list=None) -> None:
+                     residual_list=None, block_scales_list=None, out_mx_list=None, lora_t_list=None, lora_B_list=None) -> None:
     """Up to 4 `gemm_fp8` problems sharing K in ONE launch (img / txt streams; QKV + MLP-up of a single block): out_list[i] =
     epi_i((codes_i . w_i.q^T) * scales_i[m] * w_i.scale[n] + bias_i), bit for bit what `gemm_fp8` leaves for that problem alone.
     `epilogue` is one name or one per problem (bias / gelu / gate_res, freely mixed); a gate_res problem may have
     residual_list[i] is out_list[i] (in place).  Several problems may share one (codes, scales) pair or row slices of it.
 
     `block_scales_list[i]` (then scales_list[i] is None) / `out_mx_list[i]` (then out_list[i] is ignored and may be None): the MX
-    forms of `gemm_fp8`, per problem; None entries are ordinary problems, so a launch may mix MX and bf16 outputs."""
+    forms of `gemm_fp8`, per problem; None entries are ordinary problems, so a launch may mix MX and bf16 outputs.
+
+    `lora_t_list[i]` [M_i, Rp_i] / `lora_B_list[i]` [N_i, Rp_i] (bf16, both or neither per problem, Rp_i a multiple of 64, row strides
+    free; not with the MX lists): the run-time LoRA form of `gemm_fp8`, per problem.  None entries are problems without an adapter:
+    every problem leaves the bits of its own single launch, `gemm_fp8(lora_t=, lora_B=)` or plain `gemm_fp8`.  At least one
+    problem must carry an adapter; with both lists None the call is the plain launch."""
+    if lora_t_list is not None or lora_B_list is not None:
+        if block_scales_list is not None or out_mx_list is not None:
+            raise _l.ApexMIError("gemm_fp8_grouped: the run-time LoRA form (lora_t_list / lora_B_list) takes per-row scales and writes "
+                                 "bf16: block_scales_list / out_mx_list are not supported with it")
+        args = _fp8_grouped_args("gemm_fp8_grouped", codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list,
+                                 residual_list)
+        largs = _fp8_grouped_lora_args("gemm_fp8_grouped", codes_list, w_list, lora_t_list, lora_B_list)
+        _l.check(_l.load().apexmi_gemm_fp8_grouped_lora(*args, *largs, _stream()), "gemm_fp8_grouped_lora")
+        return
     args = _fp8_grouped_args("gemm_fp8_grouped", codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list,
                              residual_list, block_scales_list=block_scales_list, out_mx_list=out_mx_list)
     n = len(codes_list)
@@ -824,12 +898,16 @@ def gemm_fp8_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilo
 
 def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
                          eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor,
-                         block_scales_list=None, out_mx_list=None) -> None:
+                         block_scales_list=None, out_mx_list=None, lora_t_list=None, lora_B_list=None) -> None:
     """`gemm_fp8_grouped` with `qkv_prepare` fused into the epilogue of the problems flagged in `is_qkv` (fused QKV projections,
     N = 3 H 128), mirroring `gemm_grouped_qkv`: q / k leave normalised per head, rotated and laid out [H, S_out, 128], v leaves
     transposed [H, 128, Skp]; bit-identical to gemm_fp8_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
-    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count."""
+    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count.
+
+    `lora_t_list` / `lora_B_list`: as in `gemm_fp8_grouped` (a fused problem takes the block-diagonal B' of its q | k | v parts);
+    bit-identical to gemm_fp8_grouped(lora_t_list=, lora_B_list=) + qkv_prepare."""
     import ctypes as C
+    lora = lora_t_list is not None or lora_B_list is not None
     if block_scales_list is not None or out_mx_list is not None:
         raise _l.ApexMIError("gemm_fp8_grouped_qkv: the fused q/k/v epilogue takes per-row scales and writes bf16: "
                              "block_scales_list / out_mx_list are not supported with it")
@@ -849,10 +927,14 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
             _req(t_, torch.bfloat16, "gemm_fp8_grouped_qkv norm weight")
             assert t_.is_contiguous() and t_.numel() == 128
     VP, INT = C.c_void_p * n, C.c_int * n
-    rc = _l.load().apexmi_gemm_fp8_grouped_qkv(
-        *args, INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
-        VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
-        ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2], _stream())
+    qargs = (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
+             VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
+             ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+    if lora:
+        largs = _fp8_grouped_lora_args("gemm_fp8_grouped_qkv", codes_list, w_list, lora_t_list, lora_B_list)
+        _l.check(_l.load().apexmi_gemm_fp8_grouped_qkv_lora(*args, *qargs, *largs, _stream()), "gemm_fp8_grouped_qkv_lora")
+        return
+    rc = _l.load().apexmi_gemm_fp8_grouped_qkv(*args, *qargs, _stream())
     _l.check(rc, "gemm_fp8_grouped_qkv")
 
 

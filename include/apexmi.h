@@ -824,6 +824,35 @@ int apexmi_gemm_fp8_grouped_qkv(int count, const void* const* qa, const int64_t*
                                 const int* row0, int H, float eps, const float* rope, void* q_out, void* k_out, void* vt_out,
                                 int S_out, int Skp, apexmi_stream_t stream);
 
+/* apexmi_gemm_fp8_grouped_lora — apexmi_gemm_fp8_grouped with a RUN-TIME LoRA adapter per problem (apexmi_gemm_fp8_lora's term,
+ * inside the grouped launch).  Five more host arrays of length `count`: t[i] bf16 [M[i], Rp[i]] (row stride ldt[i] elements), lb[i]
+ * = B' bf16 [N[i], Rp[i]] (row stride ldb[i]), Rp[i] the padded rank.  Rp[i] == 0 = problem i has no adapter (t[i] / lb[i] may be
+ * NULL).  Contract: EVERY problem leaves the bits its own single launch leaves — apexmi_gemm_fp8_lora when Rp[i] > 0 (in-place
+ * scaling, bf16 tail with rank ascending, one rounding), apexmi_gemm_fp8 when Rp[i] == 0.  Per problem with an adapter the rules
+ * of apexmi_gemm_fp8_lora hold (Rp % 64 == 0; ldt, ldb >= Rp, % 8 == 0, <= 2^22; 16-byte aligned t and lb); every check runs for
+ * all problems before the launch and nothing is written when one is refused.  At least one Rp[i] must be > 0 (otherwise use
+ * apexmi_gemm_fp8_grouped).  The MX forms are not combined with it. */
+int apexmi_gemm_fp8_grouped_lora(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                 const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                 const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc, const int* M,
+                                 const int* N, int K, const int* epilogue, const float* const* gate, const void* const* R,
+                                 const int64_t* ldr, const void* const* t, const int64_t* ldt, const void* const* lb,
+                                 const int64_t* ldb, const int* Rp, apexmi_stream_t stream);
+
+/* apexmi_gemm_fp8_grouped_qkv with the same five adapter arrays: a fused QKV problem with Rp[i] > 0 prepares y = bf16(acc + bias)
+ * with the scales and the adapter term already in the accumulators (lb[i] is block-diagonal over q | k | v for per-projection
+ * adapters).  q_out, k_out and columns < S_out of vt_out are BIT-IDENTICAL to apexmi_gemm_fp8_grouped_lora followed by
+ * apexmi_qkv_prepare (rope_mode interleaved) on the same operands; the other problems of the launch are those of
+ * apexmi_gemm_fp8_grouped_lora. */
+int apexmi_gemm_fp8_grouped_qkv_lora(int count, const void* const* qa, const int64_t* lda, const float* const* sa,
+                                     const void* const* qw, const int64_t* ldw, const int* w_format, const void* const* sw,
+                                     const int64_t* sw_count, const void* const* bias, void* const* C, const int64_t* ldc,
+                                     const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                     const void* const* R, const int64_t* ldr, const int* is_qkv, const void* const* norm_q,
+                                     const void* const* norm_k, const int* row0, int H, float eps, const float* rope, void* q_out,
+                                     void* k_out, void* vt_out, int S_out, int Skp, const void* const* t, const int64_t* ldt,
+                                     const void* const* lb, const int64_t* ldb, const int* Rp, apexmi_stream_t stream);
+
 /* MX block-scaled activations (opt-in): one e8m0 scale byte per 32 consecutive k of a row, which the block-scaled
  * MFMA applies itself, instead of one f32 scale per row.  A block's scale needs only the block, so a GEMM epilogue that holds a
  * tile of the row can quantise its own output.  Per block of 32 columns (aligned to 32), on the bf16 values:
