@@ -49,4 +49,38 @@ APEXMI_DEVICE uint32_t mx_quant4(uint32_t lo, uint32_t hi, float inv) {
     return mx_quant4f(bf16_lo(lo), bf16_hi(lo), bf16_lo(hi), bf16_hi(hi), inv);
 }
 
+// ---- MXFP4 block quantiser (apexmi_quant_blocks_mxfp4, gemm_mxfp4.hip) -----------------------------------------------------------
+// The same block of 32 bf16 values and the same e8m0 scale byte, for OCP e2m1 codes: bit 3 = sign, the low three bits index the
+// magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6.  e = clamp(E - 2 + (man > 0x400000), -126, 127)  (6 = 1.5 x 2^2: the smallest 2^e with
+// amax / 2^e <= 6; 0 for a zero block), scale byte = e + 127, code = e2m1_rne(clamp(x * 2^-e, -6, 6)): round to nearest, ties to the
+// even code (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4).  The sign bit of x is KEPT, also where the
+// magnitude rounds to zero (-0.1 -> code 8 = -0).  The rounding is done in VALU arithmetic, not by v_cvt_scalef32_pk_fp4_f32:
+// that instruction's tie rule, saturation and sign of zero have not been checked against this definition, and the quantiser is a
+// streaming pass with VALU time to spare.  bf16 inputs give e <= 126, so 2^-e (mx_inv_scale) is a normal float.
+APEXMI_DEVICE int mx4_scale_byte(float amax) {
+    const uint32_t b = __float_as_uint(amax) & 0x7fffffffu;
+    if (b == 0u) return 127;
+    const int e = (int)(b >> 23) - 127 - 2 + ((b & 0x7fffffu) > 0x400000u ? 1 : 0);
+    return min(max(e, -126), 127) + 127;
+}
+
+// one value -> its e2m1 code (4 bits).  y = min(|x| 2^-e, 6) is exact (a power-of-two factor).  y >= 1: the code is the float's
+// exponent and top mantissa bit after rounding the other 22 mantissa bits to nearest even (1.0 = exponent field 127 -> code 2);
+// y < 1: the grid is 0, 0.5, 1 and y + 2^22 rounds to nearest-even halves, its two lowest mantissa bits are the code.
+APEXMI_DEVICE uint32_t mx4_code(float x, float inv) {
+    const float y = fminf(fabsf(x) * inv, 6.0f);
+    const uint32_t b = __float_as_uint(y);
+    const uint32_t normal = ((b + 0x1fffffu + ((b >> 22) & 1u)) >> 22) - 252u;
+    const uint32_t sub = __float_as_uint(y + 4194304.0f) & 3u;
+    return (y < 1.0f ? sub : normal) | ((__float_as_uint(x) >> 28) & 8u);
+}
+
+// 8 bf16 (4 dwords) -> 8 codes in one dword: byte j holds code[2 j] | code[2 j + 1] << 4 (torch's float4_e2m1fn_x2 packing)
+APEXMI_DEVICE uint32_t mx4_quant8(const u32x4 v, float inv) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r |= (mx4_code(bf16_lo(v[i]), inv) | (mx4_code(bf16_hi(v[i]), inv) << 4)) << (8 * i);
+    return r;
+}
+
 }  // namespace

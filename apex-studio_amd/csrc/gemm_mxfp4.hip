@@ -1,0 +1,243 @@
+// Opt-in MXFP4 compute: an MX block quantiser to OCP e2m1 codes with one e8m0 scale byte per 32 consecutive k, and a
+// GEMM of two such operands on v_mfma_scale_f32_32x32x64_f8f6f4 with cbsz = blgp = 4 (e2m1 x e2m1: half the cycles of the e4m3 form,
+// 4x bf16 per clock), BOTH block scales applied by the instruction.  Nothing is multiplied after the K-loop: the epilogue is the
+// unscaled one of fp8_gemm_tile.h.
+#include "common.h"
+#include "fp8_quant.h"        // mx4_scale_byte, mx4_quant8, mx_inv_scale
+#include "fp8_gemm_tile.h"    // the 128 x 128 tile, Fp8Problem, fp8_epilogue
+
+namespace {
+
+// ---- apexmi_quant_blocks_mxfp4 ------------------------------------------------------------------------------------------------
+// One pass, as quant_blocks_mxfp8_kernel: a lane holds 16 elements (32 bytes in, 8 bytes out), lanes l and l ^ 1 share a block of
+// 32, the even lane stores the scale byte.  K % 32 == 0: a row is a whole number of lane pairs and a pair never straddles two rows.
+// Threads past the last row read the last row again and store nothing.
+__global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(const bf16_t* __restrict__ a, int64_t lda, int M, int K,
+                                                                 uint8_t* __restrict__ q, int64_t ldq, uint8_t* __restrict__ bs,
+                                                                 int64_t ldbs) {
+    const int gpr = K >> 4;                                 // 16-element groups per row
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t row = gid / gpr;
+    const int k = (int)(gid - row * gpr) << 4;
+    const bool live = row < M;
+    const bf16_t* p = a + (live ? row : (int64_t)M - 1) * lda + k;
+    const u32x4 x0 = *(const u32x4*)p, x1 = *(const u32x4*)(p + 8);
+    float m = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(x0[i])), fabsf(bf16_hi(x0[i]))));
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(x1[i])), fabsf(bf16_hi(x1[i]))));
+    }
+    m = fmaxf(m, __shfl_xor(m, 1, 64));
+    const int sb = mx4_scale_byte(m);
+    const float inv = mx_inv_scale(sb);
+    if (!live) return;
+    *(u32x2*)(q + row * ldq + (k >> 1)) = u32x2{mx4_quant8(x0, inv), mx4_quant8(x1, inv)};
+    if ((k & 16) == 0) bs[row * ldbs + (k >> 5)] = (uint8_t)sb;
+}
+
+// ---- apexmi_gemm_mxfp4 --------------------------------------------------------------------------------------------------------
+// gemm_fp8_kernel's structure (gemm_fp8.hip): 128 x 128 output tile, 256 threads = 2 x 2 waves of 64 x 64, K-tiles of 128 BYTES per
+// row = 256 codes, both operand tiles staged by global_load_lds (16 bytes per lane) with the XOR swizzle on the source address, two
+// buffers, one barrier per K-tile, the XCD tile order with bands of 8 tile rows, clamped edge rows.
+//
+// A K-tile is four k-steps of 64 codes.  Operand lane map of the instruction with 4-bit formats (4 registers per lane), pinned by
+// the one-hot probes of tests/test_gpu_mxfp4.py: lane l holds the 32 codes k = 32 (l >> 5) + 0..31 of row (A) / column (B) l & 31 =
+// ONE 16-byte piece of the staged row, piece 2 ks + (l >> 5) of k-step ks; the order of the nibbles inside the piece is the same
+// for both operands and so does not matter to a dot product.  A lane's 32 codes are exactly one MX block, and the instruction
+// scales them by byte 0 (op-sel 0) of THAT lane's scale register, on either side.
+//
+// Scale bytes: a K-tile needs 8 per row and operand.  They are staged through LDS with the tile — one 4-byte global_load_lds per
+// thread and operand (thread t: row t >> 1, dword t & 1), 2 KB per buffer behind the 64 KB of codes (dynamic LDS, 68 KB: two
+// workgroups per CU fit the 160 KB) — and read back as one ds_read_b64 per row and K-tile.  The alternative, plain global loads
+// some K-tiles ahead as the MX-input form of gemm_fp8_kernel does, puts 64 cache lines per wave instruction on the vector-memory
+// path next to the staging loads; staging keeps every scale access of the K-loop on LDS.  The two were not compared by measurement.
+constexpr int X4_SCB = FBM * 8;                              // scale bytes of one operand tile: 128 rows x 8 blocks
+constexpr int X4_LDS = 4 * FOPB + 4 * X4_SCB;                // codes [buf][operand] + scales [buf][operand]
+
+struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda / ldw in bytes; sa, sw, abs, Q, QS unused
+    const uint8_t* SA;                 // activation block scales [M, K / 32]
+    const uint8_t* SW;                 // weight block scales [N, K / 32]
+    int64_t ldsa, ldsw;
+    unsigned long long* clk;
+};
+
+APEXMI_DEVICE void glds4(const void* gsrc, void* lds) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
+}
+
+// EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1;
+
+    int t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
+    const int band = 8 * G.tiles_n, first_m = (t / band) * 8;
+    const int gsz = min(G.tiles_m - first_m, 8);
+    const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
+
+    // staging: wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 rows per instruction; thread t one scale dword per operand
+    const char* a_src[4];
+    const char* w_src[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int r = 32 * wid + 8 * i + (lane >> 3);
+        const int c = (lane & 7) ^ ((r >> 1) & 7);
+        a_src[i] = (const char*)(G.A + (int64_t)min(m0 + r, G.M - 1) * G.lda + c * 16);
+        w_src[i] = (const char*)(G.W + (int64_t)min(n0 + r, G.N - 1) * G.ldw + c * 16);
+    }
+    const char* sa_src = (const char*)(G.SA + (int64_t)min(m0 + (tid >> 1), G.M - 1) * G.ldsa + (tid & 1) * 4);
+    const char* sw_src = (const char*)(G.SW + (int64_t)min(n0 + (tid >> 1), G.N - 1) * G.ldsw + (tid & 1) * 4);
+    auto stage = [&](int kt, int buf) {
+        uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;     // wave-uniform; the hardware adds lane * 16
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            glds16(a_src[i] + (int64_t)kt * FBK, da + 8 * i * FBK);
+            glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
+        }
+        uint8_t* ds = lds + 4 * FOPB + buf * 2 * X4_SCB + wid * 256;   // wave-uniform; the hardware adds lane * 4
+        glds4(sa_src + kt * 8, ds);
+        glds4(sw_src + kt * 8, ds + X4_SCB);
+    };
+
+    unsigned long long clk_c0 = 0, clk_r0 = 0;
+    if (G.clk != nullptr) {          // kernel-uniform
+        clk_c0 = __builtin_readcyclecounter();
+        clk_r0 = __builtin_amdgcn_s_memrealtime();
+    }
+
+    f32x16 acc[2][2];                 // [weight tile (output columns)][activation tile (output rows)]
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int nk = G.K / (2 * FBK);
+    const int fr = lane & 31, fh = lane >> 5;
+    stage(0, 0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int buf = kt & 1;
+        if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
+        const uint8_t* ta = lds + buf * 2 * FOPB;
+        const uint8_t* tw = ta + FOPB;
+        const uint8_t* sa = lds + 4 * FOPB + buf * 2 * X4_SCB;
+        const uint8_t* sw = sa + X4_SCB;
+        // the 8 scale bytes of the lane's rows; lane half fh takes the odd blocks: byte 2 ks + fh of the 8 is byte 0 after the shift
+        u32x2 xa[2], xw[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            xa[i] = *(const u32x2*)(sa + (64 * wr + 32 * i + fr) * 8);
+            xw[i] = *(const u32x2*)(sw + (64 * wc + 32 * i + fr) * 8);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int piece = 2 * ks + fh;
+            const int shift = 16 * (ks & 1) + 8 * fh;
+            i32x8 fa[2], fw[2];
+            int ea[2], ew[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int ra = 64 * wr + 32 * i + fr, rw = 64 * wc + 32 * i + fr;
+                const u32x4 pa = *(const u32x4*)(ta + ra * FBK + ((piece ^ ((ra >> 1) & 7)) << 4));
+                const u32x4 pw = *(const u32x4*)(tw + rw * FBK + ((piece ^ ((rw >> 1) & 7)) << 4));
+                fa[i] = i32x8{(int)pa[0], (int)pa[1], (int)pa[2], (int)pa[3], 0, 0, 0, 0};
+                fw[i] = i32x8{(int)pw[0], (int)pw[1], (int)pw[2], (int)pw[3], 0, 0, 0, 0};
+                ea[i] = (int)(xa[i][ks >> 1] >> shift);
+                ew[i] = (int)(xw[i][ks >> 1] >> shift);
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fw[i], fa[j], acc[i][j], 4, 4, 0, ew[i], 0, ea[j]);
+        }
+        __syncthreads();
+    }
+
+    if (G.clk != nullptr) {
+        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
+        if (tid == 0) {
+            atomicAdd(G.clk, c1 - clk_c0);
+            atomicAdd(G.clk + 1, r1 - clk_r0);
+        }
+    }
+    fp8_epilogue<EPI, false>(acc, G, m0, n0, wr, wc, fr, fh);
+}
+
+}  // namespace
+
+extern "C" int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* scales, int64_t lds_,
+                                         apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(a && codes && scales, "quant_blocks_mxfp4: null operand");
+    APEXMI_REQUIRE(M >= 1, "quant_blocks_mxfp4: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(K >= 32 && K % 32 == 0, "quant_blocks_mxfp4: K=%d must be a multiple of 32", K);
+    APEXMI_REQUIRE(lda >= K && ldq >= K / 2 && lda % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 16) == 0,
+                   "quant_blocks_mxfp4: rows must be 16-byte aligned, a at least K and the codes at least K / 2 bytes wide (lda %lld, "
+                   "ldq %lld)", (long long)lda, (long long)ldq);
+    APEXMI_REQUIRE(lds_ >= K / 32, "quant_blocks_mxfp4: rows of the block scales must be at least K / 32 = %d wide (lds %lld)", K / 32,
+                   (long long)lds_);
+    ApexmiProfScope prof(5, stream, 0.0, (2.5 + 1.0 / 32) * (double)M * K);
+    const int64_t threads = (int64_t)M * (K / 16);
+    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "quant_blocks_mxfp4: M=%d x K=%d is too large for one launch", M, K);
+    hipLaunchKernelGGL(quant_blocks_mxfp4_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M,
+                       K, (uint8_t*)codes, ldq, (uint8_t*)scales, lds_);
+    return apexmi_check_launch("quant_blocks_mxfp4");
+}
+
+template <int EPI>
+static void mxfp4_launch(const Mxfp4Gemm& G, hipStream_t stream) {
+    static uint64_t attr_set = 0;       // 68 KB of dynamic LDS is above the default limit
+    APEXMI_SET_ATTR_ONCE(attr_set,
+        (void)hipFuncSetAttribute((const void*)gemm_mxfp4_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
+    hipLaunchKernelGGL(gemm_mxfp4_kernel<EPI>, dim3((unsigned)(G.tiles_m * G.tiles_n)), dim3(256), X4_LDS, stream, G);
+}
+
+extern "C" int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
+                                 int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
+                                 const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* who = "gemm_mxfp4";
+    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand", who);
+    APEXMI_REQUIRE(M >= 1, "%s: M=%d must be at least 1", who, M);
+    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "%s: N=%d must be a multiple of 16", who, N);
+    APEXMI_REQUIRE(K >= 256 && K % 256 == 0, "%s: K=%d must be a multiple of 256 (a K-tile is 128 bytes of e2m1 codes)", who, K);
+    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
+                   "%s: f32 output (epilogue %d, the f32 residual stream) is not supported: the output is bf16", who, epilogue);
+    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
+                   "%s: epilogue %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue);
+    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K / 2 && ldw >= K / 2 && ldc >= N,
+                   "%s: leading dimensions must keep rows 16-byte aligned, code rows at least K / 2 = %d bytes (lda %lld, ldw %lld, ldc "
+                   "%lld)", who, K / 2, (long long)lda, (long long)ldw, (long long)ldc);
+    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22), "%s: leading dimensions above 2^22 bytes are not supported (lda %lld, ldw %lld)",
+                   who, (long long)lda, (long long)ldw);
+    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
+                   "%s: the block scales must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, K / 32,
+                   (long long)ldsa, (long long)ldsw);
+    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)bias % 8) == 0,
+                   "%s: operands must be 16-byte aligned (output and bias 8-byte)", who);
+    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
+        APEXMI_REQUIRE(gate && R, "%s: gate/residual epilogue needs gate and R", who);
+        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "%s: gate/R alignment", who);
+    }
+    const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
+    APEXMI_REQUIRE((int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
+    Mxfp4Gemm G{};
+    (Fp8Problem&)G = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, nullptr, nullptr, (const bf16_t*)bias, (bf16_t*)C, gate,
+                                (const bf16_t*)R, lda, ldw, ldc, ldr, M, N, K, 0, tm, tn};
+    G.SA = (const uint8_t*)sa, G.SW = (const uint8_t*)sw, G.ldsa = ldsa, G.ldsw = ldsw;
+    G.clk = apexmi_clk_ptr();
+    ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * ((double)M + N) * K + 2.0 * (double)M * N);
+    switch (epilogue) {
+        case APEXMI_EPI_BIAS: mxfp4_launch<APEXMI_EPI_BIAS>(G, stream); break;
+        case APEXMI_EPI_BIAS_GELU: mxfp4_launch<APEXMI_EPI_BIAS_GELU>(G, stream); break;
+        default: mxfp4_launch<APEXMI_EPI_BIAS_GATE_RES>(G, stream); break;
+    }
+    return apexmi_check_launch(who);
+}

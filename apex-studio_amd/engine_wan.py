@@ -26,7 +26,7 @@ class WanT2VEngine(EngineLoraMixin):
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
-                 fp8_mx_ffn: bool = False):
+                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -75,6 +75,16 @@ class WanT2VEngine(EngineLoraMixin):
                     tr.set_fp8_compute(True, lora=True)
                 else:
                     tr.set_fp8_compute(True)
+        # the block Linears of bf16 experts multiply as MXFP4 (`set_fp4_compute`, DESIGN.md §3.6: an opt-in approximation on MXFP4
+        # copies beside the bf16 weights; not for resident-fp8 experts, so never together with fp8_compute); fp4_linears: a subset
+        # of the seven block Linears, None = all
+        self.fp4_compute = bool(fp4_compute)
+        self.fp4_linears = None if fp4_linears is None else tuple(fp4_linears)
+        if self.fp4_linears is not None and not self.fp4_compute:
+            raise ValueError("fp4_linears needs fp4_compute=True: it names the Linears of the MXFP4 compute mode")
+        if self.fp4_compute:
+            for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
+                tr.set_fp4_compute(True, linears=self.fp4_linears)
         self.vae = vae
         self.scheduler = scheduler or UniPCMultistepScheduler(shift=3.0)
         self.boundary_ratio = boundary_ratio
@@ -267,12 +277,12 @@ class WanI2VEngine(WanT2VEngine):
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
-                 fp8_mx_ffn: bool = False):
+                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
                          vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
                          attention_window=attention_window, fp8_compute=fp8_compute,
                          attention_band=attention_band, fp8_lora=fp8_lora, fp8_fused_quant=fp8_fused_quant,
-                         fp8_mx_ffn=fp8_mx_ffn)
+                         fp8_mx_ffn=fp8_mx_ffn, fp4_compute=fp4_compute, fp4_linears=fp4_linears)
         self.image_encoder = image_encoder
 
     @property

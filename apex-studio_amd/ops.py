@@ -715,6 +715,168 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
     return out
 
 
+# ---- opt-in MXFP4 compute: e2m1 codes, two to a byte, one e8m0 scale byte per 32 consecutive k ---------------------
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # the magnitudes of the low three code bits; bit 3 is the sign
+
+
+def quant_blocks_mxfp4(a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP4 block quantisation of bf16 `a` [M, K] (row stride free, K % 32 == 0) -> (codes uint8 [M, K / 2]: OCP e2m1, byte j of a
+    row = code[2 j] | code[2 j + 1] << 4 as torch's float4_e2m1fn_x2 packs them; scales uint8 [M, K / 32] = e8m0 exponents; row
+    strides free, code rows 16-byte aligned).  Per block of 32 consecutive columns:
+        amax = max |a| with unbiased f32 exponent E and mantissa bits man;  e = clamp(E - 2 + (man > 0x400000), -126, 127)
+        (0 for a zero block);  scale byte = e + 127;  code = e2m1_rne(clamp(a * 2^-e, -6, 6))
+    2^e is the smallest power of two with amax / 2^e <= 6, so the clamp clips nothing; ties go to the even code (0.25 -> 0,
+    0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4) and the sign bit of `a` is kept, also where the magnitude
+    rounds to zero.  Inputs must be finite.  One launch; what `gemm_mxfp4` reads on both sides."""
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"quant_blocks_mxfp4.a: expected a torch.bfloat16 tensor, got {getattr(a, 'dtype', type(a).__name__)}")
+    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 32 != 0 or a.shape[1] < 32 or a.shape[0] < 1:
+        raise _l.ApexMIError(f"quant_blocks_mxfp4.a: expected [M >= 1, K % 32 == 0] with contiguous rows, got {tuple(a.shape)}")
+    M, K = a.shape
+    if out is None:
+        out = torch.empty((M, (K // 2 + 15) // 16 * 16), dtype=torch.uint8, device=a.device)[:, :K // 2]
+    if scale_out is None:
+        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
+    _check_mxfp4_pair("quant_blocks_mxfp4.out", out, scale_out, M, K)
+    _req(a, torch.bfloat16, "quant_blocks_mxfp4.a")
+    _l.check(_l.load().apexmi_quant_blocks_mxfp4(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
+                                                 scale_out.stride(0), _stream()), "quant_blocks_mxfp4")
+    return out, scale_out
+
+
+def _check_mxfp4_pair(who: str, q, s, M: int, K: int, on_device: bool = True) -> None:
+    """An MXFP4 (codes [M, K / 2], scales [M, K / 32]) pair, both uint8 tensors with contiguous rows: type and shape first, then
+    (what every launch asks) the device"""
+    for name, t, cols in (("codes", q, K // 2), ("scales", s, K // 32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise _l.ApexMIError(f"{who}: the {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.dim() != 2 or tuple(t.shape) != (M, cols) or t.stride(1) != 1:
+            raise _l.ApexMIError(f"{who}: the {name} must be [{M}, {cols}] with contiguous rows (K = {K}), got {tuple(t.shape)}")
+        if on_device:
+            _req(t, torch.uint8, f"{who} ({name})")
+
+
+class Mxfp4Weight:
+    """An MXFP4 copy of a bf16 weight [N, K] for the opt-in fp4 compute: `q` uint8 [N, K / 2] e2m1 codes, `s` uint8 [N, K / 32]
+    e8m0 scale bytes, as `quant_blocks_mxfp4` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
+    sits beside it (on the weight tensor's `_fp4` slot, where `ops.gemm` looks); 0.53 bytes per weight element.  `compute`: "fp4"
+    (routed by `mxfp4_route`) or anything else (ignored)."""
+
+    def __init__(self, q: torch.Tensor, s: torch.Tensor):
+        N, K = q.shape[0], 2 * q.shape[1]
+        _check_mxfp4_pair("Mxfp4Weight", q, s, N, K, on_device=False)      # a CPU record can still be asked for its route
+        self.q, self.s, self.shape, self.compute = q, s, (N, K), "fp4"
+
+    @classmethod
+    def from_bf16(cls, w: torch.Tensor) -> "Mxfp4Weight":
+        return cls(*quant_blocks_mxfp4(w))
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return self.q.numel() + self.s.numel()
+
+    def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bf16 [N, K] = value(code) x 2^(scale byte - 127): exact in bf16 (one mantissa bit times a power of two) unless 4 or 6 x 2^126
+        overflows, which only a block holding values above 2^127 produces.  Plain torch: test and tool support, not a hot path."""
+        N, K = self.shape
+        lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=self.q.device)
+        q = self.q.long()
+        v = torch.stack([lut[q & 15], lut[q >> 4]], dim=-1).view(N, K // 32, 32)
+        v = (v * torch.exp2(self.s.float() - 127.0).unsqueeze(-1)).view(N, K).to(torch.bfloat16)
+        if out is None:
+            return v
+        _req(out, torch.bfloat16, "Mxfp4Weight.dequant.out")
+        out.copy_(v)
+        return out
+
+
+def _fp4_of(w):
+    """The MXFP4 record behind `w` (an Mxfp4Weight, or a weight tensor carrying one in `_fp4`), or None."""
+    return w if isinstance(w, Mxfp4Weight) else getattr(w, "_fp4", None)
+
+
+def mxfp4_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
+    """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as `quant_blocks_mxfp4` + `gemm_mxfp4`.  Pure: reads dtypes, shapes
+    and strides only (CPU tensors are fine).  True only when ALL of these hold:
+      * `w` is (or carries in `_fp4`) an `Mxfp4Weight` with `compute == "fp4"`;
+      * `a` is bf16 and `out` is bf16 or None (float activations = the f32-storage mode and a float `out` = the f32 residual
+        stream keep the bf16 path);
+      * the shape is eligible: M >= 1, K % 256 == 0, N % 16 == 0, 16-byte rows of `a`, and the epilogue is one of bias / gelu /
+        gate_res."""
+    f4 = _fp4_of(w)
+    if not isinstance(f4, Mxfp4Weight) or f4.compute != "fp4":
+        return False
+    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
+        return False
+    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
+        return False
+    M, K = a.shape
+    N = f4.shape[0]
+    return M >= 1 and K == f4.shape[1] and K % 256 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0
+
+
+_fp4_act_scratch: dict = {}
+
+
+def _act_scratch_mxfp4(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-stream home of the activation's MXFP4 codes [M, K / 2] and scale bytes [M, K / 32] (as `_act_scratch`)."""
+    key = (dev.index, torch.cuda.current_stream().cuda_stream)
+    q, s = _fp4_act_scratch.get(key, (None, None))
+    if q is None or q.numel() < M * (K // 2):
+        q = torch.empty(M * (K // 2), dtype=torch.uint8, device=dev)
+    if s is None or s.numel() < M * (K // 32):
+        s = torch.empty(M * (K // 32), dtype=torch.uint8, device=dev)
+    _fp4_act_scratch[key] = (q, s)
+    return q[:M * (K // 2)].view(M, K // 2), s[:M * (K // 32)].view(M, K // 32)
+
+
+def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] (bf16) = epi(sum_k value(codes[m, k]) 2^(scales[m, k / 32] - 127) value(w.q[n, k]) 2^(w.s[n, k / 32] - 127) + bias):
+    e2m1 x e2m1 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, one bf16 rounding.  `codes` /
+    `scales` as `quant_blocks_mxfp4` returns them; `w` an `Mxfp4Weight`; epilogue bias / gelu / gate_res (`residual` may be `out`).
+    K % 256 == 0, N % 16 == 0."""
+    who = "gemm_mxfp4"
+    if not isinstance(w, Mxfp4Weight):
+        raise _l.ApexMIError(f"{who}: expected an Mxfp4Weight, got {type(w).__name__}")
+    if epilogue not in _FP8_EPI:
+        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2:
+        raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(codes).__name__}")
+    M, (N, K) = codes.shape[0], w.shape
+    _check_mxfp4_pair(who, codes, scales, M, K)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
+    _req(out, None, who + ".out")
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise _l.ApexMIError(f"{who}.out: expected [{M}, {N}] with contiguous rows, got {tuple(out.shape)}")
+    flag = 0
+    if out.dtype == torch.float32:
+        flag = _l.EPI_F32_IO          # the entry point rejects it with its own message
+    else:
+        _req(out, torch.bfloat16, who + ".out")
+    if bias is not None:
+        _req(bias, torch.bfloat16, who + ".bias")
+        assert bias.is_contiguous() and bias.numel() == N
+    if epilogue == "gate_res":
+        if gate is None or residual is None:
+            raise _l.ApexMIError(f"{who}: the gate_res epilogue needs `gate` and `residual`")
+        _req(gate, torch.float32, who + ".gate")
+        _req(residual, out.dtype, who + ".residual")
+        assert gate.is_contiguous() and gate.numel() == N and residual.shape == (M, N) and residual.stride(1) == 1
+    rc = _l.load().apexmi_gemm_mxfp4(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
+                                     w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
+                                     _EPI[epilogue] | flag, _ptr(gate), _ptr(residual),
+                                     residual.stride(0) if epilogue == "gate_res" else 0, _stream())
+    _l.check(rc, who)
+    return out
+
+
 FP8_MAX_GROUPS = 4
 
 
@@ -966,8 +1128,19 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     whose GEMM takes neither route raises instead of quietly multiplying an `a` that may never have been written.
 
     `out_mx=(codes, block_scales)`: the fp8 route writes its output as MX codes and block scales (`gemm_fp8(out_mx=)`) instead of
-    `out`, and returns the pair.  The caller decides beforehand with `fp8_mx_route`; any other route raises."""
+    `out`, and returns the pair.  The caller decides beforehand with `fp8_mx_route`; any other route raises.
+
+    OPT-IN MXFP4 COMPUTE: a bf16 weight that carries an `Mxfp4Weight` with `compute == "fp4"` in its `_fp4` slot
+    (`set_fp4_compute` of the model attaches it) takes `quant_blocks_mxfp4` (codes and scale bytes in a per-stream scratch) +
+    `gemm_mxfp4` when `mxfp4_route` says so, asked before everything above.  A weight without the slot never reaches that code."""
     _req_act(a, "gemm.a")
+    if getattr(w, "_fp4", None) is not None and mxfp4_route(a, w, out, epilogue):
+        if quantised is not None or out_mx is not None:
+            raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP4 route (the weight "
+                                 "carries an Mxfp4Weight): e4m3 codes are not fp4 operands")
+        qa, sa = _act_scratch_mxfp4(a.device, a.shape[0], a.shape[1])
+        quant_blocks_mxfp4(a, out=qa, scale_out=sa)
+        return gemm_mxfp4(qa, sa, w._fp4, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
         if quantised is not None:

@@ -268,6 +268,90 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         self._fp8_mx_ffn = bool(mx_ffn)
         return self
 
+    _FP4_LINEARS = ("qkv", "attn_out", "cross_q", "cross_kv", "cross_out", "ffn_up", "ffn_down")
+
+    def set_fp4_compute(self, on: bool, linears=None):
+        """Opt-in approximation: the selected block Linears of a bf16 model — `linears`, a subset of ("qkv",
+        "attn_out", "cross_q", "cross_kv", "cross_out", "ffn_up", "ffn_down"), None = all seven (the Linears of `_fp8_plan`) —
+        quantise their activations per block of 32 to MXFP4 and multiply e2m1 x e2m1 (`ops.quant_blocks_mxfp4` +
+        `ops.gemm_mxfp4`) against an MXFP4 copy of the weight (`ops.Mxfp4Weight.from_bf16`, one record per Linear and block, the
+        fused q|k|v and cross k|v as one record each) that sits BESIDE the bf16 weight, on its `_fp4` slot: 0.53 bytes per
+        selected weight element on top of the model.  The image k|v projection, the embedders, proj_out and attention stay bf16.
+        False detaches the records: the next forward is the original, bit for bit.  The records follow the model's invalidation
+        rule (`_weights_changed`: a load, `.to`, a merged LoRA): they are dropped there and rebuilt before the next forward
+        while the mode is on, so a LoRA merged after the switch is quantised in.  A speed option, not a parity mode; no quality
+        claim on real checkpoints.
+
+        Refused: a model with resident quantised records (a keep_fp8 / keep_quantized load has no bf16 weight to copy, and the
+        `fp8_*` switches need exactly such records, so the two modes cannot meet), f32 activation storage and the f32 residual
+        stream (their GEMMs read or write float rows, which this mode does not route; `set_storage_dtype` / `set_residual_dtype`
+        refuse float32 while the mode is on), and an unknown name in `linears`."""
+        if linears is not None:
+            try:
+                linears = tuple(linears)
+            except TypeError as err:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=) takes names out of {self._FP4_LINEARS}, got {linears!r}") from err
+            bad = [n for n in linears if n not in self._FP4_LINEARS]
+            if bad:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=): unknown Linear name(s) {bad}; the block Linears are "
+                                     f"{self._FP4_LINEARS}")
+        if not on:
+            if linears is not None:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(False) takes no `linears`: it detaches every record")
+            self._fp4_linears = None
+            self._fp4_detach()
+            return self
+        if getattr(self, "_fp8_bytes", 0):
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute needs the bf16 block weights, and this model's are resident quantised "
+                                 f"records ({self._fp8_options()} load).  The fp8_* switches need exactly such records, so the two "
+                                 "modes cannot be combined: load without those options for fp4 compute")
+        if self.storage_dtype != torch.bfloat16:
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute is for bfloat16 activation storage; the f32-storage verification "
+                                 "mode keeps the bf16 GEMMs (set_storage_dtype(torch.bfloat16) first)")
+        if self.residual_dtype != torch.bfloat16:
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute does not take the f32 residual stream: its residual GEMMs write "
+                                 "float rows, which the fp4 GEMM does not (set_residual_dtype(torch.bfloat16) first)")
+        self.pack()
+        self._fp4_linears = tuple(n for n in self._FP4_LINEARS if linears is None or n in linears)
+        self._fp4_detach()
+        self._fp4_attach()
+        return self
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and getattr(self, "_fp4_linears", None) is not None:
+            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and is for bfloat16 activation storage: float rows would quietly "
+                                 "return every Linear to bf16; set_fp4_compute(False) first")
+        return super().set_storage_dtype(dtype)
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and getattr(self, "_fp4_linears", None) is not None:
+            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and does not take the f32 residual stream: its residual GEMMs "
+                                 "would quietly return to bf16; set_fp4_compute(False) first")
+        return super().set_residual_dtype(dtype)
+
+    def _fp4_weights(self, blk) -> dict:
+        a1, a2 = blk.attn1, blk.attn2
+        return {"qkv": blk._wqkv, "attn_out": a1.to_out[0].weight, "cross_q": a2.to_q.weight, "cross_kv": blk._wkv2,
+                "cross_out": a2.to_out[0].weight, "ffn_up": blk.ffn.net[0].proj.weight, "ffn_down": blk.ffn.net[2].weight}
+
+    @torch.no_grad()
+    def _fp4_attach(self):
+        """One Mxfp4Weight per selected Linear of every block, on the slot `ops.gemm` reads (`weight._fp4`)."""
+        self._fp4_live = []
+        for blk in self.blocks:
+            ws = self._fp4_weights(blk)
+            for name in self._fp4_linears:
+                ws[name]._fp4 = ops.Mxfp4Weight.from_bf16(ws[name])
+                self._fp4_live.append(ws[name])
+        self._fp4_bytes = sum(w._fp4.nbytes() for w in self._fp4_live)
+
+    def _fp4_detach(self):
+        for w in getattr(self, "_fp4_live", ()):
+            if getattr(w, "_fp4", None) is not None:
+                del w._fp4
+        self._fp4_live = []
+        self._fp4_bytes = 0
+
     def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", out_mx=None, **norm):
         """ln_modulate(x, **norm, out=xn) -> gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf); with
         `set_fp8_compute(fused_quant=True)`, where `ops.fp8_norm_quant_route` allows it, the norm quantises for the GEMM in its own
@@ -369,6 +453,8 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
                 self._lora_pad = pad         # the activation buffers grow by this many columns (see _workspace)
                 self._ws = {}
         super()._lora_remerge(modules - resident)
+        if modules - resident:
+            self._fp4_detach()      # merged into the bf16 weights: the MXFP4 copies are rebuilt before the next forward
 
     def state_dict(self, *a, **k):
         self._fp8_guard("state_dict")
@@ -377,7 +463,9 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
     @torch.no_grad()
     def _weights_changed(self):
         """Rebuild what is DERIVED from parameter values (f32 copies of the modulation tables, [L, 6*dim] and
-        [2*dim]).  `weights.load_checkpoint_into` writes parameters in place after `pack()` and calls this."""
+        [2*dim]).  `weights.load_checkpoint_into` writes parameters in place after `pack()` and calls this.  The MXFP4 copies
+        of `set_fp4_compute` are dropped here and rebuilt before the next forward."""
+        self._fp4_detach()
         if not self._packed:
             return
         dim, dev = self.inner_dim, self.device
@@ -598,6 +686,8 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         if timestep.ndim != 1:
             raise NotImplementedError("wan.mi355: per-token timesteps are not supported")
         self.pack()
+        if getattr(self, "_fp4_linears", None) is not None and not self._fp4_live:
+            self._fp4_attach()
         enc = encoder_hidden_states.to(self.storage_dtype)
         img = None
         if encoder_hidden_states_image is not None and self.config.added_kv_proj_dim is not None:

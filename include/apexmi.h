@@ -892,6 +892,30 @@ int apexmi_gemm_fp8_grouped_mx(int count, const void* const* qa, const int64_t* 
                                const void* const* abs, const int64_t* ldabs, void* const* mx_codes, const int64_t* ldmc,
                                void* const* mx_scales, const int64_t* ldms, apexmi_stream_t stream);
 
+/* MXFP4 compute (opt-in): OCP e2m1 codes (bit 3 = sign, the low three bits index the magnitudes 0, 0.5, 1, 1.5, 2, 3,
+ * 4, 6), packed two to a byte as torch's float4_e2m1fn_x2 does — byte j of a row holds code[2 j] | code[2 j + 1] << 4 — with one
+ * e8m0 scale byte per 32 consecutive k, as apexmi_quant_blocks_mxfp8.  Per block of 32 columns (aligned to 32), on the bf16 values:
+ *     amax = max |x|, E = its unbiased f32 exponent, man = its 23 mantissa bits;
+ *     e = clamp(E - 2 + (man > 0x400000), -126, 127), 0 for a zero block        (6 = 1.5 x 2^2: the smallest 2^e with amax / 2^e <= 6)
+ *     scale byte = e + 127 (127 for a zero block, never 255);   code = e2m1( min(max(x * 2^-e, -6), 6) )   nearest, ties to the even code
+ * (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4).  The sign bit of x is kept, also where the magnitude
+ * rounds to zero.  Inputs are finite.
+ *
+ * apexmi_quant_blocks_mxfp4 — a bf16 [M, K] (row stride lda elements); codes uint8 [M, K / 2] (row stride ldq bytes); scales uint8
+ * [M, K / 32] (row stride lds bytes).  K % 32 == 0, M >= 1, 16-byte rows of a and codes.  One streaming pass. */
+int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                              apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp4 — C[M, N] (bf16, row stride ldc) = epi(sum_k a[m, k] 2^(sa[m, k / 32] - 127) w[n, k] 2^(sw[n, k / 32] - 127) + bias[n]):
+ * e2m1 x e2m1 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, nothing is multiplied after the K-loop.
+ * qa [M, K / 2], qw [N, K / 2] codes (row strides lda, ldw in bytes, multiples of 16, 16-byte aligned); sa [M, K / 32], sw [N, K / 32]
+ * scale bytes (row strides ldsa, ldsw bytes, multiples of 4, 4-byte aligned).  bias, gate, R and the three epilogues
+ * (APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU, APEXMI_EPI_BIAS_GATE_RES; R may alias C) as apexmi_gemm_fp8.  K % 256 == 0, N % 16 == 0,
+ * M >= 1.  Every argument is checked before the launch. */
+int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
+                      int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue, const float* gate,
+                      const void* R, int64_t ldr, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
