@@ -196,6 +196,11 @@ APEXMI_DEVICE void glds16(const void* gsrc, void* lds) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
                                      (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
 }
+// the 4-byte form: LDS destination is wave-uniform `lds` + lane*4
+APEXMI_DEVICE void glds4(const void* gsrc, void* lds) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
+                                     (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
+}
 
 // bijective XCD-aware remap of a 1-D block id: workgroup b is observed to run on XCD b % 8;
 // give each XCD a contiguous chunk of the logical tile list so neighbours share its L2.

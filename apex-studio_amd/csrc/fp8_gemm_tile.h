@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "fp8_quant.h"   // the MX output of the epilogue
+#include <type_traits>
 
 namespace {
 
@@ -33,6 +34,87 @@ struct Fp8Problem {
     uint8_t* QS;          // MX output block scales [M, N / 32]
     int64_t ldabs, ldq, ldqs;
 };
+
+// ---- tile front end: what every form of both kernels does before and around its K-loop ----
+// XCD-grouped tile order: each XCD takes a contiguous run of tile ids `t` (xcd_remap; of one problem); inside a run, bands of 8 tile
+// rows are walked column by column, so a band shares its weight tiles.  ops.fp8_grouped_tiles restates this walk.
+APEXMI_DEVICE void fp8_tile_origin(int t, int tiles_m, int tiles_n, int& m0, int& n0) {
+    const int band = 8 * tiles_n, first_m = (t / band) * 8;
+    const int gsz = min(tiles_m - first_m, 8);
+    m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
+}
+
+// Staging layout: lds[buf][operand][row 0..127][128 bytes].  Wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 whole
+// rows per instruction (64 lanes x 16 bytes, lane-linear), and the XOR swizzle is on the SOURCE address: 16-byte piece c of row r
+// holds the row's bytes 16 (c ^ ((r >> 1) & 7)) .., so the 16 lanes of one ds_read_b128 phase cover all 64 banks once.
+// fp8_stage_src: what this lane copies in instruction i of a K-tile = its row (tile rows past `rows` clamp to the last one) and
+// its swizzled piece of that row's first 128 bytes; `ld` in elements of T.
+template <class T>
+APEXMI_DEVICE const char* fp8_stage_src(const T* base, int64_t ld, int row0, int rows, int wid, int lane, int i) {
+    const int r = 32 * wid + 8 * i + (lane >> 3);
+    const int c = (lane & 7) ^ ((r >> 1) & 7);
+    return (const char*)(base + (int64_t)min(row0 + r, rows - 1) * ld) + c * 16;
+}
+// the wave's destination of instruction 0 (wave-uniform; the hardware adds lane * 16); instruction i is 8 i rows further, the weight
+// tile FOPB behind the activation tile
+APEXMI_DEVICE uint8_t* fp8_stage_dst(uint8_t* lds, int buf, int wid) { return lds + buf * 2 * FOPB + (32 * wid) * FBK; }
+
+// the eight source pointers of a K-loop over A [M, K] and W [N, K] (bytes); the call issues K-tile kt into lds[buf]
+struct Fp8Stager {
+    const char* a_src[4];
+    const char* w_src[4];
+    APEXMI_DEVICE Fp8Stager(const Fp8Problem& P, int m0, int n0, int wid, int lane) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a_src[i] = fp8_stage_src(P.A, P.lda, m0, P.M, wid, lane, i);
+            w_src[i] = fp8_stage_src(P.W, P.ldw, n0, P.N, wid, lane, i);
+        }
+    }
+    APEXMI_DEVICE void operator()(uint8_t* lds, int wid, int kt, int buf) const {
+        uint8_t* da = fp8_stage_dst(lds, buf, wid);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            glds16(a_src[i] + (int64_t)kt * FBK, da + 8 * i * FBK);
+            glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
+        }
+    }
+};
+
+// the swizzled 16-byte piece `piece` of row `row` of a staged tile
+APEXMI_DEVICE u32x4 lds_piece(const uint8_t* tile, int row, int piece) {
+    return *(const u32x4*)(tile + row * FBK + ((piece ^ ((row >> 1) & 7)) << 4));
+}
+
+// the live clock probe (apexmi_clk_ptr; `clk` null = off, kernel-uniform): cycles and real time from start() to stop(), summed
+// over the launch's workgroups
+struct Fp8Clock {
+    unsigned long long c0 = 0, r0 = 0;
+    APEXMI_DEVICE void start(const unsigned long long* clk) {
+        if (clk != nullptr) {
+            c0 = __builtin_readcyclecounter();
+            r0 = __builtin_amdgcn_s_memrealtime();
+        }
+    }
+    APEXMI_DEVICE void stop(unsigned long long* clk, int tid) const {
+        if (clk != nullptr) {
+            const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
+            if (tid == 0) {
+                atomicAdd(clk, c1 - c0);
+                atomicAdd(clk + 1, r1 - r0);
+            }
+        }
+    }
+};
+
+// acc[weight tile (output columns)][activation tile (output rows)] = 0
+APEXMI_DEVICE void fp8_zero_acc(f32x16 (&acc)[2][2]) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
 
 // the weight scales / the bias of the 4 columns n .. n + 3 (n clamped by the caller; a null bias is 0)
 APEXMI_DEVICE void fp8_unpack4(const u32x2 v, float (&f)[4]) { f[0] = bf16_lo(v[0]), f[1] = bf16_hi(v[0]), f[2] = bf16_lo(v[1]), f[3] = bf16_hi(v[1]); }
@@ -135,6 +217,82 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
                 }
             }
         }
+    }
+}
+
+// ---- host side: the checks of ONE problem that do not depend on the operand format, and the launch by epilogue ----
+// how the messages name a problem: `i` = its index in a grouped launch, or -1 for a single launch (every fragment empty)
+struct Fp8Where {
+    char of[32] = "", paren[32] = "", colon[32] = "", semi[32] = "";
+    explicit Fp8Where(int i) {
+        if (i < 0) return;
+        snprintf(of, sizeof(of), " of problem %d", i);
+        snprintf(paren, sizeof(paren), " (problem %d)", i);
+        snprintf(colon, sizeof(colon), "problem %d: ", i);
+        snprintf(semi, sizeof(semi), "; problem %d", i);
+    }
+};
+
+// what differs between the formats, in the rules and in the wording of the messages (passed through as the entry points word them)
+struct Fp8Format {
+    int k_tile;              // codes of one K-tile (128 bytes of a row): K is a multiple of it
+    const char* k_note;      // what follows "must be a multiple of <k_tile>"
+    int codes_per_byte;      // 1 (e4m3) or 2 (e2m1): a code row is K / codes_per_byte bytes
+    const char* ld_note;     // what follows "must keep rows 16-byte aligned"
+    const char* ld_unit;     // the unit of the 2^22 bound
+    bool scales_aligned;     // the alignment of the format's own scale operands
+    const char* align_note;  // the parenthesis of the alignment message
+};
+
+// M, N, K, the epilogue, the leading dimensions, the alignment of A / W / C / bias / gate / R and the tile count (tile0 = the tiles
+// of the problems before this one); then the operand record with sa / sw / the MX members left null
+static int fp8_check_tile_problem(const char* who, const Fp8Where& at, const Fp8Format& f, int64_t tile0, const void* qa, int64_t lda,
+                                  const void* qw, int64_t ldw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
+                                  const float* gate, const void* R, int64_t ldr, Fp8Problem* P) {
+    APEXMI_REQUIRE(M >= 1, "%s: M=%d%s must be at least 1", who, M, at.of);
+    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "%s: N=%d%s must be a multiple of 16", who, N, at.of);
+    APEXMI_REQUIRE(K >= f.k_tile && K % f.k_tile == 0, "%s: K=%d must be a multiple of %d%s", who, K, f.k_tile, f.k_note);
+    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
+                   "%s: f32 output (epilogue %d%s, the f32 residual stream) is not supported: the output is bf16", who, epilogue, at.of);
+    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
+                   "%s: epilogue %d%s is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue, at.of);
+    const int kb = K / f.codes_per_byte;
+    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= kb && ldw >= kb && ldc >= N,
+                   "%s: leading dimensions must keep rows 16-byte aligned%s (%slda %lld, ldw %lld, ldc %lld)", who, f.ld_note, at.colon,
+                   (long long)lda, (long long)ldw, (long long)ldc);
+    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22), "%s: leading dimensions above 2^22 %s are not supported (%slda %lld, ldw %lld)",
+                   who, f.ld_unit, at.colon, (long long)lda, (long long)ldw);
+    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && f.scales_aligned &&
+                       ((uintptr_t)bias % 8) == 0,
+                   "%s: operands must be 16-byte aligned (%s)", who, f.align_note);
+    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
+        APEXMI_REQUIRE(gate && R, "%s: gate/residual epilogue needs gate and R%s", who, at.paren);
+        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "%s: gate/R alignment%s", who,
+                       at.paren);
+    }
+    const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
+    APEXMI_REQUIRE(tile0 + (int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
+    *P = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, nullptr, nullptr, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
+                    lda, ldw, ldc, ldr, M, N, K, 0, tm, tn};
+    return 0;
+}
+
+// One launch of 256 threads per tile with the kernel chosen by the epilogue.  kernel_of(std::integral_constant<int, EPI>) returns
+// the instantiation; dyn_lds > 0 = that much dynamic LDS, raised above the default limit once per device and instantiation.
+template <class KernelOf, class Args>
+static void launch_by_epilogue(int epilogue, KernelOf kernel_of, const Args& G, unsigned tiles, int dyn_lds, hipStream_t stream) {
+    auto launch = [&](auto epi) {
+        auto kernel = kernel_of(epi);
+        if (dyn_lds > 0) {
+            static uint64_t attr_set = 0;       // one per instantiation of this lambda = per kernel
+            APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn_lds));
+        }
+        hipLaunchKernelGGL(kernel, dim3(tiles), dim3(256), dyn_lds, stream, G);
+    };
+    switch (epilogue) {
+        case APEXMI_EPI_BIAS: launch(std::integral_constant<int, APEXMI_EPI_BIAS>{}); break;
+        case APEXMI_EPI_BIAS_GELU: launch(std::integral_constant<int, APEXMI_EPI_BIAS_GELU>{}); break;
+        default: launch(std::integral_constant<int, APEXMI_EPI_BIAS_GATE_RES>{}); break;
     }
 }
 

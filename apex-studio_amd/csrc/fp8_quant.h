@@ -8,6 +8,17 @@ namespace {
 
 constexpr float FP8_MAX = 448.0f;        // largest finite e4m3fn value
 
+// max |x| over 16 bf16 values (8 dwords): what one lane of every quantiser here holds per step
+APEXMI_DEVICE float absmax16(const u32x4 a, const u32x4 b) {
+    float m = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(a[i])), fabsf(bf16_hi(a[i]))));
+        m = fmaxf(m, fmaxf(fabsf(bf16_lo(b[i])), fabsf(bf16_hi(b[i]))));
+    }
+    return m;
+}
+
 APEXMI_DEVICE float quant1(float x, float scale) {
     const float y = __fdiv_rn(x, scale);
     return fminf(fmaxf(y, -FP8_MAX), FP8_MAX);

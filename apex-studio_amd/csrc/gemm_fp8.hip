@@ -17,16 +17,6 @@ namespace {
 // the last one may be partial in whole 16-element groups.
 //   scale = absmax == 0 ? 1 : absmax / 448         (IEEE f32 division)
 //   code  = e4m3fn_rne(min(max(x / scale, -448), 448))   (IEEE f32 division, round to nearest even, subnormals kept)
-APEXMI_DEVICE float absmax16(const u32x4 a, const u32x4 b) {
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        m = fmaxf(m, fmaxf(fabsf(bf16_lo(a[i])), fabsf(bf16_hi(a[i]))));
-        m = fmaxf(m, fmaxf(fabsf(bf16_lo(b[i])), fabsf(bf16_hi(b[i]))));
-    }
-    return m;
-}
-
 __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __restrict__ a, int64_t lda, int M, int K,
                                                              uint8_t* __restrict__ q, int64_t ldq, float* __restrict__ scales) {
     const int lane = threadIdx.x & 63;
@@ -62,7 +52,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
     }
 }
 
-#include "quant_blocks_mxfp8.inc"   // apexmi_quant_blocks_mxfp8's streaming kernel (uses absmax16 above)
+#include "quant_blocks_mxfp8.inc"   // apexmi_quant_blocks_mxfp8's streaming kernel
 
 // ---- apexmi_gemm_fp8 ----------------------------------------------------------------------------------------------------------
 // 128 x 128 output tile, K-tile of 128 codes, 256 threads = 2 x 2 waves of 64 x 64 (2 x 2 MFMA tiles of 32 x 32, 64 accumulator
@@ -139,13 +129,6 @@ struct Fp8LoraGroup : Fp8Group {
     Fp8LoraEntry lora[FP8_MAX_GROUPS];
 };
 
-APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
-    const int sw = (row >> 1) & 7;
-    const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece ^ sw) << 4));
-    const u32x4 hi = *(const u32x4*)(tile + row * FBK + (((piece + 1) ^ sw) << 4));
-    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
-
 // The fragment of a BLOCK-SCALED k-step (the MX instantiations, problems with `abs`).  The instruction's two scale blocks are not
 // the two lane halves: block 0 = registers 0..3 of BOTH halves, scaled by byte 0 (op-sel 0) of lane l & 31's scale register, block
 // 1 = registers 4..7 of both halves, scaled by lane 32 + (l & 31)'s (measured with one-hot operands and a lane / byte code in the
@@ -153,16 +136,16 @@ APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) {
 // agree, so for these problems BOTH operands put the step's memory block b (32 codes) into scale block b: lane half h holds codes
 // 16 h + 0..15 of block 0 in registers 0..3 and codes 16 h + 0..15 of block 1 in registers 4..7 = 16-byte pieces h and 2 + h.
 APEXMI_DEVICE i32x8 lds_frag_blocks(const uint8_t* tile, int row, int piece0, int piece1) {
-    const int sw = (row >> 1) & 7;
-    const u32x4 lo = *(const u32x4*)(tile + row * FBK + ((piece0 ^ sw) << 4));
-    const u32x4 hi = *(const u32x4*)(tile + row * FBK + ((piece1 ^ sw) << 4));
+    const u32x4 lo = lds_piece(tile, row, piece0), hi = lds_piece(tile, row, piece1);
     return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
+// the fragment of a unit-scale k-step: the lane's 32 consecutive codes = pieces `piece` and `piece` + 1
+APEXMI_DEVICE i32x8 lds_frag(const uint8_t* tile, int row, int piece) { return lds_frag_blocks(tile, row, piece, piece + 1); }
 
 // a 16-byte piece of a staged tile as the operand of one v_mfma_f32_32x32x16_bf16 k-step: lane l holds the 8 bf16 k = 8 (l >> 5) + 0..7
 // of row (A) / column (B) l & 31 (gemm.hip's fragment reads), so k-step ks of a 64-wide rank tile is piece 2 ks + (l >> 5)
 APEXMI_DEVICE bf16x8 lds_frag16(const uint8_t* tile, int row, int piece) {
-    return *(const bf16x8*)(tile + row * FBK + ((piece ^ ((row >> 1) & 7)) << 4));
+    return __builtin_bit_cast(bf16x8, lds_piece(tile, row, piece));
 }
 
 // this workgroup's tile id `t` inside its problem, and the problem (index `pi`): the launch itself, or the table entry found by the
@@ -326,60 +309,32 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
 
-    // XCD-grouped tile order: each XCD takes a contiguous run of tiles; inside a run (of one problem), bands of 8 tile rows share
-    // the weight tiles
-    int t, pi;
+    int t, pi, m0, n0;
     const auto& P = fp8_problem(G, t, pi);
     [[maybe_unused]] const auto& L = fp8_lora_entry(G, pi);     // LORA: the adapter operands; Rp == 0 (grouped) = none, block-uniform
-    const int band = 8 * P.tiles_n, first_m = (t / band) * 8;
-    const int gsz = min(P.tiles_m - first_m, 8);
-    const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
+    fp8_tile_origin(t, P.tiles_m, P.tiles_n, m0, n0);
 
-    // staging: wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 rows per instruction
-    const char* a_src[4];
-    const char* w_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 32 * wid + 8 * i + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        a_src[i] = (const char*)(P.A + (int64_t)min(m0 + r, P.M - 1) * P.lda + c * 16);
-        w_src[i] = (const char*)(P.W + (int64_t)min(n0 + r, P.N - 1) * P.ldw + c * 16);
-    }
-    auto stage = [&](int kt, int buf) {
-        uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;     // wave-uniform; the hardware adds lane * 16
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(a_src[i] + (int64_t)kt * FBK, da + 8 * i * FBK);
-            glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
-        }
-    };
-    auto stage_rank = [&](int rt, int buf) {     // LORA: rank tile rt of t (rows) and B' (columns), same rows, pieces and swizzle
+    const Fp8Stager stage_codes(P, m0, n0, wid, lane);
+    auto stage = [&](int kt, int buf) { stage_codes(lds, wid, kt, buf); };
+    // LORA: rank tile rt of t (rows) and B' (columns), same rows, pieces and swizzle; the addresses are computed here, at the point of
+    // use, so that no pointer is held across the K-loop
+    auto stage_rank = [&](int rt, int buf) {
         if constexpr (LORA) {
             if (GROUPED && L.Rp == 0) return;
-            uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;
+            uint8_t* da = fp8_stage_dst(lds, buf, wid);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int r = 32 * wid + 8 * i + (lane >> 3);
-                const int c = (lane & 7) ^ ((r >> 1) & 7);
-                glds16((const char*)(L.T + (int64_t)min(m0 + r, P.M - 1) * L.ldt) + c * 16 + rt * FBK, da + 8 * i * FBK);
-                glds16((const char*)(L.LB + (int64_t)min(n0 + r, P.N - 1) * L.ldb) + c * 16 + rt * FBK, da + FOPB + 8 * i * FBK);
+                glds16(fp8_stage_src(L.T, L.ldt, m0, P.M, wid, lane, i) + rt * FBK, da + 8 * i * FBK);
+                glds16(fp8_stage_src(L.LB, L.ldb, n0, P.N, wid, lane, i) + rt * FBK, da + FOPB + 8 * i * FBK);
             }
         }
     };
 
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (G.clk != nullptr) {          // kernel-uniform
-        clk_c0 = __builtin_readcyclecounter();
-        clk_r0 = __builtin_amdgcn_s_memrealtime();
-    }
+    Fp8Clock clock;
+    clock.start(G.clk);
 
     f32x16 acc[2][2];                 // [weight tile (output columns)][activation tile (output rows)]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    fp8_zero_acc(acc);
 
     const int nk = P.K / FBK;
     const int fr = lane & 31, fh = lane >> 5;
@@ -511,13 +466,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Args G) {
         }
     }
 
-    if (G.clk != nullptr) {
-        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            atomicAdd(G.clk, c1 - clk_c0);
-            atomicAdd(G.clk + 1, r1 - clk_r0);
-        }
-    }
+    clock.stop(G.clk, tid);
 
     if constexpr (MX) {
         // block-uniform choices: bf16 or MX out; the epilogue of a grouped problem by its table entry
@@ -596,44 +545,23 @@ struct Fp8MxOperands {
 };
 
 // ONE problem of any entry point: every check, then its operand record.  `who` = the entry point's name; `i` = the problem's index
-// in a grouped launch, which the messages name, or -1 for a single launch; tile0 = the tiles of the problems before it.
+// in a grouped launch, which the messages name, or -1 for a single launch; tile0 = the tiles of the problems before it.  The e4m3
+// rules stand here (weight format, scale kinds and counts, the MX operands), the rest in fp8_check_tile_problem.
 static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const float* sa, const void* qw,
                              int64_t ldw, int w_format, const void* sw, int64_t sw_count, const void* bias, void* C, int64_t ldc, int M,
                              int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Fp8Problem* P, const Fp8MxOperands* mx = nullptr) {
-    char of[32] = "", paren[32] = "", colon[32] = "", semi[32] = "";
-    if (i >= 0) {
-        snprintf(of, sizeof(of), " of problem %d", i);
-        snprintf(paren, sizeof(paren), " (problem %d)", i);
-        snprintf(colon, sizeof(colon), "problem %d: ", i);
-        snprintf(semi, sizeof(semi), "; problem %d", i);
-    }
+    const Fp8Where at(i);
+    const char *of = at.of, *paren = at.paren;
     const bool blk = mx != nullptr && mx->abs != nullptr, mxo = mx != nullptr && (mx->Q != nullptr || mx->QS != nullptr);
     APEXMI_REQUIRE(qa && (sa || blk) && qw && sw && (C || mxo), "%s: null operand%s", who, paren);
     APEXMI_REQUIRE(!(sa && blk), "%s: row scales and block scales were both given%s: an activation carries one kind", who, paren);
     APEXMI_REQUIRE(w_format == 0, "%s: weight format %d%s is not e4m3fn (0): e5m2 weights take the bf16 path "
                                   "(apexmi_dequant_fp8_scaled + apexmi_gemm_bf16%s)", who, w_format, of, i >= 0 ? "_grouped" : "");
-    APEXMI_REQUIRE(M >= 1, "%s: M=%d%s must be at least 1", who, M, of);
-    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "%s: N=%d%s must be a multiple of 16", who, N, of);
-    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "%s: K=%d must be a multiple of 128", who, K);
-    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
-                   "%s: f32 output (epilogue %d%s, the f32 residual stream) is not supported: the output is bf16", who, epilogue, of);
-    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
-                   "%s: epilogue %d%s is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue, of);
     APEXMI_REQUIRE(sw_count == 1 || sw_count == N, "%s: the weight scale%s has %lld values for N=%d rows", who, of, (long long)sw_count, N);
-    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K && ldw >= K && ldc >= N,
-                   "%s: leading dimensions must keep rows 16-byte aligned (%slda %lld, ldw %lld, ldc %lld)", who, colon, (long long)lda,
-                   (long long)ldw, (long long)ldc);
-    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22), "%s: leading dimensions above 2^22 elements are not supported (%slda %lld, ldw %lld)",
-                   who, colon, (long long)lda, (long long)ldw);
-    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)sa % 4) == 0 &&
-                       ((uintptr_t)sw % (sw_count == 1 ? 2 : 8)) == 0 && ((uintptr_t)bias % 8) == 0,
-                   "%s: operands must be 16-byte aligned (scales and bias 8-byte%s)", who, semi);
-    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
-        APEXMI_REQUIRE(gate && R, "%s: gate/residual epilogue needs gate and R%s", who, paren);
-        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "%s: gate/R alignment%s", who, paren);
-    }
-    const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
-    APEXMI_REQUIRE(tile0 + (int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
+    char align_note[64];
+    snprintf(align_note, sizeof(align_note), "scales and bias 8-byte%s", at.semi);
+    const Fp8Format e4m3{128, "", 1, "", "elements", ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % (sw_count == 1 ? 2 : 8)) == 0, align_note};
+    if (fp8_check_tile_problem(who, at, e4m3, tile0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, P)) return 1;
     if (blk)
         APEXMI_REQUIRE(mx->ldabs >= K / 32 && mx->ldabs % 4 == 0 && ((uintptr_t)mx->abs % 4) == 0,
                        "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldabs %lld)", who, of, K / 32,
@@ -647,8 +575,7 @@ static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* 
                        "%s: the MX output%s needs 4-byte aligned code rows at least N wide and scale rows at least N / 32 wide "
                        "(ldq %lld, ldqs %lld)", who, of, (long long)mx->ldq, (long long)mx->ldqs);
     }
-    *P = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, sa, (const bf16_t*)sw, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
-                    lda, ldw, ldc, ldr, M, N, K, sw_count == 1 ? 0 : 1, tm, tn};
+    P->sa = sa, P->sw = (const bf16_t*)sw, P->sw_rows = sw_count == 1 ? 0 : 1;
     if (blk) P->abs = (const uint8_t*)mx->abs, P->ldabs = mx->ldabs;
     if (mxo) P->Q = (uint8_t*)mx->Q, P->QS = (uint8_t*)mx->QS, P->ldq = mx->ldq, P->ldqs = mx->ldqs;
     return 0;
@@ -657,12 +584,8 @@ static int fp8_check_problem(const char* who, int i, int64_t tile0, const void* 
 // a single launch of the kernel form that takes `Args`, with its compile-time epilogue
 template <class Args>
 static void fp8_launch(int epilogue, const Args& G, hipStream_t stream) {
-    const dim3 grid((unsigned)(G.tiles_m * G.tiles_n));
-    switch (epilogue) {
-        case APEXMI_EPI_BIAS: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS, Args>), grid, dim3(256), 0, stream, G); break;
-        case APEXMI_EPI_BIAS_GELU: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GELU, Args>), grid, dim3(256), 0, stream, G); break;
-        default: hipLaunchKernelGGL((gemm_fp8_kernel<APEXMI_EPI_BIAS_GATE_RES, Args>), grid, dim3(256), 0, stream, G); break;
-    }
+    launch_by_epilogue(epilogue, [](auto epi) { constexpr int EPI = decltype(epi)::value; return gemm_fp8_kernel<EPI, Args>; }, G,
+                       (unsigned)(G.tiles_m * G.tiles_n), 0, stream);
 }
 
 // both single entry points: every check before any launch; lora = the adapter operands of apexmi_gemm_fp8_lora, or null for apexmi_gemm_fp8

@@ -22,12 +22,7 @@ __global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(const bf16_t* _
     const bool live = row < M;
     const bf16_t* p = a + (live ? row : (int64_t)M - 1) * lda + k;
     const u32x4 x0 = *(const u32x4*)p, x1 = *(const u32x4*)(p + 8);
-    float m = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        m = fmaxf(m, fmaxf(fabsf(bf16_lo(x0[i])), fabsf(bf16_hi(x0[i]))));
-        m = fmaxf(m, fmaxf(fabsf(bf16_lo(x1[i])), fabsf(bf16_hi(x1[i]))));
-    }
+    float m = absmax16(x0, x1);
     m = fmaxf(m, __shfl_xor(m, 1, 64));
     const int sb = mx4_scale_byte(m);
     const float inv = mx_inv_scale(sb);
@@ -62,11 +57,6 @@ struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda 
     unsigned long long* clk;
 };
 
-APEXMI_DEVICE void glds4(const void* gsrc, void* lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds, 4, 0, 0);
-}
-
 // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
@@ -74,48 +64,25 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
 
-    int t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
-    const int band = 8 * G.tiles_n, first_m = (t / band) * 8;
-    const int gsz = min(G.tiles_m - first_m, 8);
-    const int m0 = (first_m + (t % band) % gsz) * FBM, n0 = ((t % band) / gsz) * FBN;
+    int m0, n0;
+    fp8_tile_origin(xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n), G.tiles_m, G.tiles_n, m0, n0);
 
-    // staging: wave w writes rows 32 w .. 32 w + 31 of both operand tiles, 8 rows per instruction; thread t one scale dword per operand
-    const char* a_src[4];
-    const char* w_src[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = 32 * wid + 8 * i + (lane >> 3);
-        const int c = (lane & 7) ^ ((r >> 1) & 7);
-        a_src[i] = (const char*)(G.A + (int64_t)min(m0 + r, G.M - 1) * G.lda + c * 16);
-        w_src[i] = (const char*)(G.W + (int64_t)min(n0 + r, G.N - 1) * G.ldw + c * 16);
-    }
+    // staging: the codes as in gemm_fp8_kernel; thread t adds one scale dword per operand
+    const Fp8Stager stage_codes(G, m0, n0, wid, lane);
     const char* sa_src = (const char*)(G.SA + (int64_t)min(m0 + (tid >> 1), G.M - 1) * G.ldsa + (tid & 1) * 4);
     const char* sw_src = (const char*)(G.SW + (int64_t)min(n0 + (tid >> 1), G.N - 1) * G.ldsw + (tid & 1) * 4);
     auto stage = [&](int kt, int buf) {
-        uint8_t* da = lds + buf * 2 * FOPB + (32 * wid) * FBK;     // wave-uniform; the hardware adds lane * 16
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            glds16(a_src[i] + (int64_t)kt * FBK, da + 8 * i * FBK);
-            glds16(w_src[i] + (int64_t)kt * FBK, da + FOPB + 8 * i * FBK);
-        }
+        stage_codes(lds, wid, kt, buf);
         uint8_t* ds = lds + 4 * FOPB + buf * 2 * X4_SCB + wid * 256;   // wave-uniform; the hardware adds lane * 4
         glds4(sa_src + kt * 8, ds);
         glds4(sw_src + kt * 8, ds + X4_SCB);
     };
 
-    unsigned long long clk_c0 = 0, clk_r0 = 0;
-    if (G.clk != nullptr) {          // kernel-uniform
-        clk_c0 = __builtin_readcyclecounter();
-        clk_r0 = __builtin_amdgcn_s_memrealtime();
-    }
+    Fp8Clock clock;
+    clock.start(G.clk);
 
     f32x16 acc[2][2];                 // [weight tile (output columns)][activation tile (output rows)]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    fp8_zero_acc(acc);
 
     const int nk = G.K / (2 * FBK);
     const int fr = lane & 31, fh = lane >> 5;
@@ -143,9 +110,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
             int ea[2], ew[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int ra = 64 * wr + 32 * i + fr, rw = 64 * wc + 32 * i + fr;
-                const u32x4 pa = *(const u32x4*)(ta + ra * FBK + ((piece ^ ((ra >> 1) & 7)) << 4));
-                const u32x4 pw = *(const u32x4*)(tw + rw * FBK + ((piece ^ ((rw >> 1) & 7)) << 4));
+                const u32x4 pa = lds_piece(ta, 64 * wr + 32 * i + fr, piece), pw = lds_piece(tw, 64 * wc + 32 * i + fr, piece);
                 fa[i] = i32x8{(int)pa[0], (int)pa[1], (int)pa[2], (int)pa[3], 0, 0, 0, 0};
                 fw[i] = i32x8{(int)pw[0], (int)pw[1], (int)pw[2], (int)pw[3], 0, 0, 0, 0};
                 ea[i] = (int)(xa[i][ks >> 1] >> shift);
@@ -160,13 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
         __syncthreads();
     }
 
-    if (G.clk != nullptr) {
-        const unsigned long long c1 = __builtin_readcyclecounter(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            atomicAdd(G.clk, c1 - clk_c0);
-            atomicAdd(G.clk + 1, r1 - clk_r0);
-        }
-    }
+    clock.stop(G.clk, tid);
     fp8_epilogue<EPI, false>(acc, G, m0, n0, wr, wc, fr, fh);
 }
 
@@ -191,53 +150,25 @@ extern "C" int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int 
     return apexmi_check_launch("quant_blocks_mxfp4");
 }
 
-template <int EPI>
-static void mxfp4_launch(const Mxfp4Gemm& G, hipStream_t stream) {
-    static uint64_t attr_set = 0;       // 68 KB of dynamic LDS is above the default limit
-    APEXMI_SET_ATTR_ONCE(attr_set,
-        (void)hipFuncSetAttribute((const void*)gemm_mxfp4_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
-    hipLaunchKernelGGL(gemm_mxfp4_kernel<EPI>, dim3((unsigned)(G.tiles_m * G.tiles_n)), dim3(256), X4_LDS, stream, G);
-}
-
 extern "C" int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
                                  int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                                  const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const char* who = "gemm_mxfp4";
     APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand", who);
-    APEXMI_REQUIRE(M >= 1, "%s: M=%d must be at least 1", who, M);
-    APEXMI_REQUIRE(N >= 16 && N % 16 == 0, "%s: N=%d must be a multiple of 16", who, N);
-    APEXMI_REQUIRE(K >= 256 && K % 256 == 0, "%s: K=%d must be a multiple of 256 (a K-tile is 128 bytes of e2m1 codes)", who, K);
-    APEXMI_REQUIRE((epilogue & APEXMI_EPI_F32_IO) == 0 && epilogue != APEXMI_EPI_BIAS_F32,
-                   "%s: f32 output (epilogue %d, the f32 residual stream) is not supported: the output is bf16", who, epilogue);
-    APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
-                   "%s: epilogue %d is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue);
-    APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= K / 2 && ldw >= K / 2 && ldc >= N,
-                   "%s: leading dimensions must keep rows 16-byte aligned, code rows at least K / 2 = %d bytes (lda %lld, ldw %lld, ldc "
-                   "%lld)", who, K / 2, (long long)lda, (long long)ldw, (long long)ldc);
-    APEXMI_REQUIRE(lda <= (1 << 22) && ldw <= (1 << 22), "%s: leading dimensions above 2^22 bytes are not supported (lda %lld, ldw %lld)",
-                   who, (long long)lda, (long long)ldw);
+    char ld_note[64];
+    snprintf(ld_note, sizeof(ld_note), ", code rows at least K / 2 = %d bytes", K / 2);
+    const Fp8Format e2m1{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ld_note, "bytes", true, "output and bias 8-byte"};
+    Mxfp4Gemm G{};
+    if (fp8_check_tile_problem(who, Fp8Where(-1), e2m1, 0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
     APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
                    "%s: the block scales must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, K / 32,
                    (long long)ldsa, (long long)ldsw);
-    APEXMI_REQUIRE(((uintptr_t)qa % 16) == 0 && ((uintptr_t)qw % 16) == 0 && ((uintptr_t)C % 8) == 0 && ((uintptr_t)bias % 8) == 0,
-                   "%s: operands must be 16-byte aligned (output and bias 8-byte)", who);
-    if (epilogue == APEXMI_EPI_BIAS_GATE_RES) {
-        APEXMI_REQUIRE(gate && R, "%s: gate/residual epilogue needs gate and R", who);
-        APEXMI_REQUIRE(ldr % 4 == 0 && ldr >= N && ((uintptr_t)gate % 16) == 0 && ((uintptr_t)R % 8) == 0, "%s: gate/R alignment", who);
-    }
-    const int tm = (M + FBM - 1) / FBM, tn = (N + FBN - 1) / FBN;
-    APEXMI_REQUIRE((int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
-    Mxfp4Gemm G{};
-    (Fp8Problem&)G = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, nullptr, nullptr, (const bf16_t*)bias, (bf16_t*)C, gate,
-                                (const bf16_t*)R, lda, ldw, ldc, ldr, M, N, K, 0, tm, tn};
     G.SA = (const uint8_t*)sa, G.SW = (const uint8_t*)sw, G.ldsa = ldsa, G.ldsw = ldsw;
     G.clk = apexmi_clk_ptr();
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * ((double)M + N) * K + 2.0 * (double)M * N);
-    switch (epilogue) {
-        case APEXMI_EPI_BIAS: mxfp4_launch<APEXMI_EPI_BIAS>(G, stream); break;
-        case APEXMI_EPI_BIAS_GELU: mxfp4_launch<APEXMI_EPI_BIAS_GELU>(G, stream); break;
-        default: mxfp4_launch<APEXMI_EPI_BIAS_GATE_RES>(G, stream); break;
-    }
+    // 68 KB of dynamic LDS is above the default limit
+    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp4_kernel<decltype(epi)::value>; }, G, (unsigned)(G.tiles_m * G.tiles_n),
+                       X4_LDS, stream);
     return apexmi_check_launch(who);
 }

@@ -1,5 +1,5 @@
 // The streaming kernel of apexmi_quant_blocks_mxfp8 (DESIGN.md §3.6), included by gemm_fp8.hip inside its anonymous namespace, after
-// absmax16 and fp8_quant.h.  It is a file of its own because gemm_fp8.hip's `__global__` list is pinned to gemm_fp8_kernel and
+// fp8_quant.h (absmax16, the MX block quantiser).  It is a file of its own because gemm_fp8.hip's `__global__` list is pinned to gemm_fp8_kernel and
 // quant_rows_fp8_kernel (tests/test_gemm_fp8_lora_host.py): that pin guarantees that every GEMM form — LoRA, grouped, fused q/k/v,
 // MX — is an instantiation of the ONE kernel the build's no-spill list names, never a second GEMM kernel beside it.  This kernel
 // is a streaming pass with no MFMA, so the guarantee does not concern it; the build digest covers `.inc` files.

@@ -323,13 +323,21 @@ def _fp8_of(w):
     return w if isinstance(w, ResidentWeight) else getattr(w, "_fp8", None)
 
 
-def _scratch(dev, n: int) -> torch.Tensor:
+def _stream_scratch(store: dict, dev, *wants):
+    """The current stream's buffers in `store`, one flat buffer per (numel, dtype) of `wants`, each replaced by a larger one when it
+    holds fewer elements than asked (grow-only).  Stream order makes the reuse safe: the next writer is queued behind the last
+    reader.  Every store is a dict of its own: what lives in one is not overwritten by a request to another."""
     key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    buf = _fp8_scratch.get(key)
-    if buf is None or buf.numel() < n:
-        buf = torch.empty(n, dtype=torch.bfloat16, device=dev)
-        _fp8_scratch[key] = buf
-    return buf
+    bufs = list(store.get(key, (None,) * len(wants)))
+    for i, (n, dtype) in enumerate(wants):
+        if bufs[i] is None or bufs[i].numel() < n:
+            bufs[i] = torch.empty(n, dtype=dtype, device=dev)
+    store[key] = tuple(bufs)
+    return bufs
+
+
+def _scratch(dev, n: int) -> torch.Tensor:
+    return _stream_scratch(_fp8_scratch, dev, (n, torch.bfloat16))[0]
 
 
 def _is_lora_buf(a, f8: "ResidentWeight", lora_buf) -> bool:
@@ -382,6 +390,22 @@ def _bf16_weight(w, float_acts: bool = False):
 _FP8_EPI = ("bias", "gelu", "gate_res")
 
 
+def _block_gemm_route(a: torch.Tensor, w_shape, out: Optional[torch.Tensor], epilogue: str, k_mult: int,
+                      max_row_stride: Optional[int] = None) -> bool:
+    """The rules every route onto a block-scaled-MFMA GEMM shares (`fp8_compute_route`, `fp8_lora_route`, `mxfp4_route`; each asks
+    its own question about the weight record first).  Pure.  `a` bf16 and `out` bf16 or None; `a` 2-D with contiguous rows; the
+    epilogue one of bias / gelu / gate_res; M >= 1, K the record's K = `w_shape[1]` and a multiple of `k_mult` (the codes of one
+    K-tile), N = `w_shape[0]` a multiple of 16; 16-byte rows of `a`, with a row stride of at most `max_row_stride` where given."""
+    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
+        return False
+    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
+        return False
+    M, K = a.shape
+    N = w_shape[0]
+    return M >= 1 and K == w_shape[1] and K % k_mult == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 \
+        and (max_row_stride is None or a.stride(0) <= max_row_stride)
+
+
 def fp8_compute_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
     """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as quantise + `gemm_fp8`.  Pure: reads dtypes, shapes and strides
     only (CPU tensors are fine).  True only when ALL of these hold:
@@ -394,13 +418,7 @@ def fp8_compute_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, ep
     f8 = _fp8_of(w)
     if not isinstance(f8, Fp8Weight) or f8.compute != "fp8" or f8.q.dtype != torch.float8_e4m3fn or f8.lora_A is not None:
         return False
-    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
-        return False
-    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
-        return False
-    M, K = a.shape
-    N = f8.shape[0]
-    return M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)
+    return _block_gemm_route(a, f8.shape, out, epilogue, 128, 1 << 22)
 
 
 def fp8_lora_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias",
@@ -421,13 +439,7 @@ def _fp8_lora_problem_route(a: torch.Tensor, f8, out: Optional[torch.Tensor], ep
     if not isinstance(f8, Fp8Weight) or f8.compute != "fp8" or f8.lora_compute != "fp8" or f8.q.dtype != torch.float8_e4m3fn \
             or f8.lora_A is None:
         return False
-    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
-        return False
-    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
-        return False
-    M, K = a.shape
-    N = f8.shape[0]
-    return M >= 1 and K == f8.shape[1] and K % 128 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0 and a.stride(0) <= (1 << 22)
+    return _block_gemm_route(a, f8.shape, out, epilogue, 128, 1 << 22)
 
 
 def fp8_norm_quant_rows(x: torch.Tensor, xn: torch.Tensor) -> bool:
@@ -467,13 +479,7 @@ _fp8_act_scratch: dict = {}
 
 def _act_scratch(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-stream home of the activation codes [M, K] and their row scales [M] (as `_scratch`: stream order makes the reuse safe)."""
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    q, s = _fp8_act_scratch.get(key, (None, None))
-    if q is None or q.numel() < M * K:
-        q = torch.empty(M * K, dtype=torch.uint8, device=dev)
-    if s is None or s.numel() < M:
-        s = torch.empty(M, dtype=torch.float32, device=dev)
-    _fp8_act_scratch[key] = (q, s)
+    q, s = _stream_scratch(_fp8_act_scratch, dev, (M * K, torch.uint8), (M, torch.float32))
     return q[:M * K].view(M, K), s[:M]
 
 
@@ -559,6 +565,16 @@ def _check_quantised(a: torch.Tensor, quantised) -> Tuple[torch.Tensor, torch.Te
     return qa, sa
 
 
+def _fp8_acts(a: torch.Tensor, quantised) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The e4m3 codes and row scales of `a` for the fp8 routes of `gemm`: `quantised` where the caller brought them, else
+    `quant_rows_fp8(a)` into the stream's activation scratch."""
+    if quantised is not None:
+        return _check_quantised(a, quantised)
+    qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
+    quant_rows_fp8(a, out=qa, scale_out=sa)
+    return qa, sa
+
+
 def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
                           gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-6,
                           rms: bool = False, split: int = 0, scale2: Optional[torch.Tensor] = None,
@@ -634,11 +650,21 @@ def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=N
     M, N = codes.shape[0], w.shape[0]
     K = codes.shape[1] if K is None else K
     assert codes.shape[1] == K and w.shape[1] == K and (scales is None or scales.numel() == M)
+    return _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, fused=fused, alloc=alloc)
+
+
+def _epilogue_operands(who, M: int, N: int, dev, bias, out, epilogue, gate, residual, fused=False, alloc=False, told=False):
+    """The output side of one [M, N] problem of `gemm_fp8` / `gemm_fp8_grouped` / `gemm_mxfp4`: `out` (made here if None and
+    `alloc`; not looked at if `fused`), `bias`, and the `gate` / `residual` of gate_res.  Returns (out, flag), flag = the epilogue
+    flag of a float `out`, which the entry point rejects with its own message.  `told`: a wrong `out` shape and a missing gate /
+    residual raise ApexMIError with a reason (what `gemm_mxfp4` does) instead of failing an assertion."""
     flag = 0
     if not fused:
         if out is None and alloc:
-            out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
+            out = torch.empty((M, N), dtype=torch.bfloat16, device=dev)
         _req(out, None, who + ".out")
+        if told and (tuple(out.shape) != (M, N) or out.stride(1) != 1):
+            raise _l.ApexMIError(f"{who}.out: expected [{M}, {N}] with contiguous rows, got {tuple(out.shape)}")
         assert out.shape == (M, N) and out.stride(1) == 1
         if out.dtype == torch.float32:
             flag = _l.EPI_F32_IO
@@ -648,6 +674,8 @@ def _fp8_problem(who, codes, scales, w, bias, out, epilogue, gate, residual, K=N
         _req(bias, torch.bfloat16, who + ".bias")
         assert bias.is_contiguous() and bias.numel() == N
     if epilogue == "gate_res":
+        if told and (gate is None or residual is None):
+            raise _l.ApexMIError(f"{who}: the gate_res epilogue needs `gate` and `residual`")
         _req(gate, torch.float32, who + ".gate")
         _req(residual, out.dtype, who + ".residual")
         assert gate.is_contiguous() and gate.numel() == N and residual.shape == (M, N) and residual.stride(1) == 1
@@ -681,37 +709,29 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
                              "block_scales / out_mx are not supported with it")
     out, flag = _fp8_problem("gemm_fp8", codes, scales, w, bias, out, epilogue, gate, residual, alloc=True,
                              block_scales=block_scales, out_mx=out_mx)
+    (M, K), N = codes.shape, w.shape[0]
+    # what every entry point takes: the weight side, and the shape, epilogue and gate_res operands
+    wargs = (w.q.data_ptr(), w.q.stride(0), 0 if w.q.dtype == torch.float8_e4m3fn else 1, w.scale.data_ptr(), w.scale.numel(), _ptr(bias))
+    tail = (M, N, K, _EPI[epilogue] | flag, _ptr(gate), _ptr(residual), residual.stride(0) if epilogue == "gate_res" else 0)
     if block_scales is not None or out_mx is not None:
-        (M, K), N = codes.shape, w.shape[0]
         mq, ms = out_mx if out_mx is not None else (None, None)
         rc = _l.load().apexmi_gemm_fp8_mx(
             codes.data_ptr(), codes.stride(0), _ptr(scales), _ptr(block_scales), 0 if block_scales is None else block_scales.stride(0),
-            w.q.data_ptr(), w.q.stride(0), 0 if w.q.dtype == torch.float8_e4m3fn else 1, w.scale.data_ptr(), w.scale.numel(),
-            _ptr(bias), None if out_mx is not None else out.data_ptr(), 0 if out_mx is not None else out.stride(0), _ptr(mq),
-            0 if mq is None else mq.stride(0), _ptr(ms), 0 if ms is None else ms.stride(0), M, N, K, _EPI[epilogue] | flag,
-            _ptr(gate), _ptr(residual), residual.stride(0) if epilogue == "gate_res" else 0, _stream())
+            *wargs, None if out_mx is not None else out.data_ptr(), 0 if out_mx is not None else out.stride(0), _ptr(mq),
+            0 if mq is None else mq.stride(0), _ptr(ms), 0 if ms is None else ms.stride(0), *tail, _stream())
         _l.check(rc, "gemm_fp8_mx")
         return out_mx if out_mx is not None else out
-    (M, K), N = codes.shape, w.shape[0]
-    fmt = 0 if w.q.dtype == torch.float8_e4m3fn else 1
-    epi = _EPI[epilogue] | flag
-    ldr = residual.stride(0) if epilogue == "gate_res" else 0
+    args = (codes.data_ptr(), codes.stride(0), scales.data_ptr(), *wargs, out.data_ptr(), out.stride(0), *tail)
     if lora_t is not None:
         _req(lora_t, torch.bfloat16, "gemm_fp8.lora_t")
         _req(lora_B, torch.bfloat16, "gemm_fp8.lora_B")
         assert lora_t.dim() == 2 and lora_B.dim() == 2 and lora_t.stride(1) == 1 and lora_B.stride(1) == 1
         Rp = lora_t.shape[1]
         assert lora_t.shape[0] == M and tuple(lora_B.shape) == (N, Rp)
-        rc = _l.load().apexmi_gemm_fp8_lora(codes.data_ptr(), codes.stride(0), scales.data_ptr(), w.q.data_ptr(), w.q.stride(0), fmt,
-                                            w.scale.data_ptr(), w.scale.numel(), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
-                                            epi, _ptr(gate), _ptr(residual), ldr, lora_t.data_ptr(), lora_t.stride(0),
-                                            lora_B.data_ptr(), lora_B.stride(0), Rp, _stream())
+        rc = _l.load().apexmi_gemm_fp8_lora(*args, lora_t.data_ptr(), lora_t.stride(0), lora_B.data_ptr(), lora_B.stride(0), Rp, _stream())
         _l.check(rc, "gemm_fp8_lora")
         return out
-    rc = _l.load().apexmi_gemm_fp8(codes.data_ptr(), codes.stride(0), scales.data_ptr(), w.q.data_ptr(), w.q.stride(0), fmt,
-                                   w.scale.data_ptr(), w.scale.numel(), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K, epi,
-                                   _ptr(gate), _ptr(residual), ldr, _stream())
-    _l.check(rc, "gemm_fp8")
+    _l.check(_l.load().apexmi_gemm_fp8(*args, _stream()), "gemm_fp8")
     return out
 
 
@@ -810,13 +830,7 @@ def mxfp4_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue
     f4 = _fp4_of(w)
     if not isinstance(f4, Mxfp4Weight) or f4.compute != "fp4":
         return False
-    if a.dtype != torch.bfloat16 or (out is not None and out.dtype != torch.bfloat16):
-        return False
-    if a.dim() != 2 or a.stride(1) != 1 or epilogue not in _FP8_EPI:
-        return False
-    M, K = a.shape
-    N = f4.shape[0]
-    return M >= 1 and K == f4.shape[1] and K % 256 == 0 and N % 16 == 0 and a.stride(0) % 8 == 0
+    return _block_gemm_route(a, f4.shape, out, epilogue, 256)
 
 
 _fp4_act_scratch: dict = {}
@@ -824,13 +838,7 @@ _fp4_act_scratch: dict = {}
 
 def _act_scratch_mxfp4(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-stream home of the activation's MXFP4 codes [M, K / 2] and scale bytes [M, K / 32] (as `_act_scratch`)."""
-    key = (dev.index, torch.cuda.current_stream().cuda_stream)
-    q, s = _fp4_act_scratch.get(key, (None, None))
-    if q is None or q.numel() < M * (K // 2):
-        q = torch.empty(M * (K // 2), dtype=torch.uint8, device=dev)
-    if s is None or s.numel() < M * (K // 32):
-        s = torch.empty(M * (K // 32), dtype=torch.uint8, device=dev)
-    _fp4_act_scratch[key] = (q, s)
+    q, s = _stream_scratch(_fp4_act_scratch, dev, (M * (K // 2), torch.uint8), (M * (K // 32), torch.uint8))
     return q[:M * (K // 2)].view(M, K // 2), s[:M * (K // 32)].view(M, K // 32)
 
 
@@ -850,25 +858,7 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
         raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(codes).__name__}")
     M, (N, K) = codes.shape[0], w.shape
     _check_mxfp4_pair(who, codes, scales, M, K)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=codes.device)
-    _req(out, None, who + ".out")
-    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
-        raise _l.ApexMIError(f"{who}.out: expected [{M}, {N}] with contiguous rows, got {tuple(out.shape)}")
-    flag = 0
-    if out.dtype == torch.float32:
-        flag = _l.EPI_F32_IO          # the entry point rejects it with its own message
-    else:
-        _req(out, torch.bfloat16, who + ".out")
-    if bias is not None:
-        _req(bias, torch.bfloat16, who + ".bias")
-        assert bias.is_contiguous() and bias.numel() == N
-    if epilogue == "gate_res":
-        if gate is None or residual is None:
-            raise _l.ApexMIError(f"{who}: the gate_res epilogue needs `gate` and `residual`")
-        _req(gate, torch.float32, who + ".gate")
-        _req(residual, out.dtype, who + ".residual")
-        assert gate.is_contiguous() and gate.numel() == N and residual.shape == (M, N) and residual.stride(1) == 1
+    out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
     rc = _l.load().apexmi_gemm_mxfp4(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
                                      w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
                                      _EPI[epilogue] | flag, _ptr(gate), _ptr(residual),
@@ -880,19 +870,27 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
 FP8_MAX_GROUPS = 4
 
 
+def _grouped_problems(a_list, w_list, out_list, epilogues):
+    """The problems (a, w, out, epilogue) of a grouped launch as its route predicates read them, or None where the lists do not
+    describe one: 1 to 4 problems, one weight each, `epilogues` one name or one per problem, `out_list` None or one tensor (or
+    None) per problem, and every `a` of the same K."""
+    n = len(a_list)
+    if not 1 <= n <= FP8_MAX_GROUPS or len(w_list) != n:
+        return None
+    epis = [epilogues] * n if isinstance(epilogues, str) else list(epilogues)
+    outs = [None] * n if out_list is None else list(out_list)
+    if len(epis) != n or len(outs) != n or len({a.shape[-1] for a in a_list}) != 1:
+        return None
+    return list(zip(a_list, w_list, outs, epis))
+
+
 def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
     """Whether a grouped launch over these problems may go out as quantise + `gemm_fp8_grouped`.  Pure, like `fp8_compute_route`
     (dtypes, shapes and strides only; CPU tensors are fine): true only when EVERY problem satisfies `fp8_compute_route` — a
     launch is all fp8 or all today's path, never mixed — and there are 1 to 4 of them sharing K.  `epilogues`: one name or one
     per problem; `out_list`: None, or one tensor (or None) per problem."""
-    n = len(a_list)
-    if not 1 <= n <= FP8_MAX_GROUPS or len(w_list) != n:
-        return False
-    epis = [epilogues] * n if isinstance(epilogues, str) else list(epilogues)
-    outs = [None] * n if out_list is None else list(out_list)
-    if len(epis) != n or len(outs) != n or len({a.shape[-1] for a in a_list}) != 1:
-        return False
-    return all(fp8_compute_route(a, w, o, e) for a, w, o, e in zip(a_list, w_list, outs, epis))
+    problems = _grouped_problems(a_list, w_list, out_list, epilogues)
+    return problems is not None and all(fp8_compute_route(a, w, o, e) for a, w, o, e in problems)
 
 
 def fp8_grouped_lora_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
@@ -903,15 +901,11 @@ def fp8_grouped_lora_route(a_list, w_list, out_list=None, epilogues="bias") -> b
     `lora_compute == "fp8"` that carries factors; t lives in a tensor of its own, so no padded activation buffer is needed), AT
     LEAST ONE problem carries factors (otherwise `fp8_grouped_route` is the question), and there are 1 to 4 problems sharing K.  A
     launch is all fp8 or not routed, never mixed."""
-    n = len(a_list)
-    if not 1 <= n <= FP8_MAX_GROUPS or len(w_list) != n:
-        return False
-    epis = [epilogues] * n if isinstance(epilogues, str) else list(epilogues)
-    outs = [None] * n if out_list is None else list(out_list)
-    if len(epis) != n or len(outs) != n or len({a.shape[-1] for a in a_list}) != 1:
+    problems = _grouped_problems(a_list, w_list, out_list, epilogues)
+    if problems is None:
         return False
     any_lora = False
-    for a, w, o, e in zip(a_list, w_list, outs, epis):
+    for a, w, o, e in problems:
         f8 = _fp8_of(w)
         if isinstance(f8, Fp8Weight) and f8.lora_A is not None:
             any_lora = True
@@ -942,9 +936,9 @@ def fp8_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_d
 
 def fp8_grouped_tiles(shapes):
     """The tile each workgroup of a `gemm_fp8_grouped` launch over problems `shapes` = [(M, N), ...] computes, restated from the
-    kernel (csrc/gemm_fp8.hip, fp8_problem and gemm_fp8_kernel): a list over block ids of (problem, tile row, tile column).  The XCD remap
-    runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts, and inside a problem
-    bands of 8 tile rows are walked column by column."""
+    kernel (fp8_problem in csrc/gemm_fp8.hip, fp8_tile_origin in csrc/fp8_gemm_tile.h): a list over block ids of (problem, tile row,
+    tile column).  The XCD remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile
+    counts, and inside a problem bands of 8 tile rows are walked column by column."""
     tm = [(m + 127) // 128 for m, _ in shapes]
     tn = [(n + 127) // 128 for _, n in shapes]
     tile0 = [sum(a * b for a, b in zip(tm[:i], tn[:i])) for i in range(len(shapes))]
@@ -1143,11 +1137,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         return gemm_mxfp4(qa, sa, w._fp4, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
-        if quantised is not None:
-            qa, sa = _check_quantised(a, quantised)
-        else:
-            qa, sa = _act_scratch(a.device, a.shape[0], a.shape[1])
-            quant_rows_fp8(a, out=qa, scale_out=sa)
+        qa, sa = _fp8_acts(a, quantised)
         if out_mx is not None:
             return gemm_fp8(qa, sa, f8, bias, epilogue=epilogue, out_mx=out_mx)
         return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
@@ -1162,11 +1152,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
             K, Rp = a.shape[1], f8.lora_A.shape[0]
             t = lora_buf[:, K:K + Rp]
             gemm(a, f8.lora_A, None, out=t)                      # t = a A^T in bf16, as _gemm_fp8_lora produces it
-            if quantised is not None:
-                qa, sa = _check_quantised(a, quantised)
-            else:
-                qa, sa = _act_scratch(a.device, a.shape[0], K)
-                quant_rows_fp8(a, out=qa, scale_out=sa)
+            qa, sa = _fp8_acts(a, quantised)
             return gemm_fp8(qa, sa, f8, bias, out=out, epilogue=epilogue, gate=gate, residual=residual, lora_t=t, lora_B=f8.lora_B)
         return _gemm_fp8_lora(a, f8, bias, out, epilogue, gate, residual, lora_buf)
     w = _bf16_weight(w, a.dtype == torch.float32)
