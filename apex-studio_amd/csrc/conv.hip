@@ -1552,13 +1552,14 @@ bool slab_eligible(const ConvArgs& a) {
     return g_conv_slab && a.kH == 3 && a.kW == 3 && a.py == 1 && a.px == 1 && a.kT <= 3 && (slab48(a) || slab64(a));
 }
 
-// The ONE dispatch rule of the convolution family (conv3d_cl_impl launches by it, apexmi_conv3d_cl_family reports it):
-// which tile family a filled ConvArgs takes under the current conv.* settings.  *bn = the N extent of the conv-shaped tile
+// The ONE dispatch rule of the convolution family (conv_run launches by it, apexmi_conv3d_cl_family reports it):
+// which tile family a filled ConvArgs takes under the current conv.* settings, `norm` = with the fused norm (a query has no
+// out_norm to show).  *bn = the N extent of the conv-shaped tile
 // (CONV_FAMILY_V2 only, 0 otherwise).  tile choice: the N extent that wastes the fewest matrix columns; v2 only where it
 // fills the chip.  Stacked clips (Tc > 0) stay on the 128x128 kernel: the clip boundary lives in its gather only (the
 // conv-shaped / slab tiles walk frames).
 enum { CONV_FAMILY_128 = 0, CONV_FAMILY_V2 = 1, CONV_FAMILY_SLAB48 = 2, CONV_FAMILY_SLAB64 = 3, CONV_FAMILY_SLAB96 = 4 };
-int conv_family(const ConvArgs& a, int* bn) {
+int conv_family(const ConvArgs& a, bool norm, int* bn) {
     *bn = 0;
     const int64_t M = (int64_t)a.T * a.H * a.W;
     if (a.Tc > 0) return CONV_FAMILY_128;
@@ -1566,7 +1567,7 @@ int conv_family(const ConvArgs& a, int* bn) {
         (int64_t)a.T * a.Hin * a.Win * a.Cin * 2 >= ((int64_t)1 << 31))   // 32-bit byte offsets in the gather
         return CONV_FAMILY_128;
     const int c = a.Cout;
-    if (slab_eligible(a) && !(a.out_norm != nullptr && c > (slab48(a) ? 192 : 128))) {
+    if (slab_eligible(a) && !(norm && c > (slab48(a) ? 192 : 128))) {
         // the slab kernels need a round of workgroups and mostly full tiles, not 65536 positions: e.g. the 32 x 32 x 61-frame
         // stages of the HunyuanVideo-1.5 decoder (62464 positions, 1024 channels = 1952 workgroups)
         const bool two_rows = slab48(a) && c <= 96;
@@ -1591,6 +1592,12 @@ int conv_family(const ConvArgs& a, int* bn) {
     return CONV_FAMILY_V2;
 }
 
+// nt = 1 | 2 | 3 (32-channel N tiles of a workgroup) as a template argument: f(std::integral_constant<int, nt>)
+template <typename F>
+int with_nt(int nt, F f) {
+    return nt == 1 ? f(std::integral_constant<int, 1>{}) : nt == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
+}
+
 int launch_slab(const ConvArgs& a, int family, hipStream_t stream) {
     const bool norm = a.out_norm != nullptr;
     // conv.pp: 1 (shipped) = per shape, whichever schedule measured faster (profiles/r03_vae_conv_schedules.md): the register-
@@ -1604,20 +1611,19 @@ int launch_slab(const ConvArgs& a, int family, hipStream_t stream) {
         if (g_conv_pp == 2) return norm ? launch_slabp_inst<2, 2, 2, 1, 64>(a, stream) : launch_slabp_inst<2, 2, 2, 0, 64>(a, stream);
         return norm ? launch_slab_inst<4, 1, 1, 64>(a, stream) : launch_slab_inst<4, 1, 0, 64>(a, stream);
     }
-    if (family == CONV_FAMILY_SLAB96) {
-        const int nt = (a.Cout + 31) / 32;
-        if (norm) return nt == 1 ? launch_slab96_inst<1, 1>(a, stream) : nt == 2 ? launch_slab96_inst<2, 1>(a, stream) : launch_slab96_inst<3, 1>(a, stream);
-        return nt == 1 ? launch_slab96_inst<1, 0>(a, stream) : nt == 2 ? launch_slab96_inst<2, 0>(a, stream) : launch_slab96_inst<3, 0>(a, stream);
-    }
+    const int nt = (a.Cout + 31) / 32;
+    if (family == CONV_FAMILY_SLAB96)
+        return with_nt(nt, [&](auto n) {
+            constexpr int NT = decltype(n)::value;
+            return norm ? launch_slab96_inst<NT, 1>(a, stream) : launch_slab96_inst<NT, 0>(a, stream);
+        });
     if (a.Cout <= 96) {
-        const int nt = (a.Cout + 31) / 32;
         if (g_conv_pp == 3 && nt == 3 && !norm) return launch_slabp_inst<3, 4, 1, 0, 48, 4>(a, stream);
-        if (g_conv_pp >= 2) {
-            if (norm) return nt == 1 ? launch_slabp_inst<1, 2, 1, 1>(a, stream) : nt == 2 ? launch_slabp_inst<2, 2, 1, 1>(a, stream) : launch_slabp_inst<3, 2, 1, 1>(a, stream);
-            return nt == 1 ? launch_slabp_inst<1, 2, 1, 0>(a, stream) : nt == 2 ? launch_slabp_inst<2, 2, 1, 0>(a, stream) : launch_slabp_inst<3, 2, 1, 0>(a, stream);
-        }
-        if (norm) return nt == 1 ? launch_slab_inst<1, 2, 1>(a, stream) : nt == 2 ? launch_slab_inst<2, 2, 1>(a, stream) : launch_slab_inst<3, 2, 1>(a, stream);
-        return nt == 1 ? launch_slab_inst<1, 2, 0>(a, stream) : nt == 2 ? launch_slab_inst<2, 2, 0>(a, stream) : launch_slab_inst<3, 2, 0>(a, stream);
+        return with_nt(nt, [&](auto n) {
+            constexpr int NT = decltype(n)::value;
+            if (g_conv_pp >= 2) return norm ? launch_slabp_inst<NT, 2, 1, 1>(a, stream) : launch_slabp_inst<NT, 2, 1, 0>(a, stream);
+            return norm ? launch_slab_inst<NT, 2, 1>(a, stream) : launch_slab_inst<NT, 2, 0>(a, stream);
+        });
     }
     if (norm) {
         if (a.Cout > 192) {
@@ -1653,18 +1659,42 @@ int launch_v2(const ConvArgs& a, hipStream_t stream) {
     return a.up ? launch_v2_inst<CFG, 1, 0>(a, stream, nm * nn) : launch_v2_inst<CFG, 0, 0>(a, stream, nm * nn);
 }
 
-// launches what conv_family chose; *taken = false leaves the call to the 128x128 kernel
-int launch_v2_for(const ConvArgs& a, int family, int bn, hipStream_t stream, bool* taken) {
-    *taken = family != CONV_FAMILY_128;
-    if (family == CONV_FAMILY_128) return 0;
-    if (family != CONV_FAMILY_V2) return launch_slab(a, family, stream);
-    switch (bn) {
-    case 32: return launch_v2<CV_N32, true>(a, stream);
-    case 64: return launch_v2<CV_N64, true>(a, stream);
-    case 96: return launch_v2<CV_N96, true>(a, stream);
-    case 128: return launch_v2<CV_N128>(a, stream);
-    case 256: return launch_v2<CV_N256>(a, stream);
-    default: return launch_v2<CV_N192, true>(a, stream);   // (the fused norm needs one N tile: launch_v2 refuses Cout > 192)
+// 128x128 implicit GEMM; TO = float: the f32-storage verification form (float out / residual)
+template <typename TO>
+int launch_128(const ConvArgs& a, hipStream_t stream, const char* what) {
+    static uint64_t attr = 0;
+    APEXMI_SET_ATTR_ONCE(attr, (void)hipFuncSetAttribute((const void*)conv3d_cl_kernel<TO>,
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE_BYTES));
+    const int64_t M = (int64_t)a.To * a.Ho * a.Wo;
+    const int nm = (int)((M + BM - 1) / BM), nn = (a.Cout + BN - 1) / BN;
+    hipLaunchKernelGGL(conv3d_cl_kernel<TO>, dim3(nm * nn), dim3(256), 2 * STAGE_BYTES, stream, a);
+    return apexmi_check_launch(what);
+}
+
+// The ONE launch routine: a checked, filled ConvArgs (conv_fill) on the tile family conv_family chose for it (bn: the N extent
+// of the conv-shaped tile); f32io: the f32-storage verification form, which runs on the 128x128 family for every shape
+int conv_launch(const ConvArgs& a, int family, int bn, bool f32io, hipStream_t stream) {
+    const int64_t M = (int64_t)a.To * a.Ho * a.Wo;
+    ApexmiProfScope prof(0, stream, 2.0 * M * a.Cout * (double)a.ntaps * a.Cin,
+                         2.0 * ((double)M * a.Cin + (double)a.Cout * a.Kext + (double)M * a.Cout));
+    switch (family) {
+    case CONV_FAMILY_V2:
+        switch (bn) {
+        case 32: return launch_v2<CV_N32, true>(a, stream);
+        case 64: return launch_v2<CV_N64, true>(a, stream);
+        case 96: return launch_v2<CV_N96, true>(a, stream);
+        case 128: return launch_v2<CV_N128>(a, stream);
+        case 256: return launch_v2<CV_N256>(a, stream);
+        default: return launch_v2<CV_N192, true>(a, stream);   // (the fused norm needs one N tile: launch_v2 refuses Cout > 192)
+        }
+    case CONV_FAMILY_SLAB48:
+    case CONV_FAMILY_SLAB64:
+    case CONV_FAMILY_SLAB96: return launch_slab(a, family, stream);
+    default:   // CONV_FAMILY_128
+        if (f32io) return launch_128<float>(a, stream, "conv3d_cl_f32");
+        APEXMI_REQUIRE(a.out_norm == nullptr, "conv3d_cl_norm: this convolution does not run on the fused-norm tiles "
+                                              "(ask apexmi_conv3d_cl_norm_fusable first)");
+        return launch_128<bf16_t>(a, stream, "conv3d_cl");
     }
 }
 
@@ -2009,26 +2039,48 @@ extern "C" int apexmi_groupnorm_cl_f32(const void* x, void* y, const void* gamma
     return groupnorm_cl_impl<float>(x, y, gamma, beta, P, C, G, eps, silu, workspace, workspace_bytes, stream_);
 }
 
-static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const void* residual, void* out,
-                          const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH, int kW,
-                          int replicate, apexmi_stream_t stream_, int sy = 1, int sx = 1, int py = -1, int px = -1,
-                          int Ho = 0, int Wo = 0, int independent = 0, int up = 0, const void* norm_gamma = nullptr,
-                          void* out_norm = nullptr, int norm_silu = 0, int act = 0, float act_slope = 0.0f, int st = 1,
-                          int t0 = 0, int To = 0, int f32io = 0, int clip_frames = 0, int* family_query = nullptr,
-                          int* family_bn = nullptr) {
-    // family_query != nullptr: launch nothing, report the tile family this call would take (apexmi_conv3d_cl_family; the
-    // operands are not looked at, a non-null out_norm only says "with the fused norm")
-    const int Hin = H, Win = W;
-    if (up) {          // H, W arrive as the STORED extents; the convolution runs over the 2x upsampled image
-        H *= 2;
-        W *= 2;
-    }
-    if (py < 0) py = (kH - 1) / 2;   // "same" convolution
-    if (px < 0) px = (kW - 1) / 2;
-    if (Ho <= 0) Ho = H;
-    if (Wo <= 0) Wo = W;
-    hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(family_query || (in && w && (out || out_norm) && zeros), "conv3d_cl: null operand");
+// ---- host front end of the convolution entry points ------------------------------------------------
+// An entry point fills a ConvCall (only the fields it owns), conv_run checks it and fills the kernels' ConvArgs (conv_fill: every
+// refusal, no HIP call), asks the one dispatch rule (conv_family) and launches (conv_launch).  apexmi_conv3d_cl_family fills the
+// same record and stops after the rule.
+
+// One convolution as an entry point describes it.  The defaults are the plain causal "same" stride-1 convolution.
+struct ConvCall {
+    const void* in = nullptr;         // [T, H, W, Cin] as stored
+    const void* w = nullptr;          // [Cout, Kpad]
+    const void* bias = nullptr;       // [Cout] or null
+    const void* residual = nullptr;   // [To, Ho, Wo, Cout] or null
+    void* out = nullptr;              // [To, Ho, Wo, Cout] (may be null beside out_norm)
+    const void* zeros = nullptr;      // >= 16 bytes of zeros
+    int T = 0, H = 0, W = 0, Cin = 0, Cout = 0, Kpad = 0, kT = 1, kH = 1, kW = 1;   // the STORED shape
+    int replicate = 0;                // replicate padding (clamped coordinates) instead of zeros
+    int independent = 0;              // every frame on its own (no temporal taps into the previous frame)
+    int up = 0;                       // read through a nearest 2x spatial upsample
+    int sy = 1, sx = 1;               // spatial stride
+    int py = -1, px = -1;             // zero rows / columns above / left; < 0: "same", (k - 1) / 2
+    int Ho = 0, Wo = 0;               // output extents; <= 0: those of the (upsampled) input
+    int st = 1, t0 = 0, To = 0;       // temporal stride, first input frame, output frames (<= 0: T)
+    int clip_frames = 0;              // > 0: T / clip_frames independent clips stacked along T
+    bool norm = false;                // with the fused RMS norm of the output: the norm entry point, which also sets the three
+                                      // fields below, and the family query, which has no operands
+    const void* norm_gamma = nullptr;
+    void* out_norm = nullptr;
+    int norm_silu = 0;
+    int act = 0;                      // 0 none, 1 leaky ReLU with act_slope
+    float act_slope = 0.0f;
+    bool f32io = false;               // f32-storage verification form: float out / residual, `in` the three-way bf16 split
+};
+
+// Every refusal of the shared path, in one order, and the fill of `a` (every field: the caller value-initialises it).  No HIP
+// call.  operands = false (the family query): the pointers are not looked at.
+static int conv_fill(const ConvCall& c, bool operands, ConvArgs& a) {
+    const int T = c.T, Cin = c.Cin, Cout = c.Cout, Kpad = c.Kpad, kT = c.kT, kH = c.kH, kW = c.kW;
+    const int up = c.up ? 2 : 1;
+    const int H = c.H * up, W = c.W * up;   // H, W arrive as the STORED extents; the convolution runs over the 2x upsampled image
+    const int py = c.py < 0 ? (kH - 1) / 2 : c.py, px = c.px < 0 ? (kW - 1) / 2 : c.px;   // "same" convolution
+    const int Ho = c.Ho <= 0 ? H : c.Ho, Wo = c.Wo <= 0 ? W : c.Wo;
+    const int sy = c.sy, sx = c.sx, st = c.st, t0 = c.t0, To = c.To <= 0 ? T : c.To;
+    if (operands) APEXMI_REQUIRE(c.in && c.w && (c.out || c.out_norm) && c.zeros, "conv3d_cl: null operand");
     APEXMI_REQUIRE(T > 0 && H > 0 && W > 0, "conv3d_cl: empty volume");
     APEXMI_REQUIRE(Cin % 8 == 0 && Cout % 4 == 0, "conv3d_cl: Cin=%d must be a multiple of 8, Cout=%d of 4", Cin, Cout);
     const int ntaps = kT * kH * kW;
@@ -2038,106 +2090,91 @@ static int conv3d_cl_impl(const void* in, const void* w, const void* bias, const
                    "conv3d_cl: stride %dx%d / pad %d,%d / output %dx%d do not fit the %dx%d input", sy, sx, py, px, Ho, Wo, H, W);
     APEXMI_REQUIRE(Kpad % BK == 0 && Kpad >= ntaps * Cin, "conv3d_cl: Kpad=%d must be >= taps*Cin rounded up to 64", Kpad);
     APEXMI_REQUIRE((int64_t)T * H * W < (int64_t)2147483647 - BM, "conv3d_cl: volume too large for one call");
-    APEXMI_REQUIRE(((uintptr_t)in % 16) == 0 && ((uintptr_t)w % 16) == 0 && ((uintptr_t)out % 8) == 0 &&
-                       ((uintptr_t)zeros % 16) == 0,
-                   "conv3d_cl: operands must be 16-byte aligned");
-    static uint64_t attr_set = 0;
-    APEXMI_SET_ATTR_ONCE(attr_set, {
-        (void)hipFuncSetAttribute((const void*)conv3d_cl_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * STAGE_BYTES);
-        (void)hipFuncSetAttribute((const void*)conv3d_cl_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * STAGE_BYTES);
-    });
-    ConvArgs a;
-    a.in = (const bf16_t*)in;
-    a.w = (const bf16_t*)w;
-    a.bias = (const bf16_t*)bias;
-    a.res = (const bf16_t*)residual;
-    a.out = (bf16_t*)out;
-    a.zeros = (const bf16_t*)zeros;
+    if (operands)
+        APEXMI_REQUIRE(((uintptr_t)c.in % 16) == 0 && ((uintptr_t)c.w % 16) == 0 && ((uintptr_t)c.out % 8) == 0 &&
+                           ((uintptr_t)c.zeros % 16) == 0,
+                       "conv3d_cl: operands must be 16-byte aligned");
     // A single frame sees only the LAST temporal tap: the kT - 1 earlier ones fall in the causal zero padding
     // (QwenImage's image VAE and every T = 1 tile run 3x3x3 kernels on one frame).  Skip them: start at the last
     // temporal slice of the packed weight (k = tap * Cin + ci, taps time-major) and iterate kH*kW taps — a third of the
     // work, the same sum (the skipped products are exact zeros).
-    int Kext = Kpad, kT_eff = kT, ntaps_eff = ntaps;
     const int skip = (kT - 1) * kH * kW * Cin, kspatial = ((kH * kW * Cin + BK - 1) / BK) * BK;
-    APEXMI_REQUIRE(!independent || kT == 1 || (!replicate && skip % 8 == 0 && skip + kspatial <= Kpad),
+    APEXMI_REQUIRE(!c.independent || kT == 1 || (!c.replicate && skip % 8 == 0 && skip + kspatial <= Kpad),
                    "conv3d_cl_frames: Kpad=%d leaves no room to address the last temporal slice (need >= %d; pack the "
                    "weight with apexmi's packing rule)", Kpad, skip + kspatial);
-    if ((T == 1 || independent) && kT > 1 && !replicate && skip % 8 == 0 && skip + kspatial <= Kpad) {
-        if (w) a.w += skip;
-        Kext = kspatial;
-        kT_eff = 1;
-        ntaps_eff = kH * kW;
-    }
-    a.T = T; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Kpad = Kpad; a.Kext = Kext;
-    a.kT = kT_eff; a.kH = kH; a.kW = kW; a.ntaps = ntaps_eff;
-    a.q64 = 64 / Cin;
-    a.r64 = 64 % Cin;
-    a.replicate = replicate;
-    a.Ho = Ho; a.Wo = Wo; a.sy = sy; a.sx = sx; a.py = py; a.px = px;
-    a.up = up ? 1 : 0; a.Hin = Hin; a.Win = Win;
-    a.norm_gamma = (const bf16_t*)norm_gamma; a.out_norm = (bf16_t*)out_norm; a.norm_silu = norm_silu;
-    APEXMI_REQUIRE(act == 0 || (act == 1 && out_norm == nullptr), "conv3d_cl: activation %d unsupported (0 none, 1 leaky ReLU; "
-                                                                  "not together with the fused norm)", act);
-    a.act = act; a.act_slope = act_slope;
-    if (To <= 0) To = T;
+    const bool last_tap = (T == 1 || c.independent) && kT > 1 && !c.replicate && skip % 8 == 0 && skip + kspatial <= Kpad;
+    APEXMI_REQUIRE(c.act == 0 || (c.act == 1 && !c.norm), "conv3d_cl: activation %d unsupported (0 none, 1 leaky ReLU; "
+                                                          "not together with the fused norm)", c.act);
     APEXMI_REQUIRE(st >= 1 && t0 >= 0 && (To - 1) * st + t0 < T, "conv3d_cl: temporal stride %d / first frame %d / %d output frames "
                                                                  "do not fit %d input frames", st, t0, To, T);
-    APEXMI_REQUIRE((st == 1 && t0 == 0 && To == T) || (!up && !independent && out_norm == nullptr && T > 1),
+    APEXMI_REQUIRE((st == 1 && t0 == 0 && To == T) || (!c.up && !c.independent && !c.norm && T > 1),
                    "conv3d_cl: a temporal stride excludes the upsample / independent-frame / fused-norm modes");
+    APEXMI_REQUIRE(c.clip_frames >= 0 && (c.clip_frames == 0 || (T % c.clip_frames == 0 && st == 1 && t0 == 0 && To == T && !c.up &&
+                                                                 !c.independent && !c.norm)),
+                   "conv3d_cl: clip_frames=%d must divide T=%d (stride-1 plain convolutions only)", c.clip_frames, T);
+    if (operands && c.f32io)
+        APEXMI_REQUIRE(c.out && !c.norm && ((uintptr_t)c.out % 16) == 0 && ((uintptr_t)c.residual % 16) == 0,
+                       "conv3d_cl_f32: float out / residual must be 16-byte aligned (no fused norm)");
+    a.in = (const bf16_t*)c.in;
+    a.w = (const bf16_t*)c.w + (last_tap && c.w ? skip : 0);
+    a.bias = (const bf16_t*)c.bias;
+    a.res = (const bf16_t*)c.residual;
+    a.out = (bf16_t*)c.out;
+    a.zeros = (const bf16_t*)c.zeros;
+    a.T = T; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.Kpad = Kpad; a.Kext = last_tap ? kspatial : Kpad;
+    a.kT = last_tap ? 1 : kT; a.kH = kH; a.kW = kW; a.ntaps = last_tap ? kH * kW : ntaps;
+    a.q64 = 64 / Cin;
+    a.r64 = 64 % Cin;
+    a.replicate = c.replicate;
+    a.Ho = Ho; a.Wo = Wo; a.sy = sy; a.sx = sx; a.py = py; a.px = px;
+    a.up = c.up ? 1 : 0; a.Hin = c.H; a.Win = c.W;
+    a.norm_gamma = (const bf16_t*)c.norm_gamma; a.out_norm = (bf16_t*)c.out_norm; a.norm_silu = c.norm_silu;
+    a.act = c.act; a.act_slope = c.act_slope;
     a.To = To; a.st = st; a.t0 = t0;
-    APEXMI_REQUIRE(clip_frames >= 0 && (clip_frames == 0 || (T % clip_frames == 0 && st == 1 && t0 == 0 && To == T && !up &&
-                                                             !independent && out_norm == nullptr)),
-                   "conv3d_cl: clip_frames=%d must divide T=%d (stride-1 plain convolutions only)", clip_frames, T);
-    a.Tc = clip_frames == T ? 0 : clip_frames;
+    a.Tc = c.clip_frames == T ? 0 : c.clip_frames;
     a.prof = (unsigned long long*)g_conv_prof;
     a.dbg = g_conv_dbg;
     a.torder = g_conv_torder;
+    return 0;
+}
+
+static int conv_run(const ConvCall& c, apexmi_stream_t stream_) {
+    ConvArgs a{};
+    if (const int rc = conv_fill(c, true, a)) return rc;
     int bn = 0;
-    const int family = f32io ? CONV_FAMILY_128 : conv_family(a, &bn);
-    if (family_query) {
-        *family_query = family;
-        if (family_bn) *family_bn = bn;
-        return 0;
-    }
-    const int64_t M = (int64_t)To * Ho * Wo;
-    const int nm = (int)((M + BM - 1) / BM), nn = (Cout + BN - 1) / BN;
-    ApexmiProfScope prof(0, stream, 2.0 * M * Cout * (double)ntaps_eff * Cin,
-                         2.0 * ((double)M * Cin + (double)Cout * Kext + (double)M * Cout));
-    if (f32io) {   // verification mode: float out / residual, the 128x128 implicit GEMM for every shape
-        APEXMI_REQUIRE(out && out_norm == nullptr && ((uintptr_t)out % 16) == 0 && ((uintptr_t)residual % 16) == 0,
-                       "conv3d_cl_f32: float out / residual must be 16-byte aligned (no fused norm)");
-        hipLaunchKernelGGL(conv3d_cl_kernel<float>, dim3(nm * nn), dim3(256), 2 * STAGE_BYTES, stream, a);
-        return apexmi_check_launch("conv3d_cl_f32");
-    }
-    bool taken = false;
-    const int rc2 = launch_v2_for(a, family, bn, stream, &taken);
-    if (taken) return rc2;
-    APEXMI_REQUIRE(out_norm == nullptr, "conv3d_cl_norm: this convolution does not run on the fused-norm tiles "
-                                        "(ask apexmi_conv3d_cl_norm_fusable first)");
-    hipLaunchKernelGGL(conv3d_cl_kernel<bf16_t>, dim3(nm * nn), dim3(256), 2 * STAGE_BYTES, stream, a);
-    return apexmi_check_launch("conv3d_cl");
+    const int family = c.f32io ? CONV_FAMILY_128 : conv_family(a, c.norm, &bn);
+    return conv_launch(a, family, bn, c.f32io, (hipStream_t)stream_);
 }
 
 extern "C" int apexmi_conv3d_cl(const void* in, const void* w, const void* bias, const void* residual,
                                 void* out, const void* zeros, int T, int H, int W, int Cin, int Cout,
                                 int Kpad, int kT, int kH, int kW, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_clips(const void* in, const void* w, const void* bias, const void* residual, void* out,
                                       const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH,
                                       int kW, int replicate, int clip_frames, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, replicate, stream_, 1, 1, -1,
-                          -1, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0.0f, 1, 0, 0, 0, clip_frames);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.replicate = replicate;
+    c.clip_frames = clip_frames;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_up2(const void* in, const void* w, const void* bias, const void* residual, void* out,
                                     const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH,
                                     int kW, int independent, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, 1, 1, -1, -1,
-                          0, 0, independent, 1);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.independent = independent;
+    c.up = 1;
+    return conv_run(c, stream_);
 }
 
 // can apexmi_conv3d_cl_norm run this shape?  (stride-1 zero-padded conv on the v2 tiles with every output channel of a
@@ -2148,17 +2185,21 @@ extern "C" int apexmi_conv3d_cl_norm_fusable(int T, int H, int W, int Cin, int C
            (Cout <= 96 || (Cout > 128 && Cout <= 192));
 }
 
+// launches nothing and touches no HIP API: the shared record through conv_fill (no operands) and the dispatch rule
 extern "C" int apexmi_conv3d_cl_family(int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH, int kW, int replicate,
                                        int independent, int up, int norm, int clip_frames, int stride_h, int stride_w,
                                        int pad_top, int pad_left, int Ho, int Wo, int stride_t, int t_first, int To,
                                        int* n_extent) {
-    int family = -1, bn = 0;
-    static char norm_flag;   // never written: a non-null out_norm selects the fused-norm side of the rule
-    const int rc = conv3d_cl_impl(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, T, H, W, Cin, Cout, Kpad, kT, kH, kW,
-                                  replicate, nullptr, stride_h, stride_w, pad_top, pad_left, Ho, Wo, independent, up, nullptr,
-                                  norm ? &norm_flag : nullptr, 0, 0, 0.0f, stride_t, t_first, To, 0, clip_frames, &family, &bn);
-    if (n_extent) *n_extent = rc ? 0 : bn;
-    return rc ? -1 : family;
+    ConvCall c;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.replicate = replicate; c.independent = independent; c.up = up; c.norm = norm != 0; c.clip_frames = clip_frames;
+    c.sy = stride_h; c.sx = stride_w; c.py = pad_top; c.px = pad_left; c.Ho = Ho; c.Wo = Wo;
+    c.st = stride_t; c.t0 = t_first; c.To = To;
+    ConvArgs a{};
+    int bn = 0;
+    const int family = conv_fill(c, false, a) ? -1 : conv_family(a, c.norm, &bn);
+    if (n_extent) *n_extent = bn;
+    return family;
 }
 
 extern "C" int apexmi_conv3d_cl_norm(const void* in, const void* w, const void* bias, const void* residual, void* out,
@@ -2167,22 +2208,35 @@ extern "C" int apexmi_conv3d_cl_norm(const void* in, const void* w, const void* 
                                      apexmi_stream_t stream_) {
     APEXMI_REQUIRE(out_norm && gamma, "conv3d_cl_norm: out_norm and gamma are required");
     APEXMI_REQUIRE(Cout % 8 == 0, "conv3d_cl_norm: Cout=%d must be a multiple of 8", Cout);
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, 1, 1, -1, -1,
-                          0, 0, independent, up, gamma, out_norm, silu);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.independent = independent;
+    c.up = up;
+    c.norm = true; c.norm_gamma = gamma; c.out_norm = out_norm; c.norm_silu = silu;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_act(const void* in, const void* w, const void* bias, const void* residual, void* out,
                                     const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH,
                                     int kW, int independent, int up, int act, float slope, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, 1, 1, -1, -1,
-                          0, 0, independent, up, nullptr, nullptr, 0, act, slope);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.independent = independent;
+    c.up = up;
+    c.act = act; c.act_slope = slope;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_frames(const void* in, const void* w, const void* bias, const void* residual,
                                        void* out, const void* zeros, int N, int H, int W, int Cin, int Cout, int Kpad,
                                        int kT, int kH, int kW, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, N, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, 1, 1, -1, -1,
-                          0, 0, 1);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = N; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.independent = 1;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_strided(const void* in, const void* w, const void* bias, const void* residual,
@@ -2190,16 +2244,22 @@ extern "C" int apexmi_conv3d_cl_strided(const void* in, const void* w, const voi
                                         int kT, int kH, int kW, int stride_h, int stride_w, int pad_top, int pad_left,
                                         int Ho, int Wo, apexmi_stream_t stream_) {
     APEXMI_REQUIRE(Ho > 0 && Wo > 0, "conv3d_cl_strided: empty output %dx%d", Ho, Wo);
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, stride_h,
-                          stride_w, pad_top, pad_left, Ho, Wo);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.sy = stride_h; c.sx = stride_w; c.py = pad_top; c.px = pad_left; c.Ho = Ho; c.Wo = Wo;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_tstrided(const void* in, const void* w, const void* bias, const void* residual, void* out,
                                          const void* zeros, int T, int H, int W, int Cin, int Cout, int Kpad, int kT, int kH,
                                          int kW, int stride_t, int t_first, int To, apexmi_stream_t stream_) {
     APEXMI_REQUIRE(To > 0, "conv3d_cl_tstrided: empty output");
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 0, stream_, 1, 1, -1, -1, 0, 0,
-                          0, 0, nullptr, nullptr, 0, 0, 0.0f, stride_t, t_first, To);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.st = stride_t; c.t0 = t_first; c.To = To;
+    return conv_run(c, stream_);
 }
 
 // f32-storage verification mode, every variant of the convolution through one entry point: `in` = the three-way bf16
@@ -2211,15 +2271,25 @@ extern "C" int apexmi_conv3d_cl_f32(const void* in, const void* w, const void* b
                                     const void* zeros, int T, int H, int W, int Cin3, int Cout, int Kpad, int kT, int kH,
                                     int kW, int flags, int stride_h, int stride_w, int pad_top, int pad_left, int Ho, int Wo,
                                     int stride_t, int t_first, int To, int act, float slope, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin3, Cout, Kpad, kT, kH, kW, flags & 1, stream_,
-                          stride_h, stride_w, pad_top, pad_left, Ho, Wo, (flags >> 1) & 1, (flags >> 2) & 1, nullptr, nullptr, 0,
-                          act, slope, stride_t, t_first, To, 1);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin3; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.replicate = flags & 1; c.independent = (flags >> 1) & 1; c.up = (flags >> 2) & 1;
+    c.sy = stride_h; c.sx = stride_w; c.py = pad_top; c.px = pad_left; c.Ho = Ho; c.Wo = Wo;
+    c.st = stride_t; c.t0 = t_first; c.To = To;
+    c.act = act; c.act_slope = slope;
+    c.f32io = true;
+    return conv_run(c, stream_);
 }
 
 extern "C" int apexmi_conv3d_cl_replicate(const void* in, const void* w, const void* bias, const void* residual,
                                           void* out, const void* zeros, int T, int H, int W, int Cin, int Cout,
                                           int Kpad, int kT, int kH, int kW, apexmi_stream_t stream_) {
-    return conv3d_cl_impl(in, w, bias, residual, out, zeros, T, H, W, Cin, Cout, Kpad, kT, kH, kW, 1, stream_);
+    ConvCall c;
+    c.in = in; c.w = w; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.T = T; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.Kpad = Kpad; c.kT = kT; c.kH = kH; c.kW = kW;
+    c.replicate = 1;
+    return conv_run(c, stream_);
 }
 
 template <typename T>

@@ -2579,9 +2579,34 @@ def _conv_w3(w_packed: torch.Tensor, ksize, cin: int) -> torch.Tensor:
     return t
 
 
+def _conv_operands(who: str, x, w_packed, bias, residual=None, out=None, up: int = 1):
+    """The operand refusals the channels-last convolution wrappers share; returns (T, H, W, cin, cout, kpad).  residual and a
+    given out must have the output's shape [T, up H, up W, cout] (up = 2: the convolution reads x through the 2x upsample)."""
+    _req_act(x, f"{who}.x")
+    _req(w_packed, torch.bfloat16, f"{who}.w")
+    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
+    T, H, W, cin = x.shape
+    cout, kpad = w_packed.shape
+    if bias is not None:
+        assert bias.numel() == cout and bias.is_contiguous()
+    if residual is not None:
+        assert tuple(residual.shape) == (T, up * H, up * W, cout) and residual.is_contiguous()
+    if out is not None:
+        assert tuple(out.shape) == (T, up * H, up * W, cout) and out.is_contiguous()
+    return T, H, W, cin, cout, kpad
+
+
+def _conv_prefix(x, w_packed, bias, residual, out, dims, ksize) -> tuple:
+    """The 15 leading arguments of every apexmi_conv3d_cl* entry point; dims = (T, H, W, cin, cout, kpad) as _conv_operands
+    returns them."""
+    return (x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), _ptr(out), _zeros16(x.device).data_ptr(), *dims,
+            int(ksize[0]), int(ksize[1]), int(ksize[2]))
+
+
 def _conv_f32(x, w_packed, bias, ksize, out_shape, residual=None, out=None, replicate=False, independent_frames=False,
               upsample2x=False, stride=(1, 1), pad=(-1, -1), out_hw=(0, 0), tstride=(1, 0, 0), slope=None):
-    """The f32-storage verification form of every conv3d_cl* wrapper below: float activations in, float out / residual."""
+    """The f32-storage verification form of every conv3d_cl* wrapper below: float activations in, float out / residual.  The
+    wrappers have run _conv_operands; what is checked here is the float storage."""
     _req(x, torch.float32, "conv3d_cl.x")
     T, H, W, cin = x.shape
     x3 = split3(x.view(T * H * W, cin)).view(T, H, W, 3 * cin)
@@ -2594,9 +2619,8 @@ def _conv_f32(x, w_packed, bias, ksize, out_shape, residual=None, out=None, repl
         _req(residual, torch.float32, "conv3d_cl.residual")
         assert residual.shape == out.shape and residual.is_contiguous()
     flags = (1 if replicate else 0) | (2 if independent_frames else 0) | (4 if upsample2x else 0)
-    rc = _l.load().apexmi_conv3d_cl_f32(x3.data_ptr(), w3.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                        _zeros16(x.device).data_ptr(), T, H, W, 3 * cin, cout, w3.shape[1], int(ksize[0]),
-                                        int(ksize[1]), int(ksize[2]), flags, int(stride[0]), int(stride[1]), int(pad[0]),
+    rc = _l.load().apexmi_conv3d_cl_f32(*_conv_prefix(x3, w3, bias, residual, out, (T, H, W, 3 * cin, cout, w3.shape[1]), ksize),
+                                        flags, int(stride[0]), int(stride[1]), int(pad[0]),
                                         int(pad[1]), int(out_hw[0]), int(out_hw[1]), int(tstride[0]), int(tstride[1]),
                                         int(tstride[2]), 0 if slope is None else 1, 0.0 if slope is None else float(slope),
                                         _stream())
@@ -2612,12 +2636,10 @@ def conv3d_cl(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tens
     clamped coordinates as HunyuanVideo15CausalConv3d pads.  upsample2x: the convolution reads x through a nearest 2x
     spatial upsample (output [T,2H,2W,Cout4]) without materialising it.  clip_frames: the T frames are T / clip_frames
     independent clips stacked along T (the tiles of a tiled decode in one launch, `apexmi_conv3d_cl_clips`)."""
-    _req_act(x, "conv3d_cl.x")
-    _req(w_packed, torch.bfloat16, "conv3d_cl.w")
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
-    T, H, W, cin = x.shape
-    cout, kpad = w_packed.shape
-    Ho, Wo = (2 * H, 2 * W) if upsample2x else (H, W)
+    up = 2 if upsample2x else 1
+    dims = _conv_operands("conv3d_cl", x, w_packed, bias, residual, out, up)
+    T, H, W, cin, cout, kpad = dims
+    shape = (T, up * H, up * W, cout)
     if x.dtype == torch.float32 and _shipped_verify and not (clip_frames and clip_frames != T):
         # verification through the shipped convolution tiles (slab / conv-shaped / 128x128, whichever production picks for this
         # shape): bf16 rounding of the float input, the kernel's bf16 result widened; the residual is added in float
@@ -2633,35 +2655,21 @@ def conv3d_cl(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tens
         assert not (replicate and independent_frames) and not (replicate and upsample2x)
         if clip_frames and clip_frames != T:
             raise _l.ApexMIError("conv3d_cl: stacked clips are not part of the f32-storage verification mode")
-        return _conv_f32(x, w_packed, bias, ksize, (T, Ho, Wo, cout), residual=residual, out=out, replicate=replicate,
+        return _conv_f32(x, w_packed, bias, ksize, shape, residual=residual, out=out, replicate=replicate,
                          independent_frames=independent_frames, upsample2x=upsample2x)
     if out is None:
-        out = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
-    assert out.is_contiguous() and out.shape == (T, Ho, Wo, cout)
-    if bias is not None:
-        assert bias.numel() == cout and bias.is_contiguous()
-    if residual is not None:
-        assert residual.shape == out.shape and residual.is_contiguous()
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
     assert not (replicate and independent_frames) and not (replicate and upsample2x)
+    args, lib = _conv_prefix(x, w_packed, bias, residual, out, dims, ksize), _l.load()
     if upsample2x:
-        rc = _l.load().apexmi_conv3d_cl_up2(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                            _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, int(ksize[0]),
-                                            int(ksize[1]), int(ksize[2]), 1 if independent_frames else 0, _stream())
-        _l.check(rc, "conv3d_cl_up2")
+        _l.check(lib.apexmi_conv3d_cl_up2(*args, 1 if independent_frames else 0, _stream()), "conv3d_cl_up2")
         return out
     if clip_frames and clip_frames != T:
         assert not independent_frames and T % int(clip_frames) == 0
-        rc = _l.load().apexmi_conv3d_cl_clips(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                              _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, int(ksize[0]),
-                                              int(ksize[1]), int(ksize[2]), 1 if replicate else 0, int(clip_frames), _stream())
-        _l.check(rc, "conv3d_cl_clips")
+        _l.check(lib.apexmi_conv3d_cl_clips(*args, 1 if replicate else 0, int(clip_frames), _stream()), "conv3d_cl_clips")
         return out
-    fn = (_l.load().apexmi_conv3d_cl_replicate if replicate else
-          _l.load().apexmi_conv3d_cl_frames if independent_frames else _l.load().apexmi_conv3d_cl)
-    rc = fn(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-            _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, int(ksize[0]), int(ksize[1]), int(ksize[2]),
-            _stream())
-    _l.check(rc, "conv3d_cl")
+    fn = lib.apexmi_conv3d_cl_replicate if replicate else lib.apexmi_conv3d_cl_frames if independent_frames else lib.apexmi_conv3d_cl
+    _l.check(fn(*args, _stream()), "conv3d_cl")
     return out
 
 
@@ -2670,23 +2678,16 @@ def conv3d_cl_act(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.
                   independent_frames: bool = False) -> torch.Tensor:
     """act(conv(x) + bias (+ residual)) with act = leaky ReLU(slope) (slope None: no activation), zero padding, causal in
     time; upsample2x / independent_frames as conv3d_cl.  The TAEHV blocks (reference vae/tae/model.py:20-45)."""
-    _req_act(x, "conv3d_cl_act.x")
-    _req(w_packed, torch.bfloat16, "conv3d_cl_act.w")
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
-    T, H, W, cin = x.shape
-    cout, kpad = w_packed.shape
-    Ho, Wo = (2 * H, 2 * W) if upsample2x else (H, W)
+    up = 2 if upsample2x else 1
+    dims = _conv_operands("conv3d_cl_act", x, w_packed, bias, residual, None, up)
+    T, H, W, cin, cout, kpad = dims
+    shape = (T, up * H, up * W, cout)
     if x.dtype == torch.float32:
-        return _conv_f32(x, w_packed, bias, ksize, (T, Ho, Wo, cout), residual=residual, independent_frames=independent_frames,
+        return _conv_f32(x, w_packed, bias, ksize, shape, residual=residual, independent_frames=independent_frames,
                          upsample2x=upsample2x, slope=slope)
-    out = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
-    if bias is not None:
-        assert bias.numel() == cout and bias.is_contiguous()
-    if residual is not None:
-        assert residual.shape == out.shape and residual.is_contiguous()
-    rc = _l.load().apexmi_conv3d_cl_act(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), out.data_ptr(),
-                                        _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, int(ksize[0]), int(ksize[1]),
-                                        int(ksize[2]), 1 if independent_frames else 0, 1 if upsample2x else 0,
+    out = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+    rc = _l.load().apexmi_conv3d_cl_act(*_conv_prefix(x, w_packed, bias, residual, out, dims, ksize),
+                                        1 if independent_frames else 0, 1 if upsample2x else 0,
                                         0 if slope is None else 1, 0.0 if slope is None else float(slope), _stream())
     _l.check(rc, "conv3d_cl_act")
     return out
@@ -2748,9 +2749,10 @@ def conv3d_cl_norm(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch
                    upsample2x: bool = False, independent_frames: bool = False):
     """conv3d_cl with the RMS norm (+ SiLU) of its output fused into the epilogue: returns (y or None, norm(y)).
     Shapes the fused tiles do not cover (`conv3d_cl_norm_fusable`) run as conv3d_cl + rmsnorm_cl — same values."""
-    _req_act(x, "conv3d_cl_norm.x")
+    up = 2 if upsample2x else 1
+    dims = _conv_operands("conv3d_cl_norm", x, w_packed, bias, residual, None, up)
     _req(gamma, torch.bfloat16, "conv3d_cl_norm.gamma")
-    cout, kpad = w_packed.shape
+    T, H, W, cin, cout, kpad = dims
     if (x.dtype == torch.float32 and _shipped_verify and gamma.numel() == cout and conv3d_cl_norm_fusable(x, cout, upsample2x)):
         # verification through the shipped FUSED tile: conv + bias (+ bf16-rounded residual, as production holds it) + RMS norm
         # (+ SiLU) in one epilogue on the bf16 rounding of the float input; both results widened
@@ -2767,17 +2769,12 @@ def conv3d_cl_norm(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch
                                  f"fused / separate RMS norm needs the layer's channel count to equal the packed one")
         y = conv3d_cl(x, w_packed, bias, ksize, residual=residual, upsample2x=upsample2x, independent_frames=independent_frames)
         return (y if want_raw else None), rmsnorm_cl(y, gamma, silu=silu)
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous() and gamma.is_contiguous()
-    T, H, W, cin = x.shape
-    Ho, Wo = (2 * H, 2 * W) if upsample2x else (H, W)
-    y = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device) if want_raw else None
-    yn = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
-    if residual is not None:
-        assert residual.shape == yn.shape and residual.is_contiguous()
-    rc = _l.load().apexmi_conv3d_cl_norm(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), _ptr(residual), _ptr(y), yn.data_ptr(),
-                                         gamma.data_ptr(), 1 if silu else 0, _zeros16(x.device).data_ptr(), T, H, W, cin, cout,
-                                         kpad, int(ksize[0]), int(ksize[1]), int(ksize[2]), 1 if independent_frames else 0,
-                                         1 if upsample2x else 0, _stream())
+    assert gamma.is_contiguous()
+    y = torch.empty((T, up * H, up * W, cout), dtype=torch.bfloat16, device=x.device) if want_raw else None
+    yn = torch.empty((T, up * H, up * W, cout), dtype=torch.bfloat16, device=x.device)
+    args = _conv_prefix(x, w_packed, bias, residual, y, dims, ksize)
+    rc = _l.load().apexmi_conv3d_cl_norm(*args[:5], yn.data_ptr(), gamma.data_ptr(), 1 if silu else 0, *args[5:],
+                                         1 if independent_frames else 0, 1 if upsample2x else 0, _stream())
     _l.check(rc, "conv3d_cl_norm")
     return y, yn
 
@@ -2786,63 +2783,42 @@ def conv3d_cl_tstrided(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[t
                        t_first: int, out_frames: int) -> torch.Tensor:
     """Causal conv3d evaluated only at input frames t_first, t_first + stride_t, ...: x [T,H,W,Cin] -> [out_frames,H,W,Cout4]
     (WanResample "downsample3d" time_conv, reference vae/wan/model.py:340-365)."""
-    _req_act(x, "conv3d_cl_tstrided.x")
-    _req(w_packed, torch.bfloat16, "conv3d_cl_tstrided.w")
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
-    T, H, W, cin = x.shape
-    cout, kpad = w_packed.shape
+    dims = _conv_operands("conv3d_cl_tstrided", x, w_packed, bias)
+    T, H, W, cin, cout, kpad = dims
     if x.dtype == torch.float32:
         return _conv_f32(x, w_packed, bias, ksize, (out_frames, H, W, cout), tstride=(stride_t, t_first, out_frames))
     out = torch.empty((out_frames, H, W, cout), dtype=torch.bfloat16, device=x.device)
-    if bias is not None:
-        assert bias.numel() == cout and bias.is_contiguous()
-    rc = _l.load().apexmi_conv3d_cl_tstrided(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), None, out.data_ptr(),
-                                             _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, int(ksize[0]), int(ksize[1]),
-                                             int(ksize[2]), int(stride_t), int(t_first), int(out_frames), _stream())
+    rc = _l.load().apexmi_conv3d_cl_tstrided(*_conv_prefix(x, w_packed, bias, None, out, dims, ksize), int(stride_t), int(t_first),
+                                             int(out_frames), _stream())
     _l.check(rc, "conv3d_cl_tstrided")
+    return out
+
+
+def _conv2d_cl_strided(who: str, x, w_packed, bias, stride: int, pad: int, extent) -> torch.Tensor:
+    """The one body of conv2d_cl_down2 / conv2d_cl_strided: a 3x3 per-frame convolution with `pad` zero rows / columns above /
+    left, `stride` both ways; extent: input height / width -> the output's (each wrapper's own formula)."""
+    dims = _conv_operands(who, x, w_packed, bias)
+    T, H, W, cin, cout, kpad = dims
+    Ho, Wo = extent(H), extent(W)
+    if x.dtype == torch.float32:
+        return _conv_f32(x, w_packed, bias, (1, 3, 3), (T, Ho, Wo, cout), stride=(stride, stride), pad=(pad, pad), out_hw=(Ho, Wo))
+    out = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
+    rc = _l.load().apexmi_conv3d_cl_strided(*_conv_prefix(x, w_packed, bias, None, out, dims, (1, 3, 3)), stride, stride, pad, pad,
+                                            Ho, Wo, _stream())
+    _l.check(rc, "conv3d_cl_strided")
     return out
 
 
 def conv2d_cl_down2(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
     """ZeroPad2d((0, 1, 0, 1)) + Conv2d(3x3, stride 2) per frame: x [T, H, W, Cin] -> [T, Ho, Wo, Cout4] with
     Ho = (H - 2) // 2 + 1 (= H / 2 for even H); w_packed from pack_conv_weight of the [Cout, Cin, 3, 3] weight."""
-    _req_act(x, "conv2d_cl_down2.x")
-    _req(w_packed, torch.bfloat16, "conv2d_cl_down2.w")
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
-    T, H, W, cin = x.shape
-    cout, kpad = w_packed.shape
-    Ho, Wo = (H - 2) // 2 + 1, (W - 2) // 2 + 1
-    if x.dtype == torch.float32:
-        return _conv_f32(x, w_packed, bias, (1, 3, 3), (T, Ho, Wo, cout), stride=(2, 2), pad=(0, 0), out_hw=(Ho, Wo))
-    out = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
-    if bias is not None:
-        assert bias.numel() == cout and bias.is_contiguous()
-    rc = _l.load().apexmi_conv3d_cl_strided(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), None, out.data_ptr(),
-                                            _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, 1, 3, 3, 2, 2, 0, 0,
-                                            Ho, Wo, _stream())
-    _l.check(rc, "conv3d_cl_strided")
-    return out
+    return _conv2d_cl_strided("conv2d_cl_down2", x, w_packed, bias, 2, 0, lambda n: (n - 2) // 2 + 1)
 
 
 def conv2d_cl_strided(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], stride: int = 2, pad: int = 1) -> torch.Tensor:
     """nn.Conv2d(3x3, stride, padding=pad) per frame: x [T, H, W, Cin] -> [T, Ho, Wo, Cout4], Ho = (H + 2 pad - 3) // stride + 1
     (the TAEHV encoder's downsampling convolutions, reference vae/tae/model.py:218, :223, :228)."""
-    _req_act(x, "conv2d_cl_strided.x")
-    _req(w_packed, torch.bfloat16, "conv2d_cl_strided.w")
-    assert x.dim() == 4 and x.is_contiguous() and w_packed.is_contiguous()
-    T, H, W, cin = x.shape
-    cout, kpad = w_packed.shape
-    Ho, Wo = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
-    if x.dtype == torch.float32:
-        return _conv_f32(x, w_packed, bias, (1, 3, 3), (T, Ho, Wo, cout), stride=(stride, stride), pad=(pad, pad), out_hw=(Ho, Wo))
-    out = torch.empty((T, Ho, Wo, cout), dtype=torch.bfloat16, device=x.device)
-    if bias is not None:
-        assert bias.numel() == cout and bias.is_contiguous()
-    rc = _l.load().apexmi_conv3d_cl_strided(x.data_ptr(), w_packed.data_ptr(), _ptr(bias), None, out.data_ptr(),
-                                            _zeros16(x.device).data_ptr(), T, H, W, cin, cout, kpad, 1, 3, 3, stride, stride, pad, pad,
-                                            Ho, Wo, _stream())
-    _l.check(rc, "conv3d_cl_strided")
-    return out
+    return _conv2d_cl_strided("conv2d_cl_strided", x, w_packed, bias, stride, pad, lambda n: (n + 2 * pad - 3) // stride + 1)
 
 
 def rmsnorm_cl(x: torch.Tensor, gamma: torch.Tensor, silu: bool = False,
