@@ -1,7 +1,7 @@
 // What the block-scaled-MFMA GEMMs share: the 128 x 128 output tile with 128-byte K-tiles, the operand record of ONE
-// product and the f32 epilogue on the 32 x 32 result layout.  Included by gemm_fp8.hip (e4m3 x e4m3, every form) and gemm_mxfp4.hip
-// (e2m1 x e2m1): the result layout of v_mfma_scale_f32_32x32x64_f8f6f4 does not depend on the operand format, so one epilogue
-// serves both.
+// product, the f32 epilogue on the 32 x 32 result layout, and the grouped form's table entry with its fused q/k/v preparation.
+// Included by gemm_fp8.hip (e4m3 x e4m3, every form) and gemm_mxfp4.hip (e2m1 x e2m1, single and grouped): the result layout of
+// v_mfma_scale_f32_32x32x64_f8f6f4 does not depend on the operand format, so one epilogue serves both.
 #pragma once
 #include "common.h"
 #include "fp8_quant.h"   // the MX output of the epilogue
@@ -220,6 +220,165 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
     }
 }
 
+// ---- the grouped form: what the table of either kernel holds per problem, and the fused q/k/v preparation ----
+constexpr int FP8_MAX_GROUPS = 4;
+
+// One problem of a grouped launch (Fp8Group in gemm_fp8.hip, Mxfp4Group in gemm_mxfp4.hip): up to 4 problems that share K in ONE
+// launch (the img + txt streams of a Flux double block, QKV + MLP-up of a single block).  The table travels by value in the kernel
+// arguments.  xcd_remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts
+// (tile0), and the epilogue (bias | gelu | gate_res) is chosen per problem: a block-uniform branch.
+struct Fp8GroupProblem : Fp8Problem {
+    int epi, tile0;
+    // fused q/k/v preparation (apexmi_gemm_fp8_grouped_qkv, apexmi_gemm_mxfp4_grouped_qkv): N = 3 H 128, rows [row0, row0 + M) of the
+    // joint sequence, nq / nk = the per-head RMSNorm weights of this problem's stream (or null).  C is not written.
+    int qkv, row0;
+    const bf16_t* nq;
+    const bf16_t* nk;
+};
+struct Fp8QkvShared {        // outputs of the fused preparation, shared by the problems of a launch
+    bf16_t* qo;              // [H, S_out, 128]
+    bf16_t* ko;              // [H, S_out, 128]
+    bf16_t* vt;              // [H, 128, Skp]
+    const float* rope;       // [2, S_out, 128] f32 (cos | sin), interleaved pairs
+    int S_out, Skp, inner;   // inner = H * 128
+    float eps;
+};
+
+// the table entry of this workgroup among `count` entries `p` (anything derived from Fp8GroupProblem) of a launch of `total` tiles;
+// `t` = its tile id inside that problem
+template <class Entry>
+APEXMI_DEVICE Entry fp8_group_entry(const Entry (&p)[FP8_MAX_GROUPS], int count, int total, int& t, int& pi) {
+    t = xcd_remap(blockIdx.x, total);
+    pi = 0;
+#pragma unroll
+    for (int i = 1; i < FP8_MAX_GROUPS; ++i)
+        if (i < count && t >= p[i].tile0) pi = i;
+    const Entry P = p[pi];
+    t -= P.tile0;
+    return P;
+}
+
+// Fused q/k/v preparation on a tile of a problem flagged `qkv` (N = 3 H 128: a 128-column tile is exactly one head of q, of k or
+// of v, which = n0 / inner is block-uniform).  The tile y = bf16(acc * sa * sw + bias) — the value the two-pass path stores — goes
+// into the staging LDS (free after the K-loop's last barrier) as [128 rows][128 bf16], row r rotated by rot(r) = (r >> 3) +
+// 2 (r & 7) sixteen-byte chunks: the 16 consecutive rows of a store phase and the 8 position chunks of a transposed read each
+// land on different chunks.
+//   q / k: re-read in the layout of qk_norm_rope4_body (elementwise.hip): 16 lanes per row, 8 consecutive columns per lane, the
+//          sequential sum of squares, the xor butterfly 8, 4, 2, 1, rsqrtf(sq / 128 + eps), x * r * w, the two fmaf forms of the
+//          interleaved rotation and a 16-byte store into [H, S_out, 128] at row row0 + m: bit-identical to that pass.
+//   v:     read transposed, 8 consecutive positions per lane, 16-byte stores into [H, 128, Skp]; a stream whose row0 | M is not
+//          a multiple of 8 stores element-wise (a wave = 64 consecutive positions of one d-row).
+// Rows >= M store nothing; columns >= S_out of V^T are not written.
+// not SCALED (a problem of the grouped LoRA form that carried an adapter, and every problem of the fp4 kernel, whose block scales
+// the MFMA applied): the scales (and the adapter term) are in acc already, y = bf16(acc + bias), and the staging LDS is free after
+// the last barrier of the tail / the K-loop.
+APEXMI_DEVICE int fp8_qkv_rot(int r) { return (r >> 3) + 2 * (r & 7); }
+
+template <bool SCALED>
+APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupProblem& G, const Fp8QkvShared& Q, int m0, int n0, int tid,
+                                    uint8_t* lds) {
+    bf16_t* tile = (bf16_t*)lds;
+    const int lane = tid & 63, wid = tid >> 6;
+    const int wr = wid >> 1, wc = wid & 1, fr = lane & 31, fh = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        float sw[4][4], bs[4][4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;          // N % 128 == 0: every column of the tile exists
+            if constexpr (SCALED) fp8_load_sw(G, n, sw[g]);
+            fp8_load_bias(G, n, bs[g]);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r = 64 * wr + 32 * j + fr;
+            float sa = 1.f;
+            if constexpr (SCALED) sa = G.sa[min(m0 + r, G.M - 1)];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int c = 64 * wc + 32 * i + 8 * g + 4 * fh;
+                float o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if constexpr (SCALED) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
+                    else o[e] = acc[i][j][4 * g + e] + bs[g][e];
+                }
+                *(u32x2*)(tile + r * 128 + ((((c >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (c & 4)) =
+                    u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
+            }
+        }
+    }
+    __syncthreads();
+    const int which = n0 / Q.inner;                    // 0 q, 1 k, 2 v: block-uniform
+    const int h = (n0 - which * Q.inner) >> 7;
+    if (which == 2) {
+        bf16_t* vt = Q.vt + (int64_t)h * 128 * Q.Skp + G.row0 + m0;
+        if (((G.row0 | G.M) & 7) != 0) {
+            for (int i = 0; i < 64; ++i) {
+                const int idx = i * 256 + tid;
+                const int r = idx & 127, d = idx >> 7;
+                const bf16_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
+                if (m0 + r < G.M) vt[(int64_t)d * Q.Skp + r] = e;
+            }
+            return;
+        }
+#pragma unroll 2
+        for (int i = 0; i < 8; ++i) {
+            const int idx = i * 256 + tid;
+            const int sc = idx & 7, d = (idx >> 3) & 127, s8 = ((idx >> 10) * 8 + sc) * 8;     // 8 lanes = 8 position chunks of one d
+            uint32_t w[4];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int r = s8 + j;
+                const uint32_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
+                if (j & 1) w[j >> 1] |= e << 16;
+                else w[j >> 1] = e;
+            }
+            if (m0 + s8 < G.M) *(u32x4*)(vt + (int64_t)d * Q.Skp + s8) = u32x4{w[0], w[1], w[2], w[3]};
+        }
+        return;
+    }
+    const bf16_t* nw = which ? G.nk : G.nq;
+    bf16_t* dst = (which ? Q.ko : Q.qo) + (int64_t)h * Q.S_out * 128;
+    const int l16 = tid & 15, d = l16 * 8;
+    float wv[8];
+    if (nw != nullptr) unpack8(*(const u32x4*)(nw + d), wv);
+#pragma unroll 2
+    for (int p = 0; p < 8; ++p) {
+        const int r = p * 16 + (tid >> 4);
+        const int srow = G.row0 + min(m0 + r, G.M - 1);
+        const float* cp = Q.rope + (int64_t)srow * 128 + d;
+        const float* sp = Q.rope + (int64_t)Q.S_out * 128 + (int64_t)srow * 128 + d;
+        const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
+        const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
+        float cs[8], sn[8], x[8], y[8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            cs[j] = c0[j];
+            cs[j + 4] = c1[j];
+            sn[j] = s0[j];
+            sn[j + 4] = s1[j];
+        }
+        unpack8(*(const u32x4*)(tile + r * 128 + (((l16 + fp8_qkv_rot(r)) & 15) << 3)), x);
+        if (nw != nullptr) {
+            float sq = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sq += x[j] * x[j];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+            const float rn = rsqrtf(sq * (1.0f / 128) + Q.eps);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] = x[j] * rn * wv[j];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            y[2 * q] = fmaf(x[2 * q], cs[2 * q], -(x[2 * q + 1] * sn[2 * q]));
+            y[2 * q + 1] = fmaf(x[2 * q + 1], cs[2 * q + 1], x[2 * q] * sn[2 * q + 1]);
+        }
+        if (m0 + r < G.M) store8<bf16_t>(dst + (int64_t)srow * 128 + d, y);
+    }
+}
+
 // ---- host side: the checks of ONE problem that do not depend on the operand format, and the launch by epilogue ----
 // how the messages name a problem: `i` = its index in a grouped launch, or -1 for a single launch (every fragment empty)
 struct Fp8Where {
@@ -274,6 +433,47 @@ static int fp8_check_tile_problem(const char* who, const Fp8Where& at, const Fp8
     APEXMI_REQUIRE(tile0 + (int64_t)tm * tn < (1ll << 31), "%s: too many output tiles", who);
     *P = Fp8Problem{(const uint8_t*)qa, (const uint8_t*)qw, nullptr, nullptr, (const bf16_t*)bias, (bf16_t*)C, gate, (const bf16_t*)R,
                     lda, ldw, ldc, ldr, M, N, K, 0, tm, tn};
+    return 0;
+}
+
+// the fused q/k/v operands of a grouped launch as the entry points take them (apexmi_gemm_fp8_grouped_qkv(_lora),
+// apexmi_gemm_mxfp4_grouped_qkv), and their checks: the launch's shared part, then problem `i` if it is flagged
+struct Fp8QkvArgs {
+    const int* is_qkv;
+    const void* const* norm_q;
+    const void* const* norm_k;
+    const int* row0;
+    int H;
+    float eps;
+    const float* rope;
+    void* q_out;
+    void* k_out;
+    void* vt_out;
+    int S_out, Skp;
+};
+
+static int fp8_check_qkv_shared(const char* who, const Fp8QkvArgs& q, Fp8QkvShared* S) {
+    APEXMI_REQUIRE(q.is_qkv && q.row0 && q.rope && q.q_out && q.k_out && q.vt_out && q.H > 0, "%s: null argument", who);
+    APEXMI_REQUIRE(q.S_out > 0 && q.Skp >= q.S_out && q.Skp % 8 == 0, "%s: Skp=%d must be a multiple of 8 >= S_out=%d", who, q.Skp, q.S_out);
+    APEXMI_REQUIRE(((uintptr_t)q.rope % 16) == 0 && ((uintptr_t)q.q_out % 16) == 0 && ((uintptr_t)q.k_out % 16) == 0 &&
+                       ((uintptr_t)q.vt_out % 16) == 0,
+                   "%s: rope / outputs must be 16-byte aligned", who);
+    *S = Fp8QkvShared{(bf16_t*)q.q_out, (bf16_t*)q.k_out, (bf16_t*)q.vt_out, q.rope, q.S_out, q.Skp, q.H * 128, q.eps};
+    return 0;
+}
+
+static int fp8_check_qkv_problem(const char* who, const Fp8QkvArgs& q, int i, Fp8GroupProblem* P) {
+    APEXMI_REQUIRE(P->N == 3 * q.H * 128 && P->epi == APEXMI_EPI_BIAS,
+                   "%s: a fused problem has N = 3 H 128 = %d (got %d) and the plain bias epilogue", who, 3 * q.H * 128, P->N);
+    APEXMI_REQUIRE(q.row0[i] >= 0 && q.row0[i] + P->M <= q.S_out, "%s: rows [%d, %d) must lie inside S_out=%d", who, q.row0[i],
+                   q.row0[i] + P->M, q.S_out);
+    const void* nq = q.norm_q ? q.norm_q[i] : nullptr;
+    const void* nk = q.norm_k ? q.norm_k[i] : nullptr;
+    APEXMI_REQUIRE(((uintptr_t)nq % 16) == 0 && ((uintptr_t)nk % 16) == 0, "%s: norm weights must be 16-byte aligned", who);
+    P->qkv = 1;
+    P->row0 = q.row0[i];
+    P->nq = (const bf16_t*)nq;
+    P->nk = (const bf16_t*)nk;
     return 0;
 }
 

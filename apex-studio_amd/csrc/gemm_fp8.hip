@@ -68,8 +68,6 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
 // l & 31, byte j of the 32 = k offset j.  The result layout is the 32 x 32 one of every gfx950 MFMA: column l & 31, rows
 // (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).  As in the bf16 kernels the WEIGHT tile is the A operand, so a lane holds 4 consecutive
 // output columns of one output row per register group and stores them as 8 bytes.
-constexpr int FP8_MAX_GROUPS = 4;
-
 // a single launch (apexmi_gemm_fp8)
 struct Fp8Gemm : Fp8Problem {
     unsigned long long* clk;
@@ -88,26 +86,7 @@ struct Fp8LoraGemm : Fp8Gemm {
     int Rp;               // padded rank, a multiple of 64
 };
 
-// The grouped form (apexmi_gemm_fp8_grouped, apexmi_gemm_fp8_grouped_qkv): up to 4 problems that share K in ONE launch (the img +
-// txt streams of a Flux double block, QKV + MLP-up of a single block).  The table travels by value in the kernel arguments.
-// xcd_remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile counts (tile0), and the
-// epilogue (bias | gelu | gate_res) is chosen per problem: a block-uniform branch.
-struct Fp8GroupProblem : Fp8Problem {
-    int epi, tile0;
-    // fused q/k/v preparation (apexmi_gemm_fp8_grouped_qkv): N = 3 H 128, rows [row0, row0 + M) of the joint sequence, nq / nk = the
-    // per-head RMSNorm weights of this problem's stream (or null).  C is not written.
-    int qkv, row0;
-    const bf16_t* nq;
-    const bf16_t* nk;
-};
-struct Fp8QkvShared {        // outputs of the fused preparation, shared by the problems of a launch
-    bf16_t* qo;              // [H, S_out, 128]
-    bf16_t* ko;              // [H, S_out, 128]
-    bf16_t* vt;              // [H, 128, Skp]
-    const float* rope;       // [2, S_out, 128] f32 (cos | sin), interleaved pairs
-    int S_out, Skp, inner;   // inner = H * 128
-    float eps;
-};
+// The grouped form (apexmi_gemm_fp8_grouped, apexmi_gemm_fp8_grouped_qkv): a table of Fp8GroupProblem (fp8_gemm_tile.h)
 struct Fp8Group {
     Fp8GroupProblem p[FP8_MAX_GROUPS];
     int count, total;
@@ -156,14 +135,7 @@ APEXMI_DEVICE const Fp8Gemm& fp8_problem(const Fp8Gemm& G, int& t, int& pi) {
     return G;
 }
 APEXMI_DEVICE Fp8GroupProblem fp8_problem(const Fp8Group& G, int& t, int& pi) {
-    t = xcd_remap(blockIdx.x, G.total);
-    pi = 0;
-#pragma unroll
-    for (int i = 1; i < FP8_MAX_GROUPS; ++i)
-        if (i < G.count && t >= G.p[i].tile0) pi = i;
-    const Fp8GroupProblem P = G.p[pi];
-    t -= P.tile0;
-    return P;
+    return fp8_group_entry(G.p, G.count, G.total, t, pi);
 }
 
 // the adapter operands of this workgroup's problem: the launch's own (Fp8LoraGemm) or entry `pi` of the table (Fp8LoraGroup)
@@ -171,126 +143,6 @@ APEXMI_DEVICE const Fp8LoraGemm& fp8_lora_entry(const Fp8LoraGemm& G, int) { ret
 APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8LoraGroup& G, int pi) { return G.lora[pi]; }
 APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8Problem&, int) { return Fp8LoraEntry{}; }
 APEXMI_DEVICE Fp8LoraEntry fp8_lora_entry(const Fp8Group&, int) { return Fp8LoraEntry{}; }
-
-// Fused q/k/v preparation on a tile of a problem flagged `qkv` (N = 3 H 128: a 128-column tile is exactly one head of q, of k or
-// of v, which = n0 / inner is block-uniform).  The tile y = bf16(acc * sa * sw + bias) — the value the two-pass path stores — goes
-// into the staging LDS (free after the K-loop's last barrier) as [128 rows][128 bf16], row r rotated by rot(r) = (r >> 3) +
-// 2 (r & 7) sixteen-byte chunks: the 16 consecutive rows of a store phase and the 8 position chunks of a transposed read each
-// land on different chunks.
-//   q / k: re-read in the layout of qk_norm_rope4_body (elementwise.hip): 16 lanes per row, 8 consecutive columns per lane, the
-//          sequential sum of squares, the xor butterfly 8, 4, 2, 1, rsqrtf(sq / 128 + eps), x * r * w, the two fmaf forms of the
-//          interleaved rotation and a 16-byte store into [H, S_out, 128] at row row0 + m: bit-identical to that pass.
-//   v:     read transposed, 8 consecutive positions per lane, 16-byte stores into [H, 128, Skp]; a stream whose row0 | M is not
-//          a multiple of 8 stores element-wise (a wave = 64 consecutive positions of one d-row).
-// Rows >= M store nothing; columns >= S_out of V^T are not written.
-// not SCALED (a problem of the grouped LoRA form that carried an adapter): the scales and the adapter term are in acc already, y =
-// bf16(acc + bias), and the staging LDS is free after the TAIL's last barrier.
-APEXMI_DEVICE int fp8_qkv_rot(int r) { return (r >> 3) + 2 * (r & 7); }
-
-template <bool SCALED>
-APEXMI_DEVICE void fp8_qkv_epilogue(const f32x16 (&acc)[2][2], const Fp8GroupProblem& G, const Fp8QkvShared& Q, int m0, int n0, int tid,
-                                    uint8_t* lds) {
-    bf16_t* tile = (bf16_t*)lds;
-    const int lane = tid & 63, wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1, fr = lane & 31, fh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        float sw[4][4], bs[4][4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int n = n0 + 64 * wc + 32 * i + 8 * g + 4 * fh;          // N % 128 == 0: every column of the tile exists
-            if constexpr (SCALED) fp8_load_sw(G, n, sw[g]);
-            fp8_load_bias(G, n, bs[g]);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int r = 64 * wr + 32 * j + fr;
-            float sa = 1.f;
-            if constexpr (SCALED) sa = G.sa[min(m0 + r, G.M - 1)];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c = 64 * wc + 32 * i + 8 * g + 4 * fh;
-                float o[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if constexpr (SCALED) o[e] = acc[i][j][4 * g + e] * sa * sw[g][e] + bs[g][e];
-                    else o[e] = acc[i][j][4 * g + e] + bs[g][e];
-                }
-                *(u32x2*)(tile + r * 128 + ((((c >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (c & 4)) =
-                    u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
-            }
-        }
-    }
-    __syncthreads();
-    const int which = n0 / Q.inner;                    // 0 q, 1 k, 2 v: block-uniform
-    const int h = (n0 - which * Q.inner) >> 7;
-    if (which == 2) {
-        bf16_t* vt = Q.vt + (int64_t)h * 128 * Q.Skp + G.row0 + m0;
-        if (((G.row0 | G.M) & 7) != 0) {
-            for (int i = 0; i < 64; ++i) {
-                const int idx = i * 256 + tid;
-                const int r = idx & 127, d = idx >> 7;
-                const bf16_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
-                if (m0 + r < G.M) vt[(int64_t)d * Q.Skp + r] = e;
-            }
-            return;
-        }
-#pragma unroll 2
-        for (int i = 0; i < 8; ++i) {
-            const int idx = i * 256 + tid;
-            const int sc = idx & 7, d = (idx >> 3) & 127, s8 = ((idx >> 10) * 8 + sc) * 8;     // 8 lanes = 8 position chunks of one d
-            uint32_t w[4];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int r = s8 + j;
-                const uint32_t e = tile[r * 128 + ((((d >> 3) + fp8_qkv_rot(r)) & 15) << 3) + (d & 7)];
-                if (j & 1) w[j >> 1] |= e << 16;
-                else w[j >> 1] = e;
-            }
-            if (m0 + s8 < G.M) *(u32x4*)(vt + (int64_t)d * Q.Skp + s8) = u32x4{w[0], w[1], w[2], w[3]};
-        }
-        return;
-    }
-    const bf16_t* nw = which ? G.nk : G.nq;
-    bf16_t* dst = (which ? Q.ko : Q.qo) + (int64_t)h * Q.S_out * 128;
-    const int l16 = tid & 15, d = l16 * 8;
-    float wv[8];
-    if (nw != nullptr) unpack8(*(const u32x4*)(nw + d), wv);
-#pragma unroll 2
-    for (int p = 0; p < 8; ++p) {
-        const int r = p * 16 + (tid >> 4);
-        const int srow = G.row0 + min(m0 + r, G.M - 1);
-        const float* cp = Q.rope + (int64_t)srow * 128 + d;
-        const float* sp = Q.rope + (int64_t)Q.S_out * 128 + (int64_t)srow * 128 + d;
-        const f32x4 c0 = *(const f32x4*)cp, c1 = *(const f32x4*)(cp + 4);
-        const f32x4 s0 = *(const f32x4*)sp, s1 = *(const f32x4*)(sp + 4);
-        float cs[8], sn[8], x[8], y[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            cs[j] = c0[j];
-            cs[j + 4] = c1[j];
-            sn[j] = s0[j];
-            sn[j + 4] = s1[j];
-        }
-        unpack8(*(const u32x4*)(tile + r * 128 + (((l16 + fp8_qkv_rot(r)) & 15) << 3)), x);
-        if (nw != nullptr) {
-            float sq = 0.0f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) sq += x[j] * x[j];
-#pragma unroll
-            for (int o = 8; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-            const float rn = rsqrtf(sq * (1.0f / 128) + Q.eps);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = x[j] * rn * wv[j];
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            y[2 * q] = fmaf(x[2 * q], cs[2 * q], -(x[2 * q + 1] * sn[2 * q]));
-            y[2 * q + 1] = fmaf(x[2 * q + 1], cs[2 * q + 1], x[2 * q] * sn[2 * q + 1]);
-        }
-        if (m0 + r < G.M) store8<bf16_t>(dst + (int64_t)srow * 128 + d, y);
-    }
-}
 
 // LORA (G is an Fp8LoraGemm): after the fp8 K-loop the accumulators are scaled IN PLACE, acc = (acc * sa[m]) * sw[n], and a bf16 MFMA
 // tail adds sum_r t[m, r] B'[n, r] into the same registers, rank ascending: both MFMA shapes write the same 32 x 32 layout.  A rank
@@ -669,20 +521,8 @@ extern "C" int apexmi_gemm_fp8_lora(const void* qa, int64_t lda, const float* sa
 }
 
 // every grouped entry point: fp8_check_problem per problem, before the launch; qkv = the fused q/k/v operands of
-// apexmi_gemm_fp8_grouped_qkv(_lora), or null; lora = the five adapter arrays of the _lora entry points, or null
-struct Fp8QkvArgs {
-    const int* is_qkv;
-    const void* const* norm_q;
-    const void* const* norm_k;
-    const int* row0;
-    int H;
-    float eps;
-    const float* rope;
-    void* q_out;
-    void* k_out;
-    void* vt_out;
-    int S_out, Skp;
-};
+// apexmi_gemm_fp8_grouped_qkv(_lora) (Fp8QkvArgs, fp8_gemm_tile.h), or null; lora = the five adapter arrays of the _lora entry
+// points, or null
 struct Fp8LoraArrays {
     const void* const* t;
     const int64_t* ldt;
@@ -711,17 +551,7 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
     }
     bool any_lora = false;
     G.clk = apexmi_clk_ptr();
-    if (qkv != nullptr) {
-        APEXMI_REQUIRE(qkv->is_qkv && qkv->row0 && qkv->rope && qkv->q_out && qkv->k_out && qkv->vt_out && qkv->H > 0,
-                       "gemm_fp8_grouped_qkv: null argument");
-        APEXMI_REQUIRE(qkv->S_out > 0 && qkv->Skp >= qkv->S_out && qkv->Skp % 8 == 0,
-                       "gemm_fp8_grouped_qkv: Skp=%d must be a multiple of 8 >= S_out=%d", qkv->Skp, qkv->S_out);
-        APEXMI_REQUIRE(((uintptr_t)qkv->rope % 16) == 0 && ((uintptr_t)qkv->q_out % 16) == 0 && ((uintptr_t)qkv->k_out % 16) == 0 &&
-                           ((uintptr_t)qkv->vt_out % 16) == 0,
-                       "gemm_fp8_grouped_qkv: rope / outputs must be 16-byte aligned");
-        G.qs = Fp8QkvShared{(bf16_t*)qkv->q_out, (bf16_t*)qkv->k_out, (bf16_t*)qkv->vt_out, qkv->rope, qkv->S_out, qkv->Skp,
-                            qkv->H * 128, qkv->eps};
-    }
+    if (qkv != nullptr && fp8_check_qkv_shared("gemm_fp8_grouped_qkv", *qkv, &G.qs)) return 1;
     double flops = 0, bytes = 0;
     int64_t tiles = 0;
     for (int i = 0; i < count; ++i) {
@@ -734,20 +564,7 @@ static int gemm_fp8_grouped_run(int count, const void* const* qa, const int64_t*
             return 1;
         P.epi = epilogue[i];
         P.tile0 = (int)tiles;
-        if (fused) {
-            APEXMI_REQUIRE(N[i] == 3 * qkv->H * 128 && P.epi == APEXMI_EPI_BIAS,
-                           "gemm_fp8_grouped_qkv: a fused problem has N = 3 H 128 = %d (got %d) and the plain bias epilogue", 3 * qkv->H * 128,
-                           N[i]);
-            APEXMI_REQUIRE(qkv->row0[i] >= 0 && qkv->row0[i] + M[i] <= qkv->S_out,
-                           "gemm_fp8_grouped_qkv: rows [%d, %d) must lie inside S_out=%d", qkv->row0[i], qkv->row0[i] + M[i], qkv->S_out);
-            const void* nq = qkv->norm_q ? qkv->norm_q[i] : nullptr;
-            const void* nk = qkv->norm_k ? qkv->norm_k[i] : nullptr;
-            APEXMI_REQUIRE(((uintptr_t)nq % 16) == 0 && ((uintptr_t)nk % 16) == 0, "gemm_fp8_grouped_qkv: norm weights must be 16-byte aligned");
-            P.qkv = 1;
-            P.row0 = qkv->row0[i];
-            P.nq = (const bf16_t*)nq;
-            P.nk = (const bf16_t*)nk;
-        }
+        if (fused && fp8_check_qkv_problem("gemm_fp8_grouped_qkv", *qkv, i, &P)) return 1;
         tiles += (int64_t)P.tiles_m * P.tiles_n;
         flops += 2.0 * M[i] * N[i] * (double)K;
         bytes += (double)M[i] * K + (double)N[i] * K + 2.0 * (double)M[i] * N[i];

@@ -57,15 +57,43 @@ struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda 
     unsigned long long* clk;
 };
 
-// EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
+// The grouped form (apexmi_gemm_mxfp4_grouped, apexmi_gemm_mxfp4_grouped_qkv): the table entry of the fp8 kernel's grouped form
+// (Fp8GroupProblem, fp8_gemm_tile.h) plus the problem's own block scales; the table travels by value, as Fp8Group does.
+struct Mxfp4GroupProblem : Fp8GroupProblem {
+    const uint8_t* SA;
+    const uint8_t* SW;
+    int64_t ldsa, ldsw;
+};
+struct Mxfp4Group {
+    Mxfp4GroupProblem p[FP8_MAX_GROUPS];
+    int count, total;
+    Fp8QkvShared qs;
+    unsigned long long* clk;
+};
+
+// this workgroup's tile id `t` inside its problem, and the problem: the launch itself, or the table entry found by the prefix sums
+APEXMI_DEVICE const Mxfp4Gemm& mxfp4_problem(const Mxfp4Gemm& G, int& t) {
+    t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
+    return G;
+}
+APEXMI_DEVICE Mxfp4GroupProblem mxfp4_problem(const Mxfp4Group& G, int& t) {
+    int pi;
+    return fp8_group_entry(G.p, G.count, G.total, t, pi);
+}
+
+// ONE kernel for both forms, chosen by the argument type (Mxfp4Gemm, Mxfp4Group), as gemm_fp8_kernel: build.py's no-spill check
+// matches "gemm_mxfp4_kernel" and so covers every instantiation.
+// EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
+template <int EPI, class Args>
+__global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Args A) {
+    constexpr bool GROUPED = std::is_same_v<Args, Mxfp4Group>;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int wr = wid >> 1, wc = wid & 1;
 
-    int m0, n0;
-    fp8_tile_origin(xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n), G.tiles_m, G.tiles_n, m0, n0);
+    int t, m0, n0;
+    const auto& G = mxfp4_problem(A, t);         // everything per problem (row clamps, scale rows, nk) is read from it
+    fp8_tile_origin(t, G.tiles_m, G.tiles_n, m0, n0);
 
     // staging: the codes as in gemm_fp8_kernel; thread t adds one scale dword per operand
     const Fp8Stager stage_codes(G, m0, n0, wid, lane);
@@ -79,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
     };
 
     Fp8Clock clock;
-    clock.start(G.clk);
+    clock.start(A.clk);
 
     f32x16 acc[2][2];                 // [weight tile (output columns)][activation tile (output rows)]
     fp8_zero_acc(acc);
@@ -125,8 +153,17 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Mxfp4Gemm G) {
         __syncthreads();
     }
 
-    clock.stop(G.clk, tid);
-    fp8_epilogue<EPI, false>(acc, G, m0, n0, wr, wc, fr, fh);
+    clock.stop(A.clk, tid);
+    if constexpr (GROUPED) {
+        // block-uniform: the epilogue by the table entry.  The fused q/k/v preparation lays its bf16 tile over the first 32 KB of
+        // the code buffers (buffer 0, both operands), which nothing reads after the K-loop's last barrier.
+        if (G.qkv) fp8_qkv_epilogue<false>(acc, G, A.qs, m0, n0, tid, lds);
+        else if (G.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, false>(acc, G, m0, n0, wr, wc, fr, fh);
+        else if (G.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, false>(acc, G, m0, n0, wr, wc, fr, fh);
+        else fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, false>(acc, G, m0, n0, wr, wc, fr, fh);
+    } else {
+        fp8_epilogue<EPI, false>(acc, G, m0, n0, wr, wc, fr, fh);
+    }
 }
 
 }  // namespace
@@ -150,25 +187,103 @@ extern "C" int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int 
     return apexmi_check_launch("quant_blocks_mxfp4");
 }
 
+// ONE problem of either entry point: the null check, the format-independent checks (fp8_check_tile_problem with the e2m1 rules),
+// then the scale-row rule; fills the Fp8Problem part of `P` and its SA / SW / ldsa / ldsw.  `i` = the problem's index in a grouped
+// launch, which the messages name, or -1; tile0 = the tiles of the problems before it.
+template <class Problem>
+static int mxfp4_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const void* sa, int64_t ldsa,
+                               const void* qw, int64_t ldw, const void* sw, int64_t ldsw, const void* bias, void* C, int64_t ldc, int M,
+                               int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P) {
+    const Fp8Where at(i);
+    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand%s", who, at.paren);
+    char ld_note[64];
+    snprintf(ld_note, sizeof(ld_note), ", code rows at least K / 2 = %d bytes", K / 2);
+    const Fp8Format e2m1{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ld_note, "bytes", true, "output and bias 8-byte"};
+    if (fp8_check_tile_problem(who, at, e2m1, tile0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, (Fp8Problem*)P)) return 1;
+    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
+                   "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, at.of,
+                   K / 32, (long long)ldsa, (long long)ldsw);
+    P->SA = (const uint8_t*)sa, P->SW = (const uint8_t*)sw, P->ldsa = ldsa, P->ldsw = ldsw;
+    return 0;
+}
+
 extern "C" int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
                                  int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                                  const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const char* who = "gemm_mxfp4";
-    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand", who);
-    char ld_note[64];
-    snprintf(ld_note, sizeof(ld_note), ", code rows at least K / 2 = %d bytes", K / 2);
-    const Fp8Format e2m1{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ld_note, "bytes", true, "output and bias 8-byte"};
     Mxfp4Gemm G{};
-    if (fp8_check_tile_problem(who, Fp8Where(-1), e2m1, 0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
-    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
-                   "%s: the block scales must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, K / 32,
-                   (long long)ldsa, (long long)ldsw);
-    G.SA = (const uint8_t*)sa, G.SW = (const uint8_t*)sw, G.ldsa = ldsa, G.ldsw = ldsw;
+    if (mxfp4_check_problem(who, -1, 0, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
     G.clk = apexmi_clk_ptr();
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * ((double)M + N) * K + 2.0 * (double)M * N);
     // 68 KB of dynamic LDS is above the default limit
-    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp4_kernel<decltype(epi)::value>; }, G, (unsigned)(G.tiles_m * G.tiles_n),
-                       X4_LDS, stream);
+    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp4_kernel<decltype(epi)::value, Mxfp4Gemm>; }, G,
+                       (unsigned)(G.tiles_m * G.tiles_n), X4_LDS, stream);
     return apexmi_check_launch(who);
+}
+
+// both grouped entry points: every check of every problem before the launch; qkv = the fused q/k/v operands of
+// apexmi_gemm_mxfp4_grouped_qkv, or null
+static int gemm_mxfp4_grouped_run(const char* who, int count, const void* const* qa, const int64_t* lda, const void* const* sa,
+                                  const int64_t* ldsa, const void* const* qw, const int64_t* ldw, const void* const* sw,
+                                  const int64_t* ldsw, const void* const* bias, void* const* C, const int64_t* ldc, const int* M,
+                                  const int* N, int K, const int* epilogue, const float* const* gate, const void* const* R,
+                                  const int64_t* ldr, const Fp8QkvArgs* qkv, hipStream_t stream) {
+    APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "%s: count=%d not in [1,%d]", who, count, FP8_MAX_GROUPS);
+    APEXMI_REQUIRE(qa && lda && sa && ldsa && qw && ldw && sw && ldsw && C && ldc && M && N && epilogue, "%s: null argument array", who);
+    APEXMI_REQUIRE(K >= 256 && K % 256 == 0, "%s: K=%d must be a multiple of 256 (a K-tile is 128 bytes of e2m1 codes; the problems share K)",
+                   who, K);
+    Mxfp4Group G{};
+    G.count = count;
+    G.clk = apexmi_clk_ptr();
+    if (qkv != nullptr && fp8_check_qkv_shared(who, *qkv, &G.qs)) return 1;
+    double flops = 0, bytes = 0;
+    int64_t tiles = 0;
+    for (int i = 0; i < count; ++i) {
+        const bool fused = qkv != nullptr && qkv->is_qkv[i] != 0;
+        Mxfp4GroupProblem& P = G.p[i];
+        // a fused problem writes no C: its q_out stands in, N wide
+        if (mxfp4_check_problem(who, i, tiles, qa[i], lda[i], sa[i], ldsa[i], qw[i], ldw[i], sw[i], ldsw[i], bias ? bias[i] : nullptr,
+                                fused ? qkv->q_out : C[i], fused ? N[i] : ldc[i], M[i], N[i], K, epilogue[i], gate ? gate[i] : nullptr,
+                                R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P))
+            return 1;
+        P.epi = epilogue[i];
+        P.tile0 = (int)tiles;
+        if (fused && fp8_check_qkv_problem(who, *qkv, i, &P)) return 1;
+        tiles += (int64_t)P.tiles_m * P.tiles_n;
+        flops += 2.0 * M[i] * N[i] * (double)K;
+        bytes += (0.5 + 1.0 / 32) * ((double)M[i] + N[i]) * K + 2.0 * (double)M[i] * N[i];
+    }
+    G.total = (int)tiles;
+    ApexmiProfScope prof(0, stream, flops, bytes);
+    auto kernel = gemm_mxfp4_kernel<0, Mxfp4Group>;
+    static uint64_t attr_set = 0;       // 68 KB of dynamic LDS is above the default limit
+    APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), X4_LDS, stream, G);
+    return apexmi_check_launch(who);
+}
+
+// the grouped launches of the Flux blocks (apexmi_gemm_bf16_grouped) on MXFP4 operands: problem i = apexmi_gemm_mxfp4 of
+// (qa[i], sa[i]) x (qw[i], sw[i]), bit for bit
+extern "C" int apexmi_gemm_mxfp4_grouped(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                                         const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                                         const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                                         const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                                         apexmi_stream_t stream_) {
+    return gemm_mxfp4_grouped_run("gemm_mxfp4_grouped", count, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate,
+                                  R, ldr, nullptr, (hipStream_t)stream_);
+}
+
+// apexmi_gemm_mxfp4_grouped with apexmi_qkv_prepare fused into the epilogue of the problems flagged in is_qkv: bit-identical to the
+// two launches on the same codes; C[i] of a fused problem may be null and is not written
+extern "C" int apexmi_gemm_mxfp4_grouped_qkv(int count, const void* const* qa, const int64_t* lda, const void* const* sa,
+                                             const int64_t* ldsa, const void* const* qw, const int64_t* ldw, const void* const* sw,
+                                             const int64_t* ldsw, const void* const* bias, void* const* C, const int64_t* ldc,
+                                             const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                             const void* const* R, const int64_t* ldr, const int* is_qkv, const void* const* norm_q,
+                                             const void* const* norm_k, const int* row0, int H, float eps, const float* rope,
+                                             void* q_out, void* k_out, void* vt_out, int S_out, int Skp, apexmi_stream_t stream_) {
+    const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
+    return gemm_mxfp4_grouped_run("gemm_mxfp4_grouped_qkv", count, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue,
+                                  gate, R, ldr, &qkv, (hipStream_t)stream_);
 }

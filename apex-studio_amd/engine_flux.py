@@ -79,8 +79,19 @@ class FluxT2IEngine(EngineLoraMixin):
     def __init__(self, transformer, scheduler: Optional[FlowMatchEulerDiscreteScheduler] = None,
                  decode_fn: Optional[Callable[[torch.Tensor], object]] = None, vae_scale_factor: int = 8,
                  text_encoder=None, text_encoder_2=None, residual_dtype: Optional[torch.dtype] = None,
-                 fp8_compute: bool = False, fp8_fused_quant: bool = False, fp8_mx_ffn: bool = False, fp8_lora: bool = False):
+                 fp8_compute: bool = False, fp8_fused_quant: bool = False, fp8_mx_ffn: bool = False, fp8_lora: bool = False,
+                 fp4_compute: bool = False, fp4_linears=None):
         from .prompt import TextEncoder
+        # fp4_compute: the block launches of a bf16 transformer multiply as MXFP4 (`set_fp4_compute`, DESIGN.md §3.6: an opt-in
+        # approximation on MXFP4 copies beside the bf16 weights; not for a keep_fp8 model, so never together with fp8_compute);
+        # fp4_linears: a subset of the transformer's `_FP4_LINEARS`, None = all of them
+        self.fp4_compute = bool(fp4_compute)
+        self.fp4_linears = None if fp4_linears is None else tuple(fp4_linears)
+        if self.fp4_linears is not None and not self.fp4_compute:
+            raise ValueError("fp4_linears needs fp4_compute=True: it names the Linears of the MXFP4 compute mode")
+        if self.fp4_compute and fp8_compute:
+            raise ValueError("fp4_compute and fp8_compute cannot be combined: fp8 compute needs resident fp8 records (a keep_fp8 load), "
+                             "fp4 compute the bf16 weights")
         self.transformer = transformer
         # float32: the transformer keeps its residual stream in float (`set_residual_dtype`); None = bf16
         self.residual_dtype = residual_dtype
@@ -105,6 +116,8 @@ class FluxT2IEngine(EngineLoraMixin):
         if self.fp8_compute:
             more = {k: True for k, v in (("mx_ffn", self.fp8_mx_ffn), ("lora", self.fp8_lora)) if v}
             transformer.set_fp8_compute(True, fused_quant=self.fp8_fused_quant, **more)
+        if self.fp4_compute:
+            transformer.set_fp4_compute(True, linears=self.fp4_linears)
         self.scheduler = scheduler or FlowMatchEulerDiscreteScheduler.flux_dev()
         self.decode_fn = decode_fn
         self.vae_scale_factor = vae_scale_factor

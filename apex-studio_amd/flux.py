@@ -35,7 +35,7 @@ from . import lib as _l
 from .schedule import ModulationSchedule, ScheduleRegistry
 from . import ops
 # the parameter holders live in module_base; they stay importable from here (the name older code and checkpoints' tools use)
-from .module_base import (F32ResidualMixin, Fp8ResidentMixin, HipTransformer, _AdaNorm, _Config, _FF, _Linear, _Norm, _TimestepEmbedding,  # noqa: F401
+from .module_base import (F32ResidualMixin, Fp4ComputeMixin, Fp8ResidentMixin, HipTransformer, _AdaNorm, _Config, _FF, _Linear, _Norm, _TimestepEmbedding,  # noqa: F401
                           _fuse_linears, _repoint)
 
 
@@ -146,7 +146,7 @@ class _TimeTextEmbed(nn.Module):
         self.text_embedder = _TimestepEmbedding(pooled_dim, dim, **kw)
 
 
-class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
+class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin, HipTransformer):
     _converter_base = "flux.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "flux.mi355"
     _drops = {"moved": ("_packed", "_ws"), "loaded": ("_packed",), "storage": ("_ws",)}
@@ -339,6 +339,13 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             rec.set_lora([(m, d[m]["A"], d[m]["B"], self._lora_scales[n]) for m, _, _ in rec.parts
                           for n, d in self._lora_adapters.items() if m in d and self._lora_scales[n] != 0.0 and self._lora_enabled])
         super()._lora_remerge(modules - resident)
+        if modules - resident:
+            self._fp4_detach()      # merged into the bf16 weights: the MXFP4 copies are rebuilt before the next forward
+
+    def _invalidate(self, event: str):
+        if event in ("moved", "loaded", "written"):
+            self._fp4_detach()      # the weights change (`.to`, a load, `_weights_changed`): the MXFP4 copies go, and `forward` rebuilds them
+        super()._invalidate(event)
 
     def set_storage_dtype(self, dtype: torch.dtype):
         if dtype == torch.float32 and self._fp8_factors():
@@ -405,6 +412,48 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         self._fp8_compute, self._fp8_fused_quant, self._fp8_mx_ffn, self._fp8_lora = bool(on), bool(fused_quant), bool(mx_ffn), bool(lora)
         return self
 
+    # ---- opt-in MXFP4 compute on a bf16 model; the switch itself is module_base.Fp4ComputeMixin ----
+    _FP4_LINEARS = ("qkv", "attn_out", "ffn_up", "ffn_down", "single_in", "single_out")
+
+    def set_fp4_compute(self, on: bool, linears=None):
+        """Opt-in approximation: the selected block launches of a bf16 model quantise their activations per block of
+        32 to MXFP4 — ONE `ops.quant_blocks_mxfp4` over the joint buffer both streams are row slices of — and multiply e2m1 x e2m1
+        in one grouped launch (`ops.gemm_mxfp4_grouped`; `ops.gemm_mxfp4_grouped_qkv` with the fused q/k/v epilogue when `fuse_qkv`
+        is set and no IP adapter is active) against MXFP4 copies of the weights (`ops.Mxfp4Weight.from_bf16`) that sit BESIDE the
+        bf16 weights, on their `_fp4` slot: 0.53 bytes per selected weight element on top of the model.  `linears`, a subset of
+          "qkv"         `_wqkv` and `_wqkv_c` of a double block
+          "attn_out"    `to_out[0]` and `to_add_out`
+          "ffn_up", "ffn_down"   both streams each
+          "single_in"   a single block's `_wqkv` and `proj_mlp` (one launch, hence one name)
+          "single_out"  `proj_out` of a single block (K = dim + mlp; through `ops.gemm`'s fp4 route)
+        None = all six.  The embedders, the final proj_out, the modulation GEMVs, the IP-adapter projections and attention stay
+        bf16.  A launch class is routed where `ops.mxfp4_grouped_route` holds (decided on block 0); a class it refuses keeps today's
+        launch.  False detaches the records: the next forward is the original, bit for bit.  The records follow the model's
+        invalidation rule (a load, `.to`, a merged LoRA): dropped there, rebuilt before the next forward while the mode is on.  A
+        speed option, not a parity mode; no quality claim on real checkpoints.
+
+        Refused: a resident (`keep_fp8`) model — so the mode never meets the `fp8_*` switches —, f32 activation storage and the
+        f32 residual stream (`set_storage_dtype` / `set_residual_dtype` refuse float32 while the mode is on), an unknown name, and
+        `linears` together with `on=False`."""
+        return self._fp4_switch(on, linears)
+
+    def _fp4_blocks(self):
+        return list(self.transformer_blocks) + list(self.single_transformer_blocks)
+
+    def _fp4_weights(self, blk) -> dict:
+        a = blk.attn
+        if isinstance(blk, _SingleBlock):
+            return {"single_in": (blk._wqkv, blk.proj_mlp.weight), "single_out": (blk.proj_out.weight,)}
+        ff, ffc = blk.ff.net, blk.ff_context.net
+        return {"qkv": (blk._wqkv, blk._wqkv_c), "attn_out": (a.to_out[0].weight, a.to_add_out.weight),
+                "ffn_up": (ff[0].proj.weight, ffc[0].proj.weight), "ffn_down": (ff[2].weight, ffc[2].weight)}
+
+    def _rows_fp4(self, src):
+        """(codes, scale bytes) of the rows of the joint buffer `src` by ONE quantise launch into the per-stream fp4 scratch; the
+        streams of a grouped launch are row slices of both."""
+        qa, sa = ops._act_scratch_mxfp4(src.device, src.shape[0], src.shape[1])
+        return ops.quant_blocks_mxfp4(src, out=qa, scale_out=sa)
+
     def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, **kw):
         """ln_modulate(X, *mod, out=XN, **kw) in front of a grouped launch (bf16 outputs) over the row ranges `rows` of XN and the
         weights `w_list`, which is the ONLY reader of XN.  With `set_fp8_compute(fused_quant=True)`, where that launch takes its
@@ -447,10 +496,17 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         qa, sa = ops._act_scratch(src.device, src.shape[0], src.shape[1])
         return ops.quant_rows_fp8(src, out=qa, scale_out=sa)
 
-    def _grouped(self, src, rows, w_list, bias_list, out_list, epilogue, gate_list=None, residual_list=None, quantised=None):
+    def _grouped(self, src, rows, w_list, bias_list, out_list, epilogue, gate_list=None, residual_list=None, quantised=None,
+                 fp4=False):
         """One grouped launch whose problems read the row ranges `rows` (slices) of ONE activation buffer `src`: today's
         `ops.gemm_grouped`, or — in fp8-compute mode, when `ops.fp8_grouped_route` holds for every problem — one quantise launch
-        over `src` (unless `quantised` brings the codes) and `ops.gemm_fp8_grouped`."""
+        over `src` (unless `quantised` brings the codes) and `ops.gemm_fp8_grouped`.  `fp4`: the caller has asked
+        `ops.mxfp4_grouped_route` for this launch class (set_fp4_compute): one `quant_blocks_mxfp4` over `src` and
+        `ops.gemm_mxfp4_grouped` on the weights' MXFP4 records."""
+        if fp4:
+            qa, sa = self._rows_fp4(src)
+            return ops.gemm_mxfp4_grouped([qa[r] for r in rows], [sa[r] for r in rows], [w._fp4 for w in w_list], bias_list, out_list,
+                                          epilogue=epilogue, gate_list=gate_list, residual_list=residual_list)
         w_list = [w if ops._fp8_of(w) is None else ops._fp8_of(w) for w in w_list]
         a_list = [src[r] for r in rows]
         if self._fp8_compute and ops.fp8_grouped_route(a_list, w_list, out_list, epilogue):
@@ -661,6 +717,20 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
         fp8_s = fp8 and not overlap and len(self.single_transformer_blocks) > 0 and ops.fp8_grouped_route(
             [XN, XN], [self.single_transformer_blocks[0]._wqkv, rec(self.single_transformer_blocks[0].proj_mlp.weight)],
             [QKV, CAT[:, dim:]], ["bias", "gelu"])
+        # opt-in MXFP4 compute (set_fp4_compute; a bf16 model, never a resident one): each launch class is decided ONCE, on block 0
+        # of its kind — every block carries records for the same names —, by the pure predicate; a class it refuses (a name that
+        # is not selected, an ineligible shape) keeps today's launch
+        f4_qkv = f4_out = f4_up = f4_down = f4_sin = False
+        if self._fp4_linears is not None and len(self.transformer_blocks) > 0:
+            b0 = self.transformer_blocks[0]
+            att_it, ffh_it = [att[s_txt:], att[:s_txt]], [FFH[s_txt:], FFH[:s_txt]]
+            f4_qkv = ops.mxfp4_grouped_route([XNi, XNt], [b0._wqkv, b0._wqkv_c], [QKV[s_txt:], QKV[:s_txt]], "bias")
+            f4_out = ops.mxfp4_grouped_route(att_it, [b0.attn.to_out[0].weight, b0.attn.to_add_out.weight], [Xi, Xt], "gate_res")
+            f4_up = ops.mxfp4_grouped_route([XNi, XNt], [b0.ff.net[0].proj.weight, b0.ff_context.net[0].proj.weight], ffh_it, "gelu")
+            f4_down = ops.mxfp4_grouped_route(ffh_it, [b0.ff.net[2].weight, b0.ff_context.net[2].weight], [Xi, Xt], "gate_res")
+        if self._fp4_linears is not None and not overlap and len(self.single_transformer_blocks) > 0:
+            s0 = self.single_transformer_blocks[0]
+            f4_sin = ops.mxfp4_grouped_route([XN, XN], [s0._wqkv, s0.proj_mlp.weight], [QKV, CAT[:, dim:]], ["bias", "gelu"])
         # run-time LoRA on resident records (set_fp8_compute(lora=True)): which blocks carry factors is the adapter's business, so
         # with factors anywhere every launch class is decided PER BLOCK: False = the plain fp8 launch, True = the fp8 launch with
         # the adapter tail (one grouped skinny GEMM in front of it), None = not routed.  Without factors the block-0 decisions
@@ -713,7 +783,13 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             fuse8_d = kind is not None and self.fuse_qkv and ip is None
             qn = self._norm_rows(X, XN, img_txt, [blk._wqkv, blk._wqkv_c] if kind is not None else [], "bias", mi(1), mi(0), split=s_txt,
                                  scale2=mt(1), shift2=mt(0))
-            if fuse8_d:
+            if f4_qkv and self.fuse_qkv and ip is None:
+                qa, sa = self._rows_fp4(XN)
+                ops.gemm_mxfp4_grouped_qkv([qa[s_txt:], qa[:s_txt]], [sa[s_txt:], sa[:s_txt]], [blk._wqkv._fp4, blk._wqkv_c._fp4],
+                                           [blk._bqkv, blk._bqkv_c], [None, None], "bias", [1, 1],
+                                           [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
+                                           [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
+            elif fuse8_d:
                 lt, lb = self._lora_t([XNi, XNt], [blk._wqkv, blk._wqkv_c]) if kind else (None, None)
                 qa, sa = self._rows_fp8(XN, qn)
                 ops.gemm_fp8_grouped_qkv([qa[s_txt:], qa[:s_txt]], [sa[s_txt:], sa[:s_txt]], [blk._wqkv, blk._wqkv_c],
@@ -727,7 +803,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                                      [s_txt, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
             else:
                 self._grouped(XN, img_txt, [blk._wqkv, blk._wqkv_c], [blk._bqkv, blk._bqkv_c], [QKV[s_txt:], QKV[:s_txt]], "bias",
-                              quantised=qn)
+                              quantised=qn, fp4=f4_qkv)
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VT[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, wq2=a.norm_added_q.weight, wk2=a.norm_added_k.weight,
                                 split=s_txt, eps=1e-6, rope=rope, rope_mode=_l.ROPE_INTERLEAVED)
@@ -737,7 +813,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                 ops.qkv_prepare(q_in[s_txt:], None, None, H, ws.IPQ[0], None, None, wq=a.norm_q.weight, eps=1e-6)
             ops.attention_prepared(Qp, Kp, VT, att_v, S)
             self._grouped(att, img_txt, [a.to_out[0].weight, a.to_add_out.weight], [a.to_out[0].bias, a.to_add_out.bias], [Xi, Xt],
-                          "gate_res", gate_list=[mi(2), mt(2)], residual_list=[Xi, Xt])
+                          "gate_res", gate_list=[mi(2), mt(2)], residual_list=[Xi, Xt], fp4=f4_out)
             ff, ffc = blk.ff.net, blk.ff_context.net
             qn = self._norm_rows(X, XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight] if fp8 else [], "gelu", mi(4), mi(3),
                                  split=s_txt, scale2=mt(4), shift2=mt(3))
@@ -751,9 +827,9 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                                      residual_list=[Xi, Xt], block_scales_list=[hs[r] for r in img_txt])
             else:
                 self._grouped(XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight], [ff[0].proj.bias, ffc[0].proj.bias],
-                              [FFH[s_txt:], FFH[:s_txt]], "gelu", quantised=qn)
+                              [FFH[s_txt:], FFH[:s_txt]], "gelu", quantised=qn, fp4=f4_up)
                 self._grouped(FFH, img_txt, [ff[2].weight, ffc[2].weight], [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res",
-                              gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt])
+                              gate_list=[mi(5), mt(5)], residual_list=[Xi, Xt], fp4=f4_down)
             if ip is not None:
                 # `hidden_states + ip_attn_output` AFTER the feed-forward (model.py:308-309); ip_attn_output = sum over adapters of
                 # scale x attention(image queries, to_k_ip(tokens), to_v_ip(tokens)) (attention.py:232-262): a few keys per adapter
@@ -793,6 +869,11 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                     mlp_done = torch.cuda.Event()
                     mlp_done.record(self._side)
                 ops.gemm(XN, blk._wqkv, blk._bqkv, out=QKV)
+            elif f4_sin and self.fuse_qkv:
+                qa, sa = self._rows_fp4(XN)
+                ops.gemm_mxfp4_grouped_qkv([qa, qa], [sa, sa], [blk._wqkv._fp4, blk.proj_mlp.weight._fp4], [blk._bqkv, blk.proj_mlp.bias],
+                                           [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
+                                           [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
             elif fuse8_s:
                 # with adapters: QKV and MLP-up read the same rows, so their two skinny problems share one launch
                 lt, lb = self._lora_t([XN, XN], [blk._wqkv, rec(blk.proj_mlp.weight)]) if kind else (None, None)
@@ -808,8 +889,8 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
             else:
                 # QKV and MLP-up read the same XN: one launch, 1512 tiles = 5.9 rounds of the 256 CUs
                 self._grouped(XN, both, [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias], [QKV, CAT[:, dim:]],
-                              ["bias", "gelu"], quantised=qn)
-            if overlap or not (fuse_s or fuse8_s):
+                              ["bias", "gelu"], quantised=qn, fp4=f4_sin)
+            if overlap or not (fuse_s or fuse8_s or (f4_sin and self.fuse_qkv)):
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VT[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, split=0, eps=1e-6, rope=rope,
                                 rope_mode=_l.ROPE_INTERLEAVED)
@@ -936,6 +1017,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer)
                 raise ValueError(f"{len(ip)} image-prompt tensors for {n_ad} IP adapters")
             ip = [t.to(self.device, self.storage_dtype) for t in ip]
         self.pack()
+        self._fp4_refresh()
         if txt_ids.ndim == 3:
             txt_ids = txt_ids[0]
         if img_ids.ndim == 3:

@@ -183,6 +183,14 @@ SIGNATURES = {
     "apexmi_quant_blocks_mxfp4": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_gemm_mxfp4": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
                                     C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "apexmi_gemm_mxfp4_grouped": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp),
+                                            c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                            C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p, vp]),
+    "apexmi_gemm_mxfp4_grouped_qkv": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p,
+                                                C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p,
+                                                C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_int, C.c_float,
+                                                vp, vp, vp, vp, C.c_int, C.c_int, vp]),
     "apexmi_dequant_gguf": (C.c_int, [vp, C.c_int, C.c_int64, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_euler_step": (C.c_int, [vp, vp, vp, C.c_int64, C.c_float, C.c_int, vp]),
     "apexmi_prof_enable": (C.c_int, [C.c_int]),

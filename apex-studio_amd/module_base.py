@@ -414,6 +414,98 @@ class F32ResidualMixin:
         return self
 
 
+class Fp4ComputeMixin:
+    """The switch of the opt-in MXFP4 compute mode of the Flux and Wan transformers, in front of F32ResidualMixin
+    in the bases: name validation, the refusals, attaching / detaching the `ops.Mxfp4Weight` records that sit BESIDE the bf16 block
+    weights (on each weight's `_fp4` slot), `_fp4_bytes`, and the two dtype guards.
+
+    A class supplies `_FP4_LINEARS` (the names `linears=` takes), `_fp4_blocks()` (its blocks) and `_fp4_weights(blk)` ({name: the
+    weight, or a tuple of weights, of that name in that block}; a name a block does not have is absent), calls `_fp4_detach()` where
+    its weights change (`_weights_changed`, a merged LoRA) and `_fp4_refresh()` after `pack()` in `forward`.  The messages start with
+    the class's `_tag`."""
+
+    _FP4_LINEARS: tuple = ()
+    _fp4_linears = None      # the selected names while the mode is on
+    _fp4_live: tuple = ()    # the weights that carry a record
+    _fp4_bytes = 0
+
+    def _fp4_blocks(self):
+        raise NotImplementedError
+
+    def _fp4_weights(self, blk) -> dict:
+        raise NotImplementedError
+
+    def _fp4_switch(self, on: bool, linears=None):
+        """`set_fp4_compute(on, linears)` of the class: the names are checked before anything else, so that needs no device."""
+        if linears is not None:
+            try:
+                linears = tuple(linears)
+            except TypeError as err:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=) takes names out of {self._FP4_LINEARS}, got {linears!r}") from err
+            bad = [n for n in linears if n not in self._FP4_LINEARS]
+            if bad:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=): unknown Linear name(s) {bad}; the block Linears are "
+                                     f"{self._FP4_LINEARS}")
+        if not on:
+            if linears is not None:
+                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(False) takes no `linears`: it detaches every record")
+            self._fp4_linears = None
+            self._fp4_detach()
+            return self
+        if getattr(self, "_fp8_bytes", 0):
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute needs the bf16 block weights, and this model's are resident quantised "
+                                 f"records ({self._fp8_options()} load).  The fp8_* switches need exactly such records, so the two "
+                                 "modes cannot be combined: load without those options for fp4 compute")
+        if self.storage_dtype != torch.bfloat16:
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute is for bfloat16 activation storage; the f32-storage verification "
+                                 "mode keeps the bf16 GEMMs (set_storage_dtype(torch.bfloat16) first)")
+        if self.residual_dtype != torch.bfloat16:
+            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute does not take the f32 residual stream: its residual GEMMs write "
+                                 "float rows, which the fp4 GEMM does not (set_residual_dtype(torch.bfloat16) first)")
+        self.pack()
+        self._fp4_linears = tuple(n for n in self._FP4_LINEARS if linears is None or n in linears)
+        self._fp4_detach()
+        self._fp4_attach()
+        return self
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and self._fp4_linears is not None:
+            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and is for bfloat16 activation storage: float rows would quietly "
+                                 "return every Linear to bf16; set_fp4_compute(False) first")
+        return super().set_storage_dtype(dtype)
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        if dtype == torch.float32 and self._fp4_linears is not None:
+            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and does not take the f32 residual stream: its residual GEMMs "
+                                 "would quietly return to bf16; set_fp4_compute(False) first")
+        return super().set_residual_dtype(dtype)
+
+    @torch.no_grad()
+    def _fp4_attach(self):
+        """One Mxfp4Weight per weight of the selected names of every block, on the slot `ops.gemm` reads (`weight._fp4`)."""
+        live = []
+        for blk in self._fp4_blocks():
+            ws = self._fp4_weights(blk)
+            for name in self._fp4_linears:
+                for w in ((ws[name],) if isinstance(ws.get(name), torch.Tensor) else ws.get(name, ())):
+                    w._fp4 = ops.Mxfp4Weight.from_bf16(w)
+                    live.append(w)
+        self._fp4_live = live
+        self._fp4_bytes = sum(w._fp4.nbytes() for w in live)
+
+    def _fp4_detach(self):
+        for w in self._fp4_live:
+            if getattr(w, "_fp4", None) is not None:
+                del w._fp4
+        self._fp4_live = []
+        self._fp4_bytes = 0
+
+    def _fp4_refresh(self):
+        """Before a forward: the records a weight change dropped while the mode is on are rebuilt from the weights as they are now."""
+        if self._fp4_linears is not None and not self._fp4_live:
+            self._fp4_attach()
+
+
 class Fp8ResidentMixin:
     """Quantised block weights RESIDENT in HBM (`weights.load_checkpoint_into(keep_fp8=True / keep_quantized=True)`: fp8-scaled,
     SURVEY.md §8f-2, and GGUF blocks) of the Flux and Wan transformers, in front of HipTransformer in the bases: adopting the

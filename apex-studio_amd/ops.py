@@ -893,6 +893,16 @@ def fp8_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
     return problems is not None and all(fp8_compute_route(a, w, o, e) for a, w, o, e in problems)
 
 
+def mxfp4_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
+    """Whether a grouped launch over these problems may go out as ONE `quant_blocks_mxfp4` + `gemm_mxfp4_grouped`.  Pure, like
+    `mxfp4_route` (dtypes, shapes and strides only; CPU and meta tensors are fine): true only when EVERY problem satisfies
+    `mxfp4_route` — a launch is all fp4 or not routed, never mixed — and there are 1 to 4 of them sharing K.  `epilogues`: one
+    name or one per problem; `out_list`: None, or one tensor (or None) per problem.  `gemm_grouped` itself never routes: the
+    model asks this predicate, as it asks `fp8_grouped_route`."""
+    problems = _grouped_problems(a_list, w_list, out_list, epilogues)
+    return problems is not None and all(mxfp4_route(a, w, o, e) for a, w, o, e in problems)
+
+
 def fp8_grouped_lora_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
     """Whether a grouped launch over these problems, some of whose records carry run-time LoRA factors, may go out as skinny
     `gemm_grouped` + quantise + `gemm_fp8_grouped(lora_t_list=, lora_B_list=)`.  Pure, like `fp8_compute_route` (dtypes, shapes and
@@ -935,9 +945,9 @@ def fp8_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_d
 
 
 def fp8_grouped_tiles(shapes):
-    """The tile each workgroup of a `gemm_fp8_grouped` launch over problems `shapes` = [(M, N), ...] computes, restated from the
-    kernel (fp8_problem in csrc/gemm_fp8.hip, fp8_tile_origin in csrc/fp8_gemm_tile.h): a list over block ids of (problem, tile row,
-    tile column).  The XCD remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile
+    """The tile each workgroup of a `gemm_fp8_grouped` or `gemm_mxfp4_grouped` launch (the walk does not depend on the operand
+    format) over problems `shapes` = [(M, N), ...] computes, restated from the kernels (fp8_group_entry and fp8_tile_origin in
+    csrc/fp8_gemm_tile.h): a list over block ids of (problem, tile row, tile column).  The XCD remap runs over the launch's total tile count, the problem is found by the prefix sums of the tile
     counts, and inside a problem bands of 8 tile rows are walked column by column."""
     tm = [(m + 127) // 128 for m, _ in shapes]
     tn = [(n + 127) // 128 for _, n in shapes]
@@ -1092,6 +1102,101 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
         return
     rc = _l.load().apexmi_gemm_fp8_grouped_qkv(*args, *qargs, _stream())
     _l.check(rc, "gemm_fp8_grouped_qkv")
+
+
+def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None):
+    """ctypes arrays of a grouped fp4 launch after the per-problem checks (`_check_mxfp4_pair`, `_epilogue_operands`); `fused[i]`:
+    problem i writes no `out`.  Every refusal raises ApexMIError with a reason before the library is asked; a float `out` is left
+    to the entry point, which rejects it with its own message."""
+    import ctypes as C
+    lists = (codes_list, scales_list, w_list, out_list)
+    n = len(codes_list)
+    if not 1 <= n <= FP8_MAX_GROUPS or any(len(x) != n for x in lists):
+        raise _l.ApexMIError(f"{who}: a launch holds 1 to {FP8_MAX_GROUPS} problems with one codes / scales / weight / out entry each, "
+                             f"got {[len(x) for x in lists]}")
+    epis = [epilogue] * n if isinstance(epilogue, str) else list(epilogue)
+    none = [None] * n
+    bias_list, gate_list, residual_list = list(bias_list or none), list(gate_list or none), list(residual_list or none)
+    fused = list(fused or [0] * n)
+    if any(len(x) != n for x in (epis, bias_list, gate_list, residual_list, fused)):
+        raise _l.ApexMIError(f"{who}: one epilogue name, or one per problem, and one bias / gate / residual entry (or None) per problem")
+    for i, (w, e) in enumerate(zip(w_list, epis)):
+        if not isinstance(w, Mxfp4Weight):
+            raise _l.ApexMIError(f"{who}: problem {i}: expected an Mxfp4Weight, got {type(w).__name__}")
+        if e not in _FP8_EPI:
+            raise _l.ApexMIError(f"{who}: problem {i}: epilogue '{e}' is not one of {_FP8_EPI}")
+    K = w_list[0].shape[1]
+    if any(w.shape[1] != K for w in w_list):
+        raise _l.ApexMIError(f"{who}: the problems of a launch share K, got {[w.shape[1] for w in w_list]}")
+    flags = []
+    for i, (q, s, w, b, o, e, g, r, f) in enumerate(zip(codes_list, scales_list, w_list, bias_list, out_list, epis, gate_list,
+                                                        residual_list, fused)):
+        at = f"{who} (problem {i})"
+        if not isinstance(q, torch.Tensor) or q.dim() != 2:
+            raise _l.ApexMIError(f"{at}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(q).__name__}")
+        _check_mxfp4_pair(at, q, s, q.shape[0], K)
+        flags.append(_epilogue_operands(at, q.shape[0], w.shape[0], q.device, b, o, e, g, r, fused=bool(f), told=True)[1])
+    VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
+    return (n, VP(*[t.data_ptr() for t in codes_list]), I64(*[t.stride(0) for t in codes_list]),
+            VP(*[t.data_ptr() for t in scales_list]), I64(*[t.stride(0) for t in scales_list]),
+            VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),
+            VP(*[w.s.data_ptr() for w in w_list]), I64(*[w.s.stride(0) for w in w_list]), VP(*[_ptr(b) for b in bias_list]),
+            VP(*[None if f else o.data_ptr() for o, f in zip(out_list, fused)]),
+            I64(*[0 if f else o.stride(0) for o, f in zip(out_list, fused)]), INT(*[t.shape[0] for t in codes_list]),
+            INT(*[w.shape[0] for w in w_list]), K, INT(*[_EPI[e] | fl for e, fl in zip(epis, flags)]),
+            VP(*[_ptr(g) if e == "gate_res" else None for g, e in zip(gate_list, epis)]),
+            VP(*[_ptr(r) if e == "gate_res" else None for r, e in zip(residual_list, epis)]),
+            I64(*[(r.stride(0) if e == "gate_res" else 0) for r, e in zip(residual_list, epis)]))
+
+
+def gemm_mxfp4_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilogue="bias", gate_list=None,
+                       residual_list=None) -> None:
+    """Up to 4 `gemm_mxfp4` problems sharing K in ONE launch (img / txt streams; QKV + MLP-up of a single block): out_list[i] =
+    epi_i(codes_i x w_list[i] + bias_i) with both block scales applied by the MFMA, bit for bit what `gemm_mxfp4` leaves for that
+    problem alone.  `w_list` holds `Mxfp4Weight`s; `epilogue` is one name or one per problem (bias / gelu / gate_res, freely
+    mixed); a gate_res problem may have residual_list[i] is out_list[i] (in place).  Several problems may share one (codes,
+    scales) pair or row slices of it.  Refusals raise ApexMIError with a reason and write nothing."""
+    who = "gemm_mxfp4_grouped"
+    args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list)
+    _l.check(_l.load().apexmi_gemm_mxfp4_grouped(*args, _stream()), who)
+
+
+def gemm_mxfp4_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
+                           eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor) -> None:
+    """`gemm_mxfp4_grouped` with `qkv_prepare` fused into the epilogue of the problems flagged in `is_qkv` (fused QKV projections,
+    N = 3 H 128), mirroring `gemm_fp8_grouped_qkv`: q / k leave normalised per head, rotated and laid out [H, S_out, 128], v leaves
+    transposed [H, 128, Skp]; bit-identical to gemm_mxfp4_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
+    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count."""
+    import ctypes as C
+    who = "gemm_mxfp4_grouped_qkv"
+    n = len(codes_list)
+    if len(is_qkv) != n or len(row0) != n:
+        raise _l.ApexMIError(f"{who}: is_qkv and row0 take one entry per problem")
+    args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
+                               fused=[1 if f else 0 for f in is_qkv])
+    for name, t_ in (("qo", qo), ("ko", ko), ("vt", vt)):
+        if not isinstance(t_, torch.Tensor):
+            raise _l.ApexMIError(f"{who}: null q/k/v output `{name}`")
+        _req(t_, torch.bfloat16, f"{who} output {name}")
+    if not isinstance(rope, torch.Tensor):
+        raise _l.ApexMIError(f"{who}: null rope table")
+    _req(rope, torch.float32, f"{who}.rope")
+    S_out = qo.shape[1]
+    if not (qo.is_contiguous() and ko.is_contiguous() and vt.is_contiguous() and rope.is_contiguous()
+            and tuple(qo.shape) == tuple(ko.shape) == (H, S_out, 128) and vt.dim() == 3 and tuple(vt.shape[:2]) == (H, 128)
+            and tuple(rope.shape) == (2, S_out, 128)):
+        raise _l.ApexMIError(f"{who}: expected contiguous qo / ko [{H}, S_out, 128], vt [{H}, 128, Skp] and rope [2, S_out, 128], got "
+                             f"{tuple(qo.shape)}, {tuple(ko.shape)}, {tuple(vt.shape)}, {tuple(rope.shape)}")
+    none = [None] * n
+    for t_ in list(norm_q or none) + list(norm_k or none):
+        if t_ is not None:
+            _req(t_, torch.bfloat16, f"{who} norm weight")
+            assert t_.is_contiguous() and t_.numel() == 128
+    VP, INT = C.c_void_p * n, C.c_int * n
+    qargs = (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
+             VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
+             ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+    _l.check(_l.load().apexmi_gemm_mxfp4_grouped_qkv(*args, *qargs, _stream()), who)
 
 
 _EPI = {"bias": _l.EPI_BIAS, "gelu": _l.EPI_BIAS_GELU, "gate_res": _l.EPI_BIAS_GATE_RES,

@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import F32ResidualMixin, Fp8ResidentMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
+from .module_base import F32ResidualMixin, Fp4ComputeMixin, Fp8ResidentMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
 
 
 class _WanAttn(nn.Module):
@@ -110,7 +110,7 @@ class _Conv3dParams(nn.Module):
         self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
 
 
-class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
+class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "wan.mi355"
     _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans", "_band_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
@@ -286,71 +286,15 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         `fp8_*` switches need exactly such records, so the two modes cannot meet), f32 activation storage and the f32 residual
         stream (their GEMMs read or write float rows, which this mode does not route; `set_storage_dtype` / `set_residual_dtype`
         refuse float32 while the mode is on), and an unknown name in `linears`."""
-        if linears is not None:
-            try:
-                linears = tuple(linears)
-            except TypeError as err:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=) takes names out of {self._FP4_LINEARS}, got {linears!r}") from err
-            bad = [n for n in linears if n not in self._FP4_LINEARS]
-            if bad:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=): unknown Linear name(s) {bad}; the block Linears are "
-                                     f"{self._FP4_LINEARS}")
-        if not on:
-            if linears is not None:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(False) takes no `linears`: it detaches every record")
-            self._fp4_linears = None
-            self._fp4_detach()
-            return self
-        if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute needs the bf16 block weights, and this model's are resident quantised "
-                                 f"records ({self._fp8_options()} load).  The fp8_* switches need exactly such records, so the two "
-                                 "modes cannot be combined: load without those options for fp4 compute")
-        if self.storage_dtype != torch.bfloat16:
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute is for bfloat16 activation storage; the f32-storage verification "
-                                 "mode keeps the bf16 GEMMs (set_storage_dtype(torch.bfloat16) first)")
-        if self.residual_dtype != torch.bfloat16:
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute does not take the f32 residual stream: its residual GEMMs write "
-                                 "float rows, which the fp4 GEMM does not (set_residual_dtype(torch.bfloat16) first)")
-        self.pack()
-        self._fp4_linears = tuple(n for n in self._FP4_LINEARS if linears is None or n in linears)
-        self._fp4_detach()
-        self._fp4_attach()
-        return self
+        return self._fp4_switch(on, linears)      # module_base.Fp4ComputeMixin: the part of the switch shared with Flux
 
-    def set_storage_dtype(self, dtype: torch.dtype):
-        if dtype == torch.float32 and getattr(self, "_fp4_linears", None) is not None:
-            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and is for bfloat16 activation storage: float rows would quietly "
-                                 "return every Linear to bf16; set_fp4_compute(False) first")
-        return super().set_storage_dtype(dtype)
-
-    def set_residual_dtype(self, dtype: torch.dtype):
-        if dtype == torch.float32 and getattr(self, "_fp4_linears", None) is not None:
-            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and does not take the f32 residual stream: its residual GEMMs "
-                                 "would quietly return to bf16; set_fp4_compute(False) first")
-        return super().set_residual_dtype(dtype)
+    def _fp4_blocks(self):
+        return self.blocks
 
     def _fp4_weights(self, blk) -> dict:
         a1, a2 = blk.attn1, blk.attn2
         return {"qkv": blk._wqkv, "attn_out": a1.to_out[0].weight, "cross_q": a2.to_q.weight, "cross_kv": blk._wkv2,
                 "cross_out": a2.to_out[0].weight, "ffn_up": blk.ffn.net[0].proj.weight, "ffn_down": blk.ffn.net[2].weight}
-
-    @torch.no_grad()
-    def _fp4_attach(self):
-        """One Mxfp4Weight per selected Linear of every block, on the slot `ops.gemm` reads (`weight._fp4`)."""
-        self._fp4_live = []
-        for blk in self.blocks:
-            ws = self._fp4_weights(blk)
-            for name in self._fp4_linears:
-                ws[name]._fp4 = ops.Mxfp4Weight.from_bf16(ws[name])
-                self._fp4_live.append(ws[name])
-        self._fp4_bytes = sum(w._fp4.nbytes() for w in self._fp4_live)
-
-    def _fp4_detach(self):
-        for w in getattr(self, "_fp4_live", ()):
-            if getattr(w, "_fp4", None) is not None:
-                del w._fp4
-        self._fp4_live = []
-        self._fp4_bytes = 0
 
     def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", out_mx=None, **norm):
         """ln_modulate(x, **norm, out=xn) -> gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf); with
@@ -686,8 +630,7 @@ class WanTransformer3DModel(Fp8ResidentMixin, F32ResidualMixin, HipTransformer):
         if timestep.ndim != 1:
             raise NotImplementedError("wan.mi355: per-token timesteps are not supported")
         self.pack()
-        if getattr(self, "_fp4_linears", None) is not None and not self._fp4_live:
-            self._fp4_attach()
+        self._fp4_refresh()
         enc = encoder_hidden_states.to(self.storage_dtype)
         img = None
         if encoder_hidden_states_image is not None and self.config.added_kv_proj_dim is not None:

@@ -916,6 +916,37 @@ int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa,
                       int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue, const float* gate,
                       const void* R, int64_t ldr, apexmi_stream_t stream);
 
+/* apexmi_gemm_mxfp4_grouped — up to 4 apexmi_gemm_mxfp4 problems that share K in ONE launch: the MXFP4 counterpart of
+ * apexmi_gemm_fp8_grouped, for the nn.Linear calls apexmi_gemm_bf16_grouped replaces (the image and text streams of a Flux double
+ * block, flux model.py:245-263; a single block's QKV + MLP-up, model.py:207-214) in the opt-in fp4 compute mode.  Arrays are host arrays of length
+ * `count`; problem i has its own codes qa[i] / lda[i], scale bytes sa[i] / ldsa[i], weight codes qw[i] / ldw[i] and scale bytes
+ * sw[i] / ldsw[i], bias[i], C[i] / ldc[i], M[i], N[i], epilogue[i] (bias, tanh GELU and gate x y + residual may be MIXED), gate[i]
+ * and R[i] / ldr[i] (R[i] may alias C[i]).  bias, gate, R and ldr may be NULL, as may their entries.  Per output element the
+ * arithmetic is apexmi_gemm_mxfp4's, so every problem leaves the bits it would leave alone.  Every rule of apexmi_gemm_mxfp4 holds
+ * per problem and is checked for all problems before the launch: nothing is written when one is refused (count outside [1, 4],
+ * K % 256 != 0, N % 16 != 0, f32 output, a null operand). */
+int apexmi_gemm_mxfp4_grouped(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                              const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                              const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                              const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                              apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp4_grouped with the q/k/v preparation fused into the epilogue of the problems flagged in is_qkv: the contract of
+ * apexmi_gemm_fp8_grouped_qkv on the fp4 kernel (the q / k / v projections with norm_q / norm_k and the rotary embedding of
+ * FluxAttnProcessor.__call__, transformer/flux/base/attention.py:62-94), for any total row count and any H >= 1.
+ * is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out and Skp as there; a fused problem has N[i] = 3 H 128 and
+ * the plain bias epilogue, and its C[i] may be NULL and is not written.  q_out, k_out and columns < S_out of vt_out are
+ * BIT-IDENTICAL to apexmi_gemm_mxfp4_grouped followed by apexmi_qkv_prepare (rope_mode interleaved) on the same codes.  Refused
+ * before the launch, besides what apexmi_gemm_mxfp4_grouped refuses: a fused problem whose N is not 3 H 128, a null q_out / k_out /
+ * vt_out / rope / is_qkv / row0, rows outside [0, S_out). */
+int apexmi_gemm_mxfp4_grouped_qkv(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                                  const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                                  const void* const* bias, void* const* C, const int64_t* ldc, const int* M, const int* N, int K,
+                                  const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                                  const int* is_qkv, const void* const* norm_q, const void* const* norm_k, const int* row0, int H,
+                                  float eps, const float* rope, void* q_out, void* k_out, void* vt_out, int S_out, int Skp,
+                                  apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
