@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_NAME = "libapex_mi355.so"
 LIB_PATH = os.path.join(PKG_DIR, LIB_NAME)
 SOURCES = ["runtime.hip", "gemm.hip", "attention.hip", "attention_masked.hip", "attention_varlen.hip", "attention_dual.hip", "attention_wide.hip", "elementwise.hip", "dequant_gguf.hip",
-           "conv.hip", "gemm_fp8.hip", "gemm_mxfp4.hip"]
+           "conv.hip", "gemm_fp8.hip", "gemm_mxfp4.hip", "gemm_mxfp6.hip"]
 ARCH = "gfx950"
 
 
@@ -39,7 +39,7 @@ if os.environ.get("APEXMI_DEBUG", "0") not in ("", "0"):
 NO_SPILL = {"attention.hip": ["attn_fwd_d128_w64_kernel", "attn_fwd_d128_w64r_kernel", "attn_fwd_d128_w64_band_kernel"],
             "attention_masked.hip": ["attn_masked_kernel", "attn_window_map_kernel"],
             "attention_varlen.hip": ["attn_varlen_kernel", "attn_varlen_vt_kernel"], "attention_dual.hip": ["attn_dual_kernel"], "attention_wide.hip": ["attn_wide_kernel"],
-            "gemm_fp8.hip": ["gemm_fp8_kernel"], "gemm_mxfp4.hip": ["gemm_mxfp4_kernel"],
+            "gemm_fp8.hip": ["gemm_fp8_kernel"], "gemm_mxfp4.hip": ["gemm_mxfp4_kernel"], "gemm_mxfp6.hip": ["gemm_mxfp6_kernel"],
             # the quantising norms hold the whole row (up to 2 x 80 floats a lane) across two reductions: a spill would cost the
             # traffic the fusion removes
             "elementwise.hip": ["ln_modulate_quant_kernel", "ln_modulate_wave_quant_kernel"]}

@@ -1,7 +1,8 @@
 // What the block-scaled-MFMA GEMMs share: the 128 x 128 output tile with 128-byte K-tiles, the operand record of ONE
 // product, the f32 epilogue on the 32 x 32 result layout, and the grouped form's table entry with its fused q/k/v preparation.
 // Included by gemm_fp8.hip (e4m3 x e4m3, every form) and gemm_mxfp4.hip (e2m1 x e2m1, single and grouped): the result layout of
-// v_mfma_scale_f32_32x32x64_f8f6f4 does not depend on the operand format, so one epilogue serves both.
+// v_mfma_scale_f32_32x32x64_f8f6f4 does not depend on the operand format, so one epilogue serves both.  gemm_mxfp6.hip (e2m3 x e2m3)
+// takes the tile order, the clock probe, the epilogue and the host side; its K-tile is 96 bytes a row, staged by its own code.
 #pragma once
 #include "common.h"
 #include "fp8_quant.h"   // the MX output of the epilogue
@@ -401,6 +402,7 @@ struct Fp8Format {
     const char* ld_unit;     // the unit of the 2^22 bound
     bool scales_aligned;     // the alignment of the format's own scale operands
     const char* align_note;  // the parenthesis of the alignment message
+    int code_bits = 0;       // 6 (e2m3): a code row is K * 6 / 8 bytes and codes_per_byte is not read; 0 = by codes_per_byte
 };
 
 // M, N, K, the epilogue, the leading dimensions, the alignment of A / W / C / bias / gate / R and the tile count (tile0 = the tiles
@@ -415,7 +417,7 @@ static int fp8_check_tile_problem(const char* who, const Fp8Where& at, const Fp8
                    "%s: f32 output (epilogue %d%s, the f32 residual stream) is not supported: the output is bf16", who, epilogue, at.of);
     APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU || epilogue == APEXMI_EPI_BIAS_GATE_RES,
                    "%s: epilogue %d%s is not one of bias (0), tanh GELU (1), gate x y + residual (2)", who, epilogue, at.of);
-    const int kb = K / f.codes_per_byte;
+    const int kb = f.code_bits ? K / 8 * f.code_bits : K / f.codes_per_byte;
     APEXMI_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0 && lda >= kb && ldw >= kb && ldc >= N,
                    "%s: leading dimensions must keep rows 16-byte aligned%s (%slda %lld, ldw %lld, ldc %lld)", who, f.ld_note, at.colon,
                    (long long)lda, (long long)ldw, (long long)ldc);

@@ -94,4 +94,44 @@ APEXMI_DEVICE uint32_t mx4_quant8(const u32x4 v, float inv) {
     return r;
 }
 
+// ---- MXFP6 block quantiser (apexmi_quant_blocks_mxfp6, gemm_mxfp6.hip) -----------------------------------------------------------
+// The same block of 32 bf16 values and the same e8m0 scale byte, for OCP e2m3 codes: sign << 5 | exp << 3 | man, bias 1; exp = 0 is
+// man / 8, otherwise (1 + man / 8) 2^(exp - 1): 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5.  e = clamp(E - 2 + (man >
+// 0x700000), -126, 127)  (7.5 = 1.875 x 2^2: the smallest 2^e with amax / 2^e <= 7.5; 0 for a zero block), scale byte = e + 127,
+// code = e2m3_rne(clamp(x * 2^-e, -7.5, 7.5)): round to nearest, ties to the even code; the sign bit of x is KEPT, also on a zero
+// magnitude.  VALU arithmetic as mx4_code, not v_cvt_scalef32_pk32_fp6_bf16: that instruction's tie rule, saturation and sign of
+// zero have not been checked against this definition.
+APEXMI_DEVICE int mx6_scale_byte(float amax) {
+    const uint32_t b = __float_as_uint(amax) & 0x7fffffffu;
+    if (b == 0u) return 127;
+    const int e = (int)(b >> 23) - 127 - 2 + ((b & 0x7fffffu) > 0x700000u ? 1 : 0);
+    return min(max(e, -126), 127) + 127;
+}
+
+// one value -> its e2m3 code (6 bits).  y = min(|x| 2^-e, 7.5) is exact.  y >= 1: the low five code bits are the float's exponent
+// and top three mantissa bits after rounding the other 20 to nearest even (1.0 = exponent field 127 -> exp 1, man 0 = 8; a carry
+// out of the mantissa moves into the exponent, as it must); y < 1: the grid is k / 8, and y + 2^20 (ulp 2^-3) rounds to nearest-even
+// eighths, its four lowest mantissa bits are the code (8 / 8 = code 8 = 1.0).
+APEXMI_DEVICE uint32_t mx6_code(float x, float inv) {
+    const float y = fminf(fabsf(x) * inv, 7.5f);
+    const uint32_t b = __float_as_uint(y);
+    const uint32_t normal = ((b + 0x7ffffu + ((b >> 20) & 1u)) >> 20) - 1008u;
+    const uint32_t sub = __float_as_uint(y + 1048576.0f) & 15u;
+    return (y < 1.0f ? sub : normal) | ((__float_as_uint(x) >> 26) & 32u);
+}
+
+// 16 bf16 (8 dwords) -> 16 codes in three dwords: code j in bits 6 j .. 6 j + 5 of the 96-bit little-endian integer, half of a
+// block's 24 bytes
+APEXMI_DEVICE void mx6_quant16(const u32x4 v0, const u32x4 v1, float inv, uint32_t (&out)[3]) {
+    uint32_t c[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        c[2 * i] = mx6_code(bf16_lo(v0[i]), inv), c[2 * i + 1] = mx6_code(bf16_hi(v0[i]), inv);
+        c[8 + 2 * i] = mx6_code(bf16_lo(v1[i]), inv), c[9 + 2 * i] = mx6_code(bf16_hi(v1[i]), inv);
+    }
+    out[0] = c[0] | c[1] << 6 | c[2] << 12 | c[3] << 18 | c[4] << 24 | c[5] << 30;
+    out[1] = c[5] >> 2 | c[6] << 4 | c[7] << 10 | c[8] << 16 | c[9] << 22 | c[10] << 28;
+    out[2] = c[10] >> 4 | c[11] << 2 | c[12] << 8 | c[13] << 14 | c[14] << 20 | c[15] << 26;
+}
+
 }  // namespace

@@ -26,7 +26,8 @@ class WanT2VEngine(EngineLoraMixin):
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
-                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None):
+                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None,
+                 fp6_compute: bool = False, fp6_linears=None):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -85,6 +86,15 @@ class WanT2VEngine(EngineLoraMixin):
         if self.fp4_compute:
             for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
                 tr.set_fp4_compute(True, linears=self.fp4_linears)
+        # the same with MXFP6 (`set_fp6_compute`: the error class of fp8 on the fp4 matrix rate); both may be on with disjoint
+        # `*_linears`, e.g. fp6 for the attention projections and fp4 for the FFN pair — the model refuses a name selected by both
+        self.fp6_compute = bool(fp6_compute)
+        self.fp6_linears = None if fp6_linears is None else tuple(fp6_linears)
+        if self.fp6_linears is not None and not self.fp6_compute:
+            raise ValueError("fp6_linears needs fp6_compute=True: it names the Linears of the MXFP6 compute mode")
+        if self.fp6_compute:
+            for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
+                tr.set_fp6_compute(True, linears=self.fp6_linears)
         self.vae = vae
         self.scheduler = scheduler or UniPCMultistepScheduler(shift=3.0)
         self.boundary_ratio = boundary_ratio
@@ -277,12 +287,14 @@ class WanI2VEngine(WanT2VEngine):
                  vae_scale_factor_temporal: int = 4, vae_scale_factor_spatial: int = 8, text_encoder=None, image_encoder=None,
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
-                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None):
+                 fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None,
+                 fp6_compute: bool = False, fp6_linears=None):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
                          vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
                          attention_window=attention_window, fp8_compute=fp8_compute,
                          attention_band=attention_band, fp8_lora=fp8_lora, fp8_fused_quant=fp8_fused_quant,
-                         fp8_mx_ffn=fp8_mx_ffn, fp4_compute=fp4_compute, fp4_linears=fp4_linears)
+                         fp8_mx_ffn=fp8_mx_ffn, fp4_compute=fp4_compute, fp4_linears=fp4_linears,
+                         fp6_compute=fp6_compute, fp6_linears=fp6_linears)
         self.image_encoder = image_encoder
 
     @property

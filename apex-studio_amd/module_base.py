@@ -414,20 +414,19 @@ class F32ResidualMixin:
         return self
 
 
-class Fp4ComputeMixin:
-    """The switch of the opt-in MXFP4 compute mode (DESIGN.md §3.6) of the Flux and Wan transformers, in front of F32ResidualMixin
-    in the bases: name validation, the refusals, attaching / detaching the `ops.Mxfp4Weight` records that sit BESIDE the bf16 block
-    weights (on each weight's `_fp4` slot), `_fp4_bytes`, and the two dtype guards.
+class _MxComputeSwitch:
+    """What the switches of the two opt-in block-format compute modes share (`Fp4ComputeMixin`: MXFP4,
+    `Fp6ComputeMixin`: MXFP6): name validation, the refusals, attaching / detaching the records that sit BESIDE the bf16 block weights,
+    the byte count, and the two dtype guards — ONE implementation, parameterised by the mode's name `n` ("fp4" / "fp6"): the
+    weight's slot is `_<n>`, the record class `_MX_RECORDS[n]`, the switch `set_<n>_compute`, the state `_<n>_linears` (the selected
+    names while the mode is on, else None), `_<n>_live` (the weights that carry a record) and `_<n>_bytes`.
 
-    A class supplies `_FP4_LINEARS` (the names `linears=` takes), `_fp4_blocks()` (its blocks) and `_fp4_weights(blk)` ({name: the
-    weight, or a tuple of weights, of that name in that block}; a name a block does not have is absent), calls `_fp4_detach()` where
-    its weights change (`_weights_changed`, a merged LoRA) and `_fp4_refresh()` after `pack()` in `forward`.  The messages start with
-    the class's `_tag`."""
+    Both modes take the names `_FP4_LINEARS` and find the weights through `_fp4_blocks()` (the blocks) and `_fp4_weights(blk)` ({name:
+    the weight, or a tuple of weights, of that name in that block}; a name a block does not have is absent), which the class supplies.
+    A Linear takes at most one of the modes: a name selected by both is refused.  The messages start with the class's `_tag`."""
 
+    _MX_RECORDS = {"fp4": "Mxfp4Weight", "fp6": "Mxfp6Weight"}
     _FP4_LINEARS: tuple = ()
-    _fp4_linears = None      # the selected names while the mode is on
-    _fp4_live: tuple = ()    # the weights that carry a record
-    _fp4_bytes = 0
 
     def _fp4_blocks(self):
         raise NotImplementedError
@@ -435,75 +434,142 @@ class Fp4ComputeMixin:
     def _fp4_weights(self, blk) -> dict:
         raise NotImplementedError
 
-    def _fp4_switch(self, on: bool, linears=None):
-        """`set_fp4_compute(on, linears)` of the class: the names are checked before anything else, so that needs no device."""
+    def _mx_switch(self, n: str, on: bool, linears=None):
+        """`set_<n>_compute(on, linears)` of the class: the names are checked before anything else, so that needs no device."""
         if linears is not None:
             try:
                 linears = tuple(linears)
             except TypeError as err:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=) takes names out of {self._FP4_LINEARS}, got {linears!r}") from err
-            bad = [n for n in linears if n not in self._FP4_LINEARS]
+                raise _l.ApexMIError(f"{self._tag}: set_{n}_compute(linears=) takes names out of {self._FP4_LINEARS}, got {linears!r}") from err
+            bad = [name for name in linears if name not in self._FP4_LINEARS]
             if bad:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(linears=): unknown Linear name(s) {bad}; the block Linears are "
+                raise _l.ApexMIError(f"{self._tag}: set_{n}_compute(linears=): unknown Linear name(s) {bad}; the block Linears are "
                                      f"{self._FP4_LINEARS}")
         if not on:
             if linears is not None:
-                raise _l.ApexMIError(f"{self._tag}: set_fp4_compute(False) takes no `linears`: it detaches every record")
-            self._fp4_linears = None
-            self._fp4_detach()
+                raise _l.ApexMIError(f"{self._tag}: set_{n}_compute(False) takes no `linears`: it detaches every record")
+            setattr(self, f"_{n}_linears", None)
+            self._mx_detach(n)
             return self
+        selected = tuple(name for name in self._FP4_LINEARS if linears is None or name in linears)
+        for other in self._MX_RECORDS:
+            both = [name for name in selected if other != n and name in (getattr(self, f"_{other}_linears", None) or ())]
+            if both:
+                raise _l.ApexMIError(f"{self._tag}: set_{n}_compute(linears=): {both} multiply as {other} already (set_{other}_compute): "
+                                     f"a Linear takes one of the two modes, so select disjoint names or switch {other} compute off first")
         if getattr(self, "_fp8_bytes", 0):
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute needs the bf16 block weights, and this model's are resident quantised "
+            raise _l.ApexMIError(f"{self._tag}: set_{n}_compute needs the bf16 block weights, and this model's are resident quantised "
                                  f"records ({self._fp8_options()} load).  The fp8_* switches need exactly such records, so the two "
-                                 "modes cannot be combined: load without those options for fp4 compute")
+                                 f"modes cannot be combined: load without those options for {n} compute")
         if self.storage_dtype != torch.bfloat16:
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute is for bfloat16 activation storage; the f32-storage verification "
+            raise _l.ApexMIError(f"{self._tag}: set_{n}_compute is for bfloat16 activation storage; the f32-storage verification "
                                  "mode keeps the bf16 GEMMs (set_storage_dtype(torch.bfloat16) first)")
         if self.residual_dtype != torch.bfloat16:
-            raise _l.ApexMIError(f"{self._tag}: set_fp4_compute does not take the f32 residual stream: its residual GEMMs write "
-                                 "float rows, which the fp4 GEMM does not (set_residual_dtype(torch.bfloat16) first)")
+            raise _l.ApexMIError(f"{self._tag}: set_{n}_compute does not take the f32 residual stream: its residual GEMMs write "
+                                 f"float rows, which the {n} GEMM does not (set_residual_dtype(torch.bfloat16) first)")
         self.pack()
-        self._fp4_linears = tuple(n for n in self._FP4_LINEARS if linears is None or n in linears)
-        self._fp4_detach()
-        self._fp4_attach()
+        setattr(self, f"_{n}_linears", selected)
+        self._mx_detach(n)
+        self._mx_attach(n)
         return self
 
+    def _mx_guard_storage(self, n: str, dtype: torch.dtype):
+        if dtype == torch.float32 and getattr(self, f"_{n}_linears") is not None:
+            raise _l.ApexMIError(f"{self._tag}: {n} compute is on and is for bfloat16 activation storage: float rows would quietly "
+                                 f"return every Linear to bf16; set_{n}_compute(False) first")
+
+    def _mx_guard_residual(self, n: str, dtype: torch.dtype):
+        if dtype == torch.float32 and getattr(self, f"_{n}_linears") is not None:
+            raise _l.ApexMIError(f"{self._tag}: {n} compute is on and does not take the f32 residual stream: its residual GEMMs "
+                                 f"would quietly return to bf16; set_{n}_compute(False) first")
+
+    @torch.no_grad()
+    def _mx_attach(self, n: str):
+        """One record per weight of the selected names of every block, on the slot `ops.gemm` reads (`weight._<n>`)."""
+        record, slot, live = getattr(ops, self._MX_RECORDS[n]), f"_{n}", []
+        for blk in self._fp4_blocks():
+            ws = self._fp4_weights(blk)
+            for name in getattr(self, f"_{n}_linears"):
+                for w in ((ws[name],) if isinstance(ws.get(name), torch.Tensor) else ws.get(name, ())):
+                    setattr(w, slot, record.from_bf16(w))
+                    live.append(w)
+        setattr(self, f"_{n}_live", live)
+        setattr(self, f"_{n}_bytes", sum(getattr(w, slot).nbytes() for w in live))
+
+    def _mx_detach(self, n: str):
+        for w in getattr(self, f"_{n}_live"):
+            if getattr(w, f"_{n}", None) is not None:
+                delattr(w, f"_{n}")
+        setattr(self, f"_{n}_live", [])
+        setattr(self, f"_{n}_bytes", 0)
+
+    def _mx_refresh(self, n: str):
+        """Before a forward: the records a weight change dropped while the mode is on are rebuilt from the weights as they are now."""
+        if getattr(self, f"_{n}_linears") is not None and not getattr(self, f"_{n}_live"):
+            self._mx_attach(n)
+
+
+class Fp4ComputeMixin(_MxComputeSwitch):
+    """The switch of the opt-in MXFP4 compute mode (DESIGN.md §3.6) of the Flux and Wan transformers, in front of F32ResidualMixin
+    in the bases: name validation, the refusals, attaching / detaching the `ops.Mxfp4Weight` records that sit BESIDE the bf16 block
+    weights (on each weight's `_fp4` slot), `_fp4_bytes`, and the two dtype guards (`_MxComputeSwitch` with the mode "fp4").
+
+    A class supplies `_FP4_LINEARS` (the names `linears=` takes), `_fp4_blocks()` (its blocks) and `_fp4_weights(blk)` ({name: the
+    weight, or a tuple of weights, of that name in that block}; a name a block does not have is absent), calls `_fp4_detach()` where
+    its weights change (`_weights_changed`, a merged LoRA) and `_fp4_refresh()` after `pack()` in `forward`.  The messages start with
+    the class's `_tag`."""
+
+    _fp4_linears = None      # the selected names while the mode is on
+    _fp4_live: tuple = ()    # the weights that carry a record
+    _fp4_bytes = 0
+
+    def _fp4_switch(self, on: bool, linears=None):
+        return self._mx_switch("fp4", on, linears)
+
     def set_storage_dtype(self, dtype: torch.dtype):
-        if dtype == torch.float32 and self._fp4_linears is not None:
-            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and is for bfloat16 activation storage: float rows would quietly "
-                                 "return every Linear to bf16; set_fp4_compute(False) first")
+        self._mx_guard_storage("fp4", dtype)
         return super().set_storage_dtype(dtype)
 
     def set_residual_dtype(self, dtype: torch.dtype):
-        if dtype == torch.float32 and self._fp4_linears is not None:
-            raise _l.ApexMIError(f"{self._tag}: fp4 compute is on and does not take the f32 residual stream: its residual GEMMs "
-                                 "would quietly return to bf16; set_fp4_compute(False) first")
+        self._mx_guard_residual("fp4", dtype)
         return super().set_residual_dtype(dtype)
 
-    @torch.no_grad()
     def _fp4_attach(self):
-        """One Mxfp4Weight per weight of the selected names of every block, on the slot `ops.gemm` reads (`weight._fp4`)."""
-        live = []
-        for blk in self._fp4_blocks():
-            ws = self._fp4_weights(blk)
-            for name in self._fp4_linears:
-                for w in ((ws[name],) if isinstance(ws.get(name), torch.Tensor) else ws.get(name, ())):
-                    w._fp4 = ops.Mxfp4Weight.from_bf16(w)
-                    live.append(w)
-        self._fp4_live = live
-        self._fp4_bytes = sum(w._fp4.nbytes() for w in live)
+        self._mx_attach("fp4")
 
     def _fp4_detach(self):
-        for w in self._fp4_live:
-            if getattr(w, "_fp4", None) is not None:
-                del w._fp4
-        self._fp4_live = []
-        self._fp4_bytes = 0
+        self._mx_detach("fp4")
 
     def _fp4_refresh(self):
-        """Before a forward: the records a weight change dropped while the mode is on are rebuilt from the weights as they are now."""
-        if self._fp4_linears is not None and not self._fp4_live:
-            self._fp4_attach()
+        self._mx_refresh("fp4")
+
+
+class Fp6ComputeMixin(_MxComputeSwitch):
+    """The switch of the opt-in MXFP6 compute mode, beside Fp4ComputeMixin in the bases of a class that supplies what
+    that mixin asks for: `ops.Mxfp6Weight` records on each selected weight's `_fp6` slot, `_fp6_bytes`, the same names, refusals and
+    dtype guards (`_MxComputeSwitch` with the mode "fp6").  The class calls `_fp6_detach()` / `_fp6_refresh()` where it calls the fp4
+    ones.  Both modes may be on when their `linears` are disjoint."""
+
+    _fp6_linears = None
+    _fp6_live: tuple = ()
+    _fp6_bytes = 0
+
+    def _fp6_switch(self, on: bool, linears=None):
+        return self._mx_switch("fp6", on, linears)
+
+    def set_storage_dtype(self, dtype: torch.dtype):
+        self._mx_guard_storage("fp6", dtype)
+        return super().set_storage_dtype(dtype)
+
+    def set_residual_dtype(self, dtype: torch.dtype):
+        self._mx_guard_residual("fp6", dtype)
+        return super().set_residual_dtype(dtype)
+
+    def _fp6_detach(self):
+        self._mx_detach("fp6")
+
+    def _fp6_refresh(self):
+        self._mx_refresh("fp6")
 
 
 class Fp8ResidentMixin:

@@ -867,6 +867,149 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
     return out
 
 
+# ---- opt-in MXFP6 compute: e2m3 codes, 32 to 24 bytes, one e8m0 scale byte per 32 consecutive k ---------------------
+# the magnitudes of the low five code bits (exp << 3 | man, bias 1; exp = 0 is man / 8); bit 5 is the sign
+E2M3_VALUES = tuple(m / 8 if e == 0 else (1 + m / 8) * 2.0 ** (e - 1) for e in range(4) for m in range(8))
+
+
+def quant_blocks_mxfp6(a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP6 block quantisation of bf16 `a` [M, K] (row stride free, K % 32 == 0) -> (codes uint8 [M, 3 K / 4]: OCP e2m3, block b of a
+    row = bytes 24 b .. 24 b + 23, code j of the block = bits 6 j .. 6 j + 5 of those bytes as one little-endian integer; scales uint8
+    [M, K / 32] = e8m0 exponents; row strides free, code rows 8-byte aligned — 16 for `gemm_mxfp6`, which the default `out` has).  Per
+    block of 32 consecutive columns:
+        amax = max |a| with unbiased f32 exponent E and mantissa bits man;  e = clamp(E - 2 + (man > 0x700000), -126, 127)
+        (0 for a zero block);  scale byte = e + 127;  code = e2m3_rne(clamp(a * 2^-e, -7.5, 7.5))
+    2^e is the smallest power of two with amax / 2^e <= 7.5, so the clamp clips nothing; ties go to the even code and the sign bit of
+    `a` is kept, also where the magnitude rounds to zero.  Inputs must be finite.  One launch; what `gemm_mxfp6` reads on both sides."""
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"quant_blocks_mxfp6.a: expected a torch.bfloat16 tensor, got {getattr(a, 'dtype', type(a).__name__)}")
+    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 32 != 0 or a.shape[1] < 32 or a.shape[0] < 1:
+        raise _l.ApexMIError(f"quant_blocks_mxfp6.a: expected [M >= 1, K % 32 == 0] with contiguous rows, got {tuple(a.shape)}")
+    M, K = a.shape
+    kb = K // 4 * 3
+    if out is None:
+        out = torch.empty((M, (kb + 15) // 16 * 16), dtype=torch.uint8, device=a.device)[:, :kb]
+    if scale_out is None:
+        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
+    _check_mxfp6_pair("quant_blocks_mxfp6.out", out, scale_out, M, K)
+    _req(a, torch.bfloat16, "quant_blocks_mxfp6.a")
+    _l.check(_l.load().apexmi_quant_blocks_mxfp6(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
+                                                 scale_out.stride(0), _stream()), "quant_blocks_mxfp6")
+    return out, scale_out
+
+
+def _check_mxfp6_pair(who: str, q, s, M: int, K: int, on_device: bool = True) -> None:
+    """An MXFP6 (codes [M, 3 K / 4], scales [M, K / 32]) pair, as `_check_mxfp4_pair`"""
+    for name, t, cols in (("codes", q, K // 4 * 3), ("scales", s, K // 32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise _l.ApexMIError(f"{who}: the {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+        if t.dim() != 2 or tuple(t.shape) != (M, cols) or t.stride(1) != 1:
+            raise _l.ApexMIError(f"{who}: the {name} must be [{M}, {cols}] with contiguous rows (K = {K}), got {tuple(t.shape)}")
+        if on_device:
+            _req(t, torch.uint8, f"{who} ({name})")
+
+
+def _unpack_e2m3(q: torch.Tensor) -> torch.Tensor:
+    """uint8 [R, 3 K / 4] -> the 6-bit codes int64 [R, K]: 4 codes per 3 bytes, little-endian"""
+    b = q.long().view(q.shape[0], -1, 3)
+    v = b[..., 0] | b[..., 1] << 8 | b[..., 2] << 16
+    return torch.stack([(v >> s) & 63 for s in (0, 6, 12, 18)], dim=-1).view(q.shape[0], -1)
+
+
+class Mxfp6Weight:
+    """An MXFP6 copy of a bf16 weight [N, K] for the opt-in fp6 compute: `q` uint8 [N, 3 K / 4] e2m3 codes, `s` uint8 [N, K / 32]
+    e8m0 scale bytes, as `quant_blocks_mxfp6` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
+    sits beside it (on the weight tensor's `_fp6` slot, where `ops.gemm` looks); 0.78 bytes per weight element.  `compute`: "fp6"
+    (routed by `mxfp6_route`) or anything else (ignored)."""
+
+    def __init__(self, q: torch.Tensor, s: torch.Tensor):
+        if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] % 24 != 0:
+            raise _l.ApexMIError(f"Mxfp6Weight: the codes must be a uint8 [N, 3 K / 4] tensor of whole 24-byte blocks, got "
+                                 f"{tuple(getattr(q, 'shape', ()))}")
+        N, K = q.shape[0], q.shape[1] // 3 * 4
+        _check_mxfp6_pair("Mxfp6Weight", q, s, N, K, on_device=False)      # a CPU record can still be asked for its route
+        self.q, self.s, self.shape, self.compute = q, s, (N, K), "fp6"
+
+    @classmethod
+    def from_bf16(cls, w: torch.Tensor) -> "Mxfp6Weight":
+        return cls(*quant_blocks_mxfp6(w))
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return self.q.numel() + self.s.numel()
+
+    def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """bf16 [N, K] = value(code) x 2^(scale byte - 127): exact in bf16 (four significant bits times a power of two) unless it
+        overflows, which only a block holding values above 2^127 produces.  Plain torch: test and tool support, not a hot path."""
+        N, K = self.shape
+        lut = torch.tensor(E2M3_VALUES + tuple(-v for v in E2M3_VALUES), dtype=torch.float32, device=self.q.device)
+        v = lut[_unpack_e2m3(self.q)].view(N, K // 32, 32)
+        v = (v * torch.exp2(self.s.float() - 127.0).unsqueeze(-1)).view(N, K).to(torch.bfloat16)
+        if out is None:
+            return v
+        _req(out, torch.bfloat16, "Mxfp6Weight.dequant.out")
+        out.copy_(v)
+        return out
+
+
+def _fp6_of(w):
+    """The MXFP6 record behind `w` (an Mxfp6Weight, or a weight tensor carrying one in `_fp6`), or None."""
+    return w if isinstance(w, Mxfp6Weight) else getattr(w, "_fp6", None)
+
+
+def mxfp6_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
+    """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as `quant_blocks_mxfp6` + `gemm_mxfp6`.  Pure: reads dtypes, shapes
+    and strides only (CPU and meta tensors are fine).  True only when ALL of these hold:
+      * `w` is (or carries in `_fp6`) an `Mxfp6Weight` with `compute == "fp6"`;
+      * `a` is bf16 and `out` is bf16 or None (float activations = the f32-storage mode and a float `out` = the f32 residual
+        stream keep the bf16 path);
+      * the shape is eligible: M >= 1, K % 128 == 0, N % 16 == 0, 16-byte rows of `a`, and the epilogue is one of bias / gelu /
+        gate_res."""
+    f6 = _fp6_of(w)
+    if not isinstance(f6, Mxfp6Weight) or f6.compute != "fp6":
+        return False
+    return _block_gemm_route(a, f6.shape, out, epilogue, 128)
+
+
+_fp6_act_scratch: dict = {}
+
+
+def _act_scratch_mxfp6(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-stream home of the activation's MXFP6 codes [M, 3 K / 4] and scale bytes [M, K / 32] (as `_act_scratch`)."""
+    kb = K // 4 * 3
+    q, s = _stream_scratch(_fp6_act_scratch, dev, (M * kb, torch.uint8), (M * (K // 32), torch.uint8))
+    return q[:M * kb].view(M, kb), s[:M * (K // 32)].view(M, K // 32)
+
+
+def gemm_mxfp6(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp6Weight", bias: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] (bf16) = epi(sum_k value(codes[m, k]) 2^(scales[m, k / 32] - 127) value(w.q[n, k]) 2^(w.s[n, k / 32] - 127) + bias):
+    e2m3 x e2m3 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, one bf16 rounding.  `codes` /
+    `scales` as `quant_blocks_mxfp6` returns them; `w` an `Mxfp6Weight`; epilogue bias / gelu / gate_res (`residual` may be `out`).
+    K % 128 == 0, N % 16 == 0."""
+    who = "gemm_mxfp6"
+    if not isinstance(w, Mxfp6Weight):
+        raise _l.ApexMIError(f"{who}: expected an Mxfp6Weight, got {type(w).__name__}")
+    if epilogue not in _FP8_EPI:
+        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2:
+        raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, 3 K / 4] tensor, got {type(codes).__name__}")
+    M, (N, K) = codes.shape[0], w.shape
+    _check_mxfp6_pair(who, codes, scales, M, K)
+    out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
+    rc = _l.load().apexmi_gemm_mxfp6(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
+                                     w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
+                                     _EPI[epilogue] | flag, _ptr(gate), _ptr(residual),
+                                     residual.stride(0) if epilogue == "gate_res" else 0, _stream())
+    _l.check(rc, who)
+    return out
+
+
 FP8_MAX_GROUPS = 4
 
 
@@ -1231,7 +1374,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
 
     OPT-IN MXFP4 COMPUTE: a bf16 weight that carries an `Mxfp4Weight` with `compute == "fp4"` in its `_fp4` slot
     (`set_fp4_compute` of the model attaches it) takes `quant_blocks_mxfp4` (codes and scale bytes in a per-stream scratch) +
-    `gemm_mxfp4` when `mxfp4_route` says so, asked before everything above.  A weight without the slot never reaches that code."""
+    `gemm_mxfp4` when `mxfp4_route` says so, asked before everything above.  A weight without the slot never reaches that code.
+
+    OPT-IN MXFP6 COMPUTE: the same with an `Mxfp6Weight` (`compute == "fp6"`) in the weight's `_fp6` slot
+    (`set_fp6_compute`), `quant_blocks_mxfp6` + `gemm_mxfp6` and `mxfp6_route`.  A weight carries at most one of the two slots
+    (the models' switches see to it); `gemm_grouped` routes neither."""
     _req_act(a, "gemm.a")
     if getattr(w, "_fp4", None) is not None and mxfp4_route(a, w, out, epilogue):
         if quantised is not None or out_mx is not None:
@@ -1240,6 +1387,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         qa, sa = _act_scratch_mxfp4(a.device, a.shape[0], a.shape[1])
         quant_blocks_mxfp4(a, out=qa, scale_out=sa)
         return gemm_mxfp4(qa, sa, w._fp4, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
+    if getattr(w, "_fp6", None) is not None and mxfp6_route(a, w, out, epilogue):
+        if quantised is not None or out_mx is not None:
+            raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP6 route (the weight "
+                                 "carries an Mxfp6Weight): e4m3 codes are not fp6 operands")
+        qa, sa = _act_scratch_mxfp6(a.device, a.shape[0], a.shape[1])
+        quant_blocks_mxfp6(a, out=qa, scale_out=sa)
+        return gemm_mxfp6(qa, sa, w._fp6, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
         qa, sa = _fp8_acts(a, quantised)

@@ -34,7 +34,7 @@ import torch.nn as nn
 
 from . import lib as _l
 from . import ops
-from .module_base import F32ResidualMixin, Fp4ComputeMixin, Fp8ResidentMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
+from .module_base import F32ResidualMixin, Fp4ComputeMixin, Fp6ComputeMixin, Fp8ResidentMixin, HipTransformer, _Config, _FF, _Linear, _Norm, _fuse_linears
 
 
 class _WanAttn(nn.Module):
@@ -110,7 +110,7 @@ class _Conv3dParams(nn.Module):
         self.bias = nn.Parameter(torch.empty(cout, **kw), requires_grad=False)
 
 
-class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin, HipTransformer):
+class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, Fp6ComputeMixin, F32ResidualMixin, HipTransformer):
     _converter_base = "wan.base"      # which key-converter table original-format weight files / LoRAs go through (converters.py)
     _tag = "wan.mi355"
     _drops = {"moved": ("_packed", "_ws", "_rope", "_window_plans", "_band_plans"), "loaded": ("_packed",), "storage": ("_ws",)}
@@ -288,6 +288,19 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin,
         refuse float32 while the mode is on), and an unknown name in `linears`."""
         return self._fp4_switch(on, linears)      # module_base.Fp4ComputeMixin: the part of the switch shared with Flux
 
+    def set_fp6_compute(self, on: bool, linears=None):
+        """Opt-in approximation: `set_fp4_compute` with MXFP6 in the place of MXFP4 — the selected block Linears
+        (the same seven names, None = all) quantise their activations per block of 32 to OCP e2m3 and multiply e2m3 x e2m3
+        (`ops.quant_blocks_mxfp6` + `ops.gemm_mxfp6`) against an MXFP6 copy of the weight (`ops.Mxfp6Weight.from_bf16`) on the
+        weight's `_fp6` slot: 0.78 bytes per selected weight element on top of the model.  The error class of the fp8 mode (three
+        mantissa bits) on the fp4 matrix instruction's rate; no quality claim on real checkpoints.  The records follow the same
+        invalidation rule, and the refusals are those of `set_fp4_compute`.
+
+        Both modes may be on at once when their `linears` are disjoint (fp6 for the attention projections, fp4 for the FFN pair):
+        a name selected by both is refused, by either switch, before anything touches the device.  False detaches the fp6 records
+        only."""
+        return self._fp6_switch(on, linears)      # module_base.Fp6ComputeMixin
+
     def _fp4_blocks(self):
         return self.blocks
 
@@ -399,6 +412,7 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin,
         super()._lora_remerge(modules - resident)
         if modules - resident:
             self._fp4_detach()      # merged into the bf16 weights: the MXFP4 copies are rebuilt before the next forward
+            self._fp6_detach()      # and the MXFP6 ones
 
     def state_dict(self, *a, **k):
         self._fp8_guard("state_dict")
@@ -408,8 +422,9 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin,
     def _weights_changed(self):
         """Rebuild what is DERIVED from parameter values (f32 copies of the modulation tables, [L, 6*dim] and
         [2*dim]).  `weights.load_checkpoint_into` writes parameters in place after `pack()` and calls this.  The MXFP4 copies
-        of `set_fp4_compute` are dropped here and rebuilt before the next forward."""
+        of `set_fp4_compute` and the MXFP6 copies of `set_fp6_compute` are dropped here and rebuilt before the next forward."""
         self._fp4_detach()
+        self._fp6_detach()
         if not self._packed:
             return
         dim, dev = self.inner_dim, self.device
@@ -631,6 +646,7 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin,
             raise NotImplementedError("wan.mi355: per-token timesteps are not supported")
         self.pack()
         self._fp4_refresh()
+        self._fp6_refresh()
         enc = encoder_hidden_states.to(self.storage_dtype)
         img = None
         if encoder_hidden_states_image is not None and self.config.added_kv_proj_dim is not None:

@@ -947,6 +947,32 @@ int apexmi_gemm_mxfp4_grouped_qkv(int count, const void* const* qa, const int64_
                                   float eps, const float* rope, void* q_out, void* k_out, void* vt_out, int S_out, int Skp,
                                   apexmi_stream_t stream);
 
+/* MXFP6 compute (opt-in): OCP e2m3 codes, 6 bits = sign << 5 | exp << 3 | man with bias 1 (exp = 0: man / 8; otherwise
+ * (1 + man / 8) 2^(exp - 1): the magnitudes 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), with one e8m0 scale byte per 32
+ * consecutive k, as apexmi_quant_blocks_mxfp4.  A row of K codes is 3 K / 4 bytes: block b is bytes 24 b .. 24 b + 23, and code j of the
+ * block is bits 6 j .. 6 j + 5 of those 24 bytes read as one little-endian integer.  Per block of 32 columns (aligned to 32), on the
+ * bf16 values:
+ *     amax = max |x|, E = its unbiased f32 exponent, man = its 23 mantissa bits;
+ *     e = clamp(E - 2 + (man > 0x700000), -126, 127), 0 for a zero block    (7.5 = 1.875 x 2^2: the smallest 2^e with amax / 2^e <= 7.5)
+ *     scale byte = e + 127 (127 for a zero block, never 255);   code = e2m3( min(max(x * 2^-e, -7.5), 7.5) )   nearest, ties to the even code
+ * The sign bit of x is kept, also where the magnitude rounds to zero.  Inputs are finite.
+ *
+ * apexmi_quant_blocks_mxfp6 — a bf16 [M, K] (row stride lda elements, 16-byte rows); codes uint8 [M, 3 K / 4] (row stride ldq bytes,
+ * 8-byte rows at least; apexmi_gemm_mxfp6 asks for 16); scales uint8 [M, K / 32] (row stride lds bytes).  K % 32 == 0, M >= 1.  One
+ * streaming pass. */
+int apexmi_quant_blocks_mxfp6(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* scales, int64_t lds,
+                              apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp6 — C[M, N] (bf16, row stride ldc) = epi(sum_k a[m, k] 2^(sa[m, k / 32] - 127) w[n, k] 2^(sw[n, k / 32] - 127) + bias[n]):
+ * e2m3 x e2m3 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, nothing is multiplied after the K-loop.
+ * qa [M, 3 K / 4], qw [N, 3 K / 4] codes (row strides lda, ldw in bytes, multiples of 16, 16-byte aligned); sa [M, K / 32], sw [N, K / 32]
+ * scale bytes (row strides ldsa, ldsw bytes, multiples of 4, 4-byte aligned).  bias, gate, R and the three epilogues
+ * (APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU, APEXMI_EPI_BIAS_GATE_RES; R may alias C) as apexmi_gemm_mxfp4.  K % 128 == 0, N % 16 == 0,
+ * M >= 1.  Every argument is checked before the launch. */
+int apexmi_gemm_mxfp6(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
+                      int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue, const float* gate,
+                      const void* R, int64_t ldr, apexmi_stream_t stream);
+
 /* GGUF-quantised checkpoint weights (`load_gguf`, R/src/quantize/load.py:364; the reference's `GGMLLinear` dequantises with
  * torch ops on every forward, R/src/quantize/ggml_layer.py:220).  `blocks`: the raw GGUF block bytes of an [rows, K] weight
  * (blocks run along K, rows are contiguous; any row range of a tensor is such a buffer).  out[r, c] (bf16, row stride ldo >= K
