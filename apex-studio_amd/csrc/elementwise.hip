@@ -2,7 +2,7 @@
 // q/k RMSNorm + RoPE + layout pass, V transpose, conditioning GEMV, timestep embedding, casts and
 // the Euler scheduler axpy.  All of them move 16 bytes per lane and keep statistics in f32.
 #include "common.h"
-#include "fp8_quant.h"   // FP8_MAX, quant1: the norm that quantises its own output
+#include "fp8_quant.h"   // FP8_MAX, quant1, mx4_scale_byte, mx4_quant8f: the norms that quantise their own output
 
 namespace {
 
@@ -60,6 +60,19 @@ APEXMI_DEVICE void quant_store8(uint8_t* q, const float* keep, float s) {
     *(u32x2*)q = u32x2{quant4_f32(keep, s), quant4_f32(keep + 4, s)};
 }
 
+// apexmi_quant_blocks_mxfp4's scale byte and codes from the rounded values (apexmi_ln_modulate_quant_mxfp4): a lane holds 8
+// consecutive columns, lanes 4 b .. 4 b + 3 one block of 32.  `m` = the lane's own maximum; every lane of the group must call.
+APEXMI_DEVICE int mx4_block_scale_byte(float m) {
+    m = fmaxf(m, __shfl_xor(m, 1, 64));
+    m = fmaxf(m, __shfl_xor(m, 2, 64));
+    return mx4_scale_byte(m);
+}
+// 8 codes (4 bytes) per lane and chunk; `first` = the lane of the group that stores the scale byte
+APEXMI_DEVICE void mx4_store8(uint8_t* q, uint8_t* s, bool first, const float* keep, int sb) {
+    *(uint32_t*)q = mx4_quant8f(keep, mx_inv_scale(sb));
+    if (first) *s = (uint8_t)sb;
+}
+
 // The kernel bodies live in ln_modulate_row.inc / ln_modulate_wave_rows.inc, included once per kernel: the plain kernels and the
 // quantising ones (apexmi_ln_modulate_quant_fp8) share one source of the arithmetic, and the plain kernels' text is unchanged.
 template <typename T, int NIT, typename TO = T>
@@ -76,17 +89,28 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(
 // norm + modulate + per-row e4m3 quantise in one pass (apexmi_ln_modulate_quant_fp8): ln_modulate_kernel<T, NIT, bf16_t>'s
 // arithmetic, then apexmi_quant_rows_fp8's on the rounded row, which never leaves the registers.  `out` may be null (no bf16 row
 // is stored); codes [M, C] uint8 (row stride ldq bytes), scales [M].
-template <typename T, int NIT>
+// FMT = LN_FMT_MXFP4 (apexmi_ln_modulate_quant_mxfp4): apexmi_quant_blocks_mxfp4's arithmetic instead; codes [M, C / 2], `scales_`
+// = the scale bytes [M, C / 32] with row stride lds.  One kernel name for both formats: build.py's no-spill check matches it.
+constexpr int LN_FMT_E4M3_ROWS = 1, LN_FMT_MXFP4 = 2;
+template <typename T, int NIT, int FMT = LN_FMT_E4M3_ROWS>
 __global__ __launch_bounds__(256) void ln_modulate_quant_kernel(
     const T* __restrict__ x, int64_t ldx, bf16_t* __restrict__ out, int64_t ldo, int M, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2, uint8_t* __restrict__ codes, int64_t ldq,
-    float* __restrict__ scales) {
+    void* __restrict__ scales_, int64_t lds) {
     typedef bf16_t TO;
+    if constexpr (FMT == LN_FMT_MXFP4) {
+        uint8_t* scales = (uint8_t*)scales_;
+#define LN_QUANT 2
+#include "ln_modulate_row.inc"
+#undef LN_QUANT
+    } else {
+        float* scales = (float*)scales_;
 #define LN_QUANT 1
 #include "ln_modulate_row.inc"
 #undef LN_QUANT
+    }
 }
 
 // s + a * a with the product rounded on its own, never contracted to an fma.  The square of a float is inexact, so the two forms
@@ -115,17 +139,25 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(
 }
 
 // ln_modulate_quant_kernel's wave-per-row twin: ln_modulate_wave_kernel<T, NCH, NR, bf16_t>'s arithmetic, then the quantiser's
-template <typename T, int NCH, int NR>
+template <typename T, int NCH, int NR, int FMT = LN_FMT_E4M3_ROWS>
 __global__ __launch_bounds__(256) void ln_modulate_wave_quant_kernel(
     const T* __restrict__ x, int64_t ldx, bf16_t* __restrict__ out, int64_t ldo, int M, int C,
     const float* __restrict__ scale, const float* __restrict__ shift,
     const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta, float eps, int rms, int split,
     const float* __restrict__ scale2, const float* __restrict__ shift2, uint8_t* __restrict__ codes, int64_t ldq,
-    float* __restrict__ scales) {
+    void* __restrict__ scales_, int64_t lds) {
     typedef bf16_t TO;
+    if constexpr (FMT == LN_FMT_MXFP4) {
+        uint8_t* scales = (uint8_t*)scales_;
+#define LN_QUANT 2
+#include "ln_modulate_wave_rows.inc"
+#undef LN_QUANT
+    } else {
+        float* scales = (float*)scales_;
 #define LN_QUANT 1
 #include "ln_modulate_wave_rows.inc"
 #undef LN_QUANT
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -933,17 +965,22 @@ extern "C" int apexmi_ln_modulate(const void* x, int64_t ldx, void* out, int64_t
 int g_ln_wave = 1;  // apexmi_tune_set("ln.wave", 0/1/2) for C in {3072, 3584, 5120}: 0 row-per-workgroup kernel | 1 one row per wave | 2 two rows per wave (bf16 x; bit-identical to 1)
 void apexmi_set_ln_wave(int v) { g_ln_wave = v; }
 
-// The dispatch of every norm entry point: which kernel family and how many rows per wave a (T, C, `ln.wave`) runs.  QUANT =
-// apexmi_ln_modulate_quant_fp8: the same choice, the chosen kernel's quantising twin (the two families sum in different shapes,
-// so the twin of the OTHER family would not reproduce apexmi_ln_modulate2's rows).
-template <typename T, typename TO, bool QUANT>
+// The dispatch of every norm entry point: which kernel family and how many rows per wave a (T, C, `ln.wave`) runs.  QUANT != 0
+// (LN_FMT_E4M3_ROWS = apexmi_ln_modulate_quant_fp8, LN_FMT_MXFP4 = apexmi_ln_modulate_quant_mxfp4): the same choice, the chosen
+// kernel's quantising twin in that format (the two families sum in different shapes, so the twin of the OTHER family would not
+// reproduce apexmi_ln_modulate2's rows).  `scales`: float [M], or the scale bytes with row stride `lds`.
+template <typename T, typename TO, int QUANT>
 static int ln_modulate2_launch(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,
                                const float* scale, const float* shift, const void* gamma,
                                const void* beta, float eps, int rms, int split,
-                               const float* scale2, const float* shift2, void* codes, int64_t ldq, float* scales,
+                               const float* scale2, const float* shift2, void* codes, int64_t ldq, void* scales, int64_t lds,
                                hipStream_t stream) {
-    // QUANT: x in, 1 byte of codes out, the bf16 row only if asked for, 4 bytes of scale per row
-    ApexmiProfScope prof(3, stream, 0.0, QUANT ? (double)(sizeof(T) + 1 + (out ? sizeof(TO) : 0)) * (double)M * C + 4.0 * M
+    const char* who = QUANT == LN_FMT_MXFP4 ? "ln_modulate_quant_mxfp4" : QUANT ? "ln_modulate_quant_fp8" : "ln_modulate";
+    // QUANT: x in, 1 byte of codes (MXFP4: 17 / 32 of a byte, codes and scale bytes) out, the bf16 row only if asked for, 4 bytes of
+    // scale per row
+    ApexmiProfScope prof(3, stream, 0.0,
+                         QUANT == LN_FMT_MXFP4 ? (double)(sizeof(T) + 0.53125 + (out ? sizeof(TO) : 0)) * (double)M * C
+                         : QUANT               ? (double)(sizeof(T) + 1 + (out ? sizeof(TO) : 0)) * (double)M * C + 4.0 * M
                                                : (double)(sizeof(T) + sizeof(TO)) * (double)M * C);
 #define LNW_LAUNCH_R(N, R)                                                                                                      \
     do {                                                                                                                        \
@@ -952,9 +989,9 @@ static int ln_modulate2_launch(const void* x, int64_t ldx, void* out, int64_t ld
                                (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms,          \
                                split, scale2, shift2);                                                                          \
         else if constexpr (R == 1 || sizeof(T) == 2)                                                                            \
-            hipLaunchKernelGGL((ln_modulate_wave_quant_kernel<T, N, R>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0, stream, \
-                               (const T*)x, ldx, (bf16_t*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                   \
-                               (const bf16_t*)beta, eps, rms, split, scale2, shift2, (uint8_t*)codes, ldq, scales);             \
+            hipLaunchKernelGGL((ln_modulate_wave_quant_kernel<T, N, R, QUANT>), dim3((M + 4 * R - 1) / (4 * R)), dim3(256), 0,  \
+                               stream, (const T*)x, ldx, (bf16_t*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,           \
+                               (const bf16_t*)beta, eps, rms, split, scale2, shift2, (uint8_t*)codes, ldq, scales, lds);        \
     } while (0)
 #define LNW_LAUNCH(N)                         \
     do {                                      \
@@ -971,7 +1008,7 @@ static int ln_modulate2_launch(const void* x, int64_t ldx, void* out, int64_t ld
             case 10: LNW_LAUNCH(10); break;
             default: done = false;
         }
-        if (done) return apexmi_check_launch(QUANT ? "ln_modulate_quant_fp8" : "ln_modulate");
+        if (done) return apexmi_check_launch(who);
     }
 #undef LNW_LAUNCH_R
 #undef LNW_LAUNCH
@@ -983,16 +1020,16 @@ static int ln_modulate2_launch(const void* x, int64_t ldx, void* out, int64_t ld
                                (TO*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma,                                       \
                                (const bf16_t*)beta, eps, rms, split, scale2, shift2);                                         \
         else                                                                                                                  \
-            hipLaunchKernelGGL((ln_modulate_quant_kernel<T, N>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx,             \
+            hipLaunchKernelGGL((ln_modulate_quant_kernel<T, N, QUANT>), dim3(M), dim3(256), 0, stream, (const T*)x, ldx,      \
                                (bf16_t*)out, ldo, M, C, scale, shift, (const bf16_t*)gamma, (const bf16_t*)beta, eps, rms,    \
-                               split, scale2, shift2, (uint8_t*)codes, ldq, scales);                                          \
+                               split, scale2, shift2, (uint8_t*)codes, ldq, scales, lds);                                     \
     } while (0)
     if (nit <= 1) LN_LAUNCH(1);
     else if (nit <= 2) LN_LAUNCH(2);
     else if (nit <= 3) LN_LAUNCH(3);
     else LN_LAUNCH(4);
 #undef LN_LAUNCH
-    return apexmi_check_launch(QUANT ? "ln_modulate_quant_fp8" : "ln_modulate");
+    return apexmi_check_launch(who);
 }
 
 template <typename T, typename TO = T>
@@ -1012,8 +1049,8 @@ static int ln_modulate2_impl(const void* x, int64_t ldx, void* out, int64_t ldo,
                    "ln_modulate: rows must be 16-byte aligned");
     APEXMI_REQUIRE((!scale || ((uintptr_t)scale % 16) == 0) && (!shift || ((uintptr_t)shift % 16) == 0),
                    "ln_modulate: scale/shift must be 16-byte aligned");
-    return ln_modulate2_launch<T, TO, false>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2,
-                                             nullptr, 0, nullptr, stream);
+    return ln_modulate2_launch<T, TO, 0>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2,
+                                         nullptr, 0, nullptr, 0, stream);
 }
 
 template <typename T>
@@ -1024,8 +1061,8 @@ static int ln_modulate_quant_impl(const void* x, int64_t ldx, void* out, int64_t
                        ((uintptr_t)codes % 16) == 0 && (!out || (ldo >= C && ldo % 8 == 0 && ((uintptr_t)out % 16) == 0)),
                    "ln_modulate_quant_fp8: rows must be 16-byte aligned and at least C wide (ldx %lld, ldq %lld, ldo %lld)",
                    (long long)ldx, (long long)ldq, (long long)ldo);
-    return ln_modulate2_launch<T, bf16_t, true>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2, shift2,
-                                                codes, ldq, scales, stream);
+    return ln_modulate2_launch<T, bf16_t, LN_FMT_E4M3_ROWS>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2,
+                                                            shift2, codes, ldq, scales, 0, stream);
 }
 
 // norm + modulate + per-row e4m3 quantise (include/apexmi.h): apexmi_ln_modulate2 / apexmi_ln_modulate2_f32in followed by
@@ -1053,6 +1090,40 @@ extern "C" int apexmi_ln_modulate_quant_fp8(const void* x, int64_t ldx, int x_dt
                                              scale2, shift2, stream);
     return ln_modulate_quant_impl<bf16_t>(x, ldx, out, ldo, codes, ldq, scales, M, C, scale, shift, gamma, beta, eps, rms, split,
                                           scale2, shift2, stream);
+}
+
+// norm + modulate + MXFP4 block quantise (include/apexmi.h): apexmi_ln_modulate2 / apexmi_ln_modulate2_f32in followed by
+// apexmi_quant_blocks_mxfp4, as one launch of the kernel the norm alone would have run, in its MXFP4 form
+extern "C" int apexmi_ln_modulate_quant_mxfp4(const void* x, int64_t ldx, int x_dtype, void* out, int64_t ldo, void* codes,
+                                              int64_t ldq, void* scales, int64_t lds, int M, int C, const float* scale,
+                                              const float* shift, const void* gamma, const void* beta, float eps, int rms, int split,
+                                              const float* scale2, const float* shift2, apexmi_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    APEXMI_REQUIRE(x && codes && scales, "ln_modulate_quant_mxfp4: null operand");
+    APEXMI_REQUIRE(x_dtype == APEXMI_BF16 || x_dtype == APEXMI_F32,
+                   "ln_modulate_quant_mxfp4: x_dtype=%d must be APEXMI_BF16 or APEXMI_F32", x_dtype);
+    APEXMI_REQUIRE(M >= 1, "ln_modulate_quant_mxfp4: M=%d must be at least 1", M);
+    APEXMI_REQUIRE(C >= 128 && C % 128 == 0 && C <= LN_MAX_C, "ln_modulate_quant_mxfp4: C=%d must be a multiple of 128 and <= %d", C,
+                   LN_MAX_C);
+    APEXMI_REQUIRE(split >= 0 && split <= M, "ln_modulate_quant_mxfp4: split=%d outside [0, M]", split);
+    const int xe = x_dtype == APEXMI_F32 ? 4 : 2;
+    APEXMI_REQUIRE(ldx >= C && ldx % (16 / xe) == 0 && ((uintptr_t)x % 16) == 0 && ldq >= C / 2 && ldq % 16 == 0 &&
+                       ((uintptr_t)codes % 16) == 0 && (!out || (ldo >= C && ldo % 8 == 0 && ((uintptr_t)out % 16) == 0)),
+                   "ln_modulate_quant_mxfp4: rows must be 16-byte aligned, x and out at least C and the codes at least C / 2 bytes wide "
+                   "(ldx %lld, ldq %lld, ldo %lld)", (long long)ldx, (long long)ldq, (long long)ldo);
+    APEXMI_REQUIRE(lds >= C / 32, "ln_modulate_quant_mxfp4: rows of the block scales must be at least C / 32 = %d wide (lds %lld)", C / 32,
+                   (long long)lds);
+    APEXMI_REQUIRE((!scale || ((uintptr_t)scale % 16) == 0) && (!shift || ((uintptr_t)shift % 16) == 0),
+                   "ln_modulate_quant_mxfp4: scale/shift must be 16-byte aligned");
+    APEXMI_REQUIRE(split == 0 || ((!scale2 || ((uintptr_t)scale2 % 16) == 0) && (!shift2 || ((uintptr_t)shift2 % 16) == 0)),
+                   "ln_modulate_quant_mxfp4: scale2/shift2 must be 16-byte aligned");
+    APEXMI_REQUIRE((!gamma || ((uintptr_t)gamma % 16) == 0) && (!beta || ((uintptr_t)beta % 16) == 0),
+                   "ln_modulate_quant_mxfp4: gamma/beta must be 16-byte aligned");
+    if (x_dtype == APEXMI_F32)
+        return ln_modulate2_launch<float, bf16_t, LN_FMT_MXFP4>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2,
+                                                                shift2, codes, ldq, scales, lds, stream);
+    return ln_modulate2_launch<bf16_t, bf16_t, LN_FMT_MXFP4>(x, ldx, out, ldo, M, C, scale, shift, gamma, beta, eps, rms, split, scale2,
+                                                             shift2, codes, ldq, scales, lds, stream);
 }
 
 extern "C" int apexmi_ln_modulate2(const void* x, int64_t ldx, void* out, int64_t ldo, int M, int C,

@@ -143,7 +143,12 @@ APEXMI_DEVICE void fp8_load_bias(const Fp8Problem& G, int n, float (&bs)[4]) {
 // MXIN (the MX instantiations): a problem with block-scaled activations (G.abs, block-uniform) uses sa = 1.  MXOUT (bias / gelu, N % 128 == 0): the value pack_bf16 would
 // store is quantised per 32-column block instead — a lane holds 16 of the block's columns of its row in acc[i][j], lane l ^ 32 the
 // other 16 — and leaves as 4 codes per register group plus one scale byte per block and row (the fh == 0 lane); C is not written.
-template <int EPI, bool SCALED, bool MXIN = false, bool MXOUT = false>
+// MXOUT is the FORMAT of that output: MXO_NONE, MXO_E4M3 (apexmi_quant_blocks_mxfp8's codes, a byte each; `true` of the e4m3
+// callers) or MXO_E2M1 (apexmi_quant_blocks_mxfp4's, two to a byte: Q is [M, N / 2]).  A lane's four consecutive columns are two
+// bytes of e2m1 codes; the lane pair swaps halves (one more exchange with l ^ 32) so that each lane stores two whole dwords — fh 0
+// the row's bytes of register groups 0 and 1, fh 1 those of groups 2 and 3 — instead of four 2-byte pieces.
+constexpr int MXO_NONE = 0, MXO_E4M3 = 1, MXO_E2M1 = 2;
+template <int EPI, bool SCALED, bool MXIN = false, int MXOUT = MXO_NONE>
 APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, int m0, int n0, int wr, int wc, int fr, int fh) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -194,7 +199,7 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
                     o[2] = bf16_lo(rr[g][1]) + gt[g][2] * o[2];
                     o[3] = bf16_hi(rr[g][1]) + gt[g][3] * o[3];
                 }
-                if constexpr (MXOUT) {
+                if constexpr (MXOUT != MXO_NONE) {
                     const uint32_t p0 = pack_bf16(o[0], o[1]), p1 = pack_bf16(o[2], o[3]);
                     mxv[4 * g] = bf16_lo(p0), mxv[4 * g + 1] = bf16_hi(p0), mxv[4 * g + 2] = bf16_lo(p1), mxv[4 * g + 3] = bf16_hi(p1);
 #pragma unroll
@@ -204,7 +209,24 @@ APEXMI_DEVICE void fp8_epilogue(const f32x16 (&acc)[2][2], const Fp8Problem G, i
                         *(u32x2*)(G.C + (int64_t)m * G.ldc + n) = u32x2{pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3])};
                 }
             }
-            if constexpr (MXOUT) {
+            if constexpr (MXOUT == MXO_E2M1) {
+                mxm = fmaxf(mxm, __shfl_xor(mxm, 32, 64));       // every lane takes part: rows >= M compute on clamped loads
+                const int sb = mx4_scale_byte(mxm);
+                const float inv = mx_inv_scale(sb);
+                const int nb = n0 + 64 * wc + 32 * i;           // N % 128 == 0: every column of the tile exists
+                uint32_t h[4];                                  // group g: the codes of columns nb + 8 g + 4 fh .. + 3, 16 bits
+#pragma unroll
+                for (int g = 0; g < 4; ++g) h[g] = mx4_quant4f(mxv[4 * g], mxv[4 * g + 1], mxv[4 * g + 2], mxv[4 * g + 3], inv);
+                const uint32_t w01 = h[0] | h[1] << 16, w23 = h[2] | h[3] << 16;
+                const uint32_t got = (uint32_t)__shfl_xor((int)(fh ? w01 : w23), 32, 64);   // the partner's halves of MY two groups
+                const uint32_t lo = fh ? got : w01, hi = fh ? w23 : got;                    // columns + 0..3 | columns + 4..7
+                if (m < G.M) {
+                    uint32_t* q = (uint32_t*)(G.Q + (int64_t)m * G.ldq + (nb >> 1) + 8 * fh);
+                    q[0] = (lo & 0xffffu) | hi << 16;
+                    q[1] = lo >> 16 | (hi & 0xffff0000u);
+                    if (fh == 0) G.QS[(int64_t)m * G.ldqs + (nb >> 5)] = (uint8_t)sb;
+                }
+            } else if constexpr (MXOUT == MXO_E4M3) {
                 mxm = fmaxf(mxm, __shfl_xor(mxm, 32, 64));       // every lane takes part: rows >= M compute on clamped loads
                 const int sb = mx_scale_byte(mxm);
                 const float inv = mx_inv_scale(sb);

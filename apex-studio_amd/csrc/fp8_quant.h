@@ -94,6 +94,16 @@ APEXMI_DEVICE uint32_t mx4_quant8(const u32x4 v, float inv) {
     return r;
 }
 
+// 4 / 8 f32 values (bf16-exact) -> their codes, packed as mx4_quant8 packs them: the norm that quantises its own output
+// (apexmi_ln_modulate_quant_mxfp4) and the MX output of apexmi_gemm_mxfp4_mx hold the rounded values unpacked
+APEXMI_DEVICE uint32_t mx4_quant4f(float a, float b, float c, float d, float inv) {
+    return mx4_code(a, inv) | mx4_code(b, inv) << 4 | mx4_code(c, inv) << 8 | mx4_code(d, inv) << 12;
+}
+
+APEXMI_DEVICE uint32_t mx4_quant8f(const float* f, float inv) {
+    return mx4_quant4f(f[0], f[1], f[2], f[3], inv) | mx4_quant4f(f[4], f[5], f[6], f[7], inv) << 16;
+}
+
 // ---- MXFP6 block quantiser (apexmi_quant_blocks_mxfp6, gemm_mxfp6.hip) -----------------------------------------------------------
 // The same block of 32 bf16 values and the same e8m0 scale byte, for OCP e2m3 codes: sign << 5 | exp << 3 | man, bias 1; exp = 0 is
 // man / 8, otherwise (1 + man / 8) 2^(exp - 1): 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5.  e = clamp(E - 2 + (man >

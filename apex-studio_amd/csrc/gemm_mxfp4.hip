@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(const bf16_t* _
 constexpr int X4_SCB = FBM * 8;                              // scale bytes of one operand tile: 128 rows x 8 blocks
 constexpr int X4_LDS = 4 * FOPB + 4 * X4_SCB;                // codes [buf][operand] + scales [buf][operand]
 
-struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda / ldw in bytes; sa, sw, abs, Q, QS unused
+struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda / ldw in bytes; sa, sw, abs unused; Q / QS: the MX output
     const uint8_t* SA;                 // activation block scales [M, K / 32]
     const uint8_t* SW;                 // weight block scales [N, K / 32]
     int64_t ldsa, ldsw;
@@ -84,7 +84,10 @@ APEXMI_DEVICE Mxfp4GroupProblem mxfp4_problem(const Mxfp4Group& G, int& t) {
 // ONE kernel for both forms, chosen by the argument type (Mxfp4Gemm, Mxfp4Group), as gemm_fp8_kernel: build.py's no-spill check
 // matches "gemm_mxfp4_kernel" and so covers every instantiation.
 // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
-template <int EPI, class Args>
+// MXO (apexmi_gemm_mxfp4_mx, apexmi_gemm_mxfp4_grouped(_qkv)_mx): the output leaves as MXFP4 codes and scale bytes (Q / QS, the
+// MXO_E2M1 epilogue of fp8_gemm_tile.h; bias and gelu) — the single form always, a problem of the grouped form where its Q is set
+// (block-uniform).  Instantiations of their own: the launches without MX output run the kernels they ran before MXO existed.
+template <int EPI, class Args, bool MXO = false>
 __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Args A) {
     constexpr bool GROUPED = std::is_same_v<Args, Mxfp4Group>;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -158,9 +161,14 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Args A) {
         // block-uniform: the epilogue by the table entry.  The fused q/k/v preparation lays its bf16 tile over the first 32 KB of
         // the code buffers (buffer 0, both operands), which nothing reads after the K-loop's last barrier.
         if (G.qkv) fp8_qkv_epilogue<false>(acc, G, A.qs, m0, n0, tid, lds);
+        else if (MXO && G.Q != nullptr && G.epi == APEXMI_EPI_BIAS_GELU)
+            fp8_epilogue<APEXMI_EPI_BIAS_GELU, false, false, MXO_E2M1>(acc, G, m0, n0, wr, wc, fr, fh);
+        else if (MXO && G.Q != nullptr) fp8_epilogue<APEXMI_EPI_BIAS, false, false, MXO_E2M1>(acc, G, m0, n0, wr, wc, fr, fh);
         else if (G.epi == APEXMI_EPI_BIAS) fp8_epilogue<APEXMI_EPI_BIAS, false>(acc, G, m0, n0, wr, wc, fr, fh);
         else if (G.epi == APEXMI_EPI_BIAS_GELU) fp8_epilogue<APEXMI_EPI_BIAS_GELU, false>(acc, G, m0, n0, wr, wc, fr, fh);
         else fp8_epilogue<APEXMI_EPI_BIAS_GATE_RES, false>(acc, G, m0, n0, wr, wc, fr, fh);
+    } else if constexpr (MXO) {
+        fp8_epilogue<EPI, false, false, MXO_E2M1>(acc, G, m0, n0, wr, wc, fr, fh);
     } else {
         fp8_epilogue<EPI, false>(acc, G, m0, n0, wr, wc, fr, fh);
     }
@@ -190,12 +198,31 @@ extern "C" int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int 
 // ONE problem of either entry point: the null check, the format-independent checks (fp8_check_tile_problem with the e2m1 rules),
 // then the scale-row rule; fills the Fp8Problem part of `P` and its SA / SW / ldsa / ldsw.  `i` = the problem's index in a grouped
 // launch, which the messages name, or -1; tile0 = the tiles of the problems before it.
+// mx = the MX output of the _mx entry points (both members null = the bf16 output C): C may then be null and is not written.
+struct Mxfp4MxOut {
+    void* Q;              // codes [M, N / 2]
+    int64_t ldq;
+    void* QS;             // scale bytes [M, N / 32]
+    int64_t ldqs;
+};
 template <class Problem>
 static int mxfp4_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const void* sa, int64_t ldsa,
                                const void* qw, int64_t ldw, const void* sw, int64_t ldsw, const void* bias, void* C, int64_t ldc, int M,
-                               int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P) {
+                               int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P,
+                               const Mxfp4MxOut* mx = nullptr) {
     const Fp8Where at(i);
-    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand%s", who, at.paren);
+    const bool mxo = mx != nullptr && (mx->Q != nullptr || mx->QS != nullptr);
+    APEXMI_REQUIRE(qa && sa && qw && sw && (C || mxo), "%s: null operand%s", who, at.paren);
+    if (mxo) {
+        APEXMI_REQUIRE(mx->Q && mx->QS, "%s: the MX output%s needs codes and block scales", who, at.of);
+        APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU,
+                       "%s: the MX output%s exists for the bias (0) and tanh GELU (1) epilogues, not epilogue %d", who, at.of, epilogue);
+        APEXMI_REQUIRE(N % 128 == 0, "%s: N=%d%s must be a multiple of 128 for the MX output", who, N, at.of);
+        APEXMI_REQUIRE(mx->ldq >= N / 2 && mx->ldq % 4 == 0 && ((uintptr_t)mx->Q % 4) == 0 && mx->ldqs >= N / 32 && mx->ldqs % 4 == 0,
+                       "%s: the MX output%s needs 4-byte aligned code rows at least N / 2 bytes wide and scale rows at least N / 32 "
+                       "wide, a multiple of 4 (ldmc %lld, ldms %lld)", who, at.of, (long long)mx->ldq, (long long)mx->ldqs);
+        if (C == nullptr) ldc = N;      // not written, not read
+    }
     char ld_note[64];
     snprintf(ld_note, sizeof(ld_note), ", code rows at least K / 2 = %d bytes", K / 2);
     const Fp8Format e2m1{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ld_note, "bytes", true, "output and bias 8-byte"};
@@ -204,6 +231,7 @@ static int mxfp4_check_problem(const char* who, int i, int64_t tile0, const void
                    "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, at.of,
                    K / 32, (long long)ldsa, (long long)ldsw);
     P->SA = (const uint8_t*)sa, P->SW = (const uint8_t*)sw, P->ldsa = ldsa, P->ldsw = ldsw;
+    if (mxo) P->Q = (uint8_t*)mx->Q, P->QS = (uint8_t*)mx->QS, P->ldq = mx->ldq, P->ldqs = mx->ldqs;
     return 0;
 }
 
@@ -222,40 +250,84 @@ extern "C" int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, in
     return apexmi_check_launch(who);
 }
 
-// both grouped entry points: every check of every problem before the launch; qkv = the fused q/k/v operands of
-// apexmi_gemm_mxfp4_grouped_qkv, or null
+// apexmi_gemm_mxfp4 whose output leaves as MXFP4 (include/apexmi.h): the bf16 launch followed by apexmi_quant_blocks_mxfp4 on its
+// output, bit for bit, as one launch that writes no C.  Null mx_codes and mx_scales = apexmi_gemm_mxfp4 itself.
+extern "C" int apexmi_gemm_mxfp4_mx(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
+                                    int64_t ldsw, const void* bias, void* C, int64_t ldc, void* mx_codes, int64_t ldmc, void* mx_scales,
+                                    int64_t ldms, int M, int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr,
+                                    apexmi_stream_t stream_) {
+    if (!mx_codes && !mx_scales)
+        return apexmi_gemm_mxfp4(qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, stream_);
+    hipStream_t stream = (hipStream_t)stream_;
+    const char* who = "gemm_mxfp4_mx";
+    const Mxfp4MxOut mx{mx_codes, ldmc, mx_scales, ldms};
+    Mxfp4Gemm G{};
+    if (mxfp4_check_problem(who, -1, 0, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G, &mx)) return 1;
+    G.clk = apexmi_clk_ptr();
+    ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * (((double)M + N) * K + (double)M * N));
+    // the check left bias or gelu: the gate_res case of the switch names the bias kernel and is never taken
+    launch_by_epilogue(epilogue, [](auto epi) {
+        constexpr int EPI = decltype(epi)::value == APEXMI_EPI_BIAS_GELU ? APEXMI_EPI_BIAS_GELU : APEXMI_EPI_BIAS;
+        return gemm_mxfp4_kernel<EPI, Mxfp4Gemm, true>;
+    }, G, (unsigned)(G.tiles_m * G.tiles_n), X4_LDS, stream);
+    return apexmi_check_launch(who);
+}
+
+// the MX outputs of a grouped launch as the _mx entry points take them: entry i both null = problem i writes its bf16 C
+struct Mxfp4MxArrays {
+    void* const* codes;
+    const int64_t* ldmc;
+    void* const* scales;
+    const int64_t* ldms;
+};
+
+// every grouped entry point: every check of every problem before the launch; qkv = the fused q/k/v operands of
+// apexmi_gemm_mxfp4_grouped_qkv(_mx), or null; mxa = the MX outputs of the _mx entry points, or null
 static int gemm_mxfp4_grouped_run(const char* who, int count, const void* const* qa, const int64_t* lda, const void* const* sa,
                                   const int64_t* ldsa, const void* const* qw, const int64_t* ldw, const void* const* sw,
                                   const int64_t* ldsw, const void* const* bias, void* const* C, const int64_t* ldc, const int* M,
                                   const int* N, int K, const int* epilogue, const float* const* gate, const void* const* R,
-                                  const int64_t* ldr, const Fp8QkvArgs* qkv, hipStream_t stream) {
+                                  const int64_t* ldr, const Fp8QkvArgs* qkv, hipStream_t stream, const Mxfp4MxArrays* mxa = nullptr) {
     APEXMI_REQUIRE(count >= 1 && count <= FP8_MAX_GROUPS, "%s: count=%d not in [1,%d]", who, count, FP8_MAX_GROUPS);
     APEXMI_REQUIRE(qa && lda && sa && ldsa && qw && ldw && sw && ldsw && C && ldc && M && N && epilogue, "%s: null argument array", who);
     APEXMI_REQUIRE(K >= 256 && K % 256 == 0, "%s: K=%d must be a multiple of 256 (a K-tile is 128 bytes of e2m1 codes; the problems share K)",
                    who, K);
+    APEXMI_REQUIRE(!mxa || (mxa->codes && mxa->ldmc && mxa->scales && mxa->ldms), "%s: null argument array", who);
     Mxfp4Group G{};
     G.count = count;
     G.clk = apexmi_clk_ptr();
     if (qkv != nullptr && fp8_check_qkv_shared(who, *qkv, &G.qs)) return 1;
     double flops = 0, bytes = 0;
     int64_t tiles = 0;
+    bool any_mx = false;
     for (int i = 0; i < count; ++i) {
         const bool fused = qkv != nullptr && qkv->is_qkv[i] != 0;
+        const Mxfp4MxOut mx = mxa ? Mxfp4MxOut{mxa->codes[i], mxa->ldmc[i], mxa->scales[i], mxa->ldms[i]} : Mxfp4MxOut{};
+        const bool mxo = mx.Q != nullptr || mx.QS != nullptr;
+        APEXMI_REQUIRE(!(fused && mxo), "%s: a fused q/k/v problem (problem %d) writes q / k / V^T and takes no MX output", who, i);
+        any_mx |= mxo;
         Mxfp4GroupProblem& P = G.p[i];
         // a fused problem writes no C: its q_out stands in, N wide
         if (mxfp4_check_problem(who, i, tiles, qa[i], lda[i], sa[i], ldsa[i], qw[i], ldw[i], sw[i], ldsw[i], bias ? bias[i] : nullptr,
                                 fused ? qkv->q_out : C[i], fused ? N[i] : ldc[i], M[i], N[i], K, epilogue[i], gate ? gate[i] : nullptr,
-                                R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P))
+                                R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P, &mx))
             return 1;
         P.epi = epilogue[i];
         P.tile0 = (int)tiles;
         if (fused && fp8_check_qkv_problem(who, *qkv, i, &P)) return 1;
         tiles += (int64_t)P.tiles_m * P.tiles_n;
         flops += 2.0 * M[i] * N[i] * (double)K;
-        bytes += (0.5 + 1.0 / 32) * ((double)M[i] + N[i]) * K + 2.0 * (double)M[i] * N[i];
+        bytes += (0.5 + 1.0 / 32) * ((double)M[i] + N[i]) * K + (mxo ? 0.5 + 1.0 / 32 : 2.0) * (double)M[i] * N[i];
     }
     G.total = (int)tiles;
     ApexmiProfScope prof(0, stream, flops, bytes);
+    if (any_mx) {       // a launch without an MX output runs the kernel it always ran
+        auto kernel = gemm_mxfp4_kernel<0, Mxfp4Group, true>;
+        static uint64_t attr_set = 0;
+        APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), X4_LDS, stream, G);
+        return apexmi_check_launch(who);
+    }
     auto kernel = gemm_mxfp4_kernel<0, Mxfp4Group>;
     static uint64_t attr_set = 0;       // 68 KB of dynamic LDS is above the default limit
     APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
@@ -286,4 +358,32 @@ extern "C" int apexmi_gemm_mxfp4_grouped_qkv(int count, const void* const* qa, c
     const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
     return gemm_mxfp4_grouped_run("gemm_mxfp4_grouped_qkv", count, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue,
                                   gate, R, ldr, &qkv, (hipStream_t)stream_);
+}
+
+// apexmi_gemm_mxfp4_grouped where problem i with mx_codes[i] set leaves as MXFP4 (include/apexmi.h): that problem is
+// apexmi_gemm_mxfp4_mx, the others apexmi_gemm_mxfp4, bit for bit, in one launch
+extern "C" int apexmi_gemm_mxfp4_grouped_mx(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                                            const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                                            const void* const* bias, void* const* C, const int64_t* ldc, void* const* mx_codes,
+                                            const int64_t* ldmc, void* const* mx_scales, const int64_t* ldms, const int* M, const int* N,
+                                            int K, const int* epilogue, const float* const* gate, const void* const* R,
+                                            const int64_t* ldr, apexmi_stream_t stream_) {
+    const Mxfp4MxArrays mxa{mx_codes, ldmc, mx_scales, ldms};
+    return gemm_mxfp4_grouped_run("gemm_mxfp4_grouped_mx", count, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue,
+                                  gate, R, ldr, nullptr, (hipStream_t)stream_, &mxa);
+}
+
+// apexmi_gemm_mxfp4_grouped_qkv with the MX outputs of apexmi_gemm_mxfp4_grouped_mx on the problems that are NOT fused q/k/v
+extern "C" int apexmi_gemm_mxfp4_grouped_qkv_mx(int count, const void* const* qa, const int64_t* lda, const void* const* sa,
+                                                const int64_t* ldsa, const void* const* qw, const int64_t* ldw, const void* const* sw,
+                                                const int64_t* ldsw, const void* const* bias, void* const* C, const int64_t* ldc,
+                                                void* const* mx_codes, const int64_t* ldmc, void* const* mx_scales, const int64_t* ldms,
+                                                const int* M, const int* N, int K, const int* epilogue, const float* const* gate,
+                                                const void* const* R, const int64_t* ldr, const int* is_qkv, const void* const* norm_q,
+                                                const void* const* norm_k, const int* row0, int H, float eps, const float* rope,
+                                                void* q_out, void* k_out, void* vt_out, int S_out, int Skp, apexmi_stream_t stream_) {
+    const Fp8QkvArgs qkv{is_qkv, norm_q, norm_k, row0, H, eps, rope, q_out, k_out, vt_out, S_out, Skp};
+    const Mxfp4MxArrays mxa{mx_codes, ldmc, mx_scales, ldms};
+    return gemm_mxfp4_grouped_run("gemm_mxfp4_grouped_qkv_mx", count, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue,
+                                  gate, R, ldr, &qkv, (hipStream_t)stream_, &mxa);
 }

@@ -1,5 +1,6 @@
-// Body of ln_modulate_wave_kernel (LN_QUANT 0) and of ln_modulate_wave_quant_kernel (LN_QUANT 1), elementwise.hip: as
-// ln_modulate_row.inc, for the wave-per-row family.  Expects the kernel's parameters and T, NCH, NR, TO in scope.
+// Body of ln_modulate_wave_kernel (LN_QUANT 0) and of ln_modulate_wave_quant_kernel (LN_QUANT 1 and 2), elementwise.hip: as
+// ln_modulate_row.inc, for the wave-per-row family.  Expects the kernel's parameters and T, NCH, NR, TO in scope.  Every lane of a
+// wave that reaches a row's store step is live (the row test is wave-uniform), so the block shuffles of LN_QUANT 2 are convergent.
     // NR rows per wave (`ln.wave` = NR): all NR rows' loads are issued before the first reduction, so a wave has NR x NCH
     // 16-byte loads in flight and the second row's statistics / stores overlap the first row's store drain.  Per row the
     // arithmetic is the same for every NR (bit-identical outputs).
@@ -36,7 +37,11 @@
                 else sq += d * d;
             }
         const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-#if LN_QUANT
+#if LN_QUANT == 2
+        TO* op = out == nullptr ? nullptr : out + (int64_t)row * ldo;
+        uint8_t* qp = codes + (int64_t)row * ldq;
+        uint8_t* sp = scales + (int64_t)row * lds;
+#elif LN_QUANT
         TO* op = out == nullptr ? nullptr : out + (int64_t)row * ldo;
         float amax = 0.0f;
 #else
@@ -78,13 +83,17 @@
                     y[j + 4] += s1[j];
                 }
             }
-#if LN_QUANT
+#if LN_QUANT == 2
+            float bmax = 0.0f;
+            ln_quant_keep8(op == nullptr ? nullptr : op + c * 8, y, v[r][it], bmax);
+            mx4_store8(qp + c * 4, sp + (c >> 2), (c & 3) == 0, v[r][it], mx4_block_scale_byte(bmax));
+#elif LN_QUANT
             ln_quant_keep8(op == nullptr ? nullptr : op + c * 8, y, v[r][it], amax);
 #else
             store8<TO>(op + c * 8, y);
 #endif
         }
-#if LN_QUANT
+#if LN_QUANT == 1
         const float qs = quant_row_scale(wave_max(amax));
         if (lane == 0) scales[row] = qs;
         uint8_t* qp = codes + (int64_t)row * ldq;

@@ -80,7 +80,7 @@ class FluxT2IEngine(EngineLoraMixin):
                  decode_fn: Optional[Callable[[torch.Tensor], object]] = None, vae_scale_factor: int = 8,
                  text_encoder=None, text_encoder_2=None, residual_dtype: Optional[torch.dtype] = None,
                  fp8_compute: bool = False, fp8_fused_quant: bool = False, fp8_mx_ffn: bool = False, fp8_lora: bool = False,
-                 fp4_compute: bool = False, fp4_linears=None):
+                 fp4_compute: bool = False, fp4_linears=None, fp4_fused_quant: bool = False, fp4_mx_ffn: bool = False):
         from .prompt import TextEncoder
         # fp4_compute: the block launches of a bf16 transformer multiply as MXFP4 (`set_fp4_compute`, DESIGN.md §3.6: an opt-in
         # approximation on MXFP4 copies beside the bf16 weights; not for a keep_fp8 model, so never together with fp8_compute);
@@ -92,6 +92,14 @@ class FluxT2IEngine(EngineLoraMixin):
         if self.fp4_compute and fp8_compute:
             raise ValueError("fp4_compute and fp8_compute cannot be combined: fp8 compute needs resident fp8 records (a keep_fp8 load), "
                              "fp4 compute the bf16 weights")
+        # fp4_fused_quant / fp4_mx_ffn: the norms in front of the fp4 QKV, FF-up and single-block launches write the MXFP4 codes
+        # themselves / the FF hidden state and the single block's MLP columns stay MXFP4 between their launches
+        # (`set_fp4_compute(fused_quant=, mx_ffn=)`: fewer launches and bytes, the same numbers); both need fp4_compute
+        self.fp4_fused_quant, self.fp4_mx_ffn = bool(fp4_fused_quant), bool(fp4_mx_ffn)
+        if self.fp4_fused_quant and not self.fp4_compute:
+            raise ValueError("fp4_fused_quant=True needs fp4_compute=True: the fused norm quantises for the MXFP4 GEMM")
+        if self.fp4_mx_ffn and not self.fp4_compute:
+            raise ValueError("fp4_mx_ffn=True needs fp4_compute=True: the MXFP4 hidden state belongs to the MXFP4 GEMMs")
         self.transformer = transformer
         # float32: the transformer keeps its residual stream in float (`set_residual_dtype`); None = bf16
         self.residual_dtype = residual_dtype
@@ -117,7 +125,8 @@ class FluxT2IEngine(EngineLoraMixin):
             more = {k: True for k, v in (("mx_ffn", self.fp8_mx_ffn), ("lora", self.fp8_lora)) if v}
             transformer.set_fp8_compute(True, fused_quant=self.fp8_fused_quant, **more)
         if self.fp4_compute:
-            transformer.set_fp4_compute(True, linears=self.fp4_linears)
+            more = {k: True for k, v in (("fused_quant", self.fp4_fused_quant), ("mx_ffn", self.fp4_mx_ffn)) if v}
+            transformer.set_fp4_compute(True, linears=self.fp4_linears, **more)
         self.scheduler = scheduler or FlowMatchEulerDiscreteScheduler.flux_dev()
         self.decode_fn = decode_fn
         self.vae_scale_factor = vae_scale_factor

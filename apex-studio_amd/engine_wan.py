@@ -27,7 +27,7 @@ class WanT2VEngine(EngineLoraMixin):
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
                  fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None,
-                 fp6_compute: bool = False, fp6_linears=None):
+                 fp6_compute: bool = False, fp6_linears=None, fp4_fused_quant: bool = False, fp4_mx_ffn: bool = False):
         from .prompt import TextEncoder
         self.text_encoder = text_encoder if text_encoder is None or isinstance(text_encoder, TextEncoder) \
             else TextEncoder(text_encoder)                      # UMT5-XXL (manifest wan-2.2-a14b-text-to-video yml)
@@ -83,9 +83,18 @@ class WanT2VEngine(EngineLoraMixin):
         self.fp4_linears = None if fp4_linears is None else tuple(fp4_linears)
         if self.fp4_linears is not None and not self.fp4_compute:
             raise ValueError("fp4_linears needs fp4_compute=True: it names the Linears of the MXFP4 compute mode")
+        # fp4_fused_quant / fp4_mx_ffn: the norms in front of the fp4 q|k|v, cross-attention query and FFN-up Linears write the MXFP4
+        # codes themselves / the FFN hidden state stays MXFP4 between the two FFN Linears (`set_fp4_compute(fused_quant=, mx_ffn=)`:
+        # fewer launches and bytes, the same numbers); both need fp4_compute
+        self.fp4_fused_quant, self.fp4_mx_ffn = bool(fp4_fused_quant), bool(fp4_mx_ffn)
+        if self.fp4_fused_quant and not self.fp4_compute:
+            raise ValueError("fp4_fused_quant=True needs fp4_compute=True: the fused norm quantises for the MXFP4 GEMM")
+        if self.fp4_mx_ffn and not self.fp4_compute:
+            raise ValueError("fp4_mx_ffn=True needs fp4_compute=True: the MXFP4 hidden state belongs to the MXFP4 GEMMs")
         if self.fp4_compute:
+            more = {k: True for k, v in (("fused_quant", self.fp4_fused_quant), ("mx_ffn", self.fp4_mx_ffn)) if v}
             for tr in {id(t): t for t in (self.high_noise_transformer, self.low_noise_transformer)}.values():
-                tr.set_fp4_compute(True, linears=self.fp4_linears)
+                tr.set_fp4_compute(True, linears=self.fp4_linears, **more)
         # the same with MXFP6 (`set_fp6_compute`: the error class of fp8 on the fp4 matrix rate); both may be on with disjoint
         # `*_linears`, e.g. fp6 for the attention projections and fp4 for the FFN pair — the model refuses a name selected by both
         self.fp6_compute = bool(fp6_compute)
@@ -288,13 +297,13 @@ class WanI2VEngine(WanT2VEngine):
                  residual_dtype: Optional[torch.dtype] = None, attention_window=None, fp8_compute: bool = False,
                  attention_band: Optional[int] = None, fp8_lora: bool = False, fp8_fused_quant: bool = False,
                  fp8_mx_ffn: bool = False, fp4_compute: bool = False, fp4_linears=None,
-                 fp6_compute: bool = False, fp6_linears=None):
+                 fp6_compute: bool = False, fp6_linears=None, fp4_fused_quant: bool = False, fp4_mx_ffn: bool = False):
         super().__init__(high_noise_transformer, low_noise_transformer, vae, scheduler, boundary_ratio,
                          vae_scale_factor_temporal, vae_scale_factor_spatial, text_encoder, residual_dtype=residual_dtype,
                          attention_window=attention_window, fp8_compute=fp8_compute,
                          attention_band=attention_band, fp8_lora=fp8_lora, fp8_fused_quant=fp8_fused_quant,
                          fp8_mx_ffn=fp8_mx_ffn, fp4_compute=fp4_compute, fp4_linears=fp4_linears,
-                         fp6_compute=fp6_compute, fp6_linears=fp6_linears)
+                         fp6_compute=fp6_compute, fp6_linears=fp6_linears, fp4_fused_quant=fp4_fused_quant, fp4_mx_ffn=fp4_mx_ffn)
         self.image_encoder = image_encoder
 
     @property

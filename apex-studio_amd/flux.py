@@ -415,7 +415,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
     # ---- opt-in MXFP4 compute on a bf16 model; the switch itself is module_base.Fp4ComputeMixin ----
     _FP4_LINEARS = ("qkv", "attn_out", "ffn_up", "ffn_down", "single_in", "single_out")
 
-    def set_fp4_compute(self, on: bool, linears=None):
+    def set_fp4_compute(self, on: bool, linears=None, fused_quant: bool = False, mx_ffn: bool = False):
         """Opt-in approximation: the selected block launches of a bf16 model quantise their activations per block of
         32 to MXFP4 — ONE `ops.quant_blocks_mxfp4` over the joint buffer both streams are row slices of — and multiply e2m1 x e2m1
         in one grouped launch (`ops.gemm_mxfp4_grouped`; `ops.gemm_mxfp4_grouped_qkv` with the fused q/k/v epilogue when `fuse_qkv`
@@ -434,8 +434,20 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
 
         Refused: a resident (`keep_fp8`) model — so the mode never meets the `fp8_*` switches —, f32 activation storage and the
         f32 residual stream (`set_storage_dtype` / `set_residual_dtype` refuse float32 while the mode is on), an unknown name, and
-        `linears` together with `on=False`."""
-        return self._fp4_switch(on, linears)
+        `linears` together with `on=False`.
+
+        `fused_quant=True` (needs `on=True`): the norms in front of the QKV pair, the FF-up pair and the single block's QKV +
+        MLP-up launch write the MXFP4 codes and scale bytes of the joint buffer themselves (`ops.ln_modulate_quant_mxfp4`) where
+        those classes route to fp4, so their `quant_blocks_mxfp4` launch disappears and the bf16 normalised rows are never stored;
+        the streams stay row slices of one codes buffer.  `mx_ffn=True` (needs `on=True`, composes with `fused_quant`): where
+        `ops.mxfp4_grouped_mx_route` holds, the FF-up pair of a double block writes its GELU output as MXFP4 into the bytes of the
+        hidden buffer (`ops.gemm_mxfp4_grouped(out_mx_list=)`) and the FF-down pair reads it; in a single block (dim % 128 == 0,
+        "single_in" and "single_out" both routed) the MLP-up problem writes its codes into columns [dim, dim + mlp) of a codes /
+        scales buffer for the concatenated rows, ONE `quant_blocks_mxfp4` covers the attention columns only, and `proj_out` reads
+        the joint codes.  Both change launches and traffic only: the forward is bit-identical to the mode without them.  A class
+        that `ops.mxfp4_grouped_route` refuses, the APEX_FLUX_OVERLAP path and the QKV pair with an active IP adapter keep their
+        launches.  The defaults (False) leave every launch as it is."""
+        return self._fp4_switch(on, linears, fused_quant, mx_ffn)
 
     def _fp4_blocks(self):
         return list(self.transformer_blocks) + list(self.single_transformer_blocks)
@@ -448,17 +460,23 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
         return {"qkv": (blk._wqkv, blk._wqkv_c), "attn_out": (a.to_out[0].weight, a.to_add_out.weight),
                 "ffn_up": (ff[0].proj.weight, ffc[0].proj.weight), "ffn_down": (ff[2].weight, ffc[2].weight)}
 
-    def _rows_fp4(self, src):
-        """(codes, scale bytes) of the rows of the joint buffer `src` by ONE quantise launch into the per-stream fp4 scratch; the
-        streams of a grouped launch are row slices of both."""
+    def _rows_fp4(self, src, quantised=None):
+        """(codes, scale bytes) of the rows of the joint buffer `src`: the fused norm's (`quantised`), or ONE quantise launch into
+        the per-stream fp4 scratch; the streams of a grouped launch are row slices of both."""
+        if quantised is not None:
+            return quantised
         qa, sa = ops._act_scratch_mxfp4(src.device, src.shape[0], src.shape[1])
         return ops.quant_blocks_mxfp4(src, out=qa, scale_out=sa)
 
-    def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, **kw):
+    def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, fp4=False, **kw):
         """ln_modulate(X, *mod, out=XN, **kw) in front of a grouped launch (bf16 outputs) over the row ranges `rows` of XN and the
         weights `w_list`, which is the ONLY reader of XN.  With `set_fp8_compute(fused_quant=True)`, where that launch takes its
         fp8 route and the fused norm accepts the rows, the norm quantises in its own launch and does not store XN: returns
-        (codes, scales), else None.  An empty `w_list` = the caller already knows that the launch does not route."""
+        (codes, scales), else None.  An empty `w_list` = the caller already knows that the launch does not route.  `fp4`: the
+        launch is an fp4 one (the caller has asked `ops.mxfp4_grouped_route`); with `set_fp4_compute(fused_quant=True)` the norm
+        then writes the MXFP4 pair of the joint buffer and returns it."""
+        if fp4 and self._fp4_fused_quant and ops.fp8_norm_quant_rows(X, XN):
+            return ops.ln_modulate_quant_mxfp4(X, *mod, **kw)
         if self._fp8_fused_quant and w_list:
             ws = [w if ops._fp8_of(w) is None else ops._fp8_of(w) for w in w_list]
             probe = XN.new_empty((0,), dtype=torch.bfloat16)     # the predicates read the dtype of `out` only
@@ -497,16 +515,19 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
         return ops.quant_rows_fp8(src, out=qa, scale_out=sa)
 
     def _grouped(self, src, rows, w_list, bias_list, out_list, epilogue, gate_list=None, residual_list=None, quantised=None,
-                 fp4=False):
+                 fp4=False, out_mx_list=None):
         """One grouped launch whose problems read the row ranges `rows` (slices) of ONE activation buffer `src`: today's
         `ops.gemm_grouped`, or — in fp8-compute mode, when `ops.fp8_grouped_route` holds for every problem — one quantise launch
         over `src` (unless `quantised` brings the codes) and `ops.gemm_fp8_grouped`.  `fp4`: the caller has asked
         `ops.mxfp4_grouped_route` for this launch class (set_fp4_compute): one `quant_blocks_mxfp4` over `src` and
-        `ops.gemm_mxfp4_grouped` on the weights' MXFP4 records."""
+        `ops.gemm_mxfp4_grouped` on the weights' MXFP4 records (`quantised`: the fused norm's MXFP4 pair; `out_mx_list`: see
+        `ops.gemm_mxfp4_grouped`, fp4 only)."""
         if fp4:
-            qa, sa = self._rows_fp4(src)
+            qa, sa = self._rows_fp4(src, quantised)
+            mx = {} if out_mx_list is None else {"out_mx_list": out_mx_list}
             return ops.gemm_mxfp4_grouped([qa[r] for r in rows], [sa[r] for r in rows], [w._fp4 for w in w_list], bias_list, out_list,
-                                          epilogue=epilogue, gate_list=gate_list, residual_list=residual_list)
+                                          epilogue=epilogue, gate_list=gate_list, residual_list=residual_list, **mx)
+        assert out_mx_list is None
         w_list = [w if ops._fp8_of(w) is None else ops._fp8_of(w) for w in w_list]
         a_list = [src[r] for r in rows]
         if self._fp8_compute and ops.fp8_grouped_route(a_list, w_list, out_list, epilogue):
@@ -731,6 +752,23 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
         if self._fp4_linears is not None and not overlap and len(self.single_transformer_blocks) > 0:
             s0 = self.single_transformer_blocks[0]
             f4_sin = ops.mxfp4_grouped_route([XN, XN], [s0._wqkv, s0.proj_mlp.weight], [QKV, CAT[:, dim:]], ["bias", "gelu"])
+        # set_fp4_compute(mx_ffn=True): the FF hidden state of the double blocks as MXFP4 codes + scale bytes in the bytes of FFH, and
+        # the single block's MLP columns as codes in a codes / scales buffer for CAT (ws.CATQ / ws.CATS) that proj_out reads
+        mx4_d = mx4_s = False
+        if self._fp4_mx_ffn and f4_up and f4_down and FFH.stride(0) % 8 == 0:
+            b0 = self.transformer_blocks[0]
+            mx4_d = ops.mxfp4_grouped_mx_route([XNi, XNt], [b0.ff.net[0].proj.weight, b0.ff_context.net[0].proj.weight],
+                                               [b0.ff.net[2].weight, b0.ff_context.net[2].weight], "gelu", "gate_res", [Xi, Xt])
+        if mx4_d:
+            raw4 = FFH.view(torch.uint8)
+            hq4, hs4 = raw4[:, :FFH.shape[1] // 2], raw4[:, FFH.shape[1] // 2:FFH.shape[1] // 2 + FFH.shape[1] // 32]
+        if self._fp4_mx_ffn and f4_sin and dim % 128 == 0 and (CAT.shape[1] - dim) % 128 == 0:
+            mx4_s = ops.mxfp4_route(CAT, self.single_transformer_blocks[0].proj_out.weight, X, "gate_res")
+        if mx4_s:
+            if getattr(ws, "CATQ", None) is None:
+                ws.CATQ = torch.empty(S, (CAT.shape[1] // 2 + 15) // 16 * 16, device=X.device, dtype=torch.uint8)[:, :CAT.shape[1] // 2]
+                ws.CATS = torch.empty(S, (CAT.shape[1] // 32 + 3) // 4 * 4, device=X.device, dtype=torch.uint8)[:, :CAT.shape[1] // 32]
+            cat_mx = [None, (ws.CATQ[:, dim // 2:], ws.CATS[:, dim // 32:])]
         # run-time LoRA on resident records (set_fp8_compute(lora=True)): which blocks carry factors is the adapter's business, so
         # with factors anywhere every launch class is decided PER BLOCK: False = the plain fp8 launch, True = the fp8 launch with
         # the adapter tail (one grouped skinny GEMM in front of it), None = not routed.  Without factors the block-0 decisions
@@ -782,9 +820,9 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
                 (False if fp8_d else None)
             fuse8_d = kind is not None and self.fuse_qkv and ip is None
             qn = self._norm_rows(X, XN, img_txt, [blk._wqkv, blk._wqkv_c] if kind is not None else [], "bias", mi(1), mi(0), split=s_txt,
-                                 scale2=mt(1), shift2=mt(0))
+                                 scale2=mt(1), shift2=mt(0), fp4=f4_qkv and ip is None)
             if f4_qkv and self.fuse_qkv and ip is None:
-                qa, sa = self._rows_fp4(XN)
+                qa, sa = self._rows_fp4(XN, qn)
                 ops.gemm_mxfp4_grouped_qkv([qa[s_txt:], qa[:s_txt]], [sa[s_txt:], sa[:s_txt]], [blk._wqkv._fp4, blk._wqkv_c._fp4],
                                            [blk._bqkv, blk._bqkv_c], [None, None], "bias", [1, 1],
                                            [a.norm_q.weight, a.norm_added_q.weight], [a.norm_k.weight, a.norm_added_k.weight],
@@ -816,8 +854,16 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
                           "gate_res", gate_list=[mi(2), mt(2)], residual_list=[Xi, Xt], fp4=f4_out)
             ff, ffc = blk.ff.net, blk.ff_context.net
             qn = self._norm_rows(X, XN, img_txt, [ff[0].proj.weight, ffc[0].proj.weight] if fp8 else [], "gelu", mi(4), mi(3),
-                                 split=s_txt, scale2=mt(4), shift2=mt(3))
-            if mx_d and (not lora_live or mx_route(blk)):
+                                 split=s_txt, scale2=mt(4), shift2=mt(3), fp4=f4_up)
+            if mx4_d:
+                qa, sa = self._rows_fp4(XN, qn)
+                ops.gemm_mxfp4_grouped([qa[r] for r in img_txt], [sa[r] for r in img_txt], [ff[0].proj.weight._fp4, ffc[0].proj.weight._fp4],
+                                       [ff[0].proj.bias, ffc[0].proj.bias], [None, None], "gelu",
+                                       out_mx_list=[(hq4[r], hs4[r]) for r in img_txt])
+                ops.gemm_mxfp4_grouped([hq4[r] for r in img_txt], [hs4[r] for r in img_txt], [ff[2].weight._fp4, ffc[2].weight._fp4],
+                                       [ff[2].bias, ffc[2].bias], [Xi, Xt], "gate_res", gate_list=[mi(5), mt(5)],
+                                       residual_list=[Xi, Xt])
+            elif mx_d and (not lora_live or mx_route(blk)):
                 qa, sa = self._rows_fp8(XN, qn)
                 ops.gemm_fp8_grouped([qa[r] for r in img_txt], [sa[r] for r in img_txt], [rec(ff[0].proj.weight), rec(ffc[0].proj.weight)],
                                      [ff[0].proj.bias, ffc[0].proj.bias], [None, None], "gelu",
@@ -856,7 +902,8 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
             kind = (False if fp8_s else None) if not lora_live else fp8_kind(
                 [XN, XN], [blk._wqkv, rec(blk.proj_mlp.weight)], [QKV, CAT[:, dim:]], ["bias", "gelu"])
             fuse8_s = kind is not None and self.fuse_qkv
-            qn = self._norm_rows(X, XN, both, [blk._wqkv, blk.proj_mlp.weight] if kind is not None else [], ["bias", "gelu"], ms(1), ms(0))
+            qn = self._norm_rows(X, XN, both, [blk._wqkv, blk.proj_mlp.weight] if kind is not None else [], ["bias", "gelu"], ms(1), ms(0),
+                                 fp4=f4_sin)
             if overlap:
                 # experiment (APEX_FLUX_OVERLAP=1): the MLP-up GEMM on the side stream underneath q/k prepare +
                 # attention, whose 1.69-round launch leaves 80 CUs idle in its second round
@@ -870,10 +917,11 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
                     mlp_done.record(self._side)
                 ops.gemm(XN, blk._wqkv, blk._bqkv, out=QKV)
             elif f4_sin and self.fuse_qkv:
-                qa, sa = self._rows_fp4(XN)
+                qa, sa = self._rows_fp4(XN, qn)
                 ops.gemm_mxfp4_grouped_qkv([qa, qa], [sa, sa], [blk._wqkv._fp4, blk.proj_mlp.weight._fp4], [blk._bqkv, blk.proj_mlp.bias],
                                            [None, CAT[:, dim:]], ["bias", "gelu"], [1, 0], [a.norm_q.weight, None],
-                                           [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0])
+                                           [a.norm_k.weight, None], [0, 0], H, 1e-6, rope, Qp[0], Kp[0], VT[0],
+                                           **({"out_mx_list": cat_mx} if mx4_s else {}))
             elif fuse8_s:
                 # with adapters: QKV and MLP-up read the same rows, so their two skinny problems share one launch
                 lt, lb = self._lora_t([XN, XN], [blk._wqkv, rec(blk.proj_mlp.weight)]) if kind else (None, None)
@@ -889,7 +937,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
             else:
                 # QKV and MLP-up read the same XN: one launch, 1512 tiles = 5.9 rounds of the 256 CUs
                 self._grouped(XN, both, [blk._wqkv, blk.proj_mlp.weight], [blk._bqkv, blk.proj_mlp.bias], [QKV, CAT[:, dim:]],
-                              ["bias", "gelu"], quantised=qn, fp4=f4_sin)
+                              ["bias", "gelu"], quantised=qn, fp4=f4_sin, out_mx_list=cat_mx if mx4_s else None)
             if overlap or not (fuse_s or fuse8_s or (f4_sin and self.fuse_qkv)):
                 ops.qkv_prepare(q_in, k_in, v_in, H, Qp[0], Kp[0], VT[0], wq=a.norm_q.weight,
                                 wk=a.norm_k.weight, split=0, eps=1e-6, rope=rope,
@@ -907,6 +955,11 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
                 qa, sa = self._rows_fp8(CAT, None)
                 ops.gemm_fp8(qa, sa, po, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2), residual=X, lora_t=lt[0],
                              lora_B=lb[0])
+            elif mx4_s:
+                # the MLP columns of the codes came from the MLP-up epilogue: quantise the attention columns only
+                ops.quant_blocks_mxfp4(CAT[:, :dim], out=ws.CATQ[:, :dim // 2], scale_out=ws.CATS[:, :dim // 32])
+                ops.gemm(CAT, blk.proj_out.weight, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2), residual=X,
+                         quantised_mxfp4=(ws.CATQ, ws.CATS))
             else:
                 ops.gemm(CAT, blk.proj_out.weight, blk.proj_out.bias, out=X, epilogue="gate_res", gate=ms(2),
                          residual=X)

@@ -191,6 +191,20 @@ SIGNATURES = {
                                                 C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p,
                                                 C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_int, C.c_float,
                                                 vp, vp, vp, vp, C.c_int, C.c_int, vp]),
+    "apexmi_ln_modulate_quant_mxfp4": (C.c_int, [vp, C.c_int64, C.c_int, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, C.c_int, C.c_int, vp,
+                                                 vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp]),
+    "apexmi_gemm_mxfp4_mx": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp,
+                                       C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int64, vp]),
+    "apexmi_gemm_mxfp4_grouped_mx": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp),
+                                               c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p,
+                                               C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(vp),
+                                               C.POINTER(vp), c_i64p, vp]),
+    "apexmi_gemm_mxfp4_grouped_qkv_mx": (C.c_int, [C.c_int, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p,
+                                                   C.POINTER(vp), c_i64p, C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(vp), c_i64p,
+                                                   C.POINTER(vp), c_i64p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                                   C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp), c_i64p, C.POINTER(C.c_int),
+                                                   C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int), C.c_int, C.c_float, vp, vp, vp, vp,
+                                                   C.c_int, C.c_int, vp]),
     "apexmi_quant_blocks_mxfp6": (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int64, vp]),
     "apexmi_gemm_mxfp6": (C.c_int, [vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, C.c_int, C.c_int,
                                     C.c_int, C.c_int, vp, vp, C.c_int64, vp]),

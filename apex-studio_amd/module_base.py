@@ -523,8 +523,19 @@ class Fp4ComputeMixin(_MxComputeSwitch):
     _fp4_live: tuple = ()    # the weights that carry a record
     _fp4_bytes = 0
 
-    def _fp4_switch(self, on: bool, linears=None):
-        return self._mx_switch("fp4", on, linears)
+    # the two launch fusions of the mode (`set_fp4_compute(fused_quant=, mx_ffn=)`): which norms and GEMM epilogues write MXFP4
+    # themselves is the class's business, the flags and their refusals are shared
+    _fp4_fused_quant = False
+    _fp4_mx_ffn = False
+
+    def _fp4_switch(self, on: bool, linears=None, fused_quant: bool = False, mx_ffn: bool = False):
+        if fused_quant and not on:
+            raise ValueError(f"{self._tag}: set_fp4_compute(fused_quant=True) needs on=True: the fused norm quantises for the fp4 GEMM")
+        if mx_ffn and not on:
+            raise ValueError(f"{self._tag}: set_fp4_compute(mx_ffn=True) needs on=True: the MXFP4 hidden state belongs to the fp4 GEMMs")
+        self._mx_switch("fp4", on, linears)
+        self._fp4_fused_quant, self._fp4_mx_ffn = bool(fused_quant), bool(mx_ffn)
+        return self
 
     def set_storage_dtype(self, dtype: torch.dtype):
         self._mx_guard_storage("fp4", dtype)

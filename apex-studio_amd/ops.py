@@ -842,13 +842,32 @@ def _act_scratch_mxfp4(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]
     return q[:M * (K // 2)].view(M, K // 2), s[:M * (K // 32)].view(M, K // 32)
 
 
+def _mxfp4_out_mx(who: str, out_mx, M: int, N: int, epilogue: str):
+    """The `out_mx` pair of one [M, N] problem of `gemm_mxfp4` / `gemm_mxfp4_grouped(_qkv)`: (codes uint8 [M, N / 2], scales uint8
+    [M, N / 32]), bias or gelu, N % 128 == 0.  Returns the pair."""
+    try:
+        mq, ms = out_mx
+    except (TypeError, ValueError):
+        raise _l.ApexMIError(f"{who}: out_mx: expected a (codes, scales) pair") from None
+    if epilogue not in ("bias", "gelu"):
+        raise _l.ApexMIError(f"{who}: out_mx exists for the bias and gelu epilogues, not '{epilogue}'")
+    if N % 128 != 0:
+        raise _l.ApexMIError(f"{who}: out_mx needs N % 128 == 0, got N={N}")
+    _check_mxfp4_pair(who + ".out_mx", mq, ms, M, N)
+    return mq, ms
+
+
 def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+               residual: Optional[torch.Tensor] = None, out_mx=None):
     """out[M, N] (bf16) = epi(sum_k value(codes[m, k]) 2^(scales[m, k / 32] - 127) value(w.q[n, k]) 2^(w.s[n, k / 32] - 127) + bias):
     e2m1 x e2m1 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, one bf16 rounding.  `codes` /
     `scales` as `quant_blocks_mxfp4` returns them; `w` an `Mxfp4Weight`; epilogue bias / gelu / gate_res (`residual` may be `out`).
-    K % 256 == 0, N % 16 == 0."""
+    K % 256 == 0, N % 16 == 0.
+
+    `out_mx=(codes_out uint8 [M, N / 2], scales_out uint8 [M, N / 32])` (bias / gelu, N % 128 == 0; row strides free, multiples of
+    4): the launch quantises its own output in the epilogue and writes those instead of `out` (which is ignored); bit-identical
+    to the bf16 launch followed by `quant_blocks_mxfp4`.  Returns the pair."""
     who = "gemm_mxfp4"
     if not isinstance(w, Mxfp4Weight):
         raise _l.ApexMIError(f"{who}: expected an Mxfp4Weight, got {type(w).__name__}")
@@ -858,6 +877,14 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
         raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(codes).__name__}")
     M, (N, K) = codes.shape[0], w.shape
     _check_mxfp4_pair(who, codes, scales, M, K)
+    if out_mx is not None:
+        mq, ms = _mxfp4_out_mx(who, out_mx, M, N, epilogue)
+        _epilogue_operands(who, M, N, codes.device, bias, None, epilogue, None, None, fused=True, told=True)
+        rc = _l.load().apexmi_gemm_mxfp4_mx(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
+                                            w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), None, 0, mq.data_ptr(),
+                                            mq.stride(0), ms.data_ptr(), ms.stride(0), M, N, K, _EPI[epilogue], None, None, 0, _stream())
+        _l.check(rc, "gemm_mxfp4_mx")
+        return mq, ms
     out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
     rc = _l.load().apexmi_gemm_mxfp4(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
                                      w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
@@ -865,6 +892,79 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
                                      residual.stride(0) if epilogue == "gate_res" else 0, _stream())
     _l.check(rc, who)
     return out
+
+
+def mxfp4_norm_quant_route(x: torch.Tensor, xn: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
+    """Whether the pair `ln_modulate(x, ..., out=xn)` -> `gemm(xn, w, out=out, epilogue=epilogue)` may go out as
+    `ln_modulate_quant_mxfp4` -> `gemm(..., quantised_mxfp4=)`: the norm writes the e2m1 codes and scale bytes itself and the
+    GEMM's own `quant_blocks_mxfp4` launch disappears.  Pure, like `mxfp4_route` (dtypes, shapes and strides only; CPU tensors
+    are fine).  True only when the GEMM takes `mxfp4_route` on `xn` AND the fused norm accepts the pair (`fp8_norm_quant_rows`:
+    `x` bf16 or float32 [M, C] with 16-byte rows, `xn` bf16 of the same shape, C % 128 == 0 and C <= 8192).  The fp4 mode has no
+    adapter tail, so nothing but the GEMM reads `xn`: the caller stores no bf16 row unless something of its own reads it."""
+    return fp8_norm_quant_rows(x, xn) and mxfp4_route(xn, w, out, epilogue)
+
+
+def mxfp4_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_down: str = "gate_res",
+                   out: Optional[torch.Tensor] = None) -> bool:
+    """Whether the pair `h = gemm(a, w_up, epilogue=epilogue_up)` -> `gemm(h, w_down, out=out, epilogue=epilogue_down)` may keep
+    `h` in MXFP4 between the two launches: `gemm_mxfp4(out_mx=)` -> `gemm_mxfp4` on that pair.  Pure, like `mxfp4_route`
+    (dtypes, shapes and strides; CPU tensors are fine).  `a_or_shape`: the bf16 input [M, K] of the up projection, or its shape.
+    True only when BOTH weights carry fp4 records and take `mxfp4_route`, the up epilogue is bias or gelu, N_up % 256 == 0 (the
+    down launch's K-tile rule, which includes the MX output's N % 128 == 0), and `out` (the down projection's output and, for
+    gate_res, its residual) is bf16 or None."""
+    a = a_or_shape if isinstance(a_or_shape, torch.Tensor) else torch.empty(tuple(a_or_shape), dtype=torch.bfloat16, device="meta")
+    f_up = _fp4_of(w_up)
+    if epilogue_up not in ("bias", "gelu") or not mxfp4_route(a, f_up, None, epilogue_up):
+        return False
+    n_up = f_up.shape[0]
+    if n_up % 256 != 0:
+        return False
+    h = torch.empty((a.shape[0], n_up), dtype=torch.bfloat16, device="meta")
+    return mxfp4_route(h, w_down, out, epilogue_down)
+
+
+def ln_modulate_quant_mxfp4(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+                            gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                            rms: bool = False, split: int = 0, scale2: Optional[torch.Tensor] = None,
+                            shift2: Optional[torch.Tensor] = None, codes: Optional[torch.Tensor] = None,
+                            scale_out: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`ln_modulate(x, ...)` into bf16 followed by `quant_blocks_mxfp4` on its output, as ONE launch: -> (codes uint8 [M, C / 2],
+    scales uint8 [M, C / 32]), bit-identical to the two launches.  `x` bf16, or float32 (the f32 residual stream); C % 128 == 0.
+    `out` (optional, bf16 [M, C], row stride free): also receives the normalised rows, bit-identical to `ln_modulate(x, ...,
+    out=out)`; None = the bf16 rows are never stored.  `codes` / `scale_out` (row strides free, code rows 16-byte aligned) default
+    to the per-stream activation scratch of `gemm`'s fp4 route, valid until that stream's next fp4 GEMM or fused norm."""
+    who = "ln_modulate_quant_mxfp4"
+    _req(x, None, who + ".x")
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _l.ApexMIError(f"{who}.x: expected torch.bfloat16 or torch.float32, got {x.dtype}")
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 128 != 0 or x.shape[0] < 1:
+        raise _l.ApexMIError(f"{who}.x: expected [M >= 1, C % 128 == 0] with contiguous rows, got {tuple(x.shape)}")
+    M, Cc = x.shape
+    if codes is None and scale_out is None:
+        codes, scale_out = _act_scratch_mxfp4(x.device, M, Cc)
+    if codes is None:
+        codes = torch.empty((M, (Cc // 2 + 15) // 16 * 16), dtype=torch.uint8, device=x.device)[:, :Cc // 2]
+    if scale_out is None:
+        scale_out = torch.empty((M, Cc // 32), dtype=torch.uint8, device=x.device)
+    _check_mxfp4_pair(who + ".codes", codes, scale_out, M, Cc)
+    if out is not None:
+        _req(out, torch.bfloat16, who + ".out")
+        assert out.shape == (M, Cc) and out.stride(1) == 1
+    for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
+        if t is not None:
+            _req(t, torch.float32, f"{who}.{nm}")
+            assert t.is_contiguous() and t.numel() == Cc
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _req(t, torch.bfloat16, f"{who}.{nm}")
+            assert t.is_contiguous() and t.numel() == Cc
+    rc = _l.load().apexmi_ln_modulate_quant_mxfp4(
+        x.data_ptr(), x.stride(0), _l.F32 if x.dtype == torch.float32 else _l.BF16, _ptr(out), 0 if out is None else out.stride(0),
+        codes.data_ptr(), codes.stride(0), scale_out.data_ptr(), scale_out.stride(0), M, Cc, _ptr(scale), _ptr(shift), _ptr(gamma),
+        _ptr(beta), float(eps), 1 if rms else 0, int(split), _ptr(scale2), _ptr(shift2), _stream())
+    _l.check(rc, who)
+    return codes, scale_out
 
 
 # ---- opt-in MXFP6 compute (DESIGN.md §3.6): e2m3 codes, 32 to 24 bytes, one e8m0 scale byte per 32 consecutive k ---------------------
@@ -1044,6 +1144,22 @@ def mxfp4_grouped_route(a_list, w_list, out_list=None, epilogues="bias") -> bool
     model asks this predicate, as it asks `fp8_grouped_route`."""
     problems = _grouped_problems(a_list, w_list, out_list, epilogues)
     return problems is not None and all(mxfp4_route(a, w, o, e) for a, w, o, e in problems)
+
+
+def mxfp4_grouped_mx_route(a_list, w_up_list, w_down_list, epilogues_up="gelu", epilogues_down="gate_res", out_list=None) -> bool:
+    """Whether the pair of grouped launches h_i = epi_up(a_i w_up_i^T) -> epi_down(h_i w_down_i^T) may keep every h_i in MXFP4
+    between them: `gemm_mxfp4_grouped(out_mx_list=)` -> `gemm_mxfp4_grouped` on those pairs.  Pure, like `mxfp4_grouped_route`.
+    True only when both launches take `mxfp4_grouped_route` and every problem takes `mxfp4_mx_route`."""
+    n = len(a_list)
+    eu = [epilogues_up] * n if isinstance(epilogues_up, str) else list(epilogues_up)
+    ed = [epilogues_down] * n if isinstance(epilogues_down, str) else list(epilogues_down)
+    outs = list(out_list) if out_list is not None else [None] * n
+    if not (len(w_up_list) == len(w_down_list) == len(eu) == len(ed) == len(outs) == n) or not mxfp4_grouped_route(a_list, w_up_list, None, eu):
+        return False
+    if not all(mxfp4_mx_route(a, wu, wd, e1, e2, o) for a, wu, wd, e1, e2, o in zip(a_list, w_up_list, w_down_list, eu, ed, outs)):
+        return False
+    hs = [torch.empty((a.shape[0], _fp4_of(wu).shape[0]), dtype=torch.bfloat16, device="meta") for a, wu in zip(a_list, w_up_list)]
+    return mxfp4_grouped_route(hs, w_down_list, outs, ed)
 
 
 def fp8_grouped_lora_route(a_list, w_list, out_list=None, epilogues="bias") -> bool:
@@ -1247,10 +1363,12 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
     _l.check(rc, "gemm_fp8_grouped_qkv")
 
 
-def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None):
+def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None,
+                        out_mx_list=None):
     """ctypes arrays of a grouped fp4 launch after the per-problem checks (`_check_mxfp4_pair`, `_epilogue_operands`); `fused[i]`:
     problem i writes no `out`.  Every refusal raises ApexMIError with a reason before the library is asked; a float `out` is left
-    to the entry point, which rejects it with its own message."""
+    to the entry point, which rejects it with its own message.  `out_mx_list` (one pair or None per problem): the arrays of the
+    _mx entry points, with the four MX arrays behind ldc; a problem with a pair writes no `out`."""
     import ctypes as C
     lists = (codes_list, scales_list, w_list, out_list)
     n = len(codes_list)
@@ -1263,6 +1381,15 @@ def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_lis
     fused = list(fused or [0] * n)
     if any(len(x) != n for x in (epis, bias_list, gate_list, residual_list, fused)):
         raise _l.ApexMIError(f"{who}: one epilogue name, or one per problem, and one bias / gate / residual entry (or None) per problem")
+    mx = none
+    if out_mx_list is not None:
+        mx = list(out_mx_list)
+        if len(mx) != n:
+            raise _l.ApexMIError(f"{who}: out_mx_list takes one (codes, scales) pair or None per problem")
+        for i, (om, f) in enumerate(zip(mx, fused)):
+            if om is not None and f:
+                raise _l.ApexMIError(f"{who}: problem {i}: a fused q/k/v problem writes q / k / V^T and takes no out_mx")
+        fused = [1 if (f or om is not None) else 0 for f, om in zip(fused, mx)]
     for i, (w, e) in enumerate(zip(w_list, epis)):
         if not isinstance(w, Mxfp4Weight):
             raise _l.ApexMIError(f"{who}: problem {i}: expected an Mxfp4Weight, got {type(w).__name__}")
@@ -1278,14 +1405,20 @@ def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_lis
         if not isinstance(q, torch.Tensor) or q.dim() != 2:
             raise _l.ApexMIError(f"{at}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(q).__name__}")
         _check_mxfp4_pair(at, q, s, q.shape[0], K)
+        if mx[i] is not None:
+            mx[i] = _mxfp4_out_mx(at, mx[i], q.shape[0], w.shape[0], e)
         flags.append(_epilogue_operands(at, q.shape[0], w.shape[0], q.device, b, o, e, g, r, fused=bool(f), told=True)[1])
     VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
+    mx_args = ()
+    if out_mx_list is not None:
+        mx_args = (VP(*[None if om is None else om[0].data_ptr() for om in mx]), I64(*[0 if om is None else om[0].stride(0) for om in mx]),
+                   VP(*[None if om is None else om[1].data_ptr() for om in mx]), I64(*[0 if om is None else om[1].stride(0) for om in mx]))
     return (n, VP(*[t.data_ptr() for t in codes_list]), I64(*[t.stride(0) for t in codes_list]),
             VP(*[t.data_ptr() for t in scales_list]), I64(*[t.stride(0) for t in scales_list]),
             VP(*[w.q.data_ptr() for w in w_list]), I64(*[w.q.stride(0) for w in w_list]),
             VP(*[w.s.data_ptr() for w in w_list]), I64(*[w.s.stride(0) for w in w_list]), VP(*[_ptr(b) for b in bias_list]),
             VP(*[None if f else o.data_ptr() for o, f in zip(out_list, fused)]),
-            I64(*[0 if f else o.stride(0) for o, f in zip(out_list, fused)]), INT(*[t.shape[0] for t in codes_list]),
+            I64(*[0 if f else o.stride(0) for o, f in zip(out_list, fused)]), *mx_args, INT(*[t.shape[0] for t in codes_list]),
             INT(*[w.shape[0] for w in w_list]), K, INT(*[_EPI[e] | fl for e, fl in zip(epis, flags)]),
             VP(*[_ptr(g) if e == "gate_res" else None for g, e in zip(gate_list, epis)]),
             VP(*[_ptr(r) if e == "gate_res" else None for r, e in zip(residual_list, epis)]),
@@ -1293,30 +1426,39 @@ def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_lis
 
 
 def gemm_mxfp4_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilogue="bias", gate_list=None,
-                       residual_list=None) -> None:
+                       residual_list=None, out_mx_list=None) -> None:
     """Up to 4 `gemm_mxfp4` problems sharing K in ONE launch (img / txt streams; QKV + MLP-up of a single block): out_list[i] =
     epi_i(codes_i x w_list[i] + bias_i) with both block scales applied by the MFMA, bit for bit what `gemm_mxfp4` leaves for that
     problem alone.  `w_list` holds `Mxfp4Weight`s; `epilogue` is one name or one per problem (bias / gelu / gate_res, freely
     mixed); a gate_res problem may have residual_list[i] is out_list[i] (in place).  Several problems may share one (codes,
-    scales) pair or row slices of it.  Refusals raise ApexMIError with a reason and write nothing."""
+    scales) pair or row slices of it.  Refusals raise ApexMIError with a reason and write nothing.
+    `out_mx_list` (one `gemm_mxfp4(out_mx=)` pair or None per problem): a problem with a pair leaves as MXFP4 codes and scale
+    bytes instead of out_list[i] (ignored, may be None), bit for bit `gemm_mxfp4(out_mx=)` alone; MX and bf16 outputs may be
+    mixed in one launch."""
     who = "gemm_mxfp4_grouped"
-    args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list)
+    args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list,
+                               out_mx_list=out_mx_list)
+    if out_mx_list is not None:
+        _l.check(_l.load().apexmi_gemm_mxfp4_grouped_mx(*args, _stream()), who + "_mx")
+        return
     _l.check(_l.load().apexmi_gemm_mxfp4_grouped(*args, _stream()), who)
 
 
 def gemm_mxfp4_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
-                           eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor) -> None:
+                           eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor,
+                           out_mx_list=None) -> None:
     """`gemm_mxfp4_grouped` with `qkv_prepare` fused into the epilogue of the problems flagged in `is_qkv` (fused QKV projections,
     N = 3 H 128), mirroring `gemm_fp8_grouped_qkv`: q / k leave normalised per head, rotated and laid out [H, S_out, 128], v leaves
     transposed [H, 128, Skp]; bit-identical to gemm_mxfp4_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
-    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count."""
+    written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count.  `out_mx_list`: as
+    `gemm_mxfp4_grouped`, for the problems that are not fused q/k/v (a fused problem with a pair raises)."""
     import ctypes as C
     who = "gemm_mxfp4_grouped_qkv"
     n = len(codes_list)
     if len(is_qkv) != n or len(row0) != n:
         raise _l.ApexMIError(f"{who}: is_qkv and row0 take one entry per problem")
     args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
-                               fused=[1 if f else 0 for f in is_qkv])
+                               fused=[1 if f else 0 for f in is_qkv], out_mx_list=out_mx_list)
     for name, t_ in (("qo", qo), ("ko", ko), ("vt", vt)):
         if not isinstance(t_, torch.Tensor):
             raise _l.ApexMIError(f"{who}: null q/k/v output `{name}`")
@@ -1339,6 +1481,9 @@ def gemm_mxfp4_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list,
     qargs = (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
              VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
              ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+    if out_mx_list is not None:
+        _l.check(_l.load().apexmi_gemm_mxfp4_grouped_qkv_mx(*args, *qargs, _stream()), who + "_mx")
+        return
     _l.check(_l.load().apexmi_gemm_mxfp4_grouped_qkv(*args, *qargs, _stream()), who)
 
 
@@ -1350,7 +1495,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
          out: Optional[torch.Tensor] = None, epilogue: str = "bias",
          gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
          lora_buf: Optional[torch.Tensor] = None,
-         quantised: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_mx=None) -> torch.Tensor:
+         quantised: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_mx=None,
+         quantised_mxfp4: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, out_mxfp4=None) -> torch.Tensor:
     """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  2-D operands, last dim contiguous; a / out / residual bf16, or float32
     in the f32-storage verification mode (w and bias stay bf16).  A bf16 `a` with a float32 `out` (and `residual`) is the
     f32 RESIDUAL STREAM: the same launch with the float epilogue, no split of `a`.  `lora_buf`: see _gemm_fp8_lora (ignored
@@ -1375,6 +1521,11 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     OPT-IN MXFP4 COMPUTE: a bf16 weight that carries an `Mxfp4Weight` with `compute == "fp4"` in its `_fp4` slot
     (`set_fp4_compute` of the model attaches it) takes `quant_blocks_mxfp4` (codes and scale bytes in a per-stream scratch) +
     `gemm_mxfp4` when `mxfp4_route` says so, asked before everything above.  A weight without the slot never reaches that code.
+    `quantised_mxfp4=(codes, scales)`: the activations of that route ALREADY quantised — what `quant_blocks_mxfp4(a)` would
+    return, as `ln_modulate_quant_mxfp4` or an `out_mxfp4` launch produces it — so the route skips its quantise launch and reads
+    only the shape and dtype of `a`.  `out_mxfp4=(codes, scales)`: the route writes its output as MXFP4 (`gemm_mxfp4(out_mx=)`)
+    instead of `out`, and returns the pair.  The caller decides beforehand with `mxfp4_norm_quant_route` / `mxfp4_mx_route`; a
+    call that passes either and does not take the fp4 route raises.
 
     OPT-IN MXFP6 COMPUTE: the same with an `Mxfp6Weight` (`compute == "fp6"`) in the weight's `_fp6` slot
     (`set_fp6_compute`), `quant_blocks_mxfp6` + `gemm_mxfp6` and `mxfp6_route`.  A weight carries at most one of the two slots
@@ -1384,9 +1535,18 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
         if quantised is not None or out_mx is not None:
             raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP4 route (the weight "
                                  "carries an Mxfp4Weight): e4m3 codes are not fp4 operands")
-        qa, sa = _act_scratch_mxfp4(a.device, a.shape[0], a.shape[1])
-        quant_blocks_mxfp4(a, out=qa, scale_out=sa)
+        if quantised_mxfp4 is not None:
+            qa, sa = quantised_mxfp4
+            _check_mxfp4_pair("gemm.quantised_mxfp4", qa, sa, a.shape[0], a.shape[1])
+        else:
+            qa, sa = _act_scratch_mxfp4(a.device, a.shape[0], a.shape[1])
+            quant_blocks_mxfp4(a, out=qa, scale_out=sa)
+        if out_mxfp4 is not None:
+            return gemm_mxfp4(qa, sa, w._fp4, bias, epilogue=epilogue, out_mx=out_mxfp4)
         return gemm_mxfp4(qa, sa, w._fp4, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
+    if quantised_mxfp4 is not None or out_mxfp4 is not None:
+        raise _l.ApexMIError("gemm: `quantised_mxfp4` / `out_mxfp4` were passed but this call does not take the MXFP4 route "
+                             "(mxfp4_route is False): decide with mxfp4_norm_quant_route / mxfp4_mx_route first")
     if getattr(w, "_fp6", None) is not None and mxfp6_route(a, w, out, epilogue):
         if quantised is not None or out_mx is not None:
             raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP6 route (the weight "

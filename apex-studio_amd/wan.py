@@ -270,7 +270,7 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, Fp6ComputeMixin, 
 
     _FP4_LINEARS = ("qkv", "attn_out", "cross_q", "cross_kv", "cross_out", "ffn_up", "ffn_down")
 
-    def set_fp4_compute(self, on: bool, linears=None):
+    def set_fp4_compute(self, on: bool, linears=None, fused_quant: bool = False, mx_ffn: bool = False):
         """Opt-in approximation: the selected block Linears of a bf16 model — `linears`, a subset of ("qkv",
         "attn_out", "cross_q", "cross_kv", "cross_out", "ffn_up", "ffn_down"), None = all seven (the Linears of `_fp8_plan`) —
         quantise their activations per block of 32 to MXFP4 and multiply e2m1 x e2m1 (`ops.quant_blocks_mxfp4` +
@@ -285,8 +285,19 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, Fp6ComputeMixin, 
         Refused: a model with resident quantised records (a keep_fp8 / keep_quantized load has no bf16 weight to copy, and the
         `fp8_*` switches need exactly such records, so the two modes cannot meet), f32 activation storage and the f32 residual
         stream (their GEMMs read or write float rows, which this mode does not route; `set_storage_dtype` / `set_residual_dtype`
-        refuse float32 while the mode is on), and an unknown name in `linears`."""
-        return self._fp4_switch(on, linears)      # module_base.Fp4ComputeMixin: the part of the switch shared with Flux
+        refuse float32 while the mode is on), and an unknown name in `linears`.
+
+        `fused_quant=True` (needs `on=True`): the fp4-selected ones of the three Linears that read a buffer a norm wrote one
+        launch earlier — the fused q|k|v, the cross-attention query behind an affine `norm2`, the FFN-up projection — get their
+        e2m1 codes and scale bytes from the norm kernel itself (`ops.ln_modulate_quant_mxfp4`, passed on through
+        `ops.gemm(quantised_mxfp4=)`) wherever `ops.mxfp4_norm_quant_route` allows it: their `quant_blocks_mxfp4` launch
+        disappears and the bf16 normalised rows are never stored.  `mx_ffn=True` (needs `on=True`, composes with `fused_quant`):
+        with `ffn_up` and `ffn_down` both on fp4 and where `ops.mxfp4_mx_route` holds, FFN-up quantises its own GELU output in the
+        epilogue (`ops.gemm_mxfp4(out_mx=)`) into the bytes of the hidden buffer and FFN-down reads those codes, so the hidden
+        state's `quant_blocks_mxfp4` launch and its bf16 round trip disappear.  Both change launches and traffic only: the
+        forward is bit-identical to `set_fp4_compute(True, linears)` without them.  A name selected for fp6 keeps its launches.
+        The defaults (False) leave every launch as it is."""
+        return self._fp4_switch(on, linears, fused_quant, mx_ffn)      # module_base.Fp4ComputeMixin: the part shared with Flux
 
     def set_fp6_compute(self, on: bool, linears=None):
         """Opt-in approximation: `set_fp4_compute` with MXFP6 in the place of MXFP4 — the selected block Linears
@@ -309,12 +320,19 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, Fp6ComputeMixin, 
         return {"qkv": blk._wqkv, "attn_out": a1.to_out[0].weight, "cross_q": a2.to_q.weight, "cross_kv": blk._wkv2,
                 "cross_out": a2.to_out[0].weight, "ffn_up": blk.ffn.net[0].proj.weight, "ffn_down": blk.ffn.net[2].weight}
 
-    def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", out_mx=None, **norm):
+    def _norm_gemm(self, x, xn, w, bias, out, lora_buf, epilogue="bias", out_mx=None, out_mxfp4=None, **norm):
         """ln_modulate(x, **norm, out=xn) -> gemm(xn, w, bias, out=out, epilogue=epilogue, lora_buf=lora_buf); with
         `set_fp8_compute(fused_quant=True)`, where `ops.fp8_norm_quant_route` allows it, the norm quantises for the GEMM in its own
         launch (and stores `xn` only if the GEMM's adapter tail reads it).  Nothing else reads `xn` between the two.  `out_mx`: see
-        `ops.gemm` (the caller has asked `ops.fp8_mx_route`)."""
+        `ops.gemm` (the caller has asked `ops.fp8_mx_route`).  With `set_fp4_compute(fused_quant=True)` the same for an fp4
+        Linear, where `ops.mxfp4_norm_quant_route` allows it: `xn` is not stored (the fp4 mode has no adapter tail).  `out_mxfp4`:
+        see `ops.gemm` (the caller has asked `ops.mxfp4_mx_route`)."""
         mx = {} if out_mx is None else {"out_mx": out_mx}
+        if out_mxfp4 is not None:
+            mx["out_mxfp4"] = out_mxfp4
+        if self._fp4_fused_quant and ops.mxfp4_norm_quant_route(x, xn, w, out, epilogue):
+            q = ops.ln_modulate_quant_mxfp4(x, **norm)
+            return ops.gemm(xn, w, bias, out=out, epilogue=epilogue, quantised_mxfp4=q, **mx)
         if getattr(self, "_fp8_fused_quant", False):
             fuse, need_row = ops.fp8_norm_quant_route(x, xn, w, out, epilogue, lora_buf)
             if fuse:
@@ -607,6 +625,16 @@ class WanTransformer3DModel(Fp8ResidentMixin, Fp4ComputeMixin, Fp6ComputeMixin, 
                                 scale=m(4), shift=m(3), eps=eps)
                 ops.gemm_fp8(hq, None, ops._fp8_of(w_down), blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5), residual=X,
                              block_scales=hs)
+                continue
+            if self._fp4_mx_ffn and ws.FFHf.stride(0) % 8 == 0 and ops.mxfp4_mx_route(XN, w_up, w_down, "gelu", "gate_res", out=X):
+                # the hidden state as MXFP4 codes + scale bytes in the bytes of FFHf (ffn / 2 + ffn / 32 of a row's 2 ffn), which
+                # holds no bf16 row in this mode
+                raw = ws.FFHf.view(torch.uint8)
+                ffn = FFH.shape[1]
+                hq, hs = raw[:, :ffn // 2], raw[:, ffn // 2:ffn // 2 + ffn // 32]
+                self._norm_gemm(X, XN, w_up, blk.ffn.net[0].proj.bias, None, ws.XNf, epilogue="gelu", out_mxfp4=(hq, hs),
+                                scale=m(4), shift=m(3), eps=eps)
+                ops.gemm_mxfp4(hq, hs, w_down._fp4, blk.ffn.net[2].bias, out=X, epilogue="gate_res", gate=m(5), residual=X)
                 continue
             self._norm_gemm(X, XN, w_up, blk.ffn.net[0].proj.bias, FFH, ws.XNf, epilogue="gelu",
                             scale=m(4), shift=m(3), eps=eps)

@@ -947,6 +947,58 @@ int apexmi_gemm_mxfp4_grouped_qkv(int count, const void* const* qa, const int64_
                                   float eps, const float* rope, void* q_out, void* k_out, void* vt_out, int S_out, int Skp,
                                   apexmi_stream_t stream);
 
+/* apexmi_ln_modulate_quant_mxfp4 — replaces apexmi_ln_modulate2 (x_dtype APEXMI_BF16) or apexmi_ln_modulate2_f32in (x_dtype
+ * APEXMI_F32, ldx in floats) followed by apexmi_quant_blocks_mxfp4 on its output, where a norm feeds an fp4 Linear: one launch that
+ * keeps the normalised row in registers, rounds it to bf16 as the norm's store does and quantises the ROUNDED values per block of
+ * 32 columns (4 adjacent lanes; no row-wide reduction, no second pass).  About 5.06 bytes per element become 2.53 (4.53 with
+ * `out`).  codes uint8 [M, C / 2] (row stride ldq bytes), scales uint8 [M, C / 32] (row stride lds bytes); out bf16 [M, C] (row
+ * stride ldo elements) or NULL: no bf16 row is stored.  codes, scales and out are BIT-IDENTICAL to the two launches, for every
+ * (x_dtype, C, `ln.wave`): the kernel is the MXFP4 form of the one the norm alone would have run.  Bytes of a codes or scales row
+ * past C / 2 and C / 32 are not written.  Every other operand as apexmi_ln_modulate2.  M >= 1; C % 128 == 0 and C <= 8192; 16-byte
+ * rows with ldx, ldo >= C, ldq >= C / 2 and ldq % 16 == 0, lds >= C / 32; 16-byte aligned modulation and affine vectors; split in
+ * [0, M].  Every argument is checked before the launch. */
+int apexmi_ln_modulate_quant_mxfp4(const void* x, int64_t ldx, int x_dtype, void* out, int64_t ldo, void* codes, int64_t ldq,
+                                   void* scales, int64_t lds, int M, int C, const float* scale, const float* shift,
+                                   const void* gamma, const void* beta, float eps, int rms, int split, const float* scale2,
+                                   const float* shift2, apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp4_mx — replaces apexmi_gemm_mxfp4 followed by apexmi_quant_blocks_mxfp4 on its output, where the next Linear is an
+ * fp4 one too (the FFN hidden state): the epilogue quantises the value it would have stored as bf16, per aligned block of 32
+ * output columns, and writes mx_codes uint8 [M, N / 2] (row stride ldmc bytes) and mx_scales uint8 [M, N / 32] (row stride ldms
+ * bytes), BIT-IDENTICAL to the two launches.  C is not written and may be NULL; rows >= M of the outputs are not written.  For
+ * APEXMI_EPI_BIAS and APEXMI_EPI_BIAS_GELU; N % 128 == 0; ldmc >= N / 2, ldmc % 4 == 0 and mx_codes 4-byte aligned (a consumer
+ * GEMM asks for 16), ldms >= N / 32 and ldms % 4 == 0.  Refused before the launch, besides what apexmi_gemm_mxfp4 refuses: the
+ * gate x y + residual epilogue, N % 128 != 0, scales without codes or codes without scales.  mx_codes and mx_scales both NULL:
+ * apexmi_gemm_mxfp4 itself, its launch and its bits. */
+int apexmi_gemm_mxfp4_mx(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
+                         int64_t ldsw, const void* bias, void* C, int64_t ldc, void* mx_codes, int64_t ldmc, void* mx_scales,
+                         int64_t ldms, int M, int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr,
+                         apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp4_grouped_mx — replaces apexmi_gemm_mxfp4_grouped followed by apexmi_quant_blocks_mxfp4 on the outputs that feed
+ * fp4 Linears (the FF-up pair of a Flux double block).  The per-problem arrays mx_codes[i] / ldmc[i] / mx_scales[i] / ldms[i] as
+ * apexmi_gemm_mxfp4_mx; a problem whose two entries are NULL behaves exactly as in apexmi_gemm_mxfp4_grouped, so one launch may
+ * mix MX and bf16 outputs, and a launch without any MX output is apexmi_gemm_mxfp4_grouped's.  Every problem is checked before
+ * the launch; nothing is written on a refusal. */
+int apexmi_gemm_mxfp4_grouped_mx(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                                 const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                                 const void* const* bias, void* const* C, const int64_t* ldc, void* const* mx_codes,
+                                 const int64_t* ldmc, void* const* mx_scales, const int64_t* ldms, const int* M, const int* N, int K,
+                                 const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                                 apexmi_stream_t stream);
+
+/* apexmi_gemm_mxfp4_grouped_qkv_mx — replaces apexmi_gemm_mxfp4_grouped_qkv followed by apexmi_quant_blocks_mxfp4 on the output of a
+ * problem that is NOT fused q/k/v (the MLP-up problem of a Flux single block): the MX arrays of apexmi_gemm_mxfp4_grouped_mx on
+ * the fused-q/k/v launch.  A fused q/k/v problem with an MX entry is refused. */
+int apexmi_gemm_mxfp4_grouped_qkv_mx(int count, const void* const* qa, const int64_t* lda, const void* const* sa, const int64_t* ldsa,
+                                     const void* const* qw, const int64_t* ldw, const void* const* sw, const int64_t* ldsw,
+                                     const void* const* bias, void* const* C, const int64_t* ldc, void* const* mx_codes,
+                                     const int64_t* ldmc, void* const* mx_scales, const int64_t* ldms, const int* M, const int* N,
+                                     int K, const int* epilogue, const float* const* gate, const void* const* R, const int64_t* ldr,
+                                     const int* is_qkv, const void* const* norm_q, const void* const* norm_k, const int* row0, int H,
+                                     float eps, const float* rope, void* q_out, void* k_out, void* vt_out, int S_out, int Skp,
+                                     apexmi_stream_t stream);
+
 /* MXFP6 compute (opt-in): OCP e2m3 codes, 6 bits = sign << 5 | exp << 3 | man with bias 1 (exp = 0: man / 8; otherwise
  * (1 + man / 8) 2^(exp - 1): the magnitudes 0, 0.125 .. 0.875, 1 .. 1.875, 2 .. 3.75, 4 .. 7.5), with one e8m0 scale byte per 32
  * consecutive k, as apexmi_quant_blocks_mxfp4.  A row of K codes is 3 K / 4 bytes: block b is bytes 24 b .. 24 b + 23, and code j of the
