@@ -520,4 +520,85 @@ static void launch_by_epilogue(int epilogue, KernelOf kernel_of, const Args& G, 
     }
 }
 
+// ---- host side of the MX formats whose block scales ride in the MFMA (gemm_mxfp4.hip, gemm_mxfp6.hip): one problem record, one
+// check; and the one body of the three MX block quantisers (apexmi_quant_blocks_mxfp8 / _mxfp4 / _mxfp6) ----
+struct MxGemm : Fp8Problem {           // A / W: packed codes, lda / ldw in bytes; sa, sw, abs unused; Q / QS: the MX output (e2m1 only)
+    const uint8_t* SA;                 // activation block scales [M, K / 32]
+    const uint8_t* SW;                 // weight block scales [N, K / 32]
+    int64_t ldsa, ldsw;
+    unsigned long long* clk;
+};
+
+// the MX output of the _mx entry points (both members null = the bf16 output C): C may then be null and is not written
+struct MxOut {
+    void* Q;              // codes [M, N / 2]
+    int64_t ldq;
+    void* QS;             // scale bytes [M, N / 32]
+    int64_t ldqs;
+};
+
+// ONE problem of any entry point: the null check, the MX output's rules (only a format whose kernel has that epilogue passes
+// `mx`; e2m1 today, which the wording assumes), the format-independent checks (fp8_check_tile_problem with the rules of `f`, whose
+// ld_note is a pattern for the bytes of a code row), then the scale-row rule; fills the Fp8Problem part of `P` and its SA / SW /
+// ldsa / ldsw.  `i` = the problem's index in a grouped launch, which the messages name, or -1; tile0 = the tiles of the problems
+// before it.
+template <class Problem>
+static int mx_check_problem(const char* who, int i, int64_t tile0, Fp8Format f, const void* qa, int64_t lda, const void* sa, int64_t ldsa,
+                            const void* qw, int64_t ldw, const void* sw, int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N,
+                            int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P, const MxOut* mx = nullptr) {
+    const Fp8Where at(i);
+    const bool mxo = mx != nullptr && (mx->Q != nullptr || mx->QS != nullptr);
+    APEXMI_REQUIRE(qa && sa && qw && sw && (C || mxo), "%s: null operand%s", who, at.paren);
+    if (mxo) {
+        APEXMI_REQUIRE(mx->Q && mx->QS, "%s: the MX output%s needs codes and block scales", who, at.of);
+        APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU,
+                       "%s: the MX output%s exists for the bias (0) and tanh GELU (1) epilogues, not epilogue %d", who, at.of, epilogue);
+        APEXMI_REQUIRE(N % 128 == 0, "%s: N=%d%s must be a multiple of 128 for the MX output", who, N, at.of);
+        APEXMI_REQUIRE(mx->ldq >= N / 2 && mx->ldq % 4 == 0 && ((uintptr_t)mx->Q % 4) == 0 && mx->ldqs >= N / 32 && mx->ldqs % 4 == 0,
+                       "%s: the MX output%s needs 4-byte aligned code rows at least N / 2 bytes wide and scale rows at least N / 32 "
+                       "wide, a multiple of 4 (ldmc %lld, ldms %lld)", who, at.of, (long long)mx->ldq, (long long)mx->ldqs);
+        if (C == nullptr) ldc = N;      // not written, not read
+    }
+    char ld_note[64];
+    snprintf(ld_note, sizeof(ld_note), f.ld_note, f.code_bits ? K / 8 * f.code_bits : K / f.codes_per_byte);
+    f.ld_note = ld_note;
+    if (fp8_check_tile_problem(who, at, f, tile0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, (Fp8Problem*)P)) return 1;
+    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
+                   "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, at.of,
+                   K / 32, (long long)ldsa, (long long)ldsw);
+    P->SA = (const uint8_t*)sa, P->SW = (const uint8_t*)sw, P->ldsa = ldsa, P->ldsw = ldsw;
+    if (mxo) P->Q = (uint8_t*)mx->Q, P->QS = (uint8_t*)mx->QS, P->ldq = mx->ldq, P->ldqs = mx->ldqs;
+    return 0;
+}
+
+// what differs between the three MX block quantisers, in the rules and in the wording of the messages
+struct MxQuantFormat {
+    const char* who;         // the entry point's name without "apexmi_"
+    int block_bytes;         // bytes of a block's 32 codes: 32 (e4m3), 16 (e2m1), 24 (e2m3); a code row is K / 32 of them
+    int code_align;          // alignment of `codes` and of its rows, in bytes
+    int k_mult;              // K is a multiple of it, and at least it
+    const char* rows_rule;   // the rule of the rows, as its message words it
+    const char* lds_name;    // how the messages name the leading dimension of the scales
+};
+
+// the body of apexmi_quant_blocks_mx*: `kernel` takes 16 elements per thread, (a, lda, M, K, codes, ldq, scales, lds)
+template <class Kernel>
+static int mx_quant_blocks(const MxQuantFormat& f, Kernel kernel, const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq,
+                           void* scales, int64_t lds_, hipStream_t stream) {
+    APEXMI_REQUIRE(a && codes && scales, "%s: null operand", f.who);
+    APEXMI_REQUIRE(M >= 1, "%s: M=%d must be at least 1", f.who, M);
+    APEXMI_REQUIRE(K >= f.k_mult && K % f.k_mult == 0, "%s: K=%d must be a multiple of %d", f.who, K, f.k_mult);
+    APEXMI_REQUIRE(lda >= K && ldq >= K / 32 * f.block_bytes && lda % 8 == 0 && ldq % f.code_align == 0 && ((uintptr_t)a % 16) == 0 &&
+                       ((uintptr_t)codes % f.code_align) == 0,
+                   "%s: %s (lda %lld, ldq %lld)", f.who, f.rows_rule, (long long)lda, (long long)ldq);
+    APEXMI_REQUIRE(lds_ >= K / 32, "%s: rows of the block scales must be at least K / 32 = %d wide (%s %lld)", f.who, K / 32, f.lds_name,
+                   (long long)lds_);
+    ApexmiProfScope prof(5, stream, 0.0, (2.0 + (f.block_bytes + 1) / 32.0) * (double)M * K);     // bf16 in, codes and scale bytes out
+    const int64_t threads = (int64_t)M * (K / 16);
+    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "%s: M=%d x K=%d is too large for one launch", f.who, M, K);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M, K, (uint8_t*)codes,
+                       ldq, (uint8_t*)scales, lds_);
+    return apexmi_check_launch(f.who);
+}
+
 }  // namespace

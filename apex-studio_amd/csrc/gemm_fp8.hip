@@ -369,21 +369,8 @@ extern "C" int apexmi_quant_rows_fp8(const void* a, int64_t lda, int M, int K, v
 
 extern "C" int apexmi_quant_blocks_mxfp8(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* block_scales,
                                          int64_t ldbs, apexmi_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(a && codes && block_scales, "quant_blocks_mxfp8: null operand");
-    APEXMI_REQUIRE(M >= 1, "quant_blocks_mxfp8: M=%d must be at least 1", M);
-    APEXMI_REQUIRE(K >= 128 && K % 128 == 0, "quant_blocks_mxfp8: K=%d must be a multiple of 128", K);
-    APEXMI_REQUIRE(lda >= K && ldq >= K && lda % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 16) == 0,
-                   "quant_blocks_mxfp8: rows must be 16-byte aligned and at least K wide (lda %lld, ldq %lld)", (long long)lda,
-                   (long long)ldq);
-    APEXMI_REQUIRE(ldbs >= K / 32, "quant_blocks_mxfp8: rows of the block scales must be at least K / 32 = %d wide (ldbs %lld)", K / 32,
-                   (long long)ldbs);
-    ApexmiProfScope prof(5, stream, 0.0, (3.0 + 1.0 / 32) * (double)M * K);
-    const int64_t threads = (int64_t)M * (K / 16);
-    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "quant_blocks_mxfp8: M=%d x K=%d is too large for one launch", M, K);
-    hipLaunchKernelGGL(quant_blocks_mxfp8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M,
-                       K, (uint8_t*)codes, ldq, (uint8_t*)block_scales, ldbs);
-    return apexmi_check_launch("quant_blocks_mxfp8");
+    const MxQuantFormat e4m3{"quant_blocks_mxfp8", 32, 16, 128, "rows must be 16-byte aligned and at least K wide", "ldbs"};
+    return mx_quant_blocks(e4m3, quant_blocks_mxfp8_kernel, a, lda, M, K, codes, ldq, block_scales, ldbs, (hipStream_t)stream_);
 }
 
 // the MX operands of one problem (apexmi_gemm_fp8_mx, apexmi_gemm_fp8_grouped_mx); null members = not used

@@ -50,13 +50,6 @@ __global__ __launch_bounds__(256) void quant_blocks_mxfp4_kernel(const bf16_t* _
 constexpr int X4_SCB = FBM * 8;                              // scale bytes of one operand tile: 128 rows x 8 blocks
 constexpr int X4_LDS = 4 * FOPB + 4 * X4_SCB;                // codes [buf][operand] + scales [buf][operand]
 
-struct Mxfp4Gemm : Fp8Problem {        // A / W: e2m1 codes, two to a byte, lda / ldw in bytes; sa, sw, abs unused; Q / QS: the MX output
-    const uint8_t* SA;                 // activation block scales [M, K / 32]
-    const uint8_t* SW;                 // weight block scales [N, K / 32]
-    int64_t ldsa, ldsw;
-    unsigned long long* clk;
-};
-
 // The grouped form (apexmi_gemm_mxfp4_grouped, apexmi_gemm_mxfp4_grouped_qkv): the table entry of the fp8 kernel's grouped form
 // (Fp8GroupProblem, fp8_gemm_tile.h) plus the problem's own block scales; the table travels by value, as Fp8Group does.
 struct Mxfp4GroupProblem : Fp8GroupProblem {
@@ -72,7 +65,7 @@ struct Mxfp4Group {
 };
 
 // this workgroup's tile id `t` inside its problem, and the problem: the launch itself, or the table entry found by the prefix sums
-APEXMI_DEVICE const Mxfp4Gemm& mxfp4_problem(const Mxfp4Gemm& G, int& t) {
+APEXMI_DEVICE const MxGemm& mxfp4_problem(const MxGemm& G, int& t) {
     t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
     return G;
 }
@@ -81,7 +74,7 @@ APEXMI_DEVICE Mxfp4GroupProblem mxfp4_problem(const Mxfp4Group& G, int& t) {
     return fp8_group_entry(G.p, G.count, G.total, t, pi);
 }
 
-// ONE kernel for both forms, chosen by the argument type (Mxfp4Gemm, Mxfp4Group), as gemm_fp8_kernel: build.py's no-spill check
+// ONE kernel for both forms, chosen by the argument type (MxGemm, Mxfp4Group), as gemm_fp8_kernel: build.py's no-spill check
 // matches "gemm_mxfp4_kernel" and so covers every instantiation.
 // EPI: APEXMI_EPI_BIAS, APEXMI_EPI_BIAS_GELU or APEXMI_EPI_BIAS_GATE_RES; the grouped form reads it from its problem instead
 // MXO (apexmi_gemm_mxfp4_mx, apexmi_gemm_mxfp4_grouped(_qkv)_mx): the output leaves as MXFP4 codes and scale bytes (Q / QS, the
@@ -178,74 +171,26 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp4_kernel(const Args A) {
 
 extern "C" int apexmi_quant_blocks_mxfp4(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* scales, int64_t lds_,
                                          apexmi_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(a && codes && scales, "quant_blocks_mxfp4: null operand");
-    APEXMI_REQUIRE(M >= 1, "quant_blocks_mxfp4: M=%d must be at least 1", M);
-    APEXMI_REQUIRE(K >= 32 && K % 32 == 0, "quant_blocks_mxfp4: K=%d must be a multiple of 32", K);
-    APEXMI_REQUIRE(lda >= K && ldq >= K / 2 && lda % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 16) == 0,
-                   "quant_blocks_mxfp4: rows must be 16-byte aligned, a at least K and the codes at least K / 2 bytes wide (lda %lld, "
-                   "ldq %lld)", (long long)lda, (long long)ldq);
-    APEXMI_REQUIRE(lds_ >= K / 32, "quant_blocks_mxfp4: rows of the block scales must be at least K / 32 = %d wide (lds %lld)", K / 32,
-                   (long long)lds_);
-    ApexmiProfScope prof(5, stream, 0.0, (2.5 + 1.0 / 32) * (double)M * K);
-    const int64_t threads = (int64_t)M * (K / 16);
-    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "quant_blocks_mxfp4: M=%d x K=%d is too large for one launch", M, K);
-    hipLaunchKernelGGL(quant_blocks_mxfp4_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M,
-                       K, (uint8_t*)codes, ldq, (uint8_t*)scales, lds_);
-    return apexmi_check_launch("quant_blocks_mxfp4");
+    const MxQuantFormat e2m1{"quant_blocks_mxfp4", 16, 16, 32,
+                             "rows must be 16-byte aligned, a at least K and the codes at least K / 2 bytes wide", "lds"};
+    return mx_quant_blocks(e2m1, quant_blocks_mxfp4_kernel, a, lda, M, K, codes, ldq, scales, lds_, (hipStream_t)stream_);
 }
 
-// ONE problem of either entry point: the null check, the format-independent checks (fp8_check_tile_problem with the e2m1 rules),
-// then the scale-row rule; fills the Fp8Problem part of `P` and its SA / SW / ldsa / ldsw.  `i` = the problem's index in a grouped
-// launch, which the messages name, or -1; tile0 = the tiles of the problems before it.
-// mx = the MX output of the _mx entry points (both members null = the bf16 output C): C may then be null and is not written.
-struct Mxfp4MxOut {
-    void* Q;              // codes [M, N / 2]
-    int64_t ldq;
-    void* QS;             // scale bytes [M, N / 32]
-    int64_t ldqs;
-};
-template <class Problem>
-static int mxfp4_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const void* sa, int64_t ldsa,
-                               const void* qw, int64_t ldw, const void* sw, int64_t ldsw, const void* bias, void* C, int64_t ldc, int M,
-                               int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P,
-                               const Mxfp4MxOut* mx = nullptr) {
-    const Fp8Where at(i);
-    const bool mxo = mx != nullptr && (mx->Q != nullptr || mx->QS != nullptr);
-    APEXMI_REQUIRE(qa && sa && qw && sw && (C || mxo), "%s: null operand%s", who, at.paren);
-    if (mxo) {
-        APEXMI_REQUIRE(mx->Q && mx->QS, "%s: the MX output%s needs codes and block scales", who, at.of);
-        APEXMI_REQUIRE(epilogue == APEXMI_EPI_BIAS || epilogue == APEXMI_EPI_BIAS_GELU,
-                       "%s: the MX output%s exists for the bias (0) and tanh GELU (1) epilogues, not epilogue %d", who, at.of, epilogue);
-        APEXMI_REQUIRE(N % 128 == 0, "%s: N=%d%s must be a multiple of 128 for the MX output", who, N, at.of);
-        APEXMI_REQUIRE(mx->ldq >= N / 2 && mx->ldq % 4 == 0 && ((uintptr_t)mx->Q % 4) == 0 && mx->ldqs >= N / 32 && mx->ldqs % 4 == 0,
-                       "%s: the MX output%s needs 4-byte aligned code rows at least N / 2 bytes wide and scale rows at least N / 32 "
-                       "wide, a multiple of 4 (ldmc %lld, ldms %lld)", who, at.of, (long long)mx->ldq, (long long)mx->ldqs);
-        if (C == nullptr) ldc = N;      // not written, not read
-    }
-    char ld_note[64];
-    snprintf(ld_note, sizeof(ld_note), ", code rows at least K / 2 = %d bytes", K / 2);
-    const Fp8Format e2m1{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ld_note, "bytes", true, "output and bias 8-byte"};
-    if (fp8_check_tile_problem(who, at, e2m1, tile0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, (Fp8Problem*)P)) return 1;
-    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
-                   "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, at.of,
-                   K / 32, (long long)ldsa, (long long)ldsw);
-    P->SA = (const uint8_t*)sa, P->SW = (const uint8_t*)sw, P->ldsa = ldsa, P->ldsw = ldsw;
-    if (mxo) P->Q = (uint8_t*)mx->Q, P->QS = (uint8_t*)mx->QS, P->ldq = mx->ldq, P->ldqs = mx->ldqs;
-    return 0;
-}
+// the e2m1 rules and wording of mx_check_problem (fp8_gemm_tile.h)
+constexpr Fp8Format X4_FORMAT{256, " (a K-tile is 128 bytes of e2m1 codes)", 2, ", code rows at least K / 2 = %d bytes", "bytes", true,
+                              "output and bias 8-byte"};
 
 extern "C" int apexmi_gemm_mxfp4(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
                                  int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                                  const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const char* who = "gemm_mxfp4";
-    Mxfp4Gemm G{};
-    if (mxfp4_check_problem(who, -1, 0, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
+    MxGemm G{};
+    if (mx_check_problem(who, -1, 0, X4_FORMAT, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
     G.clk = apexmi_clk_ptr();
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * ((double)M + N) * K + 2.0 * (double)M * N);
     // 68 KB of dynamic LDS is above the default limit
-    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp4_kernel<decltype(epi)::value, Mxfp4Gemm>; }, G,
+    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp4_kernel<decltype(epi)::value, MxGemm>; }, G,
                        (unsigned)(G.tiles_m * G.tiles_n), X4_LDS, stream);
     return apexmi_check_launch(who);
 }
@@ -260,15 +205,15 @@ extern "C" int apexmi_gemm_mxfp4_mx(const void* qa, int64_t lda, const void* sa,
         return apexmi_gemm_mxfp4(qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, stream_);
     hipStream_t stream = (hipStream_t)stream_;
     const char* who = "gemm_mxfp4_mx";
-    const Mxfp4MxOut mx{mx_codes, ldmc, mx_scales, ldms};
-    Mxfp4Gemm G{};
-    if (mxfp4_check_problem(who, -1, 0, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G, &mx)) return 1;
+    const MxOut mx{mx_codes, ldmc, mx_scales, ldms};
+    MxGemm G{};
+    if (mx_check_problem(who, -1, 0, X4_FORMAT, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G, &mx)) return 1;
     G.clk = apexmi_clk_ptr();
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.5 + 1.0 / 32) * (((double)M + N) * K + (double)M * N));
     // the check left bias or gelu: the gate_res case of the switch names the bias kernel and is never taken
     launch_by_epilogue(epilogue, [](auto epi) {
         constexpr int EPI = decltype(epi)::value == APEXMI_EPI_BIAS_GELU ? APEXMI_EPI_BIAS_GELU : APEXMI_EPI_BIAS;
-        return gemm_mxfp4_kernel<EPI, Mxfp4Gemm, true>;
+        return gemm_mxfp4_kernel<EPI, MxGemm, true>;
     }, G, (unsigned)(G.tiles_m * G.tiles_n), X4_LDS, stream);
     return apexmi_check_launch(who);
 }
@@ -302,13 +247,13 @@ static int gemm_mxfp4_grouped_run(const char* who, int count, const void* const*
     bool any_mx = false;
     for (int i = 0; i < count; ++i) {
         const bool fused = qkv != nullptr && qkv->is_qkv[i] != 0;
-        const Mxfp4MxOut mx = mxa ? Mxfp4MxOut{mxa->codes[i], mxa->ldmc[i], mxa->scales[i], mxa->ldms[i]} : Mxfp4MxOut{};
+        const MxOut mx = mxa ? MxOut{mxa->codes[i], mxa->ldmc[i], mxa->scales[i], mxa->ldms[i]} : MxOut{};
         const bool mxo = mx.Q != nullptr || mx.QS != nullptr;
         APEXMI_REQUIRE(!(fused && mxo), "%s: a fused q/k/v problem (problem %d) writes q / k / V^T and takes no MX output", who, i);
         any_mx |= mxo;
         Mxfp4GroupProblem& P = G.p[i];
         // a fused problem writes no C: its q_out stands in, N wide
-        if (mxfp4_check_problem(who, i, tiles, qa[i], lda[i], sa[i], ldsa[i], qw[i], ldw[i], sw[i], ldsw[i], bias ? bias[i] : nullptr,
+        if (mx_check_problem(who, i, tiles, X4_FORMAT, qa[i], lda[i], sa[i], ldsa[i], qw[i], ldw[i], sw[i], ldsw[i], bias ? bias[i] : nullptr,
                                 fused ? qkv->q_out : C[i], fused ? N[i] : ldc[i], M[i], N[i], K, epilogue[i], gate ? gate[i] : nullptr,
                                 R ? R[i] : nullptr, ldr ? ldr[i] : 0, &P, &mx))
             return 1;
@@ -321,17 +266,12 @@ static int gemm_mxfp4_grouped_run(const char* who, int count, const void* const*
     }
     G.total = (int)tiles;
     ApexmiProfScope prof(0, stream, flops, bytes);
-    if (any_mx) {       // a launch without an MX output runs the kernel it always ran
-        auto kernel = gemm_mxfp4_kernel<0, Mxfp4Group, true>;
-        static uint64_t attr_set = 0;
-        APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
-        hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), X4_LDS, stream, G);
-        return apexmi_check_launch(who);
-    }
-    auto kernel = gemm_mxfp4_kernel<0, Mxfp4Group>;
-    static uint64_t attr_set = 0;       // 68 KB of dynamic LDS is above the default limit
-    APEXMI_SET_ATTR_ONCE(attr_set, (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, X4_LDS));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(256), X4_LDS, stream, G);
+    // 68 KB of dynamic LDS is above the default limit.  The table entries carry the epilogues: the launch names none, and one without
+    // an MX output runs the kernel it always ran.
+    if (any_mx)
+        launch_by_epilogue(APEXMI_EPI_BIAS, [](auto) { return gemm_mxfp4_kernel<0, Mxfp4Group, true>; }, G, (unsigned)tiles, X4_LDS, stream);
+    else
+        launch_by_epilogue(APEXMI_EPI_BIAS, [](auto) { return gemm_mxfp4_kernel<0, Mxfp4Group>; }, G, (unsigned)tiles, X4_LDS, stream);
     return apexmi_check_launch(who);
 }
 

@@ -4,7 +4,7 @@
 // instruction.  Nothing is multiplied after the K-loop: the epilogue is the unscaled one of fp8_gemm_tile.h.
 #include "common.h"
 #include "fp8_quant.h"        // mx6_scale_byte, mx6_quant16, mx_inv_scale
-#include "fp8_gemm_tile.h"    // the 128 x 128 tile order, Fp8Problem, fp8_epilogue, the host-side check and launch
+#include "fp8_gemm_tile.h"    // the 128 x 128 tile order, MxGemm, fp8_epilogue, the host-side checks and launch
 
 namespace {
 
@@ -77,15 +77,8 @@ constexpr int X6_BUF = 2 * X6_OPB + 2 * X6_SCB;              // one buffer
 constexpr int X6_LDS = 2 * X6_BUF;
 static_assert(FBM == FBN && X6_OPB == 3 * 256 * 16 && X6_BUF % 16 == 0, "three 16-byte pieces per thread and operand tile");
 
-struct Mxfp6Gemm : Fp8Problem {        // A / W: e2m3 codes, 24 bytes per 32, lda / ldw in bytes; sa, sw, abs, Q, QS unused
-    const uint8_t* SA;                 // activation block scales [M, K / 32]
-    const uint8_t* SW;                 // weight block scales [N, K / 32]
-    int64_t ldsa, ldsw;
-    unsigned long long* clk;
-};
-
 // this workgroup's tile id `t` inside its problem, and the problem: the launch itself (a grouped table would be another overload)
-APEXMI_DEVICE const Mxfp6Gemm& mxfp6_problem(const Mxfp6Gemm& G, int& t) {
+APEXMI_DEVICE const MxGemm& mxfp6_problem(const MxGemm& G, int& t) {
     t = xcd_remap(blockIdx.x, G.tiles_m * G.tiles_n);
     return G;
 }
@@ -201,52 +194,26 @@ __global__ __launch_bounds__(256, 2) void gemm_mxfp6_kernel(const Args A) {
 
 extern "C" int apexmi_quant_blocks_mxfp6(const void* a, int64_t lda, int M, int K, void* codes, int64_t ldq, void* scales, int64_t lds_,
                                          apexmi_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    APEXMI_REQUIRE(a && codes && scales, "quant_blocks_mxfp6: null operand");
-    APEXMI_REQUIRE(M >= 1, "quant_blocks_mxfp6: M=%d must be at least 1", M);
-    APEXMI_REQUIRE(K >= 32 && K % 32 == 0, "quant_blocks_mxfp6: K=%d must be a multiple of 32", K);
-    APEXMI_REQUIRE(lda >= K && ldq >= K / 4 * 3 && lda % 8 == 0 && ldq % 8 == 0 && ((uintptr_t)a % 16) == 0 && ((uintptr_t)codes % 8) == 0,
-                   "quant_blocks_mxfp6: rows of a must be 16-byte and code rows 8-byte aligned, a at least K and the codes at least "
-                   "3 K / 4 bytes wide (lda %lld, ldq %lld)", (long long)lda, (long long)ldq);
-    APEXMI_REQUIRE(lds_ >= K / 32, "quant_blocks_mxfp6: rows of the block scales must be at least K / 32 = %d wide (lds %lld)", K / 32,
-                   (long long)lds_);
-    ApexmiProfScope prof(5, stream, 0.0, (2.75 + 1.0 / 32) * (double)M * K);
-    const int64_t threads = (int64_t)M * (K / 16);
-    APEXMI_REQUIRE((threads + 255) / 256 < (1ll << 31), "quant_blocks_mxfp6: M=%d x K=%d is too large for one launch", M, K);
-    hipLaunchKernelGGL(quant_blocks_mxfp6_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)a, lda, M,
-                       K, (uint8_t*)codes, ldq, (uint8_t*)scales, lds_);
-    return apexmi_check_launch("quant_blocks_mxfp6");
+    const MxQuantFormat e2m3{"quant_blocks_mxfp6", 24, 8, 32,
+                             "rows of a must be 16-byte and code rows 8-byte aligned, a at least K and the codes at least 3 K / 4 bytes wide",
+                             "lds"};
+    return mx_quant_blocks(e2m3, quant_blocks_mxfp6_kernel, a, lda, M, K, codes, ldq, scales, lds_, (hipStream_t)stream_);
 }
 
-// ONE problem: the null check, the format-independent checks (fp8_check_tile_problem with the e2m3 rules), then the scale-row rule;
-// fills the Fp8Problem part of `P` and its SA / SW / ldsa / ldsw.  `i` = the problem's index in a grouped launch, or -1.
-template <class Problem>
-static int mxfp6_check_problem(const char* who, int i, int64_t tile0, const void* qa, int64_t lda, const void* sa, int64_t ldsa,
-                               const void* qw, int64_t ldw, const void* sw, int64_t ldsw, const void* bias, void* C, int64_t ldc, int M,
-                               int N, int K, int epilogue, const float* gate, const void* R, int64_t ldr, Problem* P) {
-    const Fp8Where at(i);
-    APEXMI_REQUIRE(qa && sa && qw && sw && C, "%s: null operand%s", who, at.paren);
-    char ld_note[64];
-    snprintf(ld_note, sizeof(ld_note), ", code rows at least 3 K / 4 = %d bytes", K / 4 * 3);
-    const Fp8Format e2m3{X6_KT, " (a K-tile is 96 bytes of e2m3 codes)", 1, ld_note, "bytes", true, "output and bias 8-byte", 6};
-    if (fp8_check_tile_problem(who, at, e2m3, tile0, qa, lda, qw, ldw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, (Fp8Problem*)P)) return 1;
-    APEXMI_REQUIRE(ldsa >= K / 32 && ldsw >= K / 32 && ldsa % 4 == 0 && ldsw % 4 == 0 && ((uintptr_t)sa % 4) == 0 && ((uintptr_t)sw % 4) == 0,
-                   "%s: the block scales%s must be 4-byte aligned rows of at least K / 32 = %d bytes (ldsa %lld, ldsw %lld)", who, at.of,
-                   K / 32, (long long)ldsa, (long long)ldsw);
-    P->SA = (const uint8_t*)sa, P->SW = (const uint8_t*)sw, P->ldsa = ldsa, P->ldsw = ldsw;
-    return 0;
-}
+// the e2m3 rules and wording of mx_check_problem (fp8_gemm_tile.h)
+constexpr Fp8Format X6_FORMAT{X6_KT, " (a K-tile is 96 bytes of e2m3 codes)", 1, ", code rows at least 3 K / 4 = %d bytes", "bytes", true,
+                              "output and bias 8-byte", 6};
 
 extern "C" int apexmi_gemm_mxfp6(const void* qa, int64_t lda, const void* sa, int64_t ldsa, const void* qw, int64_t ldw, const void* sw,
                                  int64_t ldsw, const void* bias, void* C, int64_t ldc, int M, int N, int K, int epilogue,
                                  const float* gate, const void* R, int64_t ldr, apexmi_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     const char* who = "gemm_mxfp6";
-    Mxfp6Gemm G{};
-    if (mxfp6_check_problem(who, -1, 0, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
+    MxGemm G{};
+    if (mx_check_problem(who, -1, 0, X6_FORMAT, qa, lda, sa, ldsa, qw, ldw, sw, ldsw, bias, C, ldc, M, N, K, epilogue, gate, R, ldr, &G)) return 1;
     G.clk = apexmi_clk_ptr();
     ApexmiProfScope prof(0, stream, 2.0 * M * N * (double)K, (0.75 + 1.0 / 32) * ((double)M + N) * K + 2.0 * (double)M * N);
-    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp6_kernel<decltype(epi)::value, Mxfp6Gemm>; }, G,
+    launch_by_epilogue(epilogue, [](auto epi) { return gemm_mxfp6_kernel<decltype(epi)::value, MxGemm>; }, G,
                        (unsigned)(G.tiles_m * G.tiles_n), X6_LDS, stream);
     return apexmi_check_launch(who);
 }

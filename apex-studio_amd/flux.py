@@ -465,7 +465,7 @@ class FluxTransformer2DModel(Fp8ResidentMixin, Fp4ComputeMixin, F32ResidualMixin
         the per-stream fp4 scratch; the streams of a grouped launch are row slices of both."""
         if quantised is not None:
             return quantised
-        qa, sa = ops._act_scratch_mxfp4(src.device, src.shape[0], src.shape[1])
+        qa, sa = ops._act_scratch_mx(ops._MXFP4, src.device, src.shape[0], src.shape[1])
         return ops.quant_blocks_mxfp4(src, out=qa, scale_out=sa)
 
     def _norm_rows(self, X, XN, rows, w_list, epilogue, *mod, fp4=False, **kw):

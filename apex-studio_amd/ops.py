@@ -5,6 +5,7 @@ libapex_mi355.so.  Every wrapper refuses CPU tensors: the product path has no fa
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import operator
 from typing import List, Optional, Sequence, Tuple
@@ -406,6 +407,22 @@ def _block_gemm_route(a: torch.Tensor, w_shape, out: Optional[torch.Tensor], epi
         and (max_row_stride is None or a.stride(0) <= max_row_stride)
 
 
+def _updown_route(route, record_of, n_mult: int, a_or_shape, w_up, w_down, epilogue_up: str, epilogue_down: str, out) -> bool:
+    """Whether the pair `h = gemm(a, w_up, epilogue=epilogue_up)` -> `gemm(h, w_down, out=out, epilogue=epilogue_down)` may keep `h`
+    in the MX form of `route` (`fp8_compute_route`, `mxfp4_route`) between the two launches.  Pure.  `a_or_shape`: the bf16 input
+    [M, K] of the up projection, or its shape.  True only when both launches take `route`, the up epilogue is bias or gelu and
+    N_up (read from the record `record_of(w_up)`) is a multiple of `n_mult`."""
+    a = a_or_shape if isinstance(a_or_shape, torch.Tensor) else torch.empty(tuple(a_or_shape), dtype=torch.bfloat16, device="meta")
+    f_up = record_of(w_up)
+    if epilogue_up not in ("bias", "gelu") or not route(a, f_up, None, epilogue_up):
+        return False
+    n_up = f_up.shape[0]
+    if n_up % n_mult != 0:
+        return False
+    h = torch.empty((a.shape[0], n_up), dtype=torch.bfloat16, device="meta")
+    return route(h, w_down, out, epilogue_down)
+
+
 def fp8_compute_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
     """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as quantise + `gemm_fp8`.  Pure: reads dtypes, shapes and strides
     only (CPU tensors are fine).  True only when ALL of these hold:
@@ -575,6 +592,32 @@ def _fp8_acts(a: torch.Tensor, quantised) -> Tuple[torch.Tensor, torch.Tensor]:
     return qa, sa
 
 
+def _norm_quant_operands(who: str, x, out, scale, shift, scale2, shift2, gamma, beta, told: bool = False) -> Tuple[int, int]:
+    """The operands the quantising norms (`ln_modulate_quant_fp8`, `ln_modulate_quant_mxfp4`) share: the rows `x` [M, C] (bf16 or
+    float32), the optional bf16 `out` of the same shape, the float32 modulation vectors and the bf16 affine vectors of C elements.
+    Returns (M, C).  `told`: a wrong shape of `x` (C % 128 and M >= 1 included) raises ApexMIError with a reason (what the fp4 form
+    does) instead of failing an assertion on its rank and rows."""
+    _req(x, None, who + ".x")
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise _l.ApexMIError(f"{who}.x: expected torch.bfloat16 or torch.float32, got {x.dtype}")
+    if told and (x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 128 != 0 or x.shape[0] < 1):
+        raise _l.ApexMIError(f"{who}.x: expected [M >= 1, C % 128 == 0] with contiguous rows, got {tuple(x.shape)}")
+    assert x.dim() == 2 and x.stride(1) == 1
+    M, Cc = x.shape
+    if out is not None:
+        _req(out, torch.bfloat16, who + ".out")
+        assert out.shape == (M, Cc) and out.stride(1) == 1
+    for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
+        if t is not None:
+            _req(t, torch.float32, f"{who}.{nm}")
+            assert t.is_contiguous() and t.numel() == Cc
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None:
+            _req(t, torch.bfloat16, f"{who}.{nm}")
+            assert t.is_contiguous() and t.numel() == Cc
+    return M, Cc
+
+
 def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
                           gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-6,
                           rms: bool = False, split: int = 0, scale2: Optional[torch.Tensor] = None,
@@ -586,11 +629,7 @@ def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
     (optional, bf16 [M, C], row stride free): also receives the normalised rows, bit-identical to `ln_modulate(x, ..., out=out)`;
     None = the bf16 rows are never stored (3 bytes per element moved instead of 7).  `codes` / `scale_out` default to the
     per-stream activation scratch of `gemm`'s fp8 route, valid until that stream's next fp8 GEMM or fused norm."""
-    _req(x, None, "ln_modulate_quant_fp8.x")
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise _l.ApexMIError(f"ln_modulate_quant_fp8.x: expected torch.bfloat16 or torch.float32, got {x.dtype}")
-    assert x.dim() == 2 and x.stride(1) == 1
-    M, Cc = x.shape
+    M, Cc = _norm_quant_operands("ln_modulate_quant_fp8", x, out, scale, shift, scale2, shift2, gamma, beta)
     if codes is None and scale_out is None:
         codes, scale_out = _act_scratch(x.device, M, Cc)
     if codes is None:
@@ -600,17 +639,6 @@ def ln_modulate_quant_fp8(x: torch.Tensor, scale: Optional[torch.Tensor] = None,
     _req(codes, torch.uint8, "ln_modulate_quant_fp8.codes")
     _req(scale_out, torch.float32, "ln_modulate_quant_fp8.scale_out")
     assert codes.shape == (M, Cc) and codes.stride(1) == 1 and scale_out.is_contiguous() and scale_out.numel() == M
-    if out is not None:
-        _req(out, torch.bfloat16, "ln_modulate_quant_fp8.out")
-        assert out.shape == (M, Cc) and out.stride(1) == 1
-    for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
-        if t is not None:
-            _req(t, torch.float32, "ln_modulate_quant_fp8." + nm)
-            assert t.is_contiguous() and t.numel() == Cc
-    for t, nm in ((gamma, "gamma"), (beta, "beta")):
-        if t is not None:
-            _req(t, torch.bfloat16, "ln_modulate_quant_fp8." + nm)
-            assert t.is_contiguous() and t.numel() == Cc
     rc = _l.load().apexmi_ln_modulate_quant_fp8(
         x.data_ptr(), x.stride(0), _l.F32 if x.dtype == torch.float32 else _l.BF16, _ptr(out), 0 if out is None else out.stride(0),
         codes.data_ptr(), codes.stride(0), scale_out.data_ptr(), M, Cc, _ptr(scale), _ptr(shift), _ptr(gamma), _ptr(beta),
@@ -735,8 +763,66 @@ def gemm_fp8(codes: torch.Tensor, scales: torch.Tensor, w: "Fp8Weight", bias: Op
     return out
 
 
-# ---- opt-in MXFP4 compute: e2m1 codes, two to a byte, one e8m0 scale byte per 32 consecutive k ---------------------
+# ---- opt-in MXFP4 / MXFP6 compute: packed e2m1 / e2m3 codes, one e8m0 scale byte per 32 consecutive k --------------
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)      # the magnitudes of the low three code bits; bit 3 is the sign
+# the magnitudes of the low five code bits (exp << 3 | man, bias 1; exp = 0 is man / 8); bit 5 is the sign
+E2M3_VALUES = tuple(m / 8 if e == 0 else (1 + m / 8) * 2.0 ** (e - 1) for e in range(4) for m in range(8))
+
+
+@dataclasses.dataclass(frozen=True)
+class _MxFormat:
+    """What differs, on the host side, between the MX formats whose two block scales the MFMA applies: one row per format, read
+    by the one quantiser body, pair check, weight record, route rule, activation scratch and GEMM wrapper below and by the loop
+    in `gemm`.  A new format is one row, its kernel and a record subclass."""
+    mode: str                    # the `compute` word of a record that routes
+    slot: str                    # the attribute of a weight tensor that carries its record
+    bits: int                    # of a code: a row of K codes (whole blocks of 32) is K bits / 8 bytes
+    k_mult: int                  # the K multiple of the GEMM route = the codes of one K-tile
+    mx_n_mult: Optional[int]     # the N multiple of an MX output (`out_mx`), or None: the GEMM has no MX-output entry point
+    values: tuple                # the magnitudes of the codes below the sign bit, which is the top one
+    quant: str                   # the public quantiser and GEMM wrapper.  `gemm` calls them by these names, as its callers do;
+    gemm: str                    # the library's entry points are "apexmi_" + name, the MX-output one + "_mx"
+    name: str                    # the words of the messages: the format,
+    record: str                  # its weight record
+    cols: str                    # and the bytes of a code row
+
+    def row_bytes(self, K: int) -> int:
+        return K * self.bits // 8
+
+    def k_of(self, nbytes: int) -> int:
+        return nbytes * 8 // self.bits
+
+
+_MXFP4 = _MxFormat("fp4", "_fp4", 4, 256, 128, E2M1_VALUES, "quant_blocks_mxfp4", "gemm_mxfp4", "MXFP4", "Mxfp4Weight", "K / 2")
+_MXFP6 = _MxFormat("fp6", "_fp6", 6, 128, None, E2M3_VALUES, "quant_blocks_mxfp6", "gemm_mxfp6", "MXFP6", "Mxfp6Weight", "3 K / 4")
+_MX_FORMATS = (_MXFP4, _MXFP6)      # the order `gemm` asks them in
+_MX_SLOTS = tuple((f.slot, f) for f in _MX_FORMATS)      # what `gemm` walks on every call: no attribute loads for a plain weight
+
+
+def _empty_mx_codes(fmt: _MxFormat, M: int, K: int, device) -> torch.Tensor:
+    """An unwritten codes buffer [M, K bits / 8] whose rows are padded to 16 bytes, the alignment the GEMMs ask of a code row"""
+    kb = fmt.row_bytes(K)
+    return torch.empty((M, (kb + 15) // 16 * 16), dtype=torch.uint8, device=device)[:, :kb]
+
+
+def _quant_blocks_mx(fmt: _MxFormat, a, out, scale_out) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`quant_blocks_mxfp4` / `quant_blocks_mxfp6`: the argument check, the default `out` (rows padded to 16 bytes), the pair check
+    and the launch."""
+    who = fmt.quant
+    if not isinstance(a, torch.Tensor) or a.dtype != torch.bfloat16:
+        raise _l.ApexMIError(f"{who}.a: expected a torch.bfloat16 tensor, got {getattr(a, 'dtype', type(a).__name__)}")
+    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 32 != 0 or a.shape[1] < 32 or a.shape[0] < 1:
+        raise _l.ApexMIError(f"{who}.a: expected [M >= 1, K % 32 == 0] with contiguous rows, got {tuple(a.shape)}")
+    M, K = a.shape
+    if out is None:
+        out = _empty_mx_codes(fmt, M, K, a.device)
+    if scale_out is None:
+        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
+    _check_mx_codes(fmt, who + ".out", out, scale_out, M, K)
+    _req(a, torch.bfloat16, who + ".a")
+    _l.check(getattr(_l.load(), "apexmi_" + who)(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
+                                                 scale_out.stride(0), _stream()), who)
+    return out, scale_out
 
 
 def quant_blocks_mxfp4(a: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -749,26 +835,26 @@ def quant_blocks_mxfp4(a: torch.Tensor, out: Optional[torch.Tensor] = None,
     2^e is the smallest power of two with amax / 2^e <= 6, so the clamp clips nothing; ties go to the even code (0.25 -> 0,
     0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4) and the sign bit of `a` is kept, also where the magnitude
     rounds to zero.  Inputs must be finite.  One launch; what `gemm_mxfp4` reads on both sides."""
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.bfloat16:
-        raise _l.ApexMIError(f"quant_blocks_mxfp4.a: expected a torch.bfloat16 tensor, got {getattr(a, 'dtype', type(a).__name__)}")
-    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 32 != 0 or a.shape[1] < 32 or a.shape[0] < 1:
-        raise _l.ApexMIError(f"quant_blocks_mxfp4.a: expected [M >= 1, K % 32 == 0] with contiguous rows, got {tuple(a.shape)}")
-    M, K = a.shape
-    if out is None:
-        out = torch.empty((M, (K // 2 + 15) // 16 * 16), dtype=torch.uint8, device=a.device)[:, :K // 2]
-    if scale_out is None:
-        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
-    _check_mxfp4_pair("quant_blocks_mxfp4.out", out, scale_out, M, K)
-    _req(a, torch.bfloat16, "quant_blocks_mxfp4.a")
-    _l.check(_l.load().apexmi_quant_blocks_mxfp4(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
-                                                 scale_out.stride(0), _stream()), "quant_blocks_mxfp4")
-    return out, scale_out
+    return _quant_blocks_mx(_MXFP4, a, out, scale_out)
 
 
-def _check_mxfp4_pair(who: str, q, s, M: int, K: int, on_device: bool = True) -> None:
-    """An MXFP4 (codes [M, K / 2], scales [M, K / 32]) pair, both uint8 tensors with contiguous rows: type and shape first, then
-    (what every launch asks) the device"""
-    for name, t, cols in (("codes", q, K // 2), ("scales", s, K // 32)):
+def quant_blocks_mxfp6(a: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """MXFP6 block quantisation of bf16 `a` [M, K] (row stride free, K % 32 == 0) -> (codes uint8 [M, 3 K / 4]: OCP e2m3, block b of a
+    row = bytes 24 b .. 24 b + 23, code j of the block = bits 6 j .. 6 j + 5 of those bytes as one little-endian integer; scales uint8
+    [M, K / 32] = e8m0 exponents; row strides free, code rows 8-byte aligned — 16 for `gemm_mxfp6`, which the default `out` has).  Per
+    block of 32 consecutive columns:
+        amax = max |a| with unbiased f32 exponent E and mantissa bits man;  e = clamp(E - 2 + (man > 0x700000), -126, 127)
+        (0 for a zero block);  scale byte = e + 127;  code = e2m3_rne(clamp(a * 2^-e, -7.5, 7.5))
+    2^e is the smallest power of two with amax / 2^e <= 7.5, so the clamp clips nothing; ties go to the even code and the sign bit of
+    `a` is kept, also where the magnitude rounds to zero.  Inputs must be finite.  One launch; what `gemm_mxfp6` reads on both sides."""
+    return _quant_blocks_mx(_MXFP6, a, out, scale_out)
+
+
+def _check_mx_codes(fmt: _MxFormat, who: str, q, s, M: int, K: int, on_device: bool = True) -> None:
+    """A (codes [M, K bits / 8], scales [M, K / 32]) pair of `fmt`, both uint8 tensors with contiguous rows: type and shape first,
+    then (what every launch asks) the device"""
+    for name, t, cols in (("codes", q, fmt.row_bytes(K)), ("scales", s, K // 32)):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
             raise _l.ApexMIError(f"{who}: the {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
         if t.dim() != 2 or tuple(t.shape) != (M, cols) or t.stride(1) != 1:
@@ -777,20 +863,31 @@ def _check_mxfp4_pair(who: str, q, s, M: int, K: int, on_device: bool = True) ->
             _req(t, torch.uint8, f"{who} ({name})")
 
 
-class Mxfp4Weight:
-    """An MXFP4 copy of a bf16 weight [N, K] for the opt-in fp4 compute: `q` uint8 [N, K / 2] e2m1 codes, `s` uint8 [N, K / 32]
-    e8m0 scale bytes, as `quant_blocks_mxfp4` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
-    sits beside it (on the weight tensor's `_fp4` slot, where `ops.gemm` looks); 0.53 bytes per weight element.  `compute`: "fp4"
-    (routed by `mxfp4_route`) or anything else (ignored)."""
+def _unpack_codes(fmt: _MxFormat, q: torch.Tensor) -> torch.Tensor:
+    """uint8 [R, K bits / 8] -> the codes int64 [R, K]: bit fields of one little-endian integer, in the smallest groups of whole
+    bytes that hold whole codes (e2m1: 2 codes a byte, e2m3: 4 codes per 3 bytes)"""
+    g = fmt.bits // math.gcd(fmt.bits, 8)
+    b = q.long().view(q.shape[0], -1, g)
+    v = sum(b[..., i] << 8 * i for i in range(g))
+    return torch.stack([(v >> sh) & ((1 << fmt.bits) - 1) for sh in range(0, 8 * g, fmt.bits)], dim=-1).view(q.shape[0], -1)
+
+
+class _MxWeight:
+    """An MX copy of a bf16 weight [N, K] in the format `fmt` of the subclass: `q` uint8 [N, K bits / 8] codes, `s` uint8 [N, K / 32]
+    e8m0 scale bytes, as the format's quantiser writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and the
+    record sits beside it, on the weight tensor's `fmt.slot`, where `ops.gemm` looks.  `compute`: `fmt.mode` (routed) or anything
+    else (ignored)."""
+    fmt: _MxFormat
 
     def __init__(self, q: torch.Tensor, s: torch.Tensor):
-        N, K = q.shape[0], 2 * q.shape[1]
-        _check_mxfp4_pair("Mxfp4Weight", q, s, N, K, on_device=False)      # a CPU record can still be asked for its route
-        self.q, self.s, self.shape, self.compute = q, s, (N, K), "fp4"
+        fmt = self.fmt
+        N, K = q.shape[0], fmt.k_of(q.shape[1])
+        _check_mx_codes(fmt, fmt.record, q, s, N, K, on_device=False)      # a CPU record can still be asked for its route
+        self.q, self.s, self.shape, self.compute = q, s, (N, K), fmt.mode
 
     @classmethod
-    def from_bf16(cls, w: torch.Tensor) -> "Mxfp4Weight":
-        return cls(*quant_blocks_mxfp4(w))
+    def from_bf16(cls, w: torch.Tensor):
+        return cls(*globals()[cls.fmt.quant](w))
 
     @property
     def device(self):
@@ -800,23 +897,56 @@ class Mxfp4Weight:
         return self.q.numel() + self.s.numel()
 
     def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """bf16 [N, K] = value(code) x 2^(scale byte - 127): exact in bf16 (one mantissa bit times a power of two) unless 4 or 6 x 2^126
-        overflows, which only a block holding values above 2^127 produces.  Plain torch: test and tool support, not a hot path."""
-        N, K = self.shape
-        lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=self.q.device)
-        q = self.q.long()
-        v = torch.stack([lut[q & 15], lut[q >> 4]], dim=-1).view(N, K // 32, 32)
+        """bf16 [N, K] = value(code) x 2^(scale byte - 127): exact in bf16 (at most four significant bits times a power of two) unless
+        it overflows, which only a block holding values above 2^127 produces.  Plain torch: test and tool support, not a hot path."""
+        fmt, (N, K) = self.fmt, self.shape
+        lut = torch.tensor(fmt.values + tuple(-v for v in fmt.values), dtype=torch.float32, device=self.q.device)
+        v = lut[_unpack_codes(fmt, self.q)].view(N, K // 32, 32)
         v = (v * torch.exp2(self.s.float() - 127.0).unsqueeze(-1)).view(N, K).to(torch.bfloat16)
         if out is None:
             return v
-        _req(out, torch.bfloat16, "Mxfp4Weight.dequant.out")
+        _req(out, torch.bfloat16, fmt.record + ".dequant.out")
         out.copy_(v)
         return out
 
 
-def _fp4_of(w):
-    """The MXFP4 record behind `w` (an Mxfp4Weight, or a weight tensor carrying one in `_fp4`), or None."""
-    return w if isinstance(w, Mxfp4Weight) else getattr(w, "_fp4", None)
+class Mxfp4Weight(_MxWeight):
+    """An MXFP4 copy of a bf16 weight [N, K] for the opt-in fp4 compute: `q` uint8 [N, K / 2] e2m1 codes, `s` uint8 [N, K / 32]
+    e8m0 scale bytes, as `quant_blocks_mxfp4` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
+    sits beside it (on the weight tensor's `_fp4` slot, where `ops.gemm` looks); 0.53 bytes per weight element.  `compute`: "fp4"
+    (routed by `mxfp4_route`) or anything else (ignored)."""
+    fmt = _MXFP4
+
+
+class Mxfp6Weight(_MxWeight):
+    """An MXFP6 copy of a bf16 weight [N, K] for the opt-in fp6 compute: `q` uint8 [N, 3 K / 4] e2m3 codes, `s` uint8 [N, K / 32]
+    e8m0 scale bytes, as `quant_blocks_mxfp6` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
+    sits beside it (on the weight tensor's `_fp6` slot, where `ops.gemm` looks); 0.78 bytes per weight element.  `compute`: "fp6"
+    (routed by `mxfp6_route`) or anything else (ignored)."""
+    fmt = _MXFP6
+
+    def __init__(self, q: torch.Tensor, s: torch.Tensor):
+        if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] % 24 != 0:
+            raise _l.ApexMIError(f"Mxfp6Weight: the codes must be a uint8 [N, 3 K / 4] tensor of whole 24-byte blocks, got "
+                                 f"{tuple(getattr(q, 'shape', ()))}")
+        super().__init__(q, s)
+
+
+def _mx_of(fmt: _MxFormat, w):
+    """The record of `fmt` behind `w` (the record itself, or a weight tensor carrying one in `fmt.slot`), or None."""
+    return w if isinstance(w, _MxWeight) and w.fmt is fmt else getattr(w, fmt.slot, None)
+
+
+def _mxfp4_of(w):
+    return _mx_of(_MXFP4, w)
+
+
+def _mx_route(fmt: _MxFormat, a: torch.Tensor, w, out: Optional[torch.Tensor], epilogue: str) -> bool:
+    """`mxfp4_route` / `mxfp6_route`: a record of `fmt` that is switched on, and the shared shape rules with the format's K-tile."""
+    f = _mx_of(fmt, w)
+    if not isinstance(f, _MxWeight) or f.fmt is not fmt or f.compute != fmt.mode:
+        return False
+    return _block_gemm_route(a, f.shape, out, epilogue, fmt.k_mult)
 
 
 def mxfp4_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
@@ -827,34 +957,75 @@ def mxfp4_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue
         stream keep the bf16 path);
       * the shape is eligible: M >= 1, K % 256 == 0, N % 16 == 0, 16-byte rows of `a`, and the epilogue is one of bias / gelu /
         gate_res."""
-    f4 = _fp4_of(w)
-    if not isinstance(f4, Mxfp4Weight) or f4.compute != "fp4":
-        return False
-    return _block_gemm_route(a, f4.shape, out, epilogue, 256)
+    return _mx_route(_MXFP4, a, w, out, epilogue)
 
 
-_fp4_act_scratch: dict = {}
+def mxfp6_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
+    """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as `quant_blocks_mxfp6` + `gemm_mxfp6`.  Pure: reads dtypes, shapes
+    and strides only (CPU and meta tensors are fine).  True only when ALL of these hold:
+      * `w` is (or carries in `_fp6`) an `Mxfp6Weight` with `compute == "fp6"`;
+      * `a` is bf16 and `out` is bf16 or None (float activations = the f32-storage mode and a float `out` = the f32 residual
+        stream keep the bf16 path);
+      * the shape is eligible: M >= 1, K % 128 == 0, N % 16 == 0, 16-byte rows of `a`, and the epilogue is one of bias / gelu /
+        gate_res."""
+    return _mx_route(_MXFP6, a, w, out, epilogue)
 
 
-def _act_scratch_mxfp4(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-stream home of the activation's MXFP4 codes [M, K / 2] and scale bytes [M, K / 32] (as `_act_scratch`)."""
-    q, s = _stream_scratch(_fp4_act_scratch, dev, (M * (K // 2), torch.uint8), (M * (K // 32), torch.uint8))
-    return q[:M * (K // 2)].view(M, K // 2), s[:M * (K // 32)].view(M, K // 32)
+_mx_act_scratch: dict = {}      # fmt.mode -> a store of `_stream_scratch`: the formats do not overwrite each other
 
 
-def _mxfp4_out_mx(who: str, out_mx, M: int, N: int, epilogue: str):
-    """The `out_mx` pair of one [M, N] problem of `gemm_mxfp4` / `gemm_mxfp4_grouped(_qkv)`: (codes uint8 [M, N / 2], scales uint8
-    [M, N / 32]), bias or gelu, N % 128 == 0.  Returns the pair."""
+def _act_scratch_mx(fmt: _MxFormat, dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-stream home of the activation's codes [M, K bits / 8] and scale bytes [M, K / 32] in `fmt` (as `_act_scratch`)."""
+    kb, nb = fmt.row_bytes(K), K // 32
+    q, s = _stream_scratch(_mx_act_scratch.setdefault(fmt.mode, {}), dev, (M * kb, torch.uint8), (M * nb, torch.uint8))
+    return q[:M * kb].view(M, kb), s[:M * nb].view(M, nb)
+
+
+def _mx_out_mx(fmt: _MxFormat, who: str, out_mx, M: int, N: int, epilogue: str):
+    """The `out_mx` pair of one [M, N] problem of `gemm_mxfp4` / `gemm_mxfp4_grouped(_qkv)`: (codes uint8 [M, N bits / 8], scales
+    uint8 [M, N / 32]), bias or gelu, N a multiple of `fmt.mx_n_mult`.  Returns the pair."""
     try:
         mq, ms = out_mx
     except (TypeError, ValueError):
         raise _l.ApexMIError(f"{who}: out_mx: expected a (codes, scales) pair") from None
     if epilogue not in ("bias", "gelu"):
         raise _l.ApexMIError(f"{who}: out_mx exists for the bias and gelu epilogues, not '{epilogue}'")
-    if N % 128 != 0:
-        raise _l.ApexMIError(f"{who}: out_mx needs N % 128 == 0, got N={N}")
-    _check_mxfp4_pair(who + ".out_mx", mq, ms, M, N)
+    if N % fmt.mx_n_mult != 0:
+        raise _l.ApexMIError(f"{who}: out_mx needs N % {fmt.mx_n_mult} == 0, got N={N}")
+    _check_mx_codes(fmt, who + ".out_mx", mq, ms, M, N)
     return mq, ms
+
+
+def _gemm_mx(fmt: _MxFormat, codes, scales, w, bias, out, epilogue: str, gate, residual, out_mx=None):
+    """`gemm_mxfp4` / `gemm_mxfp6`: one launch of the format's GEMM, or of its MX-output entry point with `out_mx`."""
+    who = fmt.gemm
+    if out_mx is not None and fmt.mx_n_mult is None:
+        raise _l.ApexMIError(f"{who}: out_mx: the {fmt.name} GEMM has no epilogue that quantises its own output (there is no "
+                             f"apexmi_{who}_mx entry point)")
+    if not isinstance(w, _MxWeight) or w.fmt is not fmt:
+        raise _l.ApexMIError(f"{who}: expected an {fmt.record}, got {type(w).__name__}")
+    if epilogue not in _FP8_EPI:
+        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2:
+        raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, {fmt.cols}] tensor, got {type(codes).__name__}")
+    M, (N, K) = codes.shape[0], w.shape
+    _check_mx_codes(fmt, who, codes, scales, M, K)
+    if out_mx is not None:
+        mq, ms = _mx_out_mx(fmt, who, out_mx, M, N, epilogue)
+        _epilogue_operands(who, M, N, codes.device, bias, None, epilogue, None, None, fused=True, told=True)
+    else:
+        out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
+    operands = (codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(), w.q.stride(0), w.s.data_ptr(),
+                w.s.stride(0), _ptr(bias))
+    if out_mx is not None:
+        rc = getattr(_l.load(), f"apexmi_{who}_mx")(*operands, None, 0, mq.data_ptr(), mq.stride(0), ms.data_ptr(), ms.stride(0), M, N, K,
+                                                    _EPI[epilogue], None, None, 0, _stream())
+        _l.check(rc, who + "_mx")
+        return mq, ms
+    rc = getattr(_l.load(), "apexmi_" + who)(*operands, out.data_ptr(), out.stride(0), M, N, K, _EPI[epilogue] | flag, _ptr(gate),
+                                             _ptr(residual), residual.stride(0) if epilogue == "gate_res" else 0, _stream())
+    _l.check(rc, who)
+    return out
 
 
 def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias: Optional[torch.Tensor] = None,
@@ -868,30 +1039,17 @@ def gemm_mxfp4(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp4Weight", bias
     `out_mx=(codes_out uint8 [M, N / 2], scales_out uint8 [M, N / 32])` (bias / gelu, N % 128 == 0; row strides free, multiples of
     4): the launch quantises its own output in the epilogue and writes those instead of `out` (which is ignored); bit-identical
     to the bf16 launch followed by `quant_blocks_mxfp4`.  Returns the pair."""
-    who = "gemm_mxfp4"
-    if not isinstance(w, Mxfp4Weight):
-        raise _l.ApexMIError(f"{who}: expected an Mxfp4Weight, got {type(w).__name__}")
-    if epilogue not in _FP8_EPI:
-        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
-    if not isinstance(codes, torch.Tensor) or codes.dim() != 2:
-        raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(codes).__name__}")
-    M, (N, K) = codes.shape[0], w.shape
-    _check_mxfp4_pair(who, codes, scales, M, K)
-    if out_mx is not None:
-        mq, ms = _mxfp4_out_mx(who, out_mx, M, N, epilogue)
-        _epilogue_operands(who, M, N, codes.device, bias, None, epilogue, None, None, fused=True, told=True)
-        rc = _l.load().apexmi_gemm_mxfp4_mx(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
-                                            w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), None, 0, mq.data_ptr(),
-                                            mq.stride(0), ms.data_ptr(), ms.stride(0), M, N, K, _EPI[epilogue], None, None, 0, _stream())
-        _l.check(rc, "gemm_mxfp4_mx")
-        return mq, ms
-    out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
-    rc = _l.load().apexmi_gemm_mxfp4(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
-                                     w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
-                                     _EPI[epilogue] | flag, _ptr(gate), _ptr(residual),
-                                     residual.stride(0) if epilogue == "gate_res" else 0, _stream())
-    _l.check(rc, who)
-    return out
+    return _gemm_mx(_MXFP4, codes, scales, w, bias, out, epilogue, gate, residual, out_mx)
+
+
+def gemm_mxfp6(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp6Weight", bias: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
+               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] (bf16) = epi(sum_k value(codes[m, k]) 2^(scales[m, k / 32] - 127) value(w.q[n, k]) 2^(w.s[n, k / 32] - 127) + bias):
+    e2m3 x e2m3 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, one bf16 rounding.  `codes` /
+    `scales` as `quant_blocks_mxfp6` returns them; `w` an `Mxfp6Weight`; epilogue bias / gelu / gate_res (`residual` may be `out`).
+    K % 128 == 0, N % 16 == 0."""
+    return _gemm_mx(_MXFP6, codes, scales, w, bias, out, epilogue, gate, residual)
 
 
 def mxfp4_norm_quant_route(x: torch.Tensor, xn: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
@@ -912,15 +1070,7 @@ def mxfp4_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue
     True only when BOTH weights carry fp4 records and take `mxfp4_route`, the up epilogue is bias or gelu, N_up % 256 == 0 (the
     down launch's K-tile rule, which includes the MX output's N % 128 == 0), and `out` (the down projection's output and, for
     gate_res, its residual) is bf16 or None."""
-    a = a_or_shape if isinstance(a_or_shape, torch.Tensor) else torch.empty(tuple(a_or_shape), dtype=torch.bfloat16, device="meta")
-    f_up = _fp4_of(w_up)
-    if epilogue_up not in ("bias", "gelu") or not mxfp4_route(a, f_up, None, epilogue_up):
-        return False
-    n_up = f_up.shape[0]
-    if n_up % 256 != 0:
-        return False
-    h = torch.empty((a.shape[0], n_up), dtype=torch.bfloat16, device="meta")
-    return mxfp4_route(h, w_down, out, epilogue_down)
+    return _updown_route(mxfp4_route, _mxfp4_of, 256, a_or_shape, w_up, w_down, epilogue_up, epilogue_down, out)
 
 
 def ln_modulate_quant_mxfp4(x: torch.Tensor, scale: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
@@ -935,179 +1085,20 @@ def ln_modulate_quant_mxfp4(x: torch.Tensor, scale: Optional[torch.Tensor] = Non
     out=out)`; None = the bf16 rows are never stored.  `codes` / `scale_out` (row strides free, code rows 16-byte aligned) default
     to the per-stream activation scratch of `gemm`'s fp4 route, valid until that stream's next fp4 GEMM or fused norm."""
     who = "ln_modulate_quant_mxfp4"
-    _req(x, None, who + ".x")
-    if x.dtype not in (torch.bfloat16, torch.float32):
-        raise _l.ApexMIError(f"{who}.x: expected torch.bfloat16 or torch.float32, got {x.dtype}")
-    if x.dim() != 2 or x.stride(1) != 1 or x.shape[1] % 128 != 0 or x.shape[0] < 1:
-        raise _l.ApexMIError(f"{who}.x: expected [M >= 1, C % 128 == 0] with contiguous rows, got {tuple(x.shape)}")
-    M, Cc = x.shape
+    M, Cc = _norm_quant_operands(who, x, out, scale, shift, scale2, shift2, gamma, beta, told=True)
     if codes is None and scale_out is None:
-        codes, scale_out = _act_scratch_mxfp4(x.device, M, Cc)
+        codes, scale_out = _act_scratch_mx(_MXFP4, x.device, M, Cc)
     if codes is None:
-        codes = torch.empty((M, (Cc // 2 + 15) // 16 * 16), dtype=torch.uint8, device=x.device)[:, :Cc // 2]
+        codes = _empty_mx_codes(_MXFP4, M, Cc, x.device)
     if scale_out is None:
         scale_out = torch.empty((M, Cc // 32), dtype=torch.uint8, device=x.device)
-    _check_mxfp4_pair(who + ".codes", codes, scale_out, M, Cc)
-    if out is not None:
-        _req(out, torch.bfloat16, who + ".out")
-        assert out.shape == (M, Cc) and out.stride(1) == 1
-    for t, nm in ((scale, "scale"), (shift, "shift"), (scale2, "scale2"), (shift2, "shift2")):
-        if t is not None:
-            _req(t, torch.float32, f"{who}.{nm}")
-            assert t.is_contiguous() and t.numel() == Cc
-    for t, nm in ((gamma, "gamma"), (beta, "beta")):
-        if t is not None:
-            _req(t, torch.bfloat16, f"{who}.{nm}")
-            assert t.is_contiguous() and t.numel() == Cc
+    _check_mx_codes(_MXFP4, who + ".codes", codes, scale_out, M, Cc)
     rc = _l.load().apexmi_ln_modulate_quant_mxfp4(
         x.data_ptr(), x.stride(0), _l.F32 if x.dtype == torch.float32 else _l.BF16, _ptr(out), 0 if out is None else out.stride(0),
         codes.data_ptr(), codes.stride(0), scale_out.data_ptr(), scale_out.stride(0), M, Cc, _ptr(scale), _ptr(shift), _ptr(gamma),
         _ptr(beta), float(eps), 1 if rms else 0, int(split), _ptr(scale2), _ptr(shift2), _stream())
     _l.check(rc, who)
     return codes, scale_out
-
-
-# ---- opt-in MXFP6 compute (DESIGN.md §3.6): e2m3 codes, 32 to 24 bytes, one e8m0 scale byte per 32 consecutive k ---------------------
-# the magnitudes of the low five code bits (exp << 3 | man, bias 1; exp = 0 is man / 8); bit 5 is the sign
-E2M3_VALUES = tuple(m / 8 if e == 0 else (1 + m / 8) * 2.0 ** (e - 1) for e in range(4) for m in range(8))
-
-
-def quant_blocks_mxfp6(a: torch.Tensor, out: Optional[torch.Tensor] = None,
-                       scale_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """MXFP6 block quantisation of bf16 `a` [M, K] (row stride free, K % 32 == 0) -> (codes uint8 [M, 3 K / 4]: OCP e2m3, block b of a
-    row = bytes 24 b .. 24 b + 23, code j of the block = bits 6 j .. 6 j + 5 of those bytes as one little-endian integer; scales uint8
-    [M, K / 32] = e8m0 exponents; row strides free, code rows 8-byte aligned — 16 for `gemm_mxfp6`, which the default `out` has).  Per
-    block of 32 consecutive columns:
-        amax = max |a| with unbiased f32 exponent E and mantissa bits man;  e = clamp(E - 2 + (man > 0x700000), -126, 127)
-        (0 for a zero block);  scale byte = e + 127;  code = e2m3_rne(clamp(a * 2^-e, -7.5, 7.5))
-    2^e is the smallest power of two with amax / 2^e <= 7.5, so the clamp clips nothing; ties go to the even code and the sign bit of
-    `a` is kept, also where the magnitude rounds to zero.  Inputs must be finite.  One launch; what `gemm_mxfp6` reads on both sides."""
-    if not isinstance(a, torch.Tensor) or a.dtype != torch.bfloat16:
-        raise _l.ApexMIError(f"quant_blocks_mxfp6.a: expected a torch.bfloat16 tensor, got {getattr(a, 'dtype', type(a).__name__)}")
-    if a.dim() != 2 or a.stride(1) != 1 or a.shape[1] % 32 != 0 or a.shape[1] < 32 or a.shape[0] < 1:
-        raise _l.ApexMIError(f"quant_blocks_mxfp6.a: expected [M >= 1, K % 32 == 0] with contiguous rows, got {tuple(a.shape)}")
-    M, K = a.shape
-    kb = K // 4 * 3
-    if out is None:
-        out = torch.empty((M, (kb + 15) // 16 * 16), dtype=torch.uint8, device=a.device)[:, :kb]
-    if scale_out is None:
-        scale_out = torch.empty((M, K // 32), dtype=torch.uint8, device=a.device)
-    _check_mxfp6_pair("quant_blocks_mxfp6.out", out, scale_out, M, K)
-    _req(a, torch.bfloat16, "quant_blocks_mxfp6.a")
-    _l.check(_l.load().apexmi_quant_blocks_mxfp6(a.data_ptr(), a.stride(0), M, K, out.data_ptr(), out.stride(0), scale_out.data_ptr(),
-                                                 scale_out.stride(0), _stream()), "quant_blocks_mxfp6")
-    return out, scale_out
-
-
-def _check_mxfp6_pair(who: str, q, s, M: int, K: int, on_device: bool = True) -> None:
-    """An MXFP6 (codes [M, 3 K / 4], scales [M, K / 32]) pair, as `_check_mxfp4_pair`"""
-    for name, t, cols in (("codes", q, K // 4 * 3), ("scales", s, K // 32)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
-            raise _l.ApexMIError(f"{who}: the {name} must be a torch.uint8 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-        if t.dim() != 2 or tuple(t.shape) != (M, cols) or t.stride(1) != 1:
-            raise _l.ApexMIError(f"{who}: the {name} must be [{M}, {cols}] with contiguous rows (K = {K}), got {tuple(t.shape)}")
-        if on_device:
-            _req(t, torch.uint8, f"{who} ({name})")
-
-
-def _unpack_e2m3(q: torch.Tensor) -> torch.Tensor:
-    """uint8 [R, 3 K / 4] -> the 6-bit codes int64 [R, K]: 4 codes per 3 bytes, little-endian"""
-    b = q.long().view(q.shape[0], -1, 3)
-    v = b[..., 0] | b[..., 1] << 8 | b[..., 2] << 16
-    return torch.stack([(v >> s) & 63 for s in (0, 6, 12, 18)], dim=-1).view(q.shape[0], -1)
-
-
-class Mxfp6Weight:
-    """An MXFP6 copy of a bf16 weight [N, K] for the opt-in fp6 compute: `q` uint8 [N, 3 K / 4] e2m3 codes, `s` uint8 [N, K / 32]
-    e8m0 scale bytes, as `quant_blocks_mxfp6` writes them.  NOT a ResidentWeight: the bf16 weight stays where it is and this record
-    sits beside it (on the weight tensor's `_fp6` slot, where `ops.gemm` looks); 0.78 bytes per weight element.  `compute`: "fp6"
-    (routed by `mxfp6_route`) or anything else (ignored)."""
-
-    def __init__(self, q: torch.Tensor, s: torch.Tensor):
-        if not isinstance(q, torch.Tensor) or q.dim() != 2 or q.shape[1] % 24 != 0:
-            raise _l.ApexMIError(f"Mxfp6Weight: the codes must be a uint8 [N, 3 K / 4] tensor of whole 24-byte blocks, got "
-                                 f"{tuple(getattr(q, 'shape', ()))}")
-        N, K = q.shape[0], q.shape[1] // 3 * 4
-        _check_mxfp6_pair("Mxfp6Weight", q, s, N, K, on_device=False)      # a CPU record can still be asked for its route
-        self.q, self.s, self.shape, self.compute = q, s, (N, K), "fp6"
-
-    @classmethod
-    def from_bf16(cls, w: torch.Tensor) -> "Mxfp6Weight":
-        return cls(*quant_blocks_mxfp6(w))
-
-    @property
-    def device(self):
-        return self.q.device
-
-    def nbytes(self) -> int:
-        return self.q.numel() + self.s.numel()
-
-    def dequant(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """bf16 [N, K] = value(code) x 2^(scale byte - 127): exact in bf16 (four significant bits times a power of two) unless it
-        overflows, which only a block holding values above 2^127 produces.  Plain torch: test and tool support, not a hot path."""
-        N, K = self.shape
-        lut = torch.tensor(E2M3_VALUES + tuple(-v for v in E2M3_VALUES), dtype=torch.float32, device=self.q.device)
-        v = lut[_unpack_e2m3(self.q)].view(N, K // 32, 32)
-        v = (v * torch.exp2(self.s.float() - 127.0).unsqueeze(-1)).view(N, K).to(torch.bfloat16)
-        if out is None:
-            return v
-        _req(out, torch.bfloat16, "Mxfp6Weight.dequant.out")
-        out.copy_(v)
-        return out
-
-
-def _fp6_of(w):
-    """The MXFP6 record behind `w` (an Mxfp6Weight, or a weight tensor carrying one in `_fp6`), or None."""
-    return w if isinstance(w, Mxfp6Weight) else getattr(w, "_fp6", None)
-
-
-def mxfp6_route(a: torch.Tensor, w, out: Optional[torch.Tensor] = None, epilogue: str = "bias") -> bool:
-    """Whether `gemm(a, w, out=out, epilogue=epilogue)` goes out as `quant_blocks_mxfp6` + `gemm_mxfp6`.  Pure: reads dtypes, shapes
-    and strides only (CPU and meta tensors are fine).  True only when ALL of these hold:
-      * `w` is (or carries in `_fp6`) an `Mxfp6Weight` with `compute == "fp6"`;
-      * `a` is bf16 and `out` is bf16 or None (float activations = the f32-storage mode and a float `out` = the f32 residual
-        stream keep the bf16 path);
-      * the shape is eligible: M >= 1, K % 128 == 0, N % 16 == 0, 16-byte rows of `a`, and the epilogue is one of bias / gelu /
-        gate_res."""
-    f6 = _fp6_of(w)
-    if not isinstance(f6, Mxfp6Weight) or f6.compute != "fp6":
-        return False
-    return _block_gemm_route(a, f6.shape, out, epilogue, 128)
-
-
-_fp6_act_scratch: dict = {}
-
-
-def _act_scratch_mxfp6(dev, M: int, K: int) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Per-stream home of the activation's MXFP6 codes [M, 3 K / 4] and scale bytes [M, K / 32] (as `_act_scratch`)."""
-    kb = K // 4 * 3
-    q, s = _stream_scratch(_fp6_act_scratch, dev, (M * kb, torch.uint8), (M * (K // 32), torch.uint8))
-    return q[:M * kb].view(M, kb), s[:M * (K // 32)].view(M, K // 32)
-
-
-def gemm_mxfp6(codes: torch.Tensor, scales: torch.Tensor, w: "Mxfp6Weight", bias: Optional[torch.Tensor] = None,
-               out: Optional[torch.Tensor] = None, epilogue: str = "bias", gate: Optional[torch.Tensor] = None,
-               residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[M, N] (bf16) = epi(sum_k value(codes[m, k]) 2^(scales[m, k / 32] - 127) value(w.q[n, k]) 2^(w.s[n, k / 32] - 127) + bias):
-    e2m3 x e2m3 on the block-scaled MFMA, which applies both scale bytes; f32 accumulation, one bf16 rounding.  `codes` /
-    `scales` as `quant_blocks_mxfp6` returns them; `w` an `Mxfp6Weight`; epilogue bias / gelu / gate_res (`residual` may be `out`).
-    K % 128 == 0, N % 16 == 0."""
-    who = "gemm_mxfp6"
-    if not isinstance(w, Mxfp6Weight):
-        raise _l.ApexMIError(f"{who}: expected an Mxfp6Weight, got {type(w).__name__}")
-    if epilogue not in _FP8_EPI:
-        raise _l.ApexMIError(f"{who}: epilogue '{epilogue}' is not one of {_FP8_EPI}")
-    if not isinstance(codes, torch.Tensor) or codes.dim() != 2:
-        raise _l.ApexMIError(f"{who}: null operand: `codes` must be a uint8 [M, 3 K / 4] tensor, got {type(codes).__name__}")
-    M, (N, K) = codes.shape[0], w.shape
-    _check_mxfp6_pair(who, codes, scales, M, K)
-    out, flag = _epilogue_operands(who, M, N, codes.device, bias, out, epilogue, gate, residual, alloc=True, told=True)
-    rc = _l.load().apexmi_gemm_mxfp6(codes.data_ptr(), codes.stride(0), scales.data_ptr(), scales.stride(0), w.q.data_ptr(),
-                                     w.q.stride(0), w.s.data_ptr(), w.s.stride(0), _ptr(bias), out.data_ptr(), out.stride(0), M, N, K,
-                                     _EPI[epilogue] | flag, _ptr(gate), _ptr(residual),
-                                     residual.stride(0) if epilogue == "gate_res" else 0, _stream())
-    _l.check(rc, who)
-    return out
 
 
 FP8_MAX_GROUPS = 4
@@ -1158,7 +1149,7 @@ def mxfp4_grouped_mx_route(a_list, w_up_list, w_down_list, epilogues_up="gelu", 
         return False
     if not all(mxfp4_mx_route(a, wu, wd, e1, e2, o) for a, wu, wd, e1, e2, o in zip(a_list, w_up_list, w_down_list, eu, ed, outs)):
         return False
-    hs = [torch.empty((a.shape[0], _fp4_of(wu).shape[0]), dtype=torch.bfloat16, device="meta") for a, wu in zip(a_list, w_up_list)]
+    hs = [torch.empty((a.shape[0], _mxfp4_of(wu).shape[0]), dtype=torch.bfloat16, device="meta") for a, wu in zip(a_list, w_up_list)]
     return mxfp4_grouped_route(hs, w_down_list, outs, ed)
 
 
@@ -1192,15 +1183,7 @@ def fp8_mx_route(a_or_shape, w_up, w_down, epilogue_up: str = "gelu", epilogue_d
     (dtypes, shapes and strides; CPU tensors are fine).  `a_or_shape`: the bf16 input [M, K] of the up projection, or its shape.
     True only when BOTH Linears take `fp8_compute_route` (so neither record carries run-time LoRA factors), N_up % 128 == 0, the
     up epilogue is bias or gelu, and `out` (the down projection's output and, for gate_res, its residual) is bf16 or None."""
-    a = a_or_shape if isinstance(a_or_shape, torch.Tensor) else torch.empty(tuple(a_or_shape), dtype=torch.bfloat16, device="meta")
-    f_up = _fp8_of(w_up)
-    if epilogue_up not in ("bias", "gelu") or not fp8_compute_route(a, f_up, None, epilogue_up):
-        return False
-    n_up = f_up.shape[0]
-    if n_up % 128 != 0:
-        return False
-    h = torch.empty((a.shape[0], n_up), dtype=torch.bfloat16, device="meta")
-    return fp8_compute_route(h, w_down, out, epilogue_down)
+    return _updown_route(fp8_compute_route, _fp8_of, 128, a_or_shape, w_up, w_down, epilogue_up, epilogue_down, out)
 
 
 def fp8_grouped_tiles(shapes):
@@ -1321,6 +1304,38 @@ def gemm_fp8_grouped(codes_list, scales_list, w_list, bias_list, out_list, epilo
     _l.check(_l.load().apexmi_gemm_fp8_grouped(*args, _stream()), "gemm_fp8_grouped")
 
 
+def _qkv_tail_args(who: str, n: int, is_qkv, norm_q, norm_k, row0, H: int, eps: float, rope, qo, ko, vt, told: bool = False) -> tuple:
+    """The fused-q/k/v tail of the arguments of `gemm_fp8_grouped_qkv` / `gemm_mxfp4_grouped_qkv` (n problems) after its checks:
+    contiguous bf16 qo / ko [H, S_out, 128] and vt [H, 128, Skp], the float32 rope table [2, S_out, 128], bf16 norm weights of 128.
+    `told`: a missing output or table and wrong shapes raise ApexMIError with a reason (what the fp4 form does) instead of failing
+    an assertion."""
+    import ctypes as C
+    for name, t_ in (("qo", qo), ("ko", ko), ("vt", vt)):
+        if told and not isinstance(t_, torch.Tensor):
+            raise _l.ApexMIError(f"{who}: null q/k/v output `{name}`")
+        _req(t_, torch.bfloat16, f"{who} output {name}" if told else f"{who} output")
+    if told and not isinstance(rope, torch.Tensor):
+        raise _l.ApexMIError(f"{who}: null rope table")
+    _req(rope, torch.float32, f"{who}.rope")
+    S_out = qo.shape[1]
+    fits = qo.is_contiguous() and ko.is_contiguous() and vt.is_contiguous() and rope.is_contiguous() \
+        and tuple(qo.shape) == tuple(ko.shape) == (H, S_out, 128) and vt.dim() == 3 and tuple(vt.shape[:2]) == (H, 128) \
+        and tuple(rope.shape) == (2, S_out, 128)
+    if told and not fits:
+        raise _l.ApexMIError(f"{who}: expected contiguous qo / ko [{H}, S_out, 128], vt [{H}, 128, Skp] and rope [2, S_out, 128], got "
+                             f"{tuple(qo.shape)}, {tuple(ko.shape)}, {tuple(vt.shape)}, {tuple(rope.shape)}")
+    assert fits
+    none = [None] * n
+    for t_ in list(norm_q or none) + list(norm_k or none):
+        if t_ is not None:
+            _req(t_, torch.bfloat16, f"{who} norm weight")
+            assert t_.is_contiguous() and t_.numel() == 128
+    VP, INT = C.c_void_p * n, C.c_int * n
+    return (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
+            VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
+            ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+
+
 def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, epilogue, is_qkv, norm_q, norm_k, row0, H: int,
                          eps: float, rope: torch.Tensor, qo: torch.Tensor, ko: torch.Tensor, vt: torch.Tensor,
                          block_scales_list=None, out_mx_list=None, lora_t_list=None, lora_B_list=None) -> None:
@@ -1331,7 +1346,6 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
 
     `lora_t_list` / `lora_B_list`: as in `gemm_fp8_grouped` (a fused problem takes the block-diagonal B' of its q | k | v parts);
     bit-identical to gemm_fp8_grouped(lora_t_list=, lora_B_list=) + qkv_prepare."""
-    import ctypes as C
     lora = lora_t_list is not None or lora_B_list is not None
     if block_scales_list is not None or out_mx_list is not None:
         raise _l.ApexMIError("gemm_fp8_grouped_qkv: the fused q/k/v epilogue takes per-row scales and writes bf16: "
@@ -1339,22 +1353,7 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
     n = len(codes_list)
     args = _fp8_grouped_args("gemm_fp8_grouped_qkv", codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
                              fused=[1 if f else 0 for f in is_qkv])
-    for t_ in (qo, ko, vt):
-        _req(t_, torch.bfloat16, "gemm_fp8_grouped_qkv output")
-        assert t_.is_contiguous()
-    _req(rope, torch.float32, "gemm_fp8_grouped_qkv.rope")
-    S_out = qo.shape[1]
-    assert qo.shape == ko.shape == (H, S_out, 128) and vt.shape[:2] == (H, 128) and rope.is_contiguous()
-    assert rope.shape == (2, S_out, 128)
-    none = [None] * n
-    for t_ in list(norm_q or none) + list(norm_k or none):
-        if t_ is not None:
-            _req(t_, torch.bfloat16, "gemm_fp8_grouped_qkv norm weight")
-            assert t_.is_contiguous() and t_.numel() == 128
-    VP, INT = C.c_void_p * n, C.c_int * n
-    qargs = (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
-             VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
-             ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+    qargs = _qkv_tail_args("gemm_fp8_grouped_qkv", n, is_qkv, norm_q, norm_k, row0, H, eps, rope, qo, ko, vt)
     if lora:
         largs = _fp8_grouped_lora_args("gemm_fp8_grouped_qkv", codes_list, w_list, lora_t_list, lora_B_list)
         _l.check(_l.load().apexmi_gemm_fp8_grouped_qkv_lora(*args, *qargs, *largs, _stream()), "gemm_fp8_grouped_qkv_lora")
@@ -1365,7 +1364,7 @@ def gemm_fp8_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list, e
 
 def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, gate_list, residual_list, fused=None,
                         out_mx_list=None):
-    """ctypes arrays of a grouped fp4 launch after the per-problem checks (`_check_mxfp4_pair`, `_epilogue_operands`); `fused[i]`:
+    """ctypes arrays of a grouped fp4 launch after the per-problem checks (`_check_mx_codes`, `_epilogue_operands`); `fused[i]`:
     problem i writes no `out`.  Every refusal raises ApexMIError with a reason before the library is asked; a float `out` is left
     to the entry point, which rejects it with its own message.  `out_mx_list` (one pair or None per problem): the arrays of the
     _mx entry points, with the four MX arrays behind ldc; a problem with a pair writes no `out`."""
@@ -1404,9 +1403,9 @@ def _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_lis
         at = f"{who} (problem {i})"
         if not isinstance(q, torch.Tensor) or q.dim() != 2:
             raise _l.ApexMIError(f"{at}: null operand: `codes` must be a uint8 [M, K / 2] tensor, got {type(q).__name__}")
-        _check_mxfp4_pair(at, q, s, q.shape[0], K)
+        _check_mx_codes(_MXFP4, at, q, s, q.shape[0], K)
         if mx[i] is not None:
-            mx[i] = _mxfp4_out_mx(at, mx[i], q.shape[0], w.shape[0], e)
+            mx[i] = _mx_out_mx(_MXFP4, at, mx[i], q.shape[0], w.shape[0], e)
         flags.append(_epilogue_operands(at, q.shape[0], w.shape[0], q.device, b, o, e, g, r, fused=bool(f), told=True)[1])
     VP, I64, INT = C.c_void_p * n, C.c_int64 * n, C.c_int * n
     mx_args = ()
@@ -1452,35 +1451,13 @@ def gemm_mxfp4_grouped_qkv(codes_list, scales_list, w_list, bias_list, out_list,
     transposed [H, 128, Skp]; bit-identical to gemm_mxfp4_grouped + qkv_prepare on the same codes (columns >= S_out of `vt` are not
     written).  out_list[i] of a fused problem is ignored (may be None).  Any row count and head count.  `out_mx_list`: as
     `gemm_mxfp4_grouped`, for the problems that are not fused q/k/v (a fused problem with a pair raises)."""
-    import ctypes as C
     who = "gemm_mxfp4_grouped_qkv"
     n = len(codes_list)
     if len(is_qkv) != n or len(row0) != n:
         raise _l.ApexMIError(f"{who}: is_qkv and row0 take one entry per problem")
     args = _mxfp4_grouped_args(who, codes_list, scales_list, w_list, bias_list, out_list, epilogue, None, None,
                                fused=[1 if f else 0 for f in is_qkv], out_mx_list=out_mx_list)
-    for name, t_ in (("qo", qo), ("ko", ko), ("vt", vt)):
-        if not isinstance(t_, torch.Tensor):
-            raise _l.ApexMIError(f"{who}: null q/k/v output `{name}`")
-        _req(t_, torch.bfloat16, f"{who} output {name}")
-    if not isinstance(rope, torch.Tensor):
-        raise _l.ApexMIError(f"{who}: null rope table")
-    _req(rope, torch.float32, f"{who}.rope")
-    S_out = qo.shape[1]
-    if not (qo.is_contiguous() and ko.is_contiguous() and vt.is_contiguous() and rope.is_contiguous()
-            and tuple(qo.shape) == tuple(ko.shape) == (H, S_out, 128) and vt.dim() == 3 and tuple(vt.shape[:2]) == (H, 128)
-            and tuple(rope.shape) == (2, S_out, 128)):
-        raise _l.ApexMIError(f"{who}: expected contiguous qo / ko [{H}, S_out, 128], vt [{H}, 128, Skp] and rope [2, S_out, 128], got "
-                             f"{tuple(qo.shape)}, {tuple(ko.shape)}, {tuple(vt.shape)}, {tuple(rope.shape)}")
-    none = [None] * n
-    for t_ in list(norm_q or none) + list(norm_k or none):
-        if t_ is not None:
-            _req(t_, torch.bfloat16, f"{who} norm weight")
-            assert t_.is_contiguous() and t_.numel() == 128
-    VP, INT = C.c_void_p * n, C.c_int * n
-    qargs = (INT(*[1 if f else 0 for f in is_qkv]), VP(*[_ptr(t_) for t_ in (norm_q or none)]),
-             VP(*[_ptr(t_) for t_ in (norm_k or none)]), INT(*[int(r) for r in row0]), int(H), float(eps), rope.data_ptr(), qo.data_ptr(),
-             ko.data_ptr(), vt.data_ptr(), S_out, vt.shape[2])
+    qargs = _qkv_tail_args(who, n, is_qkv, norm_q, norm_k, row0, H, eps, rope, qo, ko, vt, told=True)
     if out_mx_list is not None:
         _l.check(_l.load().apexmi_gemm_mxfp4_grouped_qkv_mx(*args, *qargs, _stream()), who + "_mx")
         return
@@ -1531,29 +1508,28 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None,
     (`set_fp6_compute`), `quant_blocks_mxfp6` + `gemm_mxfp6` and `mxfp6_route`.  A weight carries at most one of the two slots
     (the models' switches see to it); `gemm_grouped` routes neither."""
     _req_act(a, "gemm.a")
-    if getattr(w, "_fp4", None) is not None and mxfp4_route(a, w, out, epilogue):
-        if quantised is not None or out_mx is not None:
-            raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP4 route (the weight "
-                                 "carries an Mxfp4Weight): e4m3 codes are not fp4 operands")
-        if quantised_mxfp4 is not None:
-            qa, sa = quantised_mxfp4
-            _check_mxfp4_pair("gemm.quantised_mxfp4", qa, sa, a.shape[0], a.shape[1])
-        else:
-            qa, sa = _act_scratch_mxfp4(a.device, a.shape[0], a.shape[1])
-            quant_blocks_mxfp4(a, out=qa, scale_out=sa)
-        if out_mxfp4 is not None:
-            return gemm_mxfp4(qa, sa, w._fp4, bias, epilogue=epilogue, out_mx=out_mxfp4)
-        return gemm_mxfp4(qa, sa, w._fp4, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
-    if quantised_mxfp4 is not None or out_mxfp4 is not None:
+    fmt = None
+    for slot, f in _MX_SLOTS:
+        if getattr(w, slot, None) is not None and _mx_route(f, a, w, out, epilogue):
+            fmt = f
+            break
+    if (quantised_mxfp4 is not None or out_mxfp4 is not None) and fmt is not _MXFP4:
         raise _l.ApexMIError("gemm: `quantised_mxfp4` / `out_mxfp4` were passed but this call does not take the MXFP4 route "
                              "(mxfp4_route is False): decide with mxfp4_norm_quant_route / mxfp4_mx_route first")
-    if getattr(w, "_fp6", None) is not None and mxfp6_route(a, w, out, epilogue):
+    if fmt is not None:
         if quantised is not None or out_mx is not None:
-            raise _l.ApexMIError("gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the MXFP6 route (the weight "
-                                 "carries an Mxfp6Weight): e4m3 codes are not fp6 operands")
-        qa, sa = _act_scratch_mxfp6(a.device, a.shape[0], a.shape[1])
-        quant_blocks_mxfp6(a, out=qa, scale_out=sa)
-        return gemm_mxfp6(qa, sa, w._fp6, bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
+            raise _l.ApexMIError(f"gemm: `quantised` / `out_mx` belong to the fp8 route, and this call takes the {fmt.name} route (the "
+                                 f"weight carries an {fmt.record}): e4m3 codes are not {fmt.mode} operands")
+        public = globals()      # the wrappers by their public names, as a caller (or a test that counts calls) sees them
+        if quantised_mxfp4 is not None:
+            qa, sa = quantised_mxfp4
+            _check_mx_codes(fmt, "gemm.quantised_mxfp4", qa, sa, a.shape[0], a.shape[1])
+        else:
+            qa, sa = _act_scratch_mx(fmt, a.device, a.shape[0], a.shape[1])
+            public[fmt.quant](a, out=qa, scale_out=sa)
+        if out_mxfp4 is not None:
+            return public[fmt.gemm](qa, sa, getattr(w, fmt.slot), bias, epilogue=epilogue, out_mx=out_mxfp4)
+        return public[fmt.gemm](qa, sa, getattr(w, fmt.slot), bias, out=out, epilogue=epilogue, gate=gate, residual=residual)
     f8 = _fp8_of(w)
     if f8 is not None and getattr(f8, "compute", "bf16") == "fp8" and fp8_compute_route(a, f8, out, epilogue):
         qa, sa = _fp8_acts(a, quantised)

@@ -1,7 +1,8 @@
 """The one route rule and the one grouped-list rule behind the opt-in low-precision GEMM routes (ops._block_gemm_route,
-ops._grouped_problems), driven over a table and compared with a plain restatement written here; and that the three public
-predicates built on the rule — ops.fp8_compute_route, the problem rule of ops.fp8_lora_route and ops.mxfp4_route — differ from each
-other in exactly two places: the K multiple (128 against 256) and the row-stride bound (2^22 against none).  No GPU: meta tensors."""
+ops._grouped_problems), driven over a table and compared with a plain restatement written here; and that the public predicates
+built on the rule — ops.fp8_compute_route, the problem rule of ops.fp8_lora_route, ops.mxfp4_route and ops.mxfp6_route — differ from
+each other in exactly two places, three ways: the K multiple and the row-stride bound are (128, 2^22) for fp8, (256, none) for fp4
+and (128, none) for fp6.  No GPU: meta tensors."""
 import itertools
 
 import torch
@@ -77,7 +78,7 @@ def test_the_rule_against_its_restatement():
 
 
 def _records(N, K):
-    """an e4m3 record without factors, one with factors, and an fp4 record beside a bf16 weight, all [N, K] and switched on"""
+    """an e4m3 record without factors, one with factors, and an fp4 and an fp6 record beside a bf16 weight, all [N, K] and switched on"""
     from apex_studio_amd import ops
     plain = ops.Fp8Weight(torch.zeros(N, K).to(F8), torch.ones(N))
     plain.compute = "fp8"
@@ -86,39 +87,58 @@ def _records(N, K):
     lora.parts = [("lin", 0, N)]
     lora.set_lora([("lin", torch.zeros(4, K), torch.zeros(N, 4), 1.0)])
     fp4 = ops.Mxfp4Weight(torch.zeros(N, K // 2, dtype=torch.uint8), torch.full((N, K // 32), 127, dtype=torch.uint8))
-    return plain, lora, fp4
+    fp6 = ops.Mxfp6Weight(torch.zeros(N, K // 4 * 3, dtype=torch.uint8), torch.full((N, K // 32), 127, dtype=torch.uint8))
+    return plain, lora, fp4, fp6
 
 
 def test_the_three_public_predicates_differ_only_in_k_multiple_and_stride_bound():
     import apex_studio_amd  # noqa: F401
     from apex_studio_amd import ops
     recs = {}
-    differ = {"k": 0, "stride": 0}
+    differ = {"k": 0, "stride": 0, "6 from 8": 0, "6 from 4": 0}
     for label, a, (N, Kw), out, epi in _table():
         if (N, Kw) not in recs:
             recs[(N, Kw)] = _records(N, Kw)
-        plain, lora, fp4 = recs[(N, Kw)]
+        plain, lora, fp4, fp6 = recs[(N, Kw)]
         r8 = ops.fp8_compute_route(a, plain, out, epi)
         rl = ops._fp8_lora_problem_route(a, lora, out, epi)
         r4 = ops.mxfp4_route(a, fp4, out, epi)
+        r6 = ops.mxfp6_route(a, fp6, out, epi)
         # each is its record test plus the one rule with its own two constants
         assert r8 is _want(a, (N, Kw), out, epi, 128, BOUND), label
         assert rl is r8, label
         assert r4 is _want(a, (N, Kw), out, epi, 256, None), label
+        assert r6 is _want(a, (N, Kw), out, epi, 128, None), label
         if r8 != r4:
             k_only_128 = Kw % 128 == 0 and Kw % 256 != 0
             past = a.dim() == 2 and a.stride(0) > BOUND
             assert (r8 and k_only_128 and not past) or (r4 and past and not k_only_128), label
             differ["k" if r8 else "stride"] += 1
-    assert differ["k"] > 0 and differ["stride"] > 0, differ
+        # fp6 shares its K multiple with fp8 and its missing bound with fp4: it parts from fp8 only past the bound, and from fp4
+        # only at a K that is a multiple of 128 alone
+        if r6 != r8:
+            assert r6 and a.dim() == 2 and a.stride(0) > BOUND, label
+            differ["6 from 8"] += 1
+        if r6 != r4:
+            assert r6 and Kw % 128 == 0 and Kw % 256 != 0, label
+            differ["6 from 4"] += 1
+    assert all(n > 0 for n in differ.values()), differ
     # the record tests themselves: a record of the wrong kind, or switched off, never routes
     a = _meta((4, 256), (256, 1), BF)
-    plain, lora, fp4 = _records(32, 256)
+    plain, lora, fp4, fp6 = _records(32, 256)
     assert ops.fp8_compute_route(a, plain) and ops._fp8_lora_problem_route(a, lora, None, "bias") and ops.mxfp4_route(a, fp4)
+    assert ops.mxfp6_route(a, fp6)
     assert not ops.fp8_compute_route(a, lora) and not ops._fp8_lora_problem_route(a, plain, None, "bias")
     assert not ops.fp8_compute_route(a, fp4) and not ops.mxfp4_route(a, plain)
-    plain.compute, lora.lora_compute, fp4.compute = "bf16", "bf16", "bf16"
+    assert not ops.mxfp6_route(a, fp4) and not ops.mxfp4_route(a, fp6) and not ops.mxfp6_route(a, plain) and not ops.fp8_compute_route(a, fp6)
+    w = torch.empty(32, 256, dtype=BF, device="meta")
+    w._fp6, w._fp4 = fp4, fp6                      # each record in the other format's slot
+    assert not ops.mxfp6_route(a, w) and not ops.mxfp4_route(a, w)
+    w._fp6, w._fp4 = fp6, fp4
+    assert ops.mxfp6_route(a, w) and ops.mxfp4_route(a, w)
+    plain.compute, lora.lora_compute, fp4.compute, fp6.compute = "bf16", "bf16", "bf16", "bf16"
     assert not ops.fp8_compute_route(a, plain) and not ops._fp8_lora_problem_route(a, lora, None, "bias") and not ops.mxfp4_route(a, fp4)
+    assert not ops.mxfp6_route(a, fp6) and not ops.mxfp6_route(a, w) and not ops.mxfp4_route(a, w)
 
 
 def _want_problems(a_list, w_list, out_list, epilogues):
@@ -140,7 +160,7 @@ def _want_problems(a_list, w_list, out_list, epilogues):
 def test_the_grouped_list_rule_and_both_grouped_predicates():
     import apex_studio_amd  # noqa: F401
     from apex_studio_amd import ops
-    plain, lora, _ = _records(32, 256)
+    plain, lora, _, _ = _records(32, 256)
     a = _meta((4, 256), (256, 1), BF)
     other_k = _meta((4, 128), (128, 1), BF)
     o = _meta((4, 32), (32, 1), BF)

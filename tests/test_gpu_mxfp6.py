@@ -179,6 +179,56 @@ def test_route_through_ops_gemm_is_the_two_launches():
     assert torch.equal(ops.gemm(a, w), plain), "without the record the call is the earlier one"
 
 
+@pytest.mark.parametrize("mode", ["fp4", "fp6"])
+def test_the_shared_front_end_routes_either_format_as_its_explicit_pair(mode):
+    """`ops.gemm` on a weight carrying the format's record against `quant_blocks_mxfpN` + `gemm_mxfpN` with fresh buffers, bit for
+    bit, under bias / gelu / gate_res at M = 130 (a tile and two edge rows), N = 144 (a tile and one 16-column group), K = 512 (two
+    fp4 K-tiles, four fp6 K-tiles); again after an M = 64 call on the same stream has taken smaller views of the per-stream
+    activation scratch; and with a call of the OTHER format in between, whose scratch is a store of its own."""
+    ops = _ops()
+    M, N, K = 130, 144, 512
+    kinds = {"fp4": (ops.Mxfp4Weight, "_fp4", ops.quant_blocks_mxfp4, ops.gemm_mxfp4, ops.mxfp4_route),
+             "fp6": (ops.Mxfp6Weight, "_fp6", ops.quant_blocks_mxfp6, ops.gemm_mxfp6, ops.mxfp6_route)}
+    a, wdata = R.random_rows(M, K).to(DEV), R.random_rows(N, K, seed=12)
+    bias, gate = R.random_rows(1, N, seed=13).view(N).to(DEV), R.random_rows(1, N, seed=14).view(N).float().to(DEV)
+    res = R.random_rows(M, N, seed=15).to(DEV)
+    weights = {}
+    for m, (cls, slot, _, _, route) in kinds.items():
+        w = wdata.to(DEV)
+        setattr(w, slot, cls.from_bf16(w))
+        assert route(a, w) and route(a[:64], w)
+        weights[m] = w
+    epilogues = {"bias": {}, "gelu": {}, "gate_res": {"gate": gate}}
+
+    def explicit(m, rows, epi, extra):
+        _, slot, quant, gemm, _ = kinds[m]
+        qa, sa = quant(a[:rows])
+        kw = dict(extra, residual=res[:rows]) if epi == "gate_res" else extra
+        return gemm(qa, sa, getattr(weights[m], slot), bias, epilogue=epi, **kw)
+
+    def routed(m, rows, epi, extra):
+        kw = dict(extra, residual=res[:rows]) if epi == "gate_res" else extra
+        return ops.gemm(a[:rows], weights[m], bias, epilogue=epi, **kw)
+
+    other = "fp6" if mode == "fp4" else "fp4"
+    for epi, extra in epilogues.items():
+        want = {(m, rows): explicit(m, rows, epi, extra) for m in kinds for rows in (M, 64)}
+        assert not torch.equal(want[mode, M], want[other, M]), "the two formats round differently: the comparison can tell them apart"
+        assert torch.equal(routed(mode, M, epi, extra), want[mode, M]), (epi, "the route is its explicit pair")
+        assert torch.equal(routed(mode, 64, epi, extra), want[mode, 64]), (epi, "a smaller view of the same scratch")
+        assert torch.equal(routed(mode, M, epi, extra), want[mode, M]), (epi, "the larger view again")
+        first, second, third = routed(mode, M, epi, extra), routed(other, M, epi, extra), routed(mode, M, epi, extra)
+        assert torch.equal(first, want[mode, M]) and torch.equal(second, want[other, M]) and torch.equal(third, want[mode, M]), \
+            (epi, "back to back on one stream, each format still matches its own pair")
+    # the stores themselves: the two formats' views of this stream's scratch do not overlap
+    spans = []
+    for fmt in ops._MX_FORMATS:
+        for t in ops._act_scratch_mx(fmt, a.device, M, K):
+            spans.append((t.data_ptr(), t.data_ptr() + t.numel()))
+    spans.sort()
+    assert len(spans) == 4 and all(hi <= lo for (_, hi), (lo, _) in zip(spans, spans[1:])), spans
+
+
 # ------------------------------------------------------------------------------------------------------------- 5. like for like
 @pytest.mark.parametrize("case", [(300, 272, 1280), (129, 528, 512)], ids=["300-272-1280", "129-528-512"])
 def test_random_operands_like_for_like_with_the_bf16_kernel(case):

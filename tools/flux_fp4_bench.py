@@ -77,7 +77,7 @@ def launch_classes(g):
     out = {}
 
     def quant(src):
-        qa, sa = ops._act_scratch_mxfp4(src.device, src.shape[0], src.shape[1])
+        qa, sa = ops._act_scratch_mx(ops._MXFP4, src.device, src.shape[0], src.shape[1])
         return ops.quant_blocks_mxfp4(src, out=qa, scale_out=sa)
 
     def three(flops, bf16, fp4_gemm, src):
